@@ -29,7 +29,7 @@ def test_bench_with_several_ranks_on_one_device(world):
     env = dict(os.environ, FX_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "6", "--warmup", "1", "--batch", "48", "--contexts", "2", "--repeats", "2",
-           "--check", "2", "--no-extras", "--no-cpu-baseline"]
+           "--check", "2", "--full", "--no-extras", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric')]

@@ -13,7 +13,7 @@ lib = sys.argv[1]
 capi.LIB_PATH = os.path.join(os.path.dirname(capi.LIB_PATH), lib)
 import bench  # noqa: E402
 
-sys.argv = ["bench.py", "--no-extras", "--no-cpu-baseline", "--check", "0", "--steps", "60"] + sys.argv[2:]
+sys.argv = ["bench.py", "--full", "--repeats", "0", "--no-extras", "--no-cpu-baseline", "--check", "0", "--steps", "60"] + sys.argv[2:]
 buf = io.StringIO()
 with contextlib.redirect_stdout(buf):
     bench.main()

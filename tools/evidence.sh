@@ -9,9 +9,9 @@ E=$R/gpurun_out/evidence_$TAG
 mkdir -p "$E"
 cd "$R"
 bash tools/kernel_info.sh > "$E/kernel_info.txt" 2>&1   # registers, spills, scratch, LDS and code size of every kernel of the product library
-python3 bench.py > "$E/bench_default_run.json" 2> "$E/bench_default_run.err"
-FX_BENCH_FORCE_DIST=1 python3 bench.py --no-extras --no-cpu-baseline > "$E/force_dist.json" 2> "$E/force_dist.err"
-python3 bench.py --contexts 1 --no-extras --no-cpu-baseline > "$E/bench_one_at_a_time.json" 2> /dev/null
+python3 bench.py --full --repeats 0 > "$E/bench_default_run.json" 2> "$E/bench_default_run.err"
+FX_BENCH_FORCE_DIST=1 python3 bench.py --full --repeats 0 --no-extras --no-cpu-baseline > "$E/force_dist.json" 2> "$E/force_dist.err"
+python3 bench.py --full --repeats 0 --contexts 1 --no-extras --no-cpu-baseline > "$E/bench_one_at_a_time.json" 2> /dev/null
 feature_extraction_amd/bin/fx_multi_cli --batch 1024 --steps 40 --inflight 1 > "$E/fx_multi_1gpu.log" 2>&1
 feature_extraction_amd/bin/fx_multi_cli --batch 1024 --steps 40 --inflight 2 >> "$E/fx_multi_1gpu.log" 2>&1
 feature_extraction_amd/bin/fx_multi_cli --batch 1024 --steps 40 --inflight 4 >> "$E/fx_multi_1gpu.log" 2>&1

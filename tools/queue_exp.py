@@ -24,7 +24,7 @@ if mode == "big_alloc":
     x = torch.empty(40 << 30, dtype=torch.uint8, device=dev); del x; torch.cuda.empty_cache()
 if mode.startswith("main"):
     import contextlib, io
-    sys.argv = ["bench.py", "--no-cpu-baseline", "--steps", "20", "--repeats", "2"] + (["--no-extras"] if mode == "main_noextras" else [])
+    sys.argv = ["bench.py", "--full", "--no-cpu-baseline", "--steps", "20", "--repeats", "2"] + (["--no-extras"] if mode == "main_noextras" else [])
     if mode == "main_noc5":
         del bench.OTHER_CONFIGS[name]
     if mode == "main_only_c5":
