@@ -13,11 +13,13 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libfx_hip.so")
 
 FX_DESC_BINS = 1980
+FX_DESC_RF = 9
 FX_DESC_FLOATS = 1989
 FX_FEATURE_RECORD_BYTES = 7984
 FX_OK = 0
 FX_ERR_NO_DEVICE = 2
 FX_IN_DEVICE, FX_OUT_HOST, FX_OUT_DEBUG, FX_OUT_CLOUDS = 1, 2, 4, 8
+FX_OUT_DESC_CSR = 0x10  # with FX_OUT_HOST: the descriptor rows come back as the context's CSR block (fx_get_descriptors_csr)
 FX_FLAG_RING_OVERFLOW, FX_FLAG_CAND_OVERFLOW, FX_FLAG_KP_OVERFLOW, FX_FLAG_NBR_OVERFLOW = 0x1, 0x2, 0x4, 0x8
 FX_FLAG_NAMES = {0x1: "RING_OVERFLOW", 0x2: "CAND_OVERFLOW", 0x4: "KP_OVERFLOW", 0x8: "NBR_OVERFLOW",
                  0x10: "TOTAL_KP_OVERFLOW", 0x20: "KPC_OVERFLOW"}
@@ -84,6 +86,11 @@ class FxPc2Layout(C.Structure):
                 ("point_step", "offset_x", "offset_y", "offset_z", "offset_intensity", "is_bigendian")]
 
 
+class FxDescriptorCsrView(C.Structure):
+    _fields_ = [("rows", C.c_uint32), ("nnz", C.c_uint32), ("h_row_ptr", _U32P), ("h_col", _U32P), ("h_val", _F32P),
+                ("d_row_ptr", C.c_void_p), ("d_col", C.c_void_p), ("d_val", C.c_void_p)]
+
+
 class FxTimings(C.Structure):
     _fields_ = [("ms", C.c_float * FX_N_STAGES), ("total_ms", C.c_float), ("k_prep_exec_ms", C.c_float)]
 
@@ -104,6 +111,7 @@ FX_HEADER_VERSION = (0 << 16) | 7  # the include/fx.h these ctypes structures mi
 EXPORTS = ("fx_version", "fx_check_abi", "fx_status_str", "fx_last_error", "fx_params_default", "fx_params_launch",
            "fx_limits_default", "fx_limits_sparse", "fx_create", "fx_destroy", "fx_set_stream", "fx_get_stream", "fx_set_graph_batch", "fx_set_batches_in_flight", "fx_set_profiling", "fx_set_profiling_stages", "fx_get_timings",
            "fx_get_stage_bytes", "fx_get_limits", "fx_process_batch", "fx_synchronize", "fx_pack_features", "fx_pack_keypoint_records", "fx_keypoint_block_bytes", "fx_pack_keypoint_block",
+           "fx_descriptor_csr_bytes", "fx_pack_descriptors_csr", "fx_get_descriptors_csr", "fx_set_descriptor_csr_capacity",
            "fx_rotation_from_roll_pitch", "fx_sc3d_tables", "fx_sc3d_xaxis", "fx_synth_cfg_vlp16",
            "fx_synth_scan", "fx_unpack_pointcloud2", "fx_pack_pointxyzi")
 # the header's FX_TEST_HOOKS section: exported by lib/libfx_hip_test.so only
@@ -200,6 +208,11 @@ def load():
     lib.fx_keypoint_block_bytes.argtypes = [C.c_uint32, C.c_uint32]
     lib.fx_keypoint_block_bytes.restype = C.c_size_t
     lib.fx_pack_keypoint_block.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+    lib.fx_descriptor_csr_bytes.argtypes = [C.c_uint32, C.c_uint32]
+    lib.fx_descriptor_csr_bytes.restype = C.c_size_t
+    lib.fx_pack_descriptors_csr.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+    lib.fx_get_descriptors_csr.argtypes = [C.c_void_p, C.POINTER(FxDescriptorCsrView)]
+    lib.fx_set_descriptor_csr_capacity.argtypes = [C.c_void_p, C.c_uint32]
     lib.fx_rotation_from_roll_pitch.argtypes = [C.c_double, C.c_double, _F32P]
     lib.fx_rotation_from_roll_pitch.restype = None
     lib.fx_sc3d_tables.argtypes = [C.c_double, _F32P, _F32P, _F32P, _F32P]
@@ -283,6 +296,51 @@ def synth_scan(cfg):
     return out
 
 
+# ---- descriptors as compressed rows (CSR; include/fx.h fx_descriptor_csr_bytes)
+def csr_layout(max_rows, capacity):
+    """Byte offsets (row_ptr, col, val, end) of the sections of a CSR block: header 16 B, row_ptr u32[max_rows + 1], col u32[capacity],
+    val f32[capacity], each rounded up to 16 bytes."""
+    rp = 16
+    col = rp + 4 * ((max_rows + 1 + 3) // 4 * 4)
+    val = col + 4 * ((capacity + 3) // 4 * 4)
+    return rp, col, val, val + 4 * ((capacity + 3) // 4 * 4)
+
+
+def csr_from_dense(rows):
+    """The storage rule, stated in numpy: every word of the [n, 1989] float32 rows whose bit pattern is non-zero (-0.0 and NaN
+    included), row by row, columns increasing.  Returns (row_ptr u32[n + 1], col u32[nnz], val f32[nnz])."""
+    bits = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, FX_DESC_FLOATS).view(np.uint32)
+    nz = bits != 0
+    row_ptr = np.zeros(len(bits) + 1, np.uint32)
+    np.cumsum(nz.sum(axis=1), out=row_ptr[1:])
+    r, c = np.nonzero(nz)
+    return row_ptr, c.astype(np.uint32), bits[r, c].view(np.float32)
+
+
+def dense_from_csr(row_ptr, col, val, n_rows=None):
+    """[n, 1989] float32 rows from (row_ptr, col, val): zeros everywhere else, the stored words bit for bit.  n_rows (default
+    len(row_ptr) - 1) reads row_ptr[:n_rows + 1]; col / val are indexed from row_ptr[0]."""
+    row_ptr = np.asarray(row_ptr).astype(np.int64)
+    n = len(row_ptr) - 1 if n_rows is None else int(n_rows)
+    out = np.zeros((n, FX_DESC_FLOATS), np.uint32)
+    lo, hi = int(row_ptr[0]), int(row_ptr[n])
+    r = np.repeat(np.arange(n), np.diff(row_ptr[:n + 1]))
+    out[r, np.asarray(col)[lo:hi].astype(np.int64)] = np.ascontiguousarray(np.asarray(val)[lo:hi], dtype=np.float32).view(np.uint32)
+    return out.view(np.float32)
+
+
+def csr_parse(block, max_rows, capacity):
+    """A CSR block (bytes / uint8 array, as fx_pack_descriptors_csr writes it) as a dict: the header words and the stored
+    row_ptr[:min(rows, max_rows) + 1], col[:nnz_stored], val[:nnz_stored]."""
+    b = np.frombuffer(bytes(block), np.uint8) if not isinstance(block, np.ndarray) else np.ascontiguousarray(block).view(np.uint8)
+    rp, col, val, _ = csr_layout(max_rows, capacity)
+    rows, nnz_stored, nnz_needed, rows_stored = (int(x) for x in b[:16].view(np.uint32))
+    n = min(rows, max_rows)
+    return {"rows": rows, "nnz_stored": nnz_stored, "nnz_needed": nnz_needed, "rows_stored": rows_stored,
+            "row_ptr": b[rp:rp + 4 * (n + 1)].view(np.uint32).copy(), "row_ptr_all": b[rp:rp + 4 * (max_rows + 1)].view(np.uint32).copy(),
+            "col": b[col:col + 4 * nnz_stored].view(np.uint32).copy(), "val": b[val:val + 4 * nnz_stored].view(np.float32).copy()}
+
+
 def _np(ptr, shape, dtype):
     n = int(np.prod(shape))
     if n == 0 or not ptr:
@@ -295,6 +353,7 @@ class Context:
 
     def __init__(self, p, lim, device=0):
         self.lib = load()
+        self.device = device
         self.params, self.limits = p, lim
         self.handle = C.c_void_p()
         check(self.lib.fx_create(C.byref(p), C.byref(lim), device, C.byref(self.handle)))
@@ -364,6 +423,58 @@ class Context:
     def synchronize(self):
         check(self.lib.fx_synchronize(self.handle))
 
+    def set_descriptor_csr_capacity(self, entries):
+        """Initial entries of the context's CSR block (0: max_total_keypoints * 128); it grows when a batch needs more."""
+        check(self.lib.fx_set_descriptor_csr_capacity(self.handle, int(entries)))
+
+    def pack_descriptors_csr(self, dst_device_ptr, max_rows, capacity):
+        """fx_pack_descriptors_csr: the last batch's descriptor rows as a CSR block at dst (enqueued on the context's stream)."""
+        check(self.lib.fx_pack_descriptors_csr(self.handle, C.c_void_p(dst_device_ptr), int(max_rows), int(capacity)))
+
+    def descriptors_csr_host(self):
+        """The last FX_OUT_DESC_CSR batch's rows (fx_get_descriptors_csr) as numpy copies: (row_ptr, col, val)."""
+        v = FxDescriptorCsrView()
+        check(self.lib.fx_get_descriptors_csr(self.handle, C.byref(v)))
+        return (_np(v.h_row_ptr, (v.rows + 1,), np.uint32), _np(v.h_col, (v.nnz,), np.uint32), _np(v.h_val, (v.nnz,), np.float32))
+
+    def descriptors_csr(self, buf=None, max_rows=None, capacity=None):
+        """The last batch's descriptor rows packed on the GPU (fx_pack_descriptors_csr) into `buf` — a device torch.uint8 tensor of
+        fx_descriptor_csr_bytes(max_rows, capacity) bytes, allocated here when None — and returned as a torch.sparse_csr_tensor of
+        shape (min(rows, max_rows), 1989) whose int32 row_ptr / col and float32 values are views of `buf`, plus the header
+        {rows, nnz_stored, nnz_needed, rows_stored}.  max_rows defaults to max_total_keypoints.  Without `buf` and `capacity`
+        the block starts at 128 entries a row and is allocated again at nnz_needed when the rows need more (nothing is cut);
+        a block the caller sizes may come back cut (rows_stored < rows: the leading rows_stored rows only).
+        Stream-correct: the pack runs on the context's stream after the work the caller's current stream has queued, and the
+        caller's current stream waits for it."""
+        import torch
+        max_rows = self.limits.max_total_keypoints if max_rows is None else int(max_rows)
+        grow = buf is None and capacity is None
+        capacity = max_rows * 128 if capacity is None else int(capacity)
+        dev = torch.device("cuda", self.device)
+        cur = torch.cuda.current_stream(dev)
+        ext = torch.cuda.ExternalStream(self.stream_ptr(), device=dev)
+        while True:
+            nbytes = int(self.lib.fx_descriptor_csr_bytes(max_rows, capacity))
+            if buf is None:
+                buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            elif buf.dtype != torch.uint8 or buf.device != dev or buf.numel() < nbytes or not buf.is_contiguous() or buf.data_ptr() % 16:
+                raise ValueError(f"buf must be a contiguous, 16-byte aligned torch.uint8 tensor of >= {nbytes} bytes on {dev}")
+            ext.wait_stream(cur)  # (the buffer's allocation / the caller's last use of it)
+            self.pack_descriptors_csr(buf.data_ptr(), max_rows, capacity)
+            # (the caller's stream waits for the pack, so the buffer's later reuse on it comes after; no record_stream: the
+            #  allocator would record events on the context's stream when the tensor dies, after fx_destroy perhaps)
+            cur.wait_stream(ext)
+            h = buf[:16].view(torch.int32).cpu().tolist()
+            if not (grow and h[3] < min(h[0], max_rows)):
+                break
+            buf, capacity = None, h[2]  # (nnz_needed: every row; the dense rows are intact until the next batch)
+        hdr = {"rows": h[0], "nnz_stored": h[1], "nnz_needed": h[2], "rows_stored": h[3]}
+        rp, col, val, _ = csr_layout(max_rows, capacity)
+        n, nnz = min(h[0], max_rows), h[1]
+        t = torch.sparse_csr_tensor(buf[rp:rp + 4 * (n + 1)].view(torch.int32), buf[col:col + 4 * nnz].view(torch.int32),
+                                    buf[val:val + 4 * nnz].view(torch.float32), size=(n, FX_DESC_FLOATS))
+        return t, hdr
+
     def make_descs(self, ptrs, counts, stride_bytes=16, roll=0.0, pitch=0.0):
         n = len(ptrs)
         arr = (FxScanDesc * n)()
@@ -380,14 +491,29 @@ class Context:
         check(self.lib.fx_process_batch(self.handle, descs, batch, flags, C.byref(view)))
         return view
 
-    def process_host(self, scans, roll=0.0, pitch=0.0, debug=True):
-        """scans: list of [N,4] (or [N,8]) float32 arrays on the host.  Returns a list of dicts."""
+    def process_host(self, scans, roll=0.0, pitch=0.0, debug=True, descriptors="dense"):
+        """scans: list of [N,4] (or [N,8]) float32 arrays on the host.  Returns a list of dicts.  descriptors="csr": the rows come
+        back through FX_OUT_DESC_CSR and every dict carries desc_csr = (row_ptr, col, val) of its own rows (row_ptr from 0)
+        instead of the dense "descriptors"."""
+        if descriptors not in ("dense", "csr"):
+            raise ValueError(f"descriptors must be 'dense' or 'csr', not {descriptors!r}")
         scans = [np.ascontiguousarray(s, dtype=np.float32) for s in scans]
         stride = scans[0].shape[1] * 4 if scans else 16
         descs = self.make_descs([s.ctypes.data for s in scans], [s.shape[0] for s in scans], stride, roll, pitch)
-        flags = FX_OUT_HOST | FX_OUT_CLOUDS | (FX_OUT_DEBUG if debug else 0)
+        flags = FX_OUT_HOST | FX_OUT_CLOUDS | (FX_OUT_DEBUG if debug else 0) | (FX_OUT_DESC_CSR if descriptors == "csr" else 0)
         v = self.process_raw(descs, len(scans), flags)
-        return self.unpack(v, debug)
+        out = self.unpack(v, debug)
+        if descriptors == "csr":
+            rp, col, val = self.descriptors_csr_host()
+            off = _np(v.h_kp_offset, (v.batch + 1,), np.uint32)
+            for b, d in enumerate(out):
+                del d["descriptors"]
+                o0, o1 = min(int(off[b]), v.total_keypoints), min(int(off[b]) + d["n_keypoints"], v.total_keypoints)
+                if o1 >= len(rp):  # (estimate_descriptors = 0: no rows)
+                    o0 = o1 = 0
+                lo, hi = int(rp[o0]), int(rp[o1])
+                d["desc_csr"] = (rp[o0:o1 + 1] - rp[o0], col[lo:hi], val[lo:hi])
+        return out
 
     def unpack(self, v, debug=True):
         B = v.batch

@@ -75,6 +75,9 @@ size_t fxk_kp_block_bytes(uint32_t max_scans, uint32_t max_total);
 void fxk_pack_kp_block(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, void *dst, uint32_t max_scans, uint32_t max_total,
                        uint32_t grid);
 void fxk_rng_ord(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch);
+size_t fxk_csr_bytes(uint32_t max_rows, uint32_t cap);
+hipError_t fxk_pack_csr(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, void *dst, uint32_t max_rows, uint32_t cap,
+                        uint32_t grid, uint32_t full_rows);
 #ifdef FX_TEST_HOOKS
 void fxk_test_sort_replay(hipStream_t s, const uint32_t *sizes, uint32_t n_seq, uint32_t n, uint32_t *perm);
 void fxk_test_elevation(hipStream_t s, const float *xyz, uint32_t n, const double *tab, float *fast, uint8_t *ok, float *exact);
@@ -115,6 +118,8 @@ inline const char *test_hook(const char *name) {
 #endif
 }
 constexpr uint32_t kMergeCapSmall = 512, kListCap = 4096, kDenseMin = 1024;
+// default CSR block: 128 entries a row (1 KB: the dense pool's 7956 B / 8; the test scenes average 15 to 77 non-zero words)
+constexpr uint32_t kCsrRowEntries = 128;
 }  // namespace
 
 struct fx_ctx {
@@ -205,6 +210,15 @@ struct fx_ctx {
   int dense_force = -1;                    // test hook (FX_DENSE_SLOW): 1 always k_desc_mid's workgroups, 0 always the tier's own kernels
   uint32_t skip_mask = 0;      // experiment hook (FX_SKIP_EMPTY, test build): bit 0 no k_front_redo, bit 1 no dense tier — only for workloads that need neither; bits 2 / 3: no k_dense_finish / k_dense_density (measurement: results wrong)
   static constexpr uint32_t front_retry = 64;
+  // FX_OUT_DESC_CSR: the context's CSR block of descriptor rows (max_total_keypoints rows, csr_cap entries) and its pinned
+  // mirror, allocated at the first batch that asks for it and grown (never shrunk) when a batch needs more entries
+  uint8_t *d_csr = nullptr, *h_csr = nullptr;
+  uint32_t csr_cap = 0;          // entries of the allocated block
+  uint32_t csr_cap_want = 0;     // fx_set_descriptor_csr_capacity (0: max_total_keypoints * kCsrRowEntries)
+  bool csr_resize = false;       // fx_set_descriptor_csr_capacity after the block was allocated: reallocate at the next use
+  bool csr_valid = false;        // the last batch was FX_OUT_HOST | FX_OUT_DESC_CSR (fx_get_descriptors_csr)
+  uint32_t csr_rows = 0, csr_nnz = 0;
+  uint32_t csr_full_rows = 0;    // test hook (FX_CSR_FULL_ROWS): every row through the whole-row path
 };
 
 namespace {
@@ -235,6 +249,46 @@ fx_status host_alloc(fx_ctx *c, T **p, size_t count) {
     fx_status s_ = (expr);        \
     if (s_ != FX_OK) return s_;   \
   } while (0)
+
+// The CSR block's offsets and entry counts are u32: every row of the descriptor pool stored whole must fit
+bool csr_pool_fits(const fx_limits &L) { return (uint64_t)L.max_total_keypoints * FX_DESC_FLOATS <= 0xffffffffull; }
+size_t csr_col_offset(uint32_t max_rows) { return 16u + 4u * csr_rp_words(max_rows); }
+size_t csr_val_offset(uint32_t max_rows, uint32_t cap) { return csr_col_offset(max_rows) + 4u * csr_cap_words(cap); }
+// k_csr_count / k_csr_write: grid-stride, a wavefront a row, up to eight workgroups a CU
+fx_status enqueue_csr(fx_ctx *c, hipStream_t s, void *dst, uint32_t max_rows, uint32_t cap) {
+  const uint32_t rows_bound = std::min(c->lim.max_total_keypoints, 0xffffffffu - 3u);
+  const uint32_t grid = std::max(1u, std::min((rows_bound + 3u) / 4u, 8u * (uint32_t)c->n_cu));
+  FX_HIP(fxk_pack_csr(s, c->dp, c->buf, c->last_batch, dst, max_rows, cap, grid, c->csr_full_rows));
+  return FX_OK;
+}
+// The context's block with room for `cap` entries (max_total_keypoints rows).  An existing block is freed once the stream
+// is done with it: a reallocation happens at the first CSR batch, after fx_set_descriptor_csr_capacity, and when a batch
+// needs more entries than the block has.
+fx_status csr_reserve(fx_ctx *c, uint32_t cap) {
+  if (c->d_csr && c->csr_cap == cap) return FX_OK;
+  if (c->d_csr) {
+    FX_HIP(hipStreamSynchronize(c->stream));
+    FX_HIP(hipFree(c->d_csr));
+    FX_HIP(hipHostFree(c->h_csr));
+    c->d_csr = c->h_csr = nullptr;
+    c->csr_cap = 0;
+  }
+  const size_t bytes = fxk_csr_bytes(c->lim.max_total_keypoints, cap);
+  void *q = nullptr;
+  hipError_t e = hipMalloc(&q, bytes);
+  if (e != hipSuccess) return fail(FX_ERR_OOM, std::string("CSR block hipMalloc(") + std::to_string(bytes) + "): " + hipGetErrorString(e));
+  c->d_csr = (uint8_t *)q;
+  q = nullptr;
+  e = hipHostMalloc(&q, bytes, hipHostMallocDefault);
+  if (e != hipSuccess) {
+    (void)hipFree(c->d_csr);
+    c->d_csr = nullptr;
+    return fail(FX_ERR_OOM, std::string("CSR block hipHostMalloc(") + std::to_string(bytes) + "): " + hipGetErrorString(e));
+  }
+  c->h_csr = (uint8_t *)q;
+  c->csr_cap = cap;
+  return FX_OK;
+}
 
 }  // namespace
 
@@ -866,6 +920,7 @@ fx_status fx_create(const fx_params *params, const fx_limits *limits, int device
   if (const char *e = test_hook("FX_PREP_SLICES")) c->prep_slices = std::max(1, atoi(e));
   if (const char *e = test_hook("FX_MERGE_SLICES")) c->merge_slices = std::max(1, atoi(e));
   if (const char *e = test_hook("FX_GATHER_COUNTED")) c->gather_slices = std::max(1, atoi(e));
+  if (const char *e = test_hook("FX_CSR_FULL_ROWS")) c->csr_full_rows = atoi(e) != 0 ? 1u : 0u;
   if (c->front_ok) {
     hipError_t ce = fxk_configure_front();
     if (ce != hipSuccess) return bail(fail(FX_ERR_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(ce)));
@@ -885,6 +940,8 @@ void fx_destroy(fx_ctx *c) {
   for (void *p : c->dev_allocs) (void)hipFree(p);
   for (void *p : c->host_allocs) (void)hipHostFree(p);
   if (c->d_stage) (void)hipFree(c->d_stage);
+  if (c->d_csr) (void)hipFree(c->d_csr);
+  if (c->h_csr) (void)hipHostFree(c->h_csr);
   for (int i = 0; i < kMetaSlots; ++i)
     if (c->meta_ev[i]) (void)hipEventDestroy(c->meta_ev[i]);
   for (hipEvent_t e : c->ev_ring) (void)hipEventDestroy(e);
@@ -1042,6 +1099,10 @@ fx_status fx_synchronize(fx_ctx *c) {
 fx_status fx_process_batch(fx_ctx *c, const fx_scan_desc *scans, uint32_t batch, uint32_t flags, fx_batch_view *out) {
   if (!c || (!scans && batch) || !out) return fail(FX_ERR_INVALID_ARG, "null argument");
   if (batch > c->lim.max_batch) return fail(FX_ERR_TOO_LARGE, "batch > max_batch");
+  const bool csr = (flags & FX_OUT_DESC_CSR) != 0;
+  if (csr && !(flags & FX_OUT_HOST)) return fail(FX_ERR_INVALID_ARG, "FX_OUT_DESC_CSR needs FX_OUT_HOST");
+  if (csr && !csr_pool_fits(c->lim)) return fail(FX_ERR_TOO_LARGE, "FX_OUT_DESC_CSR: max_total_keypoints * 1989 exceeds 2^32 - 1");
+  c->csr_valid = false;
   FX_HIP(hipSetDevice(c->device));
   const fx_limits &L = c->lim;
   hipStream_t s = c->stream;
@@ -1192,7 +1253,19 @@ fx_status fx_process_batch(fx_ctx *c, const fx_scan_desc *scans, uint32_t batch,
   FX_TRY(host_alloc(c, &c->h_hdr, 5 * S));
   c->h_n_kp = c->h_hdr, c->h_kp_offset = c->h_hdr + S, c->h_flags = c->h_hdr + 2 * S, c->h_n_filt = c->h_hdr + 3 * S, c->h_n_kpc = c->h_hdr + 4 * S;
   FX_TRY(host_alloc(c, &c->h_keypoints, Bm * L.max_keypoints * 4));
-  FX_TRY(host_alloc(c, &c->h_desc, (size_t)L.max_total_keypoints * FX_DESC_FLOATS));
+  if (!csr) FX_TRY(host_alloc(c, &c->h_desc, (size_t)L.max_total_keypoints * FX_DESC_FLOATS));
+  if (csr) {
+    // the batch's rows packed behind its kernels; the header comes back with the per-scan words
+    if (!c->d_csr || c->csr_resize) {
+      const uint32_t want = c->csr_cap_want ? c->csr_cap_want
+                                            : (uint32_t)std::min<uint64_t>((uint64_t)L.max_total_keypoints * kCsrRowEntries,
+                                                                           (uint64_t)L.max_total_keypoints * FX_DESC_FLOATS);
+      FX_TRY(csr_reserve(c, std::max(want, 1u)));
+      c->csr_resize = false;
+    }
+    FX_TRY(enqueue_csr(c, s, c->d_csr, L.max_total_keypoints, c->csr_cap));
+    FX_HIP(hipMemcpyAsync(c->h_csr, c->d_csr, 16, hipMemcpyDeviceToHost, s));
+  }
   if (batch) {
     // (n_kp | kp_offset | flags | n_filt | n_kpc, S words each: everything up to the last array's last scan of this batch)
     FX_HIP(hipMemcpyAsync(c->h_hdr, B.n_kp, (4 * S + batch) * 4, hipMemcpyDeviceToHost, s));
@@ -1206,8 +1279,25 @@ fx_status fx_process_batch(fx_ctx *c, const fx_scan_desc *scans, uint32_t batch,
   out->total_keypoints = total;
   // (about as many rows as the last call had, copied BEFORE the wait, and the per-scan words in one block instead of five
   //  copies: measured for a scan per call, 0.244 ms either way — the copies are not what the call waits for; the one block stayed)
-  if (total && P.estimate_descriptors)
+  if (total && P.estimate_descriptors && !csr)
     FX_HIP(hipMemcpyAsync(c->h_desc, B.desc, (size_t)total * FX_DESC_FLOATS * 4, hipMemcpyDeviceToHost, s));
+  if (csr) {
+    const uint32_t *hd = (const uint32_t *)c->h_csr;  // {rows, nnz_stored, nnz_needed, rows_stored}
+    const uint32_t rows = hd[0], nnz = hd[2];
+    if (hd[3] < rows) {
+      // lossless: the dense rows are intact until the next batch — a larger block (an eighth of slack) and the pack again
+      const uint32_t cap = (uint32_t)std::min<uint64_t>((uint64_t)nnz + nnz / 8u, (uint64_t)L.max_total_keypoints * FX_DESC_FLOATS);
+      FX_TRY(csr_reserve(c, cap));
+      FX_TRY(enqueue_csr(c, s, c->d_csr, L.max_total_keypoints, c->csr_cap));
+    }
+    const size_t col = csr_col_offset(L.max_total_keypoints), val = csr_val_offset(L.max_total_keypoints, c->csr_cap);
+    FX_HIP(hipMemcpyAsync(c->h_csr + 16, c->d_csr + 16, ((size_t)rows + 1u) * 4u, hipMemcpyDeviceToHost, s));
+    if (nnz) {
+      FX_HIP(hipMemcpyAsync(c->h_csr + col, c->d_csr + col, (size_t)nnz * 4u, hipMemcpyDeviceToHost, s));
+      FX_HIP(hipMemcpyAsync(c->h_csr + val, c->d_csr + val, (size_t)nnz * 4u, hipMemcpyDeviceToHost, s));
+    }
+    c->csr_rows = rows, c->csr_nnz = nnz;
+  }
   if (flags & FX_OUT_CLOUDS) {
     FX_TRY(host_alloc(c, &c->h_filtered, Bm * L.max_points * 4));
     FX_TRY(host_alloc(c, &c->h_kpc, Bm * L.max_kpc_points * 4));
@@ -1251,8 +1341,9 @@ fx_status fx_process_batch(fx_ctx *c, const fx_scan_desc *scans, uint32_t batch,
   out->h_n_keypoints = c->h_n_kp;
   out->h_kp_offset = c->h_kp_offset;
   out->h_keypoints = c->h_keypoints;
-  out->h_descriptors = c->h_desc;
+  out->h_descriptors = csr ? nullptr : c->h_desc;
   out->h_flags = c->h_flags;
+  c->csr_valid = csr;
   out->h_n_filtered = c->h_n_filt;
   out->h_n_kpc = c->h_n_kpc;
   suspect.armed = false;
@@ -1397,6 +1488,39 @@ fx_status fx_pack_keypoint_block(fx_ctx *c, void *dst_device, uint32_t max_scans
   const uint32_t grid = std::max(1u, std::min(c->last_batch, 4u * (uint32_t)c->n_cu));
   fxk_pack_kp_block(c->stream, c->dp, c->buf, c->last_batch, dst_device, max_scans, max_total_keypoints, grid);
   FX_HIP(hipGetLastError());
+  return FX_OK;
+}
+
+size_t fx_descriptor_csr_bytes(uint32_t max_rows, uint32_t capacity) { return fxk_csr_bytes(max_rows, capacity); }
+
+fx_status fx_pack_descriptors_csr(fx_ctx *c, void *dst_device, uint32_t max_rows, uint32_t capacity) {
+  if (!c || !dst_device) return fail(FX_ERR_INVALID_ARG, "null argument");
+  if (((uintptr_t)dst_device % 16) != 0) return fail(FX_ERR_INVALID_ARG, "dst must be 16-byte aligned");
+  if (!csr_pool_fits(c->lim)) return fail(FX_ERR_TOO_LARGE, "max_total_keypoints * 1989 exceeds 2^32 - 1");
+  FX_HIP(hipSetDevice(c->device));
+  return enqueue_csr(c, c->stream, dst_device, max_rows, capacity);
+}
+
+fx_status fx_get_descriptors_csr(fx_ctx *c, fx_descriptor_csr_view *out) {
+  if (!c || !out) return fail(FX_ERR_INVALID_ARG, "null argument");
+  if (!c->csr_valid) return fail(FX_ERR_INVALID_ARG, "the last batch was not FX_OUT_HOST | FX_OUT_DESC_CSR");
+  const uint32_t R = c->lim.max_total_keypoints;
+  const size_t col = csr_col_offset(R), val = csr_val_offset(R, c->csr_cap);
+  out->rows = c->csr_rows;
+  out->nnz = c->csr_nnz;
+  out->h_row_ptr = (const uint32_t *)(c->h_csr + 16);
+  out->h_col = (const uint32_t *)(c->h_csr + col);
+  out->h_val = (const float *)(c->h_csr + val);
+  out->d_row_ptr = (const uint32_t *)(c->d_csr + 16);
+  out->d_col = (const uint32_t *)(c->d_csr + col);
+  out->d_val = (const float *)(c->d_csr + val);
+  return FX_OK;
+}
+
+fx_status fx_set_descriptor_csr_capacity(fx_ctx *c, uint32_t entries) {
+  if (!c) return fail(FX_ERR_INVALID_ARG, "null ctx");
+  c->csr_cap_want = entries;
+  c->csr_resize = c->d_csr != nullptr;
   return FX_OK;
 }
 

@@ -35,6 +35,13 @@ namespace fx {
 
 class StreamBatcher {
  public:
+  // One scan's descriptor rows as compressed rows (FX_OUT_DESC_CSR, include/fx.h): row k's non-zero words are
+  // col[row_ptr[k] .. row_ptr[k + 1]) (word index 0..1988 of the pcl::ShapeContext1980 row) with their values, bit for bit.
+  struct DescriptorCsr {
+    std::vector<uint32_t> row_ptr;  // [rows + 1], from 0
+    std::vector<uint32_t> col;
+    std::vector<float> val;
+  };
   struct Result {
     uint64_t id = 0;        // what push() returned
     uint32_t sensor = 0;
@@ -44,7 +51,8 @@ class StreamBatcher {
     std::string error;         // fx_last_error() of the failed batch
     double latency_ms = 0;  // push() to callback
     PointCloud keypoints;         // ~keypoints (ref: node.cpp:129-131)
-    DescriptorCloud descriptors;  // ~features payload (ref: node.cpp:113-124)
+    DescriptorCloud descriptors;  // ~features payload (ref: node.cpp:113-124); empty with csr_descriptors
+    DescriptorCsr descriptors_csr;  // with csr_descriptors: the same rows as CSR (a few KB a scan instead of 7956 B a row)
   };
   using Callback = std::function<void(Result &&)>;
   struct Stats {
@@ -62,9 +70,11 @@ class StreamBatcher {
   // support points) exhausts them, and the rows they cannot hold come back as NaN descriptors with FX_FLAG_NBR_OVERFLOW where
   // the reference computes them (ref: node.cpp:343-353).  full_pools = true starts from fx_limits_default instead
   // (ADVICE r5).
+  // csr_descriptors: deliver each scan's descriptors as Result::descriptors_csr (FX_OUT_DESC_CSR: only the non-zero words
+  // cross the link) instead of Result::descriptors.
   StreamBatcher(const fx_params &params, uint32_t max_batch, uint32_t max_points, int device, Callback cb, uint32_t pool_keypoints = 0,
-                const fx_limits *limits = nullptr, bool full_pools = false)
-      : cb_(std::move(cb)), max_batch_(max_batch), max_points_(max_points) {
+                const fx_limits *limits = nullptr, bool full_pools = false, bool csr_descriptors = false)
+      : cb_(std::move(cb)), max_batch_(max_batch), max_points_(max_points), csr_(csr_descriptors) {
     if (FX_CHECK_ABI() != FX_OK) throw std::runtime_error(std::string("fx_check_abi: ") + fx_last_error());  // (this translation unit's fx.h against the library's)
     fx_limits lim;
     if (full_pools)
@@ -166,7 +176,9 @@ class StreamBatcher {
       for (size_t i = 0; i < batch.size(); ++i)
         descs[i] = fx_scan_desc{batch[i].xyzi.data(), batch[i].n, 16, batch[i].roll, batch[i].pitch};
       fx_batch_view v;
-      const fx_status st = fx_process_batch(ctx_, descs.data(), (uint32_t)batch.size(), FX_OUT_HOST, &v);
+      fx_status st = fx_process_batch(ctx_, descs.data(), (uint32_t)batch.size(), FX_OUT_HOST | (csr_ ? FX_OUT_DESC_CSR : 0u), &v);
+      fx_descriptor_csr_view cv{};
+      if (st == FX_OK && csr_) st = fx_get_descriptors_csr(ctx_, &cv);
       if (st != FX_OK) {
         // the batch's scans come back with the status and no results; the context starts its next batch from scratch
         // (state_suspect) and the stream goes on
@@ -205,8 +217,18 @@ class StreamBatcher {
           // kp_offset and n_keypoints are not clamped to the pool, the copied rows are)
           const uint32_t off = v.h_kp_offset[i] < v.total_keypoints ? v.h_kp_offset[i] : v.total_keypoints;
           const uint32_t rows = K < v.total_keypoints - off ? K : v.total_keypoints - off;
-          r.descriptors.resize(rows);
-          if (rows) std::memcpy(r.descriptors.data(), v.h_descriptors + (size_t)off * FX_DESC_FLOATS, (size_t)rows * sizeof(Descriptor));
+          if (csr_) {
+            DescriptorCsr &d = r.descriptors_csr;
+            const uint32_t lo = off < cv.rows ? cv.h_row_ptr[off] : 0u, n = off + rows <= cv.rows ? rows : 0u;
+            const uint32_t hi = n ? cv.h_row_ptr[off + n] : lo;
+            d.row_ptr.resize((size_t)n + 1u);
+            for (uint32_t k = 0; k <= n; ++k) d.row_ptr[k] = n ? cv.h_row_ptr[off + k] - lo : 0u;
+            d.col.assign(cv.h_col + lo, cv.h_col + hi);
+            d.val.assign(cv.h_val + lo, cv.h_val + hi);
+          } else {
+            r.descriptors.resize(rows);
+            if (rows) std::memcpy(r.descriptors.data(), v.h_descriptors + (size_t)off * FX_DESC_FLOATS, (size_t)rows * sizeof(Descriptor));
+          }
         }
         r.latency_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - batch[i].t0).count();
         cb_(std::move(r));
@@ -225,6 +247,7 @@ class StreamBatcher {
   Callback cb_;
   uint32_t max_batch_, max_points_;
   bool estimate_descriptors_ = true;
+  bool csr_ = false;
   fx_ctx *ctx_ = nullptr;
   mutable std::mutex m_;
   std::condition_variable cv_;

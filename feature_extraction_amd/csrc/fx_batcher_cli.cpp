@@ -1,10 +1,11 @@
 // fx_batcher_cli — S simulated sensors (one producer thread each) push synthetic VLP-16 scans at HZ for SECONDS
 // through fx::StreamBatcher (fx_batcher.hpp); every scan's keypoints and descriptors are written to OUT for the test
 // to compare with the oracle, and the latency distribution / batch sizes are printed.
-//   fx_batcher_cli [--sensors S] [--hz HZ] [--seconds T] [--burst N] [--out FILE] [--default] [--poles P] [--max-batch B]
+//   fx_batcher_cli [--sensors S] [--hz HZ] [--seconds T] [--burst N] [--out FILE] [--default] [--poles P] [--max-batch B] [--csr]
 // Scan q of sensor s is fx_synth_scan(seed 1000 + 1000 s + q), roll 0.02, pitch -0.015.
 // OUT: per scan {u32 sensor, u32 seq, u32 flags, u32 K, K x float4 keypoints, K x 1989 float descriptors}; a scan of a batch
-// that FAILED has flags = 0x80000000 | fx_status and K = 0.
+// that FAILED has flags = 0x80000000 | fx_status and K = 0.  With --csr the descriptors come through FX_OUT_DESC_CSR and the
+// K rows are written as {u32 rows, u32 nnz, (rows + 1) x u32 row_ptr, nnz x u32 col, nnz x float val} instead.
 //   fx_batcher_cli --files A,B,... [--node] [--big-limits] --out FILE
 // pushes the scans of the given files (raw float32 x y z i records) ONE AT A TIME through one warm context — the batcher's,
 // or with --node fx::FeatureExtractionNode::cloudCallback (launch preset, roll = pitch = 0) — as sensor 0, seq 0, 1, ...
@@ -19,7 +20,7 @@ int main(int argc, char **argv) {
   try {
     uint32_t sensors = 4, burst = 0, poles = 0, max_batch = 64;
     double hz = 10.0, seconds = 2.0;
-    bool launch = true, node = false, big_limits = false;
+    bool launch = true, node = false, big_limits = false, csr = false;
     const char *out_path = nullptr, *files = nullptr;
     for (int i = 1; i < argc; ++i) {
       if (!std::strcmp(argv[i], "--sensors") && i + 1 < argc) sensors = (uint32_t)std::atoi(argv[++i]);
@@ -33,7 +34,22 @@ int main(int argc, char **argv) {
       else if (!std::strcmp(argv[i], "--files") && i + 1 < argc) files = argv[++i];
       else if (!std::strcmp(argv[i], "--node")) node = true;
       else if (!std::strcmp(argv[i], "--big-limits")) big_limits = true;
+      else if (!std::strcmp(argv[i], "--csr")) csr = true;
     }
+    // a scan's descriptor payload in OUT: dense rows, or (--csr) its CSR record
+    auto write_desc = [&](FILE *f, const fx::StreamBatcher::Result &r) {
+      if (!csr) {
+        std::fwrite(r.descriptors.data(), sizeof(fx::Descriptor), r.descriptors.size(), f);
+        return;
+      }
+      const fx::StreamBatcher::DescriptorCsr &d = r.descriptors_csr;
+      const uint32_t rows = d.row_ptr.empty() ? 0u : (uint32_t)d.row_ptr.size() - 1u, h[2] = {rows, (uint32_t)d.col.size()};
+      std::fwrite(h, 4, 2, f);
+      const uint32_t zero = 0;
+      if (d.row_ptr.empty()) std::fwrite(&zero, 4, 1, f); else std::fwrite(d.row_ptr.data(), 4, d.row_ptr.size(), f);
+      std::fwrite(d.col.data(), 4, d.col.size(), f);
+      std::fwrite(d.val.data(), 4, d.val.size(), f);
+    };
     fx_params p;
     if (launch) fx_params_launch(&p); else fx_params_default(&p);
     if (files) {
@@ -64,6 +80,7 @@ int main(int argc, char **argv) {
         std::fwrite(d.data(), sizeof(fx::Descriptor), d.size(), out);
       };
       uint32_t flags_or = 0;
+      if (node && csr) throw std::runtime_error("--csr goes with the batcher, not --node");
       if (node) {
         fx::FeatureExtractionNode n(0, 28800);
         n.useLaunchPreset();
@@ -78,15 +95,24 @@ int main(int argc, char **argv) {
         }
       } else {
         std::vector<fx::StreamBatcher::Result> results;
-        fx::StreamBatcher batcher(p, 4, 28800, 0, [&](fx::StreamBatcher::Result &&r) { results.push_back(std::move(r)); }, 0, big_limits ? &big : nullptr);
+        fx::StreamBatcher batcher(p, 4, 28800, 0, [&](fx::StreamBatcher::Result &&r) { results.push_back(std::move(r)); }, 0, big_limits ? &big : nullptr,
+                                  false, csr);
         for (size_t i = 0; i < in.size(); ++i) {
           batcher.push(0, in[i].data(), (uint32_t)(in[i].size() / 4), 16, 0.0, 0.0);
           batcher.flush();  // (every scan is a batch of its own: the context is warm, the batch before was whatever came before)
         }
         for (size_t i = 0; i < results.size(); ++i) {
           flags_or |= results[i].flags;
-          emit((uint32_t)results[i].id, results[i].status == FX_OK ? results[i].flags : (0x80000000u | (uint32_t)results[i].status), results[i].keypoints,
-               results[i].descriptors);
+          const uint32_t flags = results[i].status == FX_OK ? results[i].flags : (0x80000000u | (uint32_t)results[i].status);
+          if (csr) {
+            if (!out) continue;
+            const uint32_t hdr[4] = {0u, (uint32_t)results[i].id, flags, (uint32_t)results[i].keypoints.size()};
+            std::fwrite(hdr, 4, 4, out);
+            std::fwrite(results[i].keypoints.data(), sizeof(fx::Point), results[i].keypoints.size(), out);
+            write_desc(out, results[i]);
+          } else {
+            emit((uint32_t)results[i].id, flags, results[i].keypoints, results[i].descriptors);
+          }
         }
         if (results.size() != in.size()) throw std::runtime_error("scans lost");
       }
@@ -112,7 +138,7 @@ int main(int argc, char **argv) {
     fx::StreamBatcher batcher(p, max_batch, N, 0, [&](fx::StreamBatcher::Result &&r) {
       std::lock_guard<std::mutex> lk(rm);
       results.push_back(std::move(r));
-    });
+    }, 0, nullptr, false, csr);
     {  // one warm-up scan (first-use costs: code upload, graph capture), not counted
       batcher.push(0, scans[0].data(), N, 16, 0.02, -0.015);
       batcher.flush();
@@ -152,7 +178,7 @@ int main(int argc, char **argv) {
         const uint32_t hdr[4] = {it->second.first, it->second.second, r.status == FX_OK ? r.flags : (0x80000000u | (uint32_t)r.status), (uint32_t)r.keypoints.size()};
         std::fwrite(hdr, 4, 4, out);
         std::fwrite(r.keypoints.data(), sizeof(fx::Point), r.keypoints.size(), out);
-        std::fwrite(r.descriptors.data(), sizeof(fx::Descriptor), r.descriptors.size(), out);
+        write_desc(out, r);
       }
     }
     if (out) std::fclose(out);

@@ -65,6 +65,10 @@ struct FxScTables {
 #define FX_ATAN_N 64      // table step of k_prep's arctangent: 1 / 64 over [0, 1]
 #define FX_ATAN_DEG 6     // degree of the expansion about a table point (|offset| <= 1 / 128: truncation below 2^-51)
 #define FX_ROW_DIRTY 0xffffffffu
+// CSR block of descriptor rows (include/fx.h fx_descriptor_csr_bytes): words of row_ptr[max_rows + 1] and of col / val[cap],
+// each rounded up to 16 bytes; header 16 B, then row_ptr, col, val
+__host__ __device__ inline size_t csr_rp_words(uint32_t max_rows) { return ((size_t)max_rows + 1u + 3u) & ~(size_t)3; }
+__host__ __device__ inline size_t csr_cap_words(uint32_t cap) { return ((size_t)cap + 3u) & ~(size_t)3; }
 #define FX_N_HINTS 8      // tier_hint[]: 0 / 1 rings handed to the second run tier / the workgroup tier (largest XCD class), 2 big merges, 3 huge merges, 4 dense rows, 5 dense support points, 6 scans k_front handed to k_front_redo, 7 scans handed to the slow tier (k_slow)
 #define FX_CNT_QPOOL 32   // counters[32]: entries of the dense tier's query pool in use
 #define FX_CNT_LARGE2 16  // counters[16 + c]: rings of XCD class c the second run tier hands to the workgroup tier

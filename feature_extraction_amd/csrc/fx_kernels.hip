@@ -6470,6 +6470,163 @@ extern "C" __global__ __launch_bounds__(FX_WG) void k_pack_kp_block(FxDevParams 
   for (uint32_t k = total + blockIdx.x * FX_WG + tid; k < max_total; k += gridDim.x * FX_WG) kp[k] = make_float4(0, 0, 0, 0);
 }
 
+// ---------------------------------------------------------------- descriptor rows as CSR (fx_pack_descriptors_csr)
+// A row of 1989 words holds some tens of non-zero ones.  Block (16-byte aligned sections): header {rows, nnz_stored,
+// nnz_needed, rows_stored} (u32); row_ptr[max_rows + 1] (u32); col[capacity] (u32, word index 0..1988, increasing within a
+// row); val[capacity] (the word's bits).  A word is stored iff its bit pattern is non-zero (-0.0 and NaN are kept): the block
+// expands into the dense rows bit for bit.  Whole rows are stored in order while they fit `capacity`; the first that does not
+// and all after it stay empty (rows_stored < rows).  Three launches, every one a pure function of the dense rows (no float
+// atomics, nothing in completion order): k_csr_count writes each row's count into row_ptr[row + 1], k_csr_scan (one
+// workgroup) turns those into offsets and cuts at the capacity, k_csr_write fills the rows that fit.
+//
+// Two ways to read a row, both a wavefront a row:
+//  - a row k_desc_group filled in this batch (desc_nbins[row] <= FX_GROUP_CAP): only its recorded bins (desc_bins) and the 9
+//    rf words are read.  The recorded list is a SUPERSET of the row's non-zero bins: k_desc_group clears a row at the top of
+//    its trip (whole when desc_nbins was FX_ROW_DIRTY, else the bins recorded last time — by induction all the row held), then
+//    writes `out[bin]` only for the bins it records in desc_bins, and sets desc_nbins to their count only for a live row with
+//    nAll != 0.  Every other row of the batch gets FX_ROW_DIRTY from it: too_long rows (the wave / list / dense tiers and the
+//    NaN fill of an exhausted dense pool, the only other writers of a row) and nAll == 0 (its NaN fill; desc_nbins is then
+//    not rewritten by the closing `nAll != 0` store, it was set dirty just before).  Bins recorded with a weight that summed
+//    to zero bits are dropped by the storage rule.  desc_bins is in atomicAdd order: sorted here by rank within the wavefront.
+//  - any other row (FX_ROW_DIRTY; the test build's FX_CSR_FULL_ROWS=1 forces this for every row): the whole row with 16-byte
+//    loads over its aligned span (rows start 4-byte aligned; the pool has 4 words of padding behind its last row), the
+//    non-zero words found with a ballot per component of the float4 and their positions by popcount / mbcnt.
+__device__ __forceinline__ uint32_t csr_rows(const FxDevParams &P, const FxBuffers &B, uint32_t batch) {
+  return P.estimate_descriptors ? min(B.kp_offset[batch], P.max_total_kp) : 0u;
+}
+// Non-zero words of `row` (wave-uniform call, all 64 lanes).  col != nullptr: also stores them at [start, end) of col / val.
+__device__ __forceinline__ uint32_t csr_row(const FxBuffers &B, uint32_t row, uint32_t lane, uint32_t full_rows, uint32_t *col,
+                                            uint32_t *val, uint32_t start, uint32_t end) {
+  const float *src = B.desc + (size_t)row * FX_DESC_FLOATS;
+  const uint32_t nb = B.desc_nbins[row];
+  if (nb <= FX_GROUP_CAP && !full_rows) {
+    uint32_t bin = 0xffffu, v = 0u, r = 0u;
+    if (lane < nb) {
+      bin = B.desc_bins[(size_t)row * FX_GROUP_CAP + lane];
+      v = __float_as_uint(src[bin]);
+    }
+    if (lane < FX_DESC_RF) r = __float_as_uint(src[FX_DESC_BINS + lane]);
+    const unsigned long long m = __ballot(v != 0u), mr = __ballot(r != 0u);
+    const uint32_t n_bins = (uint32_t)__popcll(m);
+    if (col) {
+      uint32_t pos = 0;  // rank among the kept bins (they are distinct: one lane of k_desc_group per bin run)
+      for (unsigned long long q = m; q; q &= q - 1ull) {
+        const uint32_t b2 = (uint32_t)__shfl((int)bin, __ffsll((long long)q) - 1, 64);
+        pos += b2 < bin ? 1u : 0u;
+      }
+      if (v != 0u && start + pos < end) col[start + pos] = bin, val[start + pos] = v;
+      const uint32_t pr = start + n_bins + lanes_below(mr);  // (the rf words come after every bin)
+      if (r != 0u && pr < end) col[pr] = FX_DESC_BINS + lane, val[pr] = r;
+    }
+    return n_bins + (uint32_t)__popcll(mr);
+  }
+  const size_t w0 = (size_t)row * FX_DESC_FLOATS, w1 = w0 + FX_DESC_FLOATS;
+  uint32_t n = 0;
+  for (size_t a = w0 & ~(size_t)3; a < w1; a += 256) {
+    const size_t q = a + 4u * lane;
+    uint4 x = make_uint4(0u, 0u, 0u, 0u);
+    if (q < w1) x = *reinterpret_cast<const uint4 *>(B.desc + q);
+    uint32_t w[4] = {x.x, x.y, x.z, x.w};
+    unsigned long long m[4];
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j) {
+      if (q + j < w0 || q + j >= w1) w[j] = 0u;  // (the neighbouring rows' words in the aligned span)
+      m[j] = __ballot(w[j] != 0u);
+    }
+    if (col) {
+      uint32_t pos = start + n;
+#pragma unroll
+      for (uint32_t j = 0; j < 4; ++j) pos += lanes_below(m[j]);
+#pragma unroll
+      for (uint32_t j = 0; j < 4; ++j)
+        if (w[j] != 0u) {
+          if (pos < end) col[pos] = (uint32_t)(q + j - w0), val[pos] = w[j];
+          ++pos;
+        }
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j) n += (uint32_t)__popcll(m[j]);
+  }
+  return n;
+}
+// Pass 1: row_ptr[row + 1] = the row's count for the rows the block has room for; the rows beyond max_rows add theirs to
+// the header's nnz_needed (zeroed by the caller; integer sums: the result does not depend on their order).
+extern "C" __global__ __launch_bounds__(FX_WG) void k_csr_count(FxDevParams P, FxBuffers B, uint32_t batch, uint32_t *dst, uint32_t max_rows,
+                                                                 uint32_t full_rows) {
+  const uint32_t lane = threadIdx.x & 63u, rows = csr_rows(P, B, batch);
+  uint32_t *rp = dst + 4, beyond = 0;
+  for (uint32_t row = blockIdx.x * FX_NWAVE + (threadIdx.x >> 6); row < rows; row += gridDim.x * FX_NWAVE) {
+    const uint32_t n = csr_row(B, row, lane, full_rows, nullptr, nullptr, 0u, 0u);
+    if (row < max_rows) {
+      if (lane == 0) rp[row + 1u] = n;
+    } else {
+      beyond += n;
+    }
+  }
+  if (lane == 0 && beyond) atomicAdd(&dst[2], beyond);
+}
+// Pass 2 (one workgroup of 1024): inclusive scan of row_ptr[1..n] in place, tiles of 4096 entries; rows_stored = the rows
+// whose end is within capacity (the offsets rise: they are a leading run), the rest of row_ptr repeats nnz_stored.
+#define FX_CSR_SCAN_T 1024
+extern "C" __global__ __launch_bounds__(FX_CSR_SCAN_T) void k_csr_scan(FxDevParams P, FxBuffers B, uint32_t batch, uint32_t *dst, uint32_t max_rows,
+                                                                        uint32_t cap) {
+  __shared__ uint32_t s_w[FX_CSR_SCAN_T / 64], s_fit, s_stored;
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint32_t rows = csr_rows(P, B, batch), n = min(rows, max_rows);
+  uint32_t *rp = dst + 4;
+  if (tid == 0) s_fit = 0u, s_stored = 0u;
+  uint32_t carry = 0, fit = 0, stored = 0;
+  for (uint32_t t0 = 0; t0 < n; t0 += 4u * FX_CSR_SCAN_T) {
+    const uint32_t i = t0 + 4u * tid;
+    uint32_t v[4];
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j) v[j] = i + j < n ? rp[1u + i + j] : 0u;
+    v[1] += v[0], v[2] += v[1], v[3] += v[2];
+    uint32_t incl = v[3];
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint32_t o = (uint32_t)__shfl_up((int)incl, d, 64);
+      if (lane >= (uint32_t)d) incl += o;
+    }
+    __syncthreads();  // (s_w of the previous tile read by everyone)
+    if (lane == 63u) s_w[wave] = incl;
+    __syncthreads();
+    uint32_t before = carry, tile = 0;
+    for (uint32_t w2 = 0; w2 < FX_CSR_SCAN_T / 64; ++w2) {
+      before += w2 < wave ? s_w[w2] : 0u;
+      tile += s_w[w2];
+    }
+    before += incl - v[3];
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j)
+      if (i + j < n) {
+        const uint32_t e = before + v[j];
+        rp[1u + i + j] = e;
+        if (e <= cap) ++fit, stored = max(stored, e);
+      }
+    carry += tile;
+  }
+  __syncthreads();
+  if (fit) atomicAdd(&s_fit, fit);
+  if (stored) atomicMax(&s_stored, stored);
+  __syncthreads();
+  const uint32_t rows_stored = s_fit, nnz_stored = s_stored;
+  for (uint32_t r = rows_stored + 1u + tid; r <= max_rows; r += FX_CSR_SCAN_T) rp[r] = nnz_stored;
+  if (tid == 0) {
+    rp[0] = 0u;
+    const uint32_t beyond = dst[2];  // (k_csr_count's, written before this launch)
+    dst[0] = rows, dst[1] = nnz_stored, dst[2] = carry + beyond, dst[3] = rows_stored;
+  }
+}
+// Pass 3: the rows that fit, each at its offset (stores bounded by the row's own [row_ptr[row], row_ptr[row + 1])).
+extern "C" __global__ __launch_bounds__(FX_WG) void k_csr_write(FxBuffers B, uint32_t *dst, uint32_t max_rows, uint32_t cap, uint32_t full_rows) {
+  const uint32_t lane = threadIdx.x & 63u, rows = dst[3];
+  const uint32_t *rp = dst + 4;
+  uint32_t *col = dst + 4u + csr_rp_words(max_rows), *val = col + csr_cap_words(cap);
+  for (uint32_t row = blockIdx.x * FX_NWAVE + (threadIdx.x >> 6); row < rows; row += gridDim.x * FX_NWAVE)
+    (void)csr_row(B, row, lane, full_rows, col, val, rp[row], rp[row + 1u]);
+}
+
 // ====================================================================== PointCloud2 wire formats
 // Ingress: pcl::fromPCLPointCloud2 (ref: node.cpp:79-81) picks the float32 fields x, y, z by name
 // out of point_step-byte records (velodyne driver clouds carry extra fields such as `ring`, and
@@ -6796,6 +6953,17 @@ size_t fxk_kp_block_bytes(uint32_t max_scans, uint32_t max_total) {
 void fxk_pack_kp_block(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, void *dst, uint32_t max_scans, uint32_t max_total,
                        uint32_t grid) {
   hipLaunchKernelGGL(k_pack_kp_block, dim3(grid), dim3(FX_WG), 0, s, P, B, batch, (uint32_t *)dst, max_scans, max_total);
+}
+size_t fxk_csr_bytes(uint32_t max_rows, uint32_t cap) { return 16u + 4u * csr_rp_words(max_rows) + 8u * csr_cap_words(cap); }
+hipError_t fxk_pack_csr(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, void *dst, uint32_t max_rows, uint32_t cap,
+                        uint32_t grid, uint32_t full_rows) {
+  uint32_t *d = (uint32_t *)dst;
+  const hipError_t e = hipMemsetAsync(d, 0, 16, s);  // (nnz_needed gathers k_csr_count's rows beyond max_rows)
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_csr_count, dim3(grid), dim3(FX_WG), 0, s, P, B, batch, d, max_rows, full_rows);
+  hipLaunchKernelGGL(k_csr_scan, dim3(1), dim3(FX_CSR_SCAN_T), 0, s, P, B, batch, d, max_rows, cap);
+  hipLaunchKernelGGL(k_csr_write, dim3(grid), dim3(FX_WG), 0, s, B, d, max_rows, cap, full_rows);
+  return hipGetLastError();
 }
 void fxk_unpack_pc2(hipStream_t s, const void *src, uint32_t n, uint32_t point_step, uint32_t ox, uint32_t oy, uint32_t oz,
                     uint32_t oi, uint32_t big_endian, void *dst, uint32_t grid) {

@@ -304,6 +304,45 @@ fx_status fx_pack_keypoint_records(fx_ctx *ctx, void *dst_device, uint32_t rec_k
 size_t fx_keypoint_block_bytes(uint32_t max_scans, uint32_t max_total_keypoints);
 fx_status fx_pack_keypoint_block(fx_ctx *ctx, void *dst_device, uint32_t max_scans, uint32_t max_total_keypoints);
 
+/* ---- Descriptors as compressed rows (CSR) ----
+ * A descriptor row has some tens of non-zero words out of 1989.  The CSR block is one fixed-size, self-describing block of
+ * fx_descriptor_csr_bytes(max_rows, capacity) bytes, sections 16-byte aligned, in order:
+ *   header   {rows, nnz_stored, nnz_needed, rows_stored} (u32)
+ *   row_ptr  u32 [max_rows + 1]: row r's entries are [row_ptr[r], row_ptr[r+1]); entries past rows_stored repeat nnz_stored
+ *   col      u32 [capacity]: word index 0..1988 of the dense row (bins 0..1979, then rf 1980..1988), increasing within a row
+ *   val      f32 [capacity]: that word, bit for bit
+ * Rows are the batch's descriptor rows [0, total_keypoints) in d_descriptors order (scan b: [kp_offset[b], kp_offset[b+1])).
+ * A word is stored iff its 32-bit pattern is non-zero (-0.0 and NaN are kept; an FX_FLAG_NBR_OVERFLOW row stores every bin):
+ * expanding the block into zeros gives the dense rows back bit for bit.  Whole rows are stored in order while they fit
+ * `capacity`; the first row that does not fit and every row after it stay empty (rows_stored < rows; nnz_needed is what all
+ * rows need).  Nothing is written past capacity.  col / val are separate arrays: (row_ptr, col, val) wrap as a CSR matrix
+ * with int32 indices as they are.  New in 0.7 (added symbols only). */
+size_t fx_descriptor_csr_bytes(uint32_t max_rows, uint32_t capacity);
+/* Packs the last batch's descriptor rows into a CSR block at dst_device (16-byte aligned, fx_descriptor_csr_bytes bytes),
+ * enqueued on the context's stream behind the last fx_process_batch.  An empty batch or estimate_descriptors = 0 gives
+ * rows = 0; rows > max_rows stores the first max_rows rows (rows_stored <= max_rows).  FX_ERR_TOO_LARGE when the context's
+ * descriptor pool could need more than 2^32 - 1 entries (max_total_keypoints > 2 159 383). */
+fx_status fx_pack_descriptors_csr(fx_ctx *ctx, void *dst_device, uint32_t max_rows, uint32_t capacity);
+/* With FX_OUT_HOST: the host gets the context's own CSR block instead of the dense rows.  h_descriptors is then NULL (the
+ * dense host mirror is not allocated for such calls); d_descriptors is unchanged.  Only row_ptr[0..rows], col[0..nnz) and
+ * val[0..nnz) cross the link.  Lossless: a batch that needs more entries than the context block holds grows the block
+ * (device and pinned mirror) and packs again.  Read the result with fx_get_descriptors_csr. */
+#define FX_OUT_DESC_CSR 0x10u
+typedef struct fx_descriptor_csr_view {
+  uint32_t rows, nnz;
+  const uint32_t *h_row_ptr, *h_col; /* pinned host: row_ptr[rows + 1], col[nnz] */
+  const float *h_val;                /* pinned host: val[nnz] */
+  const uint32_t *d_row_ptr, *d_col; /* the context's device block */
+  const float *d_val;
+} fx_descriptor_csr_view;
+/* The last FX_OUT_HOST | FX_OUT_DESC_CSR batch's rows; valid until the next fx_process_batch (FX_ERR_INVALID_ARG when the
+ * last batch was not one). */
+fx_status fx_get_descriptors_csr(fx_ctx *ctx, fx_descriptor_csr_view *out);
+/* Initial capacity (entries) of the context's CSR block; 0 = the default, max_total_keypoints * 128 (1 KB a row: 8x less
+ * than the dense pool; the VLP-16 / 64- / 128-ring test scenes average 15 to 77 non-zero words a row).  Takes effect at the next
+ * FX_OUT_DESC_CSR batch; the block still grows when a batch needs more. */
+fx_status fx_set_descriptor_csr_capacity(fx_ctx *ctx, uint32_t entries);
+
 /* Rotation matrix of rotateCloud (ref: node.cpp:161-164): R = Ry(pitch)*Rx(roll)
  * through Eigen's AngleAxisf -> Quaternionf -> toRotationMatrix, all float. Host only. */
 void fx_rotation_from_roll_pitch(double roll, double pitch, float R[9]);
