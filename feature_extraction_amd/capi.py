@@ -511,6 +511,7 @@ class Context:
                 o0, o1 = min(int(off[b]), v.total_keypoints), min(int(off[b]) + d["n_keypoints"], v.total_keypoints)
                 if o1 >= len(rp):  # (estimate_descriptors = 0: no rows)
                     o0 = o1 = 0
+                d["rows"] = o1 - o0
                 lo, hi = int(rp[o0]), int(rp[o1])
                 d["desc_csr"] = (rp[o0:o1 + 1] - rp[o0], col[lo:hi], val[lo:hi])
         return out
@@ -529,8 +530,12 @@ class Context:
         if debug:
             n_c = _np(v.h_n_candidates, (B,), np.uint32)
         for b in range(B):
-            d = {"flags": int(flags[b]), "n_keypoints": int(n_kp[b]), "keypoints": kp[b, :n_kp[b]],
-                 "descriptors": desc[off[b]:off[b] + n_kp[b]] if len(desc) else np.zeros((0, FX_DESC_FLOATS), np.float32)}
+            # rows: the scan's descriptor rows the pool holds — its leading ones; n_keypoints unless FX_FLAG_TOTAL_KP_OVERFLOW
+            # (include/fx.h "Cuts").  0 without descriptors.
+            held = len(desc) if self.params.estimate_descriptors else 0
+            r0, r1 = min(int(off[b]), held), min(int(off[b]) + int(n_kp[b]), held)
+            d = {"flags": int(flags[b]), "n_keypoints": int(n_kp[b]), "keypoints": kp[b, :n_kp[b]], "rows": r1 - r0,
+                 "descriptors": desc[r0:r1] if held else np.zeros((0, FX_DESC_FLOATS), np.float32)}
             if v.h_filtered:
                 base = C.cast(v.h_filtered, C.c_void_p).value + b * L.max_points * 16
                 d["filtered"] = _np(C.cast(base, _F32P), (int(n_f[b]), 4), np.float32)

@@ -219,7 +219,9 @@ class StreamBatcher {
           const uint32_t rows = K < v.total_keypoints - off ? K : v.total_keypoints - off;
           if (csr_) {
             DescriptorCsr &d = r.descriptors_csr;
-            const uint32_t lo = off < cv.rows ? cv.h_row_ptr[off] : 0u, n = off + rows <= cv.rows ? rows : 0u;
+            // (the leading rows the block holds, as the dense copy delivers them)
+            const uint32_t held = off < cv.rows ? cv.rows - off : 0u, n = rows < held ? rows : held;
+            const uint32_t lo = off < cv.rows ? cv.h_row_ptr[off] : 0u;
             const uint32_t hi = n ? cv.h_row_ptr[off + n] : lo;
             d.row_ptr.resize((size_t)n + 1u);
             for (uint32_t k = 0; k <= n; ++k) d.row_ptr[k] = n ? cv.h_row_ptr[off + k] - lo : 0u;

@@ -2,10 +2,13 @@
 // through fx::StreamBatcher (fx_batcher.hpp); every scan's keypoints and descriptors are written to OUT for the test
 // to compare with the oracle, and the latency distribution / batch sizes are printed.
 //   fx_batcher_cli [--sensors S] [--hz HZ] [--seconds T] [--burst N] [--out FILE] [--default] [--poles P] [--max-batch B] [--csr]
+//                  [--rows]
 // Scan q of sensor s is fx_synth_scan(seed 1000 + 1000 s + q), roll 0.02, pitch -0.015.
 // OUT: per scan {u32 sensor, u32 seq, u32 flags, u32 K, K x float4 keypoints, K x 1989 float descriptors}; a scan of a batch
-// that FAILED has flags = 0x80000000 | fx_status and K = 0.  With --csr the descriptors come through FX_OUT_DESC_CSR and the
-// K rows are written as {u32 rows, u32 nnz, (rows + 1) x u32 row_ptr, nnz x u32 col, nnz x float val} instead.
+// that FAILED has flags = 0x80000000 | fx_status and K = 0.  With --rows the descriptors are {u32 rows, rows x 1989 float}
+// instead: the scan's rows the descriptor pool holds, its leading ones, K unless FX_FLAG_TOTAL_KP_OVERFLOW (without --rows a
+// cut scan's record is not readable).  With --csr the descriptors come through FX_OUT_DESC_CSR and the held rows are written
+// as {u32 rows, u32 nnz, (rows + 1) x u32 row_ptr, nnz x u32 col, nnz x float val} instead.
 //   fx_batcher_cli --files A,B,... [--node] [--big-limits] --out FILE
 // pushes the scans of the given files (raw float32 x y z i records) ONE AT A TIME through one warm context — the batcher's,
 // or with --node fx::FeatureExtractionNode::cloudCallback (launch preset, roll = pitch = 0) — as sensor 0, seq 0, 1, ...
@@ -20,7 +23,7 @@ int main(int argc, char **argv) {
   try {
     uint32_t sensors = 4, burst = 0, poles = 0, max_batch = 64;
     double hz = 10.0, seconds = 2.0;
-    bool launch = true, node = false, big_limits = false, csr = false;
+    bool launch = true, node = false, big_limits = false, csr = false, rows_word = false;
     const char *out_path = nullptr, *files = nullptr;
     for (int i = 1; i < argc; ++i) {
       if (!std::strcmp(argv[i], "--sensors") && i + 1 < argc) sensors = (uint32_t)std::atoi(argv[++i]);
@@ -35,11 +38,14 @@ int main(int argc, char **argv) {
       else if (!std::strcmp(argv[i], "--node")) node = true;
       else if (!std::strcmp(argv[i], "--big-limits")) big_limits = true;
       else if (!std::strcmp(argv[i], "--csr")) csr = true;
+      else if (!std::strcmp(argv[i], "--rows")) rows_word = true;
     }
     // a scan's descriptor payload in OUT: dense rows, or (--csr) its CSR record
     auto write_desc = [&](FILE *f, const fx::StreamBatcher::Result &r) {
       if (!csr) {
-        std::fwrite(r.descriptors.data(), sizeof(fx::Descriptor), r.descriptors.size(), f);
+        const uint32_t rows = (uint32_t)r.descriptors.size();
+        if (rows_word) std::fwrite(&rows, 4, 1, f);
+        std::fwrite(r.descriptors.data(), sizeof(fx::Descriptor), rows, f);
         return;
       }
       const fx::StreamBatcher::DescriptorCsr &d = r.descriptors_csr;
@@ -77,7 +83,9 @@ int main(int argc, char **argv) {
         const uint32_t hdr[4] = {0u, seq, flags, (uint32_t)kp.size()};
         std::fwrite(hdr, 4, 4, out);
         std::fwrite(kp.data(), sizeof(fx::Point), kp.size(), out);
-        std::fwrite(d.data(), sizeof(fx::Descriptor), d.size(), out);
+        const uint32_t rows = (uint32_t)d.size();
+        if (rows_word) std::fwrite(&rows, 4, 1, out);
+        std::fwrite(d.data(), sizeof(fx::Descriptor), rows, out);
       };
       uint32_t flags_or = 0;
       if (node && csr) throw std::runtime_error("--csr goes with the batcher, not --node");

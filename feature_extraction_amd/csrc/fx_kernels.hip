@@ -4085,7 +4085,8 @@ __device__ __forceinline__ void offsets_body(const FxDevParams &P, const FxBuffe
     if (b < batch) {
       const uint32_t off = run + ex;
       B.kp_offset[b] = off;
-      if (off + c > P.max_total_kp) atomicOr(&B.flags[b], FX_FLAG_TOTAL_KP_OVERFLOW);
+      // (flagged iff the pool holds fewer of its rows than it has keypoints: a scan without keypoints lost nothing)
+      if (c != 0u && off + c > P.max_total_kp) atomicOr(&B.flags[b], FX_FLAG_TOTAL_KP_OVERFLOW);
     }
     run += tot;
   }

@@ -40,7 +40,10 @@ namespace fx {
 
 struct MultiGpuOptions {
   uint32_t in_flight = 2;  // contexts (batches in flight) per device (2: 1.59 million scans/s on one MI355X, 1: 1.24, 3: 1.48 — the shared communicator orders the slots)
-  uint32_t block_keypoints = 0;  // keypoint rows of a rank's gathered block; 0 = 64 a scan of the rank's share (VLP-16 scenes have 54; a batch with more is cut and flagged FX_FLAG_KP_OVERFLOW)
+  // keypoint rows of a rank's gathered block; 0 = the rank contexts' max_total_keypoints after `limits` (64 a scan of the
+  // rank's share by default): the block then holds every keypoint whose descriptor row the rank holds, and cuts exactly where
+  // the rank's pool does.  A smaller block cuts there: the scans that lose keypoints carry FX_FLAG_KP_OVERFLOW in it.
+  uint32_t block_keypoints = 0;
   int gather_root = -1;    // >= 0: the table is gathered on that rank only (ncclGather; the other ranks' tables stay untouched); -1: on every rank (ncclAllGather)
   fx_limits limits{};      // non-zero fields override fx_limits_default(scans per rank, max_points)
   // SELF-TEST: the ranks' collective is replaced by a gather through host memory (every rank downloads its block, all ranks
@@ -96,7 +99,18 @@ class MultiGpu {
     if (FX_CHECK_ABI() != FX_OK) throw std::runtime_error(std::string("fx_check_abi: ") + fx_last_error());  // (this translation unit's fx.h against the library's)
     per_rank_ = (max_batch + G - 1) / G;
     if (gather_root_ >= (int)G) throw std::invalid_argument("fx::MultiGpu: gather_root is not a rank");
-    block_kp_ = opt.block_keypoints ? opt.block_keypoints : 64u * per_rank_;
+    fx_limits lim;  // (every slot of every rank: the same limits)
+    if (opt.sparse_limits)
+      fx_limits_sparse(&lim, per_rank_, max_points);
+    else
+      fx_limits_default(&lim, per_rank_, max_points);
+    {
+      const uint32_t *ov = reinterpret_cast<const uint32_t *>(&opt.limits);
+      uint32_t *dst = reinterpret_cast<uint32_t *>(&lim);
+      for (size_t i = 2; i < sizeof(fx_limits) / 4; ++i)  // (max_batch / max_points are the constructor's)
+        if (ov[i]) dst[i] = ov[i];
+    }
+    block_kp_ = opt.block_keypoints ? opt.block_keypoints : lim.max_total_keypoints;
     for (uint32_t r = 0; r < G; ++r) ranks_.emplace_back(new Rank());
     comms_.assign(G, nullptr);
     try {
@@ -108,15 +122,6 @@ class MultiGpu {
         hip(hipSetDevice(devices_[r]), "hipSetDevice");
         R.slots.resize(in_flight_);
         for (Slot &S : R.slots) {
-          fx_limits lim;
-          if (opt.sparse_limits)
-            fx_limits_sparse(&lim, per_rank_, max_points);
-          else
-            fx_limits_default(&lim, per_rank_, max_points);
-          const uint32_t *ov = reinterpret_cast<const uint32_t *>(&opt.limits);
-          uint32_t *dst = reinterpret_cast<uint32_t *>(&lim);
-          for (size_t i = 2; i < sizeof(fx_limits) / 4; ++i)  // (max_batch / max_points are the constructor's)
-            if (ov[i]) dst[i] = ov[i];
           if (fx_create(&params, &lim, devices_[r], &S.ctx) != FX_OK) throw std::runtime_error(std::string("fx_create: ") + fx_last_error());
           fx_set_batches_in_flight(S.ctx, in_flight_);  // (launch-policy hint: the slots of a device share its chip)
           hip(hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking), "hipStreamCreate");

@@ -3,6 +3,9 @@
 // per-rank results and prints scans/s with the inputs resident in device memory (--host-input: handed over as host
 // buffers).  On a 1-GPU box it runs with one rank: RCCL initialises and the collective runs.
 //   fx_multi_cli [--devices N] [--batch B] [--steps K] [--inflight F] [--default] [--host-input] [--selftest G] [--bad-scan I] [--root R]
+//                [--poles P] [--pool-keypoints M]
+// --poles P: scenes of P poles instead of the generator's default (256: some 150 keypoints a scan, beyond the default pool's 64).
+// --pool-keypoints M: the rank contexts' max_total_keypoints (Options::limits), and with it the gathered block's rows.
 // --root R: the table is gathered on rank R only (ncclGather) instead of on every rank (ncclAllGather).
 // --selftest G: G ranks on device 0 with the collective replaced by a gather through host memory (fx::MultiGpuOptions::
 // host_gather: RCCL refuses the same device twice) — worker threads, tickets, the error barrier, slots in flight and
@@ -30,6 +33,7 @@ int main(int argc, char **argv) {
     uint32_t batch = 256, steps = 20, in_flight = 4;
     bool launch = true, host_input = false;
     int selftest = 0, bad_scan = -1, root = -1;
+    uint32_t poles = 0, pool_keypoints = 0;
     for (int i = 1; i < argc; ++i) {
       if (!std::strcmp(argv[i], "--devices") && i + 1 < argc) want = std::atoi(argv[++i]);
       else if (!std::strcmp(argv[i], "--batch") && i + 1 < argc) batch = (uint32_t)std::atoi(argv[++i]);
@@ -40,6 +44,8 @@ int main(int argc, char **argv) {
       else if (!std::strcmp(argv[i], "--selftest") && i + 1 < argc) selftest = std::atoi(argv[++i]);
       else if (!std::strcmp(argv[i], "--bad-scan") && i + 1 < argc) bad_scan = std::atoi(argv[++i]);
       else if (!std::strcmp(argv[i], "--root") && i + 1 < argc) root = std::atoi(argv[++i]);
+      else if (!std::strcmp(argv[i], "--poles") && i + 1 < argc) poles = (uint32_t)std::atoi(argv[++i]);
+      else if (!std::strcmp(argv[i], "--pool-keypoints") && i + 1 < argc) pool_keypoints = (uint32_t)std::atoi(argv[++i]);
     }
     if (want < 1 || want > n_dev) want = n_dev;
     std::vector<int> devices;
@@ -54,6 +60,7 @@ int main(int argc, char **argv) {
     std::vector<fx_scan_desc> scans(batch);
     for (uint32_t b = 0; b < batch; ++b) {
       fx_synth_cfg_vlp16(&cfg, 1000 + b);
+      if (poles) cfg.n_poles = poles;
       fx_synth_scan(&cfg, &host[(size_t)b * N * 4], N);
       scans[b] = fx_scan_desc{&host[(size_t)b * N * 4], N, 16, 0.02, -0.015};
     }
@@ -62,6 +69,7 @@ int main(int argc, char **argv) {
     opt.sparse_limits = true;  // (the stream is synthetic VLP-16 scans)
     opt.host_gather = selftest > 0;
     opt.gather_root = root;
+    opt.limits.max_total_keypoints = pool_keypoints;  // (0: the default)
     fx::MultiGpu multi(p, devices, batch, N, opt);
     const uint32_t G = multi.world();
     std::printf("fx_multi_cli: %d device(s) visible, %u rank(s), %u scans per batch (%u per rank), %u batches in flight per device, "
@@ -72,19 +80,29 @@ int main(int argc, char **argv) {
     std::vector<float> table;
     std::vector<fx_batch_view> views;
     multi.process(scans.data(), batch, FX_OUT_HOST, &table, &views);
-    uint64_t kp_total = 0;
+    // the block rule (include/fx.h fx_pack_keypoint_block): scan b keeps the keypoints of its rank-local offsets clipped to the
+    // block's rows, in order, and carries the rank's flags plus FX_FLAG_KP_OVERFLOW when it keeps fewer than it has
+    uint64_t kp_total = 0, kp_held = 0;
+    uint32_t scans_cut = 0, scans_flagged = 0;
     for (uint32_t b = 0; b < batch; ++b) {
       const uint32_t r = fx::owner_of(b, batch, G);
       const uint32_t local = (uint32_t)(b - fx::shard_range(batch, G, r).first);
       const fx_batch_view &v = views[r];
       const fx::MultiGpu::ScanKeypoints rec = multi.keypoints(table, b, batch);
-      const uint32_t K = v.h_n_keypoints[local];
-      if (rec.n != K || rec.flags != v.h_flags[local])
-        throw std::runtime_error("gathered keypoint count / flags differ from the producing rank's");
-      if (std::memcmp(rec.kp, v.h_keypoints + (size_t)local * v.max_keypoints * 4, (size_t)K * 16) != 0)
+      const uint32_t K = v.h_n_keypoints[local], M = multi.block_keypoints();
+      const uint32_t o0 = v.h_kp_offset[local] < M ? v.h_kp_offset[local] : M;
+      const uint32_t o1 = v.h_kp_offset[local] + K < M ? v.h_kp_offset[local] + K : M;
+      const uint32_t held = o1 - o0, want_flags = v.h_flags[local] | (held < K ? FX_FLAG_KP_OVERFLOW : 0u);
+      if (rec.n != held || rec.flags != want_flags)
+        throw std::runtime_error("gathered keypoint count / flags differ from the producing rank's under the block rule");
+      if (std::memcmp(rec.kp, v.h_keypoints + (size_t)local * v.max_keypoints * 4, (size_t)held * 16) != 0)
         throw std::runtime_error("gathered keypoints differ from the producing rank's");
-      kp_total += K;
+      kp_total += K, kp_held += held;
+      scans_cut += held < K ? 1u : 0u;
+      scans_flagged += rec.flags ? 1u : 0u;
     }
+    std::printf("fx_multi_cli: block check: %llu of %llu keypoints held, %u scans cut, %u scans flagged\n", (unsigned long long)kp_held,
+                (unsigned long long)kp_total, scans_cut, scans_flagged);
     {  // every rank holds the same table
       fx::MultiGpu::Ticket t = multi.submit(scans.data(), batch, 0);
       std::vector<float> t0;

@@ -49,8 +49,25 @@ typedef enum fx_status {
 #define FX_FLAG_KP_OVERFLOW 0x4u        /* more keypoints than limits.max_keypoints */
 #define FX_FLAG_NBR_OVERFLOW 0x8u       /* the dense descriptor tier's pools are exhausted (limits.max_dense_points; the scan's
                                          * overflow region holds max_points entries): the keypoint's descriptor is NaN */
-#define FX_FLAG_TOTAL_KP_OVERFLOW 0x10u /* batch-wide keypoint pool exhausted */
-#define FX_FLAG_KPC_OVERFLOW 0x20u      /* keypoint_cloud exceeded its pool */
+#define FX_FLAG_TOTAL_KP_OVERFLOW 0x10u /* batch-wide keypoint pool exhausted: the pool holds fewer of the scan's descriptor rows
+                                         * than it has keypoints (see "Cuts" below) */
+#define FX_FLAG_KPC_OVERFLOW 0x20u      /* keypoint_cloud exceeded its pool: the scan's n_kpc is 0 */
+
+/* Cuts (tests/test_gpu_keypoint_cuts.py asserts every clause).
+ * - Per scan, max_keypoints: n_keypoints = min(clusters, max_keypoints); the scan keeps its FIRST max_keypoints keypoints in
+ *   the reference's order, with the reference's descriptors for them (the 3DSC random ordinals count earlier keypoints only),
+ *   and candidates merged into a dropped keypoint report -1.  FX_FLAG_KP_OVERFLOW iff one was dropped.
+ * - Per scan, max_kpc_points: a keypoint_cloud that does not fit is not delivered (n_kpc = 0, FX_FLAG_KPC_OVERFLOW); keypoints
+ *   and descriptors are unaffected.
+ * - Per batch, max_total_keypoints (the descriptor pool of M rows): n_keypoints and kp_offset are NOT clamped to the pool
+ *   (kp_offset[B] may exceed M), and keypoints, ~cloud, ~keypoint_cloud and the membership arrays are complete for every
+ *   scan — they do not live in the pool.  Descriptor rows exist for pool rows [0, M) only: scan b holds rows
+ *   [min(kp_offset[b], M), min(kp_offset[b] + n_keypoints[b], M)), the descriptors of its LEADING keypoints, equal to an uncut
+ *   run's.  total_keypoints = min(kp_offset[B], M).  FX_FLAG_TOTAL_KP_OVERFLOW is set exactly on the scans that hold fewer
+ *   rows than they have keypoints (a scan without keypoints lost nothing and is not flagged, wherever it lies).
+ * - Every egress reports the held rows: FX_OUT_HOST copies total_keypoints rows, the CSR block has total_keypoints rows,
+ *   fx_pack_features writes min(total_keypoints, capacity) records; fx_pack_keypoint_records and fx_pack_keypoint_block cut
+ *   keypoints at their own capacity (see there), whatever the pool held. */
 #define FX_FLAG_INTERNAL 0x40u          /* a self-check of the library failed for this scan (the sliced streaming pass's two
                                            counts of a slice's survivors disagree): its results are not to be trusted — a bug */
 

@@ -136,3 +136,71 @@ def test_a_scan_beyond_the_lds_tiers_through_the_cpp_hosts(fxlib, oracle, tmp_pa
         assert desc.shape == o["descriptors"].shape
         assert np.abs(np.where(np.isnan(o["descriptors"]), 0, desc) - np.where(np.isnan(o["descriptors"]), 0, o["descriptors"])).max(initial=0.0) <= util.DESC_TOL
     assert len(got[(0, 2)][1]) == ora[id(big)]["n_keypoints"]
+
+
+def _read_rows(path):
+    """OUT of fx_batcher_cli --rows: the held-row count before each scan's dense rows."""
+    raw = open(path, "rb").read()
+    pos, out = 0, {}
+    while pos < len(raw):
+        sensor, seq, flags, K = struct.unpack_from("<4I", raw, pos)
+        pos += 16
+        kp = np.frombuffer(raw, np.float32, K * 4, pos).reshape(K, 4)
+        pos += K * 16
+        rows, = struct.unpack_from("<I", raw, pos)
+        pos += 4
+        desc = np.frombuffer(raw, np.float32, rows * capi.FX_DESC_FLOATS, pos).reshape(rows, capi.FX_DESC_FLOATS)
+        pos += rows * capi.FX_DESC_FLOATS * 4
+        out[(sensor, seq)] = (flags, kp, desc)
+    return out
+
+
+def _read_csr(path):
+    raw = open(path, "rb").read()
+    pos, out = 0, {}
+    while pos < len(raw):
+        sensor, seq, flags, K = struct.unpack_from("<4I", raw, pos)
+        pos += 16
+        kp = np.frombuffer(raw, np.float32, K * 4, pos).reshape(K, 4)
+        pos += K * 16
+        rows, nnz = struct.unpack_from("<2I", raw, pos)
+        pos += 8
+        rp = np.frombuffer(raw, np.uint32, rows + 1, pos)
+        pos += 4 * (rows + 1)
+        col = np.frombuffer(raw, np.uint32, nnz, pos)
+        pos += 4 * nnz
+        val = np.frombuffer(raw, np.float32, nnz, pos)
+        pos += 4 * nnz
+        out[(sensor, seq)] = (flags, kp, capi.dense_from_csr(rp, col, val, rows))
+    return out
+
+
+@pytest.mark.parametrize("mode", ["dense", "csr"])
+def test_batches_cut_at_the_pool_deliver_the_leading_rows(fxlib, oracle, tmp_path, mode):
+    """Batches of more than 64 scans get the library's default pool (64 rows a scan); scans of 256 poles have some 150
+    keypoints, so a burst fills batches past it.  Every scan keeps all its keypoints; a scan the pool cut carries
+    FX_FLAG_TOTAL_KP_OVERFLOW and its LEADING rows — the oracle's rows of its first keypoints — dense or CSR alike; every
+    other scan has all its rows."""
+    exe = build.build_batcher()
+    out = tmp_path / f"cut_{mode}.bin"
+    n = 130
+    r = subprocess.run([exe, "--sensors", "1", "--burst", str(n), "--poles", "256", "--max-batch", "65", "--out", str(out)]
+                       + (["--csr"] if mode == "csr" else ["--rows"]), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+    print(r.stdout.strip())
+    got = (_read_rows if mode == "dense" else _read_csr)(out)
+    assert len(got) == n
+    p = capi.params("launch")
+    cut = 0
+    for (s, q), (flags, kp, desc) in sorted(got.items()):
+        ora = oracle.run(p, capi.synth_scan(capi.synth_cfg(1000 + q, n_poles=256)), roll=0.02, pitch=-0.015)
+        K = len(ora["keypoints"])
+        util.assert_bit_equal(kp, ora["keypoints"], f"scan {q} keypoints")
+        rows = len(desc)
+        assert flags in (0, 0x10), (q, hex(flags))
+        assert (rows == K) == (flags == 0) and rows <= K, (q, rows, K, hex(flags))
+        o = ora["descriptors"][:rows]
+        assert desc.shape == o.shape and (np.isnan(desc) == np.isnan(o)).all(), q
+        assert np.abs(np.where(np.isnan(o), 0, desc) - np.where(np.isnan(o), 0, o)).max(initial=0.0) <= util.DESC_TOL, q
+        cut += rows < K
+    assert cut > 0, "no batch reached the pool's end: the burst did not fill a batch"
