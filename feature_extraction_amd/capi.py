@@ -91,6 +91,27 @@ class FxDescriptorCsrView(C.Structure):
                 ("d_row_ptr", C.c_void_p), ("d_col", C.c_void_p), ("d_val", C.c_void_p)]
 
 
+class FxMatchPair(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("q_row0", "q_rows", "t_row0", "t_rows")]
+
+
+class FxMatchOptions(C.Structure):
+    _fields_ = [("azimuth_shifts", C.c_uint32), ("max_dist2", C.c_float), ("max_ratio", C.c_float), ("mutual", C.c_uint32)]
+
+
+class FxMatch(C.Structure):
+    _fields_ = [("train_row", C.c_int32), ("shift", C.c_uint32), ("dist2", C.c_float), ("second_row", C.c_int32),
+                ("dist2_second", C.c_float), ("flags", C.c_uint32), ("pair", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+FX_MATCH_ACCEPTED, FX_MATCH_MUTUAL = 0x1, 0x2
+FX_MATCH_NO_PAIR = 0xffffffff
+FX_MATCH_SECTOR = 165  # bins of one azimuth sector: a rotation by s sectors shifts the bin index by 165 s
+# fx_match as a numpy record (match_records)
+MATCH_DTYPE = np.dtype([("train_row", "<i4"), ("shift", "<u4"), ("dist2", "<f4"), ("second_row", "<i4"), ("dist2_second", "<f4"),
+                        ("flags", "<u4"), ("pair", "<u4"), ("reserved", "<u4")])
+
+
 class FxTimings(C.Structure):
     _fields_ = [("ms", C.c_float * FX_N_STAGES), ("total_ms", C.c_float), ("k_prep_exec_ms", C.c_float)]
 
@@ -112,6 +133,7 @@ EXPORTS = ("fx_version", "fx_check_abi", "fx_status_str", "fx_last_error", "fx_p
            "fx_limits_default", "fx_limits_sparse", "fx_create", "fx_destroy", "fx_set_stream", "fx_get_stream", "fx_set_graph_batch", "fx_set_batches_in_flight", "fx_set_profiling", "fx_set_profiling_stages", "fx_get_timings",
            "fx_get_stage_bytes", "fx_get_limits", "fx_process_batch", "fx_synchronize", "fx_pack_features", "fx_pack_keypoint_records", "fx_keypoint_block_bytes", "fx_pack_keypoint_block",
            "fx_descriptor_csr_bytes", "fx_pack_descriptors_csr", "fx_get_descriptors_csr", "fx_set_descriptor_csr_capacity",
+           "fx_match_options_default", "fx_match_descriptors_csr",
            "fx_rotation_from_roll_pitch", "fx_sc3d_tables", "fx_sc3d_xaxis", "fx_synth_cfg_vlp16",
            "fx_synth_scan", "fx_unpack_pointcloud2", "fx_pack_pointxyzi")
 # the header's FX_TEST_HOOKS section: exported by lib/libfx_hip_test.so only
@@ -213,6 +235,10 @@ def load():
     lib.fx_pack_descriptors_csr.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
     lib.fx_get_descriptors_csr.argtypes = [C.c_void_p, C.POINTER(FxDescriptorCsrView)]
     lib.fx_set_descriptor_csr_capacity.argtypes = [C.c_void_p, C.c_uint32]
+    lib.fx_match_options_default.argtypes = [C.POINTER(FxMatchOptions)]
+    lib.fx_match_options_default.restype = None
+    lib.fx_match_descriptors_csr.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
+                                             C.POINTER(FxMatchPair), C.c_uint32, C.POINTER(FxMatchOptions), C.c_void_p]
     lib.fx_rotation_from_roll_pitch.argtypes = [C.c_double, C.c_double, _F32P]
     lib.fx_rotation_from_roll_pitch.restype = None
     lib.fx_sc3d_tables.argtypes = [C.c_double, _F32P, _F32P, _F32P, _F32P]
@@ -339,6 +365,98 @@ def csr_parse(block, max_rows, capacity):
     return {"rows": rows, "nnz_stored": nnz_stored, "nnz_needed": nnz_needed, "rows_stored": rows_stored,
             "row_ptr": b[rp:rp + 4 * (n + 1)].view(np.uint32).copy(), "row_ptr_all": b[rp:rp + 4 * (max_rows + 1)].view(np.uint32).copy(),
             "col": b[col:col + 4 * nnz_stored].view(np.uint32).copy(), "val": b[val:val + 4 * nnz_stored].view(np.float32).copy()}
+
+
+# ---- matching descriptor rows across azimuth shifts (include/fx.h fx_match_descriptors_csr)
+def pairs_consecutive(kp_offset):
+    """Scan b + 1's rows as query against scan b's as train, for the scans of one batch: [(q_row0, q_rows, t_row0, t_rows)]."""
+    off = [int(x) for x in kp_offset]
+    return [(off[b + 1], off[b + 2] - off[b + 1], off[b], off[b + 1] - off[b]) for b in range(len(off) - 2)]
+
+
+def match_epsilon(d2, nq2, nt2):
+    """The error bound of a reported dist2 (include/fx.h): 2^-23 d2 + 2^-40 (|q|^2 + |t|^2)."""
+    return 2.0 ** -23 * d2 + 2.0 ** -40 * (nq2 + nt2)
+
+
+def match_records(out):
+    """A host copy of fx_match_descriptors_csr's output (a torch int32 tensor [n, 8], or any array of n * 32 bytes) as a
+    structured numpy array of MATCH_DTYPE records."""
+    if hasattr(out, "detach"):
+        out = out.detach().cpu().numpy()
+    return np.ascontiguousarray(out).view(np.uint8).reshape(-1).view(MATCH_DTYPE).copy()
+
+
+def match_reference(rows_q, rows_t, pairs, shifts=12, max_dist2=np.inf, max_ratio=1.0, mutual=False):
+    """The matching rule of include/fx.h stated in numpy on dense [n, 1989] float32 rows.  d2(q, t, s) = sum over the 1980 bins of
+    (q[c] - t[(c + 165 s) mod 1980])^2, formed directly in float64 term by term (no |q|^2 + |t|^2 - 2 q.t): where q[c] is 0 the
+    term is t^2, summed as such.  Returns a dict: "rec" (MATCH_DTYPE [n_q], what the library writes), "d2" (per pair the float64
+    array [q rows, t rows, shifts], NaN for rows that hold a NaN), "nq2" / "nt2" (|row|^2 of the bins, float64) and "ranges"
+    (per pair the clipped (q0, q1, t0, t1))."""
+    rows_q = np.ascontiguousarray(rows_q, dtype=np.float32).reshape(-1, FX_DESC_FLOATS)
+    rows_t = np.ascontiguousarray(rows_t, dtype=np.float32).reshape(-1, FX_DESC_FLOATS)
+    nq, nt, B = len(rows_q), len(rows_t), FX_DESC_BINS
+    Q, T = rows_q[:, :B].astype(np.float64), rows_t[:, :B].astype(np.float64)
+    q_nan, t_nan = np.isnan(rows_q).any(axis=1), np.isnan(rows_t).any(axis=1)
+    rec = np.zeros(nq, MATCH_DTYPE)
+    rec["train_row"] = rec["second_row"] = -1
+    rec["dist2"] = rec["dist2_second"] = np.inf
+    rec["pair"] = FX_MATCH_NO_PAIR
+    ratio2 = np.float32(max_ratio) * np.float32(max_ratio)
+    seen = np.zeros(nq, bool)
+    d2s, ranges = [], []
+    for p, (q0, qn, t0, tn) in enumerate(pairs):
+        q1, t1 = min(q0 + qn, nq), min(t0 + tn, nt)
+        q0, t0 = min(q0, q1), min(t0, t1)
+        if seen[q0:q1].any():
+            raise ValueError("query ranges of the pairs overlap")
+        seen[q0:q1] = True
+        ranges.append((q0, q1, t0, t1))
+        d2 = np.full((q1 - q0, t1 - t0, shifts), np.nan)
+        qi, ti = np.flatnonzero(~q_nan[q0:q1]), np.flatnonzero(~t_nan[t0:t1])
+        if len(qi) and len(ti):
+            Qp, Tp = Q[q0:q1][qi], T[t0:t1][ti]
+            zero = (Qp == 0).astype(np.float64)
+            for s in range(shifts):
+                Ts = np.roll(Tp, -FX_MATCH_SECTOR * s, axis=1)  # Ts[c] = t[(c + 165 s) mod 1980]
+                part = (Ts * Ts) @ zero.T  # [t, q]: the terms where q[c] is 0, each t^2
+                for k in range(len(qi)):
+                    c = np.flatnonzero(Qp[k])
+                    part[:, k] += ((Qp[k, c][None, :] - Ts[:, c]) ** 2).sum(axis=1)
+                d2[np.ix_(qi, ti, [s])] = part.T[:, :, None]
+        d2s.append(d2)
+        rec["pair"][q0:q1] = p
+        f32 = d2.astype(np.float32)  # (one rounding, as the library's; comparisons are on the fp32 values)
+        best_t = np.full((q1 - q0, t1 - t0), np.inf, np.float32)  # per train row: min over shifts, the lowest shift on ties
+        best_s = np.zeros((q1 - q0, t1 - t0), np.uint32)
+        valid = ~np.isnan(d2[:, :, 0]) if d2.size else np.zeros(d2.shape[:2], bool)
+        if d2.size:
+            f = np.where(np.isnan(f32), np.float32(np.inf), f32)
+            best_s = f.argmin(axis=2).astype(np.uint32)
+            best_t = f.min(axis=2)
+        for i in range(q1 - q0):
+            cand = np.flatnonzero(valid[i])
+            if not len(cand):
+                continue
+            order = cand[np.lexsort((cand, best_t[i, cand]))]  # by (dist2, train row)
+            r = rec[q0 + i:q0 + i + 1]
+            j = order[0]
+            r["train_row"], r["shift"], r["dist2"] = t0 + j, best_s[i, j], best_t[i, j]
+            if len(order) > 1:
+                r["second_row"], r["dist2_second"] = t0 + order[1], best_t[i, order[1]]
+            ok = bool(r["dist2"][0] <= np.float32(max_dist2))
+            if ok and np.float32(max_ratio) < 1:
+                with np.errstate(invalid="ignore"):
+                    ok = bool(r["dist2"][0] <= ratio2 * r["dist2_second"][0])
+            r["flags"] = FX_MATCH_ACCEPTED if ok else 0
+        if mutual:
+            for j in range(t1 - t0):
+                cand = np.flatnonzero(valid[:, j])
+                if len(cand):
+                    i = cand[np.lexsort((cand, best_t[cand, j]))][0]
+                    if rec["train_row"][q0 + i] == t0 + j:
+                        rec["flags"][q0 + i] |= FX_MATCH_MUTUAL
+    return {"rec": rec, "d2": d2s, "ranges": ranges, "nq2": (Q * Q).sum(axis=1), "nt2": (T * T).sum(axis=1)}
 
 
 def _np(ptr, shape, dtype):
@@ -474,6 +592,38 @@ class Context:
         t = torch.sparse_csr_tensor(buf[rp:rp + 4 * (n + 1)].view(torch.int32), buf[col:col + 4 * nnz].view(torch.int32),
                                     buf[val:val + 4 * nnz].view(torch.float32), size=(n, FX_DESC_FLOATS))
         return t, hdr
+
+    def match_descriptors(self, q, t, pairs, out=None, shifts=12, max_dist2=float("inf"), max_ratio=1.0, mutual=False):
+        """fx_match_descriptors_csr: q and t are CSR blocks as (torch.uint8 device buffer, max_rows, capacity) — what
+        descriptors_csr(buf, max_rows, capacity) filled; the same block twice matches scans inside one batch —, pairs a list of
+        (q_row0, q_rows, t_row0, t_rows) (pairs_consecutive).  Returns a device torch.int32 tensor [q_max_rows, 8], one fx_match
+        record a query row (match_records views a host copy as named fields); `out` reuses a tensor of that shape.
+        Stream-correct like descriptors_csr: the match runs on the context's stream after what the caller's current stream has
+        queued, and the caller's current stream waits for it."""
+        import torch
+        (qb, q_rows, q_cap), (tb, t_rows, t_cap) = q, t
+        dev = torch.device("cuda", self.device)
+        for b, r, cap in ((qb, q_rows, q_cap), (tb, t_rows, t_cap)):
+            nbytes = int(self.lib.fx_descriptor_csr_bytes(int(r), int(cap)))
+            if b.dtype != torch.uint8 or b.device != dev or b.numel() < nbytes or not b.is_contiguous() or b.data_ptr() % 16:
+                raise ValueError(f"a block must be a contiguous, 16-byte aligned torch.uint8 tensor of >= {nbytes} bytes on {dev}")
+        if out is None:
+            out = torch.empty((int(q_rows), 8), dtype=torch.int32, device=dev)
+        elif out.dtype != torch.int32 or out.device != dev or tuple(out.shape) != (int(q_rows), 8) or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous torch.int32 tensor [{int(q_rows)}, 8] on {dev}")
+        arr = (FxMatchPair * max(len(pairs), 1))()
+        for i, pr in enumerate(pairs):
+            arr[i].q_row0, arr[i].q_rows, arr[i].t_row0, arr[i].t_rows = (int(x) for x in pr)
+        opt = FxMatchOptions()
+        self.lib.fx_match_options_default(C.byref(opt))
+        opt.azimuth_shifts, opt.max_dist2, opt.max_ratio, opt.mutual = int(shifts), float(max_dist2), float(max_ratio), int(bool(mutual))
+        cur = torch.cuda.current_stream(dev)
+        ext = torch.cuda.ExternalStream(self.stream_ptr(), device=dev)
+        ext.wait_stream(cur)
+        check(self.lib.fx_match_descriptors_csr(self.handle, C.c_void_p(qb.data_ptr()), int(q_rows), int(q_cap), C.c_void_p(tb.data_ptr()),
+                                                int(t_rows), int(t_cap), arr, len(pairs), C.byref(opt), C.c_void_p(out.data_ptr())))
+        cur.wait_stream(ext)
+        return out
 
     def make_descs(self, ptrs, counts, stride_bytes=16, roll=0.0, pitch=0.0):
         n = len(ptrs)

@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <utility>
 #include <vector>
@@ -78,6 +79,8 @@ void fxk_rng_ord(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32
 size_t fxk_csr_bytes(uint32_t max_rows, uint32_t cap);
 hipError_t fxk_pack_csr(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, void *dst, uint32_t max_rows, uint32_t cap,
                         uint32_t grid, uint32_t full_rows);
+hipError_t fxk_match(hipStream_t s, const FxMatchArgs &A, uint32_t n_items, uint32_t mut_n, uint32_t shifts);
+uint32_t fxk_match_tile_rows(void);
 #ifdef FX_TEST_HOOKS
 void fxk_test_sort_replay(hipStream_t s, const uint32_t *sizes, uint32_t n_seq, uint32_t n, uint32_t *perm);
 void fxk_test_elevation(hipStream_t s, const float *xyz, uint32_t n, const double *tab, float *fast, uint8_t *ok, float *exact);
@@ -219,6 +222,12 @@ struct fx_ctx {
   bool csr_valid = false;        // the last batch was FX_OUT_HOST | FX_OUT_DESC_CSR (fx_get_descriptors_csr)
   uint32_t csr_rows = 0, csr_nnz = 0;
   uint32_t csr_full_rows = 0;    // test hook (FX_CSR_FULL_ROWS): every row through the whole-row path
+  // fx_match_descriptors_csr: one device buffer (the pairs and the work list, the blocks' row norms, the mutual table) and
+  // the pinned staging of its first part; both grow (never shrink) when a call needs more.  match_ev: the last call's copy
+  // out of the staging, which the next call waits for before it writes there
+  uint8_t *d_match = nullptr, *h_match = nullptr;
+  size_t match_dev_bytes = 0, match_host_bytes = 0;
+  hipEvent_t match_ev = nullptr;
 };
 
 namespace {
@@ -942,6 +951,9 @@ void fx_destroy(fx_ctx *c) {
   if (c->d_stage) (void)hipFree(c->d_stage);
   if (c->d_csr) (void)hipFree(c->d_csr);
   if (c->h_csr) (void)hipHostFree(c->h_csr);
+  if (c->d_match) (void)hipFree(c->d_match);
+  if (c->h_match) (void)hipHostFree(c->h_match);
+  if (c->match_ev) (void)hipEventDestroy(c->match_ev);
   for (int i = 0; i < kMetaSlots; ++i)
     if (c->meta_ev[i]) (void)hipEventDestroy(c->meta_ev[i]);
   for (hipEvent_t e : c->ev_ring) (void)hipEventDestroy(e);
@@ -1521,6 +1533,97 @@ fx_status fx_set_descriptor_csr_capacity(fx_ctx *c, uint32_t entries) {
   if (!c) return fail(FX_ERR_INVALID_ARG, "null ctx");
   c->csr_cap_want = entries;
   c->csr_resize = c->d_csr != nullptr;
+  return FX_OK;
+}
+
+void fx_match_options_default(fx_match_options *o) {
+  if (!o) return;
+  o->azimuth_shifts = 12u;
+  o->max_dist2 = std::numeric_limits<float>::infinity();
+  o->max_ratio = 1.0f;
+  o->mutual = 0u;
+}
+
+fx_status fx_match_descriptors_csr(fx_ctx *c, const void *q_block, uint32_t q_max_rows, uint32_t q_cap, const void *t_block, uint32_t t_max_rows,
+                                   uint32_t t_cap, const fx_match_pair *pairs, uint32_t n_pairs, const fx_match_options *opt, fx_match *out) {
+  if (!c || !q_block || !t_block || (n_pairs && !pairs) || (q_max_rows && !out)) return fail(FX_ERR_INVALID_ARG, "null argument");
+  if (((uintptr_t)q_block % 16) != 0 || ((uintptr_t)t_block % 16) != 0 || ((uintptr_t)out % 4) != 0)
+    return fail(FX_ERR_INVALID_ARG, "blocks must be 16-byte aligned");
+  fx_match_options o;
+  fx_match_options_default(&o);
+  if (opt) o = *opt;
+  if (o.azimuth_shifts != 12u && o.azimuth_shifts != 1u) return fail(FX_ERR_INVALID_ARG, "azimuth_shifts must be 12 or 1");
+  if (o.max_dist2 != o.max_dist2 || o.max_ratio != o.max_ratio) return fail(FX_ERR_INVALID_ARG, "NaN threshold");
+  {  // the query ranges must be disjoint: one record a query row
+    std::vector<std::pair<uint64_t, uint64_t>> r;
+    for (uint32_t p = 0; p < n_pairs; ++p)
+      if (pairs[p].q_rows) r.emplace_back((uint64_t)pairs[p].q_row0, (uint64_t)pairs[p].q_row0 + pairs[p].q_rows);
+    std::sort(r.begin(), r.end());
+    for (size_t i = 1; i < r.size(); ++i)
+      if (r[i].first < r[i - 1].second)
+        return fail(FX_ERR_INVALID_ARG, "query ranges of the pairs overlap at row " + std::to_string(r[i].first));
+  }
+  FX_HIP(hipSetDevice(c->device));
+  // work list (pair, tile of query rows) from the ranges the layouts admit — the kernel clips them to rows_stored —, and each
+  // pair's slots in the mutual table
+  const uint32_t tile = fxk_match_tile_rows();
+  uint64_t n_items = 0, mut_n = 0;
+  for (uint32_t p = 0; p < n_pairs; ++p) {
+    const uint32_t q0 = std::min(pairs[p].q_row0, q_max_rows), t0 = std::min(pairs[p].t_row0, t_max_rows);
+    n_items += (std::min(pairs[p].q_rows, q_max_rows - q0) + tile - 1u) / tile;
+    if (o.mutual) mut_n += std::min(pairs[p].t_rows, t_max_rows - t0);
+  }
+  if (n_items > 0x7fffffffull || mut_n > 0xffffffffull) return fail(FX_ERR_TOO_LARGE, "too many query tiles / train rows in the pairs");
+  const bool same = q_block == t_block && q_max_rows == t_max_rows && q_cap == t_cap;
+  const size_t staged = (size_t)n_pairs * sizeof(FxMatchPairDev) + (size_t)n_items * sizeof(uint2);
+  const size_t off_qn = (staged + 15u) & ~(size_t)15, off_tn = off_qn + (size_t)q_max_rows * 8u;
+  const size_t off_mut = same ? off_tn : off_tn + (size_t)t_max_rows * 8u, need = off_mut + (size_t)mut_n * 8u + 16u;
+  if (!c->match_ev) FX_HIP(hipEventCreateWithFlags(&c->match_ev, hipEventDisableTiming));
+  if (need > c->match_dev_bytes) {
+    if (c->d_match) {
+      FX_HIP(hipStreamSynchronize(c->stream));
+      FX_HIP(hipFree(c->d_match));
+      c->d_match = nullptr, c->match_dev_bytes = 0;
+    }
+    const size_t bytes = std::max(need, 2u * c->match_dev_bytes);
+    void *q = nullptr;
+    hipError_t e = hipMalloc(&q, bytes);
+    if (e != hipSuccess) return fail(FX_ERR_OOM, std::string("match buffer hipMalloc(") + std::to_string(bytes) + "): " + hipGetErrorString(e));
+    c->d_match = (uint8_t *)q, c->match_dev_bytes = bytes;
+  }
+  FX_HIP(hipEventSynchronize(c->match_ev));  // (the last call's copy out of the staging; done at once when none was recorded)
+  if (staged > c->match_host_bytes) {
+    if (c->h_match) FX_HIP(hipHostFree(c->h_match));
+    c->h_match = nullptr, c->match_host_bytes = 0;
+    void *q = nullptr;
+    hipError_t e = hipHostMalloc(&q, 2u * staged, hipHostMallocDefault);
+    if (e != hipSuccess) return fail(FX_ERR_OOM, std::string("match staging hipHostMalloc(") + std::to_string(2u * staged) + "): " + hipGetErrorString(e));
+    c->h_match = (uint8_t *)q, c->match_host_bytes = 2u * staged;
+  }
+  if (staged) {
+    FxMatchPairDev *hp = (FxMatchPairDev *)c->h_match;
+    uint2 *hi = (uint2 *)(c->h_match + (size_t)n_pairs * sizeof(FxMatchPairDev));
+    uint64_t m = 0;
+    for (uint32_t p = 0; p < n_pairs; ++p) {
+      const uint32_t q0 = std::min(pairs[p].q_row0, q_max_rows), t0 = std::min(pairs[p].t_row0, t_max_rows);
+      hp[p] = FxMatchPairDev{pairs[p].q_row0, pairs[p].q_rows, pairs[p].t_row0, pairs[p].t_rows, (uint32_t)m, {0u, 0u, 0u}};
+      if (o.mutual) m += std::min(pairs[p].t_rows, t_max_rows - t0);
+      const uint32_t tiles = (std::min(pairs[p].q_rows, q_max_rows - q0) + tile - 1u) / tile;
+      for (uint32_t k = 0; k < tiles; ++k) *hi++ = make_uint2(p, k);
+    }
+    FX_HIP(hipMemcpyAsync(c->d_match, c->h_match, staged, hipMemcpyHostToDevice, c->stream));
+    FX_HIP(hipEventRecord(c->match_ev, c->stream));
+  }
+  FxMatchArgs A{};
+  A.q_block = (const uint32_t *)q_block, A.t_block = (const uint32_t *)t_block;
+  A.q_max_rows = q_max_rows, A.q_cap = q_cap, A.t_max_rows = t_max_rows, A.t_cap = t_cap;
+  A.pairs = (const FxMatchPairDev *)c->d_match;
+  A.items = (const uint2 *)(c->d_match + (size_t)n_pairs * sizeof(FxMatchPairDev));
+  A.q_norm = (const double *)(c->d_match + off_qn), A.t_norm = same ? A.q_norm : (const double *)(c->d_match + off_tn);
+  A.mut = (unsigned long long *)(c->d_match + off_mut);
+  A.out = out;
+  A.max_dist2 = o.max_dist2, A.max_ratio = o.max_ratio, A.mutual = o.mutual ? 1u : 0u;
+  FX_HIP(fxk_match(c->stream, A, (uint32_t)n_items, (uint32_t)mut_n, o.azimuth_shifts));
   return FX_OK;
 }
 

@@ -69,6 +69,23 @@ struct FxScTables {
 // each rounded up to 16 bytes; header 16 B, then row_ptr, col, val
 __host__ __device__ inline size_t csr_rp_words(uint32_t max_rows) { return ((size_t)max_rows + 1u + 3u) & ~(size_t)3; }
 __host__ __device__ inline size_t csr_cap_words(uint32_t cap) { return ((size_t)cap + 3u) & ~(size_t)3; }
+// fx_match_descriptors_csr (csrc/fx_match.hip): one pair of row ranges as the kernels see it, and a launch's arguments.
+struct FxMatchPairDev {
+  uint32_t q_row0, q_rows, t_row0, t_rows;
+  uint32_t mut_off;  // first slot of the pair's train rows in the mutual table
+  uint32_t pad_[3];
+};
+struct FxMatchArgs {
+  const uint32_t *q_block, *t_block;  // CSR blocks (include/fx.h fx_descriptor_csr_bytes)
+  uint32_t q_max_rows, q_cap, t_max_rows, t_cap;
+  const FxMatchPairDev *pairs;
+  const uint2 *items;          // work list: (pair, tile of query rows)
+  const double *q_norm, *t_norm;  // squared norm of each stored row's bins; NaN: the row stores a NaN
+  unsigned long long *mut;     // [sum of the pairs' train rows] (fp32 bits of dist2 << 32) | query row, atomic min
+  void *out;                   // fx_match [q_max_rows]
+  float max_dist2, max_ratio;
+  uint32_t mutual;
+};
 #define FX_N_HINTS 8      // tier_hint[]: 0 / 1 rings handed to the second run tier / the workgroup tier (largest XCD class), 2 big merges, 3 huge merges, 4 dense rows, 5 dense support points, 6 scans k_front handed to k_front_redo, 7 scans handed to the slow tier (k_slow)
 #define FX_CNT_QPOOL 32   // counters[32]: entries of the dense tier's query pool in use
 #define FX_CNT_LARGE2 16  // counters[16 + c]: rings of XCD class c the second run tier hands to the workgroup tier

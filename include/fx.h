@@ -360,6 +360,53 @@ fx_status fx_get_descriptors_csr(fx_ctx *ctx, fx_descriptor_csr_view *out);
  * FX_OUT_DESC_CSR batch; the block still grows when a batch needs more. */
 fx_status fx_set_descriptor_csr_capacity(fx_ctx *ctx, uint32_t entries);
 
+/* ---- Matching descriptor rows between scans across azimuth shifts ----
+ * PCL's 3DSC draws a random azimuth reference per keypoint (fx_sc3d_xaxis): two descriptors of the same pole differ by an
+ * unknown rotation of the 12 azimuth sectors.  A bin index is l*165 + k*15 + j with l the sector, so a rotation by s sectors
+ * is a cyclic shift of the column index by 165 s, and rows are matched by trying all 12 (Frome et al., ECCV 2004):
+ *   d2(q, t, s) = sum over c < 1980 of (q[c] - t[(c + 165 s) mod 1980])^2        (the 9 rf words are ignored)
+ * Both operands are CSR blocks exactly as fx_pack_descriptors_csr writes them ((max_rows, capacity) give the layout, the
+ * header gives rows_stored); q_block == t_block matches scans inside one batch.  pairs_host[p] matches the query rows
+ * [q_row0, q_row0 + q_rows) against the train rows [t_row0, t_row0 + t_rows); ranges are clipped to each block's
+ * rows_stored, a pair with an empty side is legal, and the QUERY ranges of the pairs must be disjoint (FX_ERR_INVALID_ARG
+ * otherwise, checked on the host).  Per query row, (train_row, shift, dist2) minimise d2 over the pair's train rows and the
+ * enabled shifts — ties to the lowest train row, then the lowest shift —, and (second_row, dist2_second) are the same minimum
+ * over the pair's train rows other than train_row.  Every one of the q_max_rows records is written: a row in no pair or
+ * clipped away gets train_row = -1, pair = 0xffffffff, dist2 = dist2_second = +inf, flags = 0.  A row that stores any NaN
+ * (an FX_FLAG_NBR_OVERFLOW row) never matches and is never matched: train_row = -1 as a query, skipped as a train row.  A
+ * row without stored words is an ordinary all-zero descriptor.
+ * Numerics: dist2 is within 2^-23 d2 + 2^-40 (|q|^2 + |t|^2) of the exact value (fp64 sums of the exact fp32 products, one
+ * rounding to fp32), never negative, exactly 0 for identical rows at shift 0, and the same bits from run to run and with
+ * any number of contexts in flight.
+ * Enqueued on the context's stream; needs no batch to have been processed.  pairs_host is copied before the call returns
+ * into a context-owned buffer that grows when a call needs more; nothing else is allocated in the steady state.  New in 0.7
+ * (added symbols only). */
+typedef struct fx_match_pair { uint32_t q_row0, q_rows, t_row0, t_rows; } fx_match_pair; /* row ranges in the two blocks */
+typedef struct fx_match_options {
+  uint32_t azimuth_shifts; /* 12 (default) or 1 (shift 0 only) */
+  float max_dist2;         /* accept only d2 <= this; +inf = off (default) */
+  float max_ratio;         /* accept only d2 <= max_ratio^2 * d2_second (fp32); >= 1 = off (default 1) */
+  uint32_t mutual;         /* 1: also compute FX_MATCH_MUTUAL; default 0 */
+} fx_match_options;
+#define FX_MATCH_ACCEPTED 0x1u /* a best match exists and passes max_dist2 and max_ratio */
+#define FX_MATCH_MUTUAL 0x2u   /* (options.mutual) the query row is, for its train_row, the minimiser of (dist2, query row) over
+                                * the pair's query rows and all shifts */
+typedef struct fx_match { /* 32 B, one per query row */
+  int32_t train_row;      /* row in the train block, -1: none */
+  uint32_t shift;         /* 0..11 */
+  float dist2;
+  int32_t second_row;     /* best OTHER train row of the pair, -1: none */
+  float dist2_second;     /* +inf when none */
+  uint32_t flags;         /* FX_MATCH_* */
+  uint32_t pair;          /* index into pairs, 0xffffffff when the row is in no pair */
+  uint32_t reserved;      /* 0 */
+} fx_match;
+void fx_match_options_default(fx_match_options *o);
+fx_status fx_match_descriptors_csr(fx_ctx *ctx, const void *q_block_device, uint32_t q_max_rows, uint32_t q_capacity,
+                                   const void *t_block_device, uint32_t t_max_rows, uint32_t t_capacity,
+                                   const fx_match_pair *pairs_host, uint32_t n_pairs, const fx_match_options *opt,
+                                   fx_match *out_device /* [q_max_rows] */);
+
 /* Rotation matrix of rotateCloud (ref: node.cpp:161-164): R = Ry(pitch)*Rx(roll)
  * through Eigen's AngleAxisf -> Quaternionf -> toRotationMatrix, all float. Host only. */
 void fx_rotation_from_roll_pitch(double roll, double pitch, float R[9]);
