@@ -5,6 +5,7 @@ classes above it (csrc/fx_node.hpp).  Loading fails loudly when the library is m
 there is no Python/CPU fallback for the hot path.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -112,6 +113,25 @@ MATCH_DTYPE = np.dtype([("train_row", "<i4"), ("shift", "<u4"), ("dist2", "<f4")
                         ("flags", "<u4"), ("pair", "<u4"), ("reserved", "<u4")])
 
 
+class FxRegisterOptions(C.Structure):
+    _fields_ = [("inlier_dist", C.c_float), ("min_baseline", C.c_float), ("hyp_corr", C.c_uint32), ("min_inliers", C.c_uint32),
+                ("require_flags", C.c_uint32)]
+
+
+class FxRegistration(C.Structure):
+    _fields_ = [("c", C.c_double), ("s", C.c_double), ("tx", C.c_double), ("ty", C.c_double), ("tz", C.c_double), ("rms", C.c_float),
+                ("n_corr", C.c_uint32), ("n_inliers", C.c_uint32), ("flags", C.c_uint32), ("hyp_a", C.c_uint32), ("hyp_b", C.c_uint32)]
+
+
+FX_REG_VALID, FX_REG_TRUNCATED, FX_REG_NO_HYPOTHESIS = 0x1, 0x2, 0x4
+FX_REG_MAX_CORR = 1024
+FX_REG_NO_ROW = 0xffffffff
+# fx_registration as a numpy record (register_records)
+REG_DTYPE = np.dtype([("c", "<f8"), ("s", "<f8"), ("tx", "<f8"), ("ty", "<f8"), ("tz", "<f8"), ("rms", "<f4"), ("n_corr", "<u4"),
+                      ("n_inliers", "<u4"), ("flags", "<u4"), ("hyp_a", "<u4"), ("hyp_b", "<u4")])
+REG_DEFAULTS = dict(inlier_dist=0.30, min_baseline=2.0, hyp_corr=64, min_inliers=3, require_flags=FX_MATCH_ACCEPTED)
+
+
 class FxTimings(C.Structure):
     _fields_ = [("ms", C.c_float * FX_N_STAGES), ("total_ms", C.c_float), ("k_prep_exec_ms", C.c_float)]
 
@@ -133,7 +153,7 @@ EXPORTS = ("fx_version", "fx_check_abi", "fx_status_str", "fx_last_error", "fx_p
            "fx_limits_default", "fx_limits_sparse", "fx_create", "fx_destroy", "fx_set_stream", "fx_get_stream", "fx_set_graph_batch", "fx_set_batches_in_flight", "fx_set_profiling", "fx_set_profiling_stages", "fx_get_timings",
            "fx_get_stage_bytes", "fx_get_limits", "fx_process_batch", "fx_synchronize", "fx_pack_features", "fx_pack_keypoint_records", "fx_keypoint_block_bytes", "fx_pack_keypoint_block",
            "fx_descriptor_csr_bytes", "fx_pack_descriptors_csr", "fx_get_descriptors_csr", "fx_set_descriptor_csr_capacity",
-           "fx_match_options_default", "fx_match_descriptors_csr",
+           "fx_match_options_default", "fx_match_descriptors_csr", "fx_register_options_default", "fx_register_matches",
            "fx_rotation_from_roll_pitch", "fx_sc3d_tables", "fx_sc3d_xaxis", "fx_synth_cfg_vlp16",
            "fx_synth_scan", "fx_unpack_pointcloud2", "fx_pack_pointxyzi")
 # the header's FX_TEST_HOOKS section: exported by lib/libfx_hip_test.so only
@@ -239,6 +259,10 @@ def load():
     lib.fx_match_options_default.restype = None
     lib.fx_match_descriptors_csr.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
                                              C.POINTER(FxMatchPair), C.c_uint32, C.POINTER(FxMatchOptions), C.c_void_p]
+    lib.fx_register_options_default.argtypes = [C.POINTER(FxRegisterOptions)]
+    lib.fx_register_options_default.restype = None
+    lib.fx_register_matches.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+                                        C.c_uint32, C.POINTER(FxMatchPair), C.c_uint32, C.POINTER(FxRegisterOptions), C.c_void_p, C.c_void_p]
     lib.fx_rotation_from_roll_pitch.argtypes = [C.c_double, C.c_double, _F32P]
     lib.fx_rotation_from_roll_pitch.restype = None
     lib.fx_sc3d_tables.argtypes = [C.c_double, _F32P, _F32P, _F32P, _F32P]
@@ -459,6 +483,192 @@ def match_reference(rows_q, rows_t, pairs, shifts=12, max_dist2=np.inf, max_rati
     return {"rec": rec, "d2": d2s, "ranges": ranges, "nq2": (Q * Q).sum(axis=1), "nt2": (T * T).sum(axis=1)}
 
 
+# ---- scan-to-scan rigid motion from the matches (include/fx.h fx_register_matches)
+def keypoint_block_layout(max_scans, max_total):
+    """(first float4 row of the keypoint area, rows of the whole block) of a compact keypoint block (fx_pack_keypoint_block)."""
+    k0 = 1 + (max_scans + 1 + 3) // 4 + (max_scans + 3) // 4
+    return k0, k0 + max_total
+
+
+def keypoint_block_parse(block, max_scans, max_total):
+    """A keypoint block (bytes / array, as fx_pack_keypoint_block writes it) as a dict: the header words, kp_offset[scans + 1],
+    flags[scans] and "rows", the [keypoints stored, 4] float32 (x, y, z, elevation) rows of the keypoint area."""
+    b = np.frombuffer(bytes(block), np.uint8) if not isinstance(block, np.ndarray) else np.ascontiguousarray(block).view(np.uint8).reshape(-1)
+    k0, n_rows = keypoint_block_layout(max_scans, max_total)
+    assert len(b) >= 16 * n_rows, (len(b), max_scans, max_total)
+    u = b[:16 * n_rows].view(np.uint32)
+    scans, stored, flags_or, mt = (int(x) for x in u[:4])
+    stored = min(stored, max_total)
+    nb = min(scans, max_scans)
+    f0 = 4 + 4 * ((max_scans + 1 + 3) // 4)
+    return {"scans": scans, "keypoints": stored, "flags_or": flags_or, "max_total": mt, "kp_offset": u[4:4 + nb + 1].copy(),
+            "flags": u[f0:f0 + nb].copy(), "rows": b[16 * k0:16 * (k0 + stored)].view(np.float32).reshape(-1, 4).copy()}
+
+
+def keypoint_block_from_rows(rows, max_scans=1, max_total=None):
+    """The keypoint block of one scan holding these [n, 3 or 4] rows (what fx_pack_keypoint_block would write for a batch of one
+    such scan), as a uint8 array; for tests and for registering keypoints that did not come from a batch.  Returns (block,
+    max_scans, max_total)."""
+    rows = np.asarray(rows, np.float32).reshape(len(rows), -1)
+    n = len(rows)
+    max_total = n if max_total is None else int(max_total)
+    assert n <= max_total and max_scans >= 1
+    k0, n_rows = keypoint_block_layout(max_scans, max_total)
+    blk = np.zeros((n_rows, 4), np.float32)
+    u = blk.view(np.uint32).reshape(-1)
+    u[:4] = (1, n, 0, max_total)
+    u[5:4 + 4 * ((max_scans + 1 + 3) // 4)] = n  # kp_offset[0] = 0, every later entry the total
+    blk[k0:k0 + n, :rows.shape[1]] = rows[:, :4]
+    return blk.view(np.uint8).reshape(-1), max_scans, max_total
+
+
+def register_records(out):
+    """A host copy of fx_register_matches's output (a torch tensor, or any array of n * 64 bytes) as a structured numpy array of
+    REG_DTYPE records."""
+    if hasattr(out, "detach"):
+        out = out.detach().cpu().numpy()
+    return np.ascontiguousarray(out).view(np.uint8).reshape(-1).view(REG_DTYPE).copy()
+
+
+def register_yaw(rec):
+    """atan2(s, c) of REG_DTYPE records: the rotation about z in radians (a host convenience, not a device output)."""
+    return np.arctan2(rec["s"], rec["c"])
+
+
+def _register_fit(P, idx, c, s):
+    """The refit of include/fx.h over the correspondences idx (ascending) of P = [(qx, qy, tx, ty)] as Python floats: sequential
+    sums, (c, s) kept when the centred sums vanish.  Returns (c, s, tx, ty)."""
+    sqx = sqy = stx = sty = 0.0
+    for i in idx:
+        qx, qy, tx, ty = P[i]
+        sqx += qx
+        sqy += qy
+        stx += tx
+        sty += ty
+    n = float(len(idx))
+    qcx, qcy, tcx, tcy = sqx / n, sqy / n, stx / n, sty / n
+    sdot = scrs = 0.0
+    for i in idx:
+        qx, qy, tx, ty = P[i]
+        ux, uy, vx, vy = qx - qcx, qy - qcy, tx - tcx, ty - tcy
+        sdot += (ux * vx + uy * vy)
+        scrs += (ux * vy - uy * vx)
+    nrm = math.sqrt(sdot * sdot + scrs * scrs)
+    if nrm > 0.0:
+        c, s = sdot / nrm, scrs / nrm
+    return c, s, tcx - (c * qcx - s * qcy), tcy - (s * qcx + c * qcy)
+
+
+def _register_r2(P, i, c, s, tx, ty):
+    qx, qy, t_x, t_y = P[i]
+    rx, ry = ((c * qx - s * qy) + tx) - t_x, ((s * qx + c * qy) + ty) - t_y
+    return rx * rx + ry * ry
+
+
+def register_reference(q_kp_rows, t_kp_rows, match_records, pairs, inlier_dist=0.30, min_baseline=2.0, hyp_corr=64, min_inliers=3,
+                       require_flags=FX_MATCH_ACCEPTED):
+    """The definition of fx_register_matches (include/fx.h) in numpy.  q_kp_rows / t_kp_rows: the [stored, >= 3] float32 keypoint
+    rows of the two blocks (keypoint_block_parse(...)["rows"]); match_records: MATCH_DTYPE [q_max_rows], taken as given (from
+    the GPU or from match_reference); pairs: [(q_row0, q_rows, t_row0, t_rows)].  The hypothesis stage runs in np.float32, one
+    ufunc an operation (no contraction); the refit in Python floats in the stated order.  Returns {"rec": REG_DTYPE [n_pairs],
+    "inlier": uint32 [q_max_rows], "corr": per pair the query rows of its correspondences}."""
+    f32 = np.float32
+    kq = np.ascontiguousarray(q_kp_rows, dtype=f32).reshape(len(q_kp_rows), -1)[:, :3]
+    kt = np.ascontiguousarray(t_kp_rows, dtype=f32).reshape(len(t_kp_rows), -1)[:, :3]
+    m = np.asarray(match_records)
+    n_rows = len(m)
+    rec = np.zeros(len(pairs), REG_DTYPE)
+    inlier = np.zeros(n_rows, np.uint32)
+    corrs = []
+    idist, mb = f32(inlier_dist), f32(min_baseline)
+    if not (np.isfinite(idist) and idist > 0 and np.isfinite(mb) and mb > 0 and 2 <= hyp_corr <= 128 and min_inliers >= 2):
+        raise ValueError("options outside what fx_register_matches accepts")
+    mb2, gate, id2 = mb * mb, f32(2) * idist, idist * idist
+    id2d = float(idist) * float(idist)
+    seen = np.zeros(n_rows, bool)
+    for p, (q0, qn, _t0, _tn) in enumerate(pairs):
+        q1 = min(q0 + qn, n_rows)
+        q0 = min(q0, q1)
+        if seen[q0:q1].any():
+            raise ValueError("query ranges of the pairs overlap")
+        seen[q0:q1] = True
+        i = np.arange(q0, min(q1, len(kq)), dtype=np.int64)
+        mi = m[i]
+        tr = mi["train_row"].astype(np.int64)
+        ok = (mi["pair"] == p) & (tr >= 0) & (tr < len(kt)) & ((mi["flags"] & np.uint32(require_flags)) == np.uint32(require_flags))
+        i, tr = i[ok], tr[ok]
+        fin = np.isfinite(kq[i]).all(axis=1) & np.isfinite(kt[tr]).all(axis=1)
+        i, tr = i[fin], tr[fin]
+        r = rec[p:p + 1]
+        flags = FX_REG_TRUNCATED if len(i) > FX_REG_MAX_CORR else 0
+        i, tr = i[:FX_REG_MAX_CORR], tr[:FX_REG_MAX_CORR]
+        n = len(i)
+        corrs.append(i.astype(np.uint32))
+        r["n_corr"] = n
+        P32 = np.concatenate([kq[i][:, :2], kt[tr][:, :2]], axis=1) if n else np.zeros((0, 4), f32)  # (qx, qy, tx, ty)
+        H = min(n, int(hyp_corr))
+        best_count, best = 0, None
+        if H >= 2:
+            d2b = m["dist2"][i].view(np.uint32)
+            pool = np.lexsort((i, d2b))[:H]  # by (dist2 bits, query row)
+            a, b = np.triu_indices(H, 1)     # lexicographic (a, b), a < b
+            A, B = P32[pool[a]], P32[pool[b]]
+            with np.errstate(all="ignore"):
+                dqx, dqy, dtx, dty = B[:, 0] - A[:, 0], B[:, 1] - A[:, 1], B[:, 2] - A[:, 2], B[:, 3] - A[:, 3]
+                lq2, lt2 = dqx * dqx + dqy * dqy, dtx * dtx + dty * dty
+                keep = (lq2 >= mb2) & (lt2 >= mb2)
+                keep &= ~(np.abs(np.sqrt(lq2) - np.sqrt(lt2)) > gate)
+                dot, crs = dqx * dtx + dqy * dty, dqx * dty - dqy * dtx
+                nrm = np.sqrt(dot * dot + crs * crs)
+                keep &= nrm > 0
+                c, s = dot / nrm, crs / nrm
+                mqx, mqy, mtx, mty = (A[:, 0] + B[:, 0]) * f32(0.5), (A[:, 1] + B[:, 1]) * f32(0.5), (A[:, 2] + B[:, 2]) * f32(0.5), (A[:, 3] + B[:, 3]) * f32(0.5)
+                tx, ty = mtx - (c * mqx - s * mqy), mty - (s * mqx + c * mqy)
+                ks = np.flatnonzero(keep)
+                counts = np.zeros(len(a), np.int64)
+                for lo in range(0, len(ks), 512):  # (chunks: [samples, n] float32 temporaries)
+                    k = ks[lo:lo + 512]
+                    ck, sk, txk, tyk = c[k, None], s[k, None], tx[k, None], ty[k, None]
+                    qx, qy, t_x, t_y = P32[None, :, 0], P32[None, :, 1], P32[None, :, 2], P32[None, :, 3]
+                    rx, ry = ((ck * qx - sk * qy) + txk) - t_x, ((sk * qx + ck * qy) + tyk) - t_y
+                    agree = rx * rx + ry * ry <= id2
+                    counts[k] = agree.sum(axis=1)
+                    assert rx.dtype == f32
+            counts[counts < 2] = 0  # (a sample with fewer than 2 agreeing is no hypothesis)
+            if counts.any():
+                w = int(np.argmax(counts))  # (the first maximum: the lowest (a, b))
+                best_count, best = int(counts[w]), w
+                with np.errstate(all="ignore"):
+                    rx = ((c[w] * P32[:, 0] - s[w] * P32[:, 1]) + tx[w]) - P32[:, 2]
+                    ry = ((s[w] * P32[:, 0] + c[w] * P32[:, 1]) + ty[w]) - P32[:, 3]
+                    I0 = [int(x) for x in np.flatnonzero(rx * rx + ry * ry <= id2)]
+                assert len(I0) == best_count
+        if best is None:
+            r["c"], r["rms"], r["flags"], r["hyp_a"], r["hyp_b"] = 1.0, np.inf, flags | FX_REG_NO_HYPOTHESIS, FX_REG_NO_ROW, FX_REG_NO_ROW
+            continue
+        P = [tuple(float(x) for x in row) for row in P32]
+        Z = [(float(kq[i[k], 2]), float(kt[tr[k], 2])) for k in range(n)]
+        fit = _register_fit(P, I0, float(c[best]), float(s[best]))
+        final = I0
+        I1 = [k for k in range(n) if _register_r2(P, k, *fit) <= id2d]
+        if len(I1) >= 2:
+            fit = _register_fit(P, I1, fit[0], fit[1])
+            final = I1
+        sz = sr = 0.0
+        for k in final:
+            sz += (Z[k][1] - Z[k][0])
+            sr += _register_r2(P, k, *fit)
+        nf = float(len(final))
+        r["c"], r["s"], r["tx"], r["ty"] = fit
+        r["tz"] = sz / nf
+        r["rms"] = np.float32(math.sqrt(sr / nf))
+        r["n_inliers"] = len(final)
+        r["flags"] = flags | (FX_REG_VALID if len(final) >= min_inliers else 0)
+        r["hyp_a"], r["hyp_b"] = i[pool[a[best]]], i[pool[b[best]]]
+        inlier[i[final]] = 1
+    return {"rec": rec, "inlier": inlier, "corr": corrs}
+
+
 def _np(ptr, shape, dtype):
     n = int(np.prod(shape))
     if n == 0 or not ptr:
@@ -624,6 +834,52 @@ class Context:
                                                 int(t_rows), int(t_cap), arr, len(pairs), C.byref(opt), C.c_void_p(out.data_ptr())))
         cur.wait_stream(ext)
         return out
+
+    def register_matches(self, q_kp, t_kp, matches, pairs, out=None, inliers=None, **opts):
+        """fx_register_matches: q_kp and t_kp are keypoint blocks as (device tensor, max_scans, max_total_keypoints) — what
+        pack_keypoint_block filled —, matches the device torch.int32 tensor [q_max_rows, 8] match_descriptors returned for the
+        same `pairs`.  opts: inlier_dist, min_baseline, hyp_corr, min_inliers, require_flags (fx_register_options).  Returns
+        (out, inliers): a device torch.float64 tensor [n_pairs, 8] holding one 64-byte fx_registration a pair (register_records
+        views a host copy as named fields) and a device torch.int32 tensor [q_max_rows] of inlier words; `out` / `inliers` reuse
+        tensors of those shapes, inliers=False passes NULL (no inlier words; None is returned for them).
+        Stream-correct like match_descriptors."""
+        import torch
+        (qb, q_scans, q_total), (tb, t_scans, t_total) = q_kp, t_kp
+        dev = torch.device("cuda", self.device)
+        for b, sc, tot in ((qb, q_scans, q_total), (tb, t_scans, t_total)):
+            nbytes = int(self.lib.fx_keypoint_block_bytes(int(sc), int(tot)))
+            if b.device != dev or b.numel() * b.element_size() < nbytes or not b.is_contiguous() or b.data_ptr() % 16:
+                raise ValueError(f"a keypoint block must be a contiguous, 16-byte aligned tensor of >= {nbytes} bytes on {dev}")
+        if matches.dtype != torch.int32 or matches.device != dev or matches.dim() != 2 or matches.shape[1] != 8 or not matches.is_contiguous():
+            raise ValueError(f"matches must be a contiguous torch.int32 tensor [q_max_rows, 8] on {dev}")
+        n_rows, n_pairs = int(matches.shape[0]), len(pairs)
+        if out is None:
+            out = torch.empty((n_pairs, 8), dtype=torch.float64, device=dev)
+        elif out.dtype != torch.float64 or out.device != dev or tuple(out.shape) != (n_pairs, 8) or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous torch.float64 tensor [{n_pairs}, 8] on {dev}")
+        if inliers is None:
+            inliers = torch.empty((n_rows,), dtype=torch.int32, device=dev)
+        elif inliers is False:
+            inliers = None
+        elif inliers.dtype != torch.int32 or inliers.device != dev or tuple(inliers.shape) != (n_rows,) or not inliers.is_contiguous():
+            raise ValueError(f"inliers must be a contiguous torch.int32 tensor [{n_rows}] on {dev}")
+        arr = (FxMatchPair * max(n_pairs, 1))()
+        for i, pr in enumerate(pairs):
+            arr[i].q_row0, arr[i].q_rows, arr[i].t_row0, arr[i].t_rows = (int(x) for x in pr)
+        opt = FxRegisterOptions()
+        self.lib.fx_register_options_default(C.byref(opt))
+        for k, v in opts.items():
+            if k not in REG_DEFAULTS:
+                raise TypeError(f"unknown option {k!r}")
+            setattr(opt, k, float(v) if k in ("inlier_dist", "min_baseline") else int(v))
+        cur = torch.cuda.current_stream(dev)
+        ext = torch.cuda.ExternalStream(self.stream_ptr(), device=dev)
+        ext.wait_stream(cur)
+        check(self.lib.fx_register_matches(self.handle, C.c_void_p(qb.data_ptr()), int(q_scans), int(q_total), C.c_void_p(tb.data_ptr()),
+                                           int(t_scans), int(t_total), C.c_void_p(matches.data_ptr()), n_rows, arr, n_pairs, C.byref(opt),
+                                           C.c_void_p(out.data_ptr()), C.c_void_p(inliers.data_ptr() if inliers is not None else None)))
+        cur.wait_stream(ext)
+        return out, inliers
 
     def make_descs(self, ptrs, counts, stride_bytes=16, roll=0.0, pitch=0.0):
         n = len(ptrs)

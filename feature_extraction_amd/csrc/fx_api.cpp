@@ -81,6 +81,7 @@ hipError_t fxk_pack_csr(hipStream_t s, const FxDevParams &P, const FxBuffers &B,
                         uint32_t grid, uint32_t full_rows);
 hipError_t fxk_match(hipStream_t s, const FxMatchArgs &A, uint32_t n_items, uint32_t mut_n, uint32_t shifts);
 uint32_t fxk_match_tile_rows(void);
+hipError_t fxk_register(hipStream_t s, const FxRegisterArgs &A, uint32_t n_pairs);
 #ifdef FX_TEST_HOOKS
 void fxk_test_sort_replay(hipStream_t s, const uint32_t *sizes, uint32_t n_seq, uint32_t n, uint32_t *perm);
 void fxk_test_elevation(hipStream_t s, const float *xyz, uint32_t n, const double *tab, float *fast, uint8_t *ok, float *exact);
@@ -228,6 +229,11 @@ struct fx_ctx {
   uint8_t *d_match = nullptr, *h_match = nullptr;
   size_t match_dev_bytes = 0, match_host_bytes = 0;
   hipEvent_t match_ev = nullptr;
+  // fx_register_matches: the pairs on the device and their pinned staging, grown (never shrunk) when a call has more pairs;
+  // reg_ev: the last call's copy out of the staging
+  uint8_t *d_reg = nullptr, *h_reg = nullptr;
+  size_t reg_bytes = 0;
+  hipEvent_t reg_ev = nullptr;
 };
 
 namespace {
@@ -954,6 +960,9 @@ void fx_destroy(fx_ctx *c) {
   if (c->d_match) (void)hipFree(c->d_match);
   if (c->h_match) (void)hipHostFree(c->h_match);
   if (c->match_ev) (void)hipEventDestroy(c->match_ev);
+  if (c->d_reg) (void)hipFree(c->d_reg);
+  if (c->h_reg) (void)hipHostFree(c->h_reg);
+  if (c->reg_ev) (void)hipEventDestroy(c->reg_ev);
   for (int i = 0; i < kMetaSlots; ++i)
     if (c->meta_ev[i]) (void)hipEventDestroy(c->meta_ev[i]);
   for (hipEvent_t e : c->ev_ring) (void)hipEventDestroy(e);
@@ -1624,6 +1633,73 @@ fx_status fx_match_descriptors_csr(fx_ctx *c, const void *q_block, uint32_t q_ma
   A.out = out;
   A.max_dist2 = o.max_dist2, A.max_ratio = o.max_ratio, A.mutual = o.mutual ? 1u : 0u;
   FX_HIP(fxk_match(c->stream, A, (uint32_t)n_items, (uint32_t)mut_n, o.azimuth_shifts));
+  return FX_OK;
+}
+
+void fx_register_options_default(fx_register_options *o) {
+  if (!o) return;
+  o->inlier_dist = 0.30f;
+  o->min_baseline = 2.0f;
+  o->hyp_corr = 64u;
+  o->min_inliers = 3u;
+  o->require_flags = FX_MATCH_ACCEPTED;
+}
+
+fx_status fx_register_matches(fx_ctx *c, const void *q_kp, uint32_t q_max_scans, uint32_t q_max_total, const void *t_kp, uint32_t t_max_scans,
+                              uint32_t t_max_total, const fx_match *matches, uint32_t q_max_rows, const fx_match_pair *pairs, uint32_t n_pairs,
+                              const fx_register_options *opt, fx_registration *out, uint32_t *inlier) {
+  if (!c || !q_kp || !t_kp || (q_max_rows && !matches) || (n_pairs && (!pairs || !out))) return fail(FX_ERR_INVALID_ARG, "null argument");
+  if (!q_max_scans || !t_max_scans) return fail(FX_ERR_INVALID_ARG, "a keypoint block of no scans");
+  if (((uintptr_t)q_kp % 16) != 0 || ((uintptr_t)t_kp % 16) != 0 || ((uintptr_t)matches % 4) != 0 || ((uintptr_t)out % 8) != 0 ||
+      ((uintptr_t)inlier % 4) != 0)
+    return fail(FX_ERR_INVALID_ARG, "keypoint blocks must be 16-byte, the records 8-byte aligned");
+  fx_register_options o;
+  fx_register_options_default(&o);
+  if (opt) o = *opt;
+  if (!(o.inlier_dist > 0.f) || !std::isfinite(o.inlier_dist) || !(o.min_baseline > 0.f) || !std::isfinite(o.min_baseline))
+    return fail(FX_ERR_INVALID_ARG, "inlier_dist and min_baseline must be finite and positive");
+  if (o.hyp_corr < 2u || o.hyp_corr > 128u) return fail(FX_ERR_INVALID_ARG, "hyp_corr must be 2..128");
+  if (o.min_inliers < 2u) return fail(FX_ERR_INVALID_ARG, "min_inliers must be at least 2");
+  {  // the query ranges must be disjoint, as they were for the match: one inlier word a query row
+    std::vector<std::pair<uint64_t, uint64_t>> r;
+    for (uint32_t p = 0; p < n_pairs; ++p)
+      if (pairs[p].q_rows) r.emplace_back((uint64_t)pairs[p].q_row0, (uint64_t)pairs[p].q_row0 + pairs[p].q_rows);
+    std::sort(r.begin(), r.end());
+    for (size_t i = 1; i < r.size(); ++i)
+      if (r[i].first < r[i - 1].second)
+        return fail(FX_ERR_INVALID_ARG, "query ranges of the pairs overlap at row " + std::to_string(r[i].first));
+  }
+  FX_HIP(hipSetDevice(c->device));
+  const size_t staged = (size_t)n_pairs * sizeof(fx_match_pair);
+  if (!c->reg_ev) FX_HIP(hipEventCreateWithFlags(&c->reg_ev, hipEventDisableTiming));
+  if (staged > c->reg_bytes) {
+    if (c->d_reg) {
+      FX_HIP(hipStreamSynchronize(c->stream));
+      FX_HIP(hipFree(c->d_reg));
+      FX_HIP(hipHostFree(c->h_reg));
+      c->d_reg = c->h_reg = nullptr, c->reg_bytes = 0;
+    }
+    const size_t bytes = std::max(staged, (size_t)4096);
+    void *d = nullptr, *h = nullptr;
+    hipError_t e = hipMalloc(&d, bytes);
+    if (e == hipSuccess && (e = hipHostMalloc(&h, bytes, hipHostMallocDefault)) != hipSuccess) (void)hipFree(d);
+    if (e != hipSuccess) return fail(FX_ERR_OOM, std::string("register pairs buffer (") + std::to_string(bytes) + "): " + hipGetErrorString(e));
+    c->d_reg = (uint8_t *)d, c->h_reg = (uint8_t *)h, c->reg_bytes = bytes;
+  }
+  if (staged) {
+    FX_HIP(hipEventSynchronize(c->reg_ev));  // (the last call's copy out of the staging; done at once when none was recorded)
+    std::memcpy(c->h_reg, pairs, staged);
+    FX_HIP(hipMemcpyAsync(c->d_reg, c->h_reg, staged, hipMemcpyHostToDevice, c->stream));
+    FX_HIP(hipEventRecord(c->reg_ev, c->stream));
+  }
+  FxRegisterArgs A{};
+  A.q_kp = (const uint32_t *)q_kp, A.t_kp = (const uint32_t *)t_kp;
+  A.q_max_scans = q_max_scans, A.q_max_total = q_max_total, A.t_max_scans = t_max_scans, A.t_max_total = t_max_total;
+  A.matches = matches, A.q_max_rows = q_max_rows;
+  A.pairs = c->d_reg, A.out = out, A.inlier = inlier;
+  A.inlier_dist = o.inlier_dist, A.min_baseline = o.min_baseline;
+  A.hyp_corr = o.hyp_corr, A.min_inliers = o.min_inliers, A.require_flags = o.require_flags;
+  FX_HIP(fxk_register(c->stream, A, n_pairs));
   return FX_OK;
 }
 

@@ -86,7 +86,19 @@ struct FxMatchArgs {
   float max_dist2, max_ratio;
   uint32_t mutual;
 };
-#define FX_N_HINTS 8      // tier_hint[]: 0 / 1 rings handed to the second run tier / the workgroup tier (largest XCD class), 2 big merges, 3 huge merges, 4 dense rows, 5 dense support points, 6 scans k_front handed to k_front_redo, 7 scans handed to the slow tier (k_slow)
+// fx_register_matches (csrc/fx_register.hip): a launch's arguments.
+struct FxRegisterArgs {
+  const uint32_t *q_kp, *t_kp;  // keypoint blocks (include/fx.h fx_pack_keypoint_block)
+  uint32_t q_max_scans, q_max_total, t_max_scans, t_max_total;
+  const void *matches;          // fx_match [q_max_rows]
+  uint32_t q_max_rows;
+  const void *pairs;            // fx_match_pair [n_pairs], a workgroup each
+  void *out;                    // fx_registration [n_pairs]
+  uint32_t *inlier;             // [q_max_rows] or null
+  float inlier_dist, min_baseline;
+  uint32_t hyp_corr, min_inliers, require_flags;
+};
+#define FX_N_HINTS 8     // tier_hint[]: 0 / 1 rings handed to the second run tier / the workgroup tier (largest XCD class), 2 big merges, 3 huge merges, 4 dense rows, 5 dense support points, 6 scans k_front handed to k_front_redo, 7 scans handed to the slow tier (k_slow)
 #define FX_CNT_QPOOL 32   // counters[32]: entries of the dense tier's query pool in use
 #define FX_CNT_LARGE2 16  // counters[16 + c]: rings of XCD class c the second run tier hands to the workgroup tier
 #define FX_CNT_LARGE 24  // counters[24 + c]: ... to the large tier

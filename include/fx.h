@@ -407,6 +407,79 @@ fx_status fx_match_descriptors_csr(fx_ctx *ctx, const void *q_block_device, uint
                                    const fx_match_pair *pairs_host, uint32_t n_pairs, const fx_match_options *opt,
                                    fx_match *out_device /* [q_max_rows] */);
 
+/* ---- Scan-to-scan rigid motion from the matches ----
+ * How the sensor moved between two scans, from their keypoints and the fx_match records that pair them up: a consensus over
+ * the matched keypoints and a closed-form least-squares fit, for all pairs of a batch in one launch set.
+ * Model (4 degrees of freedom): scans are levelled before anything else (rotateCloud) and the landmarks are near-vertical poles
+ * on roughly one plane, so roll and pitch between two scans are neither large nor observable from such points, and a pole
+ * centroid's z depends on which rings hit it.  The motion is a rotation about z plus a translation, (c, s, tx, ty) with
+ * c^2 + s^2 = 1 fitted on xy only, and tz the mean z difference over the inliers: a query keypoint q maps to
+ * (c qx - s qy + tx, s qx + c qy + ty, qz + tz), which should be its train keypoint.  Full SE(3) is out of scope.
+ * Inputs: the two keypoint blocks are exactly what fx_pack_keypoint_block writes ((max_scans, max_total_keypoints) give the
+ * layout); row r of the keypoint area is descriptor row r of the same batch, and row 0's "keypoints stored" bounds the valid
+ * rows.  matches_device and pairs_host are what the caller gave to and got from fx_match_descriptors_csr; pair index p here
+ * is the `pair` field there.  The QUERY ranges of the pairs must be disjoint (FX_ERR_INVALID_ARG otherwise, as are hyp_corr
+ * outside 2..128, min_inliers < 2 and an inlier_dist or min_baseline that is not finite and positive; nothing is launched).
+ * Outputs: every one of the n_pairs records is written and, when inlier_device is given, every one of its q_max_rows words
+ * (1 = the row is in the final inlier set of its pair, else 0); nothing beyond them.
+ * Correspondences of pair p: in ascending query row, the rows i of [q_row0, q_row0 + q_rows) clipped to q_max_rows with
+ * m[i].pair == p, m[i].train_row >= 0, (m[i].flags & require_flags) == require_flags, i below the query block's and
+ * m[i].train_row below the train block's keypoints stored, and all six coordinates (x, y, z of both keypoints) finite.  Only
+ * the first FX_REG_MAX_CORR are used (FX_REG_TRUNCATED when there are more); n_corr is the number used.
+ * Sample pool: the H = min(n_corr, hyp_corr) correspondences of lowest (dist2 bits as uint32, query row); samples are the
+ * pairs (a, b), a < b, of pool ranks in lexicographic order.
+ * Hypothesis stage — fp32 in exactly this operation order, no contraction, no fma, correctly rounded divide and sqrt; with
+ * (qx, qy) -> (tx, ty) the keypoints of a correspondence and differences taken as b - a:
+ *   lq2 = dqx dqx + dqy dqy, lt2 = dtx dtx + dty dty; skip unless lq2 >= mb mb and lt2 >= mb mb (mb = min_baseline);
+ *   skip if |sqrt(lq2) - sqrt(lt2)| > 2 inlier_dist;
+ *   dot = dqx dtx + dqy dty, crs = dqx dty - dqy dtx, nrm = sqrt(dot dot + crs crs); skip unless nrm > 0;
+ *   c = dot / nrm, s = crs / nrm; midpoints mq = (qa + qb) 0.5, mt likewise;
+ *   tx = mtx - (c mqx - s mqy), ty = mty - (s mqx + c mqy);
+ *   correspondence i agrees iff rx rx + ry ry <= inlier_dist inlier_dist, rx = ((c qx - s qy) + tx) - t_x,
+ *   ry = ((s qx + c qy) + ty) - t_y.
+ * The winner is the sample with the most agreeing correspondences among all n_corr, ties to the lowest (a, b); a sample with
+ * fewer than 2 agreeing is no hypothesis.  numpy float32 reproduces this stage bit for bit; counts and the winner are integers.
+ * Refit — fp64, sequential in ascending query row, no contraction, over the winner's agreeing set:
+ *   centroids qc, tc of the set (sum, then divide); per member with u = q - qc, v = t - tc:
+ *   Sdot += (ux vx + uy vy), Scrs += (ux vy - uy vx); nrm = sqrt(Sdot Sdot + Scrs Scrs);
+ *   c = Sdot / nrm, s = Scrs / nrm when nrm > 0, else the (c, s) the fit started from (the hypothesis's, widened to double);
+ *   tx = tcx - (c qcx - s qcy), ty = tcy - (s qcx + c qcy).
+ * All n_corr correspondences are then tested again under this transform in fp64 (same residual expression; the threshold is
+ * the double product of the float inlier_dist with itself), which gives the set I1; if I1 has at least 2 members the fit is
+ * run once more over I1, otherwise the first fit and its set stay.  The reported inliers are the set the final transform was
+ * fitted to; tz is the sequential mean of t_z - q_z over it (fp64), rms = sqrt(sum r^2 / n) under the final transform, the
+ * fp64 value rounded once.  FX_REG_VALID iff n_inliers >= min_inliers.  A pair with FX_REG_NO_HYPOTHESIS carries the
+ * identity (c = 1, s = 0), tx = ty = tz = 0, rms = +inf, n_inliers = 0, hyp_a = hyp_b = 0xffffffff.
+ * The same bits from run to run and with any number of contexts in flight: every decision is an integer or an ordered,
+ * correctly rounded operation, and no sum runs in completion order.
+ * Enqueued on the context's stream; needs no batch to have been processed.  pairs_host is copied before the call returns
+ * into a context-owned buffer that grows when a call needs more; nothing else is allocated in the steady state.  New in 0.7
+ * (added symbols only). */
+#define FX_REG_MAX_CORR 1024u
+typedef struct fx_register_options {
+  float inlier_dist;      /* xy distance (m) within which a correspondence agrees with a transform; default 0.30 */
+  float min_baseline;     /* a 2-correspondence hypothesis needs both point pairs at least this far apart (m); default 2.0 */
+  uint32_t hyp_corr;      /* hypotheses are formed from the hyp_corr best correspondences; 2..128, default 64 */
+  uint32_t min_inliers;   /* FX_REG_VALID needs at least this many final inliers; >= 2, default 3 */
+  uint32_t require_flags; /* FX_MATCH_* bits a match record must carry to be used; default FX_MATCH_ACCEPTED */
+} fx_register_options;
+#define FX_REG_VALID 0x1u         /* a transform was fitted to >= min_inliers correspondences */
+#define FX_REG_TRUNCATED 0x2u     /* more than FX_REG_MAX_CORR (1024) correspondences: the first 1024 in query-row order were used */
+#define FX_REG_NO_HYPOTHESIS 0x4u /* fewer than 2 correspondences, or no sample passed the gates */
+typedef struct fx_registration { /* 64 B, one per pair */
+  double c, s, tx, ty, tz;
+  float rms;                     /* xy residual over the final inliers, the fp64 value rounded once */
+  uint32_t n_corr, n_inliers, flags;
+  uint32_t hyp_a, hyp_b;         /* query rows of the winning sample, 0xffffffff when none */
+} fx_registration;
+void fx_register_options_default(fx_register_options *o);
+fx_status fx_register_matches(fx_ctx *ctx,
+    const void *q_kp_block_device, uint32_t q_max_scans, uint32_t q_max_total_keypoints,
+    const void *t_kp_block_device, uint32_t t_max_scans, uint32_t t_max_total_keypoints,
+    const fx_match *matches_device, uint32_t q_max_rows,
+    const fx_match_pair *pairs_host, uint32_t n_pairs, const fx_register_options *opt,
+    fx_registration *out_device /* [n_pairs] */, uint32_t *inlier_device /* [q_max_rows] or NULL */);
+
 /* Rotation matrix of rotateCloud (ref: node.cpp:161-164): R = Ry(pitch)*Rx(roll)
  * through Eigen's AngleAxisf -> Quaternionf -> toRotationMatrix, all float. Host only. */
 void fx_rotation_from_roll_pitch(double roll, double pitch, float R[9]);
