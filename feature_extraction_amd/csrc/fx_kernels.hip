@@ -4729,27 +4729,41 @@ __device__ __forceinline__ void desc_wave_body(const FxDevParams &P, const FxBuf
     if (nS > FX_WAVE_CAP || nS > P.list_cap) continue;  // (never listed here: k_desc_group sends those rows to their tiers)
     float *out = B.desc + (size_t)row * FX_DESC_FLOATS;
     __builtin_amdgcn_wave_barrier();
+    // The support set is staged with its neighbours (d2 < R^2) in front, [0, nAll), and the rest — the shell out to the
+    // support radius, 30-55 % of a set, which only the density counts read — filled in from the back: the pass below then
+    // runs over ceil(nAll / 64) full chunks instead of every chunk of the set that holds a neighbour.  Nothing depends on a
+    // point's position: the density is a count over the whole set and the keys are unique.
+    uint32_t nAll = 0;
 #pragma unroll
     for (uint32_t u = 0; u < FX_WAVE_CAP / 64; ++u) {
       const uint32_t e = lane + u * 64;
+      float4 v = make_float4(0, 0, 0, 0);
+      float d2 = INFINITY;
       if (e < nS) {
-        const float4 v = lv[u];
-        sp[e] = make_float4(v.x, v.y, v.z, dist2(kp.x, kp.y, kp.z, v.x, v.y, v.z));
-        sidx[e] = __float_as_uint(v.w);
+        v = lv[u];
+        d2 = dist2(kp.x, kp.y, kp.z, v.x, v.y, v.z);
       }
+      const bool nb = d2 < P.r2_search;
+      const unsigned long long m = __ballot(nb);
+      if (e < nS) {
+        const uint32_t before = nAll + lanes_below(m);  // neighbours among the entries in front of this one
+        const uint32_t pos = nb ? before : nS - 1u - (e - before);
+        sp[pos] = make_float4(v.x, v.y, v.z, d2);
+        sidx[pos] = __float_as_uint(v.w);
+      }
+      nAll += (uint32_t)__popcll(m);
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
-    uint32_t nAll = 0, nM = 0;
+    uint32_t nM = 0;
     bool amb = false;
-    for (uint32_t e0 = 0; e0 < nS; e0 += 64) {
+    for (uint32_t e0 = 0; e0 < nAll; e0 += 64) {
       const uint32_t e = e0 + lane;
-      const float4 b = e < nS ? sp[e] : make_float4(0, 0, 0, INFINITY);
+      const bool nb = e < nAll;
+      const float4 b = nb ? sp[e] : make_float4(0, 0, 0, INFINITY);
       const float d2 = b.w;
-      const bool nb = d2 < P.r2_search;
-      nAll += (uint32_t)__popcll(__ballot(nb));
       const bool use = nb && !sc3d_is_origin(d2);
       unsigned long long key = 0;
       float w = 0.f;
@@ -4839,7 +4853,7 @@ extern "C" __global__ __launch_bounds__(FX_WG, FX_GROUP_OCC) void k_desc_group(F
   unsigned long long *nkey = reinterpret_cast<unsigned long long *>(base + 4 * FX_GROUP_CAP);      // 2 * CAP
   float *nw = reinterpret_cast<float *>(base + 6 * FX_GROUP_CAP);
   uint32_t *sidx = base + 7 * FX_GROUP_CAP;
-  uint32_t *cnt = base + 8 * FX_GROUP_CAP;  // [0] neighbours, [1] binned neighbours, [2] ambiguous
+  uint32_t *cnt = base + 8 * FX_GROUP_CAP;  // [1] binned neighbours, [2] bins written to the row
   unsigned long long *skey = reinterpret_cast<unsigned long long *>(base);  // aliases sp
   float *sw = reinterpret_cast<float *>(base + 2 * FX_GROUP_CAP);           // aliases sp
   const FxScTables *T = tables_to_lds(B, smem + FX_NWAVE * FX_GROUPS * FX_GROUP_WORDS);
@@ -4979,24 +4993,37 @@ extern "C" __global__ __launch_bounds__(FX_WG, FX_GROUP_OCC) void k_desc_group(F
     if (too_long) live = false;
     if (!live) nS = 0;
     __builtin_amdgcn_wave_barrier();
+    // Neighbours (d2 < R^2) in front, [0, nAll), the rest of the support set filled in from the back, as in the wavefront
+    // tier: a trip of the loop below costs the density count whenever one lane of the wavefront holds a neighbour, so the
+    // groups' neighbours are packed into as few trips as they fit.
+    uint32_t nAll = 0;
 #pragma unroll
     for (uint32_t u = 0; u < FX_GROUP_CAP / FX_GLANES; ++u) {
       const uint32_t e = gl + u * FX_GLANES;
+      float4 v = make_float4(0, 0, 0, 0);
+      float d2 = INFINITY;
       if (e < nS) {
-        const float4 v = lv[u];
-        sp[e] = make_float4(v.x, v.y, v.z, dist2(kp.x, kp.y, kp.z, v.x, v.y, v.z));
-        sidx[e] = __float_as_uint(v.w);
+        v = lv[u];
+        d2 = dist2(kp.x, kp.y, kp.z, v.x, v.y, v.z);
       }
+      const bool nb = d2 < P.r2_search;
+      const unsigned long long m = __ballot(nb);
+      const uint32_t gm = (uint32_t)(m >> (g * FX_GLANES)) & ((1u << FX_GLANES) - 1u);  // this group's lanes
+      if (e < nS) {
+        const uint32_t before = nAll + (uint32_t)__popc(gm & ((1u << gl) - 1u));  // neighbours among the entries in front of this one
+        const uint32_t pos = nb ? before : nS - 1u - (e - before);
+        sp[pos] = make_float4(v.x, v.y, v.z, d2);
+        sidx[pos] = __float_as_uint(v.w);
+      }
+      nAll += (uint32_t)__popc(gm);
     }
-    if (gl < 3) cnt[gl] = 0;
+    if (gl == 1 || gl == 2) cnt[gl] = 0;  // (slot 0 is free: the neighbour count is the partition's)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    for (uint32_t e = gl; e < nS; e += FX_GLANES) {
+    for (uint32_t e = gl; e < nAll; e += FX_GLANES) {
       const float4 b = sp[e];
       const float d2 = b.w;
-      if (!(d2 < P.r2_search)) continue;
-      atomicAdd(&cnt[0], 1u);
       if (sc3d_is_origin(d2)) continue;
       float lut;
       bool amb = false;
@@ -5009,7 +5036,6 @@ extern "C" __global__ __launch_bounds__(FX_WG, FX_GROUP_OCC) void k_desc_group(F
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const uint32_t nAll = live ? cnt[0] : 0u;
     uint32_t nM = live ? cnt[1] : 0u;
     // (s_waitcnt vmcnt(0): the clearing stores are acknowledged before anything else is written to the row; a wider
     //  scope would write the whole L2 back)
