@@ -48,7 +48,9 @@ typedef enum fx_status {
 #define FX_FLAG_CAND_OVERFLOW 0x2u      /* more per-ring candidates than limits.max_candidates */
 #define FX_FLAG_KP_OVERFLOW 0x4u        /* more keypoints than limits.max_keypoints */
 #define FX_FLAG_NBR_OVERFLOW 0x8u       /* the dense descriptor tier's pools are exhausted (limits.max_dense_points; the scan's
-                                         * overflow region holds max_points entries): the keypoint's descriptor is NaN */
+                                         * overflow region holds max_points entries): the keypoint's descriptor is NaN.
+                                         * WHICH rows of a batch an exhausted pool fails depends on the order they drew
+                                         * their entries in and may differ from run to run; rows that fit never do */
 #define FX_FLAG_TOTAL_KP_OVERFLOW 0x10u /* batch-wide keypoint pool exhausted: the pool holds fewer of the scan's descriptor rows
                                          * than it has keypoints (see "Cuts" below) */
 #define FX_FLAG_KPC_OVERFLOW 0x20u      /* keypoint_cloud exceeded its pool: the scan's n_kpc is 0 */

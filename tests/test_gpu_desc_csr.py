@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from feature_extraction_amd import build, capi
+from tests import desc_rows_util as rows
 from tests import util
 
 pytestmark = pytest.mark.gpu
@@ -295,19 +296,33 @@ def test_full_rows_hook_gives_the_same_block(fx_hooks):
         blocks.append(raw)
         ctx.close()
     assert (blocks[0] == blocks[1]).all()
-    # and the NaN / dense-tier rows (the whole-row path in the product too) through the fast path's neighbours
-    s = util.vlp16_scan(1000, n_poles=8, x_lo=3.0, x_hi=8.0, y_lo=-4.0, y_hi=4.0)
-    p = capi.params("default", descriptor_radius=4.0)
-    blocks = []
-    for full in (0, 1):
-        fx_hooks(FX_CSR_FULL_ROWS=full)
-        ctx = capi.Context(p, capi.limits(1, 28800, max_dense_points=4096))
-        v, dense = _dense(ctx, [s], 0.0, 0.0)
-        blocks.append(_pack(ctx)[1])
-        R = ctx.limits.max_total_keypoints
-        _check_block(capi.csr_parse(blocks[-1], R, R * capi.FX_DESC_FLOATS), dense, f"dense rows, FX_CSR_FULL_ROWS={full}")
-        ctx.close()
-    assert (blocks[0] == blocks[1]).all()
+    # and the NaN / dense-tier rows (the whole-row path in the product too) next to a group row, on hand-built scenes
+    # (tests/desc_rows_util.py) whose outcome does not depend on the order the rows draw their pool entries in: dense rows that
+    # all fit the pool, one of them NaN for want of a neighbour; then, with the smallest pool (4096 entries), dense rows that EACH
+    # exceed it — every one of them fails whichever comes first
+    for name, lim, exhausted in (("csr_fit", {}, False), ("csr_exhaust", dict(max_dense_points=4096), True)):
+        p, scenes, cases = rows.built(name)
+        (s, ora), = scenes
+        n_dense = sum(sup > rows.LIST_CAP for _, sup, _ in cases)
+        assert n_dense >= 2 and any(n == 0 and sup > rows.LIST_CAP for n, sup, _ in cases)
+        blocks = []
+        for full in (0, 1):
+            fx_hooks(FX_CSR_FULL_ROWS=full)
+            ctx = capi.Context(p, capi.limits(1, 1 << len(s).bit_length(), **lim))
+            v, dense = _dense(ctx, [s], 0.0, 0.0)
+            flags = int(capi._np(v.h_flags, (1,), np.uint32)[0])
+            nan_rows = np.isnan(dense[:, :capi.FX_DESC_BINS]).all(axis=1)
+            if exhausted:
+                assert all(sup > 4096 for _, sup, _ in cases if sup > rows.LIST_CAP)
+                assert flags == capi.FX_FLAG_NBR_OVERFLOW and int(nan_rows.sum()) == n_dense
+            else:
+                assert flags == 0 and int(nan_rows.sum()) == 1
+                util.assert_bit_equal(dense, ora["descriptors"], f"{name} against the oracle")
+            blocks.append(_pack(ctx)[1])
+            R = ctx.limits.max_total_keypoints
+            _check_block(capi.csr_parse(blocks[-1], R, R * capi.FX_DESC_FLOATS), dense, f"{name}, FX_CSR_FULL_ROWS={full}")
+            ctx.close()
+        assert (blocks[0] == blocks[1]).all(), name
 
 
 def test_python_sparse_csr_tensor_matches_the_dense_rows_on_the_gpu(fxlib):
