@@ -132,6 +132,34 @@ REG_DTYPE = np.dtype([("c", "<f8"), ("s", "<f8"), ("tx", "<f8"), ("ty", "<f8"), 
 REG_DEFAULTS = dict(inlier_dist=0.30, min_baseline=2.0, hyp_corr=64, min_inliers=3, require_flags=FX_MATCH_ACCEPTED)
 
 
+class FxPose(C.Structure):
+    _fields_ = [("c", C.c_double), ("s", C.c_double), ("tx", C.c_double), ("ty", C.c_double), ("tz", C.c_double),
+                ("segment", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class FxLandmark(C.Structure):
+    _fields_ = [("x", C.c_double), ("y", C.c_double), ("z", C.c_double), ("rms_xy", C.c_float), ("n_obs", C.c_uint32), ("obs0", C.c_uint32),
+                ("first_row", C.c_uint32), ("first_scan", C.c_uint32), ("last_scan", C.c_uint32)]
+
+
+class FxTrackHeader(C.Structure):
+    _fields_ = [("scans", C.c_uint32), ("rows", C.c_uint32), ("n_landmarks", C.c_uint32), ("n_obs", C.c_uint32),
+                ("n_conflicts", C.c_uint32), ("n_gaps", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class FxTrackOptions(C.Structure):
+    _fields_ = [("min_obs", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+FX_POSE_GAP, FX_POSE_NO_SCAN = 0x1, 0x2
+FX_TRACK_NO_ROW = 0xffffffff
+# fx_pose / fx_landmark as numpy records (track_records)
+POSE_DTYPE = np.dtype([("c", "<f8"), ("s", "<f8"), ("tx", "<f8"), ("ty", "<f8"), ("tz", "<f8"), ("segment", "<u4"), ("flags", "<u4")])
+LANDMARK_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("rms_xy", "<f4"), ("n_obs", "<u4"), ("obs0", "<u4"),
+                           ("first_row", "<u4"), ("first_scan", "<u4"), ("last_scan", "<u4")])
+TRACK_HEADER_FIELDS = ("scans", "rows", "n_landmarks", "n_obs", "n_conflicts", "n_gaps")
+
+
 class FxTimings(C.Structure):
     _fields_ = [("ms", C.c_float * FX_N_STAGES), ("total_ms", C.c_float), ("k_prep_exec_ms", C.c_float)]
 
@@ -154,6 +182,7 @@ EXPORTS = ("fx_version", "fx_check_abi", "fx_status_str", "fx_last_error", "fx_p
            "fx_get_stage_bytes", "fx_get_limits", "fx_process_batch", "fx_synchronize", "fx_pack_features", "fx_pack_keypoint_records", "fx_keypoint_block_bytes", "fx_pack_keypoint_block",
            "fx_descriptor_csr_bytes", "fx_pack_descriptors_csr", "fx_get_descriptors_csr", "fx_set_descriptor_csr_capacity",
            "fx_match_options_default", "fx_match_descriptors_csr", "fx_register_options_default", "fx_register_matches",
+           "fx_track_options_default", "fx_track_landmarks",
            "fx_rotation_from_roll_pitch", "fx_sc3d_tables", "fx_sc3d_xaxis", "fx_synth_cfg_vlp16",
            "fx_synth_scan", "fx_unpack_pointcloud2", "fx_pack_pointxyzi")
 # the header's FX_TEST_HOOKS section: exported by lib/libfx_hip_test.so only
@@ -263,6 +292,11 @@ def load():
     lib.fx_register_options_default.restype = None
     lib.fx_register_matches.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
                                         C.c_uint32, C.POINTER(FxMatchPair), C.c_uint32, C.POINTER(FxRegisterOptions), C.c_void_p, C.c_void_p]
+    lib.fx_track_options_default.argtypes = [C.POINTER(FxTrackOptions)]
+    lib.fx_track_options_default.restype = None
+    lib.fx_track_landmarks.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                       C.POINTER(FxPose), C.POINTER(FxTrackOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                       C.c_void_p]
     lib.fx_rotation_from_roll_pitch.argtypes = [C.c_double, C.c_double, _F32P]
     lib.fx_rotation_from_roll_pitch.restype = None
     lib.fx_sc3d_tables.argtypes = [C.c_double, _F32P, _F32P, _F32P, _F32P]
@@ -669,6 +703,116 @@ def register_reference(q_kp_rows, t_kp_rows, match_records, pairs, inlier_dist=0
     return {"rec": rec, "inlier": inlier, "corr": corrs}
 
 
+# ---- poses and landmark tracks of one batch of consecutive scans (include/fx.h fx_track_landmarks)
+def track_records(poses, landmark_of_row, obs_row, landmarks, header):
+    """Host copies of fx_track_landmarks's five outputs (torch tensors, or arrays of the same bytes) as a dict: "poses" (POSE_DTYPE
+    [n_scans]), "landmark_of_row" (int32 [q_max_rows]), "obs_row" (uint32 [q_max_rows]), "landmarks" (LANDMARK_DTYPE, the
+    min(n_landmarks, max_landmarks) records written) and "header" (a dict of the six counts)."""
+    def host(x):
+        if hasattr(x, "detach"):
+            x = x.detach().cpu().numpy()
+        return np.ascontiguousarray(x).view(np.uint8).reshape(-1)
+    h = host(header).view(np.uint32)
+    hdr = {k: int(h[i]) for i, k in enumerate(TRACK_HEADER_FIELDS)}
+    lm = host(landmarks)
+    lm = lm[:len(lm) // LANDMARK_DTYPE.itemsize * LANDMARK_DTYPE.itemsize].view(LANDMARK_DTYPE)
+    return {"poses": host(poses).view(POSE_DTYPE).copy(), "landmark_of_row": host(landmark_of_row).view(np.int32).copy(),
+            "obs_row": host(obs_row).view(np.uint32).copy(), "landmarks": lm[:min(hdr["n_landmarks"], len(lm))].copy(), "header": hdr}
+
+
+def track_reference(kp_offset, kp_rows, match_records, inlier, reg_records, n_scans, init_pose=None, min_obs=2):
+    """The definition of fx_track_landmarks (include/fx.h) in numpy and Python floats.  kp_offset: the block's kp_offset[scans + 1]
+    and kp_rows its [stored, >= 3] float32 keypoint rows (keypoint_block_parse(...)["kp_offset"] / ["rows"], the rows already
+    cut to min(stored, max_total_keypoints)); match_records (MATCH_DTYPE) and inlier, [q_max_rows] each, and reg_records
+    (REG_DTYPE [>= n_scans - 1]) taken as given; init_pose: (c, s, tx, ty, tz) or None.  Returns what track_records returns
+    (every landmark: no capacity), plus "parent" (int64 [q_max_rows], the kept parent of each row or -1)."""
+    off = [int(x) for x in kp_offset]
+    kp = np.ascontiguousarray(kp_rows, dtype=np.float32)
+    kp = kp.reshape(len(kp), -1)[:, :3] if kp.size else np.zeros((0, 3), np.float32)
+    m, inl, reg = np.asarray(match_records), np.asarray(inlier).astype(np.int64) & 0xffffffff, np.asarray(reg_records)
+    R = len(m)
+    n_scans, min_obs = int(n_scans), int(min_obs)
+    if n_scans < 1 or min_obs < 1 or len(inl) != R:
+        raise ValueError("arguments outside what fx_track_landmarks accepts")
+    init = (1.0, 0.0, 0.0, 0.0, 0.0) if init_pose is None else tuple(float(v) for v in init_pose)
+    if not all(math.isfinite(v) for v in init):
+        raise ValueError("init_pose must be finite")
+    S = min(n_scans, len(off) - 1)
+    rows = min(len(kp), R)
+    # good links and the pose fold
+    good = [bool(reg["flags"][p] & FX_REG_VALID) and all(math.isfinite(float(reg[f][p])) for f in ("c", "s", "tx", "ty", "tz")) for p in range(S - 1)]
+    poses = np.zeros(n_scans, POSE_DTYPE)
+    pc, ps, ptx, pty, ptz = init
+    seg = 0
+    for b in range(n_scans):
+        flags = 0
+        if b >= S:
+            flags = FX_POSE_NO_SCAN
+        elif b >= 1 and good[b - 1]:
+            rc, rs, rtx, rty, rtz = (float(reg[f][b - 1]) for f in ("c", "s", "tx", "ty", "tz"))
+            pc, ps, ptx, pty, ptz = pc * rc - ps * rs, ps * rc + pc * rs, (pc * rtx - ps * rty) + ptx, (ps * rtx + pc * rty) + pty, ptz + rtz
+        elif b >= 1:
+            seg, flags = seg + 1, FX_POSE_GAP
+        poses[b] = (pc, ps, ptx, pty, ptz, seg, flags)
+    # the scan of every row
+    scan = np.full(R, -1, np.int64)
+    for b in range(S):
+        scan[off[b]:min(off[b + 1], rows)] = b
+    finite = np.isfinite(kp).all(axis=1)
+    # proposals; a parent keeps its proposer of lowest row
+    parent = np.full(R, -1, np.int64)
+    child = {}
+    proposers = 0
+    for r in range(R):
+        b = int(scan[r])
+        if b < 1 or inl[r] != 1 or int(m["pair"][r]) != b - 1 or not good[b - 1]:
+            continue
+        t = int(m["train_row"][r])
+        if not (off[b - 1] <= t < off[b] and t < rows and finite[r] and finite[t]):
+            continue
+        proposers += 1
+        if t not in child:  # (rows ascend: the first proposer is the lowest)
+            child[t] = r
+            parent[r] = t
+    # tracks: chains from every row without a kept parent, in ascending first row
+    landmark_of_row = np.full(R, -1, np.int32)
+    obs_row = np.full(R, FX_TRACK_NO_ROW, np.uint32)
+    lms = []
+    n_obs = 0
+    for r in range(R):
+        if scan[r] < 0 or parent[r] >= 0:
+            continue
+        chain = [r]
+        while chain[-1] in child:
+            chain.append(child[chain[-1]])
+        if len(chain) < min_obs:
+            continue
+        landmark_of_row[chain] = len(lms)
+        obs_row[n_obs:n_obs + len(chain)] = chain
+        w = []
+        for q in chain:
+            c, s, tx, ty, tz = (float(poses[f][scan[q]]) for f in ("c", "s", "tx", "ty", "tz"))
+            x, y, z = (float(v) for v in kp[q])
+            w.append(((c * x - s * y) + tx, (s * x + c * y) + ty, z + tz))
+        sx = sy = sz = 0.0
+        for wx, wy, wz in w:
+            sx += wx
+            sy += wy
+            sz += wz
+        n = float(len(chain))
+        mx, my, mz = sx / n, sy / n, sz / n
+        acc = 0.0
+        for wx, wy, _ in w:
+            dx, dy = wx - mx, wy - my
+            acc += (dx * dx + dy * dy)
+        lms.append((mx, my, mz, np.float32(math.sqrt(acc / n)), len(chain), n_obs, r, int(scan[r]), int(scan[chain[-1]])))
+        n_obs += len(chain)
+    hdr = {"scans": S, "rows": rows, "n_landmarks": len(lms), "n_obs": n_obs, "n_conflicts": proposers - len(child),
+           "n_gaps": sum(1 for g in good if not g)}
+    return {"poses": poses, "landmark_of_row": landmark_of_row, "obs_row": obs_row, "landmarks": np.array(lms, LANDMARK_DTYPE),
+            "header": hdr, "parent": parent}
+
+
 def _np(ptr, shape, dtype):
     n = int(np.prod(shape))
     if n == 0 or not ptr:
@@ -880,6 +1024,52 @@ class Context:
                                            C.c_void_p(out.data_ptr()), C.c_void_p(inliers.data_ptr() if inliers is not None else None)))
         cur.wait_stream(ext)
         return out, inliers
+
+    def track_landmarks(self, kp, matches, inliers, reg, n_scans, init_pose=None, min_obs=2, max_landmarks=None, out=None):
+        """fx_track_landmarks: kp is the keypoint block as (device tensor, max_scans, max_total_keypoints), matches / inliers / reg the
+        device tensors match_descriptors and register_matches returned for pairs_consecutive of that block's scans.  init_pose:
+        (c, s, tx, ty, tz) or None; max_landmarks defaults to q_max_rows.  Returns the device tensors (poses float64 [n_scans, 6],
+        landmark_of_row int32 [q_max_rows], obs_row int32 [q_max_rows], landmarks float64 [max_landmarks, 6], header int32 [8]);
+        `out` reuses a tuple of such tensors.  track_records views host copies of them as named fields.
+        Stream-correct like register_matches."""
+        import torch
+        kb, scans, total = kp
+        dev = torch.device("cuda", self.device)
+        nbytes = int(self.lib.fx_keypoint_block_bytes(int(scans), int(total)))
+        if kb.device != dev or kb.numel() * kb.element_size() < nbytes or not kb.is_contiguous() or kb.data_ptr() % 16:
+            raise ValueError(f"the keypoint block must be a contiguous, 16-byte aligned tensor of >= {nbytes} bytes on {dev}")
+        if matches.dtype != torch.int32 or matches.device != dev or matches.dim() != 2 or matches.shape[1] != 8 or not matches.is_contiguous():
+            raise ValueError(f"matches must be a contiguous torch.int32 tensor [q_max_rows, 8] on {dev}")
+        n_rows, n_scans = int(matches.shape[0]), int(n_scans)
+        if inliers.dtype != torch.int32 or inliers.device != dev or tuple(inliers.shape) != (n_rows,) or not inliers.is_contiguous():
+            raise ValueError(f"inliers must be a contiguous torch.int32 tensor [{n_rows}] on {dev}")
+        if reg.dtype != torch.float64 or reg.device != dev or reg.dim() != 2 or reg.shape[1] != 8 or reg.shape[0] < n_scans - 1 or not reg.is_contiguous():
+            raise ValueError(f"reg must be a contiguous torch.float64 tensor [>= {n_scans - 1}, 8] on {dev}")
+        max_landmarks = n_rows if max_landmarks is None else int(max_landmarks)
+        shapes = (((max(n_scans, 0), 6), torch.float64), ((n_rows,), torch.int32), ((n_rows,), torch.int32), ((max_landmarks, 6), torch.float64),
+                  ((8,), torch.int32))
+        if out is None:
+            out = tuple(torch.empty(sh, dtype=dt, device=dev) for sh, dt in shapes)
+        for t, (sh, dt) in zip(out, shapes):
+            if t.dtype != dt or t.device != dev or tuple(t.shape) != sh or not t.is_contiguous():
+                raise ValueError(f"out must hold contiguous tensors of {shapes} on {dev}")
+        poses, lor, obs, lms, hdr = out
+        ip = None
+        if init_pose is not None:
+            ip = FxPose(*(float(v) for v in init_pose), 0, 0)
+        opt = FxTrackOptions()
+        self.lib.fx_track_options_default(C.byref(opt))
+        opt.min_obs = int(min_obs)
+        cur = torch.cuda.current_stream(dev)
+        ext = torch.cuda.ExternalStream(self.stream_ptr(), device=dev)
+        ext.wait_stream(cur)
+        check(self.lib.fx_track_landmarks(self.handle, C.c_void_p(kb.data_ptr()), int(scans), int(total), C.c_void_p(matches.data_ptr()),
+                                          C.c_void_p(inliers.data_ptr()), n_rows, C.c_void_p(reg.data_ptr()), n_scans,
+                                          C.byref(ip) if ip is not None else None, C.byref(opt), C.c_void_p(poses.data_ptr()),
+                                          C.c_void_p(lor.data_ptr()), C.c_void_p(obs.data_ptr()), C.c_void_p(lms.data_ptr()), max_landmarks,
+                                          C.c_void_p(hdr.data_ptr())))
+        cur.wait_stream(ext)
+        return out
 
     def make_descs(self, ptrs, counts, stride_bytes=16, roll=0.0, pitch=0.0):
         n = len(ptrs)

@@ -82,6 +82,8 @@ hipError_t fxk_pack_csr(hipStream_t s, const FxDevParams &P, const FxBuffers &B,
 hipError_t fxk_match(hipStream_t s, const FxMatchArgs &A, uint32_t n_items, uint32_t mut_n, uint32_t shifts);
 uint32_t fxk_match_tile_rows(void);
 hipError_t fxk_register(hipStream_t s, const FxRegisterArgs &A, uint32_t n_pairs);
+hipError_t fxk_track(hipStream_t s, const FxTrackArgs &A);
+uint32_t fxk_track_wg_rows(void);
 #ifdef FX_TEST_HOOKS
 void fxk_test_sort_replay(hipStream_t s, const uint32_t *sizes, uint32_t n_seq, uint32_t n, uint32_t *perm);
 void fxk_test_elevation(hipStream_t s, const float *xyz, uint32_t n, const double *tab, float *fast, uint8_t *ok, float *exact);
@@ -234,6 +236,9 @@ struct fx_ctx {
   uint8_t *d_reg = nullptr, *h_reg = nullptr;
   size_t reg_bytes = 0;
   hipEvent_t reg_ev = nullptr;
+  // fx_track_landmarks: the per-row scratch arrays, one buffer grown (never shrunk) when a call has more rows
+  uint8_t *d_track = nullptr;
+  uint32_t track_rows = 0;
 };
 
 namespace {
@@ -962,6 +967,7 @@ void fx_destroy(fx_ctx *c) {
   if (c->match_ev) (void)hipEventDestroy(c->match_ev);
   if (c->d_reg) (void)hipFree(c->d_reg);
   if (c->h_reg) (void)hipHostFree(c->h_reg);
+  if (c->d_track) (void)hipFree(c->d_track);
   if (c->reg_ev) (void)hipEventDestroy(c->reg_ev);
   for (int i = 0; i < kMetaSlots; ++i)
     if (c->meta_ev[i]) (void)hipEventDestroy(c->meta_ev[i]);
@@ -1700,6 +1706,70 @@ fx_status fx_register_matches(fx_ctx *c, const void *q_kp, uint32_t q_max_scans,
   A.inlier_dist = o.inlier_dist, A.min_baseline = o.min_baseline;
   A.hyp_corr = o.hyp_corr, A.min_inliers = o.min_inliers, A.require_flags = o.require_flags;
   FX_HIP(fxk_register(c->stream, A, n_pairs));
+  return FX_OK;
+}
+
+void fx_track_options_default(fx_track_options *o) {
+  if (!o) return;
+  o->min_obs = 2u;
+  o->reserved = 0u;
+}
+
+fx_status fx_track_landmarks(fx_ctx *c, const void *kp, uint32_t max_scans, uint32_t max_total, const fx_match *matches, const uint32_t *inlier,
+                             uint32_t q_max_rows, const fx_registration *reg, uint32_t n_scans, const fx_pose *init, const fx_track_options *opt,
+                             fx_pose *poses, int32_t *landmark_of_row, uint32_t *obs_row, fx_landmark *landmarks, uint32_t max_landmarks,
+                             fx_track_header *header) {
+  if (!c) return fail(FX_ERR_INVALID_ARG, "null argument");
+  if (!n_scans || n_scans > max_scans)
+    return fail(FX_ERR_INVALID_ARG, "n_scans must be 1..max_scans (" + std::to_string(n_scans) + " of " + std::to_string(max_scans) + ")");
+  if (!kp || !poses || !header || (q_max_rows && (!matches || !inlier || !landmark_of_row || !obs_row)) || (n_scans > 1u && !reg) ||
+      (max_landmarks && !landmarks))
+    return fail(FX_ERR_INVALID_ARG, "null argument");
+  if (((uintptr_t)kp % 16) != 0 || ((uintptr_t)matches % 4) != 0 || ((uintptr_t)inlier % 4) != 0 || ((uintptr_t)reg % 8) != 0 ||
+      ((uintptr_t)poses % 8) != 0 || ((uintptr_t)landmark_of_row % 4) != 0 || ((uintptr_t)obs_row % 4) != 0 || ((uintptr_t)landmarks % 8) != 0 ||
+      ((uintptr_t)header % 4) != 0)
+    return fail(FX_ERR_INVALID_ARG, "the keypoint block must be 16-byte, the records 8-byte, the words 4-byte aligned");
+  fx_track_options o;
+  fx_track_options_default(&o);
+  if (opt) o = *opt;
+  if (!o.min_obs) return fail(FX_ERR_INVALID_ARG, "min_obs must be at least 1");
+  FxTrackArgs A{};
+  A.init[0] = 1.0;
+  if (init) {
+    A.init[0] = init->c, A.init[1] = init->s, A.init[2] = init->tx, A.init[3] = init->ty, A.init[4] = init->tz;
+    for (double v : A.init)
+      if (!std::isfinite(v)) return fail(FX_ERR_INVALID_ARG, "init_pose must be finite");
+  }
+  FX_HIP(hipSetDevice(c->device));
+  const size_t wg = fxk_track_wg_rows();
+  if (q_max_rows > c->track_rows || !c->d_track) {
+    if (c->d_track) {
+      FX_HIP(hipStreamSynchronize(c->stream));
+      FX_HIP(hipFree(c->d_track));
+      c->d_track = nullptr, c->track_rows = 0;
+    }
+    const size_t rows = std::max((size_t)q_max_rows, (size_t)1024);
+    const size_t bytes = (rows * 11 + 2 * ((rows + wg - 1) / wg) + 4) * sizeof(uint32_t);
+    void *d = nullptr;
+    hipError_t e = hipMalloc(&d, bytes);
+    if (e != hipSuccess) return fail(FX_ERR_OOM, std::string("track scratch (") + std::to_string(bytes) + "): " + hipGetErrorString(e));
+    c->d_track = (uint8_t *)d, c->track_rows = (uint32_t)rows;
+  }
+  {  // the scratch arrays, [track_rows] each; the two (root, depth) buffers first: they are 8-byte words
+    const size_t n = c->track_rows;
+    uint32_t *w = (uint32_t *)c->d_track;
+    A.jump[0] = (uint2 *)w, A.jump[1] = (uint2 *)(w + 2 * n);
+    w += 4 * n;
+    A.scan_of = w, A.child = w + n, A.prop = (int32_t *)(w + 2 * n), A.len = w + 3 * n, A.lm_id = (int32_t *)(w + 4 * n), A.obs0 = w + 5 * n,
+    A.lm_root = w + 6 * n;
+    A.bsum = w + 7 * n;
+    A.counters = A.bsum + 2 * ((n + wg - 1) / wg);
+  }
+  A.kp = (const uint32_t *)kp, A.max_scans = max_scans, A.max_total = max_total;
+  A.matches = matches, A.inlier = inlier, A.q_max_rows = q_max_rows;
+  A.reg = reg, A.n_scans = n_scans, A.min_obs = o.min_obs, A.max_landmarks = max_landmarks;
+  A.poses = poses, A.landmark_of_row = landmark_of_row, A.obs_row = obs_row, A.landmarks = landmarks, A.header = header;
+  FX_HIP(fxk_track(c->stream, A));
   return FX_OK;
 }
 

@@ -98,6 +98,34 @@ struct FxRegisterArgs {
   float inlier_dist, min_baseline;
   uint32_t hyp_corr, min_inliers, require_flags;
 };
+// fx_track_landmarks (csrc/fx_track.hip): a launch set's arguments.  The scratch arrays are the context's, [q_max_rows] each.
+struct FxTrackArgs {
+  const uint32_t *kp;           // keypoint block (include/fx.h fx_pack_keypoint_block)
+  uint32_t max_scans, max_total;
+  const void *matches;          // fx_match [q_max_rows]
+  const uint32_t *inlier;       // [q_max_rows]
+  uint32_t q_max_rows;
+  const void *reg;              // fx_registration [n_scans - 1]
+  uint32_t n_scans, min_obs, max_landmarks;
+  double init[5];               // P_0: c, s, tx, ty, tz
+  void *poses;                  // fx_pose [n_scans]
+  int32_t *landmark_of_row;     // [q_max_rows]
+  uint32_t *obs_row;            // [q_max_rows]
+  void *landmarks;              // fx_landmark [max_landmarks]
+  void *header;                 // fx_track_header
+  // scratch
+  uint32_t *scan_of;            // the row's scan, FX_TRACK_NONE: a non-row
+  uint32_t *child;              // lowest proposer of the row as a parent (atomic min), FX_TRACK_NONE: none
+  int32_t *prop;                // the parent the row proposes, -1: none
+  uint2 *jump[2];               // (root so far, depth so far), ping-pong
+  uint32_t *len;                // observations of the track rooted at the row
+  int32_t *lm_id;               // landmark number of the track rooted at the row, -1: none
+  uint32_t *obs0;               // first obs_row slot of the landmark rooted at the row
+  uint32_t *lm_root;            // landmark number -> its first row
+  uint32_t *bsum;               // [2][blocks of FXT_WG rows]: landmarks / observations that begin in the block
+  uint32_t *counters;           // [0] conflicts, [1] gaps
+};
+#define FX_TRACK_NONE 0xffffffffu
 #define FX_N_HINTS 8     // tier_hint[]: 0 / 1 rings handed to the second run tier / the workgroup tier (largest XCD class), 2 big merges, 3 huge merges, 4 dense rows, 5 dense support points, 6 scans k_front handed to k_front_redo, 7 scans handed to the slow tier (k_slow)
 #define FX_CNT_QPOOL 32   // counters[32]: entries of the dense tier's query pool in use
 #define FX_CNT_LARGE2 16  // counters[16 + c]: rings of XCD class c the second run tier hands to the workgroup tier

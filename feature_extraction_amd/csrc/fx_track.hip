@@ -1,0 +1,359 @@
+// fx_track.hip — poses and landmark tracks of one batch of consecutive scans (include/fx.h fx_track_landmarks).
+//
+// The pairwise motions of fx_register_matches are folded into poses, the inlier rows are chained from scan to scan into tracks,
+// and each track of enough observations is averaged in the common frame.  Every decision is an integer (atomicMin on the child
+// word, an atomicAdd of conflict counts: both order-free), every fp64 value is an ordered chain of correctly rounded operations
+// on one lane (the build's -ffp-contract=off): the same bytes from run to run and with any number of contexts in flight.
+//
+// Launches, in stream order (FXT_WG = 256 rows a workgroup everywhere a thread is a row):
+//   k_track_init     a thread a row: the row's scan by binary search in kp_offset, child = none, the two row outputs to their
+//                    "nothing" words
+//   k_track_poses    one workgroup, tiles of FXT_WG links: the records and their good flags into LDS; one lane folds (c, s),
+//                    every thread forms its link's rotated translation from the (c, s) before it, three lanes of three
+//                    wavefronts fold tx, ty, tz (one add a step each) while a fourth counts segments; all threads write the tile
+//   k_track_link     a thread a row: validate the proposal, atomicMin(child[t], r)
+//   k_track_parent   a thread a row: kept iff child[t] == r; (root, depth) starts as (t, 1) or (r, 0); conflicts are counted a
+//                    wavefront at a time
+//   k_track_jump     ceil(log2 n_scans) launches, ping-pong: (root, depth) <- (root of root, depth + depth of root); a pure
+//                    function of the round before
+//   k_track_len      the leaf of a track (the row nobody kept as a parent) stores depth + 1 at its root: one writer a track
+//   k_track_sums / k_track_top / k_track_number   the integer scan over rows: landmarks and observations that begin in each
+//                    block of FXT_WG rows, their exclusive prefix (one workgroup, which also writes the header), and the number
+//                    and first obs_row slot of every landmark at its first row
+//   k_track_scatter  a thread a row: landmark_of_row, obs_row[obs0 + depth] = r
+//   k_track_fuse     a lane a landmark: two sequential passes over its contiguous obs_row segment
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "fx_device.h"
+#include "../../include/fx.h"
+
+#define FXT_WG 256
+#define FXT_NWAVE (FXT_WG / 64)
+
+static_assert(sizeof(fx_pose) == 48 && sizeof(fx_landmark) == 48 && sizeof(fx_track_header) == 32 && sizeof(fx_track_options) == 8, "include/fx.h");
+
+namespace {
+// the block's header words, kp_offset[max_scans + 1] and (x, y, z, elevation) rows (include/fx.h fx_pack_keypoint_block)
+struct Block {
+  const uint32_t *off;
+  const float4 *kp;
+  uint32_t S, rows;  // scans and rows that take part
+};
+__device__ __forceinline__ Block block_view(const FxTrackArgs &A) {
+  Block b;
+  b.off = A.kp + 4;
+  b.kp = reinterpret_cast<const float4 *>(A.kp) + (1u + (A.max_scans + 1u + 3u) / 4u + (A.max_scans + 3u) / 4u);
+  b.S = min(min(A.n_scans, A.kp[0]), A.max_scans);
+  b.rows = min(min(A.kp[1], A.max_total), A.q_max_rows);
+  return b;
+}
+__device__ __forceinline__ bool finite3(float4 p) { return isfinite(p.x) && isfinite(p.y) && isfinite(p.z); }
+__device__ __forceinline__ bool good_link(const fx_registration &r) {
+  return (r.flags & FX_REG_VALID) && isfinite(r.c) && isfinite(r.s) && isfinite(r.tx) && isfinite(r.ty) && isfinite(r.tz);
+}
+// is row r the first row of a landmark, and of how many observations
+__device__ __forceinline__ uint32_t landmark_len(const FxTrackArgs &A, const uint2 *jump, uint32_t r) {
+  if (r >= A.q_max_rows || A.scan_of[r] == FX_TRACK_NONE || jump[r].x != r) return 0u;
+  const uint32_t n = A.len[r];
+  return n >= A.min_obs ? n : 0u;
+}
+// exclusive prefix of (a, b) over the workgroup's threads and the totals; s_w: [2][FXT_NWAVE] words of LDS
+__device__ __forceinline__ void wg_scan2(uint32_t a, uint32_t b, uint32_t *s_w, uint32_t &ex_a, uint32_t &ex_b, uint32_t &tot_a, uint32_t &tot_b) {
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint32_t ia = a, ib = b;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t ua = (uint32_t)__shfl_up((int)ia, o, 64), ub = (uint32_t)__shfl_up((int)ib, o, 64);
+    if (lane >= (uint32_t)o) ia += ua, ib += ub;
+  }
+  __syncthreads();  // (s_w's readers of the call before)
+  if (lane == 63u) s_w[wave] = ia, s_w[FXT_NWAVE + wave] = ib;
+  __syncthreads();
+  ex_a = ia - a, ex_b = ib - b, tot_a = tot_b = 0u;
+#pragma unroll
+  for (uint32_t w = 0; w < FXT_NWAVE; ++w) {
+    const uint32_t na = s_w[w], nb = s_w[FXT_NWAVE + w];
+    ex_a += w < wave ? na : 0u, ex_b += w < wave ? nb : 0u;
+    tot_a += na, tot_b += nb;
+  }
+}
+}  // namespace
+
+extern "C" __global__ __launch_bounds__(FXT_WG) void k_track_init(FxTrackArgs A) {
+  const uint32_t r = blockIdx.x * FXT_WG + threadIdx.x;
+  if (r == 0u) A.counters[0] = 0u;
+  if (r >= A.q_max_rows) return;
+  const Block B = block_view(A);
+  uint32_t b = FX_TRACK_NONE;
+  if (r < B.rows && B.S) {
+    uint32_t lo = 0u, hi = B.S;  // the largest b in [0, S] with kp_offset[b] <= r (kp_offset[0] = 0)
+    while (lo < hi) {
+      const uint32_t mid = (lo + hi + 1u) >> 1;
+      if (B.off[mid] <= r) lo = mid;
+      else hi = mid - 1u;
+    }
+    if (lo < B.S && B.off[lo] <= r && r < B.off[lo + 1u]) b = lo;
+  }
+  A.scan_of[r] = b;
+  A.child[r] = FX_TRACK_NONE;
+  A.landmark_of_row[r] = -1;
+  A.obs_row[r] = FX_TRACK_NONE;
+}
+
+extern "C" __global__ __launch_bounds__(FXT_WG) void k_track_poses(FxTrackArgs A) {
+  __shared__ double s_r[5][FXT_WG];      // the tile's records: c, s, tx, ty, tz
+  __shared__ double s_c[FXT_WG + 1], s_s[FXT_WG + 1];  // (c, s) of the pose before the tile and of the tile's poses
+  __shared__ double s_t[3][FXT_WG + 1];  // rotated translations of the links, then tx, ty, tz of the poses (slot 0: before the tile)
+  __shared__ uint32_t s_kind[FXT_WG];    // 1 good link, 0 bad link, 2 beyond the block's scans
+  __shared__ uint32_t s_seg[FXT_WG + 1];
+  __shared__ uint32_t s_gaps;
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint32_t S = min(min(A.n_scans, A.kp[0]), A.max_scans);
+  const fx_registration *reg = reinterpret_cast<const fx_registration *>(A.reg);
+  fx_pose *poses = reinterpret_cast<fx_pose *>(A.poses);
+  if (tid == 0u) {
+    s_c[0] = A.init[0], s_s[0] = A.init[1], s_t[0][0] = A.init[2], s_t[1][0] = A.init[3], s_t[2][0] = A.init[4];
+    s_seg[0] = 0u, s_gaps = 0u;
+    fx_pose p;
+    p.c = A.init[0], p.s = A.init[1], p.tx = A.init[2], p.ty = A.init[3], p.tz = A.init[4];
+    p.segment = 0u, p.flags = S ? 0u : FX_POSE_NO_SCAN;
+    poses[0] = p;
+  }
+  for (uint32_t b0 = 1u; b0 < A.n_scans; b0 += FXT_WG) {  // the tile's poses are b0 + i, their links b0 + i - 1
+    const uint32_t n = min((uint32_t)FXT_WG, A.n_scans - b0);
+    __syncthreads();  // (the tile before is written out, its carry is in slot 0)
+    if (tid < n) {
+      const uint32_t b = b0 + tid;
+      uint32_t kind = 2u;
+      double rc = 1.0, rs = 0.0, rx = 0.0, ry = 0.0, rz = 0.0;
+      if (b < S) {
+        const fx_registration r = reg[b - 1u];
+        kind = good_link(r) ? 1u : 0u;
+        if (kind) rc = r.c, rs = r.s, rx = r.tx, ry = r.ty, rz = r.tz;
+      }
+      s_kind[tid] = kind;
+      s_r[0][tid] = rc, s_r[1][tid] = rs, s_r[2][tid] = rx, s_r[3][tid] = ry, s_r[4][tid] = rz;
+    }
+    __syncthreads();
+#ifndef FXT_SKIP_CS_FOLD  // (measurement builds of tools/track_pose_phases.py leave a phase out: wrong poses, the other phases' time)
+    if (tid == 0u) {  // the (c, s) fold: two dependent fp64 operations a step
+      double pc = s_c[0], ps = s_s[0];
+      for (uint32_t i = 0; i < n; ++i) {
+        const double rc = s_r[0][i], rs = s_r[1][i];
+        const double c = pc * rc - ps * rs, s = ps * rc + pc * rs;
+        const bool good = s_kind[i] == 1u;
+        pc = good ? c : pc, ps = good ? s : ps;
+        s_c[i + 1u] = pc, s_s[i + 1u] = ps;
+      }
+    }
+#endif
+    __syncthreads();
+    if (tid < n) {  // the link's translation in the common frame, under the pose before it
+      const double pc = s_c[tid], ps = s_s[tid], rx = s_r[2][tid], ry = s_r[3][tid];
+      s_t[0][tid + 1u] = pc * rx - ps * ry;
+      s_t[1][tid + 1u] = ps * rx + pc * ry;
+      s_t[2][tid + 1u] = s_r[4][tid];
+    }
+    __syncthreads();
+#ifndef FXT_SKIP_T_FOLD
+    if (lane == 0u) {
+      if (wave < 3u) {  // tx, ty, tz: one add a step, a wavefront each
+        double *t = s_t[wave];
+        double acc = t[0];
+        for (uint32_t i = 0; i < n; ++i) {
+          const double sum = acc + t[i + 1u];
+          acc = s_kind[i] == 1u ? sum : acc;
+          t[i + 1u] = acc;
+        }
+      } else {
+        uint32_t seg = s_seg[0], gaps = s_gaps;
+        for (uint32_t i = 0; i < n; ++i) {
+          const uint32_t bad = s_kind[i] == 0u ? 1u : 0u;
+          seg += bad, gaps += bad;
+          s_seg[i + 1u] = seg;
+        }
+        s_gaps = gaps;
+      }
+    }
+#endif
+    __syncthreads();
+    if (tid < n) {
+      fx_pose p;
+      p.c = s_c[tid + 1u], p.s = s_s[tid + 1u], p.tx = s_t[0][tid + 1u], p.ty = s_t[1][tid + 1u], p.tz = s_t[2][tid + 1u];
+      p.segment = s_seg[tid + 1u];
+      p.flags = s_kind[tid] == 1u ? 0u : s_kind[tid] == 0u ? FX_POSE_GAP : FX_POSE_NO_SCAN;
+      poses[b0 + tid] = p;
+    }
+    __syncthreads();
+    if (tid == 0u) s_c[0] = s_c[n], s_s[0] = s_s[n], s_t[0][0] = s_t[0][n], s_t[1][0] = s_t[1][n], s_t[2][0] = s_t[2][n], s_seg[0] = s_seg[n];
+  }
+  __syncthreads();
+  if (tid == 0u) A.counters[1] = s_gaps;
+}
+
+extern "C" __global__ __launch_bounds__(FXT_WG) void k_track_link(FxTrackArgs A) {
+  const uint32_t r = blockIdx.x * FXT_WG + threadIdx.x;
+  if (r >= A.q_max_rows) return;
+  const Block B = block_view(A);
+  const uint32_t b = A.scan_of[r];
+  int32_t prop = -1;
+  if (b != FX_TRACK_NONE && b >= 1u && A.inlier[r] == 1u) {
+    const fx_match m = reinterpret_cast<const fx_match *>(A.matches)[r];
+    const uint32_t t = (uint32_t)m.train_row;
+    if (m.pair == b - 1u && m.train_row >= 0 && t >= B.off[b - 1u] && t < B.off[b] && t < B.rows &&
+        good_link(reinterpret_cast<const fx_registration *>(A.reg)[b - 1u]) && finite3(B.kp[r]) && finite3(B.kp[t])) {
+      prop = m.train_row;
+      atomicMin(&A.child[t], r);
+    }
+  }
+  A.prop[r] = prop;
+}
+
+extern "C" __global__ __launch_bounds__(FXT_WG) void k_track_parent(FxTrackArgs A) {
+  const uint32_t r = blockIdx.x * FXT_WG + threadIdx.x;
+  bool lost = false;
+  if (r < A.q_max_rows) {
+    const int32_t t = A.prop[r];
+    const bool kept = t >= 0 && A.child[t] == r;
+    lost = t >= 0 && !kept;
+    A.jump[0][r] = kept ? make_uint2((uint32_t)t, 1u) : make_uint2(r, 0u);
+    A.len[r] = 0u;
+  }
+  const unsigned long long bal = __ballot(lost);
+  if ((threadIdx.x & 63u) == 0u && bal) atomicAdd(&A.counters[0], (uint32_t)__popcll(bal));
+}
+
+extern "C" __global__ __launch_bounds__(FXT_WG) void k_track_jump(const uint2 *src, uint2 *dst, uint32_t n) {
+  const uint32_t r = blockIdx.x * FXT_WG + threadIdx.x;
+  if (r >= n) return;
+  const uint2 a = src[r];
+  const uint2 b = src[a.x];
+  dst[r] = make_uint2(b.x, a.y + b.y);
+}
+
+extern "C" __global__ __launch_bounds__(FXT_WG) void k_track_len(FxTrackArgs A, const uint2 *jump) {
+  const uint32_t r = blockIdx.x * FXT_WG + threadIdx.x;
+  if (r >= A.q_max_rows || A.scan_of[r] == FX_TRACK_NONE || A.child[r] != FX_TRACK_NONE) return;
+  const uint2 j = jump[r];  // a leaf: the one row of its track nobody kept as a parent
+  A.len[j.x] = j.y + 1u;
+}
+
+extern "C" __global__ __launch_bounds__(FXT_WG) void k_track_sums(FxTrackArgs A, const uint2 *jump, uint32_t n_blocks) {
+  __shared__ uint32_t s_w[2 * FXT_NWAVE];
+  const uint32_t n = landmark_len(A, jump, blockIdx.x * FXT_WG + threadIdx.x);
+  uint32_t ea, eb, ta, tb;
+  wg_scan2(n ? 1u : 0u, n, s_w, ea, eb, ta, tb);
+  if (threadIdx.x == 0u) A.bsum[blockIdx.x] = ta, A.bsum[n_blocks + blockIdx.x] = tb;
+}
+
+extern "C" __global__ __launch_bounds__(FXT_WG) void k_track_top(FxTrackArgs A, uint32_t n_blocks) {
+  __shared__ uint32_t s_w[2 * FXT_NWAVE];
+  uint32_t base_a = 0u, base_b = 0u;
+  for (uint32_t i0 = 0u; i0 < n_blocks; i0 += FXT_WG) {  // the blocks' counts to their exclusive prefix, in place
+    const uint32_t i = i0 + threadIdx.x;
+    const uint32_t a = i < n_blocks ? A.bsum[i] : 0u, b = i < n_blocks ? A.bsum[n_blocks + i] : 0u;
+    uint32_t ea, eb, ta, tb;
+    wg_scan2(a, b, s_w, ea, eb, ta, tb);
+    if (i < n_blocks) A.bsum[i] = base_a + ea, A.bsum[n_blocks + i] = base_b + eb;
+    base_a += ta, base_b += tb;
+  }
+  if (threadIdx.x == 0u) {
+    const Block B = block_view(A);
+    fx_track_header h;
+    h.scans = B.S, h.rows = B.rows;
+    h.n_landmarks = base_a, h.n_obs = base_b, h.n_conflicts = A.counters[0], h.n_gaps = A.counters[1];
+    h.reserved[0] = h.reserved[1] = 0u;
+    *reinterpret_cast<fx_track_header *>(A.header) = h;
+  }
+}
+
+extern "C" __global__ __launch_bounds__(FXT_WG) void k_track_number(FxTrackArgs A, const uint2 *jump, uint32_t n_blocks) {
+  __shared__ uint32_t s_w[2 * FXT_NWAVE];
+  const uint32_t r = blockIdx.x * FXT_WG + threadIdx.x;
+  const uint32_t n = landmark_len(A, jump, r);
+  uint32_t ea, eb, ta, tb;
+  wg_scan2(n ? 1u : 0u, n, s_w, ea, eb, ta, tb);
+  if (r >= A.q_max_rows) return;
+  if (n) {
+    const uint32_t id = A.bsum[blockIdx.x] + ea;
+    A.lm_id[r] = (int32_t)id;
+    A.obs0[r] = A.bsum[n_blocks + blockIdx.x] + eb;
+    A.lm_root[id] = r;
+  } else {
+    A.lm_id[r] = -1;
+  }
+}
+
+extern "C" __global__ __launch_bounds__(FXT_WG) void k_track_scatter(FxTrackArgs A, const uint2 *jump) {
+  const uint32_t r = blockIdx.x * FXT_WG + threadIdx.x;
+  if (r >= A.q_max_rows || A.scan_of[r] == FX_TRACK_NONE) return;
+  const uint2 j = jump[r];
+  const int32_t id = A.lm_id[j.x];
+  if (id < 0) return;
+  A.landmark_of_row[r] = id;
+  A.obs_row[A.obs0[j.x] + j.y] = r;
+}
+
+extern "C" __global__ __launch_bounds__(FXT_WG) void k_track_fuse(FxTrackArgs A) {
+  const uint32_t i = blockIdx.x * FXT_WG + threadIdx.x;
+  const fx_track_header *h = reinterpret_cast<const fx_track_header *>(A.header);
+  if (i >= A.max_landmarks || i >= h->n_landmarks) return;
+  const Block B = block_view(A);
+  const fx_pose *poses = reinterpret_cast<const fx_pose *>(A.poses);
+  const uint32_t root = A.lm_root[i], n = A.len[root], o = A.obs0[root], first_scan = A.scan_of[root];
+  double sx = 0.0, sy = 0.0, sz = 0.0;
+  for (uint32_t k = 0; k < n; ++k) {
+    const float4 p = B.kp[A.obs_row[o + k]];
+    const fx_pose P = poses[first_scan + k];
+    const double x = (double)p.x, y = (double)p.y;
+    sx += ((P.c * x - P.s * y) + P.tx);
+    sy += ((P.s * x + P.c * y) + P.ty);
+    sz += ((double)p.z + P.tz);
+  }
+  const double dn = (double)n;
+  const double mx = sx / dn, my = sy / dn, mz = sz / dn;
+  double acc = 0.0;
+  for (uint32_t k = 0; k < n; ++k) {
+    const float4 p = B.kp[A.obs_row[o + k]];
+    const fx_pose P = poses[first_scan + k];
+    const double x = (double)p.x, y = (double)p.y;
+    const double dx = ((P.c * x - P.s * y) + P.tx) - mx, dy = ((P.s * x + P.c * y) + P.ty) - my;
+    acc += (dx * dx + dy * dy);
+  }
+  fx_landmark L;
+  L.x = mx, L.y = my, L.z = mz;
+  L.rms_xy = (float)sqrt(acc / dn);
+  L.n_obs = n, L.obs0 = o, L.first_row = root, L.first_scan = first_scan, L.last_scan = first_scan + n - 1u;
+  reinterpret_cast<fx_landmark *>(A.landmarks)[i] = L;
+}
+
+extern "C" hipError_t fxk_track(hipStream_t s, const FxTrackArgs &A) {
+  const uint32_t R = A.q_max_rows, nb = (R + FXT_WG - 1u) / FXT_WG;
+  const dim3 wg(FXT_WG), grid(nb);
+  if (nb) hipLaunchKernelGGL(k_track_init, grid, wg, 0, s, A);
+  else (void)hipMemsetAsync(A.counters, 0, sizeof(uint32_t), s);
+#ifndef FXT_SKIP_POSES
+  hipLaunchKernelGGL(k_track_poses, dim3(1), wg, 0, s, A);
+#endif
+  uint32_t cur = 0u;
+  if (nb) {
+    hipLaunchKernelGGL(k_track_link, grid, wg, 0, s, A);
+    hipLaunchKernelGGL(k_track_parent, grid, wg, 0, s, A);
+    for (uint32_t span = 1u; span < A.n_scans; span <<= 1, cur ^= 1u)  // a chain has at most n_scans - 1 links
+      hipLaunchKernelGGL(k_track_jump, grid, wg, 0, s, A.jump[cur], A.jump[cur ^ 1u], R);
+    hipLaunchKernelGGL(k_track_len, grid, wg, 0, s, A, A.jump[cur]);
+    hipLaunchKernelGGL(k_track_sums, grid, wg, 0, s, A, A.jump[cur], nb);
+  }
+  hipLaunchKernelGGL(k_track_top, dim3(1), wg, 0, s, A, nb);
+  if (nb) {
+    hipLaunchKernelGGL(k_track_number, grid, wg, 0, s, A, A.jump[cur], nb);
+    hipLaunchKernelGGL(k_track_scatter, grid, wg, 0, s, A, A.jump[cur]);
+    const uint32_t nl = R < A.max_landmarks ? R : A.max_landmarks;
+    if (nl) hipLaunchKernelGGL(k_track_fuse, dim3((nl + FXT_WG - 1u) / FXT_WG), wg, 0, s, A);
+  }
+  return hipGetLastError();
+}
+
+extern "C" uint32_t fxk_track_wg_rows(void) { return FXT_WG; }

@@ -482,6 +482,82 @@ fx_status fx_register_matches(fx_ctx *ctx,
     const fx_match_pair *pairs_host, uint32_t n_pairs, const fx_register_options *opt,
     fx_registration *out_device /* [n_pairs] */, uint32_t *inlier_device /* [q_max_rows] or NULL */);
 
+/* ---- Chaining the motions into a trajectory and the inliers into landmark tracks ----
+ * The last step of pack -> match -> register for ONE batch of consecutive scans of one sensor: the match and the register were
+ * run with q_block == t_block and the pairs "scan p + 1 (query) onto scan p (train)", p = 0 .. scans - 2 (what
+ * capi.pairs_consecutive builds), so reg[p] maps scan p + 1's frame into scan p's.  The poses of all scans in one common frame,
+ * the rows that are the same physical pole followed from scan to scan, and each pole's mean position in that frame come out of
+ * one launch set, from exactly the buffers the three calls left on the device.  Out of scope: "B sensors, this batch against
+ * the last" (two blocks), continuing tracks across calls, and any re-estimation of the motions (no bundle adjustment);
+ * init_pose_host lets a caller continue the POSES across calls when two batches overlap by one scan.
+ * Sizes: S = min(n_scans, the block's scans, max_scans) scans and rows = min(the block's keypoints stored,
+ * max_total_keypoints, q_max_rows) rows take part.  scan(r) is the b < S with kp_offset[b] <= r < kp_offset[b + 1]; a row at or
+ * beyond kp_offset[S] or `rows` belongs to nothing (a non-row).
+ * Good links: link p (p < S - 1) is good iff reg[p].flags & FX_REG_VALID and c, s, tx, ty, tz of reg[p] are all finite.
+ * Poses — an fp64 left fold in scan order, no contraction, no fma, no renormalisation of (c, s); p* is the pose before, r* the
+ * link's record:
+ *   P_0 = init_pose (the identity c = 1, s = tx = ty = tz = 0 when NULL), segment 0, flags 0 (init_pose's own segment and flags
+ *   are ignored);
+ *   good link b - 1: c = pc rc - ps rs, s = ps rc + pc rs, tx = (pc rtx - ps rty) + ptx, ty = (ps rtx + pc rty) + pty,
+ *   tz = ptz + rtz; segment kept, flags 0;
+ *   bad link b - 1: the pose of scan b - 1 as it is, segment + 1, FX_POSE_GAP;
+ *   b >= S: the pose and segment of the scan before, flags = FX_POSE_NO_SCAN only.
+ * All n_scans poses are written.  numpy float64 reproduces the fold bit for bit.
+ * Kept links: row r of scan b >= 1 proposes the parent t = matches[r].train_row iff inlier[r] == 1, matches[r].pair == b - 1,
+ * link b - 1 is good, kp_offset[b - 1] <= t < kp_offset[b], t < rows, and x, y, z of both rows are finite (the fourth word, the
+ * elevation, is not a coordinate).  These conditions also make any garbage record memory-safe.  A parent keeps its proposer of
+ * LOWEST row (an integer minimum: order-free); every other proposer starts a track of its own and counts in n_conflicts.
+ * A track is a maximal chain of kept links; every row is in exactly one.  Links join consecutive scans only and never cross a
+ * bad link, so a track's observation at depth d lies in scan first_scan + d and a track has at most one row a scan.
+ * Landmarks: the tracks of at least min_obs observations, numbered by ascending first row (the row of lowest scan).
+ * landmark_of_row[r] is that number, -1 for rows of shorter tracks and for non-rows; all q_max_rows words are written.
+ * obs_row holds the landmarks' rows grouped by landmark in landmark order, ascending scan inside each; entries from n_obs on are
+ * 0xffffffff; all q_max_rows words are written.
+ * Fusing — fp64, sequential in obs_row order, no contraction; (x, y, z) the row's float coordinates widened, (c, s, tx, ty, tz)
+ * its scan's pose: wx = (c x - s y) + tx, wy = (s x + c y) + ty, wz = z + tz.  The landmark's x, y, z are the sums of wx, wy, wz
+ * from 0.0 in that order, each divided once by (double)n_obs.  rms_xy: a second pass in the same order, acc += (dx dx + dy dy)
+ * with dx = wx - x, dy = wy - y; rms_xy = (float)sqrt(acc / (double)n_obs), the fp64 value rounded once.
+ * Capacity: the landmarks [0, min(n_landmarks, max_landmarks)) are written and nothing behind them; header.n_landmarks is the
+ * number needed; landmark_of_row and obs_row are complete either way.
+ * header: scans = S, rows, n_landmarks, n_obs (the landmarks' observations), n_conflicts, n_gaps (bad links below S), 0, 0.
+ * FX_ERR_INVALID_ARG with the reason in fx_last_error(), nothing launched: a NULL required pointer (landmarks_device may be
+ * NULL with max_landmarks == 0, reg_device with n_scans == 1, the row arrays with q_max_rows == 0; opt NULL = the defaults),
+ * n_scans == 0 or n_scans > max_scans, min_obs == 0, an init_pose whose c, s, tx, ty or tz is not finite, a keypoint block not
+ * 16-byte or records not 8-byte (words: 4-byte) aligned.
+ * The same bytes from run to run and with any number of contexts in flight: every decision is an integer (32-bit integer
+ * atomics only, minimum and sum), every fp64 value an ordered chain of correctly rounded operations on one lane.
+ * Enqueued on the context's stream; needs no batch to have been processed.  init_pose_host is copied before the call returns.
+ * Scratch is a context-owned buffer that grows when a call has more rows; nothing is allocated in the steady state.  New in 0.7
+ * (added symbols only). */
+typedef struct fx_pose {            /* 48 B: scan b's frame -> the frame of init_pose (scan 0's when NULL) */
+  double c, s, tx, ty, tz;
+  uint32_t segment, flags;
+} fx_pose;
+#define FX_POSE_GAP 0x1u            /* the link into this scan was unusable: pose held from the scan before, segment + 1 */
+#define FX_POSE_NO_SCAN 0x2u        /* b is beyond the block's scans: pose held, nothing else */
+typedef struct fx_landmark {        /* 48 B */
+  double x, y, z;                   /* mean of the observations in the common frame */
+  float rms_xy;                     /* sqrt(mean xy distance^2 of the observations from (x, y)); fp64, rounded once */
+  uint32_t n_obs, obs0;             /* its observations are obs_row[obs0 .. obs0 + n_obs), ascending scan */
+  uint32_t first_row, first_scan, last_scan;
+} fx_landmark;
+typedef struct fx_track_header {    /* 32 B */
+  uint32_t scans, rows, n_landmarks, n_obs, n_conflicts, n_gaps, reserved[2];
+} fx_track_header;
+typedef struct fx_track_options {
+  uint32_t min_obs;                 /* a track becomes a landmark with at least this many observations; >= 1, default 2 */
+  uint32_t reserved;
+} fx_track_options;
+void fx_track_options_default(fx_track_options *o);
+fx_status fx_track_landmarks(fx_ctx *ctx,
+    const void *kp_block_device, uint32_t max_scans, uint32_t max_total_keypoints,   /* fx_pack_keypoint_block */
+    const fx_match *matches_device, const uint32_t *inlier_device, uint32_t q_max_rows,
+    const fx_registration *reg_device, uint32_t n_scans,        /* reg[p], p < n_scans - 1: scan p + 1 -> scan p */
+    const fx_pose *init_pose_host /* NULL: identity */, const fx_track_options *opt,
+    fx_pose *poses_device /* [n_scans] */, int32_t *landmark_of_row_device /* [q_max_rows] */,
+    uint32_t *obs_row_device /* [q_max_rows] */, fx_landmark *landmarks_device, uint32_t max_landmarks,
+    fx_track_header *header_device);
+
 /* Rotation matrix of rotateCloud (ref: node.cpp:161-164): R = Ry(pitch)*Rx(roll)
  * through Eigen's AngleAxisf -> Quaternionf -> toRotationMatrix, all float. Host only. */
 void fx_rotation_from_roll_pitch(double roll, double pitch, float R[9]);
