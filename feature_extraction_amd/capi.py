@@ -160,6 +160,26 @@ LANDMARK_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("rms_xy", 
 TRACK_HEADER_FIELDS = ("scans", "rows", "n_landmarks", "n_obs", "n_conflicts", "n_gaps")
 
 
+class FxMapLandmark(C.Structure):
+    _fields_ = [("x", C.c_double), ("y", C.c_double), ("z", C.c_double), ("rms_xy", C.c_float), ("n_obs", C.c_uint32),
+                ("first_scan", C.c_uint32), ("last_scan", C.c_uint32), ("segment", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class FxMapHeader(C.Structure):
+    _fields_ = [("n_landmarks", C.c_uint32), ("n_needed", C.c_uint32), ("n_obs", C.c_uint32), ("scans", C.c_uint32),
+                ("batches", C.c_uint32), ("segments", C.c_uint32), ("flags", C.c_uint32), ("carry_rows", C.c_uint32),
+                ("last_joined", C.c_uint32), ("last_new", C.c_uint32), ("last_pose", FxPose)]
+
+
+FX_MAP_OVERLAP = 0x1
+FX_MAP_FULL, FX_MAP_OVERLAP_MISMATCH, FX_MAP_TRACK_TRUNCATED = 0x1, 0x2, 0x4
+FX_MAP_LM_CONTINUED = 0x1
+# fx_map_landmark as numpy records, and the header's counts (map_records)
+MAP_LANDMARK_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("rms_xy", "<f4"), ("n_obs", "<u4"), ("first_scan", "<u4"),
+                               ("last_scan", "<u4"), ("segment", "<u4"), ("flags", "<u4")])
+MAP_HEADER_FIELDS = ("n_landmarks", "n_needed", "n_obs", "scans", "batches", "segments", "flags", "carry_rows", "last_joined", "last_new")
+
+
 class FxTimings(C.Structure):
     _fields_ = [("ms", C.c_float * FX_N_STAGES), ("total_ms", C.c_float), ("k_prep_exec_ms", C.c_float)]
 
@@ -183,6 +203,7 @@ EXPORTS = ("fx_version", "fx_check_abi", "fx_status_str", "fx_last_error", "fx_p
            "fx_descriptor_csr_bytes", "fx_pack_descriptors_csr", "fx_get_descriptors_csr", "fx_set_descriptor_csr_capacity",
            "fx_match_options_default", "fx_match_descriptors_csr", "fx_register_options_default", "fx_register_matches",
            "fx_track_options_default", "fx_track_landmarks",
+           "fx_map_create", "fx_map_destroy", "fx_map_reset", "fx_map_update", "fx_map_get", "fx_map_read_header", "fx_map_read_landmarks",
            "fx_rotation_from_roll_pitch", "fx_sc3d_tables", "fx_sc3d_xaxis", "fx_synth_cfg_vlp16",
            "fx_synth_scan", "fx_unpack_pointcloud2", "fx_pack_pointxyzi")
 # the header's FX_TEST_HOOKS section: exported by lib/libfx_hip_test.so only
@@ -297,6 +318,15 @@ def load():
     lib.fx_track_landmarks.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
                                        C.POINTER(FxPose), C.POINTER(FxTrackOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                        C.c_void_p]
+    lib.fx_map_create.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+    lib.fx_map_destroy.argtypes = [C.c_void_p]
+    lib.fx_map_destroy.restype = None
+    lib.fx_map_reset.argtypes = [C.c_void_p, C.c_void_p]
+    lib.fx_map_update.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                  C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
+    lib.fx_map_get.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    lib.fx_map_read_header.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(FxMapHeader)]
+    lib.fx_map_read_landmarks.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     lib.fx_rotation_from_roll_pitch.argtypes = [C.c_double, C.c_double, _F32P]
     lib.fx_rotation_from_roll_pitch.restype = None
     lib.fx_sc3d_tables.argtypes = [C.c_double, _F32P, _F32P, _F32P, _F32P]
@@ -813,11 +843,216 @@ def track_reference(kp_offset, kp_rows, match_records, inlier, reg_records, n_sc
             "header": hdr, "parent": parent}
 
 
+# ---- the persistent landmark map: tracks carried across overlapping batches (include/fx.h fx_map_update)
+def map_state(max_landmarks, max_carry_rows):
+    """The state of a fresh map as map_reference keeps it: plain Python (a header dict, lists, one uint32 array)."""
+    hdr = {k: 0 for k in MAP_HEADER_FIELDS}
+    hdr["last_pose"] = (1.0, 0.0, 0.0, 0.0, 0.0, 0, 0)
+    return {"max_landmarks": int(max_landmarks), "max_carry_rows": int(max_carry_rows), "header": hdr, "landmarks": [], "acc": [],
+            "carry": [], "carry_kp": np.zeros((0, 4), np.uint32)}
+
+
+def map_state_records(state):
+    """A map_reference state as Map.records() returns the device's: {"header": the counts and last_pose (a 7-tuple),
+    "landmarks": MAP_LANDMARK_DTYPE [n_landmarks]}."""
+    lm = np.zeros(len(state["landmarks"]), MAP_LANDMARK_DTYPE)
+    for i, r in enumerate(state["landmarks"]):
+        lm[i] = tuple(r[f] for f in MAP_LANDMARK_DTYPE.names)
+    return {"header": dict(state["header"]), "landmarks": lm}
+
+
+def map_reference(state, kp_offset, kp_rows, track, overlap=False, track_max_landmarks=None):
+    """The definition of fx_map_update (include/fx.h) in numpy and Python floats, one batch at a time.  state: map_state(...) or
+    what an earlier call returned (it is not modified); kp_offset / kp_rows: the block's kp_offset[scans + 1] and its [stored, 4]
+    float32 rows (all four words: the overlap is a comparison of bit patterns); track: what track_records / track_reference
+    returned for the batch ("poses", "landmark_of_row", "obs_row", "landmarks", "header"); overlap: FX_MAP_OVERLAP;
+    track_max_landmarks: the max_landmarks the track was run with (default: every landmark it needed).
+    Returns (the new state, map_id_of_row int32 [q_max_rows])."""
+    import copy
+    st = copy.deepcopy(state)
+    H, cap, max_carry = st["header"], st["max_landmarks"], st["max_carry_rows"]
+    off = [int(x) for x in kp_offset]
+    kp = np.ascontiguousarray(kp_rows, dtype=np.float32)
+    kp = kp.reshape(len(kp), 4) if kp.size else np.zeros((0, 4), np.float32)
+    words = kp.view(np.uint32)
+    lor, obs_row, poses, lms, th = (track[k] for k in ("landmark_of_row", "obs_row", "poses", "landmarks", "header"))
+    R = len(lor)
+    S, rows = min(int(th["scans"]), len(off) - 1), min(int(th["rows"]), len(kp), R)
+    max_l = len(lms) if track_max_landmarks is None else min(int(track_max_landmarks), len(lms))
+    L = min(int(th["n_landmarks"]), max_l)
+    ids = np.full(R, -1, np.int32)
+    H["batches"] += 1
+    H["last_joined"] = H["last_new"] = 0
+    if S == 0:
+        return st, ids
+
+    def lo(b):
+        return min(off[b], rows)
+
+    def hi(b):
+        return max(min(off[b + 1], rows), lo(b))
+    n0 = hi(0) - lo(0)
+    accepted = bool(overlap) and H["scans"] > 0 and H["carry_rows"] == n0 and np.array_equal(words[lo(0):hi(0)], st["carry_kp"][:n0])
+    scan_base = H["scans"] - 1 if accepted else H["scans"]
+    seg_base = H["segments"] - 1 if accepted else H["segments"]
+    id_of_lm, n_new, n_joined, added = [], 0, 0, 0
+    pose = [tuple(float(poses[f][b]) for f in ("c", "s", "tx", "ty", "tz")) for b in range(S)]  # (Python floats: IEEE doubles)
+    xyz, obs = kp[:rows, :3].astype(np.float64).tolist(), np.asarray(obs_row).tolist()
+    lm_words = [np.asarray(lms[f][:L]).tolist() for f in ("first_scan", "n_obs", "obs0", "first_row")]
+    for i in range(L):
+        fs, n, o, fr = (col[i] for col in lm_words)
+        g = -1
+        if accepted and fs == 0 and 0 <= fr - lo(0) < H["carry_rows"]:
+            g = st["carry"][fr - lo(0)]
+        if g >= 0:
+            n_joined += 1
+            lid = g
+        else:
+            lid = H["n_needed"] + n_new
+            n_new += 1
+        if lid >= cap:
+            id_of_lm.append(-1)
+            continue
+        id_of_lm.append(lid)
+        if g >= 0:
+            acc, rec, start = st["acc"][lid], st["landmarks"][lid], 1
+            rec["flags"] |= FX_MAP_LM_CONTINUED
+        else:
+            acc, start = [0.0] * 8, 0
+            rec = {"n_obs": 0, "first_scan": scan_base + fs, "segment": seg_base + int(poses["segment"][fs]), "flags": 0}
+            assert lid == len(st["landmarks"])
+            st["acc"].append(acc), st["landmarks"].append(rec)
+        for k in range(start, n):
+            c, s, tx, ty, tz = pose[fs + k]
+            x, y, z = xyz[obs[o + k]]
+            wx, wy, wz = (c * x - s * y) + tx, (s * x + c * y) + ty, z + tz
+            if g < 0 and k == 0:
+                acc[3], acc[4] = wx, wy
+            dx, dy = wx - acc[3], wy - acc[4]
+            acc[0] += wx
+            acc[1] += wy
+            acc[2] += wz
+            acc[5] += dx
+            acc[6] += dy
+            acc[7] += (dx * dx + dy * dy)
+        rec["n_obs"] += n - start
+        added += n - start
+        dn = float(rec["n_obs"])
+        mx, my = acc[5] / dn, acc[6] / dn
+        var = acc[7] / dn - (mx * mx + my * my)
+        rec["x"], rec["y"], rec["z"] = acc[0] / dn, acc[1] / dn, acc[2] / dn
+        rec["rms_xy"] = np.float32(math.sqrt(var if var > 0.0 else 0.0))
+        rec["last_scan"] = scan_base + fs + n - 1
+    of_row = np.asarray(lor[:rows]).astype(np.int64)
+    has = (of_row >= 0) & (of_row < L)
+    ids[:rows][has] = np.array(id_of_lm, np.int32)[of_row[has]]
+    l_s, h_s = lo(S - 1), hi(S - 1)
+    if h_s - l_s <= max_carry:
+        keep = S == 1 and accepted
+        st["carry"] = [int(ids[l_s + j]) if ids[l_s + j] >= 0 else (st["carry"][j] if keep else -1) for j in range(h_s - l_s)]
+        st["carry_kp"], H["carry_rows"] = words[l_s:h_s].copy(), h_s - l_s
+    else:
+        st["carry"], st["carry_kp"], H["carry_rows"] = [], np.zeros((0, 4), np.uint32), 0
+    H["last_new"], H["last_joined"] = n_new, n_joined
+    H["n_needed"] += n_new
+    H["n_landmarks"] = min(H["n_needed"], cap)
+    H["n_obs"] += added
+    H["scans"] = scan_base + S
+    H["segments"] = seg_base + int(poses["segment"][S - 1]) + 1
+    H["last_pose"] = tuple(poses[S - 1].tolist())
+    if H["n_needed"] > cap:
+        H["flags"] |= FX_MAP_FULL
+    if overlap and not accepted:
+        H["flags"] |= FX_MAP_OVERLAP_MISMATCH
+    if int(th["n_landmarks"]) > max_l:
+        H["flags"] |= FX_MAP_TRACK_TRUNCATED
+    return st, ids
+
+
 def _np(ptr, shape, dtype):
     n = int(np.prod(shape))
     if n == 0 or not ptr:
         return np.zeros(shape, dtype)
     return np.ctypeslib.as_array(ptr, shape=(n,)).view(dtype).reshape(shape).copy()
+
+
+class Map:
+    """Owner of an fx_map: the persistent landmark map of one context (include/fx.h fx_map_create).  Close it before its context."""
+
+    def __init__(self, ctx, max_landmarks, max_carry_rows):
+        self.ctx, self.lib = ctx, ctx.lib
+        self.max_landmarks, self.max_carry_rows = int(max_landmarks), int(max_carry_rows)
+        self.handle = C.c_void_p()
+        check(self.lib.fx_map_create(ctx.handle, self.max_landmarks, self.max_carry_rows, C.byref(self.handle)))
+
+    def close(self):
+        if self.handle:
+            self.lib.fx_map_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        """fx_map_reset: enqueues the state of a fresh map."""
+        check(self.lib.fx_map_reset(self.ctx.handle, self.handle))
+
+    def update(self, kp, track_out, overlap=True, row_ids=None):
+        """fx_map_update: kp is the keypoint block as (device tensor, max_scans, max_total_keypoints) and track_out the five device
+        tensors Context.track_landmarks returned for it.  overlap: FX_MAP_OVERLAP (this batch's scan 0 is the last scan of the
+        batch before).  Returns map_id_of_row, a device torch.int32 tensor [q_max_rows]; `row_ids` reuses one, row_ids=False passes
+        NULL (None is returned).  Stream-correct like Context.track_landmarks; never waits for the stream."""
+        import torch
+        kb, scans, total = kp
+        poses, lor, obs, lms, hdr = track_out
+        dev = torch.device("cuda", self.ctx.device)
+        n_rows, max_landmarks = int(lor.shape[0]), int(lms.shape[0])
+        if row_ids is None:
+            row_ids = torch.empty((n_rows,), dtype=torch.int32, device=dev)
+        elif row_ids is False:
+            row_ids = None
+        elif row_ids.dtype != torch.int32 or row_ids.device != dev or tuple(row_ids.shape) != (n_rows,) or not row_ids.is_contiguous():
+            raise ValueError(f"row_ids must be a contiguous torch.int32 tensor [{n_rows}] on {dev}")
+        cur = torch.cuda.current_stream(dev)
+        ext = torch.cuda.ExternalStream(self.ctx.stream_ptr(), device=dev)
+        ext.wait_stream(cur)
+        check(self.lib.fx_map_update(self.ctx.handle, self.handle, C.c_void_p(kb.data_ptr()), int(scans), int(total), C.c_void_p(poses.data_ptr()),
+                                     C.c_void_p(lor.data_ptr()), C.c_void_p(obs.data_ptr()), n_rows, C.c_void_p(lms.data_ptr()), max_landmarks,
+                                     C.c_void_p(hdr.data_ptr()), FX_MAP_OVERLAP if overlap else 0,
+                                     C.c_void_p(row_ids.data_ptr() if row_ids is not None else None)))
+        cur.wait_stream(ext)
+        return row_ids
+
+    def device_pointers(self):
+        """fx_map_get: the device addresses of (the fx_map_header, the fx_map_landmark records)."""
+        h, l = C.c_void_p(), C.c_void_p()
+        check(self.lib.fx_map_get(self.handle, C.byref(h), C.byref(l)))
+        return h.value, l.value
+
+    def header(self):
+        """fx_map_read_header (waits for the stream): the counts and last_pose, a 7-tuple (c, s, tx, ty, tz, segment, flags)."""
+        h = FxMapHeader()
+        check(self.lib.fx_map_read_header(self.ctx.handle, self.handle, C.byref(h)))
+        out = {k: int(getattr(h, k)) for k in MAP_HEADER_FIELDS}
+        p = h.last_pose
+        out["last_pose"] = (p.c, p.s, p.tx, p.ty, p.tz, int(p.segment), int(p.flags))
+        return out
+
+    def landmarks(self, first=0, count=None):
+        """fx_map_read_landmarks (waits for the stream): records [first, first + count) as MAP_LANDMARK_DTYPE; count defaults to the
+        rest of max_landmarks."""
+        count = self.max_landmarks - first if count is None else int(count)
+        out = np.zeros(count, MAP_LANDMARK_DTYPE)
+        check(self.lib.fx_map_read_landmarks(self.ctx.handle, self.handle, int(first), count, C.c_void_p(out.ctypes.data)))
+        return out
+
+    def records(self):
+        """{"header": header(), "landmarks": the n_landmarks records stored} (waits for the stream)."""
+        h = self.header()
+        return {"header": h, "landmarks": self.landmarks(0, h["n_landmarks"])}
 
 
 class Context:
@@ -1070,6 +1305,10 @@ class Context:
                                           C.c_void_p(hdr.data_ptr())))
         cur.wait_stream(ext)
         return out
+
+    def map_create(self, max_landmarks, max_carry_rows):
+        """fx_map_create: a persistent landmark map owned by this context (Map.update after every track_landmarks)."""
+        return Map(self, max_landmarks, max_carry_rows)
 
     def make_descs(self, ptrs, counts, stride_bytes=16, roll=0.0, pitch=0.0):
         n = len(ptrs)

@@ -84,6 +84,9 @@ uint32_t fxk_match_tile_rows(void);
 hipError_t fxk_register(hipStream_t s, const FxRegisterArgs &A, uint32_t n_pairs);
 hipError_t fxk_track(hipStream_t s, const FxTrackArgs &A);
 uint32_t fxk_track_wg_rows(void);
+hipError_t fxk_map_reset(hipStream_t s, const FxMapArgs &A);
+hipError_t fxk_map_update(hipStream_t s, const FxMapArgs &A);
+uint32_t fxk_map_wg(void);
 #ifdef FX_TEST_HOOKS
 void fxk_test_sort_replay(hipStream_t s, const uint32_t *sizes, uint32_t n_seq, uint32_t n, uint32_t *perm);
 void fxk_test_elevation(hipStream_t s, const float *xyz, uint32_t n, const double *tab, float *fast, uint8_t *ok, float *exact);
@@ -239,6 +242,18 @@ struct fx_ctx {
   // fx_track_landmarks: the per-row scratch arrays, one buffer grown (never shrunk) when a call has more rows
   uint8_t *d_track = nullptr;
   uint32_t track_rows = 0;
+  // fx_map_update: the per-landmark scratch (the batch landmark's map id, the blocks' counts), grown (never shrunk) when a call
+  // has a larger max_landmarks
+  uint8_t *d_map = nullptr;
+  uint32_t map_lms = 0;
+};
+
+// A persistent landmark map (include/fx.h fx_map_create): one device buffer, carved up once.
+struct fx_map {
+  fx_ctx *ctx = nullptr;
+  int device = 0;
+  uint8_t *d = nullptr;
+  FxMapArgs a{};  // the map's own pointers and capacities; the rest is filled in per call
 };
 
 namespace {
@@ -968,6 +983,7 @@ void fx_destroy(fx_ctx *c) {
   if (c->d_reg) (void)hipFree(c->d_reg);
   if (c->h_reg) (void)hipHostFree(c->h_reg);
   if (c->d_track) (void)hipFree(c->d_track);
+  if (c->d_map) (void)hipFree(c->d_map);
   if (c->reg_ev) (void)hipEventDestroy(c->reg_ev);
   for (int i = 0; i < kMetaSlots; ++i)
     if (c->meta_ev[i]) (void)hipEventDestroy(c->meta_ev[i]);
@@ -1770,6 +1786,111 @@ fx_status fx_track_landmarks(fx_ctx *c, const void *kp, uint32_t max_scans, uint
   A.reg = reg, A.n_scans = n_scans, A.min_obs = o.min_obs, A.max_landmarks = max_landmarks;
   A.poses = poses, A.landmark_of_row = landmark_of_row, A.obs_row = obs_row, A.landmarks = landmarks, A.header = header;
   FX_HIP(fxk_track(c->stream, A));
+  return FX_OK;
+}
+
+fx_status fx_map_create(fx_ctx *c, uint32_t max_landmarks, uint32_t max_carry_rows, fx_map **out) {
+  if (!c || !out) return fail(FX_ERR_INVALID_ARG, "null argument");
+  if (!max_landmarks) return fail(FX_ERR_INVALID_ARG, "max_landmarks must be at least 1");
+  FX_HIP(hipSetDevice(c->device));
+  // header (88 -> 96), state words, records, accumulators, the carry scan's rows, the carry table: all 16-byte aligned
+  const size_t carry = std::max((size_t)max_carry_rows, (size_t)1);
+  const size_t o_st = 96, o_rec = o_st + FX_MAP_ST_WORDS * 4, o_acc = o_rec + (size_t)max_landmarks * sizeof(fx_map_landmark),
+               o_kp = o_acc + (size_t)max_landmarks * FX_MAP_ACC * sizeof(double), o_carry = o_kp + carry * 16, bytes = o_carry + carry * 4;
+  void *d = nullptr;
+  hipError_t e = hipMalloc(&d, bytes);
+  if (e != hipSuccess) return fail(FX_ERR_OOM, std::string("map (") + std::to_string(bytes) + "): " + hipGetErrorString(e));
+  fx_map *m = new fx_map;
+  m->ctx = c, m->device = c->device, m->d = (uint8_t *)d;
+  m->a.header = m->d, m->a.st = (uint32_t *)(m->d + o_st), m->a.records = m->d + o_rec, m->a.acc = (double *)(m->d + o_acc);
+  m->a.carry_kp = (uint4 *)(m->d + o_kp), m->a.carry = (int32_t *)(m->d + o_carry);
+  m->a.cap = max_landmarks, m->a.max_carry = max_carry_rows;
+  e = hipMemsetAsync(d, 0, bytes, c->stream);
+  if (e == hipSuccess) e = fxk_map_reset(c->stream, m->a);
+  if (e != hipSuccess) {
+    (void)hipFree(d);
+    delete m;
+    return fail(FX_ERR_HIP, std::string("map reset: ") + hipGetErrorString(e));
+  }
+  *out = m;
+  return FX_OK;
+}
+
+void fx_map_destroy(fx_map *m) {
+  if (!m) return;
+  (void)hipSetDevice(m->device);
+  (void)hipFree(m->d);  // (waits for the device: nothing in flight reads the map afterwards)
+  delete m;
+}
+
+fx_status fx_map_reset(fx_ctx *c, fx_map *m) {
+  if (!c || !m) return fail(FX_ERR_INVALID_ARG, "null argument");
+  if (m->ctx != c) return fail(FX_ERR_INVALID_ARG, "the map belongs to another context");
+  FX_HIP(hipSetDevice(c->device));
+  FX_HIP(fxk_map_reset(c->stream, m->a));
+  return FX_OK;
+}
+
+fx_status fx_map_update(fx_ctx *c, fx_map *m, const void *kp, uint32_t max_scans, uint32_t max_total, const fx_pose *poses,
+                        const int32_t *landmark_of_row, const uint32_t *obs_row, uint32_t q_max_rows, const fx_landmark *landmarks,
+                        uint32_t max_landmarks, const fx_track_header *track_header, uint32_t flags, int32_t *map_id_of_row) {
+  if (!c || !m || !kp || !poses || !track_header || (q_max_rows && (!landmark_of_row || !obs_row)) || (max_landmarks && !landmarks))
+    return fail(FX_ERR_INVALID_ARG, "null argument");
+  if (m->ctx != c) return fail(FX_ERR_INVALID_ARG, "the map belongs to another context");
+  if (flags & ~FX_MAP_OVERLAP) return fail(FX_ERR_INVALID_ARG, "unknown flags (only FX_MAP_OVERLAP is defined)");
+  if (((uintptr_t)kp % 16) != 0 || ((uintptr_t)poses % 8) != 0 || ((uintptr_t)landmark_of_row % 4) != 0 || ((uintptr_t)obs_row % 4) != 0 ||
+      ((uintptr_t)landmarks % 8) != 0 || ((uintptr_t)track_header % 4) != 0 || ((uintptr_t)map_id_of_row % 4) != 0)
+    return fail(FX_ERR_INVALID_ARG, "the keypoint block must be 16-byte, the records 8-byte, the words 4-byte aligned");
+  FX_HIP(hipSetDevice(c->device));
+  const size_t wg = fxk_map_wg();
+  if (max_landmarks > c->map_lms || !c->d_map) {
+    if (c->d_map) {
+      FX_HIP(hipStreamSynchronize(c->stream));
+      FX_HIP(hipFree(c->d_map));
+      c->d_map = nullptr, c->map_lms = 0;
+    }
+    const size_t n = std::max((size_t)max_landmarks, (size_t)1024);
+    const size_t bytes = (n + 2 * ((n + wg - 1) / wg)) * sizeof(uint32_t);
+    void *d = nullptr;
+    hipError_t e = hipMalloc(&d, bytes);
+    if (e != hipSuccess) return fail(FX_ERR_OOM, std::string("map scratch (") + std::to_string(bytes) + "): " + hipGetErrorString(e));
+    c->d_map = (uint8_t *)d, c->map_lms = (uint32_t)n;
+  }
+  FxMapArgs A = m->a;
+  A.id_of_lm = (int32_t *)c->d_map, A.bsum = (uint32_t *)c->d_map + c->map_lms;
+  A.kp = (const uint32_t *)kp, A.max_scans = max_scans, A.max_total = max_total;
+  A.poses = poses, A.landmark_of_row = landmark_of_row, A.obs_row = obs_row, A.q_max_rows = q_max_rows;
+  A.landmarks = landmarks, A.max_landmarks = max_landmarks, A.track_header = track_header;
+  A.flags = flags, A.map_id_of_row = map_id_of_row;
+  FX_HIP(fxk_map_update(c->stream, A));
+  return FX_OK;
+}
+
+fx_status fx_map_get(fx_map *m, const fx_map_header **header, const fx_map_landmark **landmarks) {
+  if (!m) return fail(FX_ERR_INVALID_ARG, "null argument");
+  if (header) *header = (const fx_map_header *)m->a.header;
+  if (landmarks) *landmarks = (const fx_map_landmark *)m->a.records;
+  return FX_OK;
+}
+
+fx_status fx_map_read_header(fx_ctx *c, fx_map *m, fx_map_header *out) {
+  if (!c || !m || !out) return fail(FX_ERR_INVALID_ARG, "null argument");
+  if (m->ctx != c) return fail(FX_ERR_INVALID_ARG, "the map belongs to another context");
+  FX_HIP(hipSetDevice(c->device));
+  FX_HIP(hipMemcpyAsync(out, m->a.header, sizeof(fx_map_header), hipMemcpyDeviceToHost, c->stream));
+  FX_HIP(hipStreamSynchronize(c->stream));
+  return FX_OK;
+}
+
+fx_status fx_map_read_landmarks(fx_ctx *c, fx_map *m, uint32_t first, uint32_t count, fx_map_landmark *out) {
+  if (!c || !m || (count && !out)) return fail(FX_ERR_INVALID_ARG, "null argument");
+  if (m->ctx != c) return fail(FX_ERR_INVALID_ARG, "the map belongs to another context");
+  if (first > m->a.cap || count > m->a.cap - first) return fail(FX_ERR_INVALID_ARG, "records outside the map's max_landmarks");
+  FX_HIP(hipSetDevice(c->device));
+  if (count)
+    FX_HIP(hipMemcpyAsync(out, (const fx_map_landmark *)m->a.records + first, (size_t)count * sizeof(fx_map_landmark), hipMemcpyDeviceToHost,
+                          c->stream));
+  FX_HIP(hipStreamSynchronize(c->stream));
   return FX_OK;
 }
 

@@ -125,6 +125,33 @@ struct FxTrackArgs {
   uint32_t *bsum;               // [2][blocks of FXT_WG rows]: landmarks / observations that begin in the block
   uint32_t *counters;           // [0] conflicts, [1] gaps
 };
+// fx_map_update (csrc/fx_map.hip): a launch set's arguments.  The first group is the map's own memory (fx_map_create), the last
+// the context's scratch, sized by the call's max_landmarks.
+#define FX_MAP_ACC 8       // doubles of a landmark's private accumulators: Sx, Sy, Sz, ax, ay, Dx, Dy, Q
+#define FX_MAP_ST_WORDS 8  // state words between the launches of one update: 0 the overlap scan differs, 1 overlap accepted,
+                           // 2 scan_base, 3 seg_base, 4 new landmarks, 5 continued landmarks, 7 observations accumulated
+struct FxMapArgs {
+  void *header;                 // fx_map_header
+  void *records;                // fx_map_landmark [cap]
+  double *acc;                  // [cap][FX_MAP_ACC]
+  int32_t *carry;               // [max_carry]: map id of local row j of the carry scan, -1: none
+  uint4 *carry_kp;              // [max_carry]: the carry scan's rows as they were in the block
+  uint32_t *st;                 // [FX_MAP_ST_WORDS]; words 0 and 7 are 0 between updates
+  uint32_t cap, max_carry;
+  const uint32_t *kp;           // keypoint block (include/fx.h fx_pack_keypoint_block)
+  uint32_t max_scans, max_total;
+  const void *poses;            // fx_pose [>= S]
+  const int32_t *landmark_of_row;  // [q_max_rows]
+  const uint32_t *obs_row;      // [q_max_rows]
+  uint32_t q_max_rows;
+  const void *landmarks;        // fx_landmark [max_landmarks]
+  uint32_t max_landmarks;
+  const void *track_header;     // fx_track_header
+  uint32_t flags;
+  int32_t *map_id_of_row;       // [q_max_rows] or null
+  int32_t *id_of_lm;            // [max_landmarks]: k_map_join's verdict (>= 0 continues that id, -1 new, -2 not a landmark), then the map id or -1
+  uint32_t *bsum;               // [2][blocks of FXM_WG landmarks]: new / continued landmarks of the block
+};
 #define FX_TRACK_NONE 0xffffffffu
 #define FX_N_HINTS 8     // tier_hint[]: 0 / 1 rings handed to the second run tier / the workgroup tier (largest XCD class), 2 big merges, 3 huge merges, 4 dense rows, 5 dense support points, 6 scans k_front handed to k_front_redo, 7 scans handed to the slow tier (k_slow)
 #define FX_CNT_QPOOL 32   // counters[32]: entries of the dense tier's query pool in use

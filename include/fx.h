@@ -558,6 +558,100 @@ fx_status fx_track_landmarks(fx_ctx *ctx,
     uint32_t *obs_row_device /* [q_max_rows] */, fx_landmark *landmarks_device, uint32_t max_landmarks,
     fx_track_header *header_device);
 
+/* ---- Carrying the landmark tracks across batches: a persistent map on the device ----
+ * fx_track_landmarks numbers the landmarks of ONE batch from 0.  A sensor run is many batches; the map gives every landmark one id
+ * for the whole run and one running mean.  The caller cuts the run into batches that OVERLAP BY ONE SCAN (batch k + 1 starts with
+ * the scan batch k ended with), runs process -> pack -> match -> register -> track on each with init_pose_host = the map's
+ * last_pose, and hands the track's buffers to fx_map_update.  A scan's keypoints never depend on the batch it is in, so the overlap
+ * scan's rows are the same bits in the same order in both batches, and a track of batch k + 1 that begins at local row j of its
+ * scan 0 is the continuation of the track of batch k that ended at local row j of its last scan: an integer decision.  The pose
+ * fold continues bit for bit through init_pose and a landmark's mean is a sequential fp64 sum divided once, so a map that
+ * continues the sums holds what ONE batch of the whole run would have produced, bit for bit, however the run is cut (for tracks
+ * run with min_obs == 2; see the limits below).
+ * The map is owned by the context it was created on (destroy it before the context) and updated by a launch set on that context's
+ * stream: no host synchronisation, no allocation in the steady state.  Its accumulators (the running sums, the anchor, the carry
+ * table and a copy of the carry scan's rows) are private; fx_map_landmark and fx_map_header are what a caller reads.
+ * Inputs of fx_map_update: exactly what the fx_track_landmarks call before it was given (the keypoint block and its layout,
+ * q_max_rows, max_landmarks) and what it wrote (poses, landmark_of_row, obs_row, landmarks, header); every count is read from the
+ * track's header on the device.  Anything else is memory-safe and unspecified.
+ * Sizes: S and rows are the track header's scans and rows (clipped to max_scans and to min(max_total_keypoints, q_max_rows): the
+ * same numbers when the arguments are the track's); L = min(the header's n_landmarks, max_landmarks); when n_landmarks exceeds
+ * max_landmarks FX_MAP_TRACK_TRUNCATED is set and the first L are used (rows of the others report -1).  The rows of scan b are
+ * [min(kp_offset[b], rows), min(kp_offset[b + 1], rows)).  A batch of S == 0 counts in `batches`, sets last_joined = last_new = 0
+ * and changes nothing else.
+ * Overlap: with FX_MAP_OVERLAP the caller states that this batch's scan 0 is the previous batch's last scan.  It is ACCEPTED iff
+ * the map has seen a scan (scans > 0), carry_rows equals the row count of scan 0, and all four words of every row of scan 0 equal
+ * the stored copy of the carry scan's rows, compared as 32-bit patterns.  Flag given and not accepted: FX_MAP_OVERLAP_MISMATCH
+ * is set and the batch is taken as without the flag.
+ * Numbering: scan_base = scans - 1 when accepted, else scans; seg_base = segments - 1 (the previous batch's last global segment)
+ * when accepted, else segments (0 for the first batch).  Afterwards scans = scan_base + S and segments = seg_base +
+ * poses[S - 1].segment + 1.
+ * Joins: batch landmark i < L CONTINUES map landmark g iff the overlap is accepted, its first_scan == 0 and
+ * g = carry[first_row - kp_offset[0]] >= 0.  Every other one is NEW and gets the ids n_needed, n_needed + 1, ... in the batch's
+ * landmark order: ids are order of appearance.  An id at or beyond the map's max_landmarks counts in n_needed and is not stored:
+ * FX_MAP_FULL is set, its rows report -1 and carry -1, and its continuation in a later batch is new again.
+ * Accumulation — fp64, one lane a landmark, sequential in obs_row order, no contraction, no fma.  wx, wy, wz of an observation are
+ * fx_track_landmarks's fusing clause word for word: (c x - s y) + tx, (s x + c y) + ty, z + tz from the row's float coordinates and
+ * its scan's pose in poses_device.  A new landmark starts Sx = Sy = Sz = Dx = Dy = Q = 0.0, takes the first observation's
+ * (wx, wy) as its anchor (ax, ay) and adds every observation; a continued one keeps its sums and its anchor, SKIPS its first
+ * observation (the overlap row, counted in the batch before) and adds the rest.  Adding an observation: Sx += wx, Sy += wy,
+ * Sz += wz, dx = wx - ax, dy = wy - ay, Dx += dx, Dy += dy, Q += (dx dx + dy dy).
+ * Records, with n = (double)n_obs of the landmark so far: x = Sx / n, y = Sy / n, z = Sz / n; mx = Dx / n, my = Dy / n,
+ * var = Q / n - (mx mx + my my), taken as 0 unless var > 0; rms_xy = (float)sqrt(var) (the spread about the mean through the
+ * anchor: not the track's two-pass value, equal to it within rounding).  last_scan = scan_base + the batch landmark's last_scan;
+ * a new landmark's first_scan = scan_base + its local first_scan, segment = seg_base + poses[local first_scan].segment, flags 0;
+ * a continued one gains FX_MAP_LM_CONTINUED.
+ * map_id_of_row[r]: the map id of row r's batch landmark; -1 for rows of no landmark, non-rows and landmarks not stored.  All
+ * q_max_rows words are written when the pointer is given.
+ * Carry for the next call, for every local row j of scan S - 1: the map id of the batch landmark that holds the row; otherwise
+ * the old carry[j] when S == 1 and the overlap was accepted (a batch of only the overlap scan changes nothing); otherwise -1.
+ * The rows of scan S - 1 are copied as the new carry scan.  A last scan of more rows than max_carry_rows stores no carry:
+ * carry_rows = 0 and the next overlap is a mismatch.
+ * header: n_landmarks = min(n_needed, max_landmarks) records stored; n_obs the observations accumulated into stored landmarks;
+ * last_joined / last_new this update's continued / new landmarks (new: stored or not); last_pose = poses[S - 1] as the track
+ * wrote it: what the caller passes as the next init_pose_host.
+ * FX_ERR_INVALID_ARG with the reason in fx_last_error(), nothing launched, the map unchanged: a NULL required pointer
+ * (landmarks_device may be NULL with max_landmarks == 0, the row arrays with q_max_rows == 0, map_id_of_row_device always), a map
+ * of another context, max_landmarks == 0 at create, unknown flag bits, a keypoint block not 16-byte or records not 8-byte (words:
+ * 4-byte) aligned.
+ * The same bytes from run to run and with any number of contexts in flight: every decision is an integer (32-bit integer atomics
+ * only, or and sum), every fp64 value an ordered chain of correctly rounded operations on one lane.
+ * Limits: tracks are continued only across an accepted one-scan overlap; a pole seen again after a bad link or after leaving the
+ * field of view is a new landmark (no spatial re-association, no loop closure).  The equality with one batch of the whole run
+ * holds for min_obs == 2; with a larger min_obs a track that a batch edge cuts into pieces that are each too short is missed.
+ * n_obs and n_needed are 32-bit counts.
+ * fx_map_create allocates all of the map's buffers and enqueues its first reset; fx_map_reset enqueues the state of a fresh map;
+ * fx_map_update's scratch is a context-owned buffer that grows when a call has a larger max_landmarks.  fx_map_get returns the
+ * device addresses of the header and the records (stable for the map's life; read them in stream order); fx_map_read_header and
+ * fx_map_read_landmarks copy to the host and wait for the stream (records [first, first + count) within max_landmarks).  New in
+ * 0.7 (added symbols only). */
+#define FX_MAP_OVERLAP 0x1u           /* fx_map_update flags: scan 0 of this batch is the last scan of the batch before */
+#define FX_MAP_FULL 0x1u              /* header flags, sticky: a landmark was not stored (n_needed > max_landmarks) */
+#define FX_MAP_OVERLAP_MISMATCH 0x2u  /* ... an update's FX_MAP_OVERLAP was not accepted */
+#define FX_MAP_TRACK_TRUNCATED 0x4u   /* ... a track header's n_landmarks exceeded the max_landmarks of its records */
+#define FX_MAP_LM_CONTINUED 0x1u      /* fx_map_landmark flags: continued across at least one batch edge */
+typedef struct fx_map fx_map;
+typedef struct fx_map_landmark {      /* 48 B */
+  double x, y, z;                     /* mean of the observations so far, in the frame of the run's first init_pose */
+  float rms_xy;
+  uint32_t n_obs, first_scan, last_scan, segment, flags; /* scans and segment: global numbers of the run */
+} fx_map_landmark;
+typedef struct fx_map_header {        /* 88 B */
+  uint32_t n_landmarks, n_needed, n_obs, scans, batches, segments, flags, carry_rows, last_joined, last_new;
+  fx_pose last_pose;
+} fx_map_header;
+fx_status fx_map_create(fx_ctx *ctx, uint32_t max_landmarks, uint32_t max_carry_rows, fx_map **out);
+void fx_map_destroy(fx_map *map);
+fx_status fx_map_reset(fx_ctx *ctx, fx_map *map);
+fx_status fx_map_update(fx_ctx *ctx, fx_map *map,
+    const void *kp_block_device, uint32_t max_scans, uint32_t max_total_keypoints,           /* what the track was given */
+    const fx_pose *poses_device, const int32_t *landmark_of_row_device, const uint32_t *obs_row_device, uint32_t q_max_rows,
+    const fx_landmark *landmarks_device, uint32_t max_landmarks, const fx_track_header *track_header_device, /* what it wrote */
+    uint32_t flags /* FX_MAP_OVERLAP */, int32_t *map_id_of_row_device /* [q_max_rows] or NULL */);
+fx_status fx_map_get(fx_map *map, const fx_map_header **header_device, const fx_map_landmark **landmarks_device);
+fx_status fx_map_read_header(fx_ctx *ctx, fx_map *map, fx_map_header *out_host);
+fx_status fx_map_read_landmarks(fx_ctx *ctx, fx_map *map, uint32_t first, uint32_t count, fx_map_landmark *out_host);
+
 /* Rotation matrix of rotateCloud (ref: node.cpp:161-164): R = Ry(pitch)*Rx(roll)
  * through Eigen's AngleAxisf -> Quaternionf -> toRotationMatrix, all float. Host only. */
 void fx_rotation_from_roll_pitch(double roll, double pitch, float R[9]);
