@@ -548,23 +548,36 @@ def match_reference(rows_q, rows_t, pairs, shifts=12, max_dist2=np.inf, max_rati
 
 
 # ---- scan-to-scan rigid motion from the matches (include/fx.h fx_register_matches)
+class KeypointBlockLayout(tuple):
+    """(k0, n_rows) of a compact keypoint block — the first float4 row of the keypoint area and the rows of the whole block —, which
+    also carries f0, the first u32 word of the flags section."""
+
+    def __new__(cls, f0, k0, n_rows):
+        self = super().__new__(cls, (k0, n_rows))
+        self.f0, self.k0, self.n_rows = f0, k0, n_rows
+        return self
+
+
 def keypoint_block_layout(max_scans, max_total):
-    """(first float4 row of the keypoint area, rows of the whole block) of a compact keypoint block (fx_pack_keypoint_block)."""
-    k0 = 1 + (max_scans + 1 + 3) // 4 + (max_scans + 3) // 4
-    return k0, k0 + max_total
+    """The sections of a compact keypoint block (fx_pack_keypoint_block), the Python statement of csrc/fx_device.h's kp_block_*: as
+    u32 words, the header is [0, 4), kp_offset (padded to whole rows) [4, f0) and the flags [f0, 4 * k0); as float4 rows, the
+    keypoints are [k0, n_rows).  Unpacks as (k0, n_rows); .f0 is an attribute."""
+    f0 = 4 + 4 * ((max_scans + 1 + 3) // 4)
+    k0 = f0 // 4 + (max_scans + 3) // 4
+    return KeypointBlockLayout(f0, k0, k0 + max_total)
 
 
 def keypoint_block_parse(block, max_scans, max_total):
     """A keypoint block (bytes / array, as fx_pack_keypoint_block writes it) as a dict: the header words, kp_offset[scans + 1],
     flags[scans] and "rows", the [keypoints stored, 4] float32 (x, y, z, elevation) rows of the keypoint area."""
     b = np.frombuffer(bytes(block), np.uint8) if not isinstance(block, np.ndarray) else np.ascontiguousarray(block).view(np.uint8).reshape(-1)
-    k0, n_rows = keypoint_block_layout(max_scans, max_total)
+    lay = keypoint_block_layout(max_scans, max_total)
+    f0, k0, n_rows = lay.f0, lay.k0, lay.n_rows
     assert len(b) >= 16 * n_rows, (len(b), max_scans, max_total)
     u = b[:16 * n_rows].view(np.uint32)
     scans, stored, flags_or, mt = (int(x) for x in u[:4])
     stored = min(stored, max_total)
     nb = min(scans, max_scans)
-    f0 = 4 + 4 * ((max_scans + 1 + 3) // 4)
     return {"scans": scans, "keypoints": stored, "flags_or": flags_or, "max_total": mt, "kp_offset": u[4:4 + nb + 1].copy(),
             "flags": u[f0:f0 + nb].copy(), "rows": b[16 * k0:16 * (k0 + stored)].view(np.float32).reshape(-1, 4).copy()}
 
@@ -577,11 +590,12 @@ def keypoint_block_from_rows(rows, max_scans=1, max_total=None):
     n = len(rows)
     max_total = n if max_total is None else int(max_total)
     assert n <= max_total and max_scans >= 1
-    k0, n_rows = keypoint_block_layout(max_scans, max_total)
+    lay = keypoint_block_layout(max_scans, max_total)
+    f0, k0, n_rows = lay.f0, lay.k0, lay.n_rows
     blk = np.zeros((n_rows, 4), np.float32)
     u = blk.view(np.uint32).reshape(-1)
     u[:4] = (1, n, 0, max_total)
-    u[5:4 + 4 * ((max_scans + 1 + 3) // 4)] = n  # kp_offset[0] = 0, every later entry the total
+    u[5:f0] = n  # kp_offset[0] = 0, every later entry the total
     blk[k0:k0 + n, :rows.shape[1]] = rows[:, :4]
     return blk.view(np.uint8).reshape(-1), max_scans, max_total
 

@@ -129,6 +129,28 @@ inline const char *test_hook(const char *name) {
 constexpr uint32_t kMergeCapSmall = 512, kListCap = 4096, kDenseMin = 1024;
 // default CSR block: 128 entries a row (1 KB: the dense pool's 7956 B / 8; the test scenes average 15 to 77 non-zero words)
 constexpr uint32_t kCsrRowEntries = 128;
+
+// The back end's per-context scratch (fx_match_descriptors_csr ... fx_map_update).  One policy for both types: a buffer that is
+// large enough is used as it is — no allocation, no synchronisation; one that is not is replaced by a buffer of
+// max(bytes, twice the old size, 4096) bytes, and the old one is freed only after the context's stream, which may still read
+// it, was synchronised.  Buffers never shrink; a DevScratch is allocated at its first reserve whatever the size; fx_destroy
+// releases them.
+struct DevScratch {
+  uint8_t *d = nullptr;
+  size_t bytes = 0;
+  fx_status reserve(fx_ctx *c, size_t need, const char *what);
+  void release();
+};
+// Pinned host staging, its device twin and the event of the last upload, which the next call waits for before it writes
+// the staging again.
+struct Staging {
+  uint8_t *h = nullptr, *d = nullptr;
+  size_t bytes = 0;
+  hipEvent_t ev = nullptr;
+  fx_status reserve(fx_ctx *c, size_t need, const char *what);  // room for `need` bytes in h and d; h is free to write
+  fx_status upload(fx_ctx *c, size_t n);                        // h[0, n) to d on the context's stream
+  void release();
+};
 }  // namespace
 
 struct fx_ctx {
@@ -228,24 +250,12 @@ struct fx_ctx {
   bool csr_valid = false;        // the last batch was FX_OUT_HOST | FX_OUT_DESC_CSR (fx_get_descriptors_csr)
   uint32_t csr_rows = 0, csr_nnz = 0;
   uint32_t csr_full_rows = 0;    // test hook (FX_CSR_FULL_ROWS): every row through the whole-row path
-  // fx_match_descriptors_csr: one device buffer (the pairs and the work list, the blocks' row norms, the mutual table) and
-  // the pinned staging of its first part; both grow (never shrink) when a call needs more.  match_ev: the last call's copy
-  // out of the staging, which the next call waits for before it writes there
-  uint8_t *d_match = nullptr, *h_match = nullptr;
-  size_t match_dev_bytes = 0, match_host_bytes = 0;
-  hipEvent_t match_ev = nullptr;
-  // fx_register_matches: the pairs on the device and their pinned staging, grown (never shrunk) when a call has more pairs;
-  // reg_ev: the last call's copy out of the staging
-  uint8_t *d_reg = nullptr, *h_reg = nullptr;
-  size_t reg_bytes = 0;
-  hipEvent_t reg_ev = nullptr;
-  // fx_track_landmarks: the per-row scratch arrays, one buffer grown (never shrunk) when a call has more rows
-  uint8_t *d_track = nullptr;
-  uint32_t track_rows = 0;
-  // fx_map_update: the per-landmark scratch (the batch landmark's map id, the blocks' counts), grown (never shrunk) when a call
-  // has a larger max_landmarks
-  uint8_t *d_map = nullptr;
-  uint32_t map_lms = 0;
+  // fx_match_descriptors_csr: the pairs and the work list (staged), and the blocks' row norms and the mutual table
+  Staging match_stage;
+  DevScratch match_scratch;
+  Staging reg_stage;         // fx_register_matches: the pairs
+  DevScratch track_scratch;  // fx_track_landmarks: the per-row scratch arrays
+  DevScratch map_scratch;    // fx_map_update: the batch landmark's map id, the blocks' counts
 };
 
 // A persistent landmark map (include/fx.h fx_map_create): one device buffer, carved up once.
@@ -284,6 +294,68 @@ fx_status host_alloc(fx_ctx *c, T **p, size_t count) {
     fx_status s_ = (expr);        \
     if (s_ != FX_OK) return s_;   \
   } while (0)
+
+fx_status DevScratch::reserve(fx_ctx *c, size_t need, const char *what) {
+  if (d && need <= bytes) return FX_OK;
+  if (d) {
+    FX_HIP(hipStreamSynchronize(c->stream));
+    FX_HIP(hipFree(d));
+    d = nullptr;
+  }
+  const size_t n = std::max({need, 2 * bytes, (size_t)4096});
+  bytes = 0;
+  void *q = nullptr;
+  hipError_t e = hipMalloc(&q, n);
+  if (e != hipSuccess) return fail(FX_ERR_OOM, std::string(what) + " hipMalloc(" + std::to_string(n) + "): " + hipGetErrorString(e));
+  d = (uint8_t *)q, bytes = n;
+  return FX_OK;
+}
+void DevScratch::release() {
+  if (d) (void)hipFree(d);
+}
+fx_status Staging::reserve(fx_ctx *c, size_t need, const char *what) {
+  if (!ev) FX_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  if (need > bytes) {
+    if (d) {
+      FX_HIP(hipStreamSynchronize(c->stream));
+      FX_HIP(hipFree(d));
+      FX_HIP(hipHostFree(h));
+      d = h = nullptr;
+    }
+    const size_t n = std::max({need, 2 * bytes, (size_t)4096});
+    bytes = 0;
+    void *qd = nullptr, *qh = nullptr;
+    hipError_t e = hipMalloc(&qd, n);
+    if (e == hipSuccess && (e = hipHostMalloc(&qh, n, hipHostMallocDefault)) != hipSuccess) (void)hipFree(qd);
+    if (e != hipSuccess) return fail(FX_ERR_OOM, std::string(what) + " hipMalloc + hipHostMalloc(" + std::to_string(n) + "): " + hipGetErrorString(e));
+    d = (uint8_t *)qd, h = (uint8_t *)qh, bytes = n;
+  }
+  FX_HIP(hipEventSynchronize(ev));  // (the last upload; done at once when none was recorded)
+  return FX_OK;
+}
+fx_status Staging::upload(fx_ctx *c, size_t n) {
+  if (!n) return FX_OK;
+  FX_HIP(hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, c->stream));
+  FX_HIP(hipEventRecord(ev, c->stream));
+  return FX_OK;
+}
+void Staging::release() {
+  if (d) (void)hipFree(d);
+  if (h) (void)hipHostFree(h);
+  if (ev) (void)hipEventDestroy(ev);
+}
+
+// The query ranges of the pairs must be disjoint: the match writes one record, the register one inlier word a query row
+fx_status query_ranges_disjoint(const fx_match_pair *pairs, uint32_t n_pairs) {
+  std::vector<std::pair<uint64_t, uint64_t>> r;
+  for (uint32_t p = 0; p < n_pairs; ++p)
+    if (pairs[p].q_rows) r.emplace_back((uint64_t)pairs[p].q_row0, (uint64_t)pairs[p].q_row0 + pairs[p].q_rows);
+  std::sort(r.begin(), r.end());
+  for (size_t i = 1; i < r.size(); ++i)
+    if (r[i].first < r[i - 1].second)
+      return fail(FX_ERR_INVALID_ARG, "query ranges of the pairs overlap at row " + std::to_string(r[i].first));
+  return FX_OK;
+}
 
 // The CSR block's offsets and entry counts are u32: every row of the descriptor pool stored whole must fit
 bool csr_pool_fits(const fx_limits &L) { return (uint64_t)L.max_total_keypoints * FX_DESC_FLOATS <= 0xffffffffull; }
@@ -977,14 +1049,7 @@ void fx_destroy(fx_ctx *c) {
   if (c->d_stage) (void)hipFree(c->d_stage);
   if (c->d_csr) (void)hipFree(c->d_csr);
   if (c->h_csr) (void)hipHostFree(c->h_csr);
-  if (c->d_match) (void)hipFree(c->d_match);
-  if (c->h_match) (void)hipHostFree(c->h_match);
-  if (c->match_ev) (void)hipEventDestroy(c->match_ev);
-  if (c->d_reg) (void)hipFree(c->d_reg);
-  if (c->h_reg) (void)hipHostFree(c->h_reg);
-  if (c->d_track) (void)hipFree(c->d_track);
-  if (c->d_map) (void)hipFree(c->d_map);
-  if (c->reg_ev) (void)hipEventDestroy(c->reg_ev);
+  c->match_stage.release(), c->match_scratch.release(), c->reg_stage.release(), c->track_scratch.release(), c->map_scratch.release();
   for (int i = 0; i < kMetaSlots; ++i)
     if (c->meta_ev[i]) (void)hipEventDestroy(c->meta_ev[i]);
   for (hipEvent_t e : c->ev_ring) (void)hipEventDestroy(e);
@@ -1585,15 +1650,7 @@ fx_status fx_match_descriptors_csr(fx_ctx *c, const void *q_block, uint32_t q_ma
   if (opt) o = *opt;
   if (o.azimuth_shifts != 12u && o.azimuth_shifts != 1u) return fail(FX_ERR_INVALID_ARG, "azimuth_shifts must be 12 or 1");
   if (o.max_dist2 != o.max_dist2 || o.max_ratio != o.max_ratio) return fail(FX_ERR_INVALID_ARG, "NaN threshold");
-  {  // the query ranges must be disjoint: one record a query row
-    std::vector<std::pair<uint64_t, uint64_t>> r;
-    for (uint32_t p = 0; p < n_pairs; ++p)
-      if (pairs[p].q_rows) r.emplace_back((uint64_t)pairs[p].q_row0, (uint64_t)pairs[p].q_row0 + pairs[p].q_rows);
-    std::sort(r.begin(), r.end());
-    for (size_t i = 1; i < r.size(); ++i)
-      if (r[i].first < r[i - 1].second)
-        return fail(FX_ERR_INVALID_ARG, "query ranges of the pairs overlap at row " + std::to_string(r[i].first));
-  }
+  FX_TRY(query_ranges_disjoint(pairs, n_pairs));
   FX_HIP(hipSetDevice(c->device));
   // work list (pair, tile of query rows) from the ranges the layouts admit — the kernel clips them to rows_stored —, and each
   // pair's slots in the mutual table
@@ -1607,33 +1664,12 @@ fx_status fx_match_descriptors_csr(fx_ctx *c, const void *q_block, uint32_t q_ma
   if (n_items > 0x7fffffffull || mut_n > 0xffffffffull) return fail(FX_ERR_TOO_LARGE, "too many query tiles / train rows in the pairs");
   const bool same = q_block == t_block && q_max_rows == t_max_rows && q_cap == t_cap;
   const size_t staged = (size_t)n_pairs * sizeof(FxMatchPairDev) + (size_t)n_items * sizeof(uint2);
-  const size_t off_qn = (staged + 15u) & ~(size_t)15, off_tn = off_qn + (size_t)q_max_rows * 8u;
-  const size_t off_mut = same ? off_tn : off_tn + (size_t)t_max_rows * 8u, need = off_mut + (size_t)mut_n * 8u + 16u;
-  if (!c->match_ev) FX_HIP(hipEventCreateWithFlags(&c->match_ev, hipEventDisableTiming));
-  if (need > c->match_dev_bytes) {
-    if (c->d_match) {
-      FX_HIP(hipStreamSynchronize(c->stream));
-      FX_HIP(hipFree(c->d_match));
-      c->d_match = nullptr, c->match_dev_bytes = 0;
-    }
-    const size_t bytes = std::max(need, 2u * c->match_dev_bytes);
-    void *q = nullptr;
-    hipError_t e = hipMalloc(&q, bytes);
-    if (e != hipSuccess) return fail(FX_ERR_OOM, std::string("match buffer hipMalloc(") + std::to_string(bytes) + "): " + hipGetErrorString(e));
-    c->d_match = (uint8_t *)q, c->match_dev_bytes = bytes;
-  }
-  FX_HIP(hipEventSynchronize(c->match_ev));  // (the last call's copy out of the staging; done at once when none was recorded)
-  if (staged > c->match_host_bytes) {
-    if (c->h_match) FX_HIP(hipHostFree(c->h_match));
-    c->h_match = nullptr, c->match_host_bytes = 0;
-    void *q = nullptr;
-    hipError_t e = hipHostMalloc(&q, 2u * staged, hipHostMallocDefault);
-    if (e != hipSuccess) return fail(FX_ERR_OOM, std::string("match staging hipHostMalloc(") + std::to_string(2u * staged) + "): " + hipGetErrorString(e));
-    c->h_match = (uint8_t *)q, c->match_host_bytes = 2u * staged;
-  }
+  const size_t off_tn = (size_t)q_max_rows * 8u, off_mut = same ? off_tn : off_tn + (size_t)t_max_rows * 8u;  // (the query norms at 0)
+  FX_TRY(c->match_stage.reserve(c, staged, "match pairs staging"));
+  FX_TRY(c->match_scratch.reserve(c, off_mut + (size_t)mut_n * 8u, "match scratch"));
   if (staged) {
-    FxMatchPairDev *hp = (FxMatchPairDev *)c->h_match;
-    uint2 *hi = (uint2 *)(c->h_match + (size_t)n_pairs * sizeof(FxMatchPairDev));
+    FxMatchPairDev *hp = (FxMatchPairDev *)c->match_stage.h;
+    uint2 *hi = (uint2 *)(c->match_stage.h + (size_t)n_pairs * sizeof(FxMatchPairDev));
     uint64_t m = 0;
     for (uint32_t p = 0; p < n_pairs; ++p) {
       const uint32_t q0 = std::min(pairs[p].q_row0, q_max_rows), t0 = std::min(pairs[p].t_row0, t_max_rows);
@@ -1642,16 +1678,15 @@ fx_status fx_match_descriptors_csr(fx_ctx *c, const void *q_block, uint32_t q_ma
       const uint32_t tiles = (std::min(pairs[p].q_rows, q_max_rows - q0) + tile - 1u) / tile;
       for (uint32_t k = 0; k < tiles; ++k) *hi++ = make_uint2(p, k);
     }
-    FX_HIP(hipMemcpyAsync(c->d_match, c->h_match, staged, hipMemcpyHostToDevice, c->stream));
-    FX_HIP(hipEventRecord(c->match_ev, c->stream));
+    FX_TRY(c->match_stage.upload(c, staged));
   }
   FxMatchArgs A{};
   A.q_block = (const uint32_t *)q_block, A.t_block = (const uint32_t *)t_block;
   A.q_max_rows = q_max_rows, A.q_cap = q_cap, A.t_max_rows = t_max_rows, A.t_cap = t_cap;
-  A.pairs = (const FxMatchPairDev *)c->d_match;
-  A.items = (const uint2 *)(c->d_match + (size_t)n_pairs * sizeof(FxMatchPairDev));
-  A.q_norm = (const double *)(c->d_match + off_qn), A.t_norm = same ? A.q_norm : (const double *)(c->d_match + off_tn);
-  A.mut = (unsigned long long *)(c->d_match + off_mut);
+  A.pairs = (const FxMatchPairDev *)c->match_stage.d;
+  A.items = (const uint2 *)(c->match_stage.d + (size_t)n_pairs * sizeof(FxMatchPairDev));
+  A.q_norm = (const double *)c->match_scratch.d, A.t_norm = same ? A.q_norm : (const double *)(c->match_scratch.d + off_tn);
+  A.mut = (unsigned long long *)(c->match_scratch.d + off_mut);
   A.out = out;
   A.max_dist2 = o.max_dist2, A.max_ratio = o.max_ratio, A.mutual = o.mutual ? 1u : 0u;
   FX_HIP(fxk_match(c->stream, A, (uint32_t)n_items, (uint32_t)mut_n, o.azimuth_shifts));
@@ -1682,43 +1717,17 @@ fx_status fx_register_matches(fx_ctx *c, const void *q_kp, uint32_t q_max_scans,
     return fail(FX_ERR_INVALID_ARG, "inlier_dist and min_baseline must be finite and positive");
   if (o.hyp_corr < 2u || o.hyp_corr > 128u) return fail(FX_ERR_INVALID_ARG, "hyp_corr must be 2..128");
   if (o.min_inliers < 2u) return fail(FX_ERR_INVALID_ARG, "min_inliers must be at least 2");
-  {  // the query ranges must be disjoint, as they were for the match: one inlier word a query row
-    std::vector<std::pair<uint64_t, uint64_t>> r;
-    for (uint32_t p = 0; p < n_pairs; ++p)
-      if (pairs[p].q_rows) r.emplace_back((uint64_t)pairs[p].q_row0, (uint64_t)pairs[p].q_row0 + pairs[p].q_rows);
-    std::sort(r.begin(), r.end());
-    for (size_t i = 1; i < r.size(); ++i)
-      if (r[i].first < r[i - 1].second)
-        return fail(FX_ERR_INVALID_ARG, "query ranges of the pairs overlap at row " + std::to_string(r[i].first));
-  }
+  FX_TRY(query_ranges_disjoint(pairs, n_pairs));
   FX_HIP(hipSetDevice(c->device));
   const size_t staged = (size_t)n_pairs * sizeof(fx_match_pair);
-  if (!c->reg_ev) FX_HIP(hipEventCreateWithFlags(&c->reg_ev, hipEventDisableTiming));
-  if (staged > c->reg_bytes) {
-    if (c->d_reg) {
-      FX_HIP(hipStreamSynchronize(c->stream));
-      FX_HIP(hipFree(c->d_reg));
-      FX_HIP(hipHostFree(c->h_reg));
-      c->d_reg = c->h_reg = nullptr, c->reg_bytes = 0;
-    }
-    const size_t bytes = std::max(staged, (size_t)4096);
-    void *d = nullptr, *h = nullptr;
-    hipError_t e = hipMalloc(&d, bytes);
-    if (e == hipSuccess && (e = hipHostMalloc(&h, bytes, hipHostMallocDefault)) != hipSuccess) (void)hipFree(d);
-    if (e != hipSuccess) return fail(FX_ERR_OOM, std::string("register pairs buffer (") + std::to_string(bytes) + "): " + hipGetErrorString(e));
-    c->d_reg = (uint8_t *)d, c->h_reg = (uint8_t *)h, c->reg_bytes = bytes;
-  }
-  if (staged) {
-    FX_HIP(hipEventSynchronize(c->reg_ev));  // (the last call's copy out of the staging; done at once when none was recorded)
-    std::memcpy(c->h_reg, pairs, staged);
-    FX_HIP(hipMemcpyAsync(c->d_reg, c->h_reg, staged, hipMemcpyHostToDevice, c->stream));
-    FX_HIP(hipEventRecord(c->reg_ev, c->stream));
-  }
+  FX_TRY(c->reg_stage.reserve(c, staged, "register pairs staging"));
+  if (staged) std::memcpy(c->reg_stage.h, pairs, staged);
+  FX_TRY(c->reg_stage.upload(c, staged));
   FxRegisterArgs A{};
   A.q_kp = (const uint32_t *)q_kp, A.t_kp = (const uint32_t *)t_kp;
   A.q_max_scans = q_max_scans, A.q_max_total = q_max_total, A.t_max_scans = t_max_scans, A.t_max_total = t_max_total;
   A.matches = matches, A.q_max_rows = q_max_rows;
-  A.pairs = c->d_reg, A.out = out, A.inlier = inlier;
+  A.pairs = c->reg_stage.d, A.out = out, A.inlier = inlier;
   A.inlier_dist = o.inlier_dist, A.min_baseline = o.min_baseline;
   A.hyp_corr = o.hyp_corr, A.min_inliers = o.min_inliers, A.require_flags = o.require_flags;
   FX_HIP(fxk_register(c->stream, A, n_pairs));
@@ -1757,29 +1766,16 @@ fx_status fx_track_landmarks(fx_ctx *c, const void *kp, uint32_t max_scans, uint
       if (!std::isfinite(v)) return fail(FX_ERR_INVALID_ARG, "init_pose must be finite");
   }
   FX_HIP(hipSetDevice(c->device));
-  const size_t wg = fxk_track_wg_rows();
-  if (q_max_rows > c->track_rows || !c->d_track) {
-    if (c->d_track) {
-      FX_HIP(hipStreamSynchronize(c->stream));
-      FX_HIP(hipFree(c->d_track));
-      c->d_track = nullptr, c->track_rows = 0;
-    }
-    const size_t rows = std::max((size_t)q_max_rows, (size_t)1024);
-    const size_t bytes = (rows * 11 + 2 * ((rows + wg - 1) / wg) + 4) * sizeof(uint32_t);
-    void *d = nullptr;
-    hipError_t e = hipMalloc(&d, bytes);
-    if (e != hipSuccess) return fail(FX_ERR_OOM, std::string("track scratch (") + std::to_string(bytes) + "): " + hipGetErrorString(e));
-    c->d_track = (uint8_t *)d, c->track_rows = (uint32_t)rows;
-  }
-  {  // the scratch arrays, [track_rows] each; the two (root, depth) buffers first: they are 8-byte words
-    const size_t n = c->track_rows;
-    uint32_t *w = (uint32_t *)c->d_track;
+  {  // the scratch arrays, [q_max_rows] each; the two (root, depth) buffers first: they are 8-byte words
+    const size_t n = q_max_rows, n_blocks = (n + fxk_track_wg_rows() - 1) / fxk_track_wg_rows();
+    FX_TRY(c->track_scratch.reserve(c, (11 * n + 2 * n_blocks + 4) * sizeof(uint32_t), "track scratch"));
+    uint32_t *w = (uint32_t *)c->track_scratch.d;
     A.jump[0] = (uint2 *)w, A.jump[1] = (uint2 *)(w + 2 * n);
     w += 4 * n;
     A.scan_of = w, A.child = w + n, A.prop = (int32_t *)(w + 2 * n), A.len = w + 3 * n, A.lm_id = (int32_t *)(w + 4 * n), A.obs0 = w + 5 * n,
     A.lm_root = w + 6 * n;
     A.bsum = w + 7 * n;
-    A.counters = A.bsum + 2 * ((n + wg - 1) / wg);
+    A.counters = A.bsum + 2 * n_blocks;
   }
   A.kp = (const uint32_t *)kp, A.max_scans = max_scans, A.max_total = max_total;
   A.matches = matches, A.inlier = inlier, A.q_max_rows = q_max_rows;
@@ -1842,22 +1838,10 @@ fx_status fx_map_update(fx_ctx *c, fx_map *m, const void *kp, uint32_t max_scans
       ((uintptr_t)landmarks % 8) != 0 || ((uintptr_t)track_header % 4) != 0 || ((uintptr_t)map_id_of_row % 4) != 0)
     return fail(FX_ERR_INVALID_ARG, "the keypoint block must be 16-byte, the records 8-byte, the words 4-byte aligned");
   FX_HIP(hipSetDevice(c->device));
-  const size_t wg = fxk_map_wg();
-  if (max_landmarks > c->map_lms || !c->d_map) {
-    if (c->d_map) {
-      FX_HIP(hipStreamSynchronize(c->stream));
-      FX_HIP(hipFree(c->d_map));
-      c->d_map = nullptr, c->map_lms = 0;
-    }
-    const size_t n = std::max((size_t)max_landmarks, (size_t)1024);
-    const size_t bytes = (n + 2 * ((n + wg - 1) / wg)) * sizeof(uint32_t);
-    void *d = nullptr;
-    hipError_t e = hipMalloc(&d, bytes);
-    if (e != hipSuccess) return fail(FX_ERR_OOM, std::string("map scratch (") + std::to_string(bytes) + "): " + hipGetErrorString(e));
-    c->d_map = (uint8_t *)d, c->map_lms = (uint32_t)n;
-  }
+  const size_t n_blocks = ((size_t)max_landmarks + fxk_map_wg() - 1) / fxk_map_wg();
+  FX_TRY(c->map_scratch.reserve(c, ((size_t)max_landmarks + 2 * n_blocks) * sizeof(uint32_t), "map scratch"));
   FxMapArgs A = m->a;
-  A.id_of_lm = (int32_t *)c->d_map, A.bsum = (uint32_t *)c->d_map + c->map_lms;
+  A.id_of_lm = (int32_t *)c->map_scratch.d, A.bsum = (uint32_t *)c->map_scratch.d + max_landmarks;
   A.kp = (const uint32_t *)kp, A.max_scans = max_scans, A.max_total = max_total;
   A.poses = poses, A.landmark_of_row = landmark_of_row, A.obs_row = obs_row, A.q_max_rows = q_max_rows;
   A.landmarks = landmarks, A.max_landmarks = max_landmarks, A.track_header = track_header;

@@ -3,6 +3,8 @@
 #define FX_DEVICE_H_
 #include <stdint.h>
 
+#include "../../include/fx.h"
+
 // One scan of the batch as the kernels see it.
 struct FxScanMeta {
   const float *pts;   // device pointer, records of stride_f floats, x y z at 0 1 2
@@ -69,6 +71,70 @@ struct FxScTables {
 // each rounded up to 16 bytes; header 16 B, then row_ptr, col, val
 __host__ __device__ inline size_t csr_rp_words(uint32_t max_rows) { return ((size_t)max_rows + 1u + 3u) & ~(size_t)3; }
 __host__ __device__ inline size_t csr_cap_words(uint32_t cap) { return ((size_t)cap + 3u) & ~(size_t)3; }
+// Compact keypoint block (include/fx.h fx_pack_keypoint_block; k_pack_kp_block writes it): float4 rows.  Row 0 the header words,
+// then kp_offset[max_scans + 1] and flags[max_scans], four words a row each, then max_total (x, y, z, elevation) rows.  This is
+// the layout's one definition on the device and in the host driver (Python: capi.keypoint_block_layout).
+__host__ __device__ inline uint32_t kp_block_off_rows(uint32_t max_scans) { return (max_scans + 1u + 3u) / 4u; }
+__host__ __device__ inline uint32_t kp_block_flag_rows(uint32_t max_scans) { return (max_scans + 3u) / 4u; }
+__host__ __device__ inline uint32_t kp_block_first_row(uint32_t max_scans) { return 1u + kp_block_off_rows(max_scans) + kp_block_flag_rows(max_scans); }
+__host__ __device__ inline size_t kp_block_bytes(uint32_t max_scans, uint32_t max_total) { return ((size_t)kp_block_first_row(max_scans) + max_total) * 16; }
+// What the back end's kernels (fx_match / fx_register / fx_track / fx_map .hip) share.
+// a block's kp_offset section and its keypoint rows, as float4 or as the uint4 words they are
+__device__ __forceinline__ const uint32_t *kp_block_offsets(const uint32_t *block) { return block + 4; }
+template <typename Row>
+__device__ __forceinline__ const Row *kp_block_rows(const uint32_t *block, uint32_t max_scans) {
+  return reinterpret_cast<const Row *>(block) + kp_block_first_row(max_scans);
+}
+__device__ __forceinline__ bool finite3(float4 p) { return isfinite(p.x) && isfinite(p.y) && isfinite(p.z); }
+// the rows [row0, row0 + n) of a pair that lie below `stored`
+__device__ __forceinline__ void clip_range(uint32_t row0, uint32_t n, uint32_t stored, uint32_t &lo, uint32_t &hi) {
+  hi = (uint32_t)min((unsigned long long)row0 + n, (unsigned long long)stored);
+  lo = min(row0, hi);
+}
+// The world-frame point of an observation: keypoint row p under the pose P of its scan, fp64, in exactly this operation order
+// (the build's -ffp-contract=off keeps every operation its own rounding).  include/fx.h promises that the map equals one long
+// track bit for bit: that holds because k_track_fuse and k_map_accumulate both take the point from here.
+__device__ __forceinline__ void world_point(const fx_pose &P, float4 p, double &wx, double &wy, double &wz) {
+  const double x = (double)p.x, y = (double)p.y;
+  wx = (P.c * x - P.s * y) + P.tx;
+  wy = (P.s * x + P.c * y) + P.ty;
+  wz = (double)p.z + P.tz;
+}
+// exclusive prefix of (a, b) over the threads of a workgroup of NWAVE wavefronts, and the totals; s_w: [2][NWAVE] words of LDS
+template <uint32_t NWAVE>
+__device__ __forceinline__ void wg_scan2(uint32_t a, uint32_t b, uint32_t *s_w, uint32_t &ex_a, uint32_t &ex_b, uint32_t &tot_a, uint32_t &tot_b) {
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint32_t ia = a, ib = b;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t ua = (uint32_t)__shfl_up((int)ia, o, 64), ub = (uint32_t)__shfl_up((int)ib, o, 64);
+    if (lane >= (uint32_t)o) ia += ua, ib += ub;
+  }
+  __syncthreads();  // (s_w's readers of the call before)
+  if (lane == 63u) s_w[wave] = ia, s_w[NWAVE + wave] = ib;
+  __syncthreads();
+  ex_a = ia - a, ex_b = ib - b, tot_a = tot_b = 0u;
+#pragma unroll
+  for (uint32_t w = 0; w < NWAVE; ++w) {
+    const uint32_t na = s_w[w], nb = s_w[NWAVE + w];
+    ex_a += w < wave ? na : 0u, ex_b += w < wave ? nb : 0u;
+    tot_a += na, tot_b += nb;
+  }
+}
+// one workgroup: the blocks' counts bsum[2][n_blocks] to their exclusive prefix, in place, and the totals
+template <uint32_t NWAVE>
+__device__ __forceinline__ void wg_scan2_blocks(uint32_t *bsum, uint32_t n_blocks, uint32_t *s_w, uint32_t &tot_a, uint32_t &tot_b) {
+  uint32_t base_a = 0u, base_b = 0u;
+  for (uint32_t i0 = 0u; i0 < n_blocks; i0 += NWAVE * 64u) {
+    const uint32_t i = i0 + threadIdx.x;
+    const uint32_t a = i < n_blocks ? bsum[i] : 0u, b = i < n_blocks ? bsum[n_blocks + i] : 0u;
+    uint32_t ea, eb, ta, tb;
+    wg_scan2<NWAVE>(a, b, s_w, ea, eb, ta, tb);
+    if (i < n_blocks) bsum[i] = base_a + ea, bsum[n_blocks + i] = base_b + eb;
+    base_a += ta, base_b += tb;
+  }
+  tot_a = base_a, tot_b = base_b;
+}
 // fx_match_descriptors_csr (csrc/fx_match.hip): one pair of row ranges as the kernels see it, and a launch's arguments.
 struct FxMatchPairDev {
   uint32_t q_row0, q_rows, t_row0, t_rows;
@@ -150,7 +216,7 @@ struct FxMapArgs {
   uint32_t flags;
   int32_t *map_id_of_row;       // [q_max_rows] or null
   int32_t *id_of_lm;            // [max_landmarks]: k_map_join's verdict (>= 0 continues that id, -1 new, -2 not a landmark), then the map id or -1
-  uint32_t *bsum;               // [2][blocks of FXM_WG landmarks]: new / continued landmarks of the block
+  uint32_t *bsum;               // [2][blocks of FXMAP_WG landmarks]: new / continued landmarks of the block
 };
 #define FX_TRACK_NONE 0xffffffffu
 #define FX_N_HINTS 8     // tier_hint[]: 0 / 1 rings handed to the second run tier / the workgroup tier (largest XCD class), 2 big merges, 3 huge merges, 4 dense rows, 5 dense support points, 6 scans k_front handed to k_front_redo, 7 scans handed to the slow tier (k_slow)

@@ -6458,8 +6458,7 @@ extern "C" __global__ __launch_bounds__(FX_WG) void k_pack_kp_records(FxDevParam
 // batch repeat the total); then flags[max_scans] (u32, four a row); then max_total keypoint rows (x, y, z, elevation), packed in
 // scan order, zero beyond the total.  A batch with more keypoints than max_total is cut there: the scans that lose keypoints
 // carry FX_FLAG_KP_OVERFLOW.  The size is fixed by (max_scans, max_total): every rank hands the collective the same count.
-__host__ __device__ inline uint32_t kp_block_off_rows(uint32_t max_scans) { return (max_scans + 1u + 3u) / 4u; }
-__host__ __device__ inline uint32_t kp_block_flag_rows(uint32_t max_scans) { return (max_scans + 3u) / 4u; }
+// (The sections' sizes are fx_device.h's kp_block_*: the consumers find the rows by the same functions.)
 extern "C" __global__ __launch_bounds__(FX_WG) void k_pack_kp_block(FxDevParams P, FxBuffers B, uint32_t batch, uint32_t *dst, uint32_t max_scans,
                                                                      uint32_t max_total) {
   __shared__ uint32_t s_or[FX_NWAVE];
@@ -6974,9 +6973,7 @@ void fxk_pack_kp_records(hipStream_t s, const FxDevParams &P, const FxBuffers &B
                          uint32_t rec_kp) {
   hipLaunchKernelGGL(k_pack_kp_records, dim3(batch), dim3(FX_WG), 0, s, P, B, batch, (float4 *)dst, rec_kp);
 }
-size_t fxk_kp_block_bytes(uint32_t max_scans, uint32_t max_total) {
-  return ((size_t)1 + kp_block_off_rows(max_scans) + kp_block_flag_rows(max_scans) + max_total) * 16;
-}
+size_t fxk_kp_block_bytes(uint32_t max_scans, uint32_t max_total) { return kp_block_bytes(max_scans, max_total); }
 void fxk_pack_kp_block(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, void *dst, uint32_t max_scans, uint32_t max_total,
                        uint32_t grid) {
   hipLaunchKernelGGL(k_pack_kp_block, dim3(grid), dim3(FX_WG), 0, s, P, B, batch, (uint32_t *)dst, max_scans, max_total);

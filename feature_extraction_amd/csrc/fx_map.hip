@@ -7,7 +7,7 @@
 // with any number of contexts in flight.  Every count comes from the track's header on the device; the grids are sized by
 // q_max_rows and max_landmarks and exit early.
 //
-// Launches, in stream order (FXM_WG = 256 rows or landmarks a workgroup):
+// Launches, in stream order (FXMAP_WG = 256 rows or landmarks a workgroup):
 //   k_map_compare     a thread a row of scan 0: its four words against the stored copy of the carry scan's row; any difference
 //                     sets st[0] (only with FX_MAP_OVERLAP and equal row counts)
 //   k_map_join        a thread a batch landmark: continues carry[first_row - kp_offset[0]], new, or not a landmark; the block's
@@ -17,6 +17,8 @@
 //                     sequential pass over its obs_row segment into the private sums, the public record
 //   k_map_rows        a thread a row: map_id_of_row, and for the rows of scan S - 1 the carry table and the carry scan's copy
 //   k_map_finish      one lane: the header
+// The block's layout, the workgroup scan and the world-frame point of an observation are fx_device.h's (kp_block_*, wg_scan2,
+// world_point): the ones fx_track.hip uses, which is what keeps the map equal to one long track.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stddef.h>
@@ -25,8 +27,8 @@
 #include "fx_device.h"
 #include "../../include/fx.h"
 
-#define FXM_WG 256
-#define FXM_NWAVE (FXM_WG / 64)
+#define FXMAP_WG 256
+#define FXMAP_NWAVE (FXMAP_WG / 64)
 
 static_assert(sizeof(fx_map_landmark) == 48 && sizeof(fx_map_header) == 88 && offsetof(fx_map_header, last_pose) == 40, "include/fx.h");
 
@@ -40,8 +42,8 @@ struct View {
 __device__ __forceinline__ View view(const FxMapArgs &A) {
   const fx_track_header *h = reinterpret_cast<const fx_track_header *>(A.track_header);
   View v;
-  v.off = A.kp + 4;
-  v.kp = reinterpret_cast<const uint4 *>(A.kp) + (1u + (A.max_scans + 1u + 3u) / 4u + (A.max_scans + 3u) / 4u);
+  v.off = kp_block_offsets(A.kp);
+  v.kp = kp_block_rows<uint4>(A.kp, A.max_scans);
   v.S = min(h->scans, A.max_scans);
   v.rows = min(min(h->rows, A.max_total), A.q_max_rows);
   v.L = v.S ? min(h->n_landmarks, A.max_landmarks) : 0u;
@@ -54,26 +56,6 @@ __device__ __forceinline__ bool overlap_counts(const FxMapArgs &A, const View &v
   const fx_map_header *H = reinterpret_cast<const fx_map_header *>(A.header);
   return (A.flags & FX_MAP_OVERLAP) && v.S && H->scans && H->carry_rows == scan_hi(v, 0u) - scan_lo(v, 0u);
 }
-// exclusive prefix of (a, b) over the workgroup's threads and the totals; s_w: [2][FXM_NWAVE] words of LDS
-__device__ __forceinline__ void wg_scan2(uint32_t a, uint32_t b, uint32_t *s_w, uint32_t &ex_a, uint32_t &ex_b, uint32_t &tot_a, uint32_t &tot_b) {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  uint32_t ia = a, ib = b;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t ua = (uint32_t)__shfl_up((int)ia, o, 64), ub = (uint32_t)__shfl_up((int)ib, o, 64);
-    if (lane >= (uint32_t)o) ia += ua, ib += ub;
-  }
-  __syncthreads();  // (s_w's readers of the call before)
-  if (lane == 63u) s_w[wave] = ia, s_w[FXM_NWAVE + wave] = ib;
-  __syncthreads();
-  ex_a = ia - a, ex_b = ib - b, tot_a = tot_b = 0u;
-#pragma unroll
-  for (uint32_t w = 0; w < FXM_NWAVE; ++w) {
-    const uint32_t na = s_w[w], nb = s_w[FXM_NWAVE + w];
-    ex_a += w < wave ? na : 0u, ex_b += w < wave ? nb : 0u;
-    tot_a += na, tot_b += nb;
-  }
-}
 }  // namespace
 
 extern "C" __global__ __launch_bounds__(64) void k_map_reset(FxMapArgs A) {
@@ -84,8 +66,8 @@ extern "C" __global__ __launch_bounds__(64) void k_map_reset(FxMapArgs A) {
   for (uint32_t i = 0; i < FX_MAP_ST_WORDS; ++i) A.st[i] = 0u;
 }
 
-extern "C" __global__ __launch_bounds__(FXM_WG) void k_map_compare(FxMapArgs A) {
-  const uint32_t j = blockIdx.x * FXM_WG + threadIdx.x;
+extern "C" __global__ __launch_bounds__(FXMAP_WG) void k_map_compare(FxMapArgs A) {
+  const uint32_t j = blockIdx.x * FXMAP_WG + threadIdx.x;
   const View V = view(A);
   if (!overlap_counts(A, V)) return;
   const uint32_t lo = scan_lo(V, 0u), n0 = scan_hi(V, 0u) - lo;
@@ -97,9 +79,9 @@ extern "C" __global__ __launch_bounds__(FXM_WG) void k_map_compare(FxMapArgs A) 
   if (__ballot(differs) && (threadIdx.x & 63u) == 0u) atomicOr(&A.st[0], 1u);
 }
 
-extern "C" __global__ __launch_bounds__(FXM_WG) void k_map_join(FxMapArgs A, uint32_t n_blocks) {
-  __shared__ uint32_t s_w[2 * FXM_NWAVE];
-  const uint32_t i = blockIdx.x * FXM_WG + threadIdx.x;
+extern "C" __global__ __launch_bounds__(FXMAP_WG) void k_map_join(FxMapArgs A, uint32_t n_blocks) {
+  __shared__ uint32_t s_w[2 * FXMAP_NWAVE];
+  const uint32_t i = blockIdx.x * FXMAP_WG + threadIdx.x;
   const View V = view(A);
   const fx_map_header *H = reinterpret_cast<const fx_map_header *>(A.header);
   uint32_t is_new = 0u, is_joined = 0u;
@@ -120,21 +102,14 @@ extern "C" __global__ __launch_bounds__(FXM_WG) void k_map_join(FxMapArgs A, uin
     A.id_of_lm[i] = ok ? g : -2;
   }
   uint32_t ea, eb, ta, tb;
-  wg_scan2(is_new, is_joined, s_w, ea, eb, ta, tb);
+  wg_scan2<FXMAP_NWAVE>(is_new, is_joined, s_w, ea, eb, ta, tb);
   if (threadIdx.x == 0u) A.bsum[blockIdx.x] = ta, A.bsum[n_blocks + blockIdx.x] = tb;
 }
 
-extern "C" __global__ __launch_bounds__(FXM_WG) void k_map_top(FxMapArgs A, uint32_t n_blocks) {
-  __shared__ uint32_t s_w[2 * FXM_NWAVE];
-  uint32_t base_a = 0u, base_b = 0u;
-  for (uint32_t i0 = 0u; i0 < n_blocks; i0 += FXM_WG) {  // the blocks' counts to their exclusive prefix, in place
-    const uint32_t i = i0 + threadIdx.x;
-    const uint32_t a = i < n_blocks ? A.bsum[i] : 0u, b = i < n_blocks ? A.bsum[n_blocks + i] : 0u;
-    uint32_t ea, eb, ta, tb;
-    wg_scan2(a, b, s_w, ea, eb, ta, tb);
-    if (i < n_blocks) A.bsum[i] = base_a + ea, A.bsum[n_blocks + i] = base_b + eb;
-    base_a += ta, base_b += tb;
-  }
+extern "C" __global__ __launch_bounds__(FXMAP_WG) void k_map_top(FxMapArgs A, uint32_t n_blocks) {
+  __shared__ uint32_t s_w[2 * FXMAP_NWAVE];
+  uint32_t base_a, base_b;
+  wg_scan2_blocks<FXMAP_NWAVE>(A.bsum, n_blocks, s_w, base_a, base_b);
   if (threadIdx.x == 0u) {
     const View V = view(A);
     const fx_map_header *H = reinterpret_cast<const fx_map_header *>(A.header);
@@ -146,14 +121,14 @@ extern "C" __global__ __launch_bounds__(FXM_WG) void k_map_top(FxMapArgs A, uint
   }
 }
 
-extern "C" __global__ __launch_bounds__(FXM_WG) void k_map_accumulate(FxMapArgs A) {
-  __shared__ uint32_t s_w[2 * FXM_NWAVE];
-  const uint32_t i = blockIdx.x * FXM_WG + threadIdx.x;
+extern "C" __global__ __launch_bounds__(FXMAP_WG) void k_map_accumulate(FxMapArgs A) {
+  __shared__ uint32_t s_w[2 * FXMAP_NWAVE];
+  const uint32_t i = blockIdx.x * FXMAP_WG + threadIdx.x;
   const View V = view(A);
   const fx_map_header *H = reinterpret_cast<const fx_map_header *>(A.header);
   const int32_t verdict = i < V.L ? A.id_of_lm[i] : -2;
   uint32_t ea, eb, ta, tb;
-  wg_scan2(verdict == -1 ? 1u : 0u, 0u, s_w, ea, eb, ta, tb);
+  wg_scan2<FXMAP_NWAVE>(verdict == -1 ? 1u : 0u, 0u, s_w, ea, eb, ta, tb);
   const bool joined = verdict >= 0;
   const uint32_t id = joined ? (uint32_t)verdict : H->n_needed + A.bsum[blockIdx.x] + ea;
   const bool stored = verdict >= -1 && id < A.cap;
@@ -175,10 +150,8 @@ extern "C" __global__ __launch_bounds__(FXM_WG) void k_map_accumulate(FxMapArgs 
       R.n_obs = 0u, R.first_scan = scan_base + lm.first_scan, R.segment = seg_base + poses[lm.first_scan].segment, R.flags = 0u;
     }
     for (uint32_t k = joined ? 1u : 0u; k < lm.n_obs; ++k) {
-      const float4 p = kp[min(A.obs_row[lm.obs0 + k], V.rows - 1u)];  // (the track's rows are below `rows`)
-      const fx_pose P = poses[lm.first_scan + k];
-      const double x = (double)p.x, y = (double)p.y;
-      const double wx = (P.c * x - P.s * y) + P.tx, wy = (P.s * x + P.c * y) + P.ty, wz = (double)p.z + P.tz;
+      double wx, wy, wz;  // (the track's rows are below `rows`)
+      world_point(poses[lm.first_scan + k], kp[min(A.obs_row[lm.obs0 + k], V.rows - 1u)], wx, wy, wz);
       if (!joined && k == 0u) ax = wx, ay = wy;
       const double dx = wx - ax, dy = wy - ay;
       sx += wx, sy += wy, sz += wz;
@@ -197,12 +170,12 @@ extern "C" __global__ __launch_bounds__(FXM_WG) void k_map_accumulate(FxMapArgs 
     *rec = R;
   }
   if (i < V.L) A.id_of_lm[i] = stored ? (int32_t)id : -1;
-  wg_scan2(added, 0u, s_w, ea, eb, ta, tb);
+  wg_scan2<FXMAP_NWAVE>(added, 0u, s_w, ea, eb, ta, tb);
   if (threadIdx.x == 0u && ta) atomicAdd(&A.st[7], ta);
 }
 
-extern "C" __global__ __launch_bounds__(FXM_WG) void k_map_rows(FxMapArgs A) {
-  const uint32_t r = blockIdx.x * FXM_WG + threadIdx.x;
+extern "C" __global__ __launch_bounds__(FXMAP_WG) void k_map_rows(FxMapArgs A) {
+  const uint32_t r = blockIdx.x * FXMAP_WG + threadIdx.x;
   if (r >= A.q_max_rows) return;
   const View V = view(A);
   int32_t id = -1;
@@ -253,10 +226,10 @@ extern "C" hipError_t fxk_map_reset(hipStream_t s, const FxMapArgs &A) {
 }
 
 extern "C" hipError_t fxk_map_update(hipStream_t s, const FxMapArgs &A) {
-  const dim3 wg(FXM_WG);
+  const dim3 wg(FXMAP_WG);
   const uint32_t nc = A.q_max_rows < A.max_carry ? A.q_max_rows : A.max_carry;
-  const uint32_t nl = (A.max_landmarks + FXM_WG - 1u) / FXM_WG, nr = (A.q_max_rows + FXM_WG - 1u) / FXM_WG;
-  if ((A.flags & FX_MAP_OVERLAP) && nc) hipLaunchKernelGGL(k_map_compare, dim3((nc + FXM_WG - 1u) / FXM_WG), wg, 0, s, A);
+  const uint32_t nl = (A.max_landmarks + FXMAP_WG - 1u) / FXMAP_WG, nr = (A.q_max_rows + FXMAP_WG - 1u) / FXMAP_WG;
+  if ((A.flags & FX_MAP_OVERLAP) && nc) hipLaunchKernelGGL(k_map_compare, dim3((nc + FXMAP_WG - 1u) / FXMAP_WG), wg, 0, s, A);
   if (nl) hipLaunchKernelGGL(k_map_join, dim3(nl), wg, 0, s, A, nl);
   hipLaunchKernelGGL(k_map_top, dim3(1), wg, 0, s, A, nl);
   if (nl) hipLaunchKernelGGL(k_map_accumulate, dim3(nl), wg, 0, s, A);
@@ -265,4 +238,4 @@ extern "C" hipError_t fxk_map_update(hipStream_t s, const FxMapArgs &A) {
   return hipGetLastError();
 }
 
-extern "C" uint32_t fxk_map_wg(void) { return FXM_WG; }
+extern "C" uint32_t fxk_map_wg(void) { return FXMAP_WG; }

@@ -55,11 +55,6 @@ __device__ __forceinline__ CsrView csr_view(const uint32_t *block, uint32_t max_
   v.cap = cap;
   return v;
 }
-// the rows [row0, row0 + n) of a pair that the block stores
-__device__ __forceinline__ void clip_range(uint32_t row0, uint32_t n, uint32_t stored, uint32_t &lo, uint32_t &hi) {
-  hi = (uint32_t)min((unsigned long long)row0 + n, (unsigned long long)stored);
-  lo = min(row0, hi);
-}
 // (d, row) order of candidates; row < 0: none
 __device__ __forceinline__ bool cand_less(float da, int32_t ra, float db, int32_t rb) {
   if (ra < 0) return false;

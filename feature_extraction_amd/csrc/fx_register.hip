@@ -37,11 +37,10 @@ struct KpView {
 };
 __device__ __forceinline__ KpView kp_view(const uint32_t *block, uint32_t max_scans, uint32_t max_total) {
   KpView v;
-  v.kp = reinterpret_cast<const float4 *>(block) + (1u + (max_scans + 1u + 3u) / 4u + (max_scans + 3u) / 4u);
+  v.kp = kp_block_rows<float4>(block, max_scans);
   v.stored = min(block[1], max_total);
   return v;
 }
-__device__ __forceinline__ bool finite3(float4 p) { return isfinite(p.x) && isfinite(p.y) && isfinite(p.z); }
 
 struct Hyp {
   float c, s, tx, ty;
@@ -126,8 +125,8 @@ extern "C" __global__ __launch_bounds__(FXR_WG) void k_register(FxRegisterArgs A
   const fx_match_pair pr = reinterpret_cast<const fx_match_pair *>(A.pairs)[p];
   const fx_match *m = reinterpret_cast<const fx_match *>(A.matches);
   const KpView Q = kp_view(A.q_kp, A.q_max_scans, A.q_max_total), T = kp_view(A.t_kp, A.t_max_scans, A.t_max_total);
-  const uint32_t q_hi = (uint32_t)min((unsigned long long)pr.q_row0 + pr.q_rows, (unsigned long long)A.q_max_rows);
-  const uint32_t q_lo = min(pr.q_row0, q_hi);
+  uint32_t q_lo, q_hi;
+  clip_range(pr.q_row0, pr.q_rows, A.q_max_rows, q_lo, q_hi);
 
   // ---- gather: the correspondences in ascending query row, the first FXR_MAX_CORR kept
   uint32_t found = 0u;  // (uniform)

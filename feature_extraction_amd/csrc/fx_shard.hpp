@@ -79,6 +79,7 @@ inline void pack_record(float *dst, const float *keypoints_xyzi, uint32_t n_kp, 
 // ---- the compact keypoint block (fx_pack_keypoint_block, include/fx.h): what crosses GPUs since 0.7.  One block per rank and
 // batch, rows of four floats: row 0 {scans, keypoints stored, OR of the flags, max_total} (u32), kp_offset[max_scans + 1] (u32,
 // four a row), flags[max_scans] (u32, four a row), then max_total keypoint rows (x, y, z, elevation) packed in scan order.
+// (this header compiles without HIP: its own copy of fx_device.h's kp_block_off_rows / kp_block_flag_rows, the shared definition)
 inline size_t block_off_rows(uint32_t max_scans) { return ((size_t)max_scans + 1 + 3) / 4; }
 inline size_t block_flag_rows(uint32_t max_scans) { return ((size_t)max_scans + 3) / 4; }
 inline size_t block_floats(uint32_t max_scans, uint32_t max_total) {

@@ -22,6 +22,8 @@
 //                    and first obs_row slot of every landmark at its first row
 //   k_track_scatter  a thread a row: landmark_of_row, obs_row[obs0 + depth] = r
 //   k_track_fuse     a lane a landmark: two sequential passes over its contiguous obs_row segment
+// The block's layout, the workgroup scan and the world-frame point of an observation are fx_device.h's (kp_block_*, wg_scan2,
+// world_point): fx_map.hip uses the same ones.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -43,13 +45,12 @@ struct Block {
 };
 __device__ __forceinline__ Block block_view(const FxTrackArgs &A) {
   Block b;
-  b.off = A.kp + 4;
-  b.kp = reinterpret_cast<const float4 *>(A.kp) + (1u + (A.max_scans + 1u + 3u) / 4u + (A.max_scans + 3u) / 4u);
+  b.off = kp_block_offsets(A.kp);
+  b.kp = kp_block_rows<float4>(A.kp, A.max_scans);
   b.S = min(min(A.n_scans, A.kp[0]), A.max_scans);
   b.rows = min(min(A.kp[1], A.max_total), A.q_max_rows);
   return b;
 }
-__device__ __forceinline__ bool finite3(float4 p) { return isfinite(p.x) && isfinite(p.y) && isfinite(p.z); }
 __device__ __forceinline__ bool good_link(const fx_registration &r) {
   return (r.flags & FX_REG_VALID) && isfinite(r.c) && isfinite(r.s) && isfinite(r.tx) && isfinite(r.ty) && isfinite(r.tz);
 }
@@ -58,26 +59,6 @@ __device__ __forceinline__ uint32_t landmark_len(const FxTrackArgs &A, const uin
   if (r >= A.q_max_rows || A.scan_of[r] == FX_TRACK_NONE || jump[r].x != r) return 0u;
   const uint32_t n = A.len[r];
   return n >= A.min_obs ? n : 0u;
-}
-// exclusive prefix of (a, b) over the workgroup's threads and the totals; s_w: [2][FXT_NWAVE] words of LDS
-__device__ __forceinline__ void wg_scan2(uint32_t a, uint32_t b, uint32_t *s_w, uint32_t &ex_a, uint32_t &ex_b, uint32_t &tot_a, uint32_t &tot_b) {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  uint32_t ia = a, ib = b;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t ua = (uint32_t)__shfl_up((int)ia, o, 64), ub = (uint32_t)__shfl_up((int)ib, o, 64);
-    if (lane >= (uint32_t)o) ia += ua, ib += ub;
-  }
-  __syncthreads();  // (s_w's readers of the call before)
-  if (lane == 63u) s_w[wave] = ia, s_w[FXT_NWAVE + wave] = ib;
-  __syncthreads();
-  ex_a = ia - a, ex_b = ib - b, tot_a = tot_b = 0u;
-#pragma unroll
-  for (uint32_t w = 0; w < FXT_NWAVE; ++w) {
-    const uint32_t na = s_w[w], nb = s_w[FXT_NWAVE + w];
-    ex_a += w < wave ? na : 0u, ex_b += w < wave ? nb : 0u;
-    tot_a += na, tot_b += nb;
-  }
 }
 }  // namespace
 
@@ -244,21 +225,14 @@ extern "C" __global__ __launch_bounds__(FXT_WG) void k_track_sums(FxTrackArgs A,
   __shared__ uint32_t s_w[2 * FXT_NWAVE];
   const uint32_t n = landmark_len(A, jump, blockIdx.x * FXT_WG + threadIdx.x);
   uint32_t ea, eb, ta, tb;
-  wg_scan2(n ? 1u : 0u, n, s_w, ea, eb, ta, tb);
+  wg_scan2<FXT_NWAVE>(n ? 1u : 0u, n, s_w, ea, eb, ta, tb);
   if (threadIdx.x == 0u) A.bsum[blockIdx.x] = ta, A.bsum[n_blocks + blockIdx.x] = tb;
 }
 
 extern "C" __global__ __launch_bounds__(FXT_WG) void k_track_top(FxTrackArgs A, uint32_t n_blocks) {
   __shared__ uint32_t s_w[2 * FXT_NWAVE];
-  uint32_t base_a = 0u, base_b = 0u;
-  for (uint32_t i0 = 0u; i0 < n_blocks; i0 += FXT_WG) {  // the blocks' counts to their exclusive prefix, in place
-    const uint32_t i = i0 + threadIdx.x;
-    const uint32_t a = i < n_blocks ? A.bsum[i] : 0u, b = i < n_blocks ? A.bsum[n_blocks + i] : 0u;
-    uint32_t ea, eb, ta, tb;
-    wg_scan2(a, b, s_w, ea, eb, ta, tb);
-    if (i < n_blocks) A.bsum[i] = base_a + ea, A.bsum[n_blocks + i] = base_b + eb;
-    base_a += ta, base_b += tb;
-  }
+  uint32_t base_a, base_b;
+  wg_scan2_blocks<FXT_NWAVE>(A.bsum, n_blocks, s_w, base_a, base_b);
   if (threadIdx.x == 0u) {
     const Block B = block_view(A);
     fx_track_header h;
@@ -274,7 +248,7 @@ extern "C" __global__ __launch_bounds__(FXT_WG) void k_track_number(FxTrackArgs 
   const uint32_t r = blockIdx.x * FXT_WG + threadIdx.x;
   const uint32_t n = landmark_len(A, jump, r);
   uint32_t ea, eb, ta, tb;
-  wg_scan2(n ? 1u : 0u, n, s_w, ea, eb, ta, tb);
+  wg_scan2<FXT_NWAVE>(n ? 1u : 0u, n, s_w, ea, eb, ta, tb);
   if (r >= A.q_max_rows) return;
   if (n) {
     const uint32_t id = A.bsum[blockIdx.x] + ea;
@@ -305,21 +279,19 @@ extern "C" __global__ __launch_bounds__(FXT_WG) void k_track_fuse(FxTrackArgs A)
   const uint32_t root = A.lm_root[i], n = A.len[root], o = A.obs0[root], first_scan = A.scan_of[root];
   double sx = 0.0, sy = 0.0, sz = 0.0;
   for (uint32_t k = 0; k < n; ++k) {
+    double wx, wy, wz;
     const float4 p = B.kp[A.obs_row[o + k]];
-    const fx_pose P = poses[first_scan + k];
-    const double x = (double)p.x, y = (double)p.y;
-    sx += ((P.c * x - P.s * y) + P.tx);
-    sy += ((P.s * x + P.c * y) + P.ty);
-    sz += ((double)p.z + P.tz);
+    world_point(poses[first_scan + k], p, wx, wy, wz);
+    sx += wx, sy += wy, sz += wz;
   }
   const double dn = (double)n;
   const double mx = sx / dn, my = sy / dn, mz = sz / dn;
   double acc = 0.0;
   for (uint32_t k = 0; k < n; ++k) {
+    double wx, wy, wz;
     const float4 p = B.kp[A.obs_row[o + k]];
-    const fx_pose P = poses[first_scan + k];
-    const double x = (double)p.x, y = (double)p.y;
-    const double dx = ((P.c * x - P.s * y) + P.tx) - mx, dy = ((P.s * x + P.c * y) + P.ty) - my;
+    world_point(poses[first_scan + k], p, wx, wy, wz);
+    const double dx = wx - mx, dy = wy - my;
     acc += (dx * dx + dy * dy);
   }
   fx_landmark L;

@@ -14,6 +14,8 @@ stays in the C-ABI (a consumer that wants random access by scan without the offs
 """
 import numpy as np
 
+from .capi import keypoint_block_layout
+
 REC_KP = 127  # 1 header + 127 keypoints = 2 KiB per scan
 
 
@@ -85,7 +87,7 @@ FX_FLAG_KP_OVERFLOW = 0x4
 
 def block_rows(max_scans, max_total):
     """float4 rows of a compact keypoint block (fx_keypoint_block_bytes / 16)."""
-    return 1 + (max_scans + 1 + 3) // 4 + (max_scans + 3) // 4 + max_total
+    return keypoint_block_layout(max_scans, max_total).n_rows
 
 
 def block_keypoints_per_scan(max_scans, per_scan=64):
@@ -99,7 +101,9 @@ def pack_block(keypoints_per_scan, flags_per_scan, max_scans, max_total):
     nb = min(len(keypoints_per_scan), max_scans)
     blk = np.zeros((block_rows(max_scans, max_total), 4), np.float32)
     u = blk.view(np.uint32).reshape(-1)
-    n_off = 4 * ((max_scans + 1 + 3) // 4)
+    lay = keypoint_block_layout(max_scans, max_total)
+    f0, k0 = lay.f0, lay.k0
+    n_off = f0 - 4
     off = np.zeros(n_off, np.int64)
     run = 0
     true_off = [0]
@@ -108,15 +112,13 @@ def pack_block(keypoints_per_scan, flags_per_scan, max_scans, max_total):
         true_off.append(run)
     for i in range(n_off):
         off[i] = min(true_off[min(i, nb)], max_total)
-    u[4:4 + n_off] = off
-    f0 = 4 + n_off
+    u[4:f0] = off
     flags_or = FX_FLAG_KP_OVERFLOW if len(keypoints_per_scan) > max_scans else 0
     for b in range(nb):
         kept = min(true_off[b + 1], max_total) - min(true_off[b], max_total)
         f = int(flags_per_scan[b]) | (FX_FLAG_KP_OVERFLOW if kept < len(keypoints_per_scan[b]) else 0)
         u[f0 + b] = f
         flags_or |= f
-    k0 = 1 + n_off // 4 + (max_scans + 3) // 4
     for b in range(nb):
         n = int(off[b + 1] - off[b])
         if n:
@@ -130,10 +132,9 @@ def unpack_block(blk, max_scans):
     blk = np.ascontiguousarray(blk, dtype=np.float32).reshape(-1, 4)
     u = blk.view(np.uint32).reshape(-1)
     nb, total, flags_or, max_total = (int(v) for v in u[0:4])
-    n_off = 4 * ((max_scans + 1 + 3) // 4)
-    off = u[4:4 + n_off].astype(np.int64)
-    f0 = 4 + n_off
-    k0 = 1 + n_off // 4 + (max_scans + 3) // 4
+    lay = keypoint_block_layout(max_scans, max_total)
+    f0, k0 = lay.f0, lay.k0
+    off = u[4:f0].astype(np.int64)
     assert blk.shape[0] == block_rows(max_scans, max_total), (blk.shape, max_scans, max_total)
     out = []
     for b in range(nb):

@@ -14,8 +14,8 @@ from tests import track_util as tu
 from tests.test_gpu_track import FILL, GUARD, _batch as _process, _guarded, _upload
 
 pytestmark = pytest.mark.gpu
-# the tile sizes of csrc/fx_map.hip: FXM_WG landmarks (or rows) a workgroup, which is also the elements of one block of the integer
-# scan over the batch's landmarks; k_map_top scans FXM_WG blocks, 65536 landmarks, a round
+# the tile sizes of csrc/fx_map.hip: FXMAP_WG landmarks (or rows) a workgroup, which is also the elements of one block of the integer
+# scan over the batch's landmarks; k_map_top scans FXMAP_WG blocks, 65536 landmarks, a round
 LM_WG = ROWS_WG = SCAN_BLOCK = 256
 TOP_TILE_LMS = 256 * 256
 

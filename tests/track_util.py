@@ -206,7 +206,7 @@ def block(off, rows, max_scans, max_total, stored=None):
     u = blk.view(np.uint32).reshape(-1)
     u[:4] = (scans, stored, 0, max_total)
     u[4:4 + scans + 1] = off
-    u[4 + scans + 1:4 + 4 * ((max_scans + 1 + 3) // 4)] = off[-1]  # entries beyond the batch repeat the total
+    u[4 + scans + 1:capi.keypoint_block_layout(max_scans, max_total).f0] = off[-1]  # entries beyond the batch repeat the total
     blk[k0:k0 + n] = rows
     blk[k0 + stored:].view(np.uint8)[:] = 0xA5
     return blk.view(np.uint8).reshape(-1)

@@ -13,9 +13,12 @@ and their ratio.  Also counts the work the match does: (query row, train row) co
 each entry being 12 LDS reads and 12 fp64 multiply-adds.  Writes one JSON object.
 """
 import argparse
+import csv
+import glob
 import json
 import os
 import statistics
+import subprocess
 import sys
 
 import numpy as np
@@ -38,6 +41,23 @@ def timed(stream, fn, warmup, repeats):
         e1.synchronize()
         ms.append(e0.elapsed_time(e1))
     return ms
+
+
+def kernel_trace(script, trace_dir, batch, prefix, limit_s):
+    """{kernel: {calls, avg_us, min_us, max_us}} of the kernels whose names begin with `prefix`, from a rocprofv3 run of `script`
+    (one of the *_times.py tools, with a short repeat count) in a fresh child process under its own time limit."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = (f"timeout -k 10 {limit_s} rocprofv3 --kernel-trace --stats -d {trace_dir} -o trace --output-format csv -- "
+           f"{sys.executable} {os.path.abspath(script)} --batch {batch} --warmup 2 --repeats 5 > {trace_dir}/child.log 2>&1")
+    os.makedirs(trace_dir, exist_ok=True)
+    subprocess.check_call(["bash", "-c", cmd], cwd=root)
+    out = {}
+    for f in glob.glob(os.path.join(trace_dir, "**", "*kernel_stats.csv"), recursive=True):
+        for row in csv.DictReader(open(f)):
+            if row["Name"].startswith(prefix):
+                out[row["Name"].split("(")[0]] = {"calls": int(row["Calls"]), "avg_us": float(row["AverageNs"]) / 1e3,
+                                                 "min_us": float(row["MinNs"]) / 1e3, "max_us": float(row["MaxNs"]) / 1e3}
+    return out
 
 
 def main():

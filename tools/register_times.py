@@ -15,12 +15,9 @@ with a short repeat count and adds the per-kernel averages of k_register / k_reg
 under its own `timeout`, the steps chained with `&&`.
 """
 import argparse
-import csv
-import glob
 import json
 import os
 import statistics
-import subprocess
 import sys
 
 import numpy as np
@@ -28,23 +25,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from feature_extraction_amd import capi  # noqa: E402
-from tools.match_times import timed  # noqa: E402
-
-
-def kernel_trace(trace_dir, batch):
-    """{kernel: {calls, avg_us}} of the registration's kernels from a rocprofv3 run of this script in a child process."""
-    me = os.path.abspath(__file__)
-    cmd = (f"timeout -k 10 240 rocprofv3 --kernel-trace --stats -d {trace_dir} -o reg --output-format csv -- "
-           f"{sys.executable} {me} --batch {batch} --warmup 2 --repeats 5 > {trace_dir}/child.log 2>&1 && true")
-    os.makedirs(trace_dir, exist_ok=True)
-    subprocess.check_call(["bash", "-c", cmd], cwd=ROOT)
-    out = {}
-    for f in glob.glob(os.path.join(trace_dir, "**", "*kernel_stats.csv"), recursive=True):
-        for row in csv.DictReader(open(f)):
-            if row["Name"].startswith("k_register"):
-                out[row["Name"].split("(")[0]] = {"calls": int(row["Calls"]), "avg_us": float(row["AverageNs"]) / 1e3,
-                                                 "min_us": float(row["MinNs"]) / 1e3, "max_us": float(row["MaxNs"]) / 1e3}
-    return out
+from tools.match_times import kernel_trace, timed  # noqa: E402
 
 
 def main():
@@ -55,7 +36,7 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--trace")
     a = ap.parse_args()
-    trace = kernel_trace(a.trace, a.batch) if a.trace else None  # (the child runs before this process opens the GPU)
+    trace = kernel_trace(__file__, a.trace, a.batch, "k_register", 240) if a.trace else None  # (the child runs before this process opens the GPU)
     import ctypes as C
     import torch
     if not torch.cuda.is_available():

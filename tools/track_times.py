@@ -17,13 +17,10 @@ with a short repeat count and adds the per-kernel averages of the k_track_* kern
 GPU step runs under its own `timeout`, the steps chained with `&&`.
 """
 import argparse
-import csv
-import glob
 import json
 import math
 import os
 import statistics
-import subprocess
 import sys
 
 import numpy as np
@@ -31,23 +28,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from feature_extraction_amd import capi  # noqa: E402
-from tools.match_times import timed  # noqa: E402
-
-
-def kernel_trace(trace_dir, batch):
-    """{kernel: {calls, avg_us, min_us, max_us}} of the track's kernels from a rocprofv3 run of this script in a child process."""
-    me = os.path.abspath(__file__)
-    cmd = (f"timeout -k 10 300 rocprofv3 --kernel-trace --stats -d {trace_dir} -o track --output-format csv -- "
-           f"{sys.executable} {me} --batch {batch} --warmup 2 --repeats 5 > {trace_dir}/child.log 2>&1")
-    os.makedirs(trace_dir, exist_ok=True)
-    subprocess.check_call(["bash", "-c", cmd], cwd=ROOT)
-    out = {}
-    for f in glob.glob(os.path.join(trace_dir, "**", "*kernel_stats.csv"), recursive=True):
-        for row in csv.DictReader(open(f)):
-            if row["Name"].startswith("k_track"):
-                out[row["Name"].split("(")[0]] = {"calls": int(row["Calls"]), "avg_us": float(row["AverageNs"]) / 1e3,
-                                                 "min_us": float(row["MinNs"]) / 1e3, "max_us": float(row["MaxNs"]) / 1e3}
-    return out
+from tools.match_times import kernel_trace, timed  # noqa: E402
 
 
 def rotated(scan, n, step_deg=3.0):
@@ -143,7 +124,7 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--trace")
     a = ap.parse_args()
-    trace = kernel_trace(a.trace, a.batch) if a.trace else None  # (the child runs before this process opens the GPU)
+    trace = kernel_trace(__file__, a.trace, a.batch, "k_track", 300) if a.trace else None  # (the child runs before this process opens the GPU)
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("no GPU: device times are measured on the GPU or not at all")
