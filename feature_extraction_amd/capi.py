@@ -174,10 +174,22 @@ class FxMapHeader(C.Structure):
 FX_MAP_OVERLAP = 0x1
 FX_MAP_FULL, FX_MAP_OVERLAP_MISMATCH, FX_MAP_TRACK_TRUNCATED = 0x1, 0x2, 0x4
 FX_MAP_LM_CONTINUED = 0x1
+FX_MAP_LM_ABSORBED, FX_MAP_LM_MERGED = 0x2, 0x4  # fx_map_merge: merged into another landmark (see the alias table) / has absorbed one
 # fx_map_landmark as numpy records, and the header's counts (map_records)
 MAP_LANDMARK_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("rms_xy", "<f4"), ("n_obs", "<u4"), ("first_scan", "<u4"),
                                ("last_scan", "<u4"), ("segment", "<u4"), ("flags", "<u4")])
 MAP_HEADER_FIELDS = ("n_landmarks", "n_needed", "n_obs", "scans", "batches", "segments", "flags", "carry_rows", "last_joined", "last_new")
+
+
+class FxMapMergeOptions(C.Structure):
+    _fields_ = [("merge_dist", C.c_float), ("max_gap_scans", C.c_uint32)]
+
+
+class FxMapMergeResult(C.Structure):
+    _fields_ = [("proposals", C.c_uint32), ("merged", C.c_uint32), ("live", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+MAP_MERGE_RESULT_FIELDS = ("proposals", "merged", "live", "reserved")
 
 
 class FxTimings(C.Structure):
@@ -204,6 +216,7 @@ EXPORTS = ("fx_version", "fx_check_abi", "fx_status_str", "fx_last_error", "fx_p
            "fx_match_options_default", "fx_match_descriptors_csr", "fx_register_options_default", "fx_register_matches",
            "fx_track_options_default", "fx_track_landmarks",
            "fx_map_create", "fx_map_destroy", "fx_map_reset", "fx_map_update", "fx_map_get", "fx_map_read_header", "fx_map_read_landmarks",
+           "fx_map_merge_options_default", "fx_map_merge", "fx_map_get_alias", "fx_map_read_alias",
            "fx_rotation_from_roll_pitch", "fx_sc3d_tables", "fx_sc3d_xaxis", "fx_synth_cfg_vlp16",
            "fx_synth_scan", "fx_unpack_pointcloud2", "fx_pack_pointxyzi")
 # the header's FX_TEST_HOOKS section: exported by lib/libfx_hip_test.so only
@@ -327,6 +340,11 @@ def load():
     lib.fx_map_get.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     lib.fx_map_read_header.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(FxMapHeader)]
     lib.fx_map_read_landmarks.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+    lib.fx_map_merge_options_default.argtypes = [C.POINTER(FxMapMergeOptions)]
+    lib.fx_map_merge_options_default.restype = None
+    lib.fx_map_merge.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(FxMapMergeOptions), C.c_void_p]
+    lib.fx_map_get_alias.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    lib.fx_map_read_alias.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     lib.fx_rotation_from_roll_pitch.argtypes = [C.c_double, C.c_double, _F32P]
     lib.fx_rotation_from_roll_pitch.restype = None
     lib.fx_sc3d_tables.argtypes = [C.c_double, _F32P, _F32P, _F32P, _F32P]
@@ -875,6 +893,15 @@ def map_state_records(state):
     return {"header": dict(state["header"]), "landmarks": lm}
 
 
+def _map_record_from_sums(rec, acc):
+    """include/fx.h fx_map_update's "Records" clause: the public x, y, z and rms_xy of a landmark from its sums and its n_obs."""
+    dn = float(rec["n_obs"])
+    mx, my = acc[5] / dn, acc[6] / dn
+    var = acc[7] / dn - (mx * mx + my * my)
+    rec["x"], rec["y"], rec["z"] = acc[0] / dn, acc[1] / dn, acc[2] / dn
+    rec["rms_xy"] = np.float32(math.sqrt(var if var > 0.0 else 0.0))
+
+
 def map_reference(state, kp_offset, kp_rows, track, overlap=False, track_max_landmarks=None):
     """The definition of fx_map_update (include/fx.h) in numpy and Python floats, one batch at a time.  state: map_state(...) or
     what an earlier call returned (it is not modified); kp_offset / kp_rows: the block's kp_offset[scans + 1] and its [stored, 4]
@@ -951,11 +978,7 @@ def map_reference(state, kp_offset, kp_rows, track, overlap=False, track_max_lan
             acc[7] += (dx * dx + dy * dy)
         rec["n_obs"] += n - start
         added += n - start
-        dn = float(rec["n_obs"])
-        mx, my = acc[5] / dn, acc[6] / dn
-        var = acc[7] / dn - (mx * mx + my * my)
-        rec["x"], rec["y"], rec["z"] = acc[0] / dn, acc[1] / dn, acc[2] / dn
-        rec["rms_xy"] = np.float32(math.sqrt(var if var > 0.0 else 0.0))
+        _map_record_from_sums(rec, acc)
         rec["last_scan"] = scan_base + fs + n - 1
     of_row = np.asarray(lor[:rows]).astype(np.int64)
     has = (of_row >= 0) & (of_row < L)
@@ -981,6 +1004,85 @@ def map_reference(state, kp_offset, kp_rows, track, overlap=False, track_max_lan
     if int(th["n_landmarks"]) > max_l:
         H["flags"] |= FX_MAP_TRACK_TRUNCATED
     return st, ids
+
+
+def map_merge_reference(state, merge_dist=0.30, max_gap_scans=64):
+    """The definition of fx_map_merge (include/fx.h) in Python floats over a map_reference state: ONE call, one round.  The state
+    is not modified; state["alias"] (missing or short: -1) is kept in the new state, one entry a stored landmark.  Every pair of
+    landmarks is looked at (for every h, all g at once as numpy columns): nothing here knows of a grid.
+    Returns (the new state, {"proposals", "merged", "live", "reserved"})."""
+    import struct
+    st = dict(state, header=dict(state["header"]), landmarks=[dict(r) for r in state["landmarks"]], acc=[list(a) for a in state["acc"]],
+              carry=list(state["carry"]), carry_kp=state["carry_kp"].copy())
+    lms, accs = st["landmarks"], st["acc"]
+    N = min(int(st["header"]["n_landmarks"]), len(lms))
+    alias = [int(a) for a in st.get("alias", [])][:N]
+    alias += [-1] * (N - len(alias))
+    md = float(np.float32(merge_dist))
+    md2, gap = md * md, int(max_gap_scans)
+    if not (math.isfinite(md) and md > 0.0) or gap < 1:
+        raise ValueError("merge_dist must be finite and positive, max_gap_scans at least 1")
+
+    def takes_part(i):
+        return alias[i] == -1 and lms[i]["n_obs"] >= 1 and math.isfinite(lms[i]["x"]) and math.isfinite(lms[i]["y"])
+    part = np.array([takes_part(i) for i in range(N)], bool)
+    x, y = (np.array([float(r[f]) for r in lms[:N]], np.float64) for f in ("x", "y"))
+    first, last, seg = (np.array([int(r[f]) for r in lms[:N]], np.int64) for f in ("first_scan", "last_scan", "segment"))
+    last_p = np.where(part, last, np.int64(1) << 40)  # (a landmark that takes no part precedes nothing)
+    first_l = first.tolist()
+    bits = lambda d: struct.unpack("<Q", struct.pack("<d", d))[0]
+    # proposals: the most recent predecessor, then the nearest (d2 as the bit pattern of a non-negative double), then the lowest id
+    prop = {}
+    with np.errstate(over="ignore", invalid="ignore"):
+        for h in np.flatnonzero(part).tolist():
+            cand = np.flatnonzero((last_p < first_l[h]) & (last_p >= first_l[h] - gap) & (seg == seg[h]))
+            cand = cand[cand != h]
+            if not len(cand):
+                continue
+            dx, dy = x[cand] - x[h], y[cand] - y[h]
+            d2 = dx * dx + dy * dy
+            near = d2 <= md2
+            best = None
+            for g, d in zip(cand[near].tolist(), d2[near].tolist()):
+                key = (-int(last[g]), bits(d), g)
+                if best is None or key < best:
+                    best = key
+            if best is not None:
+                prop[h] = best[2]
+    # acceptance: a g keeps its proposer of lowest (first_scan, id)
+    keeps = {}
+    for h, g in prop.items():
+        key = (int(first[h]) << 32) | h
+        if g not in keeps or key < keeps[g]:
+            keeps[g] = key
+    succ = {g: k & 0xffffffff for g, k in keeps.items()}
+    pred = {h: g for g, h in succ.items()}
+    absorbed = {}
+    for r in sorted(g for g in succ if g not in pred):
+        R, A = lms[r], accs[r]
+        m = succ[r]
+        while m is not None:
+            M, B = lms[m], accs[m]
+            nm = float(M["n_obs"])
+            ex, ey = B[3] - A[3], B[4] - A[4]
+            A[0] += B[0]
+            A[1] += B[1]
+            A[2] += B[2]
+            A[7] += ((B[7] + 2.0 * (ex * B[5] + ey * B[6])) + nm * (ex * ex + ey * ey))
+            A[5] += (B[5] + nm * ex)
+            A[6] += (B[6] + nm * ey)
+            R["n_obs"] += M["n_obs"]
+            R["last_scan"] = M["last_scan"]
+            R["flags"] |= FX_MAP_LM_MERGED | (M["flags"] & FX_MAP_LM_CONTINUED)
+            M["flags"] |= FX_MAP_LM_ABSORBED
+            alias[m] = absorbed[m] = r
+            m = succ.get(m)
+        _map_record_from_sums(R, A)
+    alias = [absorbed.get(a, a) for a in alias]
+    st["carry"] = [alias[c] if 0 <= c < N and alias[c] >= 0 else c for c in st["carry"]]
+    st["alias"] = alias
+    live = sum(1 for i in range(N) if takes_part(i))
+    return st, {"proposals": len(prop), "merged": len(succ), "live": live, "reserved": 0}
 
 
 def _np(ptr, shape, dtype):
@@ -1039,6 +1141,40 @@ class Map:
                                      C.c_void_p(row_ids.data_ptr() if row_ids is not None else None)))
         cur.wait_stream(ext)
         return row_ids
+
+    def merge(self, merge_dist=0.30, max_gap_scans=64, result=None):
+        """fx_map_merge: one round of spatial re-association of the fragments of one pole (include/fx.h).  Returns the
+        fx_map_merge_result as a device torch.int32 tensor [4] (proposals, merged, live, 0); `result` reuses one, result=False
+        passes NULL (None is returned).  Stream-correct like update(); never waits for the stream."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        if result is None:
+            result = torch.empty((4,), dtype=torch.int32, device=dev)
+        elif result is False:
+            result = None
+        elif result.dtype != torch.int32 or result.device != dev or tuple(result.shape) != (4,) or not result.is_contiguous():
+            raise ValueError(f"result must be a contiguous torch.int32 tensor [4] on {dev}")
+        opt = FxMapMergeOptions(float(merge_dist), int(max_gap_scans))
+        cur = torch.cuda.current_stream(dev)
+        ext = torch.cuda.ExternalStream(self.ctx.stream_ptr(), device=dev)
+        ext.wait_stream(cur)
+        check(self.lib.fx_map_merge(self.ctx.handle, self.handle, C.byref(opt), C.c_void_p(result.data_ptr() if result is not None else None)))
+        cur.wait_stream(ext)
+        return result
+
+    def alias(self, first=0, count=None):
+        """fx_map_read_alias (waits for the stream): alias[first, first + count) as int32, -1 for a live landmark, else the id of
+        the live landmark that absorbed it; count defaults to the rest of max_landmarks."""
+        count = self.max_landmarks - first if count is None else int(count)
+        out = np.zeros(count, np.int32)
+        check(self.lib.fx_map_read_alias(self.ctx.handle, self.handle, int(first), count, C.c_void_p(out.ctypes.data)))
+        return out
+
+    def alias_device_pointer(self):
+        """fx_map_get_alias: the device address of the alias table, int32 [max_landmarks]."""
+        a = C.c_void_p()
+        check(self.lib.fx_map_get_alias(self.handle, C.byref(a)))
+        return a.value
 
     def device_pointers(self):
         """fx_map_get: the device addresses of (the fx_map_header, the fx_map_landmark records)."""

@@ -87,6 +87,10 @@ uint32_t fxk_track_wg_rows(void);
 hipError_t fxk_map_reset(hipStream_t s, const FxMapArgs &A);
 hipError_t fxk_map_update(hipStream_t s, const FxMapArgs &A);
 uint32_t fxk_map_wg(void);
+hipError_t fxk_map_merge(hipStream_t s, const FxMapMergeArgs &A);
+uint32_t fxk_map_merge_table(uint32_t cap);
+size_t fxk_map_merge_scratch(FxMapMergeArgs *A, uint8_t *base);
+uint32_t fxk_map_merge_wg(void);
 #ifdef FX_TEST_HOOKS
 void fxk_test_sort_replay(hipStream_t s, const uint32_t *sizes, uint32_t n_seq, uint32_t n, uint32_t *perm);
 void fxk_test_elevation(hipStream_t s, const float *xyz, uint32_t n, const double *tab, float *fast, uint8_t *ok, float *exact);
@@ -256,6 +260,7 @@ struct fx_ctx {
   Staging reg_stage;         // fx_register_matches: the pairs
   DevScratch track_scratch;  // fx_track_landmarks: the per-row scratch arrays
   DevScratch map_scratch;    // fx_map_update: the batch landmark's map id, the blocks' counts
+  DevScratch merge_scratch;  // fx_map_merge: the grid (bucket counts, landmarks in bucket order), proposals, kept links
 };
 
 // A persistent landmark map (include/fx.h fx_map_create): one device buffer, carved up once.
@@ -1049,7 +1054,8 @@ void fx_destroy(fx_ctx *c) {
   if (c->d_stage) (void)hipFree(c->d_stage);
   if (c->d_csr) (void)hipFree(c->d_csr);
   if (c->h_csr) (void)hipHostFree(c->h_csr);
-  c->match_stage.release(), c->match_scratch.release(), c->reg_stage.release(), c->track_scratch.release(), c->map_scratch.release();
+  c->match_stage.release(), c->match_scratch.release(), c->reg_stage.release(), c->track_scratch.release(), c->map_scratch.release(),
+      c->merge_scratch.release();
   for (int i = 0; i < kMetaSlots; ++i)
     if (c->meta_ev[i]) (void)hipEventDestroy(c->meta_ev[i]);
   for (hipEvent_t e : c->ev_ring) (void)hipEventDestroy(e);
@@ -1789,17 +1795,19 @@ fx_status fx_map_create(fx_ctx *c, uint32_t max_landmarks, uint32_t max_carry_ro
   if (!c || !out) return fail(FX_ERR_INVALID_ARG, "null argument");
   if (!max_landmarks) return fail(FX_ERR_INVALID_ARG, "max_landmarks must be at least 1");
   FX_HIP(hipSetDevice(c->device));
-  // header (88 -> 96), state words, records, accumulators, the carry scan's rows, the carry table: all 16-byte aligned
+  // header (88 -> 96), state words, records, accumulators, the carry scan's rows, the carry table (its bytes rounded up to 16), the
+  // alias table: all 16-byte aligned
   const size_t carry = std::max((size_t)max_carry_rows, (size_t)1);
   const size_t o_st = 96, o_rec = o_st + FX_MAP_ST_WORDS * 4, o_acc = o_rec + (size_t)max_landmarks * sizeof(fx_map_landmark),
-               o_kp = o_acc + (size_t)max_landmarks * FX_MAP_ACC * sizeof(double), o_carry = o_kp + carry * 16, bytes = o_carry + carry * 4;
+               o_kp = o_acc + (size_t)max_landmarks * FX_MAP_ACC * sizeof(double), o_carry = o_kp + carry * 16, o_alias = o_carry + ((carry * 4 + 15) & ~(size_t)15),
+               bytes = o_alias + (size_t)max_landmarks * 4;
   void *d = nullptr;
   hipError_t e = hipMalloc(&d, bytes);
   if (e != hipSuccess) return fail(FX_ERR_OOM, std::string("map (") + std::to_string(bytes) + "): " + hipGetErrorString(e));
   fx_map *m = new fx_map;
   m->ctx = c, m->device = c->device, m->d = (uint8_t *)d;
   m->a.header = m->d, m->a.st = (uint32_t *)(m->d + o_st), m->a.records = m->d + o_rec, m->a.acc = (double *)(m->d + o_acc);
-  m->a.carry_kp = (uint4 *)(m->d + o_kp), m->a.carry = (int32_t *)(m->d + o_carry);
+  m->a.carry_kp = (uint4 *)(m->d + o_kp), m->a.carry = (int32_t *)(m->d + o_carry), m->a.alias = (int32_t *)(m->d + o_alias);
   m->a.cap = max_landmarks, m->a.max_carry = max_carry_rows;
   e = hipMemsetAsync(d, 0, bytes, c->stream);
   if (e == hipSuccess) e = fxk_map_reset(c->stream, m->a);
@@ -1874,6 +1882,52 @@ fx_status fx_map_read_landmarks(fx_ctx *c, fx_map *m, uint32_t first, uint32_t c
   if (count)
     FX_HIP(hipMemcpyAsync(out, (const fx_map_landmark *)m->a.records + first, (size_t)count * sizeof(fx_map_landmark), hipMemcpyDeviceToHost,
                           c->stream));
+  FX_HIP(hipStreamSynchronize(c->stream));
+  return FX_OK;
+}
+
+void fx_map_merge_options_default(fx_map_merge_options *o) {
+  if (!o) return;
+  o->merge_dist = 0.30f;
+  o->max_gap_scans = 64;
+}
+
+fx_status fx_map_merge(fx_ctx *c, fx_map *m, const fx_map_merge_options *opt, fx_map_merge_result *result) {
+  if (!c || !m) return fail(FX_ERR_INVALID_ARG, "null argument");
+  if (m->ctx != c) return fail(FX_ERR_INVALID_ARG, "the map belongs to another context");
+  fx_map_merge_options o;
+  fx_map_merge_options_default(&o);
+  if (opt) o = *opt;
+  if (!(std::isfinite(o.merge_dist) && o.merge_dist > 0.f)) return fail(FX_ERR_INVALID_ARG, "merge_dist must be finite and positive");
+  if (!o.max_gap_scans) return fail(FX_ERR_INVALID_ARG, "max_gap_scans must be at least 1");
+  if (((uintptr_t)result % 4) != 0) return fail(FX_ERR_INVALID_ARG, "the result must be 4-byte aligned");
+  FX_HIP(hipSetDevice(c->device));
+  FxMapMergeArgs A{};
+  A.header = m->a.header, A.records = m->a.records, A.acc = m->a.acc, A.carry = m->a.carry, A.alias = m->a.alias;
+  A.cap = m->a.cap, A.max_carry = m->a.max_carry;
+  // the gate in fp64 and the grid's cell edge: md (1 + 2^-8), exact (csrc/fx_map_merge.hip proves the margin)
+  const double md = (double)o.merge_dist;
+  A.md2 = md * md, A.inv_edge = 1.0 / (md * (1.0 + 1.0 / 256.0));
+  A.max_gap = o.max_gap_scans, A.table = fxk_map_merge_table(A.cap);
+  A.result = (uint32_t *)result;
+  FX_TRY(c->merge_scratch.reserve(c, fxk_map_merge_scratch(&A, nullptr), "map merge scratch"));
+  (void)fxk_map_merge_scratch(&A, c->merge_scratch.d);
+  FX_HIP(fxk_map_merge(c->stream, A));
+  return FX_OK;
+}
+
+fx_status fx_map_get_alias(fx_map *m, const int32_t **alias) {
+  if (!m || !alias) return fail(FX_ERR_INVALID_ARG, "null argument");
+  *alias = m->a.alias;
+  return FX_OK;
+}
+
+fx_status fx_map_read_alias(fx_ctx *c, fx_map *m, uint32_t first, uint32_t count, int32_t *out) {
+  if (!c || !m || (count && !out)) return fail(FX_ERR_INVALID_ARG, "null argument");
+  if (m->ctx != c) return fail(FX_ERR_INVALID_ARG, "the map belongs to another context");
+  if (first > m->a.cap || count > m->a.cap - first) return fail(FX_ERR_INVALID_ARG, "entries outside the map's max_landmarks");
+  FX_HIP(hipSetDevice(c->device));
+  if (count) FX_HIP(hipMemcpyAsync(out, m->a.alias + first, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   FX_HIP(hipStreamSynchronize(c->stream));
   return FX_OK;
 }

@@ -100,6 +100,15 @@ __device__ __forceinline__ void world_point(const fx_pose &P, float4 p, double &
   wy = (P.s * x + P.c * y) + P.ty;
   wz = (double)p.z + P.tz;
 }
+// The public record of a map landmark from its running sums (include/fx.h fx_map_update, "Records"): the means, and the spread
+// about the mean through the anchor.  k_map_accumulate and fx_map_merge's fold both take the record from here.
+__device__ __forceinline__ void map_record_from_sums(fx_map_landmark &R, double sx, double sy, double sz, double dsx, double dsy, double q) {
+  const double dn = (double)R.n_obs;
+  const double mx = dsx / dn, my = dsy / dn;
+  const double var = q / dn - (mx * mx + my * my);
+  R.x = sx / dn, R.y = sy / dn, R.z = sz / dn;
+  R.rms_xy = (float)sqrt(var > 0.0 ? var : 0.0);
+}
 // exclusive prefix of (a, b) over the threads of a workgroup of NWAVE wavefronts, and the totals; s_w: [2][NWAVE] words of LDS
 template <uint32_t NWAVE>
 __device__ __forceinline__ void wg_scan2(uint32_t a, uint32_t b, uint32_t *s_w, uint32_t &ex_a, uint32_t &ex_b, uint32_t &tot_a, uint32_t &tot_b) {
@@ -203,6 +212,7 @@ struct FxMapArgs {
   int32_t *carry;               // [max_carry]: map id of local row j of the carry scan, -1: none
   uint4 *carry_kp;              // [max_carry]: the carry scan's rows as they were in the block
   uint32_t *st;                 // [FX_MAP_ST_WORDS]; words 0 and 7 are 0 between updates
+  int32_t *alias;               // [cap]: -1 live, else the live landmark that absorbed it (fx_map_merge; the update never touches it)
   uint32_t cap, max_carry;
   const uint32_t *kp;           // keypoint block (include/fx.h fx_pack_keypoint_block)
   uint32_t max_scans, max_total;
@@ -217,6 +227,33 @@ struct FxMapArgs {
   int32_t *map_id_of_row;       // [q_max_rows] or null
   int32_t *id_of_lm;            // [max_landmarks]: k_map_join's verdict (>= 0 continues that id, -1 new, -2 not a landmark), then the map id or -1
   uint32_t *bsum;               // [2][blocks of FXMAP_WG landmarks]: new / continued landmarks of the block
+};
+// fx_map_merge (csrc/fx_map_merge.hip): a launch set's arguments.  The first group is the map's own memory, the last the context's
+// scratch, sized by the map's max_landmarks (cap) and the hash table's `table` buckets (a power of two; bucket `table` is the far list).
+#define FX_MAP_MERGE_ST_WORDS 4  // 0 proposals, 1 kept links, 2 live landmarks after the call, 3 landmarks in the grid
+struct FxMapMergeCand {         // a landmark that takes part, as the search reads it: 32 B, in bucket order
+  double x, y;
+  uint32_t last_scan, segment, id, pad_;
+};
+struct FxMapMergeArgs {
+  const void *header;           // fx_map_header (read only: ids are stable)
+  void *records;                // fx_map_landmark [cap]
+  double *acc;                  // [cap][FX_MAP_ACC]
+  int32_t *carry;               // [max_carry]
+  int32_t *alias;               // [cap]
+  uint32_t cap, max_carry;
+  double md2, inv_edge;         // the gate (double)merge_dist squared; 1 / the cell edge
+  uint32_t max_gap, table;
+  uint32_t *result;             // fx_map_merge_result or null
+  uint32_t *st;                 // [FX_MAP_MERGE_ST_WORDS]
+  uint32_t *count;              // [table + 1]: landmarks of the bucket (the scatter counts it down to 0)
+  uint32_t *start;              // [table + 1]: the bucket's first slot within its block of buckets
+  uint32_t *bsum;               // [2][blocks of buckets]: the block's landmarks, then its first slot (the second row is unused: 0)
+  uint32_t *bucket;             // [cap]: the landmark's bucket, FX_TRACK_NONE: takes no part
+  FxMapMergeCand *cand;         // [cap]
+  int32_t *prop;                // [cap]: the g landmark h proposes, -1: none
+  unsigned long long *keep;     // [cap]: (first_scan << 32) | h of g's proposers, atomic min
+  int32_t *pred, *succ;         // [cap]: the kept link into / out of the landmark, -1: none
 };
 #define FX_TRACK_NONE 0xffffffffu
 #define FX_N_HINTS 8     // tier_hint[]: 0 / 1 rings handed to the second run tier / the workgroup tier (largest XCD class), 2 big merges, 3 huge merges, 4 dense rows, 5 dense support points, 6 scans k_front handed to k_front_redo, 7 scans handed to the slow tier (k_slow)

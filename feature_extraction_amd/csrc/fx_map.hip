@@ -18,7 +18,9 @@
 //   k_map_rows        a thread a row: map_id_of_row, and for the rows of scan S - 1 the carry table and the carry scan's copy
 //   k_map_finish      one lane: the header
 // The block's layout, the workgroup scan and the world-frame point of an observation are fx_device.h's (kp_block_*, wg_scan2,
-// world_point): the ones fx_track.hip uses, which is what keeps the map equal to one long track.
+// world_point): the ones fx_track.hip uses, which is what keeps the map equal to one long track.  The record from the sums
+// (map_record_from_sums) is shared with fx_map_merge.hip.  The alias table is fx_map_merge's: a reset fills it with -1, the update
+// never touches it.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stddef.h>
@@ -160,11 +162,7 @@ extern "C" __global__ __launch_bounds__(FXMAP_WG) void k_map_accumulate(FxMapArg
     }
     added = lm.n_obs - (joined ? 1u : 0u);
     R.n_obs += added;
-    const double dn = (double)R.n_obs;
-    const double mx = dsx / dn, my = dsy / dn;
-    const double var = q / dn - (mx * mx + my * my);
-    R.x = sx / dn, R.y = sy / dn, R.z = sz / dn;
-    R.rms_xy = (float)sqrt(var > 0.0 ? var : 0.0);
+    map_record_from_sums(R, sx, sy, sz, dsx, dsy, q);
     R.last_scan = scan_base + (lm.first_scan + lm.n_obs - 1u);
     acc[0] = sx, acc[1] = sy, acc[2] = sz, acc[3] = ax, acc[4] = ay, acc[5] = dsx, acc[6] = dsy, acc[7] = q;
     *rec = R;
@@ -221,6 +219,8 @@ extern "C" __global__ __launch_bounds__(64) void k_map_finish(FxMapArgs A) {
 }
 
 extern "C" hipError_t fxk_map_reset(hipStream_t s, const FxMapArgs &A) {
+  const hipError_t e = hipMemsetAsync(A.alias, 0xff, (size_t)A.cap * sizeof(int32_t), s);  // every landmark live: -1
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_map_reset, dim3(1), dim3(64), 0, s, A);
   return hipGetLastError();
 }

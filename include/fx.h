@@ -616,8 +616,9 @@ fx_status fx_track_landmarks(fx_ctx *ctx,
  * 4-byte) aligned.
  * The same bytes from run to run and with any number of contexts in flight: every decision is an integer (32-bit integer atomics
  * only, or and sum), every fp64 value an ordered chain of correctly rounded operations on one lane.
- * Limits: tracks are continued only across an accepted one-scan overlap; a pole seen again after a bad link or after leaving the
- * field of view is a new landmark (no spatial re-association, no loop closure).  The equality with one batch of the whole run
+ * Limits: tracks are continued only across an accepted one-scan overlap; a pole seen again after a missed detection, a bad link or
+ * after leaving the field of view enters as a new landmark.  fx_map_merge (below) folds such fragments back into one landmark
+ * within a segment; across segments and after long drift they stay apart (no loop closure).  The equality with one batch of the whole run
  * holds for min_obs == 2; with a larger min_obs a track that a batch edge cuts into pieces that are each too short is missed.
  * n_obs and n_needed are 32-bit counts.
  * fx_map_create allocates all of the map's buffers and enqueues its first reset; fx_map_reset enqueues the state of a fresh map;
@@ -651,6 +652,65 @@ fx_status fx_map_update(fx_ctx *ctx, fx_map *map,
 fx_status fx_map_get(fx_map *map, const fx_map_header **header_device, const fx_map_landmark **landmarks_device);
 fx_status fx_map_read_header(fx_ctx *ctx, fx_map *map, fx_map_header *out_host);
 fx_status fx_map_read_landmarks(fx_ctx *ctx, fx_map *map, uint32_t first, uint32_t count, fx_map_landmark *out_host);
+
+/* ---- Merging the fragments of one pole in the map: spatial re-association ----
+ * A track is a chain of links between CONSECUTIVE scans: one missed detection, one match that is no inlier or one conflict breaks
+ * it, and the pole enters the map again under a new id with a second mean.  Inside one segment the poses are one consistent frame,
+ * so the fragments of one pole lie centimetres apart there while two poles never do; fx_map_merge joins fragments that are close
+ * in xy and disjoint in time.  It is enqueued on the context's stream (no host synchronisation, no allocation in the steady state:
+ * its scratch is a context-owned buffer sized by the map's max_landmarks), may be called after any fx_map_update, any number of
+ * times, and changes nothing of a map it is never called on.
+ * The alias table is private memory of the map, int32 [max_landmarks]: alias[id] == -1, the landmark is live; otherwise the id of
+ * the live landmark that absorbed it — always fully resolved, never a chain.  fx_map_create and fx_map_reset fill it with -1,
+ * fx_map_update never touches it.
+ * ONE CALL, with N = header.n_landmarks and the records and sums as they are when it starts:
+ * Live set: landmark i < N takes part iff alias[i] == -1, n_obs >= 1 and its record's x and y are finite.
+ * Eligibility: g may precede h iff both take part, g != h, segment[g] == segment[h], last_scan[g] < first_scan[h],
+ * first_scan[h] - last_scan[g] <= max_gap_scans and d2 <= md md, where dx = x[g] - x[h], dy = y[g] - y[h], d2 = dx dx + dy dy in
+ * fp64 (no contraction, no fma) and md = (double)merge_dist.  Two landmarks ever seen in the same scan are never merged: that keeps
+ * two close but distinct poles apart.
+ * Proposal: every h with such a g proposes the one of greatest last_scan (the most recent: the track resumes where it stopped);
+ * ties go to the smallest d2, compared as the uint64 bit patterns of the non-negative doubles, then to the lowest id.
+ * Acceptance: a g keeps, among its proposers, the one of lowest first_scan, ties to the lowest id (one 64-bit integer atomic
+ * minimum on (first_scan << 32) | h: order-free).  last_scan strictly grows along a kept link and a landmark has at most one kept
+ * link in and one out, so the kept links form simple chains.
+ * Fold: a chain's root r is its member without a kept predecessor; one lane folds the members m1, m2, ... into r in chain order,
+ * fp64, no contraction.  For each m, with nm = (double)n_obs[m] and ex = ax[m] - ax[r], ey = ay[m] - ay[r] (the anchors):
+ * Sx[r] += Sx[m] (Sy, Sz likewise); Q[r] += ((Q[m] + 2.0 (ex Dx[m] + ey Dy[m])) + nm (ex ex + ey ey)); Dx[r] += (Dx[m] + nm ex),
+ * Dy[r] += (Dy[m] + nm ey); n_obs[r] += n_obs[m]; last_scan[r] = last_scan[m]; flags[r] |= FX_MAP_LM_MERGED and m's
+ * FX_MAP_LM_CONTINUED; m gains FX_MAP_LM_ABSORBED and alias[m] = r, and everything else of its record stays as it was (frozen).
+ * Then r's x, y, z and rms_xy are recomputed from its sums by fx_map_update's "Records" clause; its first_scan, segment and
+ * anchor are unchanged.
+ * Re-pointing: every alias entry that pointed at a landmark absorbed by this call is set to that landmark's root, and every
+ * carry entry >= 0 is replaced by its root, so the next fx_map_update continues the merged landmark.  The header is untouched:
+ * ids are stable and never compacted, n_obs only moved.
+ * Result (when given): proposals = the h that proposed, merged = the kept links, live = the landmarks that take part after the
+ * call, reserved = 0.
+ * One call is one round: a fragment whose proposal was not kept (another fragment resumed the same track earlier) is picked up by
+ * the next call; call until merged == 0 for a fixpoint, on which a further call changes no byte.
+ * The same bytes from run to run and with any number of contexts in flight: every decision is an integer or a minimum over a
+ * total order, every fp64 value an ordered chain on one lane.  The search structure (a hashed grid) never shows in the result.
+ * FX_ERR_INVALID_ARG with the reason in fx_last_error(), nothing launched, the map unchanged: a NULL ctx or map (fx_map_get_alias:
+ * a NULL out pointer), a map of another context, merge_dist not finite and positive, max_gap_scans == 0, result_device not 4-byte
+ * aligned; fx_map_read_alias: entries outside max_landmarks.
+ * Limits: merging happens within one segment only (no loop closure).  Chained merges of one call may join A and C that are up to
+ * 2 merge_dist apart, through B.  The map_id_of_row arrays of earlier batches keep the absorbed ids: resolve them through the
+ * alias table (id = alias[id] >= 0 ? alias[id] : id).  A cell of the grid that holds very many fragments is searched by one lane
+ * a landmark: time, not the result, grows with the square of a cell's population.
+ * fx_map_get_alias returns the table's device address (stable for the map's life; read it in stream order); fx_map_read_alias
+ * copies entries [first, first + count) to the host and waits for the stream.  New in 0.7 (added symbols only). */
+#define FX_MAP_LM_ABSORBED 0x2u  /* fx_map_landmark flags: merged into another landmark (see the alias table); the record is frozen */
+#define FX_MAP_LM_MERGED   0x4u  /* this landmark has absorbed at least one other */
+typedef struct fx_map_merge_options {
+  float merge_dist;        /* xy gate in metres between the two means; finite and > 0; default 0.30 (fx_register_options.inlier_dist's default) */
+  uint32_t max_gap_scans;  /* a fragment may resume at most this many scans after its predecessor ended; >= 1; default 64 */
+} fx_map_merge_options;
+typedef struct fx_map_merge_result { uint32_t proposals, merged, live, reserved; } fx_map_merge_result; /* 16 B */
+void fx_map_merge_options_default(fx_map_merge_options *o);
+fx_status fx_map_merge(fx_ctx *ctx, fx_map *map, const fx_map_merge_options *opt /* NULL: defaults */,
+                       fx_map_merge_result *result_device /* or NULL */);
+fx_status fx_map_get_alias(fx_map *map, const int32_t **alias_device);            /* [max_landmarks], stable for the map's life */
+fx_status fx_map_read_alias(fx_ctx *ctx, fx_map *map, uint32_t first, uint32_t count, int32_t *out_host);
 
 /* Rotation matrix of rotateCloud (ref: node.cpp:161-164): R = Ry(pitch)*Rx(roll)
  * through Eigen's AngleAxisf -> Quaternionf -> toRotationMatrix, all float. Host only. */

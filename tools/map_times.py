@@ -12,6 +12,15 @@ on the context's stream (the events are read after the run: nothing waits inside
 --warmup runs, the map reset in between.  Reported per workload: the median over all batches and repeats of track_ms and map_ms,
 the same for the first batch (nothing to join) and the later ones, and what the map held at the end.  No target is set: both are
 a handful of small launches and are expected to be launch-bound.  Writes one JSON object.
+
+  timeout -k 10 600 python tools/map_times.py --merge [--sizes 1000,100000,1000000] [--warmup 1] [--repeats 5] [--out profiles/map_merge_times.txt]
+
+times fx_map_merge instead: for every size N a map of N landmarks laid out like a world, 1 pole per 250 m^2 in a square, two thirds
+of the landmarks the first fragment of a pole (scans 0-1) and one third a second fragment of one of those poles (scans 2-3, up to
+0.2 m off), built by ONE track -> fx_map_update of a synthetic four-scan block.  Every repeat resets the map, updates it, merges
+(the call that does the work: N / 3 proposals, links and folds) and merges again (the fixpoint: the grid and the search, nothing to
+fold); each call sits between its own pair of HIP events.  Reported per size: the medians, and the ratio of the merge time to the
+size before; the requirement is time(10^6) <= 15 x time(10^5).
 """
 import argparse
 import ctypes as C
@@ -104,8 +113,106 @@ def measure(ctx, scans, roll, pitch, batch, warmup, repeats):
     return out
 
 
+def merge_case(n, rng):
+    """The four-scan block, match records, inlier words and registrations whose track holds n landmarks: roots in scans 0-1, members
+    (a third) in scans 2-3.  Host arrays."""
+    M = n // 3
+    R = n - M
+    side = (R * 250.0) ** 0.5
+    roots = rng.uniform(0.0, side, (R, 2))
+    of = rng.permutation(R)[:M]
+    r, a = rng.uniform(0.0, 0.2, M), rng.uniform(0.0, 2 * np.pi, M)
+    members = roots[of] + np.stack([r * np.cos(a), r * np.sin(a)], axis=1)
+    off = np.array([0, R, 2 * R, 2 * R + M, 2 * R + 2 * M], np.uint32)
+    rows = np.zeros((int(off[-1]), 4), np.float32)
+    rows[:R, :2] = rows[R:2 * R, :2] = roots
+    rows[2 * R:2 * R + M, :2] = rows[2 * R + M:, :2] = members
+    rows[:, 2] = 1.0
+    m = np.zeros(len(rows), capi.MATCH_DTYPE)
+    m["train_row"], m["second_row"], m["dist2"], m["dist2_second"], m["pair"] = -1, -1, np.inf, np.inf, capi.FX_MATCH_NO_PAIR
+    inl = np.zeros(len(rows), np.int32)
+    for b, (lo, hi) in enumerate(zip(off[1:-1], off[2:]), start=1):
+        m["pair"][lo:hi] = b - 1
+    for lo, n_rows, src in ((R, R, 0), (2 * R + M, M, 2 * R)):
+        m["train_row"][lo:lo + n_rows], m["flags"][lo:lo + n_rows], m["dist2"][lo:lo + n_rows], inl[lo:lo + n_rows] = np.arange(src, src + n_rows), capi.FX_MATCH_ACCEPTED, 1.0, 1
+    reg = np.zeros(3, capi.REG_DTYPE)
+    reg[:] = (1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 10, 10, capi.FX_REG_VALID, 0, 1)
+    S, T = 4, len(rows)
+    k0, n_blk = capi.keypoint_block_layout(S, T)
+    blk = np.zeros((n_blk, 4), np.float32)
+    u = blk.view(np.uint32).reshape(-1)
+    u[:4] = (S, T, 0, T)
+    u[4:4 + S + 1] = off
+    u[4 + S + 1:capi.keypoint_block_layout(S, T).f0] = off[-1]
+    blk[k0:k0 + T] = rows
+    return blk.view(np.uint8).reshape(-1), (S, T), m, inl, reg, M
+
+
+def measure_merge(ctx, n, warmup, repeats):
+    import torch
+    blk, (S, T), m, inl, reg, M = merge_case(n, np.random.default_rng(n))
+    kp = (torch.from_numpy(blk).cuda(), S, T)
+    md, inl_t = torch.from_numpy(m.view(np.int32).reshape(-1, 8).copy()).cuda(), torch.from_numpy(inl).cuda()
+    reg_t = torch.from_numpy(reg.view(np.float64).reshape(-1, 8).copy()).cuda()
+    out = ctx.track_landmarks(kp, md, inl_t, reg_t, S, max_landmarks=n)
+    mp = ctx.map_create(n, 16)
+    res = torch.zeros((4,), dtype=torch.int32, device="cuda")
+    stream = torch.cuda.ExternalStream(ctx.stream_ptr())
+    torch.cuda.synchronize()
+    t = {"update_ms": [], "merge_ms": [], "merge_fixpoint_ms": []}
+    first = None
+    for rep in range(warmup + repeats):
+        mp.reset()
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
+        e[0].record(stream)
+        mp.update(kp, out, overlap=False, row_ids=False)
+        e[1].record(stream), e[2].record(stream)
+        mp.merge(result=res)
+        e[3].record(stream)
+        ctx.synchronize()
+        got = res.cpu().numpy().tolist()
+        e[4].record(stream)
+        mp.merge(result=res)
+        e[5].record(stream)
+        ctx.synchronize()
+        first = first or got
+        assert got == first, (got, first)  # (merged may differ from M by a few: two poles may lie within the gate of one fragment)
+        if rep >= warmup:
+            for k, (a, b) in zip(t, ((0, 1), (2, 3), (4, 5))):
+                t[k].append(e[a].elapsed_time(e[b]))
+    hdr = mp.header()
+    mp.close()
+    out = {"landmarks": hdr["n_landmarks"], "mergeable": M, "result": dict(zip(capi.MAP_MERGE_RESULT_FIELDS, first))}
+    for k, v in t.items():
+        out[k] = statistics.median(v)
+        out[k + "_min_max"] = [min(v), max(v)]
+    return out
+
+
+def main_merge(a):
+    sizes = [int(x) for x in a.sizes.split(",")]
+    ctx = capi.Context(capi.params("launch"), capi.limits(2, 1024))
+    rows = [measure_merge(ctx, n, a.warmup, a.repeats) for n in sizes]
+    ctx.close()
+    lines = [f"fx_map_merge next to fx_map_update on synthetic maps (tools/map_times.py --merge): 1 pole per 250 m^2, a third of the landmarks",
+             f"the second fragment of a pole; one context, HIP events around each call, median of {a.repeats} after {a.warmup} warm-up; ms",
+             f"{'landmarks':>10} {'merged':>8} {'live':>8} {'update':>9} {'merge':>9} {'fixpoint':>9} {'merge / size before':>19}"]
+    for k, r in enumerate(rows):
+        ratio = f"{r['merge_ms'] / rows[k - 1]['merge_ms']:.2f}" if k else "-"
+        lines.append(f"{r['landmarks']:>10} {r['result']['merged']:>8} {r['result']['live']:>8} {r['update_ms']:>9.3f} {r['merge_ms']:>9.3f} {r['merge_fixpoint_ms']:>9.3f} {ratio:>19}")
+    s = "\n".join(lines)
+    print(s)
+    print(json.dumps(rows))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(s + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--merge", action="store_true", help="time fx_map_merge on synthetic maps instead")
+    ap.add_argument("--sizes", default="1000,100000,1000000")
     ap.add_argument("--scans", type=int, default=1024)
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--warmup", type=int, default=1)
@@ -115,6 +222,8 @@ def main():
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("no GPU: device times are measured on the GPU or not at all")
+    if a.merge:
+        return main_merge(a)
     N = 28800
     ctx = capi.Context(capi.params("launch"), capi.limits(a.batch, N, sparse=True))
     scenes = np.stack([capi.synth_scan(capi.synth_cfg(1000 + b)) for b in range(a.scans)])
