@@ -481,8 +481,9 @@ def pairs_consecutive(kp_offset):
 
 
 def match_epsilon(d2, nq2, nt2):
-    """The error bound of a reported dist2 (include/fx.h): 2^-23 d2 + 2^-40 (|q|^2 + |t|^2)."""
-    return 2.0 ** -23 * d2 + 2.0 ** -40 * (nq2 + nt2)
+    """The error bound of a reported dist2 (include/fx.h): 2^-23 d2 + 2^-40 (|q|^2 + |t|^2) + 2^-150, the last term half the
+    smallest fp32 subnormal (the one rounding to fp32)."""
+    return 2.0 ** -23 * d2 + 2.0 ** -40 * (nq2 + nt2) + 2.0 ** -150
 
 
 def match_records(out):
@@ -497,13 +498,13 @@ def match_reference(rows_q, rows_t, pairs, shifts=12, max_dist2=np.inf, max_rati
     """The matching rule of include/fx.h stated in numpy on dense [n, 1989] float32 rows.  d2(q, t, s) = sum over the 1980 bins of
     (q[c] - t[(c + 165 s) mod 1980])^2, formed directly in float64 term by term (no |q|^2 + |t|^2 - 2 q.t): where q[c] is 0 the
     term is t^2, summed as such.  Returns a dict: "rec" (MATCH_DTYPE [n_q], what the library writes), "d2" (per pair the float64
-    array [q rows, t rows, shifts], NaN for rows that hold a NaN), "nq2" / "nt2" (|row|^2 of the bins, float64) and "ranges"
+    array [q rows, t rows, shifts], NaN for rows that hold a non-finite word), "nq2" / "nt2" (|row|^2 of the bins, float64) and "ranges"
     (per pair the clipped (q0, q1, t0, t1))."""
     rows_q = np.ascontiguousarray(rows_q, dtype=np.float32).reshape(-1, FX_DESC_FLOATS)
     rows_t = np.ascontiguousarray(rows_t, dtype=np.float32).reshape(-1, FX_DESC_FLOATS)
     nq, nt, B = len(rows_q), len(rows_t), FX_DESC_BINS
     Q, T = rows_q[:, :B].astype(np.float64), rows_t[:, :B].astype(np.float64)
-    q_nan, t_nan = np.isnan(rows_q).any(axis=1), np.isnan(rows_t).any(axis=1)
+    q_nan, t_nan = (~np.isfinite(rows_q)).any(axis=1), (~np.isfinite(rows_t)).any(axis=1)  # (any stored word, rf included)
     rec = np.zeros(nq, MATCH_DTYPE)
     rec["train_row"] = rec["second_row"] = -1
     rec["dist2"] = rec["dist2_second"] = np.inf

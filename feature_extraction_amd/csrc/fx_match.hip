@@ -3,12 +3,13 @@
 // d2(q, t, s) = sum over the 1980 bins c of (q[c] - t[(c + 165 s) mod 1980])^2: PCL's 3DSC draws a random azimuth reference per
 // keypoint, so two descriptors of one pole differ by a rotation of the 12 azimuth sectors, a cyclic shift of the bin index
 // by 165 (bin = l * 165 + k * 15 + j, l the sector).  Evaluated as |q|^2 + |t|^2 - 2 q.t_s with every sum in fp64 over the
-// exact fp32 x fp32 products and one rounding to fp32 at the end: within 2^-23 d2 + 2^-40 (|q|^2 + |t|^2) of the exact value.
+// exact fp32 x fp32 products and one rounding to fp32 at the end: within 2^-23 d2 + 2^-40 (|q|^2 + |t|^2) + 2^-150 of the exact
+// value (subnormal results are kept, a value from 2^128 - 2^103 on is +inf).
 // Every sum runs over a row's stored entries in their stored order, by one lane: nothing depends on the launch or on what
 // else runs, and identical rows give |q|^2 = |t|^2 = q.t_0 bit for bit, so their dist2 is exactly 0.
 //
-// Launches: k_match_norms (a thread a row: |row|^2 over the bins, NaN when the row stores a NaN), k_match_init (every output
-// record to "no match", the mutual table to all ones), k_match, and with `mutual` k_match_mutual.
+// Launches: k_match_norms (a thread a row: |row|^2 over the bins, NaN when the row stores a NaN or an infinity), k_match_init
+// (every output record to "no match", the mutual table to all ones), k_match, and with `mutual` k_match_mutual.
 //
 // k_match: one workgroup per (pair, tile of 64 query rows): eight wavefronts, each taking a query row a round for up to
 // eight rounds.  The query row is scattered dense into LDS TWICE back to back (q2[c] = q2[c + 1980] = q[c]; un-written
@@ -78,7 +79,7 @@ extern "C" __global__ __launch_bounds__(256) void k_match_norms(const uint32_t *
   bool nan = false;
   for (uint32_t e = e0; e < e1; ++e) {
     const float v = __uint_as_float(V.val[e]);
-    nan = nan || v != v;
+    nan = nan || !(fabsf(v) < INFINITY);  // NaN, +Inf, -Inf
     if (V.col[e] < FX_DESC_BINS) {
       const double d = (double)v;
       a += d * d;
@@ -137,7 +138,7 @@ __global__ __launch_bounds__(FXM_WG) void k_match(FxMatchArgs A) {
       }
     }
     wave_lds_sync();
-    const bool live = active && qn == qn;  // (a row that stores a NaN never matches)
+    const bool live = active && qn == qn;  // (a row that stores a non-finite word never matches)
 
     float b_d = INFINITY, c_d = INFINITY;  // this lane's best and second-best train row so far
     int32_t b_row = -1, c_row = -1;

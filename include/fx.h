@@ -374,12 +374,16 @@ fx_status fx_set_descriptor_csr_capacity(fx_ctx *ctx, uint32_t entries);
  * otherwise, checked on the host).  Per query row, (train_row, shift, dist2) minimise d2 over the pair's train rows and the
  * enabled shifts — ties to the lowest train row, then the lowest shift —, and (second_row, dist2_second) are the same minimum
  * over the pair's train rows other than train_row.  Every one of the q_max_rows records is written: a row in no pair or
- * clipped away gets train_row = -1, pair = 0xffffffff, dist2 = dist2_second = +inf, flags = 0.  A row that stores any NaN
- * (an FX_FLAG_NBR_OVERFLOW row) never matches and is never matched: train_row = -1 as a query, skipped as a train row.  A
- * row without stored words is an ordinary all-zero descriptor.
- * Numerics: dist2 is within 2^-23 d2 + 2^-40 (|q|^2 + |t|^2) of the exact value (fp64 sums of the exact fp32 products, one
- * rounding to fp32), never negative, exactly 0 for identical rows at shift 0, and the same bits from run to run and with
- * any number of contexts in flight.
+ * clipped away gets train_row = -1, pair = 0xffffffff, dist2 = dist2_second = +inf, flags = 0.  A row that stores any
+ * non-finite word — NaN (an FX_FLAG_NBR_OVERFLOW row), +Inf or -Inf, in a bin or in an rf word — never matches and is never
+ * matched: train_row = -1 as a query, skipped as a train row.  A row without stored words is an ordinary all-zero
+ * descriptor; -0.0 words count as 0.
+ * Numerics: dist2 is within 2^-23 d2 + 2^-40 (|q|^2 + |t|^2) + 2^-150 of the exact value (fp64 sums of the exact fp32
+ * products, one rounding to fp32 that keeps subnormal results: 2^-150 is half the smallest of them), never negative and
+ * never -0.0, exactly +0 for identical rows at shift 0, and the same bits from run to run and with any number of contexts
+ * in flight.  Finite rows can be too far apart for fp32: a value of 2^128 - 2^103 or more (FLT_MAX plus half an ulp) is
+ * reported as +inf, which orders and ties like any other value, passes max_dist2 = +inf only, and passes max_ratio when
+ * dist2_second is +inf too (max_ratio^2 * inf = inf) unless max_ratio is 0 (0 * inf is NaN: rejected).
  * Enqueued on the context's stream; needs no batch to have been processed.  pairs_host is copied before the call returns
  * into a context-owned buffer that grows when a call needs more; nothing else is allocated in the steady state.  New in 0.7
  * (added symbols only). */
