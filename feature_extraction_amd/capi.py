@@ -192,6 +192,28 @@ class FxMapMergeResult(C.Structure):
 MAP_MERGE_RESULT_FIELDS = ("proposals", "merged", "live", "reserved")
 
 
+class FxLocalizeOptions(C.Structure):
+    _fields_ = [("search_dist", C.c_float), ("inlier_dist", C.c_float), ("min_baseline", C.c_float), ("hyp_corr", C.c_uint32),
+                ("min_inliers", C.c_uint32), ("min_landmark_obs", C.c_uint32), ("segment", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class FxLocalization(C.Structure):
+    _fields_ = [("pose", FxPose), ("dc", C.c_double), ("ds", C.c_double), ("dtx", C.c_double), ("dty", C.c_double), ("dtz", C.c_double),
+                ("rms", C.c_float), ("n_corr", C.c_uint32), ("n_inliers", C.c_uint32), ("flags", C.c_uint32), ("hyp_a", C.c_uint32),
+                ("hyp_b", C.c_uint32)]
+
+
+FX_LOC_MAX_CORR = 1024
+FX_LOC_ANY_SEGMENT, FX_LOC_LAST_SEGMENT = 0xffffffff, 0xfffffffe
+FX_LOC_VALID, FX_LOC_TRUNCATED, FX_LOC_NO_HYPOTHESIS, FX_LOC_BAD_PRIOR, FX_LOC_NO_SCAN = 0x1, 0x2, 0x4, 0x8, 0x10
+FX_LOC_NO_ROW = 0xffffffff
+# fx_localization as numpy records (localize_records); "pose" is a POSE_DTYPE record
+LOC_DTYPE = np.dtype([("pose", POSE_DTYPE), ("dc", "<f8"), ("ds", "<f8"), ("dtx", "<f8"), ("dty", "<f8"), ("dtz", "<f8"), ("rms", "<f4"),
+                      ("n_corr", "<u4"), ("n_inliers", "<u4"), ("flags", "<u4"), ("hyp_a", "<u4"), ("hyp_b", "<u4")])
+LOC_DEFAULTS = dict(search_dist=2.0, inlier_dist=0.30, min_baseline=2.0, hyp_corr=64, min_inliers=3, min_landmark_obs=2,
+                    segment=FX_LOC_LAST_SEGMENT)
+
+
 class FxTimings(C.Structure):
     _fields_ = [("ms", C.c_float * FX_N_STAGES), ("total_ms", C.c_float), ("k_prep_exec_ms", C.c_float)]
 
@@ -217,6 +239,7 @@ EXPORTS = ("fx_version", "fx_check_abi", "fx_status_str", "fx_last_error", "fx_p
            "fx_track_options_default", "fx_track_landmarks",
            "fx_map_create", "fx_map_destroy", "fx_map_reset", "fx_map_update", "fx_map_get", "fx_map_read_header", "fx_map_read_landmarks",
            "fx_map_merge_options_default", "fx_map_merge", "fx_map_get_alias", "fx_map_read_alias",
+           "fx_localize_options_default", "fx_map_localize",
            "fx_rotation_from_roll_pitch", "fx_sc3d_tables", "fx_sc3d_xaxis", "fx_synth_cfg_vlp16",
            "fx_synth_scan", "fx_unpack_pointcloud2", "fx_pack_pointxyzi")
 # the header's FX_TEST_HOOKS section: exported by lib/libfx_hip_test.so only
@@ -345,6 +368,10 @@ def load():
     lib.fx_map_merge.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(FxMapMergeOptions), C.c_void_p]
     lib.fx_map_get_alias.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     lib.fx_map_read_alias.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+    lib.fx_localize_options_default.argtypes = [C.POINTER(FxLocalizeOptions)]
+    lib.fx_localize_options_default.restype = None
+    lib.fx_map_localize.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
+                                    C.POINTER(FxLocalizeOptions), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.fx_rotation_from_roll_pitch.argtypes = [C.c_double, C.c_double, _F32P]
     lib.fx_rotation_from_roll_pitch.restype = None
     lib.fx_sc3d_tables.argtypes = [C.c_double, _F32P, _F32P, _F32P, _F32P]
@@ -1086,6 +1113,156 @@ def map_merge_reference(state, merge_dist=0.30, max_gap_scans=64):
     return st, {"proposals": len(prop), "merged": len(succ), "live": live, "reserved": 0}
 
 
+# ---- scans localised against the map under a prior pose (include/fx.h fx_map_localize)
+def localize_records(out):
+    """A host copy of fx_map_localize's records (a torch tensor, or any array of n * 112 bytes) as LOC_DTYPE records."""
+    if hasattr(out, "detach"):
+        out = out.detach().cpu().numpy()
+    return np.ascontiguousarray(out).view(np.uint8).reshape(-1).view(LOC_DTYPE).copy()
+
+
+def map_localize_reference(state, kp_offset, kp_rows, prior_poses, n_scans, q_max_rows=None, search_dist=2.0, inlier_dist=0.30,
+                           min_baseline=2.0, hyp_corr=64, min_inliers=3, min_landmark_obs=2, segment=FX_LOC_LAST_SEGMENT):
+    """The definition of fx_map_localize (include/fx.h) in numpy float64 over a map_reference / map_merge_reference state (which is
+    only read).  kp_offset / kp_rows: the block's kp_offset[scans + 1] and its [stored, >= 3] float32 rows, already cut to
+    min(stored, max_total_keypoints); prior_poses: POSE_DTYPE [>= n_scans]; q_max_rows: the length of the row arrays (default: the
+    block's rows).  Every (row, landmark) pair is looked at: nothing here knows of a grid.  One ufunc an operation, so nothing is
+    contracted.  Returns {"rec": LOC_DTYPE [n_scans], "map_id_of_row", "nearest_of_row": int32 [q_max_rows], "corr": per scan
+    the rows of its correspondences}."""
+    f64 = np.float64
+    off = [int(x) for x in kp_offset]
+    kp = np.ascontiguousarray(kp_rows, dtype=np.float32)
+    kp = kp.reshape(len(kp), -1)[:, :3] if kp.size else np.zeros((0, 3), np.float32)
+    n_scans = int(n_scans)
+    R = len(kp) if q_max_rows is None else int(q_max_rows)
+    sd32, id32, mb32 = np.float32(search_dist), np.float32(inlier_dist), np.float32(min_baseline)
+    if not (n_scans >= 1 and all(np.isfinite(v) and v > 0 for v in (sd32, id32, mb32)) and 2 <= hyp_corr <= 128 and min_inliers >= 2 and
+            min_landmark_obs >= 1):
+        raise ValueError("arguments outside what fx_map_localize accepts")
+    sd, idd, mbd = f64(sd32), f64(id32), f64(mb32)
+    sd2, mb2, gate, id2 = sd * sd, mbd * mbd, f64(2.0) * idd, idd * idd
+    prior = np.asarray(prior_poses)[:n_scans]
+    S, rows = min(n_scans, len(off) - 1), min(len(kp), R)
+    # the eligible landmarks
+    lms = state["landmarks"]
+    N = min(int(state["header"]["n_landmarks"]), len(lms))
+    alias = [int(a) for a in state.get("alias", [])][:N]
+    alias += [-1] * (N - len(alias))
+    lx, ly, lz = (np.array([float(r[f]) for r in lms[:N]], f64) for f in ("x", "y", "z"))
+    want = int(segment) & 0xffffffff
+    if want == FX_LOC_LAST_SEGMENT:
+        want = int(state["header"]["segments"]) - 1  # (-1 in a map of no segment: nothing is eligible)
+    elig = np.array([alias[g] == -1 and int(lms[g]["n_obs"]) >= min_landmark_obs and (want == FX_LOC_ANY_SEGMENT or int(lms[g]["segment"]) == want)
+                     for g in range(N)], bool)
+    if N:
+        elig &= np.isfinite(lx) & np.isfinite(ly) & np.isfinite(lz)
+    ids = np.flatnonzero(elig)
+    rec = np.zeros(n_scans, LOC_DTYPE)
+    rec["pose"] = prior
+    rec["dc"], rec["rms"], rec["hyp_a"], rec["hyp_b"] = 1.0, np.inf, FX_LOC_NO_ROW, FX_LOC_NO_ROW
+    nearest, map_id = np.full(R, -1, np.int32), np.full(R, -1, np.int32)
+    d2_of = np.zeros(R, np.uint64)
+    W = np.zeros((R, 3), f64)
+    corrs = []
+    with np.errstate(all="ignore"):
+        for b in range(n_scans):
+            P = prior[b]
+            if b >= S:
+                rec["flags"][b] = FX_LOC_NO_SCAN
+                corrs.append(np.zeros(0, np.uint32))
+                continue
+            pc, ps, ptx, pty, ptz = (f64(P[f]) for f in ("c", "s", "tx", "ty", "tz"))
+            if not all(np.isfinite(v) for v in (pc, ps, ptx, pty, ptz)):
+                rec["flags"][b] = FX_LOC_BAD_PRIOR
+                corrs.append(np.zeros(0, np.uint32))
+                continue
+            lo = min(off[b], rows)
+            hi = max(min(off[b + 1], rows), lo)
+            r = np.arange(lo, hi)
+            x, y, z = (kp[lo:hi, k].astype(f64) for k in range(3))
+            wx, wy, wz = (pc * x - ps * y) + ptx, (ps * x + pc * y) + pty, z + ptz
+            W[lo:hi] = np.stack([wx, wy, wz], axis=1)
+            fin = np.isfinite(kp[lo:hi]).all(axis=1)
+            if len(ids) and len(r):
+                dx, dy = lx[ids][None, :] - wx[:, None], ly[ids][None, :] - wy[:, None]
+                d2 = dx * dx + dy * dy
+                key = np.where(d2 <= sd2, d2, np.inf).view(np.uint64)  # (the bits of +inf are above those of any distance in reach)
+                j = np.argmin(key, axis=1)  # (the first minimum: ids ascend, so ties go to the lowest id)
+                hit = fin & (d2[np.arange(len(r)), j] <= sd2)
+                nearest[lo:hi][hit] = ids[j[hit]]
+                d2_of[lo:hi][hit] = d2[np.arange(len(r)), j].view(np.uint64)[hit]
+            i = r[nearest[lo:hi] >= 0]
+            flags = FX_LOC_TRUNCATED if len(i) > FX_LOC_MAX_CORR else 0
+            i = i[:FX_LOC_MAX_CORR]
+            n = len(i)
+            corrs.append(i.astype(np.uint32))
+            rec["n_corr"][b] = n
+            g = nearest[i]
+            P64 = np.stack([W[i, 0], W[i, 1], lx[g], ly[g]], axis=1) if n else np.zeros((0, 4), f64)  # (qx, qy, tx, ty)
+            H = min(n, int(hyp_corr))
+            best = None
+            if H >= 2:
+                pool = np.lexsort((i, d2_of[i]))[:H]  # by (d2 bits, row)
+                a, c_ = np.triu_indices(H, 1)          # lexicographic (a, b), a < b
+                A, B = P64[pool[a]], P64[pool[c_]]
+                dqx, dqy, dtx, dty = B[:, 0] - A[:, 0], B[:, 1] - A[:, 1], B[:, 2] - A[:, 2], B[:, 3] - A[:, 3]
+                lq2, lt2 = dqx * dqx + dqy * dqy, dtx * dtx + dty * dty
+                keep = (lq2 >= mb2) & (lt2 >= mb2)
+                keep &= ~(np.abs(np.sqrt(lq2) - np.sqrt(lt2)) > gate)
+                dot, crs = dqx * dtx + dqy * dty, dqx * dty - dqy * dtx
+                nrm = np.sqrt(dot * dot + crs * crs)
+                keep &= nrm > 0
+                c, s = dot / nrm, crs / nrm
+                half = f64(0.5)
+                mqx, mqy, mtx, mty = (A[:, 0] + B[:, 0]) * half, (A[:, 1] + B[:, 1]) * half, (A[:, 2] + B[:, 2]) * half, (A[:, 3] + B[:, 3]) * half
+                tx, ty = mtx - (c * mqx - s * mqy), mty - (s * mqx + c * mqy)
+                ks = np.flatnonzero(keep)
+                counts = np.zeros(len(a), np.int64)
+                for lo_ in range(0, len(ks), 512):  # (chunks: [samples, n] temporaries)
+                    k = ks[lo_:lo_ + 512]
+                    ck, sk, txk, tyk = c[k, None], s[k, None], tx[k, None], ty[k, None]
+                    qx, qy, t_x, t_y = P64[None, :, 0], P64[None, :, 1], P64[None, :, 2], P64[None, :, 3]
+                    rx, ry = ((ck * qx - sk * qy) + txk) - t_x, ((sk * qx + ck * qy) + tyk) - t_y
+                    counts[k] = (rx * rx + ry * ry <= id2).sum(axis=1)
+                counts[counts < 2] = 0  # (a sample with fewer than 2 agreeing is no hypothesis)
+                if counts.any():
+                    best = int(np.argmax(counts))  # (the first maximum: the lowest (a, b))
+                    rx = ((c[best] * P64[:, 0] - s[best] * P64[:, 1]) + tx[best]) - P64[:, 2]
+                    ry = ((s[best] * P64[:, 0] + c[best] * P64[:, 1]) + ty[best]) - P64[:, 3]
+                    I0 = [int(v) for v in np.flatnonzero(rx * rx + ry * ry <= id2)]
+                    assert len(I0) == int(counts[best])
+            if best is None:
+                rec["flags"][b] = flags | FX_LOC_NO_HYPOTHESIS
+                continue
+            Pl = [tuple(float(v) for v in row) for row in P64]  # (Python floats: IEEE doubles, the register's refit as it is)
+            fit = _register_fit(Pl, I0, float(c[best]), float(s[best]))
+            final = I0
+            I1 = [k for k in range(n) if _register_r2(Pl, k, *fit) <= float(id2)]
+            if len(I1) >= 2:
+                fit = _register_fit(Pl, I1, fit[0], fit[1])
+                final = I1
+            sz = sr = 0.0
+            for k in final:
+                sz += (float(lz[g[k]]) - float(W[i[k], 2]))
+                sr += _register_r2(Pl, k, *fit)
+            nf = float(len(final))
+            dc, ds, dtx_, dty_ = fit
+            dtz = sz / nf
+            rec["dc"][b], rec["ds"][b], rec["dtx"][b], rec["dty"][b], rec["dtz"][b] = dc, ds, dtx_, dty_, dtz
+            rec["rms"][b] = np.float32(math.sqrt(sr / nf))
+            rec["n_inliers"][b] = len(final)
+            valid = len(final) >= min_inliers
+            rec["flags"][b] = flags | (FX_LOC_VALID if valid else 0)
+            rec["hyp_a"][b], rec["hyp_b"][b] = i[pool[a[best]]], i[pool[c_[best]]]
+            if valid:
+                qc, qs, qtx, qty, qtz = (float(v) for v in (pc, ps, ptx, pty, ptz))
+                rec["pose"]["c"][b], rec["pose"]["s"][b] = dc * qc - ds * qs, ds * qc + dc * qs
+                rec["pose"]["tx"][b], rec["pose"]["ty"][b] = (dc * qtx - ds * qty) + dtx_, (ds * qtx + dc * qty) + dty_
+                rec["pose"]["tz"][b] = qtz + dtz
+            map_id[i[final]] = g[final]
+    return {"rec": rec, "map_id_of_row": map_id, "nearest_of_row": nearest, "corr": corrs}
+
+
 def _np(ptr, shape, dtype):
     n = int(np.prod(shape))
     if n == 0 or not ptr:
@@ -1162,6 +1339,43 @@ class Map:
         check(self.lib.fx_map_merge(self.ctx.handle, self.handle, C.byref(opt), C.c_void_p(result.data_ptr() if result is not None else None)))
         cur.wait_stream(ext)
         return result
+
+    def localize(self, kp, prior_poses, n_scans, q_max_rows=None, out=None, nearest=None, **opts):
+        """fx_map_localize: the scans of the keypoint block kp = (device tensor, max_scans, max_total_keypoints) against this map
+        under prior_poses, a device tensor of n_scans fx_pose records (the first output of Context.track_landmarks, or the "pose"
+        bytes of an earlier round).  opts: the fields of fx_localize_options (LOC_DEFAULTS).  Returns (records, map_id_of_row,
+        nearest_of_row): device tensors of n_scans * 112 bytes (localize_records reads them) and torch.int32 [q_max_rows] each;
+        out = (records, map_id_of_row) reuses two, nearest=False passes NULL (None is returned), a tensor reuses it.
+        Stream-correct like update(); never waits for the stream."""
+        import torch
+        kb, scans, total = kp
+        dev = torch.device("cuda", self.ctx.device)
+        n_scans = int(n_scans)
+        n_rows = int(total) if q_max_rows is None else int(q_max_rows)
+        bad = set(opts) - set(LOC_DEFAULTS)
+        if bad:
+            raise TypeError(f"unknown localize options {sorted(bad)}")
+        o = dict(LOC_DEFAULTS, **opts)
+        opt = FxLocalizeOptions(float(o["search_dist"]), float(o["inlier_dist"]), float(o["min_baseline"]), int(o["hyp_corr"]),
+                                int(o["min_inliers"]), int(o["min_landmark_obs"]), int(o["segment"]) & 0xffffffff, 0)
+        if out is None:
+            out = (torch.empty((n_scans, LOC_DTYPE.itemsize // 8), dtype=torch.float64, device=dev), torch.empty((n_rows,), dtype=torch.int32, device=dev))
+        recs, ids = out
+        if nearest is None:
+            nearest = torch.empty((n_rows,), dtype=torch.int32, device=dev)
+        elif nearest is False:
+            nearest = None
+        for t, size in ((recs, n_scans * LOC_DTYPE.itemsize), (ids, n_rows * 4), (nearest, n_rows * 4)):
+            if t is not None and (t.device != dev or not t.is_contiguous() or t.numel() * t.element_size() != size):
+                raise ValueError(f"outputs must be contiguous tensors of {n_scans} * 112 and {n_rows} * 4 bytes on {dev}")
+        cur = torch.cuda.current_stream(dev)
+        ext = torch.cuda.ExternalStream(self.ctx.stream_ptr(), device=dev)
+        ext.wait_stream(cur)
+        check(self.lib.fx_map_localize(self.ctx.handle, self.handle, C.c_void_p(kb.data_ptr()), int(scans), int(total),
+                                       C.c_void_p(prior_poses.data_ptr()), n_scans, n_rows, C.byref(opt), C.c_void_p(recs.data_ptr()),
+                                       C.c_void_p(ids.data_ptr() if n_rows else None), C.c_void_p(nearest.data_ptr() if nearest is not None and n_rows else None)))
+        cur.wait_stream(ext)
+        return recs, ids, nearest
 
     def alias(self, first=0, count=None):
         """fx_map_read_alias (waits for the stream): alias[first, first + count) as int32, -1 for a live landmark, else the id of

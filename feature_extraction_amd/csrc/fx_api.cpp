@@ -91,6 +91,8 @@ hipError_t fxk_map_merge(hipStream_t s, const FxMapMergeArgs &A);
 uint32_t fxk_map_merge_table(uint32_t cap);
 size_t fxk_map_merge_scratch(FxMapMergeArgs *A, uint8_t *base);
 uint32_t fxk_map_merge_wg(void);
+hipError_t fxk_map_localize(hipStream_t s, const FxMapLocalizeArgs &A);
+size_t fxk_map_localize_scratch(FxMapLocalizeArgs *A, uint8_t *base);
 #ifdef FX_TEST_HOOKS
 void fxk_test_sort_replay(hipStream_t s, const uint32_t *sizes, uint32_t n_seq, uint32_t n, uint32_t *perm);
 void fxk_test_elevation(hipStream_t s, const float *xyz, uint32_t n, const double *tab, float *fast, uint8_t *ok, float *exact);
@@ -260,7 +262,8 @@ struct fx_ctx {
   Staging reg_stage;         // fx_register_matches: the pairs
   DevScratch track_scratch;  // fx_track_landmarks: the per-row scratch arrays
   DevScratch map_scratch;    // fx_map_update: the batch landmark's map id, the blocks' counts
-  DevScratch merge_scratch;  // fx_map_merge: the grid (bucket counts, landmarks in bucket order), proposals, kept links
+  DevScratch merge_scratch;  // fx_map_merge: the grid (bucket counts, landmarks in bucket order), proposals, kept links;
+                             // fx_map_localize: the same grid, then each row's landmark and distance
 };
 
 // A persistent landmark map (include/fx.h fx_map_create): one device buffer, carved up once.
@@ -1905,7 +1908,7 @@ fx_status fx_map_merge(fx_ctx *c, fx_map *m, const fx_map_merge_options *opt, fx
   FxMapMergeArgs A{};
   A.header = m->a.header, A.records = m->a.records, A.acc = m->a.acc, A.carry = m->a.carry, A.alias = m->a.alias;
   A.cap = m->a.cap, A.max_carry = m->a.max_carry;
-  // the gate in fp64 and the grid's cell edge: md (1 + 2^-8), exact (csrc/fx_map_merge.hip proves the margin)
+  // the gate in fp64 and the grid's cell edge: md (1 + 2^-8), exact (csrc/fx_map_grid.h proves the margin)
   const double md = (double)o.merge_dist;
   A.md2 = md * md, A.inv_edge = 1.0 / (md * (1.0 + 1.0 / 256.0));
   A.max_gap = o.max_gap_scans, A.table = fxk_map_merge_table(A.cap);
@@ -1913,6 +1916,58 @@ fx_status fx_map_merge(fx_ctx *c, fx_map *m, const fx_map_merge_options *opt, fx
   FX_TRY(c->merge_scratch.reserve(c, fxk_map_merge_scratch(&A, nullptr), "map merge scratch"));
   (void)fxk_map_merge_scratch(&A, c->merge_scratch.d);
   FX_HIP(fxk_map_merge(c->stream, A));
+  return FX_OK;
+}
+
+void fx_localize_options_default(fx_localize_options *o) {
+  if (!o) return;
+  o->search_dist = 2.0f;
+  o->inlier_dist = 0.30f;
+  o->min_baseline = 2.0f;
+  o->hyp_corr = 64u;
+  o->min_inliers = 3u;
+  o->min_landmark_obs = 2u;
+  o->segment = FX_LOC_LAST_SEGMENT;
+  o->reserved = 0u;
+}
+
+fx_status fx_map_localize(fx_ctx *c, fx_map *m, const void *kp, uint32_t max_scans, uint32_t max_total, const fx_pose *priors, uint32_t n_scans,
+                          uint32_t q_max_rows, const fx_localize_options *opt, fx_localization *out, int32_t *map_id_of_row,
+                          int32_t *nearest_of_row) {
+  if (!c || !m) return fail(FX_ERR_INVALID_ARG, "null argument");
+  if (m->ctx != c) return fail(FX_ERR_INVALID_ARG, "the map belongs to another context");
+  if (!n_scans || n_scans > max_scans)
+    return fail(FX_ERR_INVALID_ARG, "n_scans must be 1..max_scans (" + std::to_string(n_scans) + " of " + std::to_string(max_scans) + ")");
+  if (!kp || !priors || !out || (q_max_rows && !map_id_of_row)) return fail(FX_ERR_INVALID_ARG, "null argument");
+  if (((uintptr_t)kp % 16) != 0 || ((uintptr_t)priors % 8) != 0 || ((uintptr_t)out % 8) != 0 || ((uintptr_t)map_id_of_row % 4) != 0 ||
+      ((uintptr_t)nearest_of_row % 4) != 0)
+    return fail(FX_ERR_INVALID_ARG, "the keypoint block must be 16-byte, the records 8-byte, the words 4-byte aligned");
+  fx_localize_options o;
+  fx_localize_options_default(&o);
+  if (opt) o = *opt;
+  if (!(std::isfinite(o.search_dist) && o.search_dist > 0.f)) return fail(FX_ERR_INVALID_ARG, "search_dist must be finite and positive");
+  if (!(o.inlier_dist > 0.f) || !std::isfinite(o.inlier_dist) || !(o.min_baseline > 0.f) || !std::isfinite(o.min_baseline))
+    return fail(FX_ERR_INVALID_ARG, "inlier_dist and min_baseline must be finite and positive");
+  if (o.hyp_corr < 2u || o.hyp_corr > 128u) return fail(FX_ERR_INVALID_ARG, "hyp_corr must be 2..128");
+  if (o.min_inliers < 2u) return fail(FX_ERR_INVALID_ARG, "min_inliers must be at least 2");
+  if (!o.min_landmark_obs) return fail(FX_ERR_INVALID_ARG, "min_landmark_obs must be at least 1");
+  if (o.reserved) return fail(FX_ERR_INVALID_ARG, "reserved must be 0");
+  FX_HIP(hipSetDevice(c->device));
+  FxMapLocalizeArgs A{};
+  A.G.header = m->a.header, A.G.records = m->a.records, A.G.acc = m->a.acc, A.G.carry = m->a.carry, A.G.alias = m->a.alias;
+  A.G.cap = m->a.cap, A.G.max_carry = m->a.max_carry;
+  // the gate in fp64 and the grid's cell edge: sd (1 + 2^-8), exact (csrc/fx_map_grid.h proves the margin)
+  const double sd = (double)o.search_dist;
+  A.G.md2 = sd * sd, A.G.inv_edge = 1.0 / (sd * (1.0 + 1.0 / 256.0));
+  A.G.table = fxk_map_merge_table(A.G.cap);
+  A.kp = (const uint32_t *)kp, A.max_scans = max_scans, A.max_total = max_total;
+  A.priors = priors, A.n_scans = n_scans, A.q_max_rows = q_max_rows;
+  A.inlier_dist = o.inlier_dist, A.min_baseline = o.min_baseline;
+  A.hyp_corr = o.hyp_corr, A.min_inliers = o.min_inliers, A.min_landmark_obs = o.min_landmark_obs, A.segment = o.segment;
+  A.out = out, A.map_id_of_row = map_id_of_row, A.nearest_of_row = nearest_of_row;
+  FX_TRY(c->merge_scratch.reserve(c, fxk_map_localize_scratch(&A, nullptr), "map localize scratch"));
+  (void)fxk_map_localize_scratch(&A, c->merge_scratch.d);
+  FX_HIP(fxk_map_localize(c->stream, A));
   return FX_OK;
 }
 

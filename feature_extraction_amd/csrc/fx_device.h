@@ -255,6 +255,22 @@ struct FxMapMergeArgs {
   unsigned long long *keep;     // [cap]: (first_scan << 32) | h of g's proposers, atomic min
   int32_t *pred, *succ;         // [cap]: the kept link into / out of the landmark, -1: none
 };
+// fx_map_localize (csrc/fx_map_localize.hip): a launch set's arguments.  G describes the grid over the map (its gate is the
+// search distance; the merge's per-landmark arrays are null); the last group is the context's scratch, [q_max_rows] each.
+struct FxMapLocalizeArgs {
+  FxMapMergeArgs G;
+  const uint32_t *kp;           // keypoint block (include/fx.h fx_pack_keypoint_block)
+  uint32_t max_scans, max_total;
+  const void *priors;           // fx_pose [n_scans]
+  uint32_t n_scans, q_max_rows;
+  float inlier_dist, min_baseline;
+  uint32_t hyp_corr, min_inliers, min_landmark_obs, segment;
+  void *out;                    // fx_localization [n_scans]
+  int32_t *map_id_of_row;       // [q_max_rows]
+  int32_t *nearest_of_row;      // [q_max_rows] or null
+  int32_t *near;                // the row's landmark, -1: none
+  unsigned long long *d2;       // its squared xy distance as bits
+};
 #define FX_TRACK_NONE 0xffffffffu
 #define FX_N_HINTS 8     // tier_hint[]: 0 / 1 rings handed to the second run tier / the workgroup tier (largest XCD class), 2 big merges, 3 huge merges, 4 dense rows, 5 dense support points, 6 scans k_front handed to k_front_redo, 7 scans handed to the slow tier (k_slow)
 #define FX_CNT_QPOOL 32   // counters[32]: entries of the dense tier's query pool in use

@@ -7,25 +7,10 @@
 // chain on one lane (the build's -ffp-contract=off).  Counts come from the map's header on the device; the grids are sized by the
 // map's max_landmarks and exit early.
 //
-// The grid.  Cell edge E = md (1 + 2^-8), md = (double)merge_dist (exact: 24 + 9 bits); a coordinate's cell is floor(t),
-// t = fl(x * fl(1 / E)).  Claim: two landmarks that pass the gate lie at most one cell apart in x and in y, as long as one of them
-// has |floor(t)| < 2^39 ("near").  Proof, for x, u = 2^-53: the gate holds for computed values, fl(fl(dx dx) + fl(dy dy)) <=
-// fl(md md) with dx = fl(px - qx); rounding is monotone and the second term is not negative, so fl(dx dx) <= fl(md md), so
-// dx^2 (1 - u) <= md^2 (1 + u) (a dx^2 that underflows is far below any md^2, md >= 2^-149), and with |px - qx| <= |dx| / (1 - u):
-// |px - qx| <= md (1 + 2^-50).  t carries two roundings: t = (x / E)(1 + d), |d| < 2^-51.  One of the two is near, so both have
-// |x / E| < 2^39 + 3 < 2^40, and |tp - tq| <= |px - qx| / E + 2^-51 (|px| + |qx|) / E < (1 + 2^-50) / (1 + 2^-8) + 2^-10
-// < 1 - 2^-8 + 2^-15 + 2^-10 < 1.  Two numbers less than 1 apart have floors at most 1 apart.  Landmarks that are not near
-// (|floor(t)| >= 2^39 in x or y: beyond 10^11 m at the default gate) are kept out of the table in one list, the far bucket, which
-// every search walks as well (it is empty in any real map); a far landmark below 2^41 also searches its 3 x 3 cells, which by the
-// claim hold every near landmark within its gate, and beyond 2^41 no near landmark can be within it.
-//
+// The grid is fx_map_grid.h's, where the proof of its one-cell margin stands; its first five launches are csrc/fx_map_grid.hip's
+// (fxk_map_grid_build), which fx_map_localize shares.
 // Launches, in stream order (FXMM_WG = 256 landmarks or buckets a workgroup; N = the header's n_landmarks):
-//   k_mm_clear    the buckets' counts and the state words to 0
-//   k_mm_mark     a thread a landmark: does it take part (alias -1, n_obs >= 1, x and y finite), its bucket, the bucket's count
-//                 (32-bit atomic add); resets its proposal, its acceptance word and its links
-//   k_mm_scan     a workgroup a block of buckets: the exclusive prefix of the counts inside the block (wg_scan2)
-//   k_mm_top      one workgroup: the blocks' exclusive prefix (wg_scan2_blocks) and the number of landmarks in the grid
-//   k_mm_scatter  a thread a landmark: its (x, y, last_scan, segment, id) into its bucket's range, the slot by an atomic on the count
+//   (fxk_map_grid_build's five: clear, mark, scan, top, scatter; csrc/fx_map_grid.hip lists them)
 //   k_mm_search   a thread a landmark h: the 3 x 3 cells' buckets and the far bucket; the best g by (greatest last_scan, smallest
 //                 d2 as bits, lowest id); prop[h] = g and keep[g] = min(keep[g], first_scan[h] << 32 | h)
 //   k_mm_link     a thread a landmark h: its proposal was kept iff the low word of keep[prop[h]] is h: pred[h], succ[g]
@@ -39,37 +24,16 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "fx_device.h"
+#include "fx_map_grid.h"
 #include "../../include/fx.h"
 
-#define FXMM_WG 256
-#define FXMM_NWAVE (FXMM_WG / 64)
-#define FXMM_NONE 0xffffffffu
+using namespace fxg;
+
+extern "C" hipError_t fxk_map_grid_build(hipStream_t s, const FxMapMergeArgs &A);
 
 static_assert(sizeof(fx_map_landmark) == 48 && sizeof(FxMapMergeCand) == 32 && sizeof(fx_map_merge_result) == 16, "include/fx.h");
 
 namespace {
-constexpr double kFar = 549755813888.0;    // 2^39: cells from here on go to the far bucket
-constexpr double kReach = 2199023255552.0;  // 2^41: a far landmark below this still searches its 3 x 3 cells
-
-__device__ __forceinline__ uint32_t n_landmarks(const FxMapMergeArgs &A) {
-  return min(reinterpret_cast<const fx_map_header *>(A.header)->n_landmarks, A.cap);
-}
-__device__ __forceinline__ const fx_map_landmark *records(const FxMapMergeArgs &A) { return reinterpret_cast<const fx_map_landmark *>(A.records); }
-__device__ __forceinline__ bool takes_part(const FxMapMergeArgs &A, uint32_t i, const fx_map_landmark &R) {
-  return A.alias[i] == -1 && R.n_obs >= 1u && isfinite(R.x) && isfinite(R.y);
-}
-__device__ __forceinline__ uint32_t bucket_of_cell(long long cx, long long cy, uint32_t table) {
-  unsigned long long h = (unsigned long long)cx * 0x9E3779B97F4A7C15ull + (unsigned long long)cy * 0xC2B2AE3D27D4EB4Full;
-  h ^= h >> 32;
-  h *= 0xD6E8FEB86659FD93ull;
-  h ^= h >> 32;
-  return (uint32_t)h & (table - 1u);
-}
-// first slot of bucket b (b <= table) in the sorted order; the slot behind the last bucket is the number of landmarks in the grid
-__device__ __forceinline__ uint32_t bucket_begin(const FxMapMergeArgs &A, uint32_t b) { return A.bsum[b / FXMM_WG] + A.start[b]; }
-__device__ __forceinline__ uint32_t bucket_end(const FxMapMergeArgs &A, uint32_t b) { return b == A.table ? A.st[3] : bucket_begin(A, b + 1u); }
-
 // the best predecessor so far of one h: greatest last_scan, then smallest d2 (bits), then lowest id
 struct Best {
   uint32_t last, id;
@@ -91,57 +55,6 @@ __device__ __forceinline__ void walk(const FxMapMergeArgs &A, uint32_t b, uint32
 }
 }  // namespace
 
-extern "C" __global__ __launch_bounds__(FXMM_WG) void k_mm_clear(FxMapMergeArgs A) {
-  const uint32_t b = blockIdx.x * FXMM_WG + threadIdx.x;
-  if (b <= A.table) A.count[b] = 0u;
-  if (b < FX_MAP_MERGE_ST_WORDS) A.st[b] = 0u;
-}
-
-extern "C" __global__ __launch_bounds__(FXMM_WG) void k_mm_mark(FxMapMergeArgs A) {
-  const uint32_t i = blockIdx.x * FXMM_WG + threadIdx.x;
-  if (i >= n_landmarks(A)) return;
-  const fx_map_landmark R = records(A)[i];
-  uint32_t b = FXMM_NONE;
-  if (takes_part(A, i, R)) {
-    const double tx = floor(R.x * A.inv_edge), ty = floor(R.y * A.inv_edge);
-    const bool far = !(fabs(tx) < kFar && fabs(ty) < kFar);
-    b = far ? A.table : bucket_of_cell((long long)tx, (long long)ty, A.table);
-    atomicAdd(&A.count[b], 1u);
-  }
-  A.bucket[i] = b;
-  A.prop[i] = -1, A.pred[i] = -1, A.succ[i] = -1;
-  A.keep[i] = ~0ull;
-}
-
-extern "C" __global__ __launch_bounds__(FXMM_WG) void k_mm_scan(FxMapMergeArgs A, uint32_t n_blocks) {
-  __shared__ uint32_t s_w[2 * FXMM_NWAVE];
-  const uint32_t b = blockIdx.x * FXMM_WG + threadIdx.x;
-  uint32_t ea, eb, ta, tb;
-  wg_scan2<FXMM_NWAVE>(b <= A.table ? A.count[b] : 0u, 0u, s_w, ea, eb, ta, tb);
-  if (b <= A.table) A.start[b] = ea;
-  if (threadIdx.x == 0u) A.bsum[blockIdx.x] = ta, A.bsum[n_blocks + blockIdx.x] = 0u;
-}
-
-extern "C" __global__ __launch_bounds__(FXMM_WG) void k_mm_top(FxMapMergeArgs A, uint32_t n_blocks) {
-  __shared__ uint32_t s_w[2 * FXMM_NWAVE];
-  uint32_t total, unused;
-  wg_scan2_blocks<FXMM_NWAVE>(A.bsum, n_blocks, s_w, total, unused);
-  if (threadIdx.x == 0u) A.st[3] = total;
-}
-
-extern "C" __global__ __launch_bounds__(FXMM_WG) void k_mm_scatter(FxMapMergeArgs A) {
-  const uint32_t i = blockIdx.x * FXMM_WG + threadIdx.x;
-  if (i >= n_landmarks(A)) return;
-  const uint32_t b = A.bucket[i];
-  if (b == FXMM_NONE) return;
-  const uint32_t slot = bucket_begin(A, b) + (atomicSub(&A.count[b], 1u) - 1u);  // any order inside the bucket
-  if (slot >= A.cap) return;  // (cannot happen: the counts are of landmarks below cap)
-  const fx_map_landmark R = records(A)[i];
-  FxMapMergeCand c;
-  c.x = R.x, c.y = R.y, c.last_scan = R.last_scan, c.segment = R.segment, c.id = i, c.pad_ = 0u;
-  A.cand[slot] = c;
-}
-
 extern "C" __global__ __launch_bounds__(FXMM_WG) void k_mm_search(FxMapMergeArgs A) {
   const uint32_t h = blockIdx.x * FXMM_WG + threadIdx.x;
   bool proposes = false;
@@ -150,12 +63,7 @@ extern "C" __global__ __launch_bounds__(FXMM_WG) void k_mm_search(FxMapMergeArgs
     const double tx = floor(R.x * A.inv_edge), ty = floor(R.y * A.inv_edge);
     Best best;
     best.any = false, best.last = 0u, best.id = 0u, best.d2 = 0ull;
-    if (fabs(tx) < kReach && fabs(ty) < kReach) {
-      const long long cx = (long long)tx, cy = (long long)ty;
-      for (int oy = -1; oy <= 1; ++oy)
-        for (int ox = -1; ox <= 1; ++ox) walk(A, bucket_of_cell(cx + ox, cy + oy, A.table), h, R, best);  // (a bucket met twice changes nothing)
-    }
-    walk(A, A.table, h, R, best);
+    grid_neighbourhood(A, tx, ty, [&](uint32_t b) { walk(A, b, h, R, best); });
     if (best.any) {
       proposes = true;
       A.prop[h] = (int32_t)best.id;
@@ -243,26 +151,15 @@ extern "C" __global__ __launch_bounds__(64) void k_mm_finish(FxMapMergeArgs A) {
 
 extern "C" hipError_t fxk_map_merge(hipStream_t s, const FxMapMergeArgs &A) {
   const dim3 wg(FXMM_WG);
-  const uint32_t nb = (A.table + 1u + FXMM_WG - 1u) / FXMM_WG, nl = (A.cap + FXMM_WG - 1u) / FXMM_WG;
+  const uint32_t nl = (A.cap + FXMM_WG - 1u) / FXMM_WG;
   const uint32_t nr = ((A.cap > A.max_carry ? A.cap : A.max_carry) + FXMM_WG - 1u) / FXMM_WG;
-  hipLaunchKernelGGL(k_mm_clear, dim3(nb), wg, 0, s, A);
-  hipLaunchKernelGGL(k_mm_mark, dim3(nl), wg, 0, s, A);
-  hipLaunchKernelGGL(k_mm_scan, dim3(nb), wg, 0, s, A, nb);
-  hipLaunchKernelGGL(k_mm_top, dim3(1), wg, 0, s, A, nb);
-  hipLaunchKernelGGL(k_mm_scatter, dim3(nl), wg, 0, s, A);
+  (void)fxk_map_grid_build(s, A);  // k_mm_clear .. k_mm_scatter
   hipLaunchKernelGGL(k_mm_search, dim3(nl), wg, 0, s, A);
   hipLaunchKernelGGL(k_mm_link, dim3(nl), wg, 0, s, A);
   hipLaunchKernelGGL(k_mm_fold, dim3(nl), wg, 0, s, A);
   hipLaunchKernelGGL(k_mm_repoint, dim3(nr), wg, 0, s, A);
   hipLaunchKernelGGL(k_mm_finish, dim3(1), dim3(64), 0, s, A);
   return hipGetLastError();
-}
-
-// buckets of the table for a map of `cap` landmarks: the power of two at or above it (load at most 1)
-extern "C" uint32_t fxk_map_merge_table(uint32_t cap) {
-  uint32_t t = 1u;
-  while (t < cap && t < 0x80000000u) t <<= 1;
-  return t;
 }
 
 // bytes of the context's scratch for a map of `cap` landmarks, and the pointers carved out of it

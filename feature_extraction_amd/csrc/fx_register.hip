@@ -13,12 +13,16 @@
 //               in registers and walks the correspondences once — all lanes read the same LDS address, a broadcast —, counting
 //               in an integer; (count, lowest sample) is reduced over the wavefront by shuffles and over the four wavefronts in LDS
 //   refit       thread 0 runs the sequential fp64 sums; the membership tests between them are dealt to all threads
+// The hypothesis, the agreement test and the refit are fx_consensus.h's: fx_map_localize.hip runs the same clauses in fp64.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
+#include "fx_consensus.h"
 #include "fx_device.h"
 #include "../../include/fx.h"
+
+using namespace fxc;
 
 #define FXR_WG 256
 #define FXR_NWAVE (FXR_WG / 64)
@@ -42,68 +46,6 @@ __device__ __forceinline__ KpView kp_view(const uint32_t *block, uint32_t max_sc
   return v;
 }
 
-struct Hyp {
-  float c, s, tx, ty;
-};
-// The transform of the sample (A, B) of (qx, qy, tx, ty) correspondences, fp32 in the header's operation order; false: gated out.
-__device__ __forceinline__ bool hypothesis(float4 A, float4 B, float mb2, float gate, Hyp &h) {
-  const float dqx = B.x - A.x, dqy = B.y - A.y, dtx = B.z - A.z, dty = B.w - A.w;
-  const float lq2 = dqx * dqx + dqy * dqy, lt2 = dtx * dtx + dty * dty;
-  if (!(lq2 >= mb2 && lt2 >= mb2)) return false;
-  if (fabsf(sqrtf(lq2) - sqrtf(lt2)) > gate) return false;
-  const float dot = dqx * dtx + dqy * dty, crs = dqx * dty - dqy * dtx;
-  const float nrm = sqrtf(dot * dot + crs * crs);
-  if (!(nrm > 0.f)) return false;
-  h.c = dot / nrm, h.s = crs / nrm;
-  const float mqx = (A.x + B.x) * 0.5f, mqy = (A.y + B.y) * 0.5f, mtx = (A.z + B.z) * 0.5f, mty = (A.w + B.w) * 0.5f;
-  h.tx = mtx - (h.c * mqx - h.s * mqy);
-  h.ty = mty - (h.s * mqx + h.c * mqy);
-  return true;
-}
-__device__ __forceinline__ bool agrees(const Hyp &h, float4 P, float id2) {
-  const float rx = ((h.c * P.x - h.s * P.y) + h.tx) - P.z, ry = ((h.s * P.x + h.c * P.y) + h.ty) - P.w;
-  return rx * rx + ry * ry <= id2;
-}
-// sample index -> pool ranks (a, b), a < b, lexicographic
-__device__ __forceinline__ void sample_ranks(uint32_t idx, uint32_t H, uint32_t &a, uint32_t &b) {
-  a = 0u;
-  while (idx >= H - 1u - a) idx -= H - 1u - a, ++a;
-  b = a + 1u + idx;
-}
-
-struct Fit {
-  double c, s, tx, ty;
-};
-// squared xy residual of a correspondence under a transform, fp64
-__device__ __forceinline__ double residual2(const Fit &f, float4 P) {
-  const double qx = (double)P.x, qy = (double)P.y;
-  const double rx = ((f.c * qx - f.s * qy) + f.tx) - (double)P.z, ry = ((f.s * qx + f.c * qy) + f.ty) - (double)P.w;
-  return rx * rx + ry * ry;
-}
-// Least-squares rotation about z + translation over the correspondences whose flag word carries `bit`, sequential in their
-// order; f.c / f.s on entry are kept when the centred sums vanish.  n >= 1 members.
-__device__ void fit_set(const float4 *s_xy, const uint32_t *s_flag, uint32_t n_corr, uint32_t bit, uint32_t n, Fit &f) {
-  double sqx = 0.0, sqy = 0.0, stx = 0.0, sty = 0.0;
-  for (uint32_t i = 0; i < n_corr; ++i)
-    if (s_flag[i] & bit) {
-      const float4 P = s_xy[i];
-      sqx += (double)P.x, sqy += (double)P.y, stx += (double)P.z, sty += (double)P.w;
-    }
-  const double dn = (double)n;
-  const double qcx = sqx / dn, qcy = sqy / dn, tcx = stx / dn, tcy = sty / dn;
-  double Sdot = 0.0, Scrs = 0.0;
-  for (uint32_t i = 0; i < n_corr; ++i)
-    if (s_flag[i] & bit) {
-      const float4 P = s_xy[i];
-      const double ux = (double)P.x - qcx, uy = (double)P.y - qcy, vx = (double)P.z - tcx, vy = (double)P.w - tcy;
-      Sdot += (ux * vx + uy * vy);
-      Scrs += (ux * vy - uy * vx);
-    }
-  const double nrm = sqrt(Sdot * Sdot + Scrs * Scrs);
-  if (nrm > 0.0) f.c = Sdot / nrm, f.s = Scrs / nrm;
-  f.tx = tcx - (f.c * qcx - f.s * qcy);
-  f.ty = tcy - (f.s * qcx + f.c * qcy);
-}
 }  // namespace
 
 extern "C" __global__ __launch_bounds__(256) void k_register_init(uint32_t *inlier, uint32_t n) {
@@ -186,7 +128,7 @@ extern "C" __global__ __launch_bounds__(FXR_WG) void k_register(FxRegisterArgs A
   for (uint32_t idx = tid; idx < n_samples; idx += FXR_WG) {
     uint32_t a, b;
     sample_ranks(idx, H, a, b);
-    Hyp h;
+    Hyp<float> h;
     if (!hypothesis(s_xy[s_pool[a]], s_xy[s_pool[b]], mb2, gate, h)) continue;
     uint32_t count = 0u;
     for (uint32_t i = 0; i < n_corr; ++i) count += agrees(h, s_xy[i], id2) ? 1u : 0u;
@@ -216,7 +158,7 @@ extern "C" __global__ __launch_bounds__(FXR_WG) void k_register(FxRegisterArgs A
   uint32_t wa, wb;
   sample_ranks(((1u << FXR_IDX_BITS) - 1u) - (best & ((1u << FXR_IDX_BITS) - 1u)), H, wa, wb);
   const uint32_t n0 = best >> FXR_IDX_BITS;
-  Hyp h0;
+  Hyp<float> h0;
   (void)hypothesis(s_xy[s_pool[wa]], s_xy[s_pool[wb]], mb2, gate, h0);
   for (uint32_t i = tid; i < n_corr; i += FXR_WG) s_d2[i] = agrees(h0, s_xy[i], id2) ? 1u : 0u;
   __syncthreads();

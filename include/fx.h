@@ -622,7 +622,8 @@ fx_status fx_track_landmarks(fx_ctx *ctx,
  * only, or and sum), every fp64 value an ordered chain of correctly rounded operations on one lane.
  * Limits: tracks are continued only across an accepted one-scan overlap; a pole seen again after a missed detection, a bad link or
  * after leaving the field of view enters as a new landmark.  fx_map_merge (below) folds such fragments back into one landmark
- * within a segment; across segments and after long drift they stay apart (no loop closure).  The equality with one batch of the whole run
+ * within a segment; across segments and after long drift they stay apart (no loop closure: fx_map_localize gives the pose of a scan
+ * against the map, which closing one would start from).  The equality with one batch of the whole run
  * holds for min_obs == 2; with a larger min_obs a track that a batch edge cuts into pieces that are each too short is missed.
  * n_obs and n_needed are 32-bit counts.
  * fx_map_create allocates all of the map's buffers and enqueues its first reset; fx_map_reset enqueues the state of a fresh map;
@@ -697,7 +698,8 @@ fx_status fx_map_read_landmarks(fx_ctx *ctx, fx_map *map, uint32_t first, uint32
  * FX_ERR_INVALID_ARG with the reason in fx_last_error(), nothing launched, the map unchanged: a NULL ctx or map (fx_map_get_alias:
  * a NULL out pointer), a map of another context, merge_dist not finite and positive, max_gap_scans == 0, result_device not 4-byte
  * aligned; fx_map_read_alias: entries outside max_landmarks.
- * Limits: merging happens within one segment only (no loop closure).  Chained merges of one call may join A and C that are up to
+ * Limits: merging happens within one segment only (no loop closure; fx_map_localize, below, gives the transform between a scan's
+ * frame and the map's, it joins nothing).  Chained merges of one call may join A and C that are up to
  * 2 merge_dist apart, through B.  The map_id_of_row arrays of earlier batches keep the absorbed ids: resolve them through the
  * alias table (id = alias[id] >= 0 ? alias[id] : id).  A cell of the grid that holds very many fragments is searched by one lane
  * a landmark: time, not the result, grows with the square of a cell's population.
@@ -715,6 +717,90 @@ fx_status fx_map_merge(fx_ctx *ctx, fx_map *map, const fx_map_merge_options *opt
                        fx_map_merge_result *result_device /* or NULL */);
 fx_status fx_map_get_alias(fx_map *map, const int32_t **alias_device);            /* [max_landmarks], stable for the map's life */
 fx_status fx_map_read_alias(fx_ctx *ctx, fx_map *map, uint32_t first, uint32_t count, int32_t *out_host);
+
+/* ---- Localising scans against the map: relocalisation with a prior pose ----
+ * Everything above places a scan in the map's frame by dead reckoning: the track folds pairwise motions and the map continues that
+ * fold.  fx_map_localize compares scans with the map itself: given the scans of a keypoint block, a PRIOR pose for each and a
+ * map, it finds which landmark each keypoint is and fits each scan's pose in the map's frame.  It is what joining the segments a
+ * bad link leaves, bounding drift and "map once, localise later" all start from.  It is enqueued on the context's stream (no
+ * host synchronisation, no allocation in the steady state: its scratch is a context-owned buffer sized by the map's
+ * max_landmarks and by q_max_rows, shared with fx_map_merge) and READS the map only: header, records, sums, alias and carry are bit
+ * for bit what they were.  Call it after a track (prior_poses_device = the track's poses_device) or alone against a finished map.
+ * Sizes: S = min(n_scans, the block's scans, max_scans) and rows = min(the block's keypoints stored, max_total_keypoints,
+ * q_max_rows), scan(r) and the non-rows exactly as in fx_track_landmarks.  All n_scans records and all q_max_rows words of both
+ * row arrays are written and nothing beyond them.  A scan b >= S gets FX_LOC_NO_SCAN and nothing else: the prior as its pose, D =
+ * the identity (dc = 1, ds = dtx = dty = dtz = 0), rms = +inf, n_corr = n_inliers = 0, hyp_a = hyp_b = 0xffffffff.  A scan b < S
+ * whose prior's c, s, tx, ty or tz is not finite gets FX_LOC_BAD_PRIOR and the same record.  Non-rows and the rows of such scans
+ * get -1 in both row arrays.
+ * Eligible landmarks: with N = header.n_landmarks as it is when the call runs, g < N is eligible iff alias[g] == -1, n_obs >=
+ * min_landmark_obs, its x, y and z are finite and its segment passes opt.segment: FX_LOC_ANY_SEGMENT passes every segment,
+ * FX_LOC_LAST_SEGMENT stands for header.segments - 1 read on the device (nothing is eligible in a map of no segment), any other
+ * value is the global segment number itself.
+ * Association, per row r of scan b whose x, y and z are finite: (wx, wy, wz) is the row under the prior, fx_track_landmarks's
+ * fusing clause word for word (the same device function).  dx = x[g] - wx, dy = y[g] - wy, d2 = dx dx + dy dy in fp64, no
+ * contraction; g is in reach iff d2 <= sd sd, sd = (double)search_dist.  nearest_of_row[r] is the eligible g in reach of lowest
+ * (d2 as uint64 bits, id), -1 when there is none or the row is not finite.  Several rows may pick the same landmark.
+ * Correspondences of scan b: its rows with nearest >= 0, in ascending row; the first FX_LOC_MAX_CORR are used (FX_LOC_TRUNCATED
+ * when there are more); n_corr is the number used.  Correspondence i carries q = (wx, wy, wz) and t = (x, y, z) of its landmark,
+ * all double.
+ * Hypothesis stage: fx_register_matches's clause word for word with every operation in fp64 (map coordinates are not small): the
+ * pool is the H = min(n_corr, hyp_corr) correspondences of lowest (d2 bits, row); the samples (a, b), a < b, in lexicographic
+ * order; the gates, c, s, the midpoints, tx, ty and the agreement test are the same expressions in the same order, with mb mb
+ * and inlier_dist inlier_dist the double products of the floats widened and 2 inlier_dist the double product 2.0 (double)
+ * inlier_dist.  The winner has the most agreeing correspondences among all n_corr, ties to the lowest (a, b); a sample with fewer
+ * than 2 agreeing is no hypothesis.  Without one the scan gets FX_LOC_NO_HYPOTHESIS, D = the identity, rms = +inf, n_inliers = 0
+ * and the prior as its pose.  numpy float64 reproduces the stage bit for bit.
+ * Refit: fx_register_matches's clause word for word (the same device code): the fit over the agreeing set, the re-test of all
+ * n_corr giving I1, the second fit when I1 has at least 2 members.  (dc, ds, dtx, dty) is the final transform, dtz the sequential
+ * mean of t_z - q_z over the final set, rms and n_inliers as in the register; hyp_a, hyp_b the rows of the winning sample.
+ * Pose: FX_LOC_VALID iff n_inliers >= min_inliers.  The pose is then the track's good-link composition of D with the prior p:
+ * c = dc pc - ds ps, s = ds pc + dc ps, tx = (dc ptx - ds pty) + dtx, ty = (ds ptx + dc pty) + dty, tz = ptz + dtz.  Otherwise
+ * it is the prior's five doubles, bit for bit; D is reported all the same.  segment and flags of the pose are the prior's.
+ * map_id_of_row[r]: the landmark of row r when r is in its scan's final inlier set, else -1.
+ * One call is one round: the output poses are fx_pose records, so a second round takes them as its priors (with a smaller
+ * search_dist).  A search distance of 2 m bounds the prior's error after one bad link; the association is right only where that
+ * error is below half the local pole spacing, and the consensus takes care of the rest.
+ * FX_ERR_INVALID_ARG with the reason in fx_last_error(), nothing launched, no output byte touched: a NULL required pointer (the
+ * row arrays may be NULL only with q_max_rows == 0, nearest_of_row_device always), a map of another context, n_scans == 0 or
+ * n_scans > max_scans, search_dist, inlier_dist or min_baseline not finite and positive, hyp_corr outside 2..128, min_inliers < 2,
+ * min_landmark_obs == 0, reserved != 0, a keypoint block not 16-byte or records not 8-byte (words: 4-byte) aligned.
+ * The same bytes from run to run and with any number of contexts in flight: every decision is an integer or a minimum over a
+ * total order, every fp64 sum an ordered chain on one lane.  The search structure (fx_map_merge's hashed grid, cell edge
+ * sd (1 + 2^-8)) never shows in the result.
+ * Limits: a prior is needed (the map stores no descriptors: no global relocalisation); the call joins no segments and
+ * re-estimates no landmark: it produces the poses and the row-to-landmark table both would start from.  A cell of the grid that
+ * holds very many landmarks is walked by one lane a row.  New in 0.7 (added symbols only). */
+#define FX_LOC_MAX_CORR 1024u
+#define FX_LOC_ANY_SEGMENT  0xffffffffu
+#define FX_LOC_LAST_SEGMENT 0xfffffffeu   /* header.segments - 1, read on the device; nothing is eligible in a map of no segment */
+typedef struct fx_localize_options {
+  float search_dist;      /* xy gate of the association under the prior, m; finite, > 0; default 2.0 */
+  float inlier_dist;      /* as fx_register_options; default 0.30 */
+  float min_baseline;     /* as fx_register_options; default 2.0 */
+  uint32_t hyp_corr;      /* 2..128, default 64 */
+  uint32_t min_inliers;   /* >= 2, default 3 */
+  uint32_t min_landmark_obs; /* a landmark takes part with at least this many observations; >= 1, default 2 */
+  uint32_t segment;       /* only landmarks of this global segment take part; default FX_LOC_LAST_SEGMENT */
+  uint32_t reserved;      /* 0 */
+} fx_localize_options;
+#define FX_LOC_VALID 0x1u         /* a correction was fitted to >= min_inliers correspondences: pose = D o prior */
+#define FX_LOC_TRUNCATED 0x2u     /* more than FX_LOC_MAX_CORR correspondences: the first 1024 in row order were used */
+#define FX_LOC_NO_HYPOTHESIS 0x4u /* fewer than 2 correspondences, or no sample passed the gates */
+#define FX_LOC_BAD_PRIOR 0x8u     /* the prior's c, s, tx, ty or tz is not finite */
+#define FX_LOC_NO_SCAN 0x10u      /* b is beyond the block's scans */
+typedef struct fx_localization {   /* 112 B, one per scan */
+  fx_pose pose;                    /* VALID: D o prior; otherwise the prior, bit for bit.  segment, flags: the prior's */
+  double dc, ds, dtx, dty, dtz;    /* D: the correction in the map frame */
+  float rms;
+  uint32_t n_corr, n_inliers, flags;
+  uint32_t hyp_a, hyp_b;           /* rows of the winning sample, 0xffffffff: none */
+} fx_localization;
+void fx_localize_options_default(fx_localize_options *o);
+fx_status fx_map_localize(fx_ctx *ctx, fx_map *map,
+    const void *kp_block_device, uint32_t max_scans, uint32_t max_total_keypoints,
+    const fx_pose *prior_poses_device, uint32_t n_scans, uint32_t q_max_rows, const fx_localize_options *opt /* NULL: defaults */,
+    fx_localization *out_device /* [n_scans] */, int32_t *map_id_of_row_device /* [q_max_rows] */,
+    int32_t *nearest_of_row_device /* [q_max_rows] or NULL */);
 
 /* Rotation matrix of rotateCloud (ref: node.cpp:161-164): R = Ry(pitch)*Rx(roll)
  * through Eigen's AngleAxisf -> Quaternionf -> toRotationMatrix, all float. Host only. */

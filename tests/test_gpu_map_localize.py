@@ -1,0 +1,326 @@
+"""fx_map_localize on the GPU.  Every call of every case is compared with capi.map_localize_reference — an all-pairs statement of
+include/fx.h's definition in numpy float64 that knows nothing of the grid — bit for bit: every record field (integers equal, the
+doubles and rms as bit patterns) and both row arrays whole.  The guard words behind the three outputs must be untouched, and so
+must the map."""
+import ctypes as C
+import threading
+
+import numpy as np
+import pytest
+
+from feature_extraction_amd import capi
+from tests import map_localize_util as lu
+from tests import map_merge_util as mm
+from tests import track_util as tu
+from tests.test_gpu_map import _run
+from tests.test_gpu_map_merge import _merge_to_fixpoint, _one_batch
+from tests.test_gpu_track import FILL, GUARD
+
+pytestmark = pytest.mark.gpu
+REC_WORDS = capi.LOC_DTYPE.itemsize // 4
+F32 = lu.F32
+ANY = capi.FX_LOC_ANY_SEGMENT
+E2 = 2.0 * (1.0 + 2.0 ** -8)  # the grid's cell edge at the default search distance
+
+
+@pytest.fixture
+def ctx(fxlib):
+    c = capi.Context(capi.params("launch"), capi.limits(2, 1024))  # (no batch is ever processed on it)
+    yield c
+    c.close()
+
+
+def _map_bytes(mp):
+    return repr(sorted(mp.header().items())).encode() + mp.landmarks().tobytes() + mp.alias().tobytes()
+
+
+def _device(ctx, off, rows, priors, max_scans, max_total, stored=None):
+    import torch
+    dev = f"cuda:{ctx.device}"
+    blk = tu.block(off, rows, max_scans, max_total, stored)
+    return (torch.from_numpy(blk).to(dev), max_scans, max_total), torch.from_numpy(np.ascontiguousarray(priors).view(np.float64).reshape(-1, 6).copy()).to(dev)
+
+
+def _call(ctx, mp, kp, pri, n_scans, q, nearest=True, **opts):
+    """Map.localize into guarded outputs.  Returns {"rec", "map_id_of_row", "nearest_of_row" (None without the array)}."""
+    import torch
+    dev = f"cuda:{ctx.device}"
+    raw = [torch.full((n + GUARD,), FILL, dtype=torch.int32, device=dev) for n in (n_scans * REC_WORDS, q, q)]
+    mp.localize(kp, pri, n_scans, q_max_rows=q, out=(raw[0][:n_scans * REC_WORDS], raw[1][:q]), nearest=raw[2][:q] if nearest else False, **opts)
+    ctx.synchronize()
+    for r, n, name in zip(raw, (n_scans * REC_WORDS, q, q if nearest else 0), ("the records", "map_id_of_row", "nearest_of_row")):
+        assert (r[n:] == FILL).all().item(), f"the guard behind {name}"
+    return {"rec": capi.localize_records(raw[0][:n_scans * REC_WORDS]), "map_id_of_row": raw[1][:q].cpu().numpy(),
+            "nearest_of_row": raw[2][:q].cpu().numpy() if nearest else None}
+
+
+def _localize(ctx, mp, st, off, rows, priors, what, n_scans=None, max_scans=None, max_total=None, q_max_rows=None, stored=None, nearest=True, **opts):
+    """One fx_map_localize against one map_localize_reference call; the map must come out as it went in."""
+    n_scans = len(off) - 1 if n_scans is None else n_scans
+    max_scans = max(len(off) - 1, n_scans) + 2 if max_scans is None else max_scans
+    max_total = len(rows) + 9 if max_total is None else max_total
+    q = len(rows) if q_max_rows is None else q_max_rows
+    kp, pri = _device(ctx, off, rows, priors, max_scans, max_total, stored)
+    before = _map_bytes(mp)
+    got = _call(ctx, mp, kp, pri, n_scans, q, nearest, **opts)
+    assert _map_bytes(mp) == before, f"{what}: the map is read, never written"
+    ref = capi.map_localize_reference(st, off[:min(len(off) - 1, max_scans) + 1], rows[:len(rows) if stored is None else stored], priors, n_scans, q_max_rows=q, **opts)
+    lu.assert_equal(got, ref, what)
+    lu.assert_prior_kept(got["rec"], priors, what)
+    return got, ref
+
+
+# ---- (a) the worlds of the reference's tests through the device chain
+def test_a1_clean_world_all_scans_in_one_call(ctx):
+    w, pieces = lu.clean_world(0, 0.01)
+    W = lu.WORLD
+    mp = ctx.map_create(W["cap"], W["carry"])
+    st, _, _, _ = _run(ctx, pieces, "(a1)", W["cap"], W["carry"], mp=mp)
+    priors = lu.poses_of(w["truth"], seed=1000)
+    got, ref = _localize(ctx, mp, st, w["off"], w["rows"], priors, "(a1)")
+    assert (got["rec"]["flags"] == capi.FX_LOC_VALID).all()
+    second, _ = _localize(ctx, mp, st, w["off"], w["rows"], got["rec"]["pose"], "(a1) second round", search_dist=0.5)
+    print("(a1)", lu.pose_errors(got["rec"]["pose"], w["truth"]), lu.pose_errors(second["rec"]["pose"], w["truth"]))
+    mp.close()
+
+
+def test_a2_flicker_world_after_a_merge(ctx):
+    w, pieces, _ = mm.flicker()
+    f = mm.FLICKER
+    mp = ctx.map_create(f["cap"], f["carry"])
+    st, _, _, _ = _run(ctx, pieces, "(a2)", f["cap"], f["carry"], mp=mp)
+    priors = lu.poses_of(w["truth"], seed=1072)
+    _localize(ctx, mp, st, w["off"], w["rows"], priors, "(a2) before the merge")
+    st, results = _merge_to_fixpoint(ctx, mp, st, "(a2)", max_gap_scans=24)
+    assert sum(r["merged"] for r in results) > 0
+    got, _ = _localize(ctx, mp, st, w["off"], w["rows"], priors, "(a2) after the merge")
+    alias = mp.alias()
+    assert (got["rec"]["flags"] & capi.FX_LOC_VALID).all() and (alias[got["nearest_of_row"][got["nearest_of_row"] >= 0]] == -1).all()
+    _localize(ctx, mp, st, w["off"], w["rows"], priors, "(a2) min_landmark_obs 5", min_landmark_obs=5, segment=0)
+    mp.close()
+
+
+# ---- (b) correspondence counts at the pool's, the workgroup's and the capacity's edges
+COUNTS = [0, 1, 2, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025]
+BIG = lu.lattice(1100, pitch=3.0)
+
+
+@pytest.fixture(scope="module")
+def big_map(fxlib):
+    c = capi.Context(capi.params("launch"), capi.limits(2, 1024))
+    mp, st = _one_batch(c, mm.fragments(BIG, 3), "(b) the map of 1100", cap=1100, carry=8)
+    assert st["header"]["n_landmarks"] == 1100
+    yield c, mp, st
+    mp.close(), c.close()
+
+
+def _counted_scans(rng):
+    """A scan per entry of COUNTS: that many rows 0.1 m (+ up to 2 cm of scatter) off landmarks chosen at random, and three strays."""
+    out = []
+    for n in COUNTS:
+        pick = rng.permutation(len(BIG))[:n]
+        rows = [(F32(BIG[k][1] + 0.1 + rng.uniform(-0.02, 0.02)), F32(BIG[k][2] - 0.05 + rng.uniform(-0.02, 0.02)), F32(rng.uniform(0, 2))) for k in pick]
+        rows += [(F32(rng.uniform(-900, -800)), F32(rng.uniform(0, 100)), 0.0) for _ in range(3)]
+        out.append([rows[i] for i in rng.permutation(len(rows))])
+    return out
+
+
+def test_b_correspondence_counts_at_every_edge(big_map):
+    c, mp, st = big_map
+    off, rows = lu.scans(_counted_scans(np.random.default_rng(81)))
+    priors = lu.identity(len(COUNTS), tz=0.5)
+    got, ref = _localize(c, mp, st, off, rows, priors, "(b) counts")
+    assert got["rec"]["n_corr"].tolist() == [min(n, 1024) for n in COUNTS]
+    assert [bool(f & capi.FX_LOC_TRUNCATED) for f in got["rec"]["flags"]] == [n > 1024 for n in COUNTS]
+    assert [bool(f & capi.FX_LOC_VALID) for f in got["rec"]["flags"]] == [n >= 3 for n in COUNTS]
+    _localize(c, mp, st, off, rows, priors, "(b) counts, pool of 128", hyp_corr=128, min_inliers=2)
+
+
+def test_b_a_block_of_max_scans_empty_scans_and_row_arrays_of_other_lengths(big_map):
+    c, mp, st = big_map
+    rng = np.random.default_rng(82)
+    some = _counted_scans(rng)[3:6]
+    by_scan = [some[0], [], some[1], [], [], some[2], []]
+    off, rows = lu.scans(by_scan)
+    n = len(by_scan)
+    priors = lu.identity(n + 2, ty=0.25)
+    _localize(c, mp, st, off, rows, priors, "(b) max_scans scans", n_scans=n, max_scans=n, max_total=len(rows))
+    _localize(c, mp, st, off, rows, priors, "(b) scans beyond the block", n_scans=n + 2, max_scans=n + 2)
+    _localize(c, mp, st, off, rows, priors, "(b) fewer scans than the block", n_scans=3)
+    for q in (len(rows) - 70, len(rows) - 1, len(rows) + 1, len(rows) + 300):
+        _localize(c, mp, st, off, rows, priors, f"(b) q_max_rows {q}", q_max_rows=q)
+    _localize(c, mp, st, off, rows, priors, "(b) a block that stores fewer rows", stored=len(rows) - 40)
+    got, _ = _localize(c, mp, st, off, rows[:0], priors, "(b) no rows at all", q_max_rows=0, max_total=4, stored=0, n_scans=2)
+    assert (got["rec"]["flags"] == capi.FX_LOC_NO_HYPOTHESIS).all()
+
+
+# ---- (c) the grid
+def _hand(ctx, frags, rows_by_scan, what, priors=None, n_scans_map=3, bad=(), cap=None, merge=False, **opts):
+    mp, st = _one_batch(ctx, mm.fragments(frags, n_scans_map, bad), what, cap=cap, carry=8)
+    if merge:
+        st, _ = _merge_to_fixpoint(ctx, mp, st, what)
+    off, rows = lu.scans(rows_by_scan)
+    priors = lu.identity(len(rows_by_scan)) if priors is None else priors
+    got, ref = _localize(ctx, mp, st, off, rows, priors, what, **opts)
+    mp.close()
+    return got
+
+
+def test_c_cell_borders_negative_and_large_coordinates_and_the_far_list(ctx):
+    frags, rows, want = [], [], []
+
+    def pair(lx, ly, rx, ry, hit=True):
+        want.append(len(frags) if hit else -1)
+        frags.append((0, F32(lx), F32(ly))), rows.append((F32(rx), F32(ry), 1.0))
+    for k in (7, -7, 0):  # borders at positive and negative coordinates and across 0 (floor, not truncation)
+        b = k * E2
+        pair(b - 0.9, 50.0 + 9 * k, b + 0.9, 50.0 + 9 * k)                      # in x
+        pair(160.0 + 9 * k, b - 0.9, 160.0 + 9 * k, b + 0.9)                    # in y
+        pair(b - 0.6, b - 30.0 * E2 - 0.6, b + 0.6, b - 30.0 * E2 + 0.6)        # diagonally
+        pair(b - 1.1, 270.0 + 9 * k, b + 1.1, 270.0 + 9 * k, hit=False)         # one cell apart and beyond the gate
+    pair(1e6, 1e6, 1e6 + 1.5, 1e6)                  # float32 steps of 1 / 16 m
+    pair(-1e6, 1e6, -1e6, 1e6 + 2.0625, hit=False)
+    pair(1e13, -1e13, 1e13, -1e13)                  # beyond 2^39 cells: the far list
+    pair(1e13, 2e13, 1e13, 2e13)
+    pair(1e30, 1e30, 1e30, 1e30)                    # beyond any cell number
+    pair(3e38, 3e38, -3e38, 3e38, hit=False)        # the ends of float32's range: d2 overflows
+    got = _hand(ctx, frags, [rows, rows[::-1]], "(c) borders", min_baseline=0.5)
+    assert got["nearest_of_row"].tolist() == want + want[::-1]
+
+
+def test_c_three_hundred_landmarks_in_one_cell(ctx):
+    """300 landmarks uniform in a box of 0.8 m (inside one cell of 2 m, or across one border), 160 rows uniform in the same box
+    and 40 around it.  The comparison with the reference is the test; the count only says that the case is not degenerate: the
+    nearest landmark of a uniform point is close to a uniform draw of the 300, and 160 such draws hit 300 (1 - exp(-160 / 300)) =
+    124 different ones on average (the reference gives 121), so fewer than 80 would mean rows that see the box from outside."""
+    rng = np.random.default_rng(83)
+    box = lambda h: (F32(12.3 + rng.uniform(-h, h)), F32(-45.6 + rng.uniform(-h, h)))
+    frags = [(0,) + box(0.4) for _ in range(300)] + lu.lattice(9, pitch=7.0)
+    rows = [box(0.4) + (1.0,) for _ in range(160)] + [box(1.5) + (1.0,) for _ in range(40)] + lu.rows_at(frags, range(300, 309), 0.05)
+    got = _hand(ctx, frags, [rows], "(c) 300 in a cell")
+    assert len(set(got["nearest_of_row"][:160].tolist())) >= 80 and (got["nearest_of_row"] >= 0).all()
+
+
+@pytest.mark.parametrize("spread", [37.0, 0.75])
+def test_c_a_map_of_eight_small_table_and_collisions(ctx, spread):
+    frags = [(0, F32(spread * k - 100.0), F32(-1.4 * spread * k + 90.0)) for k in range(8)]
+    rows = lu.rows_at(frags, range(8), 0.2, -0.1) + [(F32(spread * 3.5 - 100.0), F32(-1.4 * spread * 3.5 + 90.0), 1.0)]
+    got = _hand(ctx, frags, [rows, rows[:4]], f"(c) map of 8, {spread}", cap=8)
+    assert got["nearest_of_row"][:8].tolist() == list(range(8))
+
+
+def test_c_gate_edge_tie_and_the_filters_of_the_walk(ctx):
+    up = float(np.nextafter(0.5, 1.0))
+    pri = lu.identity(5)
+    pri["tx"] = (0.5, up, -0.5, -up, 0.0)
+    got = _hand(ctx, [(0, 0.0, 0.0), (0, 50.0, 0.0)], [[(0.0, 0.0, 1.0)]] * 5, "(c) d2 == sd sd", priors=pri, search_dist=0.5)
+    assert got["nearest_of_row"].tolist() == [0, -1, 0, -1, 0]
+    got = _hand(ctx, [(0, 0.0, 0.0), (0, 1.0, 0.0), (0, 0.0, 8.0)], [[(0.5, 0.0, 1.0), (0.5625, 0.0, 1.0), (0.0, 4.0, 1.0)]], "(c) the tie", search_dist=4.0)
+    assert got["nearest_of_row"].tolist() == [0, 1, 0]
+    frags = [(0, 10.0, 10.0), (0, 20.0, 10.0), (3, F32(10.125), 10.0), (6, 30.0, 10.0), (6, 20.0, 20.0)]
+    rows = [[(frags[k][1], frags[k][2], 1.0) for k in (2, 1, 3, 4)]]
+    for opts, want in ((dict(segment=ANY), [0, 1, 3, 4]), (dict(segment=ANY, search_dist=0.05), [-1, 1, 3, 4]), (dict(segment=ANY, min_landmark_obs=3), [0, -1, -1, -1]),
+                       ({}, [-1, -1, 3, 4]), (dict(segment=0), [0, 1, -1, -1]), (dict(segment=2), [-1] * 4)):
+        got = _hand(ctx, frags, rows, f"(c) filters {opts}", n_scans_map=8, bad=(4,), merge=True, **opts)
+        assert got["nearest_of_row"].tolist() == want, opts
+
+
+def test_c_bad_priors_bad_rows_and_an_empty_map(ctx):
+    LAT = lu.lattice(16)
+    scan = lu.rows_at(LAT, [0, 1, 2, 5, 6, 9], 0.1)
+    bad_rows = list(scan)
+    bad_rows[1], bad_rows[2] = (np.nan, scan[1][1], 1.0), (scan[2][0], scan[2][1], np.inf)
+    pri = lu.identity(7)
+    for b, f in enumerate(("c", "s", "tx", "ty", "tz")):
+        pri[f][b] = np.nan if b % 2 else -np.inf
+    pri["segment"], pri["flags"] = np.arange(7) + 3, capi.FX_POSE_GAP
+    got = _hand(ctx, LAT, [scan] * 5 + [bad_rows], "(c) bad priors", priors=pri, n_scans=7)
+    assert got["rec"]["flags"].tolist() == [capi.FX_LOC_BAD_PRIOR] * 5 + [capi.FX_LOC_VALID, capi.FX_LOC_NO_SCAN]
+    mp = ctx.map_create(8, 8)
+    off, rows = lu.scans([scan])
+    for seg in (capi.FX_LOC_LAST_SEGMENT, ANY, 0):
+        got, _ = _localize(ctx, mp, capi.map_state(8, 8), off, rows, lu.identity(1), f"(c) an empty map, segment {seg:#x}", segment=seg)
+        assert got["rec"]["flags"].tolist() == [capi.FX_LOC_NO_HYPOTHESIS] and (got["nearest_of_row"] == -1).all()
+    mp.close()
+
+
+# ---- (d) refusals
+def test_d_host_refusals_touch_no_output_byte(ctx, fxlib):
+    import torch
+    LAT = lu.lattice(16)
+    mp, st = _one_batch(ctx, mm.fragments(LAT, 3), "(d)")
+    other = capi.Context(capi.params("launch"), capi.limits(2, 1024))
+    theirs = other.map_create(8, 8)
+    off, rows = lu.scans([lu.rows_at(LAT, [0, 1, 2, 5], 0.1)])
+    (kb, S, T), pri = _device(ctx, off, rows, lu.identity(1), 4, 16)
+    dev = f"cuda:{ctx.device}"
+    out, ids, near = (torch.full((n,), FILL, dtype=torch.int32, device=dev) for n in (REC_WORDS + 2, 6, 6))
+    before = _map_bytes(mp)
+    O = capi.FxLocalizeOptions
+    ok = dict(search_dist=2.0, inlier_dist=0.3, min_baseline=2.0, hyp_corr=64, min_inliers=3, min_landmark_obs=2, segment=ANY, reserved=0)
+    opt = lambda **kw: C.byref(O(**dict(ok, **kw)))
+    good = dict(c=ctx.handle, m=mp.handle, kp=kb.data_ptr(), S=S, T=T, pri=pri.data_ptr(), n=1, q=4, opt=opt(), out=out.data_ptr(), ids=ids.data_ptr(),
+                near=near.data_ptr())
+    cases = [(dict(c=None), b"null"), (dict(m=None), b"null"), (dict(kp=None), b"null"), (dict(pri=None), b"null"), (dict(out=None), b"null"),
+             (dict(ids=None), b"null"), (dict(m=theirs.handle), b"another context"), (dict(c=other.handle), b"another context"),
+             (dict(n=0), b"n_scans"), (dict(n=S + 1), b"n_scans"), (dict(kp=kb.data_ptr() + 4), b"aligned"), (dict(pri=pri.data_ptr() + 4), b"aligned"),
+             (dict(out=out.data_ptr() + 4), b"aligned"), (dict(ids=ids.data_ptr() + 2), b"aligned"), (dict(near=near.data_ptr() + 2), b"aligned")]
+    for f in ("search_dist", "inlier_dist", "min_baseline"):
+        cases += [(dict(opt=opt(**{f: v})), f.encode()) for v in (0.0, -1.0, float("nan"), float("inf"))]
+    cases += [(dict(opt=opt(hyp_corr=1)), b"hyp_corr"), (dict(opt=opt(hyp_corr=129)), b"hyp_corr"), (dict(opt=opt(min_inliers=1)), b"min_inliers"),
+              (dict(opt=opt(min_landmark_obs=0)), b"min_landmark_obs"), (dict(opt=opt(reserved=1)), b"reserved")]
+    for change, word in cases:
+        a = dict(good, **change)
+        status = fxlib.fx_map_localize(a["c"], a["m"], a["kp"], a["S"], a["T"], a["pri"], a["n"], a["q"], a["opt"], a["out"], a["ids"], a["near"])
+        assert status == 1 and word in fxlib.fx_last_error(), (change, word, fxlib.fx_last_error())
+    ctx.synchronize()
+    assert all((t == FILL).all().item() for t in (out, ids, near)) and _map_bytes(mp) == before
+    # opt == NULL: the defaults; the row arrays may be NULL with q_max_rows == 0
+    a = good
+    assert fxlib.fx_map_localize(a["c"], a["m"], a["kp"], a["S"], a["T"], a["pri"], 1, 0, None, a["out"], None, None) == capi.FX_OK
+    assert fxlib.fx_map_localize(a["c"], a["m"], a["kp"], a["S"], a["T"], a["pri"], 1, 4, None, a["out"], a["ids"], a["near"]) == capi.FX_OK
+    ctx.synchronize()
+    ref = capi.map_localize_reference(st, off, rows, lu.identity(1), 1)
+    got = {"rec": capi.localize_records(out[:REC_WORDS]), "map_id_of_row": ids[:4].cpu().numpy(), "nearest_of_row": near[:4].cpu().numpy()}
+    lu.assert_equal(got, ref, "(d) defaults")
+    assert (out[REC_WORDS:] == FILL).all().item() and (ids[4:] == FILL).all().item() and (near[4:] == FILL).all().item()
+    theirs.close(), other.close(), mp.close()
+
+
+# ---- (e), (f) the same bytes from run to run, across contexts, with and without the optional array
+def test_e_f_identical_bytes_across_runs_contexts_and_without_nearest(ctx):
+    w, pieces, _ = mm.flicker()
+    f = mm.FLICKER
+    priors = lu.poses_of(w["truth"], seed=1072)
+
+    def once(c, nearest=True, repeat=1):
+        mp = c.map_create(f["cap"], f["carry"])
+        _run(c, pieces, "(e)", f["cap"], f["carry"], mp=mp)
+        mp.merge(max_gap_scans=24, result=False)
+        kp, pri = _device(c, w["off"], w["rows"], priors, 26, len(w["rows"]) + 9)
+        outs = []
+        for _ in range(repeat):
+            got = _call(c, mp, kp, pri, 24, len(w["rows"]), nearest, segment=ANY)
+            outs.append(got["rec"].tobytes() + got["map_id_of_row"].tobytes() + (got["nearest_of_row"].tobytes() if nearest else b""))
+        mp.close()
+        assert len(set(outs)) == 1, "the same bytes twice"
+        return outs[0]
+    first = once(ctx, repeat=2)
+    without = once(ctx, nearest=False)
+    assert first[:len(without)] == without, "(f) without nearest_of_row the other outputs are the same bytes"
+    res, errs = {}, []
+
+    def run(i):
+        try:
+            c = capi.Context(capi.params("launch"), capi.limits(2, 1024))
+            c.set_batches_in_flight(4)
+            res[i] = once(c, repeat=3)
+            c.close()
+        except Exception as e:  # (reported below)
+            errs.append(e)
+    ths = [threading.Thread(target=run, args=(i,)) for i in range(3)]
+    [x.start() for x in ths]
+    mine = once(ctx, repeat=3)  # (this context works while the others are busy on the device)
+    [x.join() for x in ths]
+    assert not errs, errs
+    assert mine == first and all(res[i] == first for i in range(3))
