@@ -707,7 +707,8 @@ def register_reference(q_kp_rows, t_kp_rows, match_records, pairs, inlier_dist=0
     idist, mb = f32(inlier_dist), f32(min_baseline)
     if not (np.isfinite(idist) and idist > 0 and np.isfinite(mb) and mb > 0 and 2 <= hyp_corr <= 128 and min_inliers >= 2):
         raise ValueError("options outside what fx_register_matches accepts")
-    mb2, gate, id2 = mb * mb, f32(2) * idist, idist * idist
+    with np.errstate(all="ignore"):  # (a min_baseline whose square leaves float32's range: 0 or +inf, as on the device)
+        mb2, gate, id2 = mb * mb, f32(2) * idist, idist * idist
     id2d = float(idist) * float(idist)
     seen = np.zeros(n_rows, bool)
     for p, (q0, qn, _t0, _tn) in enumerate(pairs):

@@ -445,6 +445,22 @@ fx_status fx_match_descriptors_csr(fx_ctx *ctx, const void *q_block_device, uint
  *   ry = ((s qx + c qy) + ty) - t_y.
  * The winner is the sample with the most agreeing correspondences among all n_corr, ties to the lowest (a, b); a sample with
  * fewer than 2 agreeing is no hypothesis.  numpy float32 reproduces this stage bit for bit; counts and the winner are integers.
+ * Scale: multiplying every coordinate, inlier_dist and min_baseline by 2^k multiplies every intermediate of the stage by a power
+ * of two, so the integers and the bits of c and s stay and tx, ty scale exactly — but only while no intermediate leaves fp32's
+ * normal range.  The widest is the operand of nrm's root: dot dot + crs crs = |dq|^2 |dt|^2 in exact arithmetic, the fourth
+ * power of the sample's baseline b = sqrt(|dq| |dt|).  It is normal for 2^-126 <= b^4 < 2^128, that is 2^-31.5 m <= b < 2^32 m
+ * (6.7e-10 m .. 4.3e9 m).  Outside:
+ *   2^-37.25 m <= b < 2^-31.5 m   the sum is subnormal and has lost bits: the sample stands, c and s no longer scale exactly;
+ *   b < 2^-37.25 m (b^4 < 2^-149) the sum rounds to 0, nrm = 0 and the sample is skipped by nrm > 0, distinct keypoints or not;
+ *   b >= 2^32 m                   the sum is +inf and so is nrm: c = s = 0 while dot and crs are finite (the transform sends every
+ *                                 keypoint to the sample's train midpoint, which is half a train baseline from its own two
+ *                                 keypoints: it gathers no agreement from them), NaN once dot or crs overflow as well (b >= 2^64 m);
+ *                                 a NaN agrees with nothing.  Where lq2 or lt2 is +inf the length gate compares a NaN
+ *                                 (inf - inf) and lets the sample through: it ends here all the same.
+ * A pair all of whose samples lie outside the band is FX_REG_NO_HYPOTHESIS.  min_baseline is squared in fp32: below 2^-75
+ * (2.6e-23) the square rounds to 0 and the baseline gate passes everything, coincident keypoints included; nrm > 0 is then the
+ * one clause that keeps 0 / 0 out.  The default min_baseline of 2 m keeps every sample that passes the gate 32 binades inside
+ * the band.  tests/test_gpu_register_numerics.py runs all of this against numpy.
  * Refit — fp64, sequential in ascending query row, no contraction, over the winner's agreeing set:
  *   centroids qc, tc of the set (sum, then divide); per member with u = q - qc, v = t - tc:
  *   Sdot += (ux vx + uy vy), Scrs += (ux vy - uy vx); nrm = sqrt(Sdot Sdot + Scrs Scrs);
@@ -750,6 +766,9 @@ fx_status fx_map_read_alias(fx_ctx *ctx, fx_map *map, uint32_t first, uint32_t c
  * inlier_dist.  The winner has the most agreeing correspondences among all n_corr, ties to the lowest (a, b); a sample with fewer
  * than 2 agreeing is no hypothesis.  Without one the scan gets FX_LOC_NO_HYPOTHESIS, D = the identity, rms = +inf, n_inliers = 0
  * and the prior as its pose.  numpy float64 reproduces the stage bit for bit.
+ * Scale: fx_register_matches's statement with fp64's range: dot dot + crs crs is normal for 2^-1022 <= b^4 < 2^1024, that is
+ * 2^-255.5 m <= b < 2^256 m; it rounds to 0 (the sample is skipped) below 2^-268.5 m (b^4 < 2^-1074) and is +inf (c = s = 0 or
+ * NaN: no agreement) from 2^256 m.  mb mb is the double product of a float: never 0, so the baseline gate cannot be disabled.
  * Refit: fx_register_matches's clause word for word (the same device code): the fit over the agreeing set, the re-test of all
  * n_corr giving I1, the second fit when I1 has at least 2 members.  (dc, ds, dtx, dty) is the final transform, dtz the sequential
  * mean of t_z - q_z over the final set, rms and n_inliers as in the register; hyp_a, hyp_b the rows of the winning sample.

@@ -96,3 +96,44 @@ def assert_prior_kept(rec, priors, what=""):
     for b in range(len(rec)):
         if not rec["flags"][b] & capi.FX_LOC_VALID:
             assert rec["pose"][b].tobytes() == priors[b].tobytes(), f"{what}: scan {b} is not VALID and its pose is not the prior"
+
+
+# ---- ties between samples of the consensus (k_loc_consensus deals its samples as k_register does, in fp64)
+TIE_H = 128
+TIE_SAMPLES = [(0, 1), (63, 64), (0, 255), (0, 256), (255, 256), (5, 8127), (4095, 4096)]
+TIE_FRAGS = [(0, 0.0, 0.0), (0, 200.0, 0.0), (0, 210.0, 0.0), (0, 211.5, 0.0), (0, 200.0, 20.0), (0, 210.0, 20.0)]
+TIE_OPTS = dict(hyp_corr=TIE_H, min_inliers=2)
+
+
+def tie_scans():
+    """A scan per (i, j) of TIE_SAMPLES: 128 rows, all in the pool, whose only live samples are i and j with 2 agreeing each.
+    The row of pool rank r lies 1 + r / 256 m from its landmark, so d2 ranks it r, and rows run against the ranks.  Junk rows
+    all sit west of landmark 0: two of them share the landmark (lt2 = 0: the baseline gate), and with a carrier, 200 m east and
+    moved north or south, the row side is about a metre longer than the landmark side (the length gate).  Carriers are moved
+    along y by their own distance: two moved the same way differ by a small rotation and agree with their own sample only;
+    moved opposite ways they are 3 m apart in length (landmarks 1 and 4) or, 11.5 m apart in x, just inside the gate (1 and 3:
+    the samples that share a member); landmarks 2 and 3 are 1.5 m apart: no sample.  Returns (rows by scan, [(hyp_a, hyp_b)] as
+    rows of the scan)."""
+    from tests import register_util as ru
+    scans_, want = [], []
+    for i, j in TIE_SAMPLES:
+        (ai, bi), (aj, bj) = ru.ranks_of(TIE_H, i), ru.ranks_of(TIE_H, j)
+        shared = set((ai, bi)) & set((aj, bj))
+        if shared:
+            s, = shared
+            x, = set((ai, bi)) - shared
+            y, = set((aj, bj)) - shared
+            car = {s: (1, 1.0), x: (2, 1.0), y: (3, -1.0)}
+        else:
+            car = {ai: (1, 1.0), bi: (2, 1.0), aj: (4, -1.0), bj: (5, -1.0)}
+        rows = []
+        for r in range(TIE_H):
+            d = 1.0 + r / 256.0
+            if r in car:
+                k, sign = car[r]
+                rows.append((TIE_FRAGS[k][1], F32(TIE_FRAGS[k][2] + sign * d), 1.0))
+            else:
+                rows.append((F32(-d), 0.0, 1.0))
+        scans_.append(rows[::-1])
+        want.append((TIE_H - 1 - ai, TIE_H - 1 - bi))
+    return scans_, want

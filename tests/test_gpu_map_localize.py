@@ -225,6 +225,16 @@ def test_c_gate_edge_tie_and_the_filters_of_the_walk(ctx):
         assert got["nearest_of_row"].tolist() == want, opts
 
 
+def test_c_ties_between_samples_in_every_position_of_the_reduction(ctx):
+    """lu.tie_scans: two live samples a scan, 2 agreeing each, in neighbouring lanes, wavefronts and rounds and at the ends of the
+    sample range (tests/test_map_localize_reference.py holds the scans to their answers): the lower sample wins."""
+    rows, want = lu.tie_scans()
+    got = _hand(ctx, lu.TIE_FRAGS, rows, "(c) ties", **lu.TIE_OPTS)
+    rec = got["rec"]
+    assert (rec["n_corr"] == lu.TIE_H).all() and (rec["n_inliers"] == 2).all() and (rec["flags"] == capi.FX_LOC_VALID).all()
+    assert [(int(a) - lu.TIE_H * b, int(c) - lu.TIE_H * b) for b, (a, c) in enumerate(zip(rec["hyp_a"], rec["hyp_b"]))] == want
+
+
 def test_c_bad_priors_bad_rows_and_an_empty_map(ctx):
     LAT = lu.lattice(16)
     scan = lu.rows_at(LAT, [0, 1, 2, 5, 6, 9], 0.1)

@@ -246,3 +246,23 @@ def test_b_more_than_max_corr_correspondences_are_truncated():
     rec = out["rec"][0]
     assert rec["n_corr"] == 1024 and rec["flags"] == VALID | TRUNC and rec["n_inliers"] == 1024
     assert out["nearest_of_row"][1024] == 1024 and out["map_id_of_row"][1024] == -1
+
+
+def test_b_ties_between_samples_go_to_the_lowest_sample():
+    """The (i, j) list of the register's tie test through the fp64 consensus: neighbouring lanes, wavefronts, rounds, and the ends
+    of the sample range.  Each scan has exactly two live samples with 2 agreeing each; the lower one wins."""
+    st = _map(lu.TIE_FRAGS)
+    rows, want = lu.tie_scans()
+    out = _loc(st, rows, **lu.TIE_OPTS)
+    rec = out["rec"]
+    assert (rec["n_corr"] == lu.TIE_H).all() and (rec["n_inliers"] == 2).all() and (rec["flags"] == VALID).all()
+    got = [(int(a) - 128 * b, int(c) - 128 * b) for b, (a, c) in enumerate(zip(rec["hyp_a"], rec["hyp_b"]))]
+    assert got == want, (got, want)
+    # the higher sample is alive as well: without the lower one's first carrier in the pool's reach it wins
+    from tests import register_util as ru
+    for b, (i, j) in enumerate(lu.TIE_SAMPLES):
+        one = [list(r) for r in rows]
+        a = want[b][0] if ru.ranks_of(lu.TIE_H, i)[0] not in ru.ranks_of(lu.TIE_H, j) else want[b][1]
+        one[b][a] = (500.0, 500.0, 1.0)  # a carrier of sample i alone leaves: no landmark in reach
+        r = _loc(st, one, **lu.TIE_OPTS)["rec"][b]
+        assert r["n_corr"] == lu.TIE_H - 1 and r["n_inliers"] == 2 and r["flags"] == VALID and (r["hyp_a"], r["hyp_b"]) != (rec["hyp_a"][b], rec["hyp_b"][b]), (i, j, r)

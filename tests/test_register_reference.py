@@ -263,3 +263,139 @@ def test_whole_chain_recovers_a_rotation_about_z(fxlib, oracle, deg):
     print(f"{deg} deg: {r['n_corr']} correspondences, {r['n_inliers']} inliers, yaw {math.degrees(yaw):.4f} deg, t ({r['tx']:.4f}, {r['ty']:.4f}, {r['tz']:.4f}), "
           f"rms {r['rms']:.4f}, error at 50 m + translation {err:.4f} m")
     assert r["flags"] & VALID and err <= 0.30 and 2 * r["n_inliers"] >= r["n_corr"]
+
+
+# ---- the gates at equality, ties, fp32's edges: the inputs of tests/test_gpu_register_numerics.py held to known answers here
+def _family(cases, opts):
+    q, t, m, pairs = ru.assemble([c[1] for c in cases])
+    return (q, t, m, pairs), capi.register_reference(q, t, m, pairs, **opts), ru.census(q, t, m, pairs, **opts)
+
+
+def test_gates_at_equality_keep_and_one_float_beyond_skips():
+    cases = ru.gate_cases()
+    _, ref, cen = _family(cases, ru.GATE_OPTS)
+    ru.check_expected(ref["rec"], ref["inlier"], _[3], cases, "gates")
+    c = {name: x for (name, _c, _w), x in zip(cases, cen)}
+    four = np.float32(4.0)
+    # each pair reaches the clause it is named for, on the side it is named for
+    assert c["baseline q =="]["lq2"][0] == four and c["baseline q =="]["baseline_rejected"] == 0
+    assert c["baseline q below"]["lq2"][0] == ru.up(4.0, -1) and c["baseline q below"]["lt2"][0] > four and c["baseline q below"]["baseline_rejected"] == 1
+    assert c["baseline t =="]["lt2"][0] == four and c["baseline t =="]["baseline_rejected"] == 0
+    assert c["baseline t below"]["lt2"][0] == ru.up(4.0, -1) and c["baseline t below"]["lq2"][0] > four and c["baseline t below"]["baseline_rejected"] == 1
+    assert c["length =="]["diff"][0] == np.float32(0.5) and c["length =="]["length_rejected"] == 0
+    assert c["length =="]["on_edge"].all() and c["length =="]["retest_on_edge"].all(), "both residuals are exactly inlier_dist, fp32 and fp64"
+    assert c["length beyond"]["diff"][0] == np.float32(0.5 + 2.0 ** -21) and (c["length beyond"]["baseline_rejected"], c["length beyond"]["length_rejected"]) == (0, 1)
+    a, b = c["agreement =="], c["agreement beyond"]
+    assert a["on_edge"].tolist() == [False] * 4 + [True] and a["counts"][a["live"]].tolist() == [2, 3] and a["winner"] == ru.sample_of(5, 2, 3)
+    assert not b["on_edge"].any() and b["counts"][b["live"]].tolist() == [2, 2] and b["live"].tolist() == a["live"].tolist() and b["winner"] == 0
+    print("gates:", {n: (x["baseline_rejected"], x["length_rejected"], x["nrm_rejected"], x["max_count"]) for n, x in c.items()})
+
+
+def test_the_retest_at_equality_and_one_float_beyond():
+    cases = ru.retest_cases()
+    inp, ref, cen = _family(cases, ru.RETEST_OPTS)
+    ru.check_expected(ref["rec"], ref["inlier"], inp[3], cases, "re-test")
+    assert cen[0]["retest_on_edge"].tolist() == [False] * 4 + [True] and not cen[0]["on_edge"].any() and cen[0]["max_count"] == 4
+    assert not cen[1]["retest_on_edge"].any() and cen[1]["max_count"] == 4
+    assert ref["rec"]["tx"][1] == 1.03125 and ref["rec"]["tx"][0] != 1.03125, "the second fit runs over five in the kept twin"
+
+
+def test_a_min_baseline_whose_square_is_zero_leaves_only_nrm_positive():
+    assert np.float32(1e-30) > 0 and np.float32(1e-30) * np.float32(1e-30) == 0
+    cases = ru.tiny_baseline_cases()
+    inp, ref, cen = _family(cases, ru.TINY_OPTS)
+    ru.check_expected(ref["rec"], ref["inlier"], inp[3], cases, "tiny min_baseline")
+    assert cen[0]["baseline_rejected"] == 0 and cen[0]["nrm_rejected"] == 3, "duplicate query rows, duplicate train rows, both"
+    assert (cen[1]["baseline_rejected"], cen[1]["length_rejected"], cen[1]["nrm_rejected"]) == (0, 0, 10) == (0, 0, cen[1]["n_samples"])
+    # with the default min_baseline the same pairs stop at the baseline gate
+    q, t, m, pairs = inp
+    assert ru.census(q, t, m, pairs, **ru.GATE_OPTS)[1]["baseline_rejected"] == 10
+
+
+@pytest.fixture(scope="module")
+def scale_base():
+    base = ru.scale_base()
+    return base, capi.register_reference(*base, **ru.SCALE_OPTS)["rec"]
+
+
+def _scaled_reference(base, k):
+    q, t, m, pairs, o = ru.scaled(base, k)
+    return capi.register_reference(q, t, m, pairs, **o)["rec"], ru.census(q, t, m, pairs, **o)
+
+
+def test_power_of_two_scaling_is_exact_inside_the_band(scale_base):
+    """The band of the committed seed, by the reference alone: every k of K_BAND leaves the integers and the bits of c and s
+    alone and scales tx, ty, tz and rms exactly."""
+    base, r0 = scale_base
+    assert ((r0["flags"] & VALID) != 0).sum() >= 7 and (r0["flags"] & NOHYP).any()
+    lo, hi = ru.K_BAND
+    assert lo <= -30 and hi >= 20 and set(ru.K_BAND_GPU) <= set(range(lo, hi + 1))
+    for k in range(lo, hi + 1):
+        ru.assert_scaled(_scaled_reference(base, k)[0], r0, k, "reference")
+
+
+def test_the_transition_zones_and_far_out_reach_fp32s_edges(scale_base):
+    base, r0 = scale_base
+    seen = {z: dict(subnormal_nrm=0, nrm_zero_distinct=0, nrm_inf=0, cs_zero=0, mixed=0) for z in ("low", "high")}
+    for k in ru.K_ZONES:
+        rec, cen = _scaled_reference(base, k)
+        z = seen["low" if k < 0 else "high"]
+        for key in ("subnormal_nrm", "nrm_zero_distinct", "nrm_inf", "cs_zero"):
+            z[key] += ru.total(cen, key)
+        valid = (rec["flags"] & VALID) != 0
+        z["mixed"] += int(valid.any() and (valid != ((r0["flags"] & VALID) != 0)).any())
+    print("zones:", seen)
+    assert seen["low"]["subnormal_nrm"] > 0 and seen["low"]["nrm_zero_distinct"] > 0 and seen["low"]["mixed"] > 0
+    assert seen["high"]["nrm_inf"] > 0 and seen["high"]["cs_zero"] > 0 and seen["high"]["mixed"] > 0
+    far = dict(nan_passed=0, cs_nonfinite=0, subnormal=0)
+    for k in ru.K_FAR:
+        rec, cen = _scaled_reference(base, k)
+        assert (rec["flags"] == NOHYP).all(), k
+        for key in far:
+            far[key] += ru.total(cen, key)
+    q, t, m, pairs, _ = ru.scaled(base, -133)
+    assert (np.abs(q[:, :3]) < ru.TINY32).all() and (np.abs(t[:, :3]) < ru.TINY32).all() and (q[:, :2] != 0).any(), "subnormal coordinates"
+    q, t, m, pairs = ru.extreme_case()
+    ext = ru.census(q, t, m, pairs, **ru.SCALE_OPTS)
+    assert (capi.register_reference(q, t, m, pairs, **ru.SCALE_OPTS)["rec"]["flags"] == NOHYP).all()
+    print("far out:", far, "at +-3e38: nan_passed", ru.total(ext, "nan_passed"))
+    assert far["nan_passed"] > 0 and far["cs_nonfinite"] > 0 and far["subnormal"] > 0 and ru.total(ext, "nan_passed") > 0
+
+
+def test_ties_and_the_ends_of_the_sample_range():
+    cases = ru.tie_cases()
+    inp, ref, cen = _family(cases, ru.TIE_OPTS)
+    ru.check_expected(ref["rec"], ref["inlier"], inp[3], cases, "ties")
+    n = len(ru.TIE_SAMPLES)
+    for (i, j), c in zip(ru.TIE_SAMPLES, cen[:n]):
+        assert c["H"] == 128 and c["live"].tolist() == [i, j] and c["counts"][[i, j]].tolist() == [2, 2] and c["winner"] == i, (i, j)
+    for (i, j), c in zip(ru.TIE_SAMPLES, cen[n:2 * n]):
+        assert c["live"].tolist() == [i, j] and c["counts"][[i, j]].tolist() == [2, 3] and c["winner"] == j, (i, j)
+    for H, c in zip(ru.LAST_H, cen[2 * n:]):
+        assert c["H"] == H and c["live"].tolist() == [H * (H - 1) // 2 - 1] and c["max_count"] == 2, H
+    assert all(ru.ranks_of(H, ru.sample_of(H, a, b)) == (a, b) for H in (2, 3, 128) for a in range(H) for b in range(a + 1, H))
+
+
+@pytest.mark.parametrize("H", ru.BITS_H)
+def test_the_pool_is_ranked_by_the_bits_of_dist2(H):
+    cases = ru.bits_cases(H)
+    inp, ref, cen = _family(cases, ru.bits_opts(H))
+    ru.check_expected(ref["rec"], ref["inlier"], inp[3], cases, f"bits {H}")
+    for (name, case, want), c in zip(cases, cen):
+        assert c["n_corr"] > c["H"] == H and set(c["pool"]) != set(c["pool_float"]) and c["pool"][0] != c["pool_float"][0], name
+    words = np.asarray(cases[1][1][2])
+    cut = cen[1]
+    run = np.flatnonzero(words == ru.RUN_WORD[H])
+    assert len(run) == 3 and cut["pool"][H - 1] == run.min() and not set(run[1:]) & set(cut["pool"]), "the cut falls inside the run: its lowest row is in"
+    assert cut["live"].tolist() == [ru.sample_of(H, 0, H - 1)] and cut["max_count"] == 4
+
+
+def test_the_refit_falls_back_to_the_first_set():
+    cases = ru.fallback_cases()
+    q, t, m, pairs = ru.assemble([c[1] for c in cases])
+    ref, cen = capi.register_reference(q, t, m, pairs, **ru.FALLBACK_OPTS), ru.census(q, t, m, pairs, **ru.FALLBACK_OPTS)
+    k = len(ru.FALLBACK_SEEDS)
+    assert [c["fallback"] for c in cen[:k]] == [True] * k and not any(c["fallback"] for c in cen[k:])
+    rec = ref["rec"][:k]
+    assert (rec["flags"] == VALID).all() and (rec["n_inliers"] == 2).all() and ref["inlier"][:2 * k].all()
+    assert (np.abs(rec["rms"] - 0.25) < 1e-6).all(), "both residuals sit at inlier_dist"
