@@ -19,6 +19,7 @@ FX_DESC_FLOATS = 1989
 FX_FEATURE_RECORD_BYTES = 7984
 FX_OK = 0
 FX_ERR_NO_DEVICE = 2
+FX_ERR_INVALID_ARG, FX_ERR_TOO_LARGE = 1, 5
 FX_IN_DEVICE, FX_OUT_HOST, FX_OUT_DEBUG, FX_OUT_CLOUDS = 1, 2, 4, 8
 FX_OUT_DESC_CSR = 0x10  # with FX_OUT_HOST: the descriptor rows come back as the context's CSR block (fx_get_descriptors_csr)
 FX_FLAG_RING_OVERFLOW, FX_FLAG_CAND_OVERFLOW, FX_FLAG_KP_OVERFLOW, FX_FLAG_NBR_OVERFLOW = 0x1, 0x2, 0x4, 0x8
@@ -192,6 +193,19 @@ class FxMapMergeResult(C.Structure):
 MAP_MERGE_RESULT_FIELDS = ("proposals", "merged", "live", "reserved")
 
 
+class FxMapCompactOptions(C.Structure):
+    _fields_ = [("min_obs", C.c_uint32), ("min_age_scans", C.c_uint32)]
+
+
+class FxMapCompactResult(C.Structure):
+    _fields_ = [("before", C.c_uint32), ("kept", C.c_uint32), ("dropped_absorbed", C.c_uint32), ("dropped_live", C.c_uint32)]
+
+
+MAP_COMPACT_RESULT_FIELDS = ("before", "kept", "dropped_absorbed", "dropped_live")
+# the snapshot of a map (include/fx.h fx_map_export_host; map_snapshot_pack is the layout's statement in Python)
+FX_MAP_SNAPSHOT_MAGIC, FX_MAP_SNAPSHOT_FORMAT, FX_MAP_SNAPSHOT_HEADER_BYTES, FX_MAP_ACC = 0x504D5846, 1, 64, 8
+
+
 class FxLocalizeOptions(C.Structure):
     _fields_ = [("search_dist", C.c_float), ("inlier_dist", C.c_float), ("min_baseline", C.c_float), ("hyp_corr", C.c_uint32),
                 ("min_inliers", C.c_uint32), ("min_landmark_obs", C.c_uint32), ("segment", C.c_uint32), ("reserved", C.c_uint32)]
@@ -240,6 +254,7 @@ EXPORTS = ("fx_version", "fx_check_abi", "fx_status_str", "fx_last_error", "fx_p
            "fx_map_create", "fx_map_destroy", "fx_map_reset", "fx_map_update", "fx_map_get", "fx_map_read_header", "fx_map_read_landmarks",
            "fx_map_merge_options_default", "fx_map_merge", "fx_map_get_alias", "fx_map_read_alias",
            "fx_localize_options_default", "fx_map_localize",
+           "fx_map_compact_options_default", "fx_map_compact", "fx_map_export_host", "fx_map_import_host", "fx_map_snapshot_check",
            "fx_rotation_from_roll_pitch", "fx_sc3d_tables", "fx_sc3d_xaxis", "fx_synth_cfg_vlp16",
            "fx_synth_scan", "fx_unpack_pointcloud2", "fx_pack_pointxyzi")
 # the header's FX_TEST_HOOKS section: exported by lib/libfx_hip_test.so only
@@ -372,6 +387,12 @@ def load():
     lib.fx_localize_options_default.restype = None
     lib.fx_map_localize.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
                                     C.POINTER(FxLocalizeOptions), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.fx_map_compact_options_default.argtypes = [C.POINTER(FxMapCompactOptions)]
+    lib.fx_map_compact_options_default.restype = None
+    lib.fx_map_compact.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(FxMapCompactOptions), C.c_void_p, C.c_void_p]
+    lib.fx_map_export_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.fx_map_import_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+    lib.fx_map_snapshot_check.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32]
     lib.fx_rotation_from_roll_pitch.argtypes = [C.c_double, C.c_double, _F32P]
     lib.fx_rotation_from_roll_pitch.restype = None
     lib.fx_sc3d_tables.argtypes = [C.c_double, _F32P, _F32P, _F32P, _F32P]
@@ -1114,6 +1135,105 @@ def map_merge_reference(state, merge_dist=0.30, max_gap_scans=64):
     return st, {"proposals": len(prop), "merged": len(succ), "live": live, "reserved": 0}
 
 
+# ---- the map compacted, and its whole state as one block of bytes (include/fx.h fx_map_compact, fx_map_export_host)
+def map_compact_reference(state, min_obs=1, min_age_scans=64):
+    """The definition of fx_map_compact (include/fx.h) in plain loops over a map_reference / map_merge_reference state, which is
+    not modified; a state without "alias" has every landmark live.  Returns (the new state, remap int32 [max_landmarks], {"before",
+    "kept", "dropped_absorbed", "dropped_live"})."""
+    min_obs, min_age = int(min_obs), int(min_age_scans) & 0xffffffff
+    if min_obs < 1:
+        raise ValueError("min_obs must be at least 1")
+    H = dict(state["header"])
+    lms, accs = state["landmarks"], state["acc"]
+    N = min(int(H["n_landmarks"]), len(lms))
+    alias = [int(a) for a in state.get("alias", [])][:N]
+    alias += [-1] * (N - len(alias))
+
+    def root(i):
+        return alias[i] if 0 <= alias[i] < N else i
+    carry = [int(c) for c in state["carry"]]
+    carried = set(root(c) for c in carry[:int(H["carry_rows"])] if 0 <= c < N)
+    new_id, K, absorbed, lost_obs = [-1] * N, 0, 0, 0
+    for i in range(N):
+        if alias[i] != -1:
+            absorbed += 1
+            continue
+        age = ((int(H["scans"]) - 1) - int(lms[i]["last_scan"])) & 0xffffffff
+        if int(lms[i]["n_obs"]) >= min_obs or age < min_age or i in carried:
+            new_id[i] = K
+            K += 1
+        else:
+            lost_obs += int(lms[i]["n_obs"])
+    st = dict(state, header=H, landmarks=[dict(lms[i]) for i in range(N) if new_id[i] >= 0],
+              acc=[list(accs[i]) for i in range(N) if new_id[i] >= 0], alias=[-1] * K, carry_kp=state["carry_kp"].copy())
+    st["carry"] = [(new_id[root(c)] if c < N else -1) if c >= 0 else c for c in carry]
+    H["n_landmarks"] = H["n_needed"] = K
+    H["n_obs"] = (int(H["n_obs"]) - lost_obs) & 0xffffffff
+    remap = np.full(int(state["max_landmarks"]), -1, np.int32)
+    for i in range(N):
+        remap[i] = new_id[root(i)]
+    return st, remap, {"before": N, "kept": K, "dropped_absorbed": absorbed, "dropped_live": N - K - absorbed}
+
+
+def _pad16(b):
+    return b + b"\0" * (-len(b) % 16)
+
+
+def map_snapshot_pack(state):
+    """A map_reference / map_merge_reference / map_compact_reference state as the bytes fx_map_export_host writes for a device map in
+    that state (include/fx.h, "The snapshot"): the layout's one statement in Python."""
+    import struct
+    H = state["header"]
+    n, r = int(H["n_landmarks"]), int(H["carry_rows"])
+    lms, accs, carry = state["landmarks"], state["acc"], [int(c) for c in state["carry"]]
+    if len(lms) != n or len(accs) != n or len(carry) != r or len(state["carry_kp"]) != r:
+        raise ValueError(f"the state holds {len(lms)} landmarks and {len(carry)} carry rows, its header says {n} and {r}")
+    alias = [int(a) for a in state.get("alias", [])][:n]
+    alias += [-1] * (n - len(alias))
+    p = H["last_pose"]
+    hdr = struct.pack("<10I", *(int(H[k]) & 0xffffffff for k in MAP_HEADER_FIELDS)) + struct.pack("<5d2I", *(float(v) for v in p[:5]), int(p[5]), int(p[6]))
+    rec = np.zeros(n, MAP_LANDMARK_DTYPE)
+    for i, R in enumerate(lms):
+        rec[i] = tuple(R[f] for f in MAP_LANDMARK_DTYPE.names)
+    body = [_pad16(hdr), rec.tobytes(), np.array(accs, "<f8").reshape(n, FX_MAP_ACC).tobytes(), _pad16(np.array(alias, "<i4").tobytes()),
+            _pad16(np.array(carry, "<i4").tobytes()), np.ascontiguousarray(state["carry_kp"], "<u4").reshape(r, 4).tobytes()]
+    total = FX_MAP_SNAPSHOT_HEADER_BYTES + sum(len(b) for b in body)
+    head = struct.pack("<10IQ", FX_MAP_SNAPSHOT_MAGIC, FX_MAP_SNAPSHOT_FORMAT, FX_HEADER_VERSION, FX_MAP_SNAPSHOT_HEADER_BYTES, n, r,
+                       C.sizeof(FxMapHeader), C.sizeof(FxMapLandmark), FX_MAP_ACC, 0, total)
+    return head + b"\0" * (FX_MAP_SNAPSHOT_HEADER_BYTES - len(head)) + b"".join(body)
+
+
+def map_snapshot_parse(data, max_landmarks=None, max_carry_rows=None):
+    """The bytes of a snapshot as a map_reference state ("alias" included); max_landmarks / max_carry_rows: the capacities the
+    state is to have (default: what the snapshot holds).  Raises ValueError on a block the layout does not describe (the content
+    checks are fx_map_snapshot_check's)."""
+    import struct
+    data = bytes(data)
+    if len(data) < FX_MAP_SNAPSHOT_HEADER_BYTES:
+        raise ValueError("shorter than the block header")
+    w = struct.unpack_from("<10IQ", data)
+    if w[0] != FX_MAP_SNAPSHOT_MAGIC or w[1] != FX_MAP_SNAPSHOT_FORMAT or (w[3], w[6], w[7], w[8]) != (64, 88, 48, FX_MAP_ACC):
+        raise ValueError(f"not a format-1 map snapshot: {w}")
+    n, r = w[4], w[5]
+    up = lambda b: (b + 15) & ~15
+    o_rec = 64 + up(88)
+    o_acc = o_rec + 48 * n
+    o_alias = o_acc + 64 * n
+    o_carry = o_alias + up(4 * n)
+    o_kp = o_carry + up(4 * r)
+    if w[10] != len(data) or len(data) != o_kp + 16 * r:
+        raise ValueError(f"total bytes {w[10]}, {len(data)} given, the sections sum to {o_kp + 16 * r}")
+    h = struct.unpack_from("<10I5d2I", data, 64)
+    hdr = dict(zip(MAP_HEADER_FIELDS, h[:10]))
+    hdr["last_pose"] = tuple(h[10:])
+    rec = np.frombuffer(data, MAP_LANDMARK_DTYPE, n, o_rec)
+    lms = [{f: (np.float32(R[f]) if f == "rms_xy" else float(R[f]) if f in "xyz" else int(R[f])) for f in MAP_LANDMARK_DTYPE.names} for R in rec]
+    acc = np.frombuffer(data, "<f8", n * FX_MAP_ACC, o_acc).reshape(n, FX_MAP_ACC).tolist()
+    return {"max_landmarks": n if max_landmarks is None else int(max_landmarks), "max_carry_rows": r if max_carry_rows is None else int(max_carry_rows),
+            "header": hdr, "landmarks": lms, "acc": acc, "alias": np.frombuffer(data, "<i4", n, o_alias).tolist(),
+            "carry": np.frombuffer(data, "<i4", r, o_carry).tolist(), "carry_kp": np.frombuffer(data, "<u4", 4 * r, o_kp).reshape(r, 4).copy()}
+
+
 # ---- scans localised against the map under a prior pose (include/fx.h fx_map_localize)
 def localize_records(out):
     """A host copy of fx_map_localize's records (a torch tensor, or any array of n * 112 bytes) as LOC_DTYPE records."""
@@ -1377,6 +1497,46 @@ class Map:
                                        C.c_void_p(ids.data_ptr() if n_rows else None), C.c_void_p(nearest.data_ptr() if nearest is not None and n_rows else None)))
         cur.wait_stream(ext)
         return recs, ids, nearest
+
+    def compact(self, min_obs=1, min_age_scans=64, remap=None, result=None):
+        """fx_map_compact: the absorbed and the let-go landmarks taken out, the others renumbered in order (include/fx.h).  Returns
+        (remap, result): device torch.int32 tensors [max_landmarks] (old id -> new id, -1: gone) and [4] (before, kept,
+        dropped_absorbed, dropped_live); a tensor given reuses it, False passes NULL (None is returned in its place).
+        Stream-correct like merge(); never waits for the stream."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        outs = []
+        for t, n, name in ((remap, self.max_landmarks, "remap"), (result, 4, "result")):
+            if t is None:
+                t = torch.empty((n,), dtype=torch.int32, device=dev)
+            elif t is False:
+                t = None
+            elif t.dtype != torch.int32 or t.device != dev or tuple(t.shape) != (n,) or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous torch.int32 tensor [{n}] on {dev}")
+            outs.append(t)
+        remap, result = outs
+        opt = FxMapCompactOptions(int(min_obs), int(min_age_scans))
+        cur = torch.cuda.current_stream(dev)
+        ext = torch.cuda.ExternalStream(self.ctx.stream_ptr(), device=dev)
+        ext.wait_stream(cur)
+        check(self.lib.fx_map_compact(self.ctx.handle, self.handle, C.byref(opt), C.c_void_p(remap.data_ptr() if remap is not None else None),
+                                      C.c_void_p(result.data_ptr() if result is not None else None)))
+        cur.wait_stream(ext)
+        return remap, result
+
+    def export_state(self):
+        """fx_map_export_host (waits for the stream): the map's whole state as the bytes of one snapshot."""
+        n = C.c_size_t()
+        check(self.lib.fx_map_export_host(self.ctx.handle, self.handle, None, 0, C.byref(n)))
+        buf = C.create_string_buffer(max(n.value, 1))
+        check(self.lib.fx_map_export_host(self.ctx.handle, self.handle, buf, n.value, C.byref(n)))
+        return buf.raw[:n.value]
+
+    def import_state(self, data):
+        """fx_map_import_host: the snapshot `data` (bytes) becomes this map's state, in stream order; a block the check refuses
+        raises FxError and leaves the map as it was."""
+        data = bytes(data)
+        check(self.lib.fx_map_import_host(self.ctx.handle, self.handle, data, len(data)))
 
     def alias(self, first=0, count=None):
         """fx_map_read_alias (waits for the stream): alias[first, first + count) as int32, -1 for a live landmark, else the id of

@@ -93,6 +93,8 @@ size_t fxk_map_merge_scratch(FxMapMergeArgs *A, uint8_t *base);
 uint32_t fxk_map_merge_wg(void);
 hipError_t fxk_map_localize(hipStream_t s, const FxMapLocalizeArgs &A);
 size_t fxk_map_localize_scratch(FxMapLocalizeArgs *A, uint8_t *base);
+hipError_t fxk_map_compact(hipStream_t s, const FxMapCompactArgs &A);
+size_t fxk_map_compact_scratch(FxMapCompactArgs *A, uint8_t *base);
 #ifdef FX_TEST_HOOKS
 void fxk_test_sort_replay(hipStream_t s, const uint32_t *sizes, uint32_t n_seq, uint32_t n, uint32_t *perm);
 void fxk_test_elevation(hipStream_t s, const float *xyz, uint32_t n, const double *tab, float *fast, uint8_t *ok, float *exact);
@@ -263,7 +265,12 @@ struct fx_ctx {
   DevScratch track_scratch;  // fx_track_landmarks: the per-row scratch arrays
   DevScratch map_scratch;    // fx_map_update: the batch landmark's map id, the blocks' counts
   DevScratch merge_scratch;  // fx_map_merge: the grid (bucket counts, landmarks in bucket order), proposals, kept links;
-                             // fx_map_localize: the same grid, then each row's landmark and distance
+                             // fx_map_localize: the same grid, then each row's landmark and distance;
+                             // fx_map_compact: the marks, the new ids, the blocks' counts, the kept records and sums staged
+  // fx_map_import_host: the snapshot's bytes, pinned, until the copies enqueued from them are done (snap_ev)
+  uint8_t *snap_h = nullptr;
+  size_t snap_bytes = 0;
+  hipEvent_t snap_ev = nullptr;
 };
 
 // A persistent landmark map (include/fx.h fx_map_create): one device buffer, carved up once.
@@ -1059,6 +1066,8 @@ void fx_destroy(fx_ctx *c) {
   if (c->h_csr) (void)hipHostFree(c->h_csr);
   c->match_stage.release(), c->match_scratch.release(), c->reg_stage.release(), c->track_scratch.release(), c->map_scratch.release(),
       c->merge_scratch.release();
+  if (c->snap_h) (void)hipHostFree(c->snap_h);
+  if (c->snap_ev) (void)hipEventDestroy(c->snap_ev);
   for (int i = 0; i < kMetaSlots; ++i)
     if (c->meta_ev[i]) (void)hipEventDestroy(c->meta_ev[i]);
   for (hipEvent_t e : c->ev_ring) (void)hipEventDestroy(e);
@@ -1984,6 +1993,168 @@ fx_status fx_map_read_alias(fx_ctx *c, fx_map *m, uint32_t first, uint32_t count
   FX_HIP(hipSetDevice(c->device));
   if (count) FX_HIP(hipMemcpyAsync(out, m->a.alias + first, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   FX_HIP(hipStreamSynchronize(c->stream));
+  return FX_OK;
+}
+
+void fx_map_compact_options_default(fx_map_compact_options *o) {
+  if (!o) return;
+  o->min_obs = 1;
+  o->min_age_scans = 64;
+}
+
+fx_status fx_map_compact(fx_ctx *c, fx_map *m, const fx_map_compact_options *opt, int32_t *remap, fx_map_compact_result *result) {
+  if (!c || !m) return fail(FX_ERR_INVALID_ARG, "null argument");
+  if (m->ctx != c) return fail(FX_ERR_INVALID_ARG, "the map belongs to another context");
+  fx_map_compact_options o;
+  fx_map_compact_options_default(&o);
+  if (opt) o = *opt;
+  if (!o.min_obs) return fail(FX_ERR_INVALID_ARG, "min_obs must be at least 1");
+  if (((uintptr_t)remap % 4) != 0 || ((uintptr_t)result % 4) != 0) return fail(FX_ERR_INVALID_ARG, "remap and the result must be 4-byte aligned");
+  FX_HIP(hipSetDevice(c->device));
+  FxMapCompactArgs A{};
+  A.header = m->a.header, A.records = m->a.records, A.acc = m->a.acc, A.carry = m->a.carry, A.alias = m->a.alias;
+  A.cap = m->a.cap, A.max_carry = m->a.max_carry;
+  A.min_obs = o.min_obs, A.min_age = o.min_age_scans;
+  A.remap = remap, A.result = (uint32_t *)result;
+  FX_TRY(c->merge_scratch.reserve(c, fxk_map_compact_scratch(&A, nullptr), "map compact scratch"));
+  (void)fxk_map_compact_scratch(&A, c->merge_scratch.d);
+  FX_HIP(fxk_map_compact(c->stream, A));
+  return FX_OK;
+}
+
+namespace {
+// The snapshot (include/fx.h fx_map_export_host): a 64-byte block header, then the sections, each from a 16-byte boundary and sized
+// by content: n landmarks, r carry rows.  This is the layout's one statement in the library (Python: capi.map_snapshot_pack).
+constexpr uint32_t kSnapMagic = 0x504D5846u, kSnapFormat = 1u, kSnapHeader = 64u;
+struct SnapLayout {
+  size_t o_hdr, o_rec, o_acc, o_alias, o_carry, o_kp, total;
+};
+SnapLayout snap_layout(uint32_t n, uint32_t r) {
+  auto up = [](size_t b) { return (b + 15u) & ~(size_t)15; };
+  SnapLayout L;
+  L.o_hdr = kSnapHeader;
+  L.o_rec = L.o_hdr + up(sizeof(fx_map_header));
+  L.o_acc = L.o_rec + (size_t)n * sizeof(fx_map_landmark);
+  L.o_alias = L.o_acc + (size_t)n * FX_MAP_ACC * sizeof(double);
+  L.o_carry = L.o_alias + up((size_t)n * 4);
+  L.o_kp = L.o_carry + up((size_t)r * 4);
+  L.total = L.o_kp + (size_t)r * 16;
+  return L;
+}
+}  // namespace
+
+fx_status fx_map_snapshot_check(const void *src, size_t bytes, uint32_t max_landmarks, uint32_t max_carry_rows) {
+  if (!src) return fail(FX_ERR_INVALID_ARG, "null argument");
+  if (bytes < kSnapHeader) return fail(FX_ERR_INVALID_ARG, "snapshot: shorter than the 64-byte block header");
+  const uint8_t *p = (const uint8_t *)src;
+  uint32_t w[10];
+  uint64_t total;
+  memcpy(w, p, sizeof w), memcpy(&total, p + 40, 8);
+  if (w[0] != kSnapMagic) return fail(FX_ERR_INVALID_ARG, "snapshot: wrong magic (not an fx_map snapshot)");
+  if (w[1] != kSnapFormat) return fail(FX_ERR_INVALID_ARG, "snapshot: unknown format " + std::to_string(w[1]) + " (this library reads format 1)");
+  if (w[3] != kSnapHeader || w[6] != sizeof(fx_map_header) || w[7] != sizeof(fx_map_landmark) || w[8] != FX_MAP_ACC)
+    return fail(FX_ERR_INVALID_ARG, "snapshot: struct sizes differ (block header " + std::to_string(w[3]) + ", fx_map_header " + std::to_string(w[6]) +
+                                        ", fx_map_landmark " + std::to_string(w[7]) + ", accumulators " + std::to_string(w[8]) + ")");
+  const uint32_t n = w[4], r = w[5];
+  const SnapLayout L = snap_layout(n, r);
+  if (total != bytes) return fail(FX_ERR_INVALID_ARG, "snapshot: total bytes " + std::to_string(total) + " but " + std::to_string(bytes) + " given");
+  if (total != L.total)
+    return fail(FX_ERR_INVALID_ARG, "snapshot: total bytes " + std::to_string(total) + " but the sections sum to " + std::to_string(L.total));
+  fx_map_header H;
+  memcpy(&H, p + L.o_hdr, sizeof H);
+  if (H.n_landmarks != n || H.carry_rows != r)
+    return fail(FX_ERR_INVALID_ARG, "snapshot: the block's counts differ from its fx_map_header (n_landmarks " + std::to_string(H.n_landmarks) +
+                                        ", carry_rows " + std::to_string(H.carry_rows) + ")");
+  if (H.n_landmarks > H.n_needed) return fail(FX_ERR_INVALID_ARG, "snapshot: n_landmarks exceeds n_needed");
+  if (n > max_landmarks) return fail(FX_ERR_TOO_LARGE, "snapshot: " + std::to_string(n) + " landmarks, max_landmarks " + std::to_string(max_landmarks));
+  if (r > max_carry_rows) return fail(FX_ERR_TOO_LARGE, "snapshot: " + std::to_string(r) + " carry rows, max_carry_rows " + std::to_string(max_carry_rows));
+  const uint8_t *alias = p + L.o_alias, *carry = p + L.o_carry;
+  auto word = [](const uint8_t *q, size_t i) {
+    int32_t v;
+    memcpy(&v, q + 4 * i, 4);
+    return v;
+  };
+  for (uint32_t i = 0; i < n; ++i) {
+    const int32_t a = word(alias, i);
+    if (a < -1 || (a >= 0 && (uint32_t)a >= n)) return fail(FX_ERR_INVALID_ARG, "snapshot: alias[" + std::to_string(i) + "] = " + std::to_string(a) + " is outside [-1, n)");
+    if (a >= 0 && word(alias, (size_t)a) != -1)
+      return fail(FX_ERR_INVALID_ARG, "snapshot: alias[" + std::to_string(i) + "] = " + std::to_string(a) + " is not resolved (a chain)");
+  }
+  for (uint32_t j = 0; j < r; ++j) {
+    const int32_t v = word(carry, j);
+    if (v < -1 || (v >= 0 && (uint32_t)v >= n)) return fail(FX_ERR_INVALID_ARG, "snapshot: carry[" + std::to_string(j) + "] = " + std::to_string(v) + " is outside [-1, n)");
+  }
+  if (H.n_needed > H.n_landmarks && max_landmarks != H.n_landmarks)
+    return fail(FX_ERR_INVALID_ARG, "snapshot: the map overflowed (n_needed " + std::to_string(H.n_needed) + " > n_landmarks " + std::to_string(H.n_landmarks) +
+                                        "): fx_map_compact it before taking it into a map of another max_landmarks");
+  return FX_OK;
+}
+
+fx_status fx_map_export_host(fx_ctx *c, fx_map *m, void *dst, size_t capacity, size_t *bytes_out) {
+  if (!c || !m || (!dst && capacity)) return fail(FX_ERR_INVALID_ARG, "null argument");
+  if (m->ctx != c) return fail(FX_ERR_INVALID_ARG, "the map belongs to another context");
+  FX_HIP(hipSetDevice(c->device));
+  fx_map_header H;
+  FX_HIP(hipMemcpyAsync(&H, m->a.header, sizeof H, hipMemcpyDeviceToHost, c->stream));
+  FX_HIP(hipStreamSynchronize(c->stream));
+  const uint32_t n = std::min(H.n_landmarks, m->a.cap), r = std::min(H.carry_rows, m->a.max_carry);
+  const SnapLayout L = snap_layout(n, r);
+  if (bytes_out) *bytes_out = L.total;
+  if (!dst) return FX_OK;
+  if (capacity < L.total) return fail(FX_ERR_TOO_LARGE, "snapshot: " + std::to_string(L.total) + " bytes, capacity " + std::to_string(capacity));
+  uint8_t *p = (uint8_t *)dst;
+  memset(p, 0, L.total);
+  const uint32_t w[10] = {kSnapMagic, kSnapFormat, fx_version(), kSnapHeader, n, r, (uint32_t)sizeof(fx_map_header), (uint32_t)sizeof(fx_map_landmark), FX_MAP_ACC, 0u};
+  const uint64_t total = L.total;
+  memcpy(p, w, sizeof w), memcpy(p + 40, &total, 8);
+  memcpy(p + L.o_hdr, &H, sizeof H);
+  if (n) {
+    FX_HIP(hipMemcpyAsync(p + L.o_rec, m->a.records, (size_t)n * sizeof(fx_map_landmark), hipMemcpyDeviceToHost, c->stream));
+    FX_HIP(hipMemcpyAsync(p + L.o_acc, m->a.acc, (size_t)n * FX_MAP_ACC * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    FX_HIP(hipMemcpyAsync(p + L.o_alias, m->a.alias, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+  }
+  if (r) {
+    FX_HIP(hipMemcpyAsync(p + L.o_carry, m->a.carry, (size_t)r * 4, hipMemcpyDeviceToHost, c->stream));
+    FX_HIP(hipMemcpyAsync(p + L.o_kp, m->a.carry_kp, (size_t)r * 16, hipMemcpyDeviceToHost, c->stream));
+  }
+  FX_HIP(hipStreamSynchronize(c->stream));
+  return FX_OK;
+}
+
+fx_status fx_map_import_host(fx_ctx *c, fx_map *m, const void *src, size_t bytes) {
+  if (!c || !m || !src) return fail(FX_ERR_INVALID_ARG, "null argument");
+  if (m->ctx != c) return fail(FX_ERR_INVALID_ARG, "the map belongs to another context");
+  FX_TRY(fx_map_snapshot_check(src, bytes, m->a.cap, m->a.max_carry));
+  FX_HIP(hipSetDevice(c->device));
+  // the pinned staging: free to write once the copies of the import before are done
+  if (!c->snap_ev) FX_HIP(hipEventCreateWithFlags(&c->snap_ev, hipEventDisableTiming));
+  FX_HIP(hipEventSynchronize(c->snap_ev));
+  if (bytes > c->snap_bytes) {
+    if (c->snap_h) FX_HIP(hipHostFree(c->snap_h));
+    c->snap_h = nullptr, c->snap_bytes = 0;
+    const size_t want = std::max(bytes, (size_t)4096);
+    void *q = nullptr;
+    hipError_t e = hipHostMalloc(&q, want, hipHostMallocDefault);
+    if (e != hipSuccess) return fail(FX_ERR_OOM, "snapshot staging hipHostMalloc(" + std::to_string(want) + "): " + hipGetErrorString(e));
+    c->snap_h = (uint8_t *)q, c->snap_bytes = want;
+  }
+  memcpy(c->snap_h, src, bytes);
+  const uint8_t *p = c->snap_h;
+  uint32_t n, r;
+  memcpy(&n, p + 16, 4), memcpy(&r, p + 20, 4);
+  const SnapLayout L = snap_layout(n, r);
+  FX_HIP(fxk_map_reset(c->stream, m->a));  // alias -1 everywhere, the state words 0
+  FX_HIP(hipMemcpyAsync(m->a.header, p + L.o_hdr, sizeof(fx_map_header), hipMemcpyHostToDevice, c->stream));
+  if (n) {
+    FX_HIP(hipMemcpyAsync(m->a.records, p + L.o_rec, (size_t)n * sizeof(fx_map_landmark), hipMemcpyHostToDevice, c->stream));
+    FX_HIP(hipMemcpyAsync(m->a.acc, p + L.o_acc, (size_t)n * FX_MAP_ACC * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    FX_HIP(hipMemcpyAsync(m->a.alias, p + L.o_alias, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+  }
+  if (r) {
+    FX_HIP(hipMemcpyAsync(m->a.carry, p + L.o_carry, (size_t)r * 4, hipMemcpyHostToDevice, c->stream));
+    FX_HIP(hipMemcpyAsync(m->a.carry_kp, p + L.o_kp, (size_t)r * 16, hipMemcpyHostToDevice, c->stream));
+  }
+  FX_HIP(hipEventRecord(c->snap_ev, c->stream));
   return FX_OK;
 }
 

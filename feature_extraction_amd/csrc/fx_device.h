@@ -271,8 +271,27 @@ struct FxMapLocalizeArgs {
   int32_t *near;                // the row's landmark, -1: none
   unsigned long long *d2;       // its squared xy distance as bits
 };
+// fx_map_compact (csrc/fx_map_compact.hip): a launch set's arguments.  The first group is the map's own memory, the last the
+// context's scratch, sized by the map's max_landmarks (cap).
+#define FX_MAP_COMPACT_ST_WORDS 4  // 0 K: landmarks kept, 1 observations of the dropped live landmarks, 2 absorbed landmarks dropped
+struct FxMapCompactArgs {
+  void *header;                 // fx_map_header
+  void *records;                // fx_map_landmark [cap]
+  double *acc;                  // [cap][FX_MAP_ACC]
+  int32_t *carry;               // [max_carry]
+  int32_t *alias;               // [cap]
+  uint32_t cap, max_carry;
+  uint32_t min_obs, min_age;
+  int32_t *remap;               // [cap] or null
+  uint32_t *result;             // fx_map_compact_result or null
+  uint32_t *mark;               // [cap]: 1: a carry entry resolves to the landmark; st follows it (one memset clears both)
+  uint32_t *st;                 // [FX_MAP_COMPACT_ST_WORDS]
+  int32_t *local;               // [cap]: a kept landmark's exclusive prefix within its block of 256, -1: dropped
+  uint32_t *bsum;               // [2][blocks of landmarks]: the block's kept landmarks / dropped live observations, then their prefix
+  uint4 *stage_rec, *stage_acc; // [cap][3], [cap][4]: the kept records and sums at their new ids, before they are copied back
+};
 #define FX_TRACK_NONE 0xffffffffu
-#define FX_N_HINTS 8     // tier_hint[]: 0 / 1 rings handed to the second run tier / the workgroup tier (largest XCD class), 2 big merges, 3 huge merges, 4 dense rows, 5 dense support points, 6 scans k_front handed to k_front_redo, 7 scans handed to the slow tier (k_slow)
+#define FX_N_HINTS 8    // tier_hint[]: 0 / 1 rings handed to the second run tier / the workgroup tier (largest XCD class), 2 big merges, 3 huge merges, 4 dense rows, 5 dense support points, 6 scans k_front handed to k_front_redo, 7 scans handed to the slow tier (k_slow)
 #define FX_CNT_QPOOL 32   // counters[32]: entries of the dense tier's query pool in use
 #define FX_CNT_LARGE2 16  // counters[16 + c]: rings of XCD class c the second run tier hands to the workgroup tier
 #define FX_CNT_LARGE 24  // counters[24 + c]: ... to the large tier

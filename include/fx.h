@@ -641,7 +641,8 @@ fx_status fx_track_landmarks(fx_ctx *ctx,
  * within a segment; across segments and after long drift they stay apart (no loop closure: fx_map_localize gives the pose of a scan
  * against the map, which closing one would start from).  The equality with one batch of the whole run
  * holds for min_obs == 2; with a larger min_obs a track that a batch edge cuts into pieces that are each too short is missed.
- * n_obs and n_needed are 32-bit counts.
+ * n_obs and n_needed are 32-bit counts.  FX_MAP_FULL is sticky and n_needed only rises under fx_map_update; fx_map_compact (below)
+ * gives the room of absorbed and let-go landmarks back, fx_map_export_host / fx_map_import_host carry a map to another context.
  * fx_map_create allocates all of the map's buffers and enqueues its first reset; fx_map_reset enqueues the state of a fresh map;
  * fx_map_update's scratch is a context-owned buffer that grows when a call has a larger max_landmarks.  fx_map_get returns the
  * device addresses of the header and the records (stable for the map's life; read them in stream order); fx_map_read_header and
@@ -704,7 +705,7 @@ fx_status fx_map_read_landmarks(fx_ctx *ctx, fx_map *map, uint32_t first, uint32
  * anchor are unchanged.
  * Re-pointing: every alias entry that pointed at a landmark absorbed by this call is set to that landmark's root, and every
  * carry entry >= 0 is replaced by its root, so the next fx_map_update continues the merged landmark.  The header is untouched:
- * ids are stable and never compacted, n_obs only moved.
+ * ids are stable and never compacted by this call, n_obs only moved (fx_map_compact, below, is the call that renumbers).
  * Result (when given): proposals = the h that proposed, merged = the kept links, live = the landmarks that take part after the
  * call, reserved = 0.
  * One call is one round: a fragment whose proposal was not kept (another fragment resumed the same track earlier) is picked up by
@@ -717,7 +718,8 @@ fx_status fx_map_read_landmarks(fx_ctx *ctx, fx_map *map, uint32_t first, uint32
  * Limits: merging happens within one segment only (no loop closure; fx_map_localize, below, gives the transform between a scan's
  * frame and the map's, it joins nothing).  Chained merges of one call may join A and C that are up to
  * 2 merge_dist apart, through B.  The map_id_of_row arrays of earlier batches keep the absorbed ids: resolve them through the
- * alias table (id = alias[id] >= 0 ? alias[id] : id).  A cell of the grid that holds very many fragments is searched by one lane
+ * alias table (id = alias[id] >= 0 ? alias[id] : id); the absorbed records, their sums and their alias entries stay until
+ * fx_map_compact (below) takes them out.  A cell of the grid that holds very many fragments is searched by one lane
  * a landmark: time, not the result, grows with the square of a cell's population.
  * fx_map_get_alias returns the table's device address (stable for the map's life; read it in stream order); fx_map_read_alias
  * copies entries [first, first + count) to the host and waits for the stream.  New in 0.7 (added symbols only). */
@@ -820,6 +822,76 @@ fx_status fx_map_localize(fx_ctx *ctx, fx_map *map,
     const fx_pose *prior_poses_device, uint32_t n_scans, uint32_t q_max_rows, const fx_localize_options *opt /* NULL: defaults */,
     fx_localization *out_device /* [n_scans] */, int32_t *map_id_of_row_device /* [q_max_rows] */,
     int32_t *nearest_of_row_device /* [q_max_rows] or NULL */);
+
+/* ---- Compacting the map: the absorbed fragments and the let-go landmarks taken out, the others renumbered ----
+ * fx_map_merge leaves every absorbed fragment in place: its record, its sums and its alias entry; every grid build marks and skips
+ * them, n_needed only rises, and a map that has filled with them drops new poles for good.  fx_map_compact gives the room back.  It
+ * is enqueued on the context's stream (no host synchronisation, no allocation in the steady state: its scratch is the context-owned
+ * buffer fx_map_merge uses, which grows once to the map's max_landmarks), may be called between any two other calls on the map, and
+ * moves bytes only: no floating-point operation occurs.  fx_map_get's and fx_map_get_alias's addresses stay what they were.
+ * ONE CALL, with N = header.n_landmarks and the state as it is when the call runs on the stream:
+ * Kept: landmark i < N is kept iff alias[i] == -1 and at least one of: n_obs >= min_obs; (header.scans - 1) - last_scan <
+ * min_age_scans in uint32 arithmetic (it was seen lately: it may still grow or be merged); some carry[j], j < header.carry_rows,
+ * resolves to i (carry[j] == i, or alias[carry[j]] == i: the next fx_map_update continues it).  Every other landmark is DROPPED: an
+ * absorbed one always (its observations live in its root), a live one of few observations not seen for min_age_scans scans when
+ * the caller asks for that with min_obs > 1.  With the defaults nothing live is dropped.
+ * New ids: a kept landmark's new id is the number of kept landmarks of lower old id (an exclusive prefix: ids stay the order of
+ * appearance, and every (distance, id) tie of fx_map_merge and fx_map_localize falls as before).  K = the number kept.
+ * Move: a kept landmark's 48-byte record (its FX_MAP_LM_* flags included) and its 8 accumulator doubles go to its new id byte for
+ * byte.  alias[0, max_landmarks) becomes -1.  Records and sums at [K, max_landmarks) are unspecified, as after fx_map_reset.
+ * Carry: every carry[j] >= 0, j < header.carry_rows, becomes the new id of its resolved root (alias[id] >= 0 ? alias[id] : id),
+ * which the rule above keeps; a word beyond N is written as -1.  The carry scan's rows and carry_rows are untouched: an
+ * overlap accepted after a compaction continues exactly the landmark it would have continued.
+ * header: n_landmarks = n_needed = K; n_obs is reduced by the sum of n_obs over the dropped LIVE landmarks (an absorbed one moved
+ * its observations to its root already); scans, batches, segments, flags, carry_rows, last_joined, last_new and last_pose are
+ * untouched.  FX_MAP_FULL stays (sticky): room shows as n_landmarks < max_landmarks, and the next new landmark gets the id K.
+ * remap (when given), all max_landmarks words: the new id of a kept landmark; the new id of its root for an absorbed one whose
+ * root is kept; -1 for everything else, ids >= N included.  A map_id_of_row array of an earlier batch is brought up to date by
+ * id = id >= 0 ? remap[id] : -1 alone: no alias lookup is needed.
+ * result (when given): before = N, kept = K, dropped_absorbed and dropped_live the two kinds of dropped landmarks.
+ * A map with nothing to drop is left bit for bit as it was, with remap[i] = i for i < N (but n_needed of a map that overflowed:
+ * it becomes n_landmarks).  A second call changes no byte.  The same bytes from run to run and with any number of contexts in
+ * flight: every decision is an integer prefix or a 32-bit sum.
+ * FX_ERR_INVALID_ARG with the reason in fx_last_error(), nothing launched, the map unchanged: a NULL ctx or map, a map of another
+ * context, min_obs == 0, remap_device or result_device not 4-byte aligned.
+ *
+ * The snapshot: the map's whole state (private sums, anchors, alias and carry tables and the carry scan included) as one block of
+ * host bytes, for a file or for another context on any device.  Little endian; every section starts 16-byte aligned and is zero
+ * padded to the next; sections are sized by content, with n = header.n_landmarks and r = header.carry_rows:
+ *   block header, 64 B: u32 magic 0x504D5846 ("FXMP"), u32 format 1, u32 fx_version(), u32 64 (this header's size), u32 n, u32 r,
+ *     u32 sizeof(fx_map_header) 88, u32 sizeof(fx_map_landmark) 48, u32 8 (accumulator doubles a landmark), u32 0, u64 total bytes,
+ *     16 B of zeros
+ *   the fx_map_header (88 B -> 96); records[n]; acc[n][8] doubles (Sx, Sy, Sz, ax, ay, Dx, Dy, Q of fx_map_update); alias[n] int32;
+ *   carry[r] int32; carry_kp[r], four words a row.
+ * The update's state words between launches are 0 between calls and not part of it.
+ * fx_map_export_host waits for the stream.  dst_host == NULL with capacity == 0 reports the size in *bytes_out and returns FX_OK; a
+ * capacity below the size returns FX_ERR_TOO_LARGE with the size reported and writes nothing; bytes_out may be NULL.  Only the n-
+ * and r-prefixes cross the link.
+ * fx_map_snapshot_check is host only and needs no device.  FX_ERR_INVALID_ARG with the reason in fx_last_error() when one of these
+ * fails: the magic, the format, the block header's size and the three struct sizes, the total against `bytes` and against the sum
+ * of the sections; n == the block's header.n_landmarks and r == its header.carry_rows; n_landmarks <= n_needed; every alias word in
+ * [-1, n) and fully resolved (alias[alias[i]] == -1); every carry word in [-1, n).  FX_ERR_TOO_LARGE when n > max_landmarks or r >
+ * max_carry_rows.  A block with n_needed > n_landmarks (the map overflowed) is refused (FX_ERR_INVALID_ARG) unless max_landmarks
+ * == n_landmarks: in a larger map the next landmark would be numbered past a hole; fx_map_compact first, which sets n_needed =
+ * n_landmarks.
+ * fx_map_import_host runs the check against the target's max_landmarks and max_carry_rows; on failure the target is bit for bit
+ * unchanged and nothing is enqueued.  On success it enqueues, on the stream, a reset (alias -1, state words 0) and the copies of
+ * the sections; the bytes are staged in context-owned pinned memory before the call returns, so src_host may be freed at once.
+ * Afterwards every call (fx_map_update with overlap, merge, localize, compact, export) behaves bit for bit as on the source map;
+ * the target may be larger than the source and may live on another context or device.  Export and import also return
+ * FX_ERR_INVALID_ARG for a NULL ctx, map or src_host, dst_host == NULL with capacity != 0, and a map of another context.  New in
+ * 0.7 (added symbols only). */
+typedef struct fx_map_compact_options {
+  uint32_t min_obs;        /* a live landmark of fewer observations may be dropped (see above); >= 1; default 1: drop nothing live */
+  uint32_t min_age_scans;  /* ... but only when it was last seen at least this many scans ago; default 64 (fx_map_merge's max_gap_scans) */
+} fx_map_compact_options;
+typedef struct fx_map_compact_result { uint32_t before, kept, dropped_absorbed, dropped_live; } fx_map_compact_result; /* 16 B */
+void fx_map_compact_options_default(fx_map_compact_options *o);
+fx_status fx_map_compact(fx_ctx *ctx, fx_map *map, const fx_map_compact_options *opt /* NULL: defaults */,
+                         int32_t *remap_device /* [max_landmarks] or NULL */, fx_map_compact_result *result_device /* or NULL */);
+fx_status fx_map_export_host(fx_ctx *ctx, fx_map *map, void *dst_host, size_t capacity, size_t *bytes_out);
+fx_status fx_map_import_host(fx_ctx *ctx, fx_map *map, const void *src_host, size_t bytes);
+fx_status fx_map_snapshot_check(const void *src_host, size_t bytes, uint32_t max_landmarks, uint32_t max_carry_rows); /* Host only */
 
 /* Rotation matrix of rotateCloud (ref: node.cpp:161-164): R = Ry(pitch)*Rx(roll)
  * through Eigen's AngleAxisf -> Quaternionf -> toRotationMatrix, all float. Host only. */

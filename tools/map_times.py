@@ -21,6 +21,14 @@ of the landmarks the first fragment of a pole (scans 0-1) and one third a second
 (the call that does the work: N / 3 proposals, links and folds) and merges again (the fixpoint: the grid and the search, nothing to
 fold); each call sits between its own pair of HIP events.  Reported per size: the medians, and the ratio of the merge time to the
 size before; the requirement is time(10^6) <= 15 x time(10^5).
+
+  timeout -k 10 600 python tools/map_times.py --compact [--sizes 1000,100000,1000000] [--warmup 1] [--repeats 5] [--out profiles/map_compact_times.txt]
+
+times fx_map_compact on the same synthetic maps after their one merge (a third of the landmarks absorbed).  Every repeat resets the
+map, updates it, merges, merges again on the fixpoint (timed: the grid and the search over N records, a third of them dead),
+compacts (timed: one pair of HIP events around the call) and merges once more on the compacted map (timed: the same grid and search
+over the 2 N / 3 live records).  Reported per size: the medians, the ratio of the compaction time to the size before (the merge's
+requirement applies: time(10^6) <= 15 x time(10^5)) and the fixpoint merge after over before.
 """
 import argparse
 import ctypes as C
@@ -189,6 +197,74 @@ def measure_merge(ctx, n, warmup, repeats):
     return out
 
 
+def measure_compact(ctx, n, warmup, repeats):
+    import torch
+    blk, (S, T), m, inl, reg, M = merge_case(n, np.random.default_rng(n))
+    kp = (torch.from_numpy(blk).cuda(), S, T)
+    md, inl_t = torch.from_numpy(m.view(np.int32).reshape(-1, 8).copy()).cuda(), torch.from_numpy(inl).cuda()
+    reg_t = torch.from_numpy(reg.view(np.float64).reshape(-1, 8).copy()).cuda()
+    out = ctx.track_landmarks(kp, md, inl_t, reg_t, S, max_landmarks=n)
+    mp = ctx.map_create(n, 16)
+    res, cres = (torch.zeros((4,), dtype=torch.int32, device="cuda") for _ in range(2))
+    remap = torch.empty((n,), dtype=torch.int32, device="cuda")
+    stream = torch.cuda.ExternalStream(ctx.stream_ptr())
+    torch.cuda.synchronize()
+    t = {"fixpoint_before_ms": [], "compact_ms": [], "fixpoint_after_ms": []}
+    first = None
+    for rep in range(warmup + repeats):
+        mp.reset()
+        mp.update(kp, out, overlap=False, row_ids=False)
+        mp.merge(result=res)
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
+        e[0].record(stream)
+        mp.merge(result=res)
+        e[1].record(stream), e[2].record(stream)
+        mp.compact(remap=remap, result=cres)
+        e[3].record(stream), e[4].record(stream)
+        mp.merge(result=res)
+        e[5].record(stream)
+        ctx.synchronize()
+        got = cres.cpu().numpy().tolist() + res.cpu().numpy().tolist()
+        first = first or got
+        assert got == first and got[5] == 0 and got[1] == got[6], (got, first)  # (nothing merges on the fixpoint; live == kept)
+        if rep >= warmup:
+            for k, (a, b) in zip(t, ((0, 1), (2, 3), (4, 5))):
+                t[k].append(e[a].elapsed_time(e[b]))
+    hdr = mp.header()
+    mp.close()
+    out = {"landmarks": n, "after": hdr["n_landmarks"], "result": dict(zip(capi.MAP_COMPACT_RESULT_FIELDS, first[:4]))}
+    for k, v in t.items():
+        out[k] = statistics.median(v)
+        out[k + "_min_max"] = [min(v), max(v)]
+    return out
+
+
+def main_compact(a):
+    sizes = [int(x) for x in a.sizes.split(",")]
+    ctx = capi.Context(capi.params("launch"), capi.limits(2, 1024))
+    rows = [measure_compact(ctx, n, a.warmup, a.repeats) for n in sizes]
+    ctx.close()
+    lines = [f"fx_map_compact on synthetic maps after one fx_map_merge (tools/map_times.py --compact): 1 pole per 250 m^2, a third of the",
+             f"landmarks absorbed; one context, HIP events around each call, median of {a.repeats} after {a.warmup} warm-up; ms.  fixpoint: fx_map_merge on",
+             f"the merged map (nothing left to merge: the grid build and the search), before and after the compaction",
+             f"{'landmarks':>10} {'kept':>8} {'absorbed':>9} {'compact':>9} {'compact / size before':>21} {'fixpoint before':>16} {'fixpoint after':>15} {'after / before':>15}"]
+    for k, r in enumerate(rows):
+        ratio = f"{r['compact_ms'] / rows[k - 1]['compact_ms']:.2f}" if k else "-"
+        lines.append(f"{r['landmarks']:>10} {r['result']['kept']:>8} {r['result']['dropped_absorbed']:>9} {r['compact_ms']:>9.3f} {ratio:>21} "
+                     f"{r['fixpoint_before_ms']:>16.3f} {r['fixpoint_after_ms']:>15.3f} {r['fixpoint_after_ms'] / r['fixpoint_before_ms']:>15.2f}")
+    by = {r["landmarks"]: r for r in rows}
+    if 100000 in by and 1000000 in by:
+        ratio = by[1000000]["compact_ms"] / by[100000]["compact_ms"]
+        lines.append(f"requirement: compact(10^6) <= 15 x compact(10^5): {ratio:.2f} x, {'met' if ratio <= 15.0 else 'NOT met'}")
+    s = "\n".join(lines)
+    print(s)
+    print(json.dumps(rows))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(s + "\n")
+
+
 def main_merge(a):
     sizes = [int(x) for x in a.sizes.split(",")]
     ctx = capi.Context(capi.params("launch"), capi.limits(2, 1024))
@@ -212,6 +288,7 @@ def main_merge(a):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--merge", action="store_true", help="time fx_map_merge on synthetic maps instead")
+    ap.add_argument("--compact", action="store_true", help="time fx_map_compact on the merged synthetic maps instead")
     ap.add_argument("--sizes", default="1000,100000,1000000")
     ap.add_argument("--scans", type=int, default=1024)
     ap.add_argument("--batch", type=int, default=128)
@@ -224,6 +301,8 @@ def main():
         raise SystemExit("no GPU: device times are measured on the GPU or not at all")
     if a.merge:
         return main_merge(a)
+    if a.compact:
+        return main_compact(a)
     N = 28800
     ctx = capi.Context(capi.params("launch"), capi.limits(a.batch, N, sparse=True))
     scenes = np.stack([capi.synth_scan(capi.synth_cfg(1000 + b)) for b in range(a.scans)])
