@@ -228,6 +228,28 @@ LOC_DEFAULTS = dict(search_dist=2.0, inlier_dist=0.30, min_baseline=2.0, hyp_cor
                     segment=FX_LOC_LAST_SEGMENT)
 
 
+class FxRelocalizeOptions(C.Structure):
+    _fields_ = [("inlier_dist", C.c_float), ("pair_tol", C.c_float), ("min_baseline", C.c_float), ("max_baseline", C.c_float),
+                ("max_seeds", C.c_uint32), ("min_inliers", C.c_uint32), ("min_margin", C.c_uint32), ("min_landmark_obs", C.c_uint32),
+                ("segment", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class FxRelocalization(C.Structure):
+    _fields_ = [("pose", FxPose), ("n_hyp", C.c_uint64), ("n_kp", C.c_uint32), ("n_seeds", C.c_uint32), ("score", C.c_uint32),
+                ("runner_up", C.c_uint32), ("flags", C.c_uint32), ("seed_a", C.c_uint32), ("seed_b", C.c_uint32), ("lm_a", C.c_uint32),
+                ("lm_b", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+FX_RELOC_MAX_KP = 64
+FX_RELOC_VALID, FX_RELOC_TRUNCATED, FX_RELOC_NO_HYPOTHESIS, FX_RELOC_AMBIGUOUS, FX_RELOC_NO_SCAN = 0x1, 0x2, 0x4, 0x8, 0x10
+FX_RELOC_NONE = 0xffffffff
+# fx_relocalization as numpy records (relocalize_records); "pose" is a POSE_DTYPE record
+RELOC_DTYPE = np.dtype([("pose", POSE_DTYPE), ("n_hyp", "<u8"), ("n_kp", "<u4"), ("n_seeds", "<u4"), ("score", "<u4"), ("runner_up", "<u4"),
+                        ("flags", "<u4"), ("seed_a", "<u4"), ("seed_b", "<u4"), ("lm_a", "<u4"), ("lm_b", "<u4"), ("reserved", "<u4")])
+RELOC_DEFAULTS = dict(inlier_dist=0.30, pair_tol=0.30, min_baseline=2.0, max_baseline=60.0, max_seeds=16, min_inliers=4, min_margin=1,
+                      min_landmark_obs=2, segment=FX_LOC_ANY_SEGMENT)
+
+
 class FxTimings(C.Structure):
     _fields_ = [("ms", C.c_float * FX_N_STAGES), ("total_ms", C.c_float), ("k_prep_exec_ms", C.c_float)]
 
@@ -253,7 +275,7 @@ EXPORTS = ("fx_version", "fx_check_abi", "fx_status_str", "fx_last_error", "fx_p
            "fx_track_options_default", "fx_track_landmarks",
            "fx_map_create", "fx_map_destroy", "fx_map_reset", "fx_map_update", "fx_map_get", "fx_map_read_header", "fx_map_read_landmarks",
            "fx_map_merge_options_default", "fx_map_merge", "fx_map_get_alias", "fx_map_read_alias",
-           "fx_localize_options_default", "fx_map_localize",
+           "fx_localize_options_default", "fx_map_localize", "fx_relocalize_options_default", "fx_map_relocalize",
            "fx_map_compact_options_default", "fx_map_compact", "fx_map_export_host", "fx_map_import_host", "fx_map_snapshot_check",
            "fx_rotation_from_roll_pitch", "fx_sc3d_tables", "fx_sc3d_xaxis", "fx_synth_cfg_vlp16",
            "fx_synth_scan", "fx_unpack_pointcloud2", "fx_pack_pointxyzi")
@@ -387,6 +409,10 @@ def load():
     lib.fx_localize_options_default.restype = None
     lib.fx_map_localize.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
                                     C.POINTER(FxLocalizeOptions), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.fx_relocalize_options_default.argtypes = [C.POINTER(FxRelocalizeOptions)]
+    lib.fx_relocalize_options_default.restype = None
+    lib.fx_map_relocalize.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                      C.POINTER(FxRelocalizeOptions), C.c_void_p, C.c_void_p]
     lib.fx_map_compact_options_default.argtypes = [C.POINTER(FxMapCompactOptions)]
     lib.fx_map_compact_options_default.restype = None
     lib.fx_map_compact.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(FxMapCompactOptions), C.c_void_p, C.c_void_p]
@@ -1384,6 +1410,166 @@ def map_localize_reference(state, kp_offset, kp_rows, prior_poses, n_scans, q_ma
     return {"rec": rec, "map_id_of_row": map_id, "nearest_of_row": nearest, "corr": corrs}
 
 
+# ---- a scan's pose in the map without a prior (include/fx.h fx_map_relocalize)
+def relocalize_records(out):
+    """A host copy of fx_map_relocalize's records (a torch tensor, or any array of n * 96 bytes) as RELOC_DTYPE records."""
+    if hasattr(out, "detach"):
+        out = out.detach().cpu().numpy()
+    return np.ascontiguousarray(out).view(np.uint8).reshape(-1).view(RELOC_DTYPE).copy()
+
+
+def map_relocalize_reference(state, kp_offset, kp_rows, n_scans, q_max_rows=None, inlier_dist=0.30, pair_tol=0.30, min_baseline=2.0,
+                             max_baseline=60.0, max_seeds=16, min_inliers=4, min_margin=1, min_landmark_obs=2, segment=FX_LOC_ANY_SEGMENT):
+    """The definition of fx_map_relocalize (include/fx.h) in numpy float64 over a map_reference / map_merge_reference state (which is
+    only read).  kp_offset / kp_rows / q_max_rows as in map_localize_reference.  Every (seed, g, h) and every (keypoint, landmark)
+    pair is looked at: nothing here knows of a grid.  One ufunc an operation, so nothing is contracted.  Returns {"rec": RELOC_DTYPE
+    [n_scans], "map_id_of_row": int32 [q_max_rows], "hyp": per scan the hypotheses as a dict of arrays s, g, h, score in
+    (s, g, h) order}."""
+    f64 = np.float64
+    off = [int(x) for x in kp_offset]
+    kp = np.ascontiguousarray(kp_rows, dtype=np.float32)
+    kp = kp.reshape(len(kp), -1)[:, :3] if kp.size else np.zeros((0, 3), np.float32)
+    n_scans = int(n_scans)
+    R = len(kp) if q_max_rows is None else int(q_max_rows)
+    id32, pt32, mb32, xb32 = np.float32(inlier_dist), np.float32(pair_tol), np.float32(min_baseline), np.float32(max_baseline)
+    if not (n_scans >= 1 and all(np.isfinite(v) and v > 0 for v in (id32, pt32, mb32)) and np.isfinite(xb32) and xb32 >= mb32 and
+            1 <= max_seeds <= FX_RELOC_MAX_KP and min_inliers >= 3 and min_margin >= 1 and min_landmark_obs >= 1):
+        raise ValueError("arguments outside what fx_map_relocalize accepts")
+    idd, ptd, mbd, xbd = f64(id32), f64(pt32), f64(mb32), f64(xb32)
+    id2, mb2, xb2, half = idd * idd, mbd * mbd, xbd * xbd, f64(0.5)
+    two = f64(2.0) * idd
+    g2 = two * two
+    S, rows = min(n_scans, len(off) - 1), min(len(kp), R)
+    # the eligible landmarks (fx_map_localize's clause)
+    lms = state["landmarks"]
+    N = min(int(state["header"]["n_landmarks"]), len(lms))
+    alias = [int(a) for a in state.get("alias", [])][:N]
+    alias += [-1] * (N - len(alias))
+    lx, ly, lz = (np.array([float(r[f]) for r in lms[:N]], f64) for f in ("x", "y", "z"))
+    want = int(segment) & 0xffffffff
+    if want == FX_LOC_LAST_SEGMENT:
+        want = int(state["header"]["segments"]) - 1  # (-1 in a map of no segment: nothing is eligible)
+    elig = np.array([alias[g] == -1 and int(lms[g]["n_obs"]) >= min_landmark_obs and (want == FX_LOC_ANY_SEGMENT or int(lms[g]["segment"]) == want)
+                     for g in range(N)], bool)
+    if N:
+        elig &= np.isfinite(lx) & np.isfinite(ly) & np.isfinite(lz)
+    ids = np.flatnonzero(elig)
+    ex, ey, ez = lx[ids], ly[ids], lz[ids]
+    E = len(ids)
+    rec = np.zeros(n_scans, RELOC_DTYPE)
+    rec["pose"]["c"] = 1.0
+    for f in ("seed_a", "seed_b", "lm_a", "lm_b"):
+        rec[f] = FX_RELOC_NONE
+    map_id = np.full(R, -1, np.int32)
+    hyps = []
+
+    def landed(wx, wy):
+        """[..., E] -> does the image land on an eligible landmark; chunked over the leading axis"""
+        out = np.zeros(wx.shape, bool)
+        if not E:
+            return out
+        step = max(1, (1 << 22) // max(1, wx.shape[1] * E))
+        for lo_ in range(0, wx.shape[0], step):
+            dx, dy = ex[None, None, :] - wx[lo_:lo_ + step, :, None], ey[None, None, :] - wy[lo_:lo_ + step, :, None]
+            out[lo_:lo_ + step] = (dx * dx + dy * dy <= id2).any(axis=2)
+        return out
+
+    with np.errstate(all="ignore"):
+        for b in range(n_scans):
+            empty = {k: np.zeros(0, np.int64) for k in ("s", "g", "h", "score")}
+            if b >= S:
+                rec["flags"][b] = FX_RELOC_NO_SCAN
+                hyps.append(empty)
+                continue
+            lo = min(off[b], rows)
+            hi = max(min(off[b + 1], rows), lo)
+            fin = np.flatnonzero(np.isfinite(kp[lo:hi]).all(axis=1)) + lo
+            flags = FX_RELOC_TRUNCATED if len(fin) > FX_RELOC_MAX_KP else 0
+            used = fin[:FX_RELOC_MAX_KP]
+            n_kp = len(used)
+            x, y, z = (kp[used, k].astype(f64) for k in range(3))
+            rec["n_kp"][b] = n_kp
+            # seeds
+            a, c_ = np.triu_indices(n_kp, 1)  # lexicographic (a, b), a < b
+            dx, dy = x[c_] - x[a], y[c_] - y[a]
+            d2 = dx * dx + dy * dy
+            cand = np.flatnonzero((mb2 <= d2) & (d2 <= xb2))
+            order = cand[np.lexsort((cand, ~d2[cand].view(np.uint64)))]  # descending d2 bits, then ascending (a, b)
+            seeds = order[:int(max_seeds)]
+            rec["n_seeds"][b] = len(seeds)
+            # hypotheses: (s, g, h) in ascending order, g and h as positions in ids
+            parts = []
+            for s_rank, k in enumerate(seeds):
+                if E < 2:
+                    break
+                xa, ya, xb_, yb_ = x[a[k]], y[a[k]], x[c_[k]], y[c_[k]]
+                dqx, dqy = xb_ - xa, yb_ - ya
+                dtx, dty = ex[None, :] - ex[:, None], ey[None, :] - ey[:, None]  # [g, h]: B.z - A.z
+                lq2, lt2 = dqx * dqx + dqy * dqy, dtx * dtx + dty * dty
+                keep = (lq2 >= mb2) & (lt2 >= mb2)
+                keep &= ~(np.abs(np.sqrt(lq2) - np.sqrt(lt2)) > ptd)
+                keep &= ~np.eye(E, dtype=bool)
+                gi, hi_ = np.nonzero(keep)  # (row-major: ascending (g, h))
+                dtx, dty = dtx[gi, hi_], dty[gi, hi_]
+                dot, crs = dqx * dtx + dqy * dty, dqx * dty - dqy * dtx
+                nrm = np.sqrt(dot * dot + crs * crs)
+                ok = nrm > 0
+                gi, hi_, dot, crs, nrm = gi[ok], hi_[ok], dot[ok], crs[ok], nrm[ok]
+                c, s = dot / nrm, crs / nrm
+                mqx, mqy = (xa + xb_) * half, (ya + yb_) * half
+                mtx, mty = (ex[gi] + ex[hi_]) * half, (ey[gi] + ey[hi_]) * half
+                tx, ty = mtx - (c * mqx - s * mqy), mty - (s * mqx + c * mqy)
+                wx = (c[:, None] * x[None, :] - s[:, None] * y[None, :]) + tx[:, None]
+                wy = (s[:, None] * x[None, :] + c[:, None] * y[None, :]) + ty[:, None]
+                score = landed(wx, wy).sum(axis=1)
+                parts.append((np.full(len(gi), s_rank), gi, hi_, score, c, s, tx, ty))
+            if parts:
+                hs, hg, hh, hscore, hc, hsn, htx, hty = (np.concatenate([p[k] for p in parts]) for k in range(8))
+            else:
+                hs = hg = hh = hscore = np.zeros(0, np.int64)
+                hc = hsn = htx = hty = np.zeros(0, f64)
+            rec["n_hyp"][b] = len(hs)
+            hyps.append({"s": hs, "g": ids[hg] if len(hg) else hg, "h": ids[hh] if len(hh) else hh, "score": hscore})
+            if not len(hs) or hscore.max() < 2:
+                rec["flags"][b] = flags | FX_RELOC_NO_HYPOTHESIS
+                continue
+            w = int(np.argmax(hscore))  # (the first maximum: the lowest (s, g, h))
+            wc, ws, wtx, wty = hc[w], hsn[w], htx[w], hty[w]
+            # rivals: the winner's seed keypoints under every hypothesis against under the winner
+            ka, kb = a[seeds[hs[w]]], c_[seeds[hs[w]]]
+            rival = np.zeros(len(hs), bool)
+            for q in (ka, kb):
+                ux, uy = (hc * x[q] - hsn * y[q]) + htx, (hsn * x[q] + hc * y[q]) + hty
+                vx, vy = (wc * x[q] - ws * y[q]) + wtx, (ws * x[q] + wc * y[q]) + wty
+                rx, ry = ux - vx, uy - vy
+                rival |= rx * rx + ry * ry > g2
+            runner = int(hscore[rival].max()) if rival.any() else 0
+            # the landmark of every keypoint under the winner: lowest (d2 bits, id) in reach
+            wx, wy = (wc * x - ws * y) + wtx, (ws * x + wc * y) + wty
+            dx, dy = ex[None, :] - wx[:, None], ey[None, :] - wy[:, None]
+            d2 = dx * dx + dy * dy
+            key = np.where(d2 <= id2, d2, np.inf).view(np.uint64)
+            j = np.argmin(key, axis=1)  # (the first minimum: ids ascend)
+            hit = d2[np.arange(n_kp), j] <= id2
+            score = int(hit.sum())
+            assert score == int(hscore[w])
+            sz = 0.0
+            for k in np.flatnonzero(hit):
+                sz += (float(ez[j[k]]) - float(z[k]))
+            P = rec["pose"]
+            P["c"][b], P["s"][b], P["tx"][b], P["ty"][b], P["tz"][b] = wc, ws, wtx, wty, sz / float(score)
+            P["segment"][b] = int(lms[int(ids[hg[w]])]["segment"])
+            rec["score"][b], rec["runner_up"][b] = score, runner
+            rec["seed_a"][b], rec["seed_b"][b] = used[ka], used[kb]
+            rec["lm_a"][b], rec["lm_b"][b] = ids[hg[w]], ids[hh[w]]
+            if score >= min_inliers:
+                flags |= FX_RELOC_VALID if score - runner >= min_margin else FX_RELOC_AMBIGUOUS
+            rec["flags"][b] = flags
+            if flags & FX_RELOC_VALID:
+                map_id[used[hit]] = ids[j[hit]]
+    return {"rec": rec, "map_id_of_row": map_id, "hyp": hyps}
+
+
 def _np(ptr, shape, dtype):
     n = int(np.prod(shape))
     if n == 0 or not ptr:
@@ -1497,6 +1683,38 @@ class Map:
                                        C.c_void_p(ids.data_ptr() if n_rows else None), C.c_void_p(nearest.data_ptr() if nearest is not None and n_rows else None)))
         cur.wait_stream(ext)
         return recs, ids, nearest
+
+    def relocalize(self, kp, n_scans, q_max_rows=None, out=None, **opts):
+        """fx_map_relocalize: the pose of the scans of the keypoint block kp = (device tensor, max_scans, max_total_keypoints) in this
+        map, without a prior.  opts: the fields of fx_relocalize_options (RELOC_DEFAULTS).  Returns (records, map_id_of_row): device
+        tensors of n_scans * 96 bytes (relocalize_records reads them; the first 48 bytes of a record are the fx_pose localize() takes
+        as a prior) and torch.int32 [q_max_rows]; out = (records, map_id_of_row) reuses two.  Stream-correct like update(); never
+        waits for the stream."""
+        import torch
+        kb, scans, total = kp
+        dev = torch.device("cuda", self.ctx.device)
+        n_scans = int(n_scans)
+        n_rows = int(total) if q_max_rows is None else int(q_max_rows)
+        bad = set(opts) - set(RELOC_DEFAULTS)
+        if bad:
+            raise TypeError(f"unknown relocalize options {sorted(bad)}")
+        o = dict(RELOC_DEFAULTS, **opts)
+        opt = FxRelocalizeOptions(float(o["inlier_dist"]), float(o["pair_tol"]), float(o["min_baseline"]), float(o["max_baseline"]),
+                                  int(o["max_seeds"]), int(o["min_inliers"]), int(o["min_margin"]), int(o["min_landmark_obs"]),
+                                  int(o["segment"]) & 0xffffffff, 0)
+        if out is None:
+            out = (torch.empty((n_scans, RELOC_DTYPE.itemsize // 8), dtype=torch.float64, device=dev), torch.empty((n_rows,), dtype=torch.int32, device=dev))
+        recs, ids = out
+        for t, size in ((recs, n_scans * RELOC_DTYPE.itemsize), (ids, n_rows * 4)):
+            if t.device != dev or not t.is_contiguous() or t.numel() * t.element_size() != size:
+                raise ValueError(f"outputs must be contiguous tensors of {n_scans} * 96 and {n_rows} * 4 bytes on {dev}")
+        cur = torch.cuda.current_stream(dev)
+        ext = torch.cuda.ExternalStream(self.ctx.stream_ptr(), device=dev)
+        ext.wait_stream(cur)
+        check(self.lib.fx_map_relocalize(self.ctx.handle, self.handle, C.c_void_p(kb.data_ptr()), int(scans), int(total), n_scans, n_rows,
+                                         C.byref(opt), C.c_void_p(recs.data_ptr()), C.c_void_p(ids.data_ptr() if n_rows else None)))
+        cur.wait_stream(ext)
+        return recs, ids
 
     def compact(self, min_obs=1, min_age_scans=64, remap=None, result=None):
         """fx_map_compact: the absorbed and the let-go landmarks taken out, the others renumbered in order (include/fx.h).  Returns

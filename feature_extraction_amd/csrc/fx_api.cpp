@@ -93,6 +93,8 @@ size_t fxk_map_merge_scratch(FxMapMergeArgs *A, uint8_t *base);
 uint32_t fxk_map_merge_wg(void);
 hipError_t fxk_map_localize(hipStream_t s, const FxMapLocalizeArgs &A);
 size_t fxk_map_localize_scratch(FxMapLocalizeArgs *A, uint8_t *base);
+hipError_t fxk_map_relocalize(hipStream_t s, const FxMapRelocalizeArgs &A);
+size_t fxk_map_relocalize_scratch(FxMapRelocalizeArgs *A, uint8_t *base);
 hipError_t fxk_map_compact(hipStream_t s, const FxMapCompactArgs &A);
 size_t fxk_map_compact_scratch(FxMapCompactArgs *A, uint8_t *base);
 #ifdef FX_TEST_HOOKS
@@ -1977,6 +1979,68 @@ fx_status fx_map_localize(fx_ctx *c, fx_map *m, const void *kp, uint32_t max_sca
   FX_TRY(c->merge_scratch.reserve(c, fxk_map_localize_scratch(&A, nullptr), "map localize scratch"));
   (void)fxk_map_localize_scratch(&A, c->merge_scratch.d);
   FX_HIP(fxk_map_localize(c->stream, A));
+  return FX_OK;
+}
+
+void fx_relocalize_options_default(fx_relocalize_options *o) {
+  if (!o) return;
+  o->inlier_dist = 0.30f;
+  o->pair_tol = 0.30f;
+  o->min_baseline = 2.0f;
+  o->max_baseline = 60.0f;
+  o->max_seeds = 16u;
+  o->min_inliers = 4u;
+  o->min_margin = 1u;
+  o->min_landmark_obs = 2u;
+  o->segment = FX_LOC_ANY_SEGMENT;
+  o->reserved = 0u;
+}
+
+fx_status fx_map_relocalize(fx_ctx *c, fx_map *m, const void *kp, uint32_t max_scans, uint32_t max_total, uint32_t n_scans, uint32_t q_max_rows,
+                            const fx_relocalize_options *opt, fx_relocalization *out, int32_t *map_id_of_row) {
+  if (!c || !m) return fail(FX_ERR_INVALID_ARG, "null argument");
+  if (m->ctx != c) return fail(FX_ERR_INVALID_ARG, "the map belongs to another context");
+  if (!n_scans || n_scans > max_scans)
+    return fail(FX_ERR_INVALID_ARG, "n_scans must be 1..max_scans (" + std::to_string(n_scans) + " of " + std::to_string(max_scans) + ")");
+  if (!kp || !out || (q_max_rows && !map_id_of_row)) return fail(FX_ERR_INVALID_ARG, "null argument");
+  if (((uintptr_t)kp % 16) != 0 || ((uintptr_t)out % 8) != 0 || ((uintptr_t)map_id_of_row % 4) != 0)
+    return fail(FX_ERR_INVALID_ARG, "the keypoint block must be 16-byte, the records 8-byte, the words 4-byte aligned");
+  fx_relocalize_options o;
+  fx_relocalize_options_default(&o);
+  if (opt) o = *opt;
+  auto positive = [](float v) { return std::isfinite(v) && v > 0.f; };
+  if (!positive(o.inlier_dist)) return fail(FX_ERR_INVALID_ARG, "inlier_dist must be finite and positive");
+  if (!positive(o.pair_tol)) return fail(FX_ERR_INVALID_ARG, "pair_tol must be finite and positive");
+  if (!positive(o.min_baseline)) return fail(FX_ERR_INVALID_ARG, "min_baseline must be finite and positive");
+  if (!(std::isfinite(o.max_baseline) && o.max_baseline >= o.min_baseline))
+    return fail(FX_ERR_INVALID_ARG, "max_baseline must be finite and at least min_baseline");
+  if (o.max_seeds < 1u || o.max_seeds > FX_RELOC_MAX_KP) return fail(FX_ERR_INVALID_ARG, "max_seeds must be 1..64");
+  if (o.min_inliers < 3u) return fail(FX_ERR_INVALID_ARG, "min_inliers must be at least 3");
+  if (!o.min_margin) return fail(FX_ERR_INVALID_ARG, "min_margin must be at least 1");
+  if (!o.min_landmark_obs) return fail(FX_ERR_INVALID_ARG, "min_landmark_obs must be at least 1");
+  if (o.reserved) return fail(FX_ERR_INVALID_ARG, "reserved must be 0");
+  FX_HIP(hipSetDevice(c->device));
+  FxMapRelocalizeArgs A{};
+  for (FxMapMergeArgs *G : {&A.P, &A.Q}) {
+    G->header = m->a.header, G->records = m->a.records, G->acc = m->a.acc, G->carry = m->a.carry, G->alias = m->a.alias;
+    G->cap = m->a.cap, G->max_carry = m->a.max_carry;
+    G->table = fxk_map_merge_table(G->cap);
+  }
+  // the two gates in fp64 and the grids' cell edges, gate (1 + 2^-8) (csrc/fx_map_grid.h proves the margin; csrc/fx_map_relocalize.hip
+  // derives the pair grid's gate (xb + pt)(1 + 2^-20) from the hypothesis's length gate)
+  const double pd = ((double)o.max_baseline + (double)o.pair_tol) * (1.0 + 1.0 / 1048576.0), id = (double)o.inlier_dist;
+  A.P.md2 = pd * pd, A.P.inv_edge = 1.0 / (pd * (1.0 + 1.0 / 256.0));
+  A.Q.md2 = id * id, A.Q.inv_edge = 1.0 / (id * (1.0 + 1.0 / 256.0));
+  A.kp = (const uint32_t *)kp, A.max_scans = max_scans, A.max_total = max_total;
+  A.n_scans = n_scans, A.q_max_rows = q_max_rows;
+  A.inlier_dist = o.inlier_dist, A.pair_tol = o.pair_tol, A.min_baseline = o.min_baseline, A.max_baseline = o.max_baseline;
+  A.max_seeds = o.max_seeds, A.min_inliers = o.min_inliers, A.min_margin = o.min_margin, A.min_landmark_obs = o.min_landmark_obs;
+  A.segment = o.segment;
+  A.chunks = (A.P.cap + FXR_CHUNK - 1u) / FXR_CHUNK;
+  A.out = out, A.map_id_of_row = map_id_of_row;
+  FX_TRY(c->merge_scratch.reserve(c, fxk_map_relocalize_scratch(&A, nullptr), "map relocalize scratch"));
+  (void)fxk_map_relocalize_scratch(&A, c->merge_scratch.d);
+  FX_HIP(fxk_map_relocalize(c->stream, A));
   return FX_OK;
 }
 

@@ -271,6 +271,39 @@ struct FxMapLocalizeArgs {
   int32_t *near;                // the row's landmark, -1: none
   unsigned long long *d2;       // its squared xy distance as bits
 };
+// fx_map_relocalize (csrc/fx_map_relocalize.hip): a launch set's arguments.  P and Q describe the two grids over the map, alive
+// together in the context's scratch (the merge's per-landmark arrays are null in both): P, the pair grid, finds the landmarks h
+// whose distance from g can pass the length gate of a seed; Q, the score grid, the landmark a keypoint's image lands on.  The last
+// group is the context's scratch.
+#define FXR_CHUNK 256  // pair-grid slots a workgroup of the hypothesis kernel takes, a lane each
+struct FxRelocPartial {         // the best hypothesis of one workgroup: 16 B
+  uint32_t score, g, h, pad_;
+};
+struct FxRelocWinner {          // the winner of a scan: 48 B
+  uint32_t score, seed, g, h;   // score 0: no winner
+  double c, s, tx, ty;
+};
+struct FxMapRelocalizeArgs {
+  FxMapMergeArgs P, Q;
+  const uint32_t *kp;           // keypoint block (include/fx.h fx_pack_keypoint_block)
+  uint32_t max_scans, max_total;
+  uint32_t n_scans, q_max_rows;
+  float inlier_dist, pair_tol, min_baseline, max_baseline;
+  uint32_t max_seeds, min_inliers, min_margin, min_landmark_obs, segment;
+  uint32_t chunks;              // workgroups of the hypothesis kernel a (scan, seed): ceil(cap / FXR_CHUNK)
+  uint32_t scan0;               // the hypothesis kernel's first scan (a launch takes 65535 scans)
+  void *out;                    // fx_relocalization [n_scans]
+  int32_t *map_id_of_row;       // [q_max_rows]
+  uint8_t *elig;                // [cap]: 1, the landmark is eligible
+  double *kq;                   // [n_scans][64][3]: the used keypoints of a scan, widened
+  uint32_t *krow;               // [n_scans][64]: their rows
+  uint32_t *meta;               // [n_scans][4]: n_kp, n_seeds, FX_RELOC_TRUNCATED or 0, 0
+  uint32_t *seeds;              // [n_scans][64]: a | b << 8 of seed rank s
+  unsigned long long *n_hyp;    // [n_scans]
+  uint32_t *runner;             // [n_scans]: the best rival's score (atomic max)
+  FxRelocPartial *partial;      // [n_scans][max_seeds][chunks]
+  FxRelocWinner *win;           // [n_scans]
+};
 // fx_map_compact (csrc/fx_map_compact.hip): a launch set's arguments.  The first group is the map's own memory, the last the
 // context's scratch, sized by the map's max_landmarks (cap).
 #define FX_MAP_COMPACT_ST_WORDS 4  // 0 K: landmarks kept, 1 observations of the dropped live landmarks, 2 absorbed landmarks dropped

@@ -638,8 +638,8 @@ fx_status fx_track_landmarks(fx_ctx *ctx,
  * only, or and sum), every fp64 value an ordered chain of correctly rounded operations on one lane.
  * Limits: tracks are continued only across an accepted one-scan overlap; a pole seen again after a missed detection, a bad link or
  * after leaving the field of view enters as a new landmark.  fx_map_merge (below) folds such fragments back into one landmark
- * within a segment; across segments and after long drift they stay apart (no loop closure: fx_map_localize gives the pose of a scan
- * against the map, which closing one would start from).  The equality with one batch of the whole run
+ * within a segment; across segments and after long drift they stay apart (no loop closure: fx_map_relocalize finds the pose of a
+ * scan in the map without a prior and fx_map_localize refines it, which closing one would start from).  The equality with one batch of the whole run
  * holds for min_obs == 2; with a larger min_obs a track that a batch edge cuts into pieces that are each too short is missed.
  * n_obs and n_needed are 32-bit counts.  FX_MAP_FULL is sticky and n_needed only rises under fx_map_update; fx_map_compact (below)
  * gives the room of absorbed and let-go landmarks back, fx_map_export_host / fx_map_import_host carry a map to another context.
@@ -715,8 +715,8 @@ fx_status fx_map_read_landmarks(fx_ctx *ctx, fx_map *map, uint32_t first, uint32
  * FX_ERR_INVALID_ARG with the reason in fx_last_error(), nothing launched, the map unchanged: a NULL ctx or map (fx_map_get_alias:
  * a NULL out pointer), a map of another context, merge_dist not finite and positive, max_gap_scans == 0, result_device not 4-byte
  * aligned; fx_map_read_alias: entries outside max_landmarks.
- * Limits: merging happens within one segment only (no loop closure; fx_map_localize, below, gives the transform between a scan's
- * frame and the map's, it joins nothing).  Chained merges of one call may join A and C that are up to
+ * Limits: merging happens within one segment only (no loop closure; fx_map_relocalize and fx_map_localize, below, give the
+ * transform between a scan's frame and the map's, without and with a prior pose; they join nothing).  Chained merges of one call may join A and C that are up to
  * 2 merge_dist apart, through B.  The map_id_of_row arrays of earlier batches keep the absorbed ids: resolve them through the
  * alias table (id = alias[id] >= 0 ? alias[id] : id); the absorbed records, their sums and their alias entries stay until
  * fx_map_compact (below) takes them out.  A cell of the grid that holds very many fragments is searched by one lane
@@ -788,7 +788,8 @@ fx_status fx_map_read_alias(fx_ctx *ctx, fx_map *map, uint32_t first, uint32_t c
  * The same bytes from run to run and with any number of contexts in flight: every decision is an integer or a minimum over a
  * total order, every fp64 sum an ordered chain on one lane.  The search structure (fx_map_merge's hashed grid, cell edge
  * sd (1 + 2^-8)) never shows in the result.
- * Limits: a prior is needed (the map stores no descriptors: no global relocalisation); the call joins no segments and
+ * Limits: a prior is needed: fx_map_relocalize (below) produces one from the map's geometry alone (the map stores no descriptors),
+ * and this call refines it; the call joins no segments and
  * re-estimates no landmark: it produces the poses and the row-to-landmark table both would start from.  A cell of the grid that
  * holds very many landmarks is walked by one lane a row.  New in 0.7 (added symbols only). */
 #define FX_LOC_MAX_CORR 1024u
@@ -822,6 +823,97 @@ fx_status fx_map_localize(fx_ctx *ctx, fx_map *map,
     const fx_pose *prior_poses_device, uint32_t n_scans, uint32_t q_max_rows, const fx_localize_options *opt /* NULL: defaults */,
     fx_localization *out_device /* [n_scans] */, int32_t *map_id_of_row_device /* [q_max_rows] */,
     int32_t *nearest_of_row_device /* [q_max_rows] or NULL */);
+
+/* ---- Finding a scan's pose in the map without a prior: global relocalisation from the pole constellation ----
+ * fx_map_localize needs a prior within about search_dist of the truth, and only dead reckoning from the run that built the map
+ * gives one.  A later run that starts somewhere in a stored map ("map once, localise later") and a segment that a bad link cut off
+ * have none.  fx_map_relocalize finds the pose from the scan's keypoints and the map's positions alone: it lays pairs of keypoints
+ * (seeds) on pairs of landmarks of the same length and scores each rigid transform that results by the keypoints it lands on a
+ * landmark.  The intended use is one fx_map_relocalize, then fx_map_localize with pose as the prior and a small search_dist
+ * (2 inlier_dist), which refits the pose over all correspondences.  It is enqueued on the context's stream (no host
+ * synchronisation, no allocation in the steady state: its scratch is the context-owned buffer the other map calls share, grown
+ * as needed) and READS the map only: header, records, sums, alias, carry and the carry scan are bit for bit what they were.
+ * Every floating-point step is fp64, no contraction, no fma; id, pt, mb, xb are inlier_dist, pair_tol, min_baseline and
+ * max_baseline widened to double.
+ * Sizes, non-rows, scans b >= S: exactly as in fx_map_localize.  All n_scans records and all q_max_rows words are written and
+ * nothing beyond them.  A scan b >= S gets flags = FX_RELOC_NO_SCAN, n_kp = n_seeds = 0, n_hyp = 0 and otherwise the record of a
+ * scan without a winner (below).
+ * Eligible landmarks: fx_map_localize's clause word for word with this call's min_landmark_obs and segment: g < N is eligible iff
+ * alias[g] == -1, n_obs >= min_landmark_obs, its x, y and z are finite and its segment passes opt.segment.
+ * Used keypoints of scan b: its rows whose x, y and z are finite, in ascending row, at most the first FX_RELOC_MAX_KP (more:
+ * FX_RELOC_TRUNCATED); their coordinates are the floats widened to double, in the scan's own frame.  n_kp is the number used;
+ * keypoint k is the k-th of them.
+ * Seeds: the candidates are the pairs (a, b), a < b, of used keypoints with mb mb <= d2 <= xb xb, dx = x[b] - x[a], dy = y[b] - y[a],
+ * d2 = dx dx + dy dy.  They are ranked by descending d2 (compared as uint64 bit patterns), then ascending (a, b); the seeds are the
+ * first n_seeds = min(count, max_seeds): long baselines fix the yaw best.
+ * Hypotheses: for the seed of rank s with keypoints (a, b), every ordered pair (g, h), g != h, of eligible landmarks: the
+ * transform is fx_register_matches's hypothesis clause in fp64 (the device function fx_map_localize uses) of the correspondences
+ * A = (x[a], y[a], X[g], Y[g]) and B = (x[b], y[b], X[h], Y[h]), with mb mb as the baseline gate (both lengths) and pt in the place
+ * of 2 inlier_dist as the length gate: |sqrt(lq2) - sqrt(lt2)| > pt is gated out.  A pair that is gated out is no hypothesis.
+ * n_hyp counts the hypotheses of the scan over all its seeds.
+ * Score of a hypothesis (c, s, tx, ty): the number of used keypoints k whose image wx = (c x - s y) + tx, wy = (s x + c y) + ty has
+ * an eligible landmark with d2 <= id id, dx = X[g] - wx, dy = Y[g] - wy, d2 = dx dx + dy dy.  Two keypoints on one landmark both
+ * count.
+ * Winner: the hypothesis of highest score, ties to the lowest (s, g, h).  A scan whose best score is below 2 or that has no
+ * hypothesis is WITHOUT A WINNER: flags = FX_RELOC_NO_HYPOTHESIS (and FX_RELOC_TRUNCATED when it applies), the identity pose
+ * (c = 1, s = tx = ty = tz = 0, segment 0, flags 0), score = runner_up = 0, seed_a = seed_b = lm_a = lm_b = 0xffffffff; n_kp,
+ * n_seeds and n_hyp are what they are.
+ * Rivals (the ambiguity test: poles in a row or a lattice admit several poses): with T* the winner's transform and a*, b* its
+ * seed keypoints, another hypothesis T is a rival iff for q = a* or q = b* the vector r = T(q) - T*(q), taken componentwise from
+ * the two images in the expression above, has r.x r.x + r.y r.y > g g, g = 2.0 id.  runner_up is the highest score among the
+ * rivals, 0 when there is none.  The hypotheses that restate the winner's pose from other seeds or landmarks are no rivals.
+ * Result: FX_RELOC_VALID iff score >= min_inliers and score - runner_up >= min_margin; FX_RELOC_AMBIGUOUS iff score >=
+ * min_inliers and the margin fails; neither below min_inliers.  Whenever there is a winner: pose (c, s, tx, ty) is its transform;
+ * the landmark of a keypoint is the eligible landmark of lowest (d2 as uint64 bits, id) among those with d2 <= id id of its image
+ * (the SCORED keypoints are those that have one); tz is the sequential sum, in ascending row, of Z[landmark] - z over the scored
+ * keypoints, divided by (double)score; pose.segment is the segment of landmark g, pose.flags 0; seed_a, seed_b are the rows of a, b
+ * and lm_a, lm_b the landmarks g, h.  map_id_of_row[r] is the landmark of row r for the scored rows of a VALID scan and -1
+ * everywhere else.
+ * FX_ERR_INVALID_ARG with the reason in fx_last_error(), nothing launched, no output byte touched: a NULL required pointer
+ * (map_id_of_row_device may be NULL only with q_max_rows == 0), a map of another context, n_scans == 0 or n_scans > max_scans,
+ * inlier_dist, pair_tol or min_baseline not finite and positive, max_baseline not finite or below min_baseline, max_seeds outside
+ * 1..64, min_inliers < 3, min_margin == 0, min_landmark_obs == 0, reserved != 0, a keypoint block not 16-byte or records not 8-byte
+ * (words: 4-byte) aligned.
+ * The same bytes from run to run and with any number of contexts in flight: every decision is an integer (32- and 64-bit integer
+ * atomics only, sum and maximum) or a minimum over a total order, every fp64 value an ordered chain on one lane.  The search
+ * structures (two of fx_map_merge's hashed grids, one with a cell edge from max_baseline + pair_tol for the landmark pairs and one
+ * from inlier_dist for the score) and the reduction never show in a result; numpy float64 reproduces every record bit for bit.
+ * Limits: the pose is that of ONE two-point hypothesis, centimetres off under noise: refine it with fx_map_localize.  The work
+ * grows with seeds x eligible landmarks x the landmarks whose distance matches the seed x keypoints, and the rivals cost a second
+ * pass; max_seeds and max_baseline bound it.  A scan whose poles repeat a pattern of the map (a row, a lattice) comes back
+ * AMBIGUOUS; a scan of fewer than three poles the map holds cannot be VALID.  The call joins no segments and writes nothing to
+ * the map.  New in 0.7 (added symbols only). */
+#define FX_RELOC_MAX_KP 64u
+typedef struct fx_relocalize_options {   /* 40 B */
+  float inlier_dist;      /* a keypoint lands on a landmark within this xy distance, m; finite, > 0; default 0.30 */
+  float pair_tol;         /* allowed difference between a seed's length and a landmark pair's; finite, > 0; default 0.30 */
+  float min_baseline;     /* shortest seed pair, m; finite, > 0; default 2.0 */
+  float max_baseline;     /* longest seed pair, m; finite, >= min_baseline; default 60.0 */
+  uint32_t max_seeds;     /* seed pairs tried per scan; 1..64, default 16 */
+  uint32_t min_inliers;   /* score needed for FX_RELOC_VALID; >= 3, default 4 */
+  uint32_t min_margin;    /* lead needed over the best rival; >= 1, default 1 */
+  uint32_t min_landmark_obs; /* a landmark takes part with at least this many observations; >= 1, default 2 */
+  uint32_t segment;       /* as fx_localize_options.segment; default FX_LOC_ANY_SEGMENT */
+  uint32_t reserved;      /* 0 */
+} fx_relocalize_options;
+#define FX_RELOC_VALID 0x1u         /* score >= min_inliers and score - runner_up >= min_margin */
+#define FX_RELOC_TRUNCATED 0x2u     /* more than FX_RELOC_MAX_KP finite rows: the first 64 in row order were used */
+#define FX_RELOC_NO_HYPOTHESIS 0x4u /* no hypothesis, or none that lands 2 keypoints */
+#define FX_RELOC_AMBIGUOUS 0x8u     /* score >= min_inliers, but a rival pose scores within min_margin of it */
+#define FX_RELOC_NO_SCAN 0x10u      /* b is beyond the block's scans */
+typedef struct fx_relocalization {   /* 96 B, one per scan */
+  fx_pose pose;                      /* the winner's transform scan -> map; the identity without a winner */
+  uint64_t n_hyp;                    /* hypotheses of the scan */
+  uint32_t n_kp, n_seeds, score, runner_up, flags;
+  uint32_t seed_a, seed_b;           /* rows of the winning seed, 0xffffffff: none */
+  uint32_t lm_a, lm_b;               /* the landmarks they were laid on, 0xffffffff: none */
+  uint32_t reserved;                 /* 0 */
+} fx_relocalization;
+void fx_relocalize_options_default(fx_relocalize_options *o);
+fx_status fx_map_relocalize(fx_ctx *ctx, fx_map *map,
+    const void *kp_block_device, uint32_t max_scans, uint32_t max_total_keypoints,
+    uint32_t n_scans, uint32_t q_max_rows, const fx_relocalize_options *opt /* NULL: defaults */,
+    fx_relocalization *out_device /* [n_scans] */, int32_t *map_id_of_row_device /* [q_max_rows] */);
 
 /* ---- Compacting the map: the absorbed fragments and the let-go landmarks taken out, the others renumbered ----
  * fx_map_merge leaves every absorbed fragment in place: its record, its sums and its alias entry; every grid build marks and skips

@@ -1,0 +1,256 @@
+"""fx_map_relocalize on the GPU.  Every call of every case is compared with capi.map_relocalize_reference — an all-pairs statement
+of include/fx.h's definition in numpy float64 that knows nothing of the grids — bit for bit: every record field (integers equal,
+the doubles as bit patterns) and the row array whole.  The guard words behind the two outputs must be untouched, and the map's
+snapshot must be the same bytes before and after."""
+import ctypes as C
+import threading
+
+import numpy as np
+import pytest
+
+from feature_extraction_amd import capi
+from tests import map_localize_util as lu
+from tests import map_merge_util as mm
+from tests import map_relocalize_util as ru
+from tests import track_util as tu
+from tests.test_gpu_map import _run
+from tests.test_gpu_map_merge import _merge_to_fixpoint, _one_batch
+from tests.test_gpu_track import FILL, GUARD
+from tests.test_map_localize_reference import XY_BOUND, YAW_BOUND
+
+pytestmark = pytest.mark.gpu
+REC_WORDS = capi.RELOC_DTYPE.itemsize // 4
+ANY, LAST = capi.FX_LOC_ANY_SEGMENT, capi.FX_LOC_LAST_SEGMENT
+F32 = lu.F32
+
+
+@pytest.fixture
+def ctx(fxlib):
+    c = capi.Context(capi.params("launch"), capi.limits(2, 1024))  # (no batch is ever processed on it)
+    yield c
+    c.close()
+
+
+def _block(ctx, off, rows, max_scans, max_total, stored=None):
+    import torch
+    return (torch.from_numpy(tu.block(off, rows, max_scans, max_total, stored)).to(f"cuda:{ctx.device}"), max_scans, max_total)
+
+
+def _call(ctx, mp, kp, n_scans, q, **opts):
+    """Map.relocalize into guarded outputs.  Returns {"rec", "map_id_of_row", "raw": the record tensor}."""
+    import torch
+    dev = f"cuda:{ctx.device}"
+    raw = [torch.full((n + GUARD,), FILL, dtype=torch.int32, device=dev) for n in (n_scans * REC_WORDS, q)]
+    mp.relocalize(kp, n_scans, q_max_rows=q, out=(raw[0][:n_scans * REC_WORDS], raw[1][:q]), **opts)
+    ctx.synchronize()
+    for r, n, name in zip(raw, (n_scans * REC_WORDS, q), ("the records", "map_id_of_row")):
+        assert (r[n:] == FILL).all().item(), f"the guard behind {name}"
+    return {"rec": capi.relocalize_records(raw[0][:n_scans * REC_WORDS]), "map_id_of_row": raw[1][:q].cpu().numpy(), "raw": raw[0]}
+
+
+def _reloc(ctx, mp, st, off, rows, what, n_scans=None, max_scans=None, max_total=None, q_max_rows=None, stored=None, **opts):
+    """One fx_map_relocalize against one map_relocalize_reference call; the map's snapshot must come out as it went in."""
+    n_scans = len(off) - 1 if n_scans is None else n_scans
+    max_scans = max(len(off) - 1, n_scans) + 2 if max_scans is None else max_scans
+    max_total = len(rows) + 9 if max_total is None else max_total
+    q = len(rows) if q_max_rows is None else q_max_rows
+    kp = _block(ctx, off, rows, max_scans, max_total, stored)
+    before = mp.export_state()
+    got = _call(ctx, mp, kp, n_scans, q, **opts)
+    assert mp.export_state() == before, f"{what}: the map is read, never written"
+    ref = capi.map_relocalize_reference(st, off[:min(len(off) - 1, max_scans) + 1], rows[:len(rows) if stored is None else stored], n_scans, q_max_rows=q, **opts)
+    ru.assert_equal(got, ref, what)
+    return got, ref
+
+
+def _hand(ctx, frags, rows_by_scan, what, n_scans_map=3, bad=(), cap=None, merge=False, **kw):
+    mp, st = _one_batch(ctx, mm.fragments(frags, n_scans_map, bad), what, cap=cap, carry=8)
+    if merge:
+        st, _ = _merge_to_fixpoint(ctx, mp, st, what)
+    off, rows = lu.scans(rows_by_scan)
+    got, ref = _reloc(ctx, mp, st, off, rows, what, **kw)
+    mp.close()
+    return got, ref
+
+
+# ---- (a) the worlds of the reference's tests through the device chain
+def test_a_clean_world_then_localize_end_to_end(ctx):
+    """All 24 scans of the clean world without a pose; then fx_map_localize with the poses found as its priors and search_dist =
+    2 inlier_dist: every scan VALID, within the bounds the project holds fx_map_localize to on this world at sigma = 0.01 m
+    (tests/test_map_localize_reference.py XY_BOUND, YAW_BOUND)."""
+    w, pieces = lu.clean_world(0, 0.01)
+    W = lu.WORLD
+    mp = ctx.map_create(W["cap"], W["carry"])
+    st, _, _, _ = _run(ctx, pieces, "(a)", W["cap"], W["carry"], mp=mp)
+    got, ref = _reloc(ctx, mp, st, w["off"], w["rows"], "(a) clean world")
+    assert (got["rec"]["flags"] == ru.VALID).all()
+    kp = _block(ctx, w["off"], w["rows"], 26, len(w["rows"]) + 9)
+    pri = got["raw"][:24 * REC_WORDS].view(24, REC_WORDS)[:, :12].contiguous()  # the fx_pose a record starts with
+    recs, ids, _ = mp.localize(kp, pri, 24, q_max_rows=len(w["rows"]), search_dist=2 * 0.30)
+    ctx.synchronize()
+    loc = capi.localize_records(recs)
+    assert (loc["flags"] == capi.FX_LOC_VALID).all()
+    dxy, dz, dyaw = lu.pose_errors(loc["pose"], w["truth"])
+    print("(a) relocalize", lu.pose_errors(got["rec"]["pose"], w["truth"]), "then localize", (dxy, dz, dyaw))
+    assert dxy <= XY_BOUND and dyaw <= YAW_BOUND
+    assert (ids.cpu().numpy() >= 0).sum() >= (got["map_id_of_row"] >= 0).sum()
+    mp.close()
+
+
+@pytest.mark.parametrize("extra", [False, True])
+def test_a_lattice_ambiguous_and_decided_by_one_pole(ctx, extra):
+    """Nearly every comparison of the reduction is a tie here: the (score, s, g, h) order is what decides."""
+    frags, rows = ru.lattice_case(extra)
+    got, _ = _hand(ctx, frags, [rows, rows[::-1]], f"(a) lattice, extra {extra}")
+    rec = got["rec"]
+    if extra:
+        assert (rec["flags"] == ru.VALID).all() and (rec["score"] == 10).all() and (rec["runner_up"] == 9).all()
+    else:
+        assert (rec["flags"] == ru.AMBIG).all() and (rec["score"] == 9).all() and (rec["runner_up"] == 9).all()
+
+
+# ---- (b) gates and counts at their edges (tests/test_map_relocalize_reference.py holds the reference to the same answers)
+@pytest.mark.parametrize("name", sorted(ru.edge_cases()))
+def test_b_gates_at_their_edges(ctx, name):
+    frags, rows, opts, expect = ru.edge_cases()[name]
+    got, _ = _hand(ctx, frags, rows, f"(b) {name}", **opts)
+    ru.check_expect({"rec": got["rec"]}, {k: v for k, v in expect.items() if k != "hyp"}, name)
+
+
+@pytest.mark.parametrize("name", sorted(ru.count_cases()))
+def test_b_counts_at_their_edges(ctx, name):
+    frags, rows, opts, expect = ru.count_cases()[name]
+    got, _ = _hand(ctx, frags, rows, f"(b) {name}", cap=len(frags), **opts)
+    ru.check_expect({"rec": got["rec"]}, expect, name)
+
+
+def test_b_scans_beyond_the_block_and_row_arrays_of_other_lengths(ctx):
+    frags, rows = ru.lattice_case(True)
+    mp, st = _one_batch(ctx, mm.fragments(frags, 3), "(b) sizes", carry=8)
+    by_scan = [rows, [], rows[:2], rows[::-1], []]
+    off, kp = lu.scans(by_scan)
+    n = len(by_scan)
+    got, _ = _reloc(ctx, mp, st, off, kp, "(b) scans beyond the block", n_scans=n + 2, max_scans=n + 2)
+    assert got["rec"]["flags"].tolist() == [ru.VALID, ru.NOHYP, 0, ru.VALID, ru.NOHYP, ru.NOSCAN, ru.NOSCAN]
+    _reloc(ctx, mp, st, off, kp, "(b) max_scans scans", n_scans=n, max_scans=n, max_total=len(kp))
+    _reloc(ctx, mp, st, off, kp, "(b) fewer scans than the block", n_scans=2)
+    for q in (len(kp) - 12, len(kp) - 1, len(kp) + 1, len(kp) + 300):
+        _reloc(ctx, mp, st, off, kp, f"(b) q_max_rows {q}", q_max_rows=q)
+    _reloc(ctx, mp, st, off, kp, "(b) a block that stores fewer rows", stored=len(kp) - 5)
+    got, _ = _reloc(ctx, mp, st, off, kp[:0], "(b) no rows at all", q_max_rows=0, max_total=4, stored=0, n_scans=2)
+    assert (got["rec"]["flags"] == ru.NOHYP).all()
+    mp.close()
+
+
+# ---- (c) eligibility
+SEG0 = [(0, 10.0, 10.0), (0, 20.0, 10.0), (0, 10.0, 30.0), (0, 25.0, 22.0)]
+SEG1 = [(6, 30.0, 10.0), (6, 20.0, 20.0), (6, 42.0, 17.0), (6, 33.0, 31.0)]
+TWO_SEGMENTS = SEG0 + [(3, F32(10.125), 10.0)] + SEG1  # ids in (first_scan, order): 0-3, the fragment 4 (absorbed by 0), 5-8
+
+
+@pytest.mark.parametrize("opts, score, seg", [(dict(segment=ANY), 8, 0), (dict(segment=0), 4, 0), (dict(segment=1), 4, 1), (dict(segment=LAST), 4, 1),
+                                              (dict(segment=2), 0, 0), (dict(segment=ANY, min_landmark_obs=3), 0, 0)])
+def test_c_absorbed_fragments_few_observations_and_segments(ctx, opts, score, seg):
+    """A map of two segments (the link into scan 5 is bad) after fx_map_merge: landmark 4 is absorbed by 0, which then has 4
+    observations and every other 2.  The scan sees all eight poles."""
+    rows = ru.view_of(TWO_SEGMENTS, [0, 1, 2, 3, 5, 6, 7, 8], 0.7, 22.0, 18.0)
+    got, _ = _hand(ctx, TWO_SEGMENTS, [rows], f"(c) {opts}", n_scans_map=8, bad=(4,), merge=True, min_inliers=3, **opts)
+    rec = got["rec"][0]
+    assert rec["score"] == score and rec["pose"]["segment"] == seg and rec["flags"] == (ru.VALID if score else ru.NOHYP), rec
+    assert 4 not in got["map_id_of_row"].tolist()
+
+
+def test_c_landmarks_in_the_far_bucket(ctx):
+    """Landmarks beyond 2^39 cells, placed as the localize tests place theirs (1e13: far for the score grid; 1e30: far for both),
+    seen by a scan whose frame is the map's."""
+    frags = lu.lattice(9, pitch=8.0) + [(0, F32(1e13), F32(-1e13)), (0, F32(1e30), F32(1e30))]
+    rows = [(x, y, 1.0) for _, x, y in frags]
+    got, _ = _hand(ctx, frags, [rows, rows[5:]], "(c) the far bucket", min_inliers=3)
+    assert got["rec"]["score"].tolist() == [11, 6] and got["map_id_of_row"].tolist() == list(range(11)) + list(range(5, 11))
+
+
+def test_c_an_empty_map(ctx):
+    mp = ctx.map_create(8, 8)
+    off, rows = lu.scans([ru.lattice_case(False)[1]])
+    for seg in (LAST, ANY, 0):
+        got, _ = _reloc(ctx, mp, capi.map_state(8, 8), off, rows, f"(c) an empty map, segment {seg:#x}", segment=seg)
+        assert got["rec"]["flags"].tolist() == [ru.NOHYP] and got["rec"]["n_hyp"].tolist() == [0]
+    mp.close()
+
+
+# ---- (d) refusals
+def test_d_host_refusals_touch_no_output_byte(ctx, fxlib):
+    import torch
+    frags, rows = ru.lattice_case(True)
+    mp, st = _one_batch(ctx, mm.fragments(frags, 3), "(d)", carry=8)
+    other = capi.Context(capi.params("launch"), capi.limits(2, 1024))
+    theirs = other.map_create(8, 8)
+    off, kp_rows = lu.scans([rows])
+    kb, S, T = _block(ctx, off, kp_rows, 4, 16)
+    dev = f"cuda:{ctx.device}"
+    out, ids = (torch.full((n,), FILL, dtype=torch.int32, device=dev) for n in (REC_WORDS + 2, 12))
+    before = mp.export_state()
+    ok = dict(capi.RELOC_DEFAULTS, reserved=0)
+    opt = lambda **kw: C.byref(capi.FxRelocalizeOptions(**dict(ok, **kw)))
+    good = dict(c=ctx.handle, m=mp.handle, kp=kb.data_ptr(), S=S, T=T, n=1, q=10, opt=opt(), out=out.data_ptr(), ids=ids.data_ptr())
+    cases = [(dict(c=None), b"null"), (dict(m=None), b"null"), (dict(kp=None), b"null"), (dict(out=None), b"null"), (dict(ids=None), b"null"),
+             (dict(m=theirs.handle), b"another context"), (dict(c=other.handle), b"another context"), (dict(n=0), b"n_scans"),
+             (dict(n=S + 1), b"n_scans"), (dict(kp=kb.data_ptr() + 4), b"aligned"), (dict(out=out.data_ptr() + 4), b"aligned"),
+             (dict(ids=ids.data_ptr() + 2), b"aligned")]
+    for f in ("inlier_dist", "pair_tol", "min_baseline"):
+        cases += [(dict(opt=opt(**{f: v})), f.encode()) for v in (0.0, -1.0, float("nan"), float("inf"))]
+    cases += [(dict(opt=opt(max_baseline=v)), b"max_baseline") for v in (1.0, float(np.nextafter(np.float32(2.0), np.float32(0.0))), float("nan"), float("inf"))]
+    cases += [(dict(opt=opt(max_seeds=0)), b"max_seeds"), (dict(opt=opt(max_seeds=65)), b"max_seeds"), (dict(opt=opt(min_inliers=2)), b"min_inliers"),
+              (dict(opt=opt(min_margin=0)), b"min_margin"), (dict(opt=opt(min_landmark_obs=0)), b"min_landmark_obs"), (dict(opt=opt(reserved=1)), b"reserved")]
+    for change, word in cases:
+        a = dict(good, **change)
+        status = fxlib.fx_map_relocalize(a["c"], a["m"], a["kp"], a["S"], a["T"], a["n"], a["q"], a["opt"], a["out"], a["ids"])
+        assert status == 1 and word in fxlib.fx_last_error(), (change, word, fxlib.fx_last_error())
+    ctx.synchronize()
+    assert all((t == FILL).all().item() for t in (out, ids)) and mp.export_state() == before
+    # opt == NULL: the defaults; the row array may be NULL with q_max_rows == 0; max_baseline == min_baseline is in range
+    a = good
+    assert fxlib.fx_map_relocalize(a["c"], a["m"], a["kp"], a["S"], a["T"], 1, 0, None, a["out"], None) == capi.FX_OK
+    assert fxlib.fx_map_relocalize(a["c"], a["m"], a["kp"], a["S"], a["T"], 1, 10, opt(max_baseline=2.0), a["out"], a["ids"]) == capi.FX_OK
+    assert fxlib.fx_map_relocalize(a["c"], a["m"], a["kp"], a["S"], a["T"], 1, 10, None, a["out"], a["ids"]) == capi.FX_OK
+    ctx.synchronize()
+    ref = capi.map_relocalize_reference(st, off, kp_rows, 1)
+    ru.assert_equal({"rec": capi.relocalize_records(out[:REC_WORDS]), "map_id_of_row": ids[:10].cpu().numpy()}, ref, "(d) defaults")
+    assert (out[REC_WORDS:] == FILL).all().item() and (ids[10:] == FILL).all().item()
+    theirs.close(), other.close(), mp.close()
+
+
+# ---- (e) the same bytes from run to run and on a second context running at the same time
+def test_e_identical_bytes_across_runs_and_contexts(ctx):
+    w, pieces, _ = mm.flicker()
+    f = mm.FLICKER
+
+    def once(c, repeat):
+        mp = c.map_create(f["cap"], f["carry"])
+        _run(c, pieces, "(e)", f["cap"], f["carry"], mp=mp)
+        mp.merge(max_gap_scans=24, result=False)
+        kp = _block(c, w["off"], w["rows"], 26, len(w["rows"]) + 9)
+        outs = []
+        for _ in range(repeat):
+            got = _call(c, mp, kp, 24, len(w["rows"]))
+            outs.append(got["rec"].tobytes() + got["map_id_of_row"].tobytes())
+        mp.close()
+        assert len(set(outs)) == 1, "the same bytes twice"
+        return outs[0]
+    first = once(ctx, 2)
+    res, errs = {}, []
+
+    def run():
+        try:
+            c = capi.Context(capi.params("launch"), capi.limits(2, 1024))
+            res[0] = once(c, 3)
+            c.close()
+        except Exception as e:  # (reported below)
+            errs.append(e)
+    th = threading.Thread(target=run)
+    th.start()
+    mine = once(ctx, 3)  # (this context works while the other is busy on the device)
+    th.join()
+    assert not errs, errs
+    assert mine == first and res[0] == first
+    assert (capi.relocalize_records(np.frombuffer(first[:24 * capi.RELOC_DTYPE.itemsize], np.uint8))["flags"] & ru.VALID).sum() >= 20

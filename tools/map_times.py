@@ -29,6 +29,13 @@ map, updates it, merges, merges again on the fixpoint (timed: the grid and the s
 compacts (timed: one pair of HIP events around the call) and merges once more on the compacted map (timed: the same grid and search
 over the 2 N / 3 live records).  Reported per size: the medians, the ratio of the compaction time to the size before (the merge's
 requirement applies: time(10^6) <= 15 x time(10^5)) and the fixpoint merge after over before.
+
+  timeout -k 10 600 python tools/map_times.py --relocalize [--sizes 10000,100000] [--warmup 1] [--repeats 3] [--out profiles/map_relocalize_times.txt]
+
+times fx_map_relocalize on the same synthetic maps (built by one update, not merged: every landmark live): 8 scans a call, each of
+the 64 poles nearest to a random position inside the map, seen from a random pose there; default options (16 seeds).  One pair of
+HIP events around the call.  Reported per size: the median time of a call, the time per scan, how many scans came back VALID and
+the mean n_hyp of a scan.  No target is set.
 """
 import argparse
 import ctypes as C
@@ -239,6 +246,70 @@ def measure_compact(ctx, n, warmup, repeats):
     return out
 
 
+def measure_relocalize(ctx, n, warmup, repeats, n_scans=8):
+    import torch
+    blk, (S, T), m, inl, reg, M = merge_case(n, np.random.default_rng(n))
+    kp = (torch.from_numpy(blk).cuda(), S, T)
+    md, inl_t = torch.from_numpy(m.view(np.int32).reshape(-1, 8).copy()).cuda(), torch.from_numpy(inl).cuda()
+    reg_t = torch.from_numpy(reg.view(np.float64).reshape(-1, 8).copy()).cuda()
+    out = ctx.track_landmarks(kp, md, inl_t, reg_t, S, max_landmarks=n)
+    mp = ctx.map_create(n, 16)
+    mp.update(kp, out, overlap=False, row_ids=False)
+    lm = mp.landmarks(0, mp.header()["n_landmarks"])
+    xy = np.stack([lm["x"], lm["y"]], axis=1)
+    rng = np.random.default_rng(n + 1)
+    rows = np.zeros((n_scans * capi.FX_RELOC_MAX_KP, 4), np.float32)
+    for b in range(n_scans):
+        at, yaw = xy[rng.integers(len(xy))] + rng.uniform(-5.0, 5.0, 2), rng.uniform(-np.pi, np.pi)
+        near = np.argsort(((xy - at) ** 2).sum(axis=1))[:capi.FX_RELOC_MAX_KP]
+        d = xy[near] - at
+        c, s = np.cos(yaw), np.sin(yaw)
+        rows[b * 64:(b + 1) * 64, 0], rows[b * 64:(b + 1) * 64, 1], rows[b * 64:(b + 1) * 64, 2] = c * d[:, 0] + s * d[:, 1], -s * d[:, 0] + c * d[:, 1], 1.0
+    T2 = len(rows)
+    k0, n_blk = capi.keypoint_block_layout(n_scans, T2)
+    sb = np.zeros((n_blk, 4), np.float32)
+    u = sb.view(np.uint32).reshape(-1)
+    u[:4] = (n_scans, T2, 0, T2)
+    u[4:4 + n_scans + 1] = np.arange(n_scans + 1) * 64
+    sb[k0:k0 + T2] = rows
+    skp = (torch.from_numpy(sb.view(np.uint8).reshape(-1)).cuda(), n_scans, T2)
+    stream = torch.cuda.ExternalStream(ctx.stream_ptr())
+    torch.cuda.synchronize()
+    ms, rec = [], None
+    for rep in range(warmup + repeats):
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        e[0].record(stream)
+        recs, _ = mp.relocalize(skp, n_scans)
+        e[1].record(stream)
+        ctx.synchronize()
+        rec = capi.relocalize_records(recs)
+        if rep >= warmup:
+            ms.append(e[0].elapsed_time(e[1]))
+    mp.close()
+    return {"landmarks": int(len(xy)), "scans": n_scans, "call_ms": statistics.median(ms), "call_ms_min_max": [min(ms), max(ms)],
+            "valid": int((rec["flags"] & capi.FX_RELOC_VALID != 0).sum()), "n_hyp_mean": float(rec["n_hyp"].mean()), "n_seeds": rec["n_seeds"].tolist()}
+
+
+def main_relocalize(a):
+    sizes = [int(x) for x in a.sizes.split(",")]
+    ctx = capi.Context(capi.params("launch"), capi.limits(2, 1024))
+    rows = [measure_relocalize(ctx, n, a.warmup, a.repeats) for n in sizes]
+    ctx.close()
+    lines = [f"fx_map_relocalize on synthetic maps (tools/map_times.py --relocalize): 1 pole per 250 m^2 (a third of them a second landmark up to",
+             f"0.2 m off), 8 scans of 64 keypoints a call, default options (16 seeds); one context, HIP events around the call, median of",
+             f"{a.repeats} after {a.warmup} warm-up; ms",
+             f"{'landmarks':>10} {'scans':>6} {'call':>10} {'a scan':>10} {'valid':>6} {'n_hyp a scan':>14}"]
+    for r in rows:
+        lines.append(f"{r['landmarks']:>10} {r['scans']:>6} {r['call_ms']:>10.3f} {r['call_ms'] / r['scans']:>10.3f} {r['valid']:>6} {r['n_hyp_mean']:>14.0f}")
+    s = "\n".join(lines)
+    print(s)
+    print(json.dumps(rows))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(s + "\n")
+
+
 def main_compact(a):
     sizes = [int(x) for x in a.sizes.split(",")]
     ctx = capi.Context(capi.params("launch"), capi.limits(2, 1024))
@@ -289,6 +360,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--merge", action="store_true", help="time fx_map_merge on synthetic maps instead")
     ap.add_argument("--compact", action="store_true", help="time fx_map_compact on the merged synthetic maps instead")
+    ap.add_argument("--relocalize", action="store_true", help="time fx_map_relocalize on the synthetic maps instead (pass --sizes 10000,100000)")
     ap.add_argument("--sizes", default="1000,100000,1000000")
     ap.add_argument("--scans", type=int, default=1024)
     ap.add_argument("--batch", type=int, default=128)
@@ -303,6 +375,8 @@ def main():
         return main_merge(a)
     if a.compact:
         return main_compact(a)
+    if a.relocalize:
+        return main_relocalize(a)
     N = 28800
     ctx = capi.Context(capi.params("launch"), capi.limits(a.batch, N, sparse=True))
     scenes = np.stack([capi.synth_scan(capi.synth_cfg(1000 + b)) for b in range(a.scans)])
