@@ -250,6 +250,29 @@ RELOC_DEFAULTS = dict(inlier_dist=0.30, pair_tol=0.30, min_baseline=2.0, max_bas
                       min_landmark_obs=2, segment=FX_LOC_ANY_SEGMENT)
 
 
+class FxMapJoinOptions(C.Structure):
+    _fields_ = [("search_dist", C.c_float), ("inlier_dist", C.c_float), ("min_baseline", C.c_float), ("hyp_corr", C.c_uint32),
+                ("min_inliers", C.c_uint32), ("min_landmark_obs", C.c_uint32), ("mode", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class FxMapJoinResult(C.Structure):
+    _fields_ = [("c", C.c_double), ("s", C.c_double), ("tx", C.c_double), ("ty", C.c_double), ("tz", C.c_double), ("dc", C.c_double),
+                ("ds", C.c_double), ("dtx", C.c_double), ("dty", C.c_double), ("dtz", C.c_double), ("rms", C.c_float), ("n_src", C.c_uint32),
+                ("n_corr", C.c_uint32), ("n_inliers", C.c_uint32), ("flags", C.c_uint32), ("moved", C.c_uint32), ("label", C.c_uint32),
+                ("segments", C.c_uint32), ("hyp_a", C.c_uint32), ("hyp_b", C.c_uint32)]
+
+
+FX_JOIN_MAX_CORR = 1024
+FX_JOIN_FIT, FX_JOIN_GIVEN, FX_JOIN_DRY_RUN = 0, 1, 2
+FX_JOIN_APPLIED, FX_JOIN_TRUNCATED, FX_JOIN_NO_HYPOTHESIS, FX_JOIN_BAD_PRIOR, FX_JOIN_BAD_SEGMENT, FX_JOIN_FITTED = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
+FX_JOIN_NONE = 0xffffffff
+# fx_map_join_result as a numpy record (join_records)
+JOIN_DTYPE = np.dtype([("c", "<f8"), ("s", "<f8"), ("tx", "<f8"), ("ty", "<f8"), ("tz", "<f8"), ("dc", "<f8"), ("ds", "<f8"), ("dtx", "<f8"),
+                       ("dty", "<f8"), ("dtz", "<f8"), ("rms", "<f4"), ("n_src", "<u4"), ("n_corr", "<u4"), ("n_inliers", "<u4"), ("flags", "<u4"),
+                       ("moved", "<u4"), ("label", "<u4"), ("segments", "<u4"), ("hyp_a", "<u4"), ("hyp_b", "<u4")])
+JOIN_DEFAULTS = dict(search_dist=2.0, inlier_dist=0.30, min_baseline=2.0, hyp_corr=64, min_inliers=3, min_landmark_obs=2, mode=FX_JOIN_FIT)
+
+
 class FxTimings(C.Structure):
     _fields_ = [("ms", C.c_float * FX_N_STAGES), ("total_ms", C.c_float), ("k_prep_exec_ms", C.c_float)]
 
@@ -277,6 +300,7 @@ EXPORTS = ("fx_version", "fx_check_abi", "fx_status_str", "fx_last_error", "fx_p
            "fx_map_merge_options_default", "fx_map_merge", "fx_map_get_alias", "fx_map_read_alias",
            "fx_localize_options_default", "fx_map_localize", "fx_relocalize_options_default", "fx_map_relocalize",
            "fx_map_compact_options_default", "fx_map_compact", "fx_map_export_host", "fx_map_import_host", "fx_map_snapshot_check",
+           "fx_map_join_options_default", "fx_map_join_segments",
            "fx_rotation_from_roll_pitch", "fx_sc3d_tables", "fx_sc3d_xaxis", "fx_synth_cfg_vlp16",
            "fx_synth_scan", "fx_unpack_pointcloud2", "fx_pack_pointxyzi")
 # the header's FX_TEST_HOOKS section: exported by lib/libfx_hip_test.so only
@@ -419,6 +443,10 @@ def load():
     lib.fx_map_export_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     lib.fx_map_import_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     lib.fx_map_snapshot_check.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32]
+    lib.fx_map_join_options_default.argtypes = [C.POINTER(FxMapJoinOptions)]
+    lib.fx_map_join_options_default.restype = None
+    lib.fx_map_join_segments.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(FxPose), C.c_void_p, C.POINTER(FxMapJoinOptions),
+                                         C.c_void_p, C.c_void_p]
     lib.fx_rotation_from_roll_pitch.argtypes = [C.c_double, C.c_double, _F32P]
     lib.fx_rotation_from_roll_pitch.restype = None
     lib.fx_sc3d_tables.argtypes = [C.c_double, _F32P, _F32P, _F32P, _F32P]
@@ -1268,6 +1296,64 @@ def localize_records(out):
     return np.ascontiguousarray(out).view(np.uint8).reshape(-1).view(LOC_DTYPE).copy()
 
 
+def _map_consensus(P64, d2_bits, names, tz, qz, hyp_corr, mb2, gate, id2):
+    """The hypothesis stage and the refit of fx_map_localize (include/fx.h), which fx_map_join_segments shares, in numpy float64
+    over the n correspondences P64 [n, 4] = (qx, qy, tx, ty): d2_bits their association distances as uint64, names what the pool's
+    ties and hyp_a / hyp_b go by (rows, landmark ids: ascending), tz and qz the targets' and the points' z.  mb2, gate, id2: the
+    gates as float64.  Call it under np.errstate(all="ignore").  Returns None without a hypothesis, else {"fit": (dc, ds, dtx,
+    dty), "dtz", "rms": float32, "final": the final inlier set (indices), "hyp": the names of the winning sample}."""
+    f64 = np.float64
+    n = len(P64)
+    H = min(n, int(hyp_corr))
+    best = None
+    if H >= 2:
+        pool = np.lexsort((names, d2_bits))[:H]  # by (d2 bits, name)
+        a, c_ = np.triu_indices(H, 1)            # lexicographic (a, b), a < b
+        A, B = P64[pool[a]], P64[pool[c_]]
+        dqx, dqy, dtx, dty = B[:, 0] - A[:, 0], B[:, 1] - A[:, 1], B[:, 2] - A[:, 2], B[:, 3] - A[:, 3]
+        lq2, lt2 = dqx * dqx + dqy * dqy, dtx * dtx + dty * dty
+        keep = (lq2 >= mb2) & (lt2 >= mb2)
+        keep &= ~(np.abs(np.sqrt(lq2) - np.sqrt(lt2)) > gate)
+        dot, crs = dqx * dtx + dqy * dty, dqx * dty - dqy * dtx
+        nrm = np.sqrt(dot * dot + crs * crs)
+        keep &= nrm > 0
+        c, s = dot / nrm, crs / nrm
+        half = f64(0.5)
+        mqx, mqy, mtx, mty = (A[:, 0] + B[:, 0]) * half, (A[:, 1] + B[:, 1]) * half, (A[:, 2] + B[:, 2]) * half, (A[:, 3] + B[:, 3]) * half
+        tx, ty = mtx - (c * mqx - s * mqy), mty - (s * mqx + c * mqy)
+        ks = np.flatnonzero(keep)
+        counts = np.zeros(len(a), np.int64)
+        for lo_ in range(0, len(ks), 512):  # (chunks: [samples, n] temporaries)
+            k = ks[lo_:lo_ + 512]
+            ck, sk, txk, tyk = c[k, None], s[k, None], tx[k, None], ty[k, None]
+            qx, qy, t_x, t_y = P64[None, :, 0], P64[None, :, 1], P64[None, :, 2], P64[None, :, 3]
+            rx, ry = ((ck * qx - sk * qy) + txk) - t_x, ((sk * qx + ck * qy) + tyk) - t_y
+            counts[k] = (rx * rx + ry * ry <= id2).sum(axis=1)
+        counts[counts < 2] = 0  # (a sample with fewer than 2 agreeing is no hypothesis)
+        if counts.any():
+            best = int(np.argmax(counts))  # (the first maximum: the lowest (a, b))
+            rx = ((c[best] * P64[:, 0] - s[best] * P64[:, 1]) + tx[best]) - P64[:, 2]
+            ry = ((s[best] * P64[:, 0] + c[best] * P64[:, 1]) + ty[best]) - P64[:, 3]
+            I0 = [int(v) for v in np.flatnonzero(rx * rx + ry * ry <= id2)]
+            assert len(I0) == int(counts[best])
+    if best is None:
+        return None
+    Pl = [tuple(float(v) for v in row) for row in P64]  # (Python floats: IEEE doubles, the register's refit as it is)
+    fit = _register_fit(Pl, I0, float(c[best]), float(s[best]))
+    final = I0
+    I1 = [k for k in range(n) if _register_r2(Pl, k, *fit) <= float(id2)]
+    if len(I1) >= 2:
+        fit = _register_fit(Pl, I1, fit[0], fit[1])
+        final = I1
+    sz = sr = 0.0
+    for k in final:
+        sz += (float(tz[k]) - float(qz[k]))
+        sr += _register_r2(Pl, k, *fit)
+    nf = float(len(final))
+    return {"fit": fit, "dtz": sz / nf, "rms": np.float32(math.sqrt(sr / nf)), "final": final,
+            "hyp": (int(names[pool[a[best]]]), int(names[pool[c_[best]]]))}
+
+
 def map_localize_reference(state, kp_offset, kp_rows, prior_poses, n_scans, q_max_rows=None, search_dist=2.0, inlier_dist=0.30,
                            min_baseline=2.0, hyp_corr=64, min_inliers=3, min_landmark_obs=2, segment=FX_LOC_LAST_SEGMENT):
     """The definition of fx_map_localize (include/fx.h) in numpy float64 over a map_reference / map_merge_reference state (which is
@@ -1346,61 +1432,17 @@ def map_localize_reference(state, kp_offset, kp_rows, prior_poses, n_scans, q_ma
             rec["n_corr"][b] = n
             g = nearest[i]
             P64 = np.stack([W[i, 0], W[i, 1], lx[g], ly[g]], axis=1) if n else np.zeros((0, 4), f64)  # (qx, qy, tx, ty)
-            H = min(n, int(hyp_corr))
-            best = None
-            if H >= 2:
-                pool = np.lexsort((i, d2_of[i]))[:H]  # by (d2 bits, row)
-                a, c_ = np.triu_indices(H, 1)          # lexicographic (a, b), a < b
-                A, B = P64[pool[a]], P64[pool[c_]]
-                dqx, dqy, dtx, dty = B[:, 0] - A[:, 0], B[:, 1] - A[:, 1], B[:, 2] - A[:, 2], B[:, 3] - A[:, 3]
-                lq2, lt2 = dqx * dqx + dqy * dqy, dtx * dtx + dty * dty
-                keep = (lq2 >= mb2) & (lt2 >= mb2)
-                keep &= ~(np.abs(np.sqrt(lq2) - np.sqrt(lt2)) > gate)
-                dot, crs = dqx * dtx + dqy * dty, dqx * dty - dqy * dtx
-                nrm = np.sqrt(dot * dot + crs * crs)
-                keep &= nrm > 0
-                c, s = dot / nrm, crs / nrm
-                half = f64(0.5)
-                mqx, mqy, mtx, mty = (A[:, 0] + B[:, 0]) * half, (A[:, 1] + B[:, 1]) * half, (A[:, 2] + B[:, 2]) * half, (A[:, 3] + B[:, 3]) * half
-                tx, ty = mtx - (c * mqx - s * mqy), mty - (s * mqx + c * mqy)
-                ks = np.flatnonzero(keep)
-                counts = np.zeros(len(a), np.int64)
-                for lo_ in range(0, len(ks), 512):  # (chunks: [samples, n] temporaries)
-                    k = ks[lo_:lo_ + 512]
-                    ck, sk, txk, tyk = c[k, None], s[k, None], tx[k, None], ty[k, None]
-                    qx, qy, t_x, t_y = P64[None, :, 0], P64[None, :, 1], P64[None, :, 2], P64[None, :, 3]
-                    rx, ry = ((ck * qx - sk * qy) + txk) - t_x, ((sk * qx + ck * qy) + tyk) - t_y
-                    counts[k] = (rx * rx + ry * ry <= id2).sum(axis=1)
-                counts[counts < 2] = 0  # (a sample with fewer than 2 agreeing is no hypothesis)
-                if counts.any():
-                    best = int(np.argmax(counts))  # (the first maximum: the lowest (a, b))
-                    rx = ((c[best] * P64[:, 0] - s[best] * P64[:, 1]) + tx[best]) - P64[:, 2]
-                    ry = ((s[best] * P64[:, 0] + c[best] * P64[:, 1]) + ty[best]) - P64[:, 3]
-                    I0 = [int(v) for v in np.flatnonzero(rx * rx + ry * ry <= id2)]
-                    assert len(I0) == int(counts[best])
-            if best is None:
+            fitd = _map_consensus(P64, d2_of[i], i, lz[g], W[i, 2], hyp_corr, mb2, gate, id2)
+            if fitd is None:
                 rec["flags"][b] = flags | FX_LOC_NO_HYPOTHESIS
                 continue
-            Pl = [tuple(float(v) for v in row) for row in P64]  # (Python floats: IEEE doubles, the register's refit as it is)
-            fit = _register_fit(Pl, I0, float(c[best]), float(s[best]))
-            final = I0
-            I1 = [k for k in range(n) if _register_r2(Pl, k, *fit) <= float(id2)]
-            if len(I1) >= 2:
-                fit = _register_fit(Pl, I1, fit[0], fit[1])
-                final = I1
-            sz = sr = 0.0
-            for k in final:
-                sz += (float(lz[g[k]]) - float(W[i[k], 2]))
-                sr += _register_r2(Pl, k, *fit)
-            nf = float(len(final))
-            dc, ds, dtx_, dty_ = fit
-            dtz = sz / nf
+            (dc, ds, dtx_, dty_), dtz, final = fitd["fit"], fitd["dtz"], fitd["final"]
             rec["dc"][b], rec["ds"][b], rec["dtx"][b], rec["dty"][b], rec["dtz"][b] = dc, ds, dtx_, dty_, dtz
-            rec["rms"][b] = np.float32(math.sqrt(sr / nf))
+            rec["rms"][b] = fitd["rms"]
             rec["n_inliers"][b] = len(final)
             valid = len(final) >= min_inliers
             rec["flags"][b] = flags | (FX_LOC_VALID if valid else 0)
-            rec["hyp_a"][b], rec["hyp_b"][b] = i[pool[a[best]]], i[pool[c_[best]]]
+            rec["hyp_a"][b], rec["hyp_b"][b] = fitd["hyp"]
             if valid:
                 qc, qs, qtx, qty, qtz = (float(v) for v in (pc, ps, ptx, pty, ptz))
                 rec["pose"]["c"][b], rec["pose"]["s"][b] = dc * qc - ds * qs, ds * qc + dc * qs
@@ -1408,6 +1450,121 @@ def map_localize_reference(state, kp_offset, kp_rows, prior_poses, n_scans, q_ma
                 rec["pose"]["tz"][b] = qtz + dtz
             map_id[i[final]] = g[final]
     return {"rec": rec, "map_id_of_row": map_id, "nearest_of_row": nearest, "corr": corrs}
+
+
+# ---- two segments of the map made one (include/fx.h fx_map_join_segments)
+def join_records(out):
+    """A host copy of fx_map_join_segments's result (a torch tensor, or any array of 120 bytes) as a JOIN_DTYPE record array [1]."""
+    if hasattr(out, "detach"):
+        out = out.detach().cpu().numpy()
+    return np.ascontiguousarray(out).view(np.uint8).reshape(-1).view(JOIN_DTYPE).copy()
+
+
+def map_join_reference(state, src, dst, prior=None, **opts):
+    """The definition of fx_map_join_segments (include/fx.h) in numpy float64 and Python floats over a map_reference /
+    map_merge_reference state, which is not modified.  prior: (c, s, tx, ty, tz) or None, the identity (a prior that is not finite is
+    the device refusal FX_JOIN_BAD_PRIOR: what a prior_device gives); opts: the fields of fx_map_join_options (JOIN_DEFAULTS).
+    Every (query, target) pair is looked at: nothing here knows of a grid.  Returns (the new state, the result: a JOIN_DTYPE
+    record, match_of_landmark int32 [max_landmarks])."""
+    f64 = np.float64
+    bad = set(opts) - set(JOIN_DEFAULTS)
+    if bad:
+        raise TypeError(f"unknown join options {sorted(bad)}")
+    o = dict(JOIN_DEFAULTS, **opts)
+    src, dst, mode = int(src), int(dst), int(o["mode"])
+    sd32, id32, mb32 = np.float32(o["search_dist"]), np.float32(o["inlier_dist"]), np.float32(o["min_baseline"])
+    if src == dst or not (all(np.isfinite(v) and v > 0 for v in (sd32, id32, mb32)) and 2 <= o["hyp_corr"] <= 128 and o["min_inliers"] >= 2 and
+                          o["min_landmark_obs"] >= 1 and 0 <= mode <= 2):
+        raise ValueError("arguments outside what fx_map_join_segments accepts")
+    sd, idd, mbd = f64(sd32), f64(id32), f64(mb32)
+    sd2, mb2, gate, id2 = sd * sd, mbd * mbd, f64(2.0) * idd, idd * idd
+    st = dict(state, header=dict(state["header"]), landmarks=[dict(r) for r in state["landmarks"]], acc=[list(a) for a in state["acc"]],
+              carry=list(state["carry"]), carry_kp=state["carry_kp"].copy())
+    H, lms, accs = st["header"], st["landmarks"], st["acc"]
+    N, SEG = min(int(H["n_landmarks"]), len(lms)), int(H["segments"])
+    alias = [int(a) for a in st.get("alias", [])][:N]
+    alias += [-1] * (N - len(alias))
+    st["alias"] = alias
+    P = tuple(float(v) for v in (prior if prior is not None else (1.0, 0.0, 0.0, 0.0, 0.0)))[:5]
+    res = np.zeros(1, JOIN_DTYPE)[0]
+    res["c"], res["s"], res["tx"], res["ty"], res["tz"] = P
+    res["dc"], res["rms"], res["label"], res["hyp_a"], res["hyp_b"], res["segments"] = 1.0, np.inf, FX_JOIN_NONE, FX_JOIN_NONE, FX_JOIN_NONE, SEG
+    match = np.full(int(st["max_landmarks"]), -1, np.int32)
+    refuse = (FX_JOIN_BAD_SEGMENT if src >= SEG or dst >= SEG else 0) | (0 if all(math.isfinite(v) for v in P) else FX_JOIN_BAD_PRIOR)
+    if refuse:
+        res["flags"] = refuse
+        return st, res, match
+    pc, ps, ptx, pty, ptz = P
+    T, flags = P, 0
+    if mode != FX_JOIN_GIVEN:
+        seg = np.array([int(r["segment"]) for r in lms[:N]], np.int64)
+        lx, ly, lz = (np.array([float(r[f]) for r in lms[:N]], f64) for f in ("x", "y", "z"))
+        elig = np.array([alias[g] == -1 and int(lms[g]["n_obs"]) >= o["min_landmark_obs"] for g in range(N)], bool)
+        if N:
+            elig &= np.isfinite(lx) & np.isfinite(ly) & np.isfinite(lz)
+        q, t = np.flatnonzero(elig & (seg == src)), np.flatnonzero(elig & (seg == dst))
+        res["n_src"] = len(q)
+        with np.errstate(all="ignore"):
+            cc, ss, tx_, ty_, tz_ = (f64(v) for v in P)
+            wx, wy, wz = (cc * lx[q] - ss * ly[q]) + tx_, (ss * lx[q] + cc * ly[q]) + ty_, lz[q] + tz_
+            near, d2_of = np.full(len(q), -1, np.int64), np.zeros(len(q), np.uint64)
+            if len(q) and len(t):
+                for lo in range(0, len(q), 256):  # (chunks: [queries, targets] temporaries)
+                    hi = min(lo + 256, len(q))
+                    dx, dy = lx[t][None, :] - wx[lo:hi, None], ly[t][None, :] - wy[lo:hi, None]
+                    d2 = dx * dx + dy * dy
+                    key = np.where(d2 <= sd2, d2, np.inf).view(np.uint64)  # (the bits of +inf are above those of any distance in reach)
+                    j = np.argmin(key, axis=1)  # (the first minimum: ids ascend, so ties go to the lowest id)
+                    dj = d2[np.arange(hi - lo), j]
+                    hit = dj <= sd2
+                    near[lo:hi][hit] = t[j[hit]]
+                    d2_of[lo:hi][hit] = dj.view(np.uint64)[hit]
+            k = np.flatnonzero(near >= 0)
+            flags = FX_JOIN_TRUNCATED if len(k) > FX_JOIN_MAX_CORR else 0
+            k = k[:FX_JOIN_MAX_CORR]
+            n = len(k)
+            res["n_corr"] = n
+            g = near[k]
+            P64 = np.stack([wx[k], wy[k], lx[g], ly[g]], axis=1) if n else np.zeros((0, 4), f64)
+            fitd = _map_consensus(P64, d2_of[k], q[k], lz[g], wz[k], o["hyp_corr"], mb2, gate, id2)
+        if fitd is None:
+            flags |= FX_JOIN_NO_HYPOTHESIS
+        else:
+            (dc, ds, dtx, dty), dtz, final = fitd["fit"], fitd["dtz"], fitd["final"]
+            res["dc"], res["ds"], res["dtx"], res["dty"], res["dtz"], res["rms"] = dc, ds, dtx, dty, dtz, fitd["rms"]
+            res["n_inliers"] = len(final)
+            res["hyp_a"], res["hyp_b"] = fitd["hyp"]
+            match[q[k[final]]] = g[final]
+            if len(final) >= o["min_inliers"]:
+                flags |= FX_JOIN_FITTED
+                T = (dc * pc - ds * ps, ds * pc + dc * ps, (dc * ptx - ds * pty) + dtx, (ds * ptx + dc * pty) + dty, ptz + dtz)
+    res["c"], res["s"], res["tx"], res["ty"], res["tz"] = T
+    applied = mode == FX_JOIN_GIVEN or (mode == FX_JOIN_FIT and bool(flags & FX_JOIN_FITTED))
+    if applied:
+        flags |= FX_JOIN_APPLIED
+        c, s, tx, ty, tz = T
+        lo, hi = min(src, dst), max(src, dst)
+        moved = 0
+        for i in range(N):
+            R, A = lms[i], accs[i]
+            if int(R["segment"]) == src:
+                moved += 1
+                n = float(R["n_obs"])
+                sx, sy, sz = (c * A[0] - s * A[1]) + n * tx, (s * A[0] + c * A[1]) + n * ty, A[2] + n * tz
+                ax, ay = (c * A[3] - s * A[4]) + tx, (s * A[3] + c * A[4]) + ty
+                dx, dy = c * A[5] - s * A[6], s * A[5] + c * A[6]
+                A[:7] = [sx, sy, sz, ax, ay, dx, dy]
+                if int(R["n_obs"]):
+                    _map_record_from_sums(R, A)
+            sg = int(R["segment"])
+            R["segment"] = hi - 1 if sg == lo else (sg - 1 if sg > lo else sg)
+        if SEG - 1 == src:
+            lc, ls, ltx, lty, ltz = (float(v) for v in H["last_pose"][:5])
+            H["last_pose"] = (c * lc - s * ls, s * lc + c * ls, (c * ltx - s * lty) + tx, (s * ltx + c * lty) + ty, ltz + tz) + tuple(H["last_pose"][5:])
+        H["segments"] = SEG - 1
+        res["moved"], res["label"], res["segments"] = moved, hi - 1, SEG - 1
+    res["flags"] = flags
+    return st, res, match
 
 
 # ---- a scan's pose in the map without a prior (include/fx.h fx_map_relocalize)
@@ -1741,6 +1898,45 @@ class Map:
                                       C.c_void_p(result.data_ptr() if result is not None else None)))
         cur.wait_stream(ext)
         return remap, result
+
+    def join_segments(self, src, dst, prior=None, prior_device=None, result=None, match=None, **opts):
+        """fx_map_join_segments: the landmarks of segment src brought into segment dst's frame, the two segments made one
+        (include/fx.h).  prior: (c, s, tx, ty, tz) on the host, or prior_device: a device address (an int) or a tensor of five
+        doubles (a view of an fx_localization's dc), or neither: the identity.  opts: the fields of fx_map_join_options
+        (JOIN_DEFAULTS).  Returns (result, match_of_landmark): device tensors of 120 bytes (join_records reads it) and
+        torch.int32 [max_landmarks]; a tensor given reuses it, False passes NULL (None is returned in its place).  Stream-correct
+        like merge(); never waits for the stream."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        bad = set(opts) - set(JOIN_DEFAULTS)
+        if bad:
+            raise TypeError(f"unknown join options {sorted(bad)}")
+        o = dict(JOIN_DEFAULTS, **opts)
+        opt = FxMapJoinOptions(float(o["search_dist"]), float(o["inlier_dist"]), float(o["min_baseline"]), int(o["hyp_corr"]),
+                               int(o["min_inliers"]), int(o["min_landmark_obs"]), int(o["mode"]) & 0xffffffff, 0)
+        if result is None:
+            result = torch.empty((JOIN_DTYPE.itemsize // 8,), dtype=torch.float64, device=dev)
+        elif result is False:
+            result = None
+        if match is None:
+            match = torch.empty((self.max_landmarks,), dtype=torch.int32, device=dev)
+        elif match is False:
+            match = None
+        for t, size in ((result, JOIN_DTYPE.itemsize), (match, self.max_landmarks * 4)):
+            if t is not None and (t.device != dev or not t.is_contiguous() or t.numel() * t.element_size() != size):
+                raise ValueError(f"outputs must be contiguous tensors of 120 and {self.max_landmarks} * 4 bytes on {dev}")
+        pose = FxPose(*(float(v) for v in tuple(prior)[:5]), 0, 0) if prior is not None else None
+        if hasattr(prior_device, "data_ptr"):
+            prior_device = prior_device.data_ptr()
+        cur = torch.cuda.current_stream(dev)
+        ext = torch.cuda.ExternalStream(self.ctx.stream_ptr(), device=dev)
+        ext.wait_stream(cur)
+        check(self.lib.fx_map_join_segments(self.ctx.handle, self.handle, int(src) & 0xffffffff, int(dst) & 0xffffffff,
+                                            C.byref(pose) if pose is not None else None, C.c_void_p(prior_device),
+                                            C.byref(opt), C.c_void_p(result.data_ptr() if result is not None else None),
+                                            C.c_void_p(match.data_ptr() if match is not None else None)))
+        cur.wait_stream(ext)
+        return result, match
 
     def export_state(self):
         """fx_map_export_host (waits for the stream): the map's whole state as the bytes of one snapshot."""

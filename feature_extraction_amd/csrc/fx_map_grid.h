@@ -1,5 +1,6 @@
 // fx_map_grid.h — the hashed grid over the map's live landmarks, which fx_map_merge (csrc/fx_map_merge.hip: a landmark looks for
-// its predecessor) and fx_map_localize (csrc/fx_map_localize.hip: a keypoint looks for its landmark) search.  The kernels that
+// its predecessor), fx_map_localize (csrc/fx_map_localize.hip: a keypoint looks for its landmark) and fx_map_join_segments
+// (csrc/fx_map_join.hip: a landmark of one segment looks for its twin in another) search.  The kernels that
 // build it are csrc/fx_map_grid.hip's; what a search needs on the device is here.
 //
 // A grid is described by an FxMapMergeArgs (fx_device.h): the gate md2 = d d with d the call's distance widened to double, inv_edge
@@ -67,6 +68,30 @@ __device__ __forceinline__ void grid_neighbourhood(const FxMapMergeArgs &A, doub
       for (int ox = -1; ox <= 1; ++ox) visit(bucket_of_cell(cx + ox, cy + oy, A.table));
   }
   visit(A.table);
+}
+// the nearest eligible landmark so far of one query point: smallest d2 (bits), then lowest id
+struct Near {
+  unsigned long long d2;
+  uint32_t id;
+  bool any;
+};
+// One bucket of the nearest search of fx_map_localize's association clause (include/fx.h), which fx_map_join_segments shares:
+// the candidates of bucket b within the gate of (wx, wy), of segment seg (any_seg: of any), with at least min_obs observations and
+// a finite z (the grid holds the merge's live set: the rest of the eligibility is here), by the lowest (d2 bits, id).
+__device__ __forceinline__ void walk_nearest(const FxMapMergeArgs &G, uint32_t min_obs, uint32_t b, double wx, double wy, uint32_t seg,
+                                             bool any_seg, Near &best) {
+  const uint32_t end = min(bucket_end(G, b), G.cap);
+  for (uint32_t p = bucket_begin(G, b); p < end; ++p) {
+    const FxMapMergeCand c = G.cand[p];
+    const double dx = c.x - wx, dy = c.y - wy;
+    const double d2 = dx * dx + dy * dy;
+    if (!(d2 <= G.md2) || !(any_seg || c.segment == seg) || c.id >= G.cap) continue;
+    const unsigned long long k = (unsigned long long)__double_as_longlong(d2);
+    if (best.any && !(k < best.d2 || (k == best.d2 && c.id < best.id))) continue;
+    const fx_map_landmark R = records(G)[c.id];
+    if (R.n_obs < min_obs || !isfinite(R.z)) continue;
+    best.any = true, best.d2 = k, best.id = c.id;
+  }
 }
 }  // namespace fxg
 #endif

@@ -11,34 +11,27 @@
 //                    point under the scan's prior (world_point), the walk over its 3 x 3 cells and the far bucket; the walk
 //                    applies min_landmark_obs, the finite z and the segment to the candidates in reach and keeps the lowest
 //                    (d2 bits, id).  Writes near[r] and d2[r] (scratch), nearest_of_row[r] when given, map_id_of_row[r] = -1
-//   k_loc_consensus  one 256-thread workgroup a scan, shaped like k_register:
+//   k_loc_consensus  one 256-thread workgroup a scan: fx_map_consensus.h's body (rank, hypotheses, refit: shared with
+//                    fx_map_join_segments) over this gather:
 //     gather      the scan's rows with a landmark into LDS in ascending row by ballot + prefix (at most FX_LOC_MAX_CORR)
-//     rank        the pool: the H correspondences of lowest (d2 bits, row), by counting in LDS
-//     hypotheses  the samples dealt to the threads by stride, fp64; a thread walks the correspondences once (all lanes read the
-//                 same LDS address, a broadcast); (count, lowest sample) reduced by shuffles, then over the wavefronts in LDS
-//     refit       thread 0 runs the sequential fp64 sums; the membership tests between them are dealt to all threads
-//   The hypothesis, the agreement test and the refit are fx_consensus.h's, which fx_register.hip instantiates in fp32.
-// LDS of k_loc_consensus: 1024 x (32 B of xy + 8 B of d2 bits + 8 B of t_z - q_z + 4 B row + 4 B flags) + the pool = 57.9 KB.
+// LDS of k_loc_consensus: fx_map_consensus.h's 57.9 KB.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
-#include "fx_consensus.h"
+#include "fx_map_consensus.h"
 #include "fx_map_grid.h"
 #include "../../include/fx.h"
 
 using namespace fxc;
 using namespace fxg;
 
-#define FXL_WG 256
-#define FXL_NWAVE (FXL_WG / 64)
-#define FXL_MAX_HYP 128u
-#define FXL_IDX_BITS 13  // samples of a pool of 128: 8128 < 2^13
+#define FXL_WG FXC_MAP_WG
+#define FXL_NWAVE FXC_MAP_NWAVE
 
 static_assert(sizeof(fx_localization) == 112 && sizeof(fx_localize_options) == 32 && sizeof(fx_pose) == 48, "include/fx.h");
-static_assert(FXL_MAX_HYP * (FXL_MAX_HYP - 1u) / 2u < (1u << FXL_IDX_BITS), "sample index bits");
-static_assert(FX_LOC_MAX_CORR < (1u << (32 - FXL_IDX_BITS)), "count bits");
+static_assert(FX_LOC_MAX_CORR == FXC_MAP_MAX_CORR, "fx_map_consensus.h");
 
 extern "C" hipError_t fxk_map_grid_build(hipStream_t s, const FxMapMergeArgs &A);
 extern "C" size_t fxk_map_merge_scratch(FxMapMergeArgs *A, uint8_t *base);
@@ -61,26 +54,8 @@ __device__ __forceinline__ bool wanted_segment(const FxMapLocalizeArgs &A, uint3
   }
   return true;
 }
-// the nearest eligible landmark so far of one row: smallest d2 (bits), then lowest id
-struct Near {
-  unsigned long long d2;
-  uint32_t id;
-  bool any;
-};
 __device__ __forceinline__ void walk(const FxMapLocalizeArgs &A, uint32_t b, double wx, double wy, uint32_t seg, bool any_seg, Near &best) {
-  const FxMapMergeArgs &G = A.G;
-  const uint32_t end = min(bucket_end(G, b), G.cap);
-  for (uint32_t p = bucket_begin(G, b); p < end; ++p) {
-    const FxMapMergeCand c = G.cand[p];
-    const double dx = c.x - wx, dy = c.y - wy;
-    const double d2 = dx * dx + dy * dy;
-    if (!(d2 <= G.md2) || !(any_seg || c.segment == seg) || c.id >= G.cap) continue;
-    const unsigned long long k = (unsigned long long)__double_as_longlong(d2);
-    if (best.any && !(k < best.d2 || (k == best.d2 && c.id < best.id))) continue;
-    const fx_map_landmark R = records(G)[c.id];  // (the grid holds the merge's live set: the rest of the eligibility is here)
-    if (R.n_obs < A.min_landmark_obs || !isfinite(R.z)) continue;
-    best.any = true, best.d2 = k, best.id = c.id;
-  }
+  walk_nearest(A.G, A.min_landmark_obs, b, wx, wy, seg, any_seg, best);
 }
 __device__ __forceinline__ void write_no_fit(fx_localization *out, const fx_pose &prior, uint32_t n_corr, uint32_t flags) {
   fx_localization r;
@@ -128,15 +103,7 @@ extern "C" __global__ __launch_bounds__(FXL_WG) void k_loc_search(FxMapLocalizeA
 }
 
 extern "C" __global__ __launch_bounds__(FXL_WG) void k_loc_consensus(FxMapLocalizeArgs A) {
-  __shared__ double4 s_xy[FX_LOC_MAX_CORR];             // (qx, qy, tx, ty): the world point under the prior, the landmark
-  __shared__ unsigned long long s_d2[FX_LOC_MAX_CORR];  // d2 bits of the association
-  __shared__ double s_dz[FX_LOC_MAX_CORR];              // t_z - q_z
-  __shared__ uint32_t s_row[FX_LOC_MAX_CORR];
-  __shared__ uint32_t s_flag[FX_LOC_MAX_CORR];  // bit 0 / 1 = member of the first / second inlier set
-  __shared__ uint32_t s_pool[FXL_MAX_HYP];      // pool rank -> correspondence
-  __shared__ uint32_t s_wave[FXL_NWAVE];
-  __shared__ Fit s_fit;
-  __shared__ uint32_t s_final;  // the flag bit of the final inlier set
+  __shared__ MapConsensusLds L;
 
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, b = blockIdx.x;
   const uint32_t S = loc_scans(A), rows = loc_rows(A);
@@ -152,118 +119,52 @@ extern "C" __global__ __launch_bounds__(FXL_WG) void k_loc_consensus(FxMapLocali
   const uint32_t q_lo = min(off[b], rows), q_hi = max(min(off[b + 1u], rows), q_lo);
 
   // ---- gather: the correspondences in ascending row, the first FX_LOC_MAX_CORR kept
-  uint32_t found = 0u;  // (uniform)
-  for (unsigned long long r0 = q_lo; r0 < q_hi && found <= FX_LOC_MAX_CORR; r0 += FXL_WG) {
-    const uint32_t i = (uint32_t)min(r0 + tid, (unsigned long long)q_hi);
-    int32_t g = -1;
-    if (i < q_hi) g = A.near[i];
-    const bool ok = g >= 0 && (uint32_t)g < A.G.cap;
-    const unsigned long long bal = __ballot(ok);
-    if (lane == 0u) s_wave[wave] = (uint32_t)__popcll(bal);
-    __syncthreads();
-    uint32_t before = 0u, all = 0u;
+  auto gather = [&](MapConsensusLds &L) {
+    uint32_t found = 0u;  // (uniform)
+    for (unsigned long long r0 = q_lo; r0 < q_hi && found <= FX_LOC_MAX_CORR; r0 += FXL_WG) {
+      const uint32_t i = (uint32_t)min(r0 + tid, (unsigned long long)q_hi);
+      int32_t g = -1;
+      if (i < q_hi) g = A.near[i];
+      const bool ok = g >= 0 && (uint32_t)g < A.G.cap;
+      const unsigned long long bal = __ballot(ok);
+      if (lane == 0u) L.wave[wave] = (uint32_t)__popcll(bal);
+      __syncthreads();
+      uint32_t before = 0u, all = 0u;
 #pragma unroll
-    for (uint32_t w = 0; w < FXL_NWAVE; ++w) {
-      const uint32_t n = s_wave[w];
-      before += w < wave ? n : 0u;
-      all += n;
+      for (uint32_t w = 0; w < FXL_NWAVE; ++w) {
+        const uint32_t n = L.wave[w];
+        before += w < wave ? n : 0u;
+        all += n;
+      }
+      const uint32_t slot = found + before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+      if (ok && slot < FX_LOC_MAX_CORR) {
+        const fx_map_landmark R = rec[g];
+        double wx, wy, wz;
+        world_point(prior, kp[i], wx, wy, wz);
+        L.xy[slot] = make_double4(wx, wy, R.x, R.y);
+        L.dz[slot] = R.z - wz;
+        L.d2[slot] = A.d2[i];
+        L.row[slot] = i;
+      }
+      found += all;
+      __syncthreads();  // (L.wave is written again next round)
     }
-    const uint32_t slot = found + before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
-    if (ok && slot < FX_LOC_MAX_CORR) {
-      const fx_map_landmark R = rec[g];
-      double wx, wy, wz;
-      world_point(prior, kp[i], wx, wy, wz);
-      s_xy[slot] = make_double4(wx, wy, R.x, R.y);
-      s_dz[slot] = R.z - wz;
-      s_d2[slot] = A.d2[i];
-      s_row[slot] = i;
-    }
-    found += all;
-    __syncthreads();  // (s_wave is written again next round)
-  }
-  const uint32_t n_corr = min(found, FX_LOC_MAX_CORR);
-  uint32_t flags = found > FX_LOC_MAX_CORR ? FX_LOC_TRUNCATED : 0u;
-  const uint32_t H = min(n_corr, A.hyp_corr);
-
-  // ---- rank the pool: correspondence i has rank #{j : (d2_j, j) < (d2_i, i)} (rows ascend with i); ranks below H are the pool
-  for (uint32_t i = tid; i < n_corr; i += FXL_WG) {
-    const unsigned long long di = s_d2[i];
-    uint32_t rank = 0u;
-    for (uint32_t j = 0; j < n_corr && rank < H; ++j) {
-      const unsigned long long dj = s_d2[j];
-      rank += (dj < di || (dj == di && j < i)) ? 1u : 0u;
-    }
-    if (rank < H) s_pool[rank] = i;
-  }
-  __syncthreads();
-
-  // ---- hypotheses: key = count << 13 | (8191 - sample), the maximum wins: most agreeing, then the lowest sample
-  const double idd = (double)A.inlier_dist, mbd = (double)A.min_baseline;
-  const double mb2 = mbd * mbd, gate = 2.0 * idd, id2 = idd * idd;
-  const uint32_t n_samples = H * (H - (H ? 1u : 0u)) / 2u;
-  uint32_t best = 0u;
-  for (uint32_t idx = tid; idx < n_samples; idx += FXL_WG) {
-    uint32_t a, c;
-    sample_ranks(idx, H, a, c);
-    Hyp<double> h;
-    if (!hypothesis(s_xy[s_pool[a]], s_xy[s_pool[c]], mb2, gate, h)) continue;
-    uint32_t count = 0u;
-    for (uint32_t i = 0; i < n_corr; ++i) count += agrees(h, s_xy[i], id2) ? 1u : 0u;
-    if (count >= 2u) best = max(best, (count << FXL_IDX_BITS) | (((1u << FXL_IDX_BITS) - 1u) - idx));
-  }
-#pragma unroll
-  for (int o = 32; o; o >>= 1) best = max(best, (uint32_t)__shfl_xor((int)best, o, 64));
-  if (lane == 0u) s_wave[wave] = best;
-  __syncthreads();
-  best = max(max(s_wave[0], s_wave[1]), max(s_wave[2], s_wave[3]));
-
-  if (!best) {  // (uniform) fewer than 2 correspondences, or no sample passed the gates with 2 agreeing
-    if (tid == 0u) write_no_fit(out, prior, n_corr, flags | FX_LOC_NO_HYPOTHESIS);
+    return found;
+  };
+  MapConsensusOut O;
+  const bool fitted = map_consensus(L, gather, A.inlier_dist, A.min_baseline, A.hyp_corr, O);
+  const uint32_t flags = O.truncated ? FX_LOC_TRUNCATED : 0u;
+  if (!fitted) {  // (uniform) fewer than 2 correspondences, or no sample passed the gates with 2 agreeing
+    if (tid == 0u) write_no_fit(out, prior, O.n_corr, flags | FX_LOC_NO_HYPOTHESIS);
     return;
   }
-
-  // ---- the winner's agreeing set (bit 0): the same operations give the same bits
-  uint32_t wa, wb;
-  sample_ranks(((1u << FXL_IDX_BITS) - 1u) - (best & ((1u << FXL_IDX_BITS) - 1u)), H, wa, wb);
-  const uint32_t n0 = best >> FXL_IDX_BITS;
-  Hyp<double> h0;
-  (void)hypothesis(s_xy[s_pool[wa]], s_xy[s_pool[wb]], mb2, gate, h0);
-  for (uint32_t i = tid; i < n_corr; i += FXL_WG) s_flag[i] = agrees(h0, s_xy[i], id2) ? 1u : 0u;
-  __syncthreads();
   if (tid == 0u) {
-    Fit f;
-    f.c = h0.c, f.s = h0.s;
-    fit_set(s_xy, s_flag, n_corr, 1u, n0, f);
-    s_fit = f;
-  }
-  __syncthreads();
-  // ---- the set the first fit agrees with (bit 1)
-  {
-    const Fit f = s_fit;
-    for (uint32_t i = tid; i < n_corr; i += FXL_WG) s_flag[i] |= residual2(f, s_xy[i]) <= id2 ? 2u : 0u;
-  }
-  __syncthreads();
-  if (tid == 0u) {
-    Fit f = s_fit;
-    uint32_t n1 = 0u;
-    for (uint32_t i = 0; i < n_corr; ++i) n1 += (s_flag[i] >> 1) & 1u;
-    uint32_t bit = 1u, n = n0;
-    if (n1 >= 2u) {
-      bit = 2u, n = n1;
-      fit_set(s_xy, s_flag, n_corr, bit, n, f);
-    }
-    double sz = 0.0, sr = 0.0;
-    for (uint32_t i = 0; i < n_corr; ++i)
-      if (s_flag[i] & bit) {
-        sz += s_dz[i];
-        sr += residual2(f, s_xy[i]);
-      }
     fx_localization r;
     r.pose = prior;
-    r.dc = f.c, r.ds = f.s, r.dtx = f.tx, r.dty = f.ty, r.dtz = sz / (double)n;
-    r.rms = (float)sqrt(sr / (double)n);
-    r.n_corr = n_corr, r.n_inliers = n, r.flags = flags | (n >= A.min_inliers ? FX_LOC_VALID : 0u);
-    r.hyp_a = s_row[s_pool[wa]], r.hyp_b = s_row[s_pool[wb]];
+    r.dc = O.dc, r.ds = O.ds, r.dtx = O.dtx, r.dty = O.dty, r.dtz = O.dtz;
+    r.rms = O.rms;
+    r.n_corr = O.n_corr, r.n_inliers = O.n_inliers, r.flags = flags | (O.n_inliers >= A.min_inliers ? FX_LOC_VALID : 0u);
+    r.hyp_a = O.hyp_a, r.hyp_b = O.hyp_b;
     if (r.flags & FX_LOC_VALID) {  // the track's good-link composition, p = D, r = the prior
       r.pose.c = r.dc * prior.c - r.ds * prior.s;
       r.pose.s = r.ds * prior.c + r.dc * prior.s;
@@ -272,12 +173,10 @@ extern "C" __global__ __launch_bounds__(FXL_WG) void k_loc_consensus(FxMapLocali
       r.pose.tz = prior.tz + r.dtz;
     }
     *out = r;
-    s_final = bit;
   }
-  __syncthreads();
-  const uint32_t bit = s_final;
-  for (uint32_t i = tid; i < n_corr; i += FXL_WG)
-    if (s_flag[i] & bit) A.map_id_of_row[s_row[i]] = A.near[s_row[i]];
+  const uint32_t bit = L.final;
+  for (uint32_t i = tid; i < O.n_corr; i += FXL_WG)
+    if (L.flag[i] & bit) A.map_id_of_row[L.row[i]] = A.near[L.row[i]];
 }
 
 extern "C" hipError_t fxk_map_localize(hipStream_t s, const FxMapLocalizeArgs &A) {

@@ -638,7 +638,8 @@ fx_status fx_track_landmarks(fx_ctx *ctx,
  * only, or and sum), every fp64 value an ordered chain of correctly rounded operations on one lane.
  * Limits: tracks are continued only across an accepted one-scan overlap; a pole seen again after a missed detection, a bad link or
  * after leaving the field of view enters as a new landmark.  fx_map_merge (below) folds such fragments back into one landmark
- * within a segment; across segments and after long drift they stay apart (no loop closure: fx_map_relocalize finds the pose of a
+ * within a segment and fx_map_join_segments (below) brings two segments a bad link left into one frame; after long drift fragments
+ * stay apart (no loop closure: fx_map_relocalize finds the pose of a
  * scan in the map without a prior and fx_map_localize refines it, which closing one would start from).  The equality with one batch of the whole run
  * holds for min_obs == 2; with a larger min_obs a track that a batch edge cuts into pieces that are each too short is missed.
  * n_obs and n_needed are 32-bit counts.  FX_MAP_FULL is sticky and n_needed only rises under fx_map_update; fx_map_compact (below)
@@ -715,7 +716,8 @@ fx_status fx_map_read_landmarks(fx_ctx *ctx, fx_map *map, uint32_t first, uint32
  * FX_ERR_INVALID_ARG with the reason in fx_last_error(), nothing launched, the map unchanged: a NULL ctx or map (fx_map_get_alias:
  * a NULL out pointer), a map of another context, merge_dist not finite and positive, max_gap_scans == 0, result_device not 4-byte
  * aligned; fx_map_read_alias: entries outside max_landmarks.
- * Limits: merging happens within one segment only (no loop closure; fx_map_relocalize and fx_map_localize, below, give the
+ * Limits: merging happens within one segment only (fx_map_join_segments, below, makes one segment of two; no loop closure:
+ * fx_map_relocalize and fx_map_localize, below, give the
  * transform between a scan's frame and the map's, without and with a prior pose; they join nothing).  Chained merges of one call may join A and C that are up to
  * 2 merge_dist apart, through B.  The map_id_of_row arrays of earlier batches keep the absorbed ids: resolve them through the
  * alias table (id = alias[id] >= 0 ? alias[id] : id); the absorbed records, their sums and their alias entries stay until
@@ -789,7 +791,7 @@ fx_status fx_map_read_alias(fx_ctx *ctx, fx_map *map, uint32_t first, uint32_t c
  * total order, every fp64 sum an ordered chain on one lane.  The search structure (fx_map_merge's hashed grid, cell edge
  * sd (1 + 2^-8)) never shows in the result.
  * Limits: a prior is needed: fx_map_relocalize (below) produces one from the map's geometry alone (the map stores no descriptors),
- * and this call refines it; the call joins no segments and
+ * and this call refines it; the call joins no segments (fx_map_join_segments, below, does, and takes a record's dc as its prior) and
  * re-estimates no landmark: it produces the poses and the row-to-landmark table both would start from.  A cell of the grid that
  * holds very many landmarks is walked by one lane a row.  New in 0.7 (added symbols only). */
 #define FX_LOC_MAX_CORR 1024u
@@ -881,8 +883,8 @@ fx_status fx_map_localize(fx_ctx *ctx, fx_map *map,
  * Limits: the pose is that of ONE two-point hypothesis, centimetres off under noise: refine it with fx_map_localize.  The work
  * grows with seeds x eligible landmarks x the landmarks whose distance matches the seed x keypoints, and the rivals cost a second
  * pass; max_seeds and max_baseline bound it.  A scan whose poles repeat a pattern of the map (a row, a lattice) comes back
- * AMBIGUOUS; a scan of fewer than three poles the map holds cannot be VALID.  The call joins no segments and writes nothing to
- * the map.  New in 0.7 (added symbols only). */
+ * AMBIGUOUS; a scan of fewer than three poles the map holds cannot be VALID.  The call joins no segments (fx_map_join_segments,
+ * below) and writes nothing to the map.  New in 0.7 (added symbols only). */
 #define FX_RELOC_MAX_KP 64u
 typedef struct fx_relocalize_options {   /* 40 B */
   float inlier_dist;      /* a keypoint lands on a landmark within this xy distance, m; finite, > 0; default 0.30 */
@@ -984,6 +986,107 @@ fx_status fx_map_compact(fx_ctx *ctx, fx_map *map, const fx_map_compact_options 
 fx_status fx_map_export_host(fx_ctx *ctx, fx_map *map, void *dst_host, size_t capacity, size_t *bytes_out);
 fx_status fx_map_import_host(fx_ctx *ctx, fx_map *map, const void *src_host, size_t bytes);
 fx_status fx_map_snapshot_check(const void *src_host, size_t bytes, uint32_t max_landmarks, uint32_t max_carry_rows); /* Host only */
+
+/* ---- Joining two segments of the map: one frame again after a bad link ----
+ * fx_track_landmarks holds the pose over an unusable link and starts a new segment; fx_map_update numbers it globally, and from
+ * there on the map is two maps in two frames: fx_map_merge merges within a segment, fx_map_localize looks at one segment, and the
+ * snapshot carries the split to the next run.  fx_map_join_segments brings the landmarks of segment src into the frame of
+ * segment dst and gives both one label: it associates src's landmarks with dst's under a PRIOR transform, fits the correction
+ * with fx_map_localize's consensus, moves src's sums, anchors and records, and renumbers the segments.  It is enqueued on the
+ * context's stream (no host synchronisation, no allocation in the steady state: its scratch is the context-owned buffer the
+ * other map calls share, grown as needed).  Every floating-point step is fp64, no contraction, no fma.
+ * Prior: prior_host (c, s, tx, ty, tz; segment and flags are ignored), or prior_device, five doubles c, s, tx, ty, tz read on
+ * the device when the call runs (the address of an fx_localization's dc, so that localise-then-join needs no host read), or
+ * neither: the identity.  After ONE bad link the held pose leaves src's frame within one link's motion of dst's, which
+ * search_dist covers.  The prior takes src's frame to dst's.
+ * ONE CALL, with N = header.n_landmarks and SEG = header.segments as they are when the call runs on the stream:
+ * Device refusals: src_segment >= SEG or dst_segment >= SEG gives FX_JOIN_BAD_SEGMENT, a prior_device with a double that is
+ * not finite FX_JOIN_BAD_PRIOR (both may be set).  The map is bit for bit unchanged; the result is T = the prior's five doubles
+ * as they are, D = the identity (dc = 1, ds = dtx = dty = dtz = 0), rms = +inf, n_src = n_corr = n_inliers = moved = 0, label =
+ * hyp_a = hyp_b = 0xffffffff, segments = SEG, and every word of match_of_landmark is -1.
+ * Targets: g < N is a target iff alias[g] == -1, n_obs >= min_landmark_obs, its x, y and z are finite and segment == dst:
+ * fx_map_localize's eligibility clause.
+ * Queries: i < N under the same test with segment == src, in ascending id; n_src is their number.  The point of a query is its
+ * record under the prior (pc, ps, ptx, pty, ptz): wx = (pc x - ps y) + ptx, wy = (ps x + pc y) + pty, wz = z + ptz.
+ * Association: fx_map_localize's clause word for word with the query's point for the row's: dx = x[g] - wx, dy = y[g] - wy, d2 =
+ * dx dx + dy dy; g is in reach iff d2 <= sd sd, sd = (double)search_dist; the target of a query is the one in reach of lowest
+ * (d2 as uint64 bits, id).  Several queries may pick the same target.
+ * Correspondences: the queries that have a target, in ascending id; the first FX_JOIN_MAX_CORR are used (FX_JOIN_TRUNCATED when
+ * there are more); n_corr is the number used.  Correspondence k carries q = (wx, wy, wz) and t = (x, y, z) of its target.
+ * Hypothesis stage and refit: fx_map_localize's clauses word for word (the same device code) with the query's id in the place of
+ * the row: the pool is the H = min(n_corr, hyp_corr) correspondences of lowest (d2 bits, query id).  Without a hypothesis:
+ * FX_JOIN_NO_HYPOTHESIS, D = the identity, rms = +inf, n_inliers = 0, hyp_a = hyp_b = 0xffffffff.  Otherwise (dc, ds, dtx, dty,
+ * dtz), rms and n_inliers are the final fit, hyp_a and hyp_b the query ids of the winning sample, and FX_JOIN_FITTED is set
+ * iff n_inliers >= min_inliers.
+ * Transform: with FX_JOIN_FITTED, T = D o prior by fx_map_localize's Pose clause: c = dc pc - ds ps, s = ds pc + dc ps, tx =
+ * (dc ptx - ds pty) + dtx, ty = (ds ptx + dc pty) + dty, tz = ptz + dtz.  Otherwise T is the prior's five doubles, bit for bit; D
+ * is reported all the same.  mode FX_JOIN_GIVEN skips association and fit: T = the prior, D = the identity, rms = +inf, n_src =
+ * n_corr = n_inliers = 0, hyp_a = hyp_b = 0xffffffff.
+ * match_of_landmark (when given): all max_landmarks words are written; word i is the target of query i when i is in the final
+ * inlier set, -1 everywhere else.
+ * Apply: the map is changed iff mode == FX_JOIN_GIVEN, or mode == FX_JOIN_FIT and FX_JOIN_FITTED holds; FX_JOIN_APPLIED is then
+ * set.  FX_JOIN_DRY_RUN fits and reports and changes no byte of the map.  Without FX_JOIN_APPLIED moved = 0, label = 0xffffffff,
+ * segments = SEG and the map is bit for bit unchanged.  With it:
+ *   moved = the number of landmarks i < N with segment == src, absorbed ones included (their frozen records and sums move with
+ *   the rest, so the snapshot stays consistent).  For each of them, with n = (double)n_obs and the sums of fx_map_update:
+ *   Sx' = (c Sx - s Sy) + n tx, Sy' = (s Sx + c Sy) + n ty, Sz' = Sz + n tz; ax' = (c ax - s ay) + tx, ay' = (s ax + c ay) + ty;
+ *   Dx' = c Dx - s Dy, Dy' = s Dx + c Dy; Q is unchanged.  Then its x, y, z and rms_xy are recomputed from the new sums by
+ *   fx_map_update's "Records" clause (a landmark of n_obs == 0, which no update makes, keeps its record).  Every landmark reads
+ *   and writes its own slot only.
+ *   Labels: with lo = min(src, dst) and hi = max(src, dst), every i < N gets segment' = hi - 1 when segment == lo, segment - 1
+ *   when segment > lo, segment otherwise; header.segments = SEG - 1; label = hi - 1.  The joined segment keeps the later label
+ *   and labels stay dense: when the run's current segment (SEG - 1) takes part it is segments - 1 afterwards, and the next
+ *   accepted overlap numbers its new landmarks into the joined segment.  A caller that holds segment numbers from before the
+ *   call (an fx_relocalization's pose.segment, an opt.segment) renumbers them by the same rule.
+ *   last_pose: iff SEG - 1 == src, its five doubles become T o last_pose by the composition above (p = T, r = last_pose); its
+ *   segment and flags stay.  Every other header word, the carry, the carry scan and the alias table stay; ids do not change.
+ * result (when given): T, D, rms, n_src, n_corr, n_inliers, flags, moved, label, segments = header.segments after the call,
+ * hyp_a, hyp_b.
+ * Order of calls: join between an fx_map_update and the next fx_track_landmarks, and read last_pose afterwards for its
+ * init_pose_host: the track then continues in dst's frame.
+ * FX_ERR_INVALID_ARG with the reason in fx_last_error(), nothing launched, no byte touched: a NULL ctx or map, a map of another
+ * context, src_segment == dst_segment, both prior pointers given, a prior_host whose c, s, tx, ty or tz is not finite,
+ * search_dist, inlier_dist or min_baseline not finite and positive, hyp_corr outside 2..128, min_inliers < 2, min_landmark_obs
+ * == 0, mode > 2, reserved != 0, prior_device or result_device not 8-byte aligned, match_of_landmark_device not 4-byte aligned.
+ * The same bytes from run to run and with any number of contexts in flight: every decision is an integer (an integer prefix,
+ * 32-bit integer sums) or a minimum over a total order, every fp64 value an ordered chain on one lane.  The search structure
+ * (fx_map_merge's hashed grid, cell edge sd (1 + 2^-8)) never shows in a byte; numpy float64 reproduces the call bit for bit.
+ * Limits: the duplicates of one pole now share a segment and are fx_map_merge's to join; they are disjoint in time across the
+ * cut, and a caller that closes a long loop raises max_gap_scans.  Q is kept, so rms_xy is exact only for c c + s s = 1 (a
+ * fitted or composed T is that within rounding).  One call makes one join.  There is no pose graph: the poses and
+ * map_id_of_row arrays handed out earlier are not revised.  New in 0.7 (added symbols only). */
+#define FX_JOIN_MAX_CORR 1024u
+#define FX_JOIN_FIT 0u      /* mode: fit T from the two segments' landmarks under the prior, apply it */
+#define FX_JOIN_GIVEN 1u    /* apply the prior as T, fit nothing */
+#define FX_JOIN_DRY_RUN 2u  /* fit and report, change no byte of the map */
+typedef struct fx_map_join_options {   /* 32 B */
+  float search_dist;      /* as fx_localize_options; default 2.0 */
+  float inlier_dist;      /* default 0.30 */
+  float min_baseline;     /* default 2.0 */
+  uint32_t hyp_corr;      /* 2..128, default 64 */
+  uint32_t min_inliers;   /* >= 2, default 3 */
+  uint32_t min_landmark_obs; /* >= 1, default 2 */
+  uint32_t mode;          /* FX_JOIN_FIT (default), FX_JOIN_GIVEN, FX_JOIN_DRY_RUN */
+  uint32_t reserved;      /* 0 */
+} fx_map_join_options;
+#define FX_JOIN_APPLIED 0x1u        /* the map was changed: src's landmarks moved by T, the segments renumbered */
+#define FX_JOIN_TRUNCATED 0x2u      /* more than FX_JOIN_MAX_CORR correspondences: the first 1024 in id order were used */
+#define FX_JOIN_NO_HYPOTHESIS 0x4u  /* fewer than 2 correspondences, or no sample passed the gates */
+#define FX_JOIN_BAD_PRIOR 0x8u      /* a double of prior_device is not finite */
+#define FX_JOIN_BAD_SEGMENT 0x10u   /* src_segment or dst_segment is not below header.segments */
+#define FX_JOIN_FITTED 0x20u        /* a correction was fitted to >= min_inliers correspondences: T = D o prior */
+typedef struct fx_map_join_result {    /* 120 B */
+  double c, s, tx, ty, tz;        /* T: src's frame -> dst's frame */
+  double dc, ds, dtx, dty, dtz;   /* D: the fitted correction, T = D o prior */
+  float rms;
+  uint32_t n_src, n_corr, n_inliers, flags, moved, label, segments;
+  uint32_t hyp_a, hyp_b;          /* query ids of the winning sample, 0xffffffff: none */
+} fx_map_join_result;
+void fx_map_join_options_default(fx_map_join_options *o);
+fx_status fx_map_join_segments(fx_ctx *ctx, fx_map *map, uint32_t src_segment, uint32_t dst_segment,
+    const fx_pose *prior_host /* or NULL */, const double *prior_device /* 5 doubles c, s, tx, ty, tz, or NULL */,
+    const fx_map_join_options *opt /* NULL: defaults */, fx_map_join_result *result_device /* or NULL */,
+    int32_t *match_of_landmark_device /* [max_landmarks] or NULL */);
 
 /* Rotation matrix of rotateCloud (ref: node.cpp:161-164): R = Ry(pitch)*Rx(roll)
  * through Eigen's AngleAxisf -> Quaternionf -> toRotationMatrix, all float. Host only. */

@@ -36,6 +36,15 @@ times fx_map_relocalize on the same synthetic maps (built by one update, not mer
 the 64 poles nearest to a random position inside the map, seen from a random pose there; default options (16 seeds).  One pair of
 HIP events around the call.  Reported per size: the median time of a call, the time per scan, how many scans came back VALID and
 the mean n_hyp of a scan.  No target is set.
+  timeout -k 10 600 python tools/map_times.py --join [--sizes 1000,100000,1000000] [--warmup 1] [--repeats 5] [--out profiles/map_join_times.txt]
+
+times fx_map_join_segments on the same synthetic maps with the link between scans 1 and 2 made unusable: the first fragments (two
+thirds of the landmarks) are segment 0, the second fragments (a third, up to 0.2 m beside their poles) segment 1, in one frame
+(the motions are the identity), so the identity prior associates every second fragment.  Every repeat resets the map, updates it,
+localises 8 scans of 64 keypoints against it (timed: fx_map_localize on the same map, any segment, the true poses as priors) and
+joins segment 1 into segment 0 (timed: one pair of HIP events around the call: the grid, N / 3 queries, the consensus over the
+first 1024 correspondences, N / 3 landmarks moved, N relabelled).  Reported per size: the medians and the join's result.  No
+target is set.
 """
 import argparse
 import ctypes as C
@@ -290,6 +299,93 @@ def measure_relocalize(ctx, n, warmup, repeats, n_scans=8):
             "valid": int((rec["flags"] & capi.FX_RELOC_VALID != 0).sum()), "n_hyp_mean": float(rec["n_hyp"].mean()), "n_seeds": rec["n_seeds"].tolist()}
 
 
+def measure_join(ctx, n, warmup, repeats, n_scans=8):
+    import torch
+    blk, (S, T), m, inl, reg, M = merge_case(n, np.random.default_rng(n))
+    reg["flags"][1] = 0  # the link scan 2 -> scan 1: the second fragments are a segment of their own
+    kp = (torch.from_numpy(blk).cuda(), S, T)
+    md, inl_t = torch.from_numpy(m.view(np.int32).reshape(-1, 8).copy()).cuda(), torch.from_numpy(inl).cuda()
+    reg_t = torch.from_numpy(reg.view(np.float64).reshape(-1, 8).copy()).cuda()
+    out = ctx.track_landmarks(kp, md, inl_t, reg_t, S, max_landmarks=n)
+    mp = ctx.map_create(n, 16)
+    mp.update(kp, out, overlap=False, row_ids=False)
+    lm = mp.landmarks(0, mp.header()["n_landmarks"])
+    xy = np.stack([lm["x"], lm["y"]], axis=1)
+    rng = np.random.default_rng(n + 1)
+    K = capi.FX_RELOC_MAX_KP
+    rows, pri = np.zeros((n_scans * K, 4), np.float32), np.zeros(n_scans, capi.POSE_DTYPE)
+    for b in range(n_scans):
+        at, yaw = xy[rng.integers(len(xy))] + rng.uniform(-5.0, 5.0, 2), rng.uniform(-np.pi, np.pi)
+        near = np.argsort(((xy - at) ** 2).sum(axis=1))[:K]
+        d = xy[near] - at
+        c, s = np.cos(yaw), np.sin(yaw)
+        rows[b * K:(b + 1) * K, 0], rows[b * K:(b + 1) * K, 1], rows[b * K:(b + 1) * K, 2] = c * d[:, 0] + s * d[:, 1], -s * d[:, 0] + c * d[:, 1], 1.0
+        pri[b] = (c, s, at[0], at[1], 0.0, 0, 0)
+    T2 = len(rows)
+    k0, n_blk = capi.keypoint_block_layout(n_scans, T2)
+    sb = np.zeros((n_blk, 4), np.float32)
+    u = sb.view(np.uint32).reshape(-1)
+    u[:4] = (n_scans, T2, 0, T2)
+    u[4:4 + n_scans + 1] = np.arange(n_scans + 1) * K
+    sb[k0:k0 + T2] = rows
+    skp = (torch.from_numpy(sb.view(np.uint8).reshape(-1)).cuda(), n_scans, T2)
+    pri_t = torch.from_numpy(pri.view(np.float64).reshape(-1, 6).copy()).cuda()
+    res = torch.zeros((capi.JOIN_DTYPE.itemsize // 8,), dtype=torch.float64, device="cuda")
+    match = torch.empty((n,), dtype=torch.int32, device="cuda")
+    stream = torch.cuda.ExternalStream(ctx.stream_ptr())
+    torch.cuda.synchronize()
+    t = {"localize_ms": [], "join_ms": []}
+    first, valid = None, 0
+    for rep in range(warmup + repeats):
+        mp.reset()
+        mp.update(kp, out, overlap=False, row_ids=False)
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        e[0].record(stream)
+        recs, _, _ = mp.localize(skp, pri_t, n_scans, nearest=False, segment=capi.FX_LOC_ANY_SEGMENT)
+        e[1].record(stream), e[2].record(stream)
+        mp.join_segments(1, 0, result=res, match=match)
+        e[3].record(stream)
+        ctx.synchronize()
+        got = capi.join_records(res)[0]
+        valid = int((capi.localize_records(recs)["flags"] & capi.FX_LOC_VALID != 0).sum())
+        first = got if first is None else first
+        assert got.tobytes() == first.tobytes() and got["flags"] & capi.FX_JOIN_APPLIED, (got, first)
+        if rep >= warmup:
+            for k, (a, b) in zip(t, ((0, 1), (2, 3))):
+                t[k].append(e[a].elapsed_time(e[b]))
+    hdr = mp.header()
+    mp.close()
+    out = {"landmarks": n, "segments_after": hdr["segments"], "localize_valid": valid,
+           "result": {k: (float(first[k]) if first[k].dtype.kind == "f" else int(first[k])) for k in capi.JOIN_DTYPE.names}}
+    for k, v in t.items():
+        out[k] = statistics.median(v)
+        out[k + "_min_max"] = [min(v), max(v)]
+    return out
+
+
+def main_join(a):
+    sizes = [int(x) for x in a.sizes.split(",")]
+    ctx = capi.Context(capi.params("launch"), capi.limits(2, 1024))
+    rows = [measure_join(ctx, n, a.warmup, a.repeats) for n in sizes]
+    ctx.close()
+    lines = [f"fx_map_join_segments next to fx_map_localize on synthetic maps (tools/map_times.py --join): 1 pole per 250 m^2, a third of the",
+             f"landmarks second fragments in a segment of their own (segment 1 joined into segment 0 under the identity prior); localize: 8 scans",
+             f"of 64 keypoints, any segment; one context, HIP events around each call, median of {a.repeats} after {a.warmup} warm-up; ms",
+             f"{'landmarks':>10} {'queries':>8} {'corr':>6} {'inliers':>8} {'moved':>8} {'flags':>6} {'join':>9} {'join / size before':>19} {'localize':>9} {'valid':>6}"]
+    for k, r in enumerate(rows):
+        ratio = f"{r['join_ms'] / rows[k - 1]['join_ms']:.2f}" if k else "-"
+        q = r["result"]
+        lines.append(f"{r['landmarks']:>10} {q['n_src']:>8} {q['n_corr']:>6} {q['n_inliers']:>8} {q['moved']:>8} {q['flags']:>#6x} {r['join_ms']:>9.3f} {ratio:>19} "
+                     f"{r['localize_ms']:>9.3f} {r['localize_valid']:>6}")
+    s = "\n".join(lines)
+    print(s)
+    print(json.dumps(rows))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(s + "\n")
+
+
 def main_relocalize(a):
     sizes = [int(x) for x in a.sizes.split(",")]
     ctx = capi.Context(capi.params("launch"), capi.limits(2, 1024))
@@ -361,6 +457,7 @@ def main():
     ap.add_argument("--merge", action="store_true", help="time fx_map_merge on synthetic maps instead")
     ap.add_argument("--compact", action="store_true", help="time fx_map_compact on the merged synthetic maps instead")
     ap.add_argument("--relocalize", action="store_true", help="time fx_map_relocalize on the synthetic maps instead (pass --sizes 10000,100000)")
+    ap.add_argument("--join", action="store_true", help="time fx_map_join_segments on two-segment synthetic maps instead")
     ap.add_argument("--sizes", default="1000,100000,1000000")
     ap.add_argument("--scans", type=int, default=1024)
     ap.add_argument("--batch", type=int, default=128)
@@ -377,6 +474,8 @@ def main():
         return main_compact(a)
     if a.relocalize:
         return main_relocalize(a)
+    if a.join:
+        return main_join(a)
     N = 28800
     ctx = capi.Context(capi.params("launch"), capi.limits(a.batch, N, sparse=True))
     scenes = np.stack([capi.synth_scan(capi.synth_cfg(1000 + b)) for b in range(a.scans)])
