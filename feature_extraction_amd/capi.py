@@ -273,6 +273,36 @@ JOIN_DTYPE = np.dtype([("c", "<f8"), ("s", "<f8"), ("tx", "<f8"), ("ty", "<f8"),
 JOIN_DEFAULTS = dict(search_dist=2.0, inlier_dist=0.30, min_baseline=2.0, hyp_corr=64, min_inliers=3, min_landmark_obs=2, mode=FX_JOIN_FIT)
 
 
+class FxMapLoopOptions(C.Structure):
+    _fields_ = [("search_dist", C.c_float), ("inlier_dist", C.c_float), ("min_baseline", C.c_float), ("hyp_corr", C.c_uint32),
+                ("min_inliers", C.c_uint32), ("min_landmark_obs", C.c_uint32), ("segment", C.c_uint32), ("min_loop_scans", C.c_uint32),
+                ("recent_scans", C.c_uint32), ("mode", C.c_uint32), ("loop_first_scan", C.c_uint32), ("loop_last_scan", C.c_uint32),
+                ("pivot_x", C.c_double), ("pivot_y", C.c_double), ("reserved", C.c_uint32)]
+
+
+class FxMapLoopResult(C.Structure):
+    _fields_ = [("c", C.c_double), ("s", C.c_double), ("tx", C.c_double), ("ty", C.c_double), ("tz", C.c_double), ("dc", C.c_double),
+                ("ds", C.c_double), ("dtx", C.c_double), ("dty", C.c_double), ("dtz", C.c_double), ("px", C.c_double), ("py", C.c_double),
+                ("rms", C.c_float), ("n_query", C.c_uint32), ("n_corr", C.c_uint32), ("n_inliers", C.c_uint32), ("flags", C.c_uint32),
+                ("moved", C.c_uint32), ("loop_first_scan", C.c_uint32), ("loop_last_scan", C.c_uint32), ("segment", C.c_uint32),
+                ("hyp_a", C.c_uint32), ("hyp_b", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+FX_LOOP_MAX_CORR = 1024
+FX_LOOP_FIT, FX_LOOP_GIVEN, FX_LOOP_DRY_RUN = 0, 1, 2
+(FX_LOOP_APPLIED, FX_LOOP_TRUNCATED, FX_LOOP_NO_HYPOTHESIS, FX_LOOP_BAD_PRIOR, FX_LOOP_BAD_SEGMENT, FX_LOOP_FITTED,
+ FX_LOOP_TOO_FAR) = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20, 0x40
+FX_LOOP_NONE = 0xffffffff
+# fx_map_loop_result as a numpy record (loop_records)
+LOOP_DTYPE = np.dtype([("c", "<f8"), ("s", "<f8"), ("tx", "<f8"), ("ty", "<f8"), ("tz", "<f8"), ("dc", "<f8"), ("ds", "<f8"), ("dtx", "<f8"),
+                       ("dty", "<f8"), ("dtz", "<f8"), ("px", "<f8"), ("py", "<f8"), ("rms", "<f4"), ("n_query", "<u4"), ("n_corr", "<u4"),
+                       ("n_inliers", "<u4"), ("flags", "<u4"), ("moved", "<u4"), ("loop_first_scan", "<u4"), ("loop_last_scan", "<u4"),
+                       ("segment", "<u4"), ("hyp_a", "<u4"), ("hyp_b", "<u4"), ("reserved", "<u4")])
+LOOP_DEFAULTS = dict(search_dist=2.0, inlier_dist=0.30, min_baseline=2.0, hyp_corr=64, min_inliers=3, min_landmark_obs=2,
+                     segment=FX_LOC_LAST_SEGMENT, min_loop_scans=256, recent_scans=32, mode=FX_LOOP_FIT, loop_first_scan=0, loop_last_scan=0,
+                     pivot_x=0.0, pivot_y=0.0)
+
+
 class FxTimings(C.Structure):
     _fields_ = [("ms", C.c_float * FX_N_STAGES), ("total_ms", C.c_float), ("k_prep_exec_ms", C.c_float)]
 
@@ -301,6 +331,7 @@ EXPORTS = ("fx_version", "fx_check_abi", "fx_status_str", "fx_last_error", "fx_p
            "fx_localize_options_default", "fx_map_localize", "fx_relocalize_options_default", "fx_map_relocalize",
            "fx_map_compact_options_default", "fx_map_compact", "fx_map_export_host", "fx_map_import_host", "fx_map_snapshot_check",
            "fx_map_join_options_default", "fx_map_join_segments",
+           "fx_map_loop_options_default", "fx_map_close_loop", "fx_map_loop_correct_poses",
            "fx_rotation_from_roll_pitch", "fx_sc3d_tables", "fx_sc3d_xaxis", "fx_synth_cfg_vlp16",
            "fx_synth_scan", "fx_unpack_pointcloud2", "fx_pack_pointxyzi")
 # the header's FX_TEST_HOOKS section: exported by lib/libfx_hip_test.so only
@@ -447,6 +478,10 @@ def load():
     lib.fx_map_join_options_default.restype = None
     lib.fx_map_join_segments.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(FxPose), C.c_void_p, C.POINTER(FxMapJoinOptions),
                                          C.c_void_p, C.c_void_p]
+    lib.fx_map_loop_options_default.argtypes = [C.POINTER(FxMapLoopOptions)]
+    lib.fx_map_loop_options_default.restype = None
+    lib.fx_map_close_loop.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(FxPose), C.c_void_p, C.POINTER(FxMapLoopOptions), C.c_void_p, C.c_void_p]
+    lib.fx_map_loop_correct_poses.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
     lib.fx_rotation_from_roll_pitch.argtypes = [C.c_double, C.c_double, _F32P]
     lib.fx_rotation_from_roll_pitch.restype = None
     lib.fx_sc3d_tables.argtypes = [C.c_double, _F32P, _F32P, _F32P, _F32P]
@@ -1567,6 +1602,192 @@ def map_join_reference(state, src, dst, prior=None, **opts):
     return st, res, match
 
 
+# ---- a loop closed in the map (include/fx.h fx_map_close_loop, fx_map_loop_correct_poses)
+def loop_records(out):
+    """A host copy of fx_map_close_loop's result (a torch tensor, or any array of 144 bytes) as a LOOP_DTYPE record array [1]."""
+    if hasattr(out, "detach"):
+        out = out.detach().cpu().numpy()
+    return np.ascontiguousarray(out).view(np.uint8).reshape(-1).view(LOOP_DTYPE).copy()
+
+
+def _loop_weight(t2, s0, s1):
+    """include/fx.h "Weight of a global scan interval": t2 = first_scan + last_scan as an integer."""
+    t2, a, b = int(t2), 2 * int(s0), 2 * int(s1)
+    if t2 <= a:
+        return 0.0
+    if t2 >= b:
+        return 1.0
+    return float(t2 - a) / float(b - a)
+
+
+def _loop_transform(T, px, py, alpha):
+    """include/fx.h "Interpolated transform": T_alpha of T = (c, s, tx, ty, tz) about the pivot, Python floats in the clause's order."""
+    c, s, tx, ty, tz = T
+    if alpha == 1.0:
+        return T
+    cu, su = (1.0 - alpha) + alpha * c, alpha * s
+    nrm = math.sqrt(cu * cu + su * su)
+    ca, sa = cu / nrm, su / nrm
+    gx, gy = (c * px - s * py) + tx, (s * px + c * py) + ty
+    hx, hy = px + alpha * (gx - px), py + alpha * (gy - py)
+    return (ca, sa, hx - (ca * px - sa * py), hy - (sa * px + ca * py), alpha * tz)
+
+
+def _rigid_compose(p, r):
+    """p o r by fx_map_localize's Pose clause."""
+    return (p[0] * r[0] - p[1] * r[1], p[1] * r[0] + p[0] * r[1], (p[0] * r[2] - p[1] * r[3]) + p[2], (p[1] * r[2] + p[0] * r[3]) + p[3], r[4] + p[4])
+
+
+def map_loop_reference(state, prior=None, **opts):
+    """The definition of fx_map_close_loop (include/fx.h) in numpy float64 and Python floats over a map_reference /
+    map_merge_reference state, which is not modified.  prior: (c, s, tx, ty, tz) or None, the identity (a prior that is not finite is
+    the device refusal FX_LOOP_BAD_PRIOR: what a prior_device gives); opts: the fields of fx_map_loop_options (LOOP_DEFAULTS).
+    Every (query, target) pair is looked at: nothing here knows of a grid.  Returns (the new state, the result: a LOOP_DTYPE
+    record, match_of_landmark int32 [max_landmarks])."""
+    f64 = np.float64
+    bad = set(opts) - set(LOOP_DEFAULTS)
+    if bad:
+        raise TypeError(f"unknown loop options {sorted(bad)}")
+    o = dict(LOOP_DEFAULTS, **opts)
+    mode, want = int(o["mode"]), int(o["segment"])
+    sd32, id32, mb32 = np.float32(o["search_dist"]), np.float32(o["inlier_dist"]), np.float32(o["min_baseline"])
+    if not (all(np.isfinite(v) and v > 0 for v in (sd32, id32, mb32)) and 2 <= o["hyp_corr"] <= 128 and o["min_inliers"] >= 2 and
+            o["min_landmark_obs"] >= 1 and 0 <= mode <= 2 and 0 <= o["recent_scans"] < o["min_loop_scans"] and want != FX_LOC_ANY_SEGMENT):
+        raise ValueError("arguments outside what fx_map_close_loop accepts")
+    if mode == FX_LOOP_GIVEN and not (0 <= o["loop_first_scan"] < o["loop_last_scan"] and math.isfinite(o["pivot_x"]) and math.isfinite(o["pivot_y"])):
+        raise ValueError("FX_LOOP_GIVEN needs loop_first_scan < loop_last_scan and a finite pivot")
+    sd, idd, mbd = f64(sd32), f64(id32), f64(mb32)
+    sd2, mb2, gate, id2 = sd * sd, mbd * mbd, f64(2.0) * idd, idd * idd
+    st = dict(state, header=dict(state["header"]), landmarks=[dict(r) for r in state["landmarks"]], acc=[list(a) for a in state["acc"]],
+              carry=list(state["carry"]), carry_kp=state["carry_kp"].copy())
+    H, lms, accs = st["header"], st["landmarks"], st["acc"]
+    N, SEG, scans = min(int(H["n_landmarks"]), len(lms)), int(H["segments"]), int(H["scans"])
+    last = scans - 1
+    alias = [int(a) for a in st.get("alias", [])][:N]
+    alias += [-1] * (N - len(alias))
+    st["alias"] = alias
+    seg_id = want if want != FX_LOC_LAST_SEGMENT else (SEG - 1 if SEG else FX_LOOP_NONE)
+    P = tuple(float(v) for v in (prior if prior is not None else (1.0, 0.0, 0.0, 0.0, 0.0)))[:5]
+    res = np.zeros(1, LOOP_DTYPE)[0]
+    res["c"], res["s"], res["tx"], res["ty"], res["tz"] = P
+    res["dc"], res["rms"], res["segment"] = 1.0, np.inf, seg_id
+    res["loop_first_scan"] = res["loop_last_scan"] = res["hyp_a"] = res["hyp_b"] = FX_LOOP_NONE
+    match = np.full(int(st["max_landmarks"]), -1, np.int32)
+    refuse = (FX_LOOP_BAD_SEGMENT if seg_id >= SEG or scans == 0 else 0) | (0 if all(math.isfinite(v) for v in P) else FX_LOOP_BAD_PRIOR)
+    if refuse:
+        res["flags"] = refuse
+        return st, res, match
+    pc, ps, ptx, pty, ptz = P
+    T, flags, ready = P, 0, False  # ready: T, the bounds and the pivot are set
+    s0 = s1 = FX_LOOP_NONE
+    px = py = 0.0
+    if mode == FX_LOOP_GIVEN:
+        s0, s1, px, py, ready = int(o["loop_first_scan"]), int(o["loop_last_scan"]), float(o["pivot_x"]), float(o["pivot_y"]), True
+    else:
+        seg = np.array([int(r["segment"]) for r in lms[:N]], np.int64)
+        first, last_of = (np.array([int(r[f]) for r in lms[:N]], np.int64) for f in ("first_scan", "last_scan"))
+        lx, ly, lz = (np.array([float(r[f]) for r in lms[:N]], f64) for f in ("x", "y", "z"))
+        elig = np.array([alias[g] == -1 and int(lms[g]["n_obs"]) >= o["min_landmark_obs"] for g in range(N)], bool)
+        if N:
+            elig &= np.isfinite(lx) & np.isfinite(ly) & np.isfinite(lz) & (seg == seg_id)
+        q = np.flatnonzero(elig & (first + int(o["recent_scans"]) >= last))
+        t = np.flatnonzero(elig & (last_of + int(o["min_loop_scans"]) <= last))
+        res["n_query"] = len(q)
+        with np.errstate(all="ignore"):
+            cc, ss, tx_, ty_, tz_ = (f64(v) for v in P)
+            wx, wy, wz = (cc * lx[q] - ss * ly[q]) + tx_, (ss * lx[q] + cc * ly[q]) + ty_, lz[q] + tz_
+            near, d2_of = np.full(len(q), -1, np.int64), np.zeros(len(q), np.uint64)
+            if len(q) and len(t):
+                for lo in range(0, len(q), 256):  # (chunks: [queries, targets] temporaries)
+                    hi = min(lo + 256, len(q))
+                    dx, dy = lx[t][None, :] - wx[lo:hi, None], ly[t][None, :] - wy[lo:hi, None]
+                    d2 = dx * dx + dy * dy
+                    key = np.where(d2 <= sd2, d2, np.inf).view(np.uint64)  # (the bits of +inf are above those of any distance in reach)
+                    j = np.argmin(key, axis=1)  # (the first minimum: ids ascend, so ties go to the lowest id)
+                    dj = d2[np.arange(hi - lo), j]
+                    hit = dj <= sd2
+                    near[lo:hi][hit] = t[j[hit]]
+                    d2_of[lo:hi][hit] = dj.view(np.uint64)[hit]
+            k = np.flatnonzero(near >= 0)
+            flags = FX_LOOP_TRUNCATED if len(k) > FX_LOOP_MAX_CORR else 0
+            k = k[:FX_LOOP_MAX_CORR]
+            n = len(k)
+            res["n_corr"] = n
+            g = near[k]
+            P64 = np.stack([wx[k], wy[k], lx[g], ly[g]], axis=1) if n else np.zeros((0, 4), f64)
+            fitd = _map_consensus(P64, d2_of[k], q[k], lz[g], wz[k], o["hyp_corr"], mb2, gate, id2)
+        if fitd is None:
+            flags |= FX_LOOP_NO_HYPOTHESIS
+        else:
+            (dc, ds, dtx, dty), dtz, final = fitd["fit"], fitd["dtz"], fitd["final"]
+            res["dc"], res["ds"], res["dtx"], res["dty"], res["dtz"], res["rms"] = dc, ds, dtx, dty, dtz, fitd["rms"]
+            res["n_inliers"] = len(final)
+            res["hyp_a"], res["hyp_b"] = fitd["hyp"]
+            qi, gi = q[k[final]], g[final]
+            match[qi] = gi
+            if len(final) >= o["min_inliers"]:
+                flags |= FX_LOOP_FITTED
+                ready = True
+                T = (dc * pc - ds * ps, ds * pc + dc * ps, (dc * ptx - ds * pty) + dtx, (ds * ptx + dc * pty) + dty, ptz + dtz)
+                s0, s1 = int(last_of[gi].max()), int(first[qi].min())
+                sx = sy = 0.0
+                for i in qi.tolist():  # (ascending id)
+                    sx += float(lx[i])
+                    sy += float(ly[i])
+                px, py = sx / float(len(final)), sy / float(len(final))
+    res["c"], res["s"], res["tx"], res["ty"], res["tz"] = T
+    res["loop_first_scan"], res["loop_last_scan"], res["px"], res["py"] = s0, s1, px, py
+    applied = False
+    if ready:
+        if not T[0] > 0.0:
+            flags |= FX_LOOP_TOO_FAR
+        else:
+            applied = mode != FX_LOOP_DRY_RUN
+    if applied:
+        flags |= FX_LOOP_APPLIED
+        moved = 0
+        for i in range(N):
+            R, A = lms[i], accs[i]
+            if int(R["segment"]) != seg_id:
+                continue
+            alpha = _loop_weight(int(R["first_scan"]) + int(R["last_scan"]), s0, s1)
+            if not alpha > 0.0:
+                continue
+            moved += 1
+            c, s, tx, ty, tz = _loop_transform(T, px, py, alpha)
+            n = float(R["n_obs"])
+            sx, sy, sz = (c * A[0] - s * A[1]) + n * tx, (s * A[0] + c * A[1]) + n * ty, A[2] + n * tz
+            ax, ay = (c * A[3] - s * A[4]) + tx, (s * A[3] + c * A[4]) + ty
+            dx, dy = c * A[5] - s * A[6], s * A[5] + c * A[6]
+            A[:7] = [sx, sy, sz, ax, ay, dx, dy]
+            if int(R["n_obs"]):
+                _map_record_from_sums(R, A)
+        if SEG - 1 == seg_id:
+            alpha = _loop_weight(2 * last, s0, s1)
+            if alpha > 0.0:
+                lp = tuple(float(v) for v in H["last_pose"][:5])
+                H["last_pose"] = _rigid_compose(_loop_transform(T, px, py, alpha), lp) + tuple(H["last_pose"][5:])
+        res["moved"] = moved
+    res["flags"] = flags
+    return st, res, match
+
+
+def loop_correct_poses_reference(result, poses, first_global_scan):
+    """The definition of fx_map_loop_correct_poses (include/fx.h): result a LOOP_DTYPE record, poses POSE_DTYPE records of the global
+    scans first_global_scan, first_global_scan + 1, ...  Returns the corrected copy."""
+    out = np.array(poses, POSE_DTYPE).copy()
+    if not int(result["flags"]) & FX_LOOP_APPLIED:
+        return out
+    T = tuple(float(result[k]) for k in ("c", "s", "tx", "ty", "tz"))
+    px, py, s0, s1 = float(result["px"]), float(result["py"]), int(result["loop_first_scan"]), int(result["loop_last_scan"])
+    for b in range(len(out)):
+        alpha = _loop_weight(2 * (int(first_global_scan) + b), s0, s1)
+        if alpha > 0.0:
+            new = _rigid_compose(_loop_transform(T, px, py, alpha), tuple(float(out[k][b]) for k in ("c", "s", "tx", "ty", "tz")))
+            out["c"][b], out["s"][b], out["tx"][b], out["ty"][b], out["tz"][b] = new
+    return out
+
+
 # ---- a scan's pose in the map without a prior (include/fx.h fx_map_relocalize)
 def relocalize_records(out):
     """A host copy of fx_map_relocalize's records (a torch tensor, or any array of n * 96 bytes) as RELOC_DTYPE records."""
@@ -1937,6 +2158,64 @@ class Map:
                                             C.c_void_p(match.data_ptr() if match is not None else None)))
         cur.wait_stream(ext)
         return result, match
+
+    def close_loop(self, prior=None, prior_device=None, result=None, match=None, **opts):
+        """fx_map_close_loop: the recent landmarks of a segment brought onto its old ones, the correction spread over the scans of
+        the loop (include/fx.h).  prior: (c, s, tx, ty, tz) on the host, or prior_device: a device address (an int) or a tensor of
+        five doubles (a view of an fx_localization's dc), or neither: the identity.  opts: the fields of fx_map_loop_options
+        (LOOP_DEFAULTS).  Returns (result, match_of_landmark): device tensors of 144 bytes (loop_records reads it) and torch.int32
+        [max_landmarks]; a tensor given reuses it, False passes NULL (None is returned in its place).  Stream-correct like
+        merge(); never waits for the stream."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        bad = set(opts) - set(LOOP_DEFAULTS)
+        if bad:
+            raise TypeError(f"unknown loop options {sorted(bad)}")
+        o = dict(LOOP_DEFAULTS, **opts)
+        u = lambda k: int(o[k]) & 0xffffffff
+        opt = FxMapLoopOptions(float(o["search_dist"]), float(o["inlier_dist"]), float(o["min_baseline"]), u("hyp_corr"), u("min_inliers"),
+                               u("min_landmark_obs"), u("segment"), u("min_loop_scans"), u("recent_scans"), u("mode"), u("loop_first_scan"),
+                               u("loop_last_scan"), float(o["pivot_x"]), float(o["pivot_y"]), 0)
+        if result is None:
+            result = torch.empty((LOOP_DTYPE.itemsize // 8,), dtype=torch.float64, device=dev)
+        elif result is False:
+            result = None
+        if match is None:
+            match = torch.empty((self.max_landmarks,), dtype=torch.int32, device=dev)
+        elif match is False:
+            match = None
+        for t, size in ((result, LOOP_DTYPE.itemsize), (match, self.max_landmarks * 4)):
+            if t is not None and (t.device != dev or not t.is_contiguous() or t.numel() * t.element_size() != size):
+                raise ValueError(f"outputs must be contiguous tensors of {LOOP_DTYPE.itemsize} and {self.max_landmarks} * 4 bytes on {dev}")
+        pose = FxPose(*(float(v) for v in tuple(prior)[:5]), 0, 0) if prior is not None else None
+        if hasattr(prior_device, "data_ptr"):
+            prior_device = prior_device.data_ptr()
+        cur = torch.cuda.current_stream(dev)
+        ext = torch.cuda.ExternalStream(self.ctx.stream_ptr(), device=dev)
+        ext.wait_stream(cur)
+        check(self.lib.fx_map_close_loop(self.ctx.handle, self.handle, C.byref(pose) if pose is not None else None, C.c_void_p(prior_device),
+                                         C.byref(opt), C.c_void_p(result.data_ptr() if result is not None else None),
+                                         C.c_void_p(match.data_ptr() if match is not None else None)))
+        cur.wait_stream(ext)
+        return result, match
+
+    def loop_correct_poses(self, result, poses, first_global_scan, n_poses=None):
+        """fx_map_loop_correct_poses: poses (a device tensor of fx_pose records, 48 bytes each: those of the global scans
+        first_global_scan, first_global_scan + 1, ...) brought up to date in place by close_loop's result (its device tensor).
+        Stream-correct like merge(); never waits for the stream."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        have = poses.numel() * poses.element_size() // POSE_DTYPE.itemsize
+        n = have if n_poses is None else int(n_poses)
+        if poses.device != dev or result.device != dev or not poses.is_contiguous() or n > have or result.numel() * result.element_size() != LOOP_DTYPE.itemsize:
+            raise ValueError(f"the result must hold {LOOP_DTYPE.itemsize} bytes and poses {n} contiguous fx_pose records on {dev}")
+        cur = torch.cuda.current_stream(dev)
+        ext = torch.cuda.ExternalStream(self.ctx.stream_ptr(), device=dev)
+        ext.wait_stream(cur)
+        check(self.lib.fx_map_loop_correct_poses(self.ctx.handle, C.c_void_p(result.data_ptr()), C.c_void_p(poses.data_ptr()),
+                                                 int(first_global_scan) & 0xffffffff, n))
+        cur.wait_stream(ext)
+        return poses
 
     def export_state(self):
         """fx_map_export_host (waits for the stream): the map's whole state as the bytes of one snapshot."""

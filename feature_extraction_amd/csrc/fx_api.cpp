@@ -99,6 +99,9 @@ hipError_t fxk_map_compact(hipStream_t s, const FxMapCompactArgs &A);
 size_t fxk_map_compact_scratch(FxMapCompactArgs *A, uint8_t *base);
 hipError_t fxk_map_join(hipStream_t s, const FxMapJoinArgs &A);
 size_t fxk_map_join_scratch(FxMapJoinArgs *A, uint8_t *base);
+hipError_t fxk_map_loop(hipStream_t s, const FxMapLoopArgs &A);
+hipError_t fxk_map_loop_poses(hipStream_t s, const void *result, void *poses, uint32_t first, uint32_t n);
+size_t fxk_map_loop_scratch(FxMapLoopArgs *A, uint8_t *base);
 #ifdef FX_TEST_HOOKS
 void fxk_test_sort_replay(hipStream_t s, const uint32_t *sizes, uint32_t n_seq, uint32_t n, uint32_t *perm);
 void fxk_test_elevation(hipStream_t s, const float *xyz, uint32_t n, const double *tab, float *fast, uint8_t *ok, float *exact);
@@ -271,7 +274,8 @@ struct fx_ctx {
   DevScratch merge_scratch;  // fx_map_merge: the grid (bucket counts, landmarks in bucket order), proposals, kept links;
                              // fx_map_localize: the same grid, then each row's landmark and distance;
                              // fx_map_compact: the marks, the new ids, the blocks' counts, the kept records and sums staged;
-                             // fx_map_join_segments: the grid, each query's target and distance, the list of correspondences
+                             // fx_map_join_segments, fx_map_close_loop: the grid, each query's target and distance, the list of
+                             // correspondences
   // fx_map_import_host: the snapshot's bytes, pinned, until the copies enqueued from them are done (snap_ev)
   uint8_t *snap_h = nullptr;
   size_t snap_bytes = 0;
@@ -2142,6 +2146,78 @@ fx_status fx_map_join_segments(fx_ctx *c, fx_map *m, uint32_t src, uint32_t dst,
   FX_TRY(c->merge_scratch.reserve(c, fxk_map_join_scratch(&A, nullptr), "map join scratch"));
   (void)fxk_map_join_scratch(&A, c->merge_scratch.d);
   FX_HIP(fxk_map_join(c->stream, A));
+  return FX_OK;
+}
+
+void fx_map_loop_options_default(fx_map_loop_options *o) {
+  if (!o) return;
+  memset(o, 0, sizeof *o);
+  o->search_dist = 2.0f;
+  o->inlier_dist = 0.30f;
+  o->min_baseline = 2.0f;
+  o->hyp_corr = 64u;
+  o->min_inliers = 3u;
+  o->min_landmark_obs = 2u;
+  o->segment = FX_LOC_LAST_SEGMENT;
+  o->min_loop_scans = 256u;
+  o->recent_scans = 32u;
+  o->mode = FX_LOOP_FIT;
+}
+
+fx_status fx_map_close_loop(fx_ctx *c, fx_map *m, const fx_pose *prior_host, const double *prior_device, const fx_map_loop_options *opt,
+                            fx_map_loop_result *result, int32_t *match_of_landmark) {
+  if (!c || !m) return fail(FX_ERR_INVALID_ARG, "null argument");
+  if (m->ctx != c) return fail(FX_ERR_INVALID_ARG, "the map belongs to another context");
+  if (prior_host && prior_device) return fail(FX_ERR_INVALID_ARG, "give the prior on the host or on the device, not both");
+  if (prior_host && !(std::isfinite(prior_host->c) && std::isfinite(prior_host->s) && std::isfinite(prior_host->tx) &&
+                      std::isfinite(prior_host->ty) && std::isfinite(prior_host->tz)))
+    return fail(FX_ERR_INVALID_ARG, "prior_host must be finite");
+  fx_map_loop_options o;
+  fx_map_loop_options_default(&o);
+  if (opt) o = *opt;
+  if (!(std::isfinite(o.search_dist) && o.search_dist > 0.f)) return fail(FX_ERR_INVALID_ARG, "search_dist must be finite and positive");
+  if (!(o.inlier_dist > 0.f) || !std::isfinite(o.inlier_dist) || !(o.min_baseline > 0.f) || !std::isfinite(o.min_baseline))
+    return fail(FX_ERR_INVALID_ARG, "inlier_dist and min_baseline must be finite and positive");
+  if (o.hyp_corr < 2u || o.hyp_corr > 128u) return fail(FX_ERR_INVALID_ARG, "hyp_corr must be 2..128");
+  if (o.min_inliers < 2u) return fail(FX_ERR_INVALID_ARG, "min_inliers must be at least 2");
+  if (!o.min_landmark_obs) return fail(FX_ERR_INVALID_ARG, "min_landmark_obs must be at least 1");
+  if (o.recent_scans >= o.min_loop_scans) return fail(FX_ERR_INVALID_ARG, "recent_scans must be below min_loop_scans");
+  if (o.segment == FX_LOC_ANY_SEGMENT) return fail(FX_ERR_INVALID_ARG, "segment must be one segment or FX_LOC_LAST_SEGMENT, not FX_LOC_ANY_SEGMENT");
+  if (o.mode > FX_LOOP_DRY_RUN) return fail(FX_ERR_INVALID_ARG, "mode must be FX_LOOP_FIT, FX_LOOP_GIVEN or FX_LOOP_DRY_RUN");
+  if (o.mode == FX_LOOP_GIVEN && o.loop_first_scan >= o.loop_last_scan)
+    return fail(FX_ERR_INVALID_ARG, "loop_first_scan must be below loop_last_scan");
+  if (o.mode == FX_LOOP_GIVEN && !(std::isfinite(o.pivot_x) && std::isfinite(o.pivot_y))) return fail(FX_ERR_INVALID_ARG, "the pivot must be finite");
+  if (o.reserved) return fail(FX_ERR_INVALID_ARG, "reserved must be 0");
+  if (((uintptr_t)prior_device % 8) != 0 || ((uintptr_t)result % 8) != 0 || ((uintptr_t)match_of_landmark % 4) != 0)
+    return fail(FX_ERR_INVALID_ARG, "prior_device and the result must be 8-byte, match_of_landmark 4-byte aligned");
+  FX_HIP(hipSetDevice(c->device));
+  FxMapLoopArgs A{};
+  A.G.header = m->a.header, A.G.records = m->a.records, A.G.acc = m->a.acc, A.G.carry = m->a.carry, A.G.alias = m->a.alias;
+  A.G.cap = m->a.cap, A.G.max_carry = m->a.max_carry;
+  // the gate in fp64 and the grid's cell edge: sd (1 + 2^-8), exact (csrc/fx_map_grid.h proves the margin): the localise's
+  const double sd = (double)o.search_dist;
+  A.G.md2 = sd * sd, A.G.inv_edge = 1.0 / (sd * (1.0 + 1.0 / 256.0));
+  A.G.table = fxk_map_merge_table(A.G.cap);
+  A.segment = o.segment, A.mode = o.mode, A.min_loop_scans = o.min_loop_scans, A.recent_scans = o.recent_scans;
+  A.given_s0 = o.loop_first_scan, A.given_s1 = o.loop_last_scan, A.given_px = o.pivot_x, A.given_py = o.pivot_y;
+  A.prior[0] = 1.0;
+  if (prior_host)
+    A.prior[0] = prior_host->c, A.prior[1] = prior_host->s, A.prior[2] = prior_host->tx, A.prior[3] = prior_host->ty, A.prior[4] = prior_host->tz;
+  A.prior_device = prior_device;
+  A.inlier_dist = o.inlier_dist, A.min_baseline = o.min_baseline;
+  A.hyp_corr = o.hyp_corr, A.min_inliers = o.min_inliers, A.min_landmark_obs = o.min_landmark_obs;
+  A.result = result, A.match = match_of_landmark;
+  FX_TRY(c->merge_scratch.reserve(c, fxk_map_loop_scratch(&A, nullptr), "map loop scratch"));
+  (void)fxk_map_loop_scratch(&A, c->merge_scratch.d);
+  FX_HIP(fxk_map_loop(c->stream, A));
+  return FX_OK;
+}
+
+fx_status fx_map_loop_correct_poses(fx_ctx *c, const fx_map_loop_result *result, fx_pose *poses, uint32_t first_global_scan, uint32_t n_poses) {
+  if (!c || !result || !poses) return fail(FX_ERR_INVALID_ARG, "null argument");
+  if (((uintptr_t)result % 8) != 0 || ((uintptr_t)poses % 8) != 0) return fail(FX_ERR_INVALID_ARG, "the result and the poses must be 8-byte aligned");
+  FX_HIP(hipSetDevice(c->device));
+  FX_HIP(fxk_map_loop_poses(c->stream, result, poses, first_global_scan, n_poses));
   return FX_OK;
 }
 

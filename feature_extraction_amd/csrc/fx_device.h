@@ -344,6 +344,29 @@ struct FxMapJoinArgs {
   uint32_t *bsum;               // [2][blocks of landmarks]: the block's queries / queries with a target, then their prefix
   uint32_t *corr;               // [FX_JOIN_MAX_CORR]: the queries of the correspondences, in ascending id
 };
+// fx_map_close_loop (csrc/fx_map_loop.hip): a launch set's arguments, shaped like the join's.  G describes the grid over the map (its
+// gate is the search distance) and carries the map's own memory; the last group is the context's scratch, sized by G.cap.
+#define FX_MAP_LOOP_ST_WORDS 4  // 0 queries, 1 queries with a target, 2 landmarks moved
+struct FxMapLoopArgs {
+  FxMapMergeArgs G;
+  uint32_t segment, mode;       // the option's segment (FX_LOC_LAST_SEGMENT is resolved on the device)
+  uint32_t min_loop_scans, recent_scans;
+  uint32_t given_s0, given_s1;  // FX_LOOP_GIVEN: the loop's bounds and the pivot
+  double given_px, given_py;
+  double prior[5];              // c, s, tx, ty, tz: the host's prior, or the identity
+  const double *prior_device;   // five doubles read on the device in its place, or null
+  float inlier_dist, min_baseline;
+  uint32_t hyp_corr, min_inliers, min_landmark_obs;
+  void *result;                 // fx_map_loop_result or null
+  int32_t *match;               // [cap] or null
+  void *fit;                    // fx_map_loop_result: what the consensus decided, for the launches behind it
+  uint32_t *st;                 // [FX_MAP_LOOP_ST_WORDS]
+  int32_t *near;                // [cap]: the query's target, -1: none or no query
+  unsigned long long *d2;       // [cap]: its squared xy distance as bits
+  uint32_t *local;              // [cap]: the exclusive prefix of the queries with a target within the block of 256
+  uint32_t *bsum;               // [2][blocks of landmarks]: the block's queries / queries with a target, then their prefix
+  uint32_t *corr;               // [FX_LOOP_MAX_CORR]: the queries of the correspondences, in ascending id
+};
 #define FX_TRACK_NONE 0xffffffffu
 #define FX_N_HINTS 8   // tier_hint[]: 0 / 1 rings handed to the second run tier / the workgroup tier (largest XCD class), 2 big merges, 3 huge merges, 4 dense rows, 5 dense support points, 6 scans k_front handed to k_front_redo, 7 scans handed to the slow tier (k_slow)
 #define FX_CNT_QPOOL 32   // counters[32]: entries of the dense tier's query pool in use

@@ -1,6 +1,7 @@
 // fx_map_grid.h — the hashed grid over the map's live landmarks, which fx_map_merge (csrc/fx_map_merge.hip: a landmark looks for
-// its predecessor), fx_map_localize (csrc/fx_map_localize.hip: a keypoint looks for its landmark) and fx_map_join_segments
-// (csrc/fx_map_join.hip: a landmark of one segment looks for its twin in another) search.  The kernels that
+// its predecessor), fx_map_localize (csrc/fx_map_localize.hip: a keypoint looks for its landmark), fx_map_join_segments
+// (csrc/fx_map_join.hip: a landmark of one segment looks for its twin in another) and fx_map_close_loop (csrc/fx_map_loop.hip: a
+// recent landmark looks for its old twin in the same segment) search.  The kernels that
 // build it are csrc/fx_map_grid.hip's; what a search needs on the device is here.
 //
 // A grid is described by an FxMapMergeArgs (fx_device.h): the gate md2 = d d with d the call's distance widened to double, inv_edge
@@ -86,6 +87,23 @@ __device__ __forceinline__ void walk_nearest(const FxMapMergeArgs &G, uint32_t m
     const double dx = c.x - wx, dy = c.y - wy;
     const double d2 = dx * dx + dy * dy;
     if (!(d2 <= G.md2) || !(any_seg || c.segment == seg) || c.id >= G.cap) continue;
+    const unsigned long long k = (unsigned long long)__double_as_longlong(d2);
+    if (best.any && !(k < best.d2 || (k == best.d2 && c.id < best.id))) continue;
+    const fx_map_landmark R = records(G)[c.id];
+    if (R.n_obs < min_obs || !isfinite(R.z)) continue;
+    best.any = true, best.d2 = k, best.id = c.id;
+  }
+}
+// The same bucket walk for fx_map_close_loop's association (include/fx.h): the candidates must be of segment seg and OLD,
+// (uint64)last_scan + min_loop <= last, beside walk_nearest's gate and eligibility; the order is the same (d2 bits, id).
+__device__ __forceinline__ void walk_nearest_old(const FxMapMergeArgs &G, uint32_t min_obs, uint32_t b, double wx, double wy, uint32_t seg,
+                                                 unsigned long long min_loop, unsigned long long last, Near &best) {
+  const uint32_t end = min(bucket_end(G, b), G.cap);
+  for (uint32_t p = bucket_begin(G, b); p < end; ++p) {
+    const FxMapMergeCand c = G.cand[p];
+    const double dx = c.x - wx, dy = c.y - wy;
+    const double d2 = dx * dx + dy * dy;
+    if (!(d2 <= G.md2) || c.segment != seg || !((unsigned long long)c.last_scan + min_loop <= last) || c.id >= G.cap) continue;
     const unsigned long long k = (unsigned long long)__double_as_longlong(d2);
     if (best.any && !(k < best.d2 || (k == best.d2 && c.id < best.id))) continue;
     const fx_map_landmark R = records(G)[c.id];

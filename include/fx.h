@@ -639,8 +639,8 @@ fx_status fx_track_landmarks(fx_ctx *ctx,
  * Limits: tracks are continued only across an accepted one-scan overlap; a pole seen again after a missed detection, a bad link or
  * after leaving the field of view enters as a new landmark.  fx_map_merge (below) folds such fragments back into one landmark
  * within a segment and fx_map_join_segments (below) brings two segments a bad link left into one frame; after long drift fragments
- * stay apart (no loop closure: fx_map_relocalize finds the pose of a
- * scan in the map without a prior and fx_map_localize refines it, which closing one would start from).  The equality with one batch of the whole run
+ * stay apart until fx_map_close_loop (below) closes the loop: fx_map_relocalize finds the pose of a
+ * scan in the map without a prior and fx_map_localize refines it, which gives the closure its prior.  The equality with one batch of the whole run
  * holds for min_obs == 2; with a larger min_obs a track that a batch edge cuts into pieces that are each too short is missed.
  * n_obs and n_needed are 32-bit counts.  FX_MAP_FULL is sticky and n_needed only rises under fx_map_update; fx_map_compact (below)
  * gives the room of absorbed and let-go landmarks back, fx_map_export_host / fx_map_import_host carry a map to another context.
@@ -716,7 +716,8 @@ fx_status fx_map_read_landmarks(fx_ctx *ctx, fx_map *map, uint32_t first, uint32
  * FX_ERR_INVALID_ARG with the reason in fx_last_error(), nothing launched, the map unchanged: a NULL ctx or map (fx_map_get_alias:
  * a NULL out pointer), a map of another context, merge_dist not finite and positive, max_gap_scans == 0, result_device not 4-byte
  * aligned; fx_map_read_alias: entries outside max_landmarks.
- * Limits: merging happens within one segment only (fx_map_join_segments, below, makes one segment of two; no loop closure:
+ * Limits: merging happens within one segment only (fx_map_join_segments, below, makes one segment of two; twins that drift
+ * holds beyond merge_dist are fx_map_close_loop's, below, to bring together first;
  * fx_map_relocalize and fx_map_localize, below, give the
  * transform between a scan's frame and the map's, without and with a prior pose; they join nothing).  Chained merges of one call may join A and C that are up to
  * 2 merge_dist apart, through B.  The map_id_of_row arrays of earlier batches keep the absorbed ids: resolve them through the
@@ -1052,9 +1053,9 @@ fx_status fx_map_snapshot_check(const void *src_host, size_t bytes, uint32_t max
  * 32-bit integer sums) or a minimum over a total order, every fp64 value an ordered chain on one lane.  The search structure
  * (fx_map_merge's hashed grid, cell edge sd (1 + 2^-8)) never shows in a byte; numpy float64 reproduces the call bit for bit.
  * Limits: the duplicates of one pole now share a segment and are fx_map_merge's to join; they are disjoint in time across the
- * cut, and a caller that closes a long loop raises max_gap_scans.  Q is kept, so rms_xy is exact only for c c + s s = 1 (a
+ * cut, and a caller that closes a long loop (fx_map_close_loop, below) raises max_gap_scans.  Q is kept, so rms_xy is exact only for c c + s s = 1 (a
  * fitted or composed T is that within rounding).  One call makes one join.  There is no pose graph: the poses and
- * map_id_of_row arrays handed out earlier are not revised.  New in 0.7 (added symbols only). */
+ * map_id_of_row arrays handed out earlier are not revised (fx_map_loop_correct_poses, below, revises poses after a loop closure).  New in 0.7 (added symbols only). */
 #define FX_JOIN_MAX_CORR 1024u
 #define FX_JOIN_FIT 0u      /* mode: fit T from the two segments' landmarks under the prior, apply it */
 #define FX_JOIN_GIVEN 1u    /* apply the prior as T, fit nothing */
@@ -1087,6 +1088,136 @@ fx_status fx_map_join_segments(fx_ctx *ctx, fx_map *map, uint32_t src_segment, u
     const fx_pose *prior_host /* or NULL */, const double *prior_device /* 5 doubles c, s, tx, ty, tz, or NULL */,
     const fx_map_join_options *opt /* NULL: defaults */, fx_map_join_result *result_device /* or NULL */,
     int32_t *match_of_landmark_device /* [max_landmarks] or NULL */);
+
+/* ---- Closing a loop in the map: drift spread over the scans of the loop ----
+ * A vehicle that comes back to a place it mapped long ago holds every pole there twice, the drift of the loop apart and in one
+ * segment: beyond fx_map_merge's merge_dist, and fx_map_localize matches the scan to the recent copies only.
+ * fx_map_close_loop associates the RECENT landmarks of one segment with its OLD ones under a prior transform, fits the closure T
+ * with fx_map_localize's consensus (the association, the correspondences, the hypothesis stage and the refit are
+ * fx_map_join_segments's clauses and run the same device code), and moves every landmark of the segment by a part of T that
+ * grows linearly with its time from the old end of the loop (nothing) to the recent end (all of T).  fx_map_loop_correct_poses
+ * brings poses handed out earlier up to date by the same rule.  Both are enqueued on the context's stream (no host
+ * synchronisation, no allocation in the steady state: the scratch is the context-owned buffer the other map calls share, grown
+ * as needed).  Every floating-point step is fp64, no contraction, no fma, no transcendental: the interpolated rotation is a
+ * normalised lerp.
+ * Prior: as fx_map_join_segments (prior_host, or prior_device: five doubles read on the device, or neither: the identity).  It
+ * takes the recent end's frame onto the old one's: about the identity after slow drift, an fx_localization's dc of a scan
+ * localised against the old landmarks otherwise.
+ * ONE CALL, with N = header.n_landmarks, SEG = header.segments and last = header.scans - 1 as they are when the call runs on
+ * the stream; seg is opt.segment, FX_LOC_LAST_SEGMENT standing for SEG - 1 as in fx_map_localize:
+ * Device refusals: seg >= SEG (a map of no segment included) or header.scans == 0 gives FX_LOOP_BAD_SEGMENT, a prior_device with
+ * a double that is not finite FX_LOOP_BAD_PRIOR (both may be set).  The map is bit for bit unchanged; the result is T = the
+ * prior's five doubles as they are, D = the identity (dc = 1, ds = dtx = dty = dtz = 0), px = py = 0, rms = +inf, n_query =
+ * n_corr = n_inliers = moved = 0, loop_first_scan = loop_last_scan = hyp_a = hyp_b = 0xffffffff, segment = seg (0xffffffff
+ * when FX_LOC_LAST_SEGMENT met a map of no segment), and every word of match_of_landmark is -1.
+ * Eligible: g < N with alias[g] == -1, n_obs >= min_landmark_obs, x, y and z finite and segment == seg (fx_map_localize's clause).
+ * Targets ("old"): the eligible g with (uint64)last_scan + min_loop_scans <= last.
+ * Queries ("recent"): the eligible i with (uint64)first_scan + recent_scans >= last, in ascending id; n_query is their number.
+ * recent_scans < min_loop_scans, so no landmark is both and every target ended before every query began.  The point of a query
+ * is its record under the prior: wx = (pc x - ps y) + ptx, wy = (ps x + pc y) + pty, wz = z + ptz.
+ * Association: dx = x[g] - wx, dy = y[g] - wy, d2 = dx dx + dy dy; target g is in reach iff d2 <= sd sd, sd =
+ * (double)search_dist; the target of a query is the one in reach of lowest (d2 as uint64 bits, id).
+ * Correspondences: the queries that have a target, in ascending id; the first FX_LOOP_MAX_CORR are used (FX_LOOP_TRUNCATED when
+ * there are more); n_corr is the number used.
+ * Hypothesis stage and refit: fx_map_localize's clauses with the query's id in the place of the row.  Without a hypothesis:
+ * FX_LOOP_NO_HYPOTHESIS, D = the identity, rms = +inf, n_inliers = 0, hyp_a = hyp_b = 0xffffffff.  Otherwise D, rms and
+ * n_inliers are the final fit, hyp_a and hyp_b the query ids of the winning sample, and FX_LOOP_FITTED is set iff n_inliers >=
+ * min_inliers.  With FX_LOOP_FITTED T = D o prior by fx_map_localize's Pose clause (as in the join), otherwise T is the prior's
+ * five doubles bit for bit.  match_of_landmark (when given): all max_landmarks words are written; word i is the target of query
+ * i when i is in the final inlier set, -1 everywhere else.
+ * Loop bounds, with FX_LOOP_FITTED: s0 = loop_first_scan = the largest last_scan of the targets of the final inlier set, s1 =
+ * loop_last_scan = the smallest first_scan of its queries: integer reductions, s0 < s1 by the windows.
+ * Pivot, with FX_LOOP_FITTED: px and py are the x and the y of the records (NOT under the prior) of the queries of the final
+ * inlier set, each summed sequentially in ascending id from 0.0 and divided once by (double)n_inliers.
+ * Without FX_LOOP_FITTED s0 = s1 = 0xffffffff and px = py = 0.  mode FX_LOOP_GIVEN skips association and fit: T = the prior, D =
+ * the identity, rms = +inf, counts 0, hyp_a = hyp_b = 0xffffffff, and s0, s1, px and py are the options' loop_first_scan,
+ * loop_last_scan, pivot_x and pivot_y.
+ * Too far: when mode == FX_LOOP_GIVEN or FX_LOOP_FITTED holds, and T's c is not above 0 (a quarter turn or more: no drift),
+ * FX_LOOP_TOO_FAR is set and nothing is applied.
+ * Weight of a global scan interval [first_scan, last_scan]: with t2 = (uint64)first_scan + last_scan (twice the mid-scan), alpha
+ * = 0 when t2 <= 2 s0, 1 when t2 >= 2 s1, else (double)(t2 - 2 s0) / (double)(2 (s1 - s0)) (both integers in uint64).
+ * Interpolated transform T_alpha of T = (c, s, tx, ty, tz): alpha == 1 gives T bit for bit, alpha == 0 the identity (nothing is
+ * touched); otherwise, in this order,
+ *   cu = (1.0 - alpha) + alpha c, su = alpha s, nrm = sqrt(cu cu + su su), ca = cu / nrm, sa = su / nrm;
+ *   gx = (c px - s py) + tx, gy = (s px + c py) + ty                       (the pivot under T);
+ *   hx = px + alpha (gx - px), hy = py + alpha (gy - py)                   (the pivot moves on a straight line);
+ *   txa = hx - (ca px - sa py), tya = hy - (sa px + ca py), tza = alpha tz.
+ * Apply: the map is changed iff FX_LOOP_TOO_FAR is not set and either mode == FX_LOOP_GIVEN, or mode == FX_LOOP_FIT and
+ * FX_LOOP_FITTED holds; FX_LOOP_APPLIED is then set.  FX_LOOP_DRY_RUN fits and reports and changes no byte.  Without
+ * FX_LOOP_APPLIED moved = 0 and the map is bit for bit unchanged.  With it:
+ *   every landmark i < N of segment seg whose alpha (of its first_scan and last_scan) is above 0, absorbed ones included (their
+ *   frozen records and sums move with the rest), moves its sums, its anchor and its record under its T_alpha by
+ *   fx_map_join_segments's Apply formulas with (ca, sa, txa, tya, tza) for (c, s, tx, ty, tz): Q is kept and x, y, z and rms_xy
+ *   are recomputed by fx_map_update's "Records" clause (a landmark of n_obs == 0 keeps its record).  moved is their number.
+ *   Every landmark reads and writes its own slot only; landmarks of other segments and those with alpha == 0 keep every byte.
+ *   last_pose: iff seg == SEG - 1, its five doubles become T_alpha o last_pose (p = T_alpha, r = last_pose in the Pose clause's
+ *   composition) with alpha taken at t2 = 2 last (a fitted loop has last >= s1: that is T itself); alpha == 0 leaves it.  Its
+ *   segment and flags stay.  Every other header word, the alias table, the carry, the carry scan, ids, labels and n_obs stay.
+ * result (when given): T, D, px, py, rms, n_query, n_corr, n_inliers, flags, moved, loop_first_scan, loop_last_scan, segment =
+ * seg, hyp_a, hyp_b, reserved = 0.
+ * Order of calls: close between an fx_map_update and the next fx_track_landmarks, and read last_pose afterwards for its
+ * init_pose_host.  Then fx_map_merge with a max_gap_scans that covers the loop fuses the twins, and fx_map_compact drops them.
+ * fx_map_loop_correct_poses: pose b of poses_device is the pose of global scan first_global_scan + b.  When the result carries
+ * FX_LOOP_APPLIED and the alpha of t2 = 2 (first_global_scan + b) (uint64) is above 0, the pose's five doubles become T_alpha o
+ * pose by the same composition; its segment and flags stay.  Without FX_LOOP_APPLIED nothing is written.  The caller passes
+ * only poses of the closed segment (result.segment).  One lane a pose.
+ * FX_ERR_INVALID_ARG with the reason in fx_last_error(), nothing launched, no byte touched: a NULL ctx or map, a map of another
+ * context, both prior pointers given, a prior_host whose c, s, tx, ty or tz is not finite, search_dist, inlier_dist or
+ * min_baseline not finite and positive, hyp_corr outside 2..128, min_inliers < 2, min_landmark_obs == 0, recent_scans >=
+ * min_loop_scans, segment == FX_LOC_ANY_SEGMENT, mode > 2, in mode FX_LOOP_GIVEN loop_first_scan >= loop_last_scan or a pivot
+ * that is not finite, reserved != 0, prior_device or result_device not 8-byte aligned, match_of_landmark_device not 4-byte
+ * aligned; fx_map_loop_correct_poses: a NULL ctx, result or poses, a result or poses not 8-byte aligned.
+ * The same bytes from run to run and with any number of contexts in flight: every decision is an integer or a minimum over a
+ * total order, every fp64 value an ordered chain of + - * / sqrt on one lane.  The grid never shows in a byte; numpy float64
+ * reproduces both calls bit for bit.
+ * Limits: a landmark carries two scan numbers, not a trajectory: its weight is that of its mid-scan, so the correction is first
+ * order, a linear spread of the closure error over the scans and no pose-graph optimum.  A landmark whose observations already
+ * span the loop (one merged across it) is placed by its mid-scan: close before merging across the loop.  Q is kept, so rms_xy is
+ * exact only for ca ca + sa sa = 1 (true within rounding).  One call closes one loop.  New in 0.7 (added symbols only). */
+#define FX_LOOP_MAX_CORR 1024u
+#define FX_LOOP_FIT 0u      /* mode: fit T from the segment's recent and old landmarks under the prior, apply it spread */
+#define FX_LOOP_GIVEN 1u    /* apply the prior as T between the given scans about the given pivot, fit nothing */
+#define FX_LOOP_DRY_RUN 2u  /* fit and report, change no byte of the map */
+typedef struct fx_map_loop_options {   /* 72 B */
+  float search_dist;      /* as fx_map_join_options; default 2.0 */
+  float inlier_dist;      /* default 0.30 */
+  float min_baseline;     /* default 2.0 */
+  uint32_t hyp_corr;      /* 2..128, default 64 */
+  uint32_t min_inliers;   /* >= 2, default 3 */
+  uint32_t min_landmark_obs; /* >= 1, default 2 */
+  uint32_t segment;       /* a global segment, or FX_LOC_LAST_SEGMENT (default); FX_LOC_ANY_SEGMENT is refused */
+  uint32_t min_loop_scans; /* a target ended at least this many scans before the map's last; default 256 */
+  uint32_t recent_scans;  /* a query began at most this many scans before the map's last; < min_loop_scans; default 32 */
+  uint32_t mode;          /* FX_LOOP_FIT (default), FX_LOOP_GIVEN, FX_LOOP_DRY_RUN */
+  uint32_t loop_first_scan, loop_last_scan; /* FX_LOOP_GIVEN only: s0 < s1; default 0, 0 */
+  double pivot_x, pivot_y; /* FX_LOOP_GIVEN only: finite; default 0, 0 */
+  uint32_t reserved;      /* 0 */
+} fx_map_loop_options;
+#define FX_LOOP_APPLIED 0x1u        /* the map was changed: the segment's landmarks moved by their part of T */
+#define FX_LOOP_TRUNCATED 0x2u      /* more than FX_LOOP_MAX_CORR correspondences: the first 1024 in id order were used */
+#define FX_LOOP_NO_HYPOTHESIS 0x4u  /* fewer than 2 correspondences, or no sample passed the gates */
+#define FX_LOOP_BAD_PRIOR 0x8u      /* a double of prior_device is not finite */
+#define FX_LOOP_BAD_SEGMENT 0x10u   /* the segment is not below header.segments, or the map has no scans */
+#define FX_LOOP_FITTED 0x20u        /* a closure was fitted to >= min_inliers correspondences: T = D o prior */
+#define FX_LOOP_TOO_FAR 0x40u       /* T turns by a quarter turn or more: no drift, nothing applied */
+typedef struct fx_map_loop_result {    /* 144 B */
+  double c, s, tx, ty, tz;        /* T: the recent end of the loop -> the old one */
+  double dc, ds, dtx, dty, dtz;   /* D: the fitted correction, T = D o prior */
+  double px, py;                  /* the pivot */
+  float rms;
+  uint32_t n_query, n_corr, n_inliers, flags, moved;
+  uint32_t loop_first_scan, loop_last_scan; /* s0, s1; 0xffffffff: none */
+  uint32_t segment;               /* the resolved segment */
+  uint32_t hyp_a, hyp_b;          /* query ids of the winning sample, 0xffffffff: none */
+  uint32_t reserved;              /* 0 */
+} fx_map_loop_result;
+void fx_map_loop_options_default(fx_map_loop_options *o);
+fx_status fx_map_close_loop(fx_ctx *ctx, fx_map *map,
+    const fx_pose *prior_host /* or NULL */, const double *prior_device /* 5 doubles c, s, tx, ty, tz, or NULL */,
+    const fx_map_loop_options *opt /* NULL: defaults */, fx_map_loop_result *result_device /* or NULL */,
+    int32_t *match_of_landmark_device /* [max_landmarks] or NULL */);
+fx_status fx_map_loop_correct_poses(fx_ctx *ctx, const fx_map_loop_result *result_device,
+    fx_pose *poses_device, uint32_t first_global_scan, uint32_t n_poses);
 
 /* Rotation matrix of rotateCloud (ref: node.cpp:161-164): R = Ry(pitch)*Rx(roll)
  * through Eigen's AngleAxisf -> Quaternionf -> toRotationMatrix, all float. Host only. */

@@ -45,6 +45,14 @@ localises 8 scans of 64 keypoints against it (timed: fx_map_localize on the same
 joins segment 1 into segment 0 (timed: one pair of HIP events around the call: the grid, N / 3 queries, the consensus over the
 first 1024 correspondences, N / 3 landmarks moved, N relabelled).  Reported per size: the medians and the join's result.  No
 target is set.
+  timeout -k 10 600 python tools/map_times.py --loop [--sizes 1000,100000,1000000] [--warmup 1] [--repeats 5] [--out profiles/map_loop_times.txt]
+
+times fx_map_close_loop on the same synthetic maps as one segment: the first fragments (scans 0-1) are the old landmarks, the second
+fragments (scans 2-3, a third, up to 0.2 m beside their poles) the recent ones (min_loop_scans 2, recent_scans 1), under the identity
+prior.  Every repeat resets the map, updates it and closes (timed: one pair of HIP events around the call: the grid, N / 3 queries,
+the consensus over the first 1024 correspondences, N / 3 landmarks moved), then corrects 1024 poses (timed).  The join of --join is
+timed on the same maps in the same run for the column beside it.  Reported per size: the medians and the closure's result.  No target
+is set.
 """
 import argparse
 import ctypes as C
@@ -386,6 +394,74 @@ def main_join(a):
             f.write(s + "\n")
 
 
+def measure_loop(ctx, n, warmup, repeats, n_poses=1024):
+    import torch
+    blk, (S, T), m, inl, reg, M = merge_case(n, np.random.default_rng(n))
+    kp = (torch.from_numpy(blk).cuda(), S, T)
+    md, inl_t = torch.from_numpy(m.view(np.int32).reshape(-1, 8).copy()).cuda(), torch.from_numpy(inl).cuda()
+    reg_t = torch.from_numpy(reg.view(np.float64).reshape(-1, 8).copy()).cuda()
+    out = ctx.track_landmarks(kp, md, inl_t, reg_t, S, max_landmarks=n)
+    mp = ctx.map_create(n, 16)
+    res = torch.zeros((capi.LOOP_DTYPE.itemsize // 8,), dtype=torch.float64, device="cuda")
+    match = torch.empty((n,), dtype=torch.int32, device="cuda")
+    poses0 = np.zeros(n_poses, capi.POSE_DTYPE)
+    poses0["c"] = 1.0
+    poses_h = torch.from_numpy(poses0.view(np.float64).reshape(-1, 6).copy()).cuda()
+    poses = poses_h.clone()
+    stream = torch.cuda.ExternalStream(ctx.stream_ptr())
+    torch.cuda.synchronize()
+    t = {"loop_ms": [], "poses_ms": []}
+    first = None
+    for rep in range(warmup + repeats):
+        mp.reset()
+        mp.update(kp, out, overlap=False, row_ids=False)
+        poses.copy_(poses_h)
+        torch.cuda.synchronize()
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        e[0].record(stream)
+        mp.close_loop(result=res, match=match, min_loop_scans=2, recent_scans=1)
+        e[1].record(stream), e[2].record(stream)
+        mp.loop_correct_poses(res, poses, 0)
+        e[3].record(stream)
+        ctx.synchronize()
+        got = capi.loop_records(res)[0]
+        first = got if first is None else first
+        assert got.tobytes() == first.tobytes() and got["flags"] & capi.FX_LOOP_APPLIED, (got, first)
+        if rep >= warmup:
+            for k, (a, b) in zip(t, ((0, 1), (2, 3))):
+                t[k].append(e[a].elapsed_time(e[b]))
+    mp.close()
+    out = {"landmarks": n, "result": {k: (float(first[k]) if first[k].dtype.kind == "f" else int(first[k])) for k in capi.LOOP_DTYPE.names}}
+    for k, v in t.items():
+        out[k] = statistics.median(v)
+        out[k + "_min_max"] = [min(v), max(v)]
+    return out
+
+
+def main_loop(a):
+    sizes = [int(x) for x in a.sizes.split(",")]
+    ctx = capi.Context(capi.params("launch"), capi.limits(2, 1024))
+    rows = [dict(measure_loop(ctx, n, a.warmup, a.repeats), join_ms=measure_join(ctx, n, a.warmup, a.repeats)["join_ms"]) for n in sizes]
+    ctx.close()
+    lines = [f"fx_map_close_loop next to fx_map_join_segments on synthetic maps (tools/map_times.py --loop): 1 pole per 250 m^2, a third of the",
+             f"landmarks second fragments two scans later (the recent ones, closed onto the first under the identity prior; for the join they are",
+             f"a segment of their own); poses: fx_map_loop_correct_poses on 1024 poses; one context, HIP events around each call, median of",
+             f"{a.repeats} after {a.warmup} warm-up; ms",
+             f"{'landmarks':>10} {'queries':>8} {'corr':>6} {'inliers':>8} {'moved':>8} {'flags':>6} {'loop':>9} {'loop / size before':>19} {'poses':>9} {'join':>9}"]
+    for k, r in enumerate(rows):
+        ratio = f"{r['loop_ms'] / rows[k - 1]['loop_ms']:.2f}" if k else "-"
+        q = r["result"]
+        lines.append(f"{r['landmarks']:>10} {q['n_query']:>8} {q['n_corr']:>6} {q['n_inliers']:>8} {q['moved']:>8} {q['flags']:>#6x} {r['loop_ms']:>9.3f} {ratio:>19} "
+                     f"{r['poses_ms']:>9.3f} {r['join_ms']:>9.3f}")
+    s = "\n".join(lines)
+    print(s)
+    print(json.dumps(rows))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(s + "\n")
+
+
 def main_relocalize(a):
     sizes = [int(x) for x in a.sizes.split(",")]
     ctx = capi.Context(capi.params("launch"), capi.limits(2, 1024))
@@ -458,6 +534,7 @@ def main():
     ap.add_argument("--compact", action="store_true", help="time fx_map_compact on the merged synthetic maps instead")
     ap.add_argument("--relocalize", action="store_true", help="time fx_map_relocalize on the synthetic maps instead (pass --sizes 10000,100000)")
     ap.add_argument("--join", action="store_true", help="time fx_map_join_segments on two-segment synthetic maps instead")
+    ap.add_argument("--loop", action="store_true", help="time fx_map_close_loop on the synthetic maps taken as one loop instead")
     ap.add_argument("--sizes", default="1000,100000,1000000")
     ap.add_argument("--scans", type=int, default=1024)
     ap.add_argument("--batch", type=int, default=128)
@@ -476,6 +553,8 @@ def main():
         return main_relocalize(a)
     if a.join:
         return main_join(a)
+    if a.loop:
+        return main_loop(a)
     N = 28800
     ctx = capi.Context(capi.params("launch"), capi.limits(a.batch, N, sparse=True))
     scenes = np.stack([capi.synth_scan(capi.synth_cfg(1000 + b)) for b in range(a.scans)])
