@@ -303,6 +303,35 @@ LOOP_DEFAULTS = dict(search_dist=2.0, inlier_dist=0.30, min_baseline=2.0, hyp_co
                      pivot_x=0.0, pivot_y=0.0)
 
 
+class FxMapFindLoopOptions(C.Structure):
+    _fields_ = [("inlier_dist", C.c_float), ("pair_tol", C.c_float), ("min_baseline", C.c_float), ("max_baseline", C.c_float),
+                ("max_seeds", C.c_uint32), ("min_inliers", C.c_uint32), ("min_margin", C.c_uint32), ("min_landmark_obs", C.c_uint32),
+                ("segment", C.c_uint32), ("target_segment", C.c_uint32), ("min_loop_scans", C.c_uint32), ("recent_scans", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class FxMapLoopCandidate(C.Structure):
+    _fields_ = [("c", C.c_double), ("s", C.c_double), ("tx", C.c_double), ("ty", C.c_double), ("tz", C.c_double), ("wc", C.c_double),
+                ("ws", C.c_double), ("wtx", C.c_double), ("wty", C.c_double), ("wtz", C.c_double), ("n_hyp", C.c_uint64),
+                ("n_query", C.c_uint32), ("n_targets", C.c_uint32), ("n_seeds", C.c_uint32), ("score", C.c_uint32), ("runner_up", C.c_uint32),
+                ("flags", C.c_uint32), ("seed_a", C.c_uint32), ("seed_b", C.c_uint32), ("lm_a", C.c_uint32), ("lm_b", C.c_uint32),
+                ("segment", C.c_uint32), ("target_segment", C.c_uint32)]
+
+
+FX_FIND_MAX_QUERY = 64
+FX_FIND_SAME_SEGMENT = 0xfffffffd
+FX_FIND_VALID, FX_FIND_TRUNCATED, FX_FIND_NO_HYPOTHESIS, FX_FIND_AMBIGUOUS, FX_FIND_BAD_SEGMENT = 0x1, 0x2, 0x4, 0x8, 0x10
+FX_FIND_NONE = 0xffffffff
+FX_FIND_NAN_BITS = 0x7ff8000000000000  # c, s, tx, ty, tz of a result that is not FX_FIND_VALID
+# fx_map_loop_candidate as a numpy record (find_loop_records)
+FIND_DTYPE = np.dtype([("c", "<f8"), ("s", "<f8"), ("tx", "<f8"), ("ty", "<f8"), ("tz", "<f8"), ("wc", "<f8"), ("ws", "<f8"), ("wtx", "<f8"),
+                       ("wty", "<f8"), ("wtz", "<f8"), ("n_hyp", "<u8"), ("n_query", "<u4"), ("n_targets", "<u4"), ("n_seeds", "<u4"),
+                       ("score", "<u4"), ("runner_up", "<u4"), ("flags", "<u4"), ("seed_a", "<u4"), ("seed_b", "<u4"), ("lm_a", "<u4"),
+                       ("lm_b", "<u4"), ("segment", "<u4"), ("target_segment", "<u4")])
+FIND_DEFAULTS = dict(inlier_dist=0.30, pair_tol=0.30, min_baseline=2.0, max_baseline=60.0, max_seeds=16, min_inliers=4, min_margin=1,
+                     min_landmark_obs=2, segment=FX_LOC_LAST_SEGMENT, target_segment=FX_FIND_SAME_SEGMENT, min_loop_scans=256, recent_scans=32)
+
+
 class FxTimings(C.Structure):
     _fields_ = [("ms", C.c_float * FX_N_STAGES), ("total_ms", C.c_float), ("k_prep_exec_ms", C.c_float)]
 
@@ -332,6 +361,7 @@ EXPORTS = ("fx_version", "fx_check_abi", "fx_status_str", "fx_last_error", "fx_p
            "fx_map_compact_options_default", "fx_map_compact", "fx_map_export_host", "fx_map_import_host", "fx_map_snapshot_check",
            "fx_map_join_options_default", "fx_map_join_segments",
            "fx_map_loop_options_default", "fx_map_close_loop", "fx_map_loop_correct_poses",
+           "fx_map_find_loop_options_default", "fx_map_find_loop",
            "fx_rotation_from_roll_pitch", "fx_sc3d_tables", "fx_sc3d_xaxis", "fx_synth_cfg_vlp16",
            "fx_synth_scan", "fx_unpack_pointcloud2", "fx_pack_pointxyzi")
 # the header's FX_TEST_HOOKS section: exported by lib/libfx_hip_test.so only
@@ -482,6 +512,9 @@ def load():
     lib.fx_map_loop_options_default.restype = None
     lib.fx_map_close_loop.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(FxPose), C.c_void_p, C.POINTER(FxMapLoopOptions), C.c_void_p, C.c_void_p]
     lib.fx_map_loop_correct_poses.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+    lib.fx_map_find_loop_options_default.argtypes = [C.POINTER(FxMapFindLoopOptions)]
+    lib.fx_map_find_loop_options_default.restype = None
+    lib.fx_map_find_loop.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(FxMapFindLoopOptions), C.c_void_p, C.c_void_p]
     lib.fx_rotation_from_roll_pitch.argtypes = [C.c_double, C.c_double, _F32P]
     lib.fx_rotation_from_roll_pitch.restype = None
     lib.fx_sc3d_tables.argtypes = [C.c_double, _F32P, _F32P, _F32P, _F32P]
@@ -1796,6 +1829,97 @@ def relocalize_records(out):
     return np.ascontiguousarray(out).view(np.uint8).reshape(-1).view(RELOC_DTYPE).copy()
 
 
+def _constellation_search(x, y, z, ex, ey, ez, id2, ptd, mb2, xb2, g2, max_seeds):
+    """The seed, hypothesis, score, winner, rival and tz clauses fx_map_relocalize and fx_map_find_loop share (include/fx.h), in
+    numpy float64: x, y, z the points (a scan's used keypoints, a loop's queries), ex, ey, ez the landmarks they may be laid on, in
+    ascending id.  Every (seed, g, h) and every (point, landmark) pair is looked at.  One ufunc an operation, so nothing is
+    contracted; call it under np.errstate(all="ignore").  Returns {"n_seeds", "hyp": (s, g, h, score) arrays in (s, g, h) order with
+    g, h as positions in ex, "win": None or a dict: T = (c, s, tx, ty), tz, score, runner, ka, kb (the winning seed's points), g, h,
+    hit (bool a point: scored) and j (a point's landmark, a position in ex)}."""
+    f64 = np.float64
+    half = f64(0.5)
+    n_kp, E = len(x), len(ex)
+
+    def landed(wx, wy):
+        """[..., E] -> does the image land on a landmark; chunked over the leading axis"""
+        out = np.zeros(wx.shape, bool)
+        if not E:
+            return out
+        step = max(1, (1 << 22) // max(1, wx.shape[1] * E))
+        for lo_ in range(0, wx.shape[0], step):
+            dx, dy = ex[None, None, :] - wx[lo_:lo_ + step, :, None], ey[None, None, :] - wy[lo_:lo_ + step, :, None]
+            out[lo_:lo_ + step] = (dx * dx + dy * dy <= id2).any(axis=2)
+        return out
+
+    # seeds
+    a, c_ = np.triu_indices(n_kp, 1)  # lexicographic (a, b), a < b
+    dx, dy = x[c_] - x[a], y[c_] - y[a]
+    d2 = dx * dx + dy * dy
+    cand = np.flatnonzero((mb2 <= d2) & (d2 <= xb2))
+    order = cand[np.lexsort((cand, ~d2[cand].view(np.uint64)))]  # descending d2 bits, then ascending (a, b)
+    seeds = order[:int(max_seeds)]
+    # hypotheses: (s, g, h) in ascending order, g and h as positions in ex
+    parts = []
+    for s_rank, k in enumerate(seeds):
+        if E < 2:
+            break
+        xa, ya, xb_, yb_ = x[a[k]], y[a[k]], x[c_[k]], y[c_[k]]
+        dqx, dqy = xb_ - xa, yb_ - ya
+        dtx, dty = ex[None, :] - ex[:, None], ey[None, :] - ey[:, None]  # [g, h]: B.z - A.z
+        lq2, lt2 = dqx * dqx + dqy * dqy, dtx * dtx + dty * dty
+        keep = (lq2 >= mb2) & (lt2 >= mb2)
+        keep &= ~(np.abs(np.sqrt(lq2) - np.sqrt(lt2)) > ptd)
+        keep &= ~np.eye(E, dtype=bool)
+        gi, hi_ = np.nonzero(keep)  # (row-major: ascending (g, h))
+        dtx, dty = dtx[gi, hi_], dty[gi, hi_]
+        dot, crs = dqx * dtx + dqy * dty, dqx * dty - dqy * dtx
+        nrm = np.sqrt(dot * dot + crs * crs)
+        ok = nrm > 0
+        gi, hi_, dot, crs, nrm = gi[ok], hi_[ok], dot[ok], crs[ok], nrm[ok]
+        c, s = dot / nrm, crs / nrm
+        mqx, mqy = (xa + xb_) * half, (ya + yb_) * half
+        mtx, mty = (ex[gi] + ex[hi_]) * half, (ey[gi] + ey[hi_]) * half
+        tx, ty = mtx - (c * mqx - s * mqy), mty - (s * mqx + c * mqy)
+        wx = (c[:, None] * x[None, :] - s[:, None] * y[None, :]) + tx[:, None]
+        wy = (s[:, None] * x[None, :] + c[:, None] * y[None, :]) + ty[:, None]
+        score = landed(wx, wy).sum(axis=1)
+        parts.append((np.full(len(gi), s_rank), gi, hi_, score, c, s, tx, ty))
+    if parts:
+        hs, hg, hh, hscore, hc, hsn, htx, hty = (np.concatenate([p[k] for p in parts]) for k in range(8))
+    else:
+        hs = hg = hh = hscore = np.zeros(0, np.int64)
+        hc = hsn = htx = hty = np.zeros(0, f64)
+    out = {"n_seeds": len(seeds), "hyp": (hs, hg, hh, hscore), "win": None}
+    if not len(hs) or hscore.max() < 2:
+        return out
+    w = int(np.argmax(hscore))  # (the first maximum: the lowest (s, g, h))
+    wc, ws, wtx, wty = hc[w], hsn[w], htx[w], hty[w]
+    # rivals: the winner's seed points under every hypothesis against under the winner
+    ka, kb = a[seeds[hs[w]]], c_[seeds[hs[w]]]
+    rival = np.zeros(len(hs), bool)
+    for q in (ka, kb):
+        ux, uy = (hc * x[q] - hsn * y[q]) + htx, (hsn * x[q] + hc * y[q]) + hty
+        vx, vy = (wc * x[q] - ws * y[q]) + wtx, (ws * x[q] + wc * y[q]) + wty
+        rx, ry = ux - vx, uy - vy
+        rival |= rx * rx + ry * ry > g2
+    runner = int(hscore[rival].max()) if rival.any() else 0
+    # the landmark of every point under the winner: lowest (d2 bits, id) in reach
+    wx, wy = (wc * x - ws * y) + wtx, (ws * x + wc * y) + wty
+    dx, dy = ex[None, :] - wx[:, None], ey[None, :] - wy[:, None]
+    d2 = dx * dx + dy * dy
+    key = np.where(d2 <= id2, d2, np.inf).view(np.uint64)
+    j = np.argmin(key, axis=1)  # (the first minimum: ids ascend)
+    hit = d2[np.arange(n_kp), j] <= id2
+    score = int(hit.sum())
+    assert score == int(hscore[w])
+    sz = 0.0
+    for k in np.flatnonzero(hit):
+        sz += (float(ez[j[k]]) - float(z[k]))
+    out["win"] = dict(T=(wc, ws, wtx, wty), tz=sz / float(score), score=score, runner=runner, ka=int(ka), kb=int(kb), g=int(hg[w]), h=int(hh[w]),
+                      hit=hit, j=j)
+    return out
+
+
 def map_relocalize_reference(state, kp_offset, kp_rows, n_scans, q_max_rows=None, inlier_dist=0.30, pair_tol=0.30, min_baseline=2.0,
                              max_baseline=60.0, max_seeds=16, min_inliers=4, min_margin=1, min_landmark_obs=2, segment=FX_LOC_ANY_SEGMENT):
     """The definition of fx_map_relocalize (include/fx.h) in numpy float64 over a map_reference / map_merge_reference state (which is
@@ -1814,7 +1938,7 @@ def map_relocalize_reference(state, kp_offset, kp_rows, n_scans, q_max_rows=None
             1 <= max_seeds <= FX_RELOC_MAX_KP and min_inliers >= 3 and min_margin >= 1 and min_landmark_obs >= 1):
         raise ValueError("arguments outside what fx_map_relocalize accepts")
     idd, ptd, mbd, xbd = f64(id32), f64(pt32), f64(mb32), f64(xb32)
-    id2, mb2, xb2, half = idd * idd, mbd * mbd, xbd * xbd, f64(0.5)
+    id2, mb2, xb2 = idd * idd, mbd * mbd, xbd * xbd
     two = f64(2.0) * idd
     g2 = two * two
     S, rows = min(n_scans, len(off) - 1), min(len(kp), R)
@@ -1833,25 +1957,12 @@ def map_relocalize_reference(state, kp_offset, kp_rows, n_scans, q_max_rows=None
         elig &= np.isfinite(lx) & np.isfinite(ly) & np.isfinite(lz)
     ids = np.flatnonzero(elig)
     ex, ey, ez = lx[ids], ly[ids], lz[ids]
-    E = len(ids)
     rec = np.zeros(n_scans, RELOC_DTYPE)
     rec["pose"]["c"] = 1.0
     for f in ("seed_a", "seed_b", "lm_a", "lm_b"):
         rec[f] = FX_RELOC_NONE
     map_id = np.full(R, -1, np.int32)
     hyps = []
-
-    def landed(wx, wy):
-        """[..., E] -> does the image land on an eligible landmark; chunked over the leading axis"""
-        out = np.zeros(wx.shape, bool)
-        if not E:
-            return out
-        step = max(1, (1 << 22) // max(1, wx.shape[1] * E))
-        for lo_ in range(0, wx.shape[0], step):
-            dx, dy = ex[None, None, :] - wx[lo_:lo_ + step, :, None], ey[None, None, :] - wy[lo_:lo_ + step, :, None]
-            out[lo_:lo_ + step] = (dx * dx + dy * dy <= id2).any(axis=2)
-        return out
-
     with np.errstate(all="ignore"):
         for b in range(n_scans):
             empty = {k: np.zeros(0, np.int64) for k in ("s", "g", "h", "score")}
@@ -1867,85 +1978,118 @@ def map_relocalize_reference(state, kp_offset, kp_rows, n_scans, q_max_rows=None
             n_kp = len(used)
             x, y, z = (kp[used, k].astype(f64) for k in range(3))
             rec["n_kp"][b] = n_kp
-            # seeds
-            a, c_ = np.triu_indices(n_kp, 1)  # lexicographic (a, b), a < b
-            dx, dy = x[c_] - x[a], y[c_] - y[a]
-            d2 = dx * dx + dy * dy
-            cand = np.flatnonzero((mb2 <= d2) & (d2 <= xb2))
-            order = cand[np.lexsort((cand, ~d2[cand].view(np.uint64)))]  # descending d2 bits, then ascending (a, b)
-            seeds = order[:int(max_seeds)]
-            rec["n_seeds"][b] = len(seeds)
-            # hypotheses: (s, g, h) in ascending order, g and h as positions in ids
-            parts = []
-            for s_rank, k in enumerate(seeds):
-                if E < 2:
-                    break
-                xa, ya, xb_, yb_ = x[a[k]], y[a[k]], x[c_[k]], y[c_[k]]
-                dqx, dqy = xb_ - xa, yb_ - ya
-                dtx, dty = ex[None, :] - ex[:, None], ey[None, :] - ey[:, None]  # [g, h]: B.z - A.z
-                lq2, lt2 = dqx * dqx + dqy * dqy, dtx * dtx + dty * dty
-                keep = (lq2 >= mb2) & (lt2 >= mb2)
-                keep &= ~(np.abs(np.sqrt(lq2) - np.sqrt(lt2)) > ptd)
-                keep &= ~np.eye(E, dtype=bool)
-                gi, hi_ = np.nonzero(keep)  # (row-major: ascending (g, h))
-                dtx, dty = dtx[gi, hi_], dty[gi, hi_]
-                dot, crs = dqx * dtx + dqy * dty, dqx * dty - dqy * dtx
-                nrm = np.sqrt(dot * dot + crs * crs)
-                ok = nrm > 0
-                gi, hi_, dot, crs, nrm = gi[ok], hi_[ok], dot[ok], crs[ok], nrm[ok]
-                c, s = dot / nrm, crs / nrm
-                mqx, mqy = (xa + xb_) * half, (ya + yb_) * half
-                mtx, mty = (ex[gi] + ex[hi_]) * half, (ey[gi] + ey[hi_]) * half
-                tx, ty = mtx - (c * mqx - s * mqy), mty - (s * mqx + c * mqy)
-                wx = (c[:, None] * x[None, :] - s[:, None] * y[None, :]) + tx[:, None]
-                wy = (s[:, None] * x[None, :] + c[:, None] * y[None, :]) + ty[:, None]
-                score = landed(wx, wy).sum(axis=1)
-                parts.append((np.full(len(gi), s_rank), gi, hi_, score, c, s, tx, ty))
-            if parts:
-                hs, hg, hh, hscore, hc, hsn, htx, hty = (np.concatenate([p[k] for p in parts]) for k in range(8))
-            else:
-                hs = hg = hh = hscore = np.zeros(0, np.int64)
-                hc = hsn = htx = hty = np.zeros(0, f64)
+            found = _constellation_search(x, y, z, ex, ey, ez, id2, ptd, mb2, xb2, g2, max_seeds)
+            rec["n_seeds"][b] = found["n_seeds"]
+            hs, hg, hh, hscore = found["hyp"]
             rec["n_hyp"][b] = len(hs)
             hyps.append({"s": hs, "g": ids[hg] if len(hg) else hg, "h": ids[hh] if len(hh) else hh, "score": hscore})
-            if not len(hs) or hscore.max() < 2:
+            W = found["win"]
+            if W is None:
                 rec["flags"][b] = flags | FX_RELOC_NO_HYPOTHESIS
                 continue
-            w = int(np.argmax(hscore))  # (the first maximum: the lowest (s, g, h))
-            wc, ws, wtx, wty = hc[w], hsn[w], htx[w], hty[w]
-            # rivals: the winner's seed keypoints under every hypothesis against under the winner
-            ka, kb = a[seeds[hs[w]]], c_[seeds[hs[w]]]
-            rival = np.zeros(len(hs), bool)
-            for q in (ka, kb):
-                ux, uy = (hc * x[q] - hsn * y[q]) + htx, (hsn * x[q] + hc * y[q]) + hty
-                vx, vy = (wc * x[q] - ws * y[q]) + wtx, (ws * x[q] + wc * y[q]) + wty
-                rx, ry = ux - vx, uy - vy
-                rival |= rx * rx + ry * ry > g2
-            runner = int(hscore[rival].max()) if rival.any() else 0
-            # the landmark of every keypoint under the winner: lowest (d2 bits, id) in reach
-            wx, wy = (wc * x - ws * y) + wtx, (ws * x + wc * y) + wty
-            dx, dy = ex[None, :] - wx[:, None], ey[None, :] - wy[:, None]
-            d2 = dx * dx + dy * dy
-            key = np.where(d2 <= id2, d2, np.inf).view(np.uint64)
-            j = np.argmin(key, axis=1)  # (the first minimum: ids ascend)
-            hit = d2[np.arange(n_kp), j] <= id2
-            score = int(hit.sum())
-            assert score == int(hscore[w])
-            sz = 0.0
-            for k in np.flatnonzero(hit):
-                sz += (float(ez[j[k]]) - float(z[k]))
+            score, runner, hit, j = W["score"], W["runner"], W["hit"], W["j"]
             P = rec["pose"]
-            P["c"][b], P["s"][b], P["tx"][b], P["ty"][b], P["tz"][b] = wc, ws, wtx, wty, sz / float(score)
-            P["segment"][b] = int(lms[int(ids[hg[w]])]["segment"])
+            P["c"][b], P["s"][b], P["tx"][b], P["ty"][b] = W["T"]
+            P["tz"][b] = W["tz"]
+            P["segment"][b] = int(lms[int(ids[W["g"]])]["segment"])
             rec["score"][b], rec["runner_up"][b] = score, runner
-            rec["seed_a"][b], rec["seed_b"][b] = used[ka], used[kb]
-            rec["lm_a"][b], rec["lm_b"][b] = ids[hg[w]], ids[hh[w]]
+            rec["seed_a"][b], rec["seed_b"][b] = used[W["ka"]], used[W["kb"]]
+            rec["lm_a"][b], rec["lm_b"][b] = ids[W["g"]], ids[W["h"]]
             if score >= min_inliers:
                 flags |= FX_RELOC_VALID if score - runner >= min_margin else FX_RELOC_AMBIGUOUS
             rec["flags"][b] = flags
             if flags & FX_RELOC_VALID:
                 map_id[used[hit]] = ids[j[hit]]
     return {"rec": rec, "map_id_of_row": map_id, "hyp": hyps}
+
+
+def find_loop_records(out):
+    """A host copy of fx_map_find_loop's result (a torch tensor, or any array of 136 bytes) as a FIND_DTYPE record."""
+    if hasattr(out, "detach"):
+        out = out.detach().cpu().numpy()
+    return np.ascontiguousarray(out).view(np.uint8).reshape(-1).view(FIND_DTYPE).copy()[0]
+
+
+def map_find_loop_reference(state, **options):
+    """The definition of fx_map_find_loop (include/fx.h) in numpy float64 over a map_reference / map_merge_reference state (which is
+    only read); options: the fields of fx_map_find_loop_options (FIND_DEFAULTS).  Every (seed, g, h) and every (query, target)
+    pair is looked at: nothing here knows of a grid.  Returns {"rec": a FIND_DTYPE record, "match_of_landmark": int32
+    [max_landmarks], "hyp": the hypotheses as a dict of arrays s, g, h, score in (s, g, h) order, g and h landmark ids}."""
+    f64 = np.float64
+    bad = set(options) - set(FIND_DEFAULTS)
+    if bad:
+        raise TypeError(f"unknown find-loop options {sorted(bad)}")
+    o = dict(FIND_DEFAULTS, **options)
+    id32, pt32, mb32, xb32 = (np.float32(o[k]) for k in ("inlier_dist", "pair_tol", "min_baseline", "max_baseline"))
+    want_q, want_t = int(o["segment"]) & 0xffffffff, int(o["target_segment"]) & 0xffffffff
+    same = want_t == FX_FIND_SAME_SEGMENT
+    if not (all(np.isfinite(v) and v > 0 for v in (id32, pt32, mb32)) and np.isfinite(xb32) and xb32 >= mb32 and
+            1 <= o["max_seeds"] <= FX_FIND_MAX_QUERY and o["min_inliers"] >= 3 and o["min_margin"] >= 1 and o["min_landmark_obs"] >= 1 and
+            FX_LOC_ANY_SEGMENT not in (want_q, want_t) and (not same or 0 <= o["recent_scans"] < o["min_loop_scans"])):
+        raise ValueError("arguments outside what fx_map_find_loop accepts")
+    idd, ptd, mbd, xbd = f64(id32), f64(pt32), f64(mb32), f64(xb32)
+    id2, mb2, xb2 = idd * idd, mbd * mbd, xbd * xbd
+    two = f64(2.0) * idd
+    g2 = two * two
+    H, lms = state["header"], state["landmarks"]
+    N, SEG, scans = min(int(H["n_landmarks"]), len(lms)), int(H["segments"]), int(H["scans"])
+    last = scans - 1
+    last_seg = SEG - 1 if SEG else FX_FIND_NONE
+    qseg = last_seg if want_q == FX_LOC_LAST_SEGMENT else want_q
+    tseg = qseg if same else (last_seg if want_t == FX_LOC_LAST_SEGMENT else want_t)
+    rec = np.zeros(1, FIND_DTYPE)[0]
+    nan = np.array([FX_FIND_NAN_BITS], np.uint64).view(f64)[0]
+    for f in ("c", "s", "tx", "ty", "tz"):
+        rec[f] = nan
+    rec["wc"] = 1.0
+    for f in ("seed_a", "seed_b", "lm_a", "lm_b"):
+        rec[f] = FX_FIND_NONE
+    rec["segment"], rec["target_segment"] = qseg, tseg
+    match = np.full(int(state["max_landmarks"]), -1, np.int32)
+    empty = {k: np.zeros(0, np.int64) for k in ("s", "g", "h", "score")}
+    if qseg >= SEG or tseg >= SEG or scans == 0 or (not same and tseg == qseg):
+        rec["flags"] = FX_FIND_BAD_SEGMENT
+        return {"rec": rec, "match_of_landmark": match, "hyp": empty}
+    alias = [int(a) for a in state.get("alias", [])][:N]
+    alias += [-1] * (N - len(alias))
+    lx, ly, lz = (np.array([float(r[f]) for r in lms[:N]], f64) for f in ("x", "y", "z"))
+    seg = np.array([int(r["segment"]) for r in lms[:N]], np.int64)
+    first, last_of = (np.array([int(r[f]) for r in lms[:N]], np.int64) for f in ("first_scan", "last_scan"))
+    elig = np.array([alias[g] == -1 and int(lms[g]["n_obs"]) >= o["min_landmark_obs"] for g in range(N)], bool)
+    if N:
+        elig &= np.isfinite(lx) & np.isfinite(ly) & np.isfinite(lz)
+    is_t = elig & (seg == tseg)
+    if same:
+        is_t &= last_of + int(o["min_loop_scans"]) <= last
+    ids = np.flatnonzero(is_t)
+    cand = np.flatnonzero(elig & (seg == qseg) & (first + int(o["recent_scans"]) >= last) & ~is_t)[::-1]  # descending id
+    flags = FX_FIND_TRUNCATED if len(cand) > FX_FIND_MAX_QUERY else 0
+    used = cand[:FX_FIND_MAX_QUERY]
+    rec["n_query"], rec["n_targets"] = len(used), len(ids)
+    with np.errstate(all="ignore"):
+        found = _constellation_search(lx[used], ly[used], lz[used], lx[ids], ly[ids], lz[ids], id2, ptd, mb2, xb2, g2, o["max_seeds"])
+    rec["n_seeds"] = found["n_seeds"]
+    hs, hg, hh, hscore = found["hyp"]
+    rec["n_hyp"] = len(hs)
+    hyp = {"s": hs, "g": ids[hg] if len(hg) else hg, "h": ids[hh] if len(hh) else hh, "score": hscore}
+    W = found["win"]
+    if W is None:
+        rec["flags"] = flags | FX_FIND_NO_HYPOTHESIS
+        return {"rec": rec, "match_of_landmark": match, "hyp": hyp}
+    score, runner = W["score"], W["runner"]
+    rec["wc"], rec["ws"], rec["wtx"], rec["wty"] = W["T"]
+    rec["wtz"] = W["tz"]
+    rec["score"], rec["runner_up"] = score, runner
+    rec["seed_a"], rec["seed_b"] = used[W["ka"]], used[W["kb"]]
+    rec["lm_a"], rec["lm_b"] = ids[W["g"]], ids[W["h"]]
+    if score >= o["min_inliers"]:
+        flags |= FX_FIND_VALID if score - runner >= o["min_margin"] else FX_FIND_AMBIGUOUS
+    rec["flags"] = flags
+    if flags & FX_FIND_VALID:
+        for f in ("c", "s", "tx", "ty", "tz"):
+            rec[f] = rec["w" + f]
+        match[used[W["hit"]]] = ids[W["j"][W["hit"]]]
+    return {"rec": rec, "match_of_landmark": match, "hyp": hyp}
 
 
 def _np(ptr, shape, dtype):
@@ -2196,6 +2340,39 @@ class Map:
         check(self.lib.fx_map_close_loop(self.ctx.handle, self.handle, C.byref(pose) if pose is not None else None, C.c_void_p(prior_device),
                                          C.byref(opt), C.c_void_p(result.data_ptr() if result is not None else None),
                                          C.c_void_p(match.data_ptr() if match is not None else None)))
+        cur.wait_stream(ext)
+        return result, match
+
+    def find_loop(self, result=None, match=None, **opts):
+        """fx_map_find_loop: the transform that lays the recent landmarks of a segment on its old ones (or on another segment's,
+        target_segment), found without a prior (include/fx.h).  opts: the fields of fx_map_find_loop_options (FIND_DEFAULTS).
+        Returns (result, match_of_landmark): device tensors of 136 bytes (find_loop_records reads it; its first five doubles are
+        what close_loop and join_segments take as prior_device) and torch.int32 [max_landmarks]; a tensor given reuses it, match =
+        False passes NULL (None is returned in its place).  Stream-correct like merge(); never waits for the stream."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        bad = set(opts) - set(FIND_DEFAULTS)
+        if bad:
+            raise TypeError(f"unknown find-loop options {sorted(bad)}")
+        o = dict(FIND_DEFAULTS, **opts)
+        u = lambda k: int(o[k]) & 0xffffffff
+        opt = FxMapFindLoopOptions(float(o["inlier_dist"]), float(o["pair_tol"]), float(o["min_baseline"]), float(o["max_baseline"]),
+                                   u("max_seeds"), u("min_inliers"), u("min_margin"), u("min_landmark_obs"), u("segment"), u("target_segment"),
+                                   u("min_loop_scans"), u("recent_scans"), 0)
+        if result is None:
+            result = torch.empty((FIND_DTYPE.itemsize // 8,), dtype=torch.float64, device=dev)
+        if match is None:
+            match = torch.empty((self.max_landmarks,), dtype=torch.int32, device=dev)
+        elif match is False:
+            match = None
+        for t, size in ((result, FIND_DTYPE.itemsize), (match, self.max_landmarks * 4)):
+            if t is not None and (t.device != dev or not t.is_contiguous() or t.numel() * t.element_size() != size):
+                raise ValueError(f"outputs must be contiguous tensors of {FIND_DTYPE.itemsize} and {self.max_landmarks} * 4 bytes on {dev}")
+        cur = torch.cuda.current_stream(dev)
+        ext = torch.cuda.ExternalStream(self.ctx.stream_ptr(), device=dev)
+        ext.wait_stream(cur)
+        check(self.lib.fx_map_find_loop(self.ctx.handle, self.handle, C.byref(opt), C.c_void_p(result.data_ptr()),
+                                        C.c_void_p(match.data_ptr() if match is not None else None)))
         cur.wait_stream(ext)
         return result, match
 

@@ -95,6 +95,8 @@ hipError_t fxk_map_localize(hipStream_t s, const FxMapLocalizeArgs &A);
 size_t fxk_map_localize_scratch(FxMapLocalizeArgs *A, uint8_t *base);
 hipError_t fxk_map_relocalize(hipStream_t s, const FxMapRelocalizeArgs &A);
 size_t fxk_map_relocalize_scratch(FxMapRelocalizeArgs *A, uint8_t *base);
+hipError_t fxk_map_find_loop(hipStream_t s, const FxMapFindLoopArgs &A);
+size_t fxk_map_find_loop_scratch(FxMapFindLoopArgs *A, uint8_t *base);
 hipError_t fxk_map_compact(hipStream_t s, const FxMapCompactArgs &A);
 size_t fxk_map_compact_scratch(FxMapCompactArgs *A, uint8_t *base);
 hipError_t fxk_map_join(hipStream_t s, const FxMapJoinArgs &A);
@@ -2033,7 +2035,7 @@ fx_status fx_map_relocalize(fx_ctx *c, fx_map *m, const void *kp, uint32_t max_s
     G->cap = m->a.cap, G->max_carry = m->a.max_carry;
     G->table = fxk_map_merge_table(G->cap);
   }
-  // the two gates in fp64 and the grids' cell edges, gate (1 + 2^-8) (csrc/fx_map_grid.h proves the margin; csrc/fx_map_relocalize.hip
+  // the two gates in fp64 and the grids' cell edges, gate (1 + 2^-8) (csrc/fx_map_grid.h proves the margin; csrc/fx_map_constellation.h
   // derives the pair grid's gate (xb + pt)(1 + 2^-20) from the hypothesis's length gate)
   const double pd = ((double)o.max_baseline + (double)o.pair_tol) * (1.0 + 1.0 / 1048576.0), id = (double)o.inlier_dist;
   A.P.md2 = pd * pd, A.P.inv_edge = 1.0 / (pd * (1.0 + 1.0 / 256.0));
@@ -2218,6 +2220,69 @@ fx_status fx_map_loop_correct_poses(fx_ctx *c, const fx_map_loop_result *result,
   if (((uintptr_t)result % 8) != 0 || ((uintptr_t)poses % 8) != 0) return fail(FX_ERR_INVALID_ARG, "the result and the poses must be 8-byte aligned");
   FX_HIP(hipSetDevice(c->device));
   FX_HIP(fxk_map_loop_poses(c->stream, result, poses, first_global_scan, n_poses));
+  return FX_OK;
+}
+
+void fx_map_find_loop_options_default(fx_map_find_loop_options *o) {
+  if (!o) return;
+  o->inlier_dist = 0.30f;
+  o->pair_tol = 0.30f;
+  o->min_baseline = 2.0f;
+  o->max_baseline = 60.0f;
+  o->max_seeds = 16u;
+  o->min_inliers = 4u;
+  o->min_margin = 1u;
+  o->min_landmark_obs = 2u;
+  o->segment = FX_LOC_LAST_SEGMENT;
+  o->target_segment = FX_FIND_SAME_SEGMENT;
+  o->min_loop_scans = 256u;
+  o->recent_scans = 32u;
+  o->reserved = 0u;
+}
+
+fx_status fx_map_find_loop(fx_ctx *c, fx_map *m, const fx_map_find_loop_options *opt, fx_map_loop_candidate *result, int32_t *match_of_landmark) {
+  if (!c || !m || !result) return fail(FX_ERR_INVALID_ARG, "null argument");
+  if (m->ctx != c) return fail(FX_ERR_INVALID_ARG, "the map belongs to another context");
+  fx_map_find_loop_options o;
+  fx_map_find_loop_options_default(&o);
+  if (opt) o = *opt;
+  auto positive = [](float v) { return std::isfinite(v) && v > 0.f; };
+  if (!positive(o.inlier_dist)) return fail(FX_ERR_INVALID_ARG, "inlier_dist must be finite and positive");
+  if (!positive(o.pair_tol)) return fail(FX_ERR_INVALID_ARG, "pair_tol must be finite and positive");
+  if (!positive(o.min_baseline)) return fail(FX_ERR_INVALID_ARG, "min_baseline must be finite and positive");
+  if (!(std::isfinite(o.max_baseline) && o.max_baseline >= o.min_baseline))
+    return fail(FX_ERR_INVALID_ARG, "max_baseline must be finite and at least min_baseline");
+  if (o.max_seeds < 1u || o.max_seeds > FX_FIND_MAX_QUERY) return fail(FX_ERR_INVALID_ARG, "max_seeds must be 1..64");
+  if (o.min_inliers < 3u) return fail(FX_ERR_INVALID_ARG, "min_inliers must be at least 3");
+  if (!o.min_margin) return fail(FX_ERR_INVALID_ARG, "min_margin must be at least 1");
+  if (!o.min_landmark_obs) return fail(FX_ERR_INVALID_ARG, "min_landmark_obs must be at least 1");
+  if (o.segment == FX_LOC_ANY_SEGMENT) return fail(FX_ERR_INVALID_ARG, "segment must be one segment or FX_LOC_LAST_SEGMENT, not FX_LOC_ANY_SEGMENT");
+  if (o.target_segment == FX_LOC_ANY_SEGMENT)
+    return fail(FX_ERR_INVALID_ARG, "target_segment must be one segment, FX_LOC_LAST_SEGMENT or FX_FIND_SAME_SEGMENT, not FX_LOC_ANY_SEGMENT");
+  if (o.target_segment == FX_FIND_SAME_SEGMENT && o.recent_scans >= o.min_loop_scans)
+    return fail(FX_ERR_INVALID_ARG, "recent_scans must be below min_loop_scans when the targets are the segment's own");
+  if (o.reserved) return fail(FX_ERR_INVALID_ARG, "reserved must be 0");
+  if (((uintptr_t)result % 8) != 0 || ((uintptr_t)match_of_landmark % 4) != 0)
+    return fail(FX_ERR_INVALID_ARG, "the result must be 8-byte, match_of_landmark 4-byte aligned");
+  FX_HIP(hipSetDevice(c->device));
+  FxMapFindLoopArgs A{};
+  for (FxMapMergeArgs *G : {&A.P, &A.Q}) {
+    G->header = m->a.header, G->records = m->a.records, G->acc = m->a.acc, G->carry = m->a.carry, G->alias = m->a.alias;
+    G->cap = m->a.cap, G->max_carry = m->a.max_carry;
+    G->table = fxk_map_merge_table(G->cap);
+  }
+  // the two gates and the grids' cell edges: fx_map_relocalize's (csrc/fx_map_constellation.h derives the pair grid's gate)
+  const double pd = ((double)o.max_baseline + (double)o.pair_tol) * (1.0 + 1.0 / 1048576.0), id = (double)o.inlier_dist;
+  A.P.md2 = pd * pd, A.P.inv_edge = 1.0 / (pd * (1.0 + 1.0 / 256.0));
+  A.Q.md2 = id * id, A.Q.inv_edge = 1.0 / (id * (1.0 + 1.0 / 256.0));
+  A.inlier_dist = o.inlier_dist, A.pair_tol = o.pair_tol, A.min_baseline = o.min_baseline, A.max_baseline = o.max_baseline;
+  A.max_seeds = o.max_seeds, A.min_inliers = o.min_inliers, A.min_margin = o.min_margin, A.min_landmark_obs = o.min_landmark_obs;
+  A.segment = o.segment, A.target_segment = o.target_segment, A.min_loop_scans = o.min_loop_scans, A.recent_scans = o.recent_scans;
+  A.chunks = (A.P.cap + FXR_CHUNK - 1u) / FXR_CHUNK;
+  A.result = result, A.match = match_of_landmark;
+  FX_TRY(c->merge_scratch.reserve(c, fxk_map_find_loop_scratch(&A, nullptr), "map find loop scratch"));
+  (void)fxk_map_find_loop_scratch(&A, c->merge_scratch.d);
+  FX_HIP(fxk_map_find_loop(c->stream, A));
   return FX_OK;
 }
 

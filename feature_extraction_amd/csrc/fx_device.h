@@ -367,6 +367,29 @@ struct FxMapLoopArgs {
   uint32_t *bsum;               // [2][blocks of landmarks]: the block's queries / queries with a target, then their prefix
   uint32_t *corr;               // [FX_LOOP_MAX_CORR]: the queries of the correspondences, in ascending id
 };
+// fx_map_find_loop (csrc/fx_map_find_loop.hip): a launch set's arguments.  P and Q are fx_map_relocalize's two grids (the search
+// is csrc/fx_map_constellation.h's, with the loop's queries in the place of a scan's keypoints); the last group is the context's
+// scratch.
+#define FX_FIND_ST_WORDS 8  // 0 n_targets, 1 the best rival's score (atomic max), 2 n_query, 3 n_seeds, 4 FX_FIND_TRUNCATED or 0,
+                            // 5 qseg, 6 tseg (resolved; 0xffffffff: FX_LOC_LAST_SEGMENT in a map of no segment), 7 FX_FIND_BAD_SEGMENT or 0
+struct FxMapFindLoopArgs {
+  FxMapMergeArgs P, Q;
+  float inlier_dist, pair_tol, min_baseline, max_baseline;
+  uint32_t max_seeds, min_inliers, min_margin, min_landmark_obs;
+  uint32_t segment, target_segment;  // the options' (FX_LOC_LAST_SEGMENT and FX_FIND_SAME_SEGMENT are resolved on the device)
+  uint32_t min_loop_scans, recent_scans;
+  uint32_t chunks;              // workgroups of the hypothesis kernel a seed: ceil(cap / FXR_CHUNK)
+  void *result;                 // fx_map_loop_candidate
+  int32_t *match;               // [cap] or null
+  unsigned long long *n_hyp;    // [1]; st follows it (one memset clears both)
+  uint32_t *st;                 // [FX_FIND_ST_WORDS]
+  uint8_t *elig;                // [cap]: 0 neither, 1 target, 2 query
+  double *kq;                   // [64][3]: the queries' x, y, z, in descending id
+  uint32_t *kid;                // [64]: their ids
+  uint32_t *seeds;              // [64]: a | b << 8 of seed rank s
+  FxRelocPartial *partial;      // [max_seeds][chunks]
+  FxRelocWinner *win;           // [1]
+};
 #define FX_TRACK_NONE 0xffffffffu
 #define FX_N_HINTS 8   // tier_hint[]: 0 / 1 rings handed to the second run tier / the workgroup tier (largest XCD class), 2 big merges, 3 huge merges, 4 dense rows, 5 dense support points, 6 scans k_front handed to k_front_redo, 7 scans handed to the slow tier (k_slow)
 #define FX_CNT_QPOOL 32   // counters[32]: entries of the dense tier's query pool in use

@@ -1,8 +1,8 @@
 // fx_map_grid.h — the hashed grid over the map's live landmarks, which fx_map_merge (csrc/fx_map_merge.hip: a landmark looks for
 // its predecessor), fx_map_localize (csrc/fx_map_localize.hip: a keypoint looks for its landmark), fx_map_join_segments
 // (csrc/fx_map_join.hip: a landmark of one segment looks for its twin in another) and fx_map_close_loop (csrc/fx_map_loop.hip: a
-// recent landmark looks for its old twin in the same segment) search.  The kernels that
-// build it are csrc/fx_map_grid.hip's; what a search needs on the device is here.
+// recent landmark looks for its old twin in the same segment) search; fx_map_relocalize and fx_map_find_loop walk two of them
+// (csrc/fx_map_constellation.h).  The kernels that build it are csrc/fx_map_grid.hip's; what a search needs on the device is here.
 //
 // A grid is described by an FxMapMergeArgs (fx_device.h): the gate md2 = d d with d the call's distance widened to double, inv_edge
 // = 1 / the cell edge, the table of `table` buckets (a power of two; bucket `table` is the far list) and the scratch arrays

@@ -1219,6 +1219,104 @@ fx_status fx_map_close_loop(fx_ctx *ctx, fx_map *map,
 fx_status fx_map_loop_correct_poses(fx_ctx *ctx, const fx_map_loop_result *result_device,
     fx_pose *poses_device, uint32_t first_global_scan, uint32_t n_poses);
 
+/* ---- Finding a loop's closure without a prior: the recent landmarks laid on the old ones as a constellation ----
+ * fx_map_close_loop and fx_map_join_segments need a prior within search_dist of the truth.  Once the drift of a loop (or the
+ * displacement of a segment) is larger, fx_map_localize matches a scan to the recent copies of the poles and fx_map_relocalize
+ * sees both copies as rivals of each other.  fx_map_find_loop runs fx_map_relocalize's constellation search on the map's own
+ * landmarks with the loop's two time windows: the RECENT landmarks of one segment (the queries) stand in the place of a scan's
+ * keypoints, and only the OLD landmarks of that segment, or the landmarks of another segment (the targets), can be landed on.
+ * The first 40 bytes of its result are five doubles c, s, tx, ty, tz: what fx_map_close_loop and fx_map_join_segments take as
+ * prior_device, so find-then-close and find-then-join need no host read.  It is enqueued on the context's stream (no host
+ * synchronisation, no allocation in the steady state: its scratch is the context-owned buffer the other map calls share, grown
+ * as needed) and READS the map only: header, records, sums, alias, carry and the carry scan are bit for bit what they were.
+ * Every floating-point step is fp64, no contraction, no fma, no transcendental; id, pt, mb, xb are inlier_dist, pair_tol,
+ * min_baseline and max_baseline widened to double.
+ * ONE CALL, with N = header.n_landmarks, SEG = header.segments and last = header.scans - 1 as they are when the call runs on the
+ * stream:
+ * Segments: qseg is opt.segment, FX_LOC_LAST_SEGMENT standing for SEG - 1.  tseg is opt.target_segment: FX_FIND_SAME_SEGMENT
+ * (the default) stands for qseg, any other value is a global segment number or FX_LOC_LAST_SEGMENT.
+ * Device refusal: qseg >= SEG or tseg >= SEG (a map of no segment included), header.scans == 0, or a target_segment other than
+ * FX_FIND_SAME_SEGMENT that resolves to qseg, gives flags = FX_FIND_BAD_SEGMENT alone: the record is that of a call without a
+ * winner (below) with n_hyp = n_query = n_targets = n_seeds = 0, segment and target_segment the resolved numbers (0xffffffff
+ * where FX_LOC_LAST_SEGMENT met a map of no segment), and every word of match_of_landmark is -1.
+ * Eligible: fx_map_localize's clause: g < N with alias[g] == -1, n_obs >= min_landmark_obs and x, y and z finite.
+ * Targets: the eligible g of segment tseg; when tseg is qseg (FX_FIND_SAME_SEGMENT) they must also be OLD, (uint64)last_scan +
+ * min_loop_scans <= last.  n_targets is their number.
+ * Queries: the candidates are the eligible i of segment qseg with (uint64)first_scan + recent_scans >= last (recent_scans =
+ * 0xffffffff admits the whole segment).  They are taken in DESCENDING id and at most the first FX_FIND_MAX_QUERY are used (more:
+ * FX_FIND_TRUNCATED): the youngest landmarks are the ones the vehicle is among.  Query k is the k-th used one in that order,
+ * n_query the number used; their coordinates are the records' doubles as they are.  No landmark is both a query and a target
+ * (recent_scans < min_loop_scans in one segment; two segments otherwise).
+ * Seeds, hypotheses, score: fx_map_relocalize's clauses word for word, query k in the place of keypoint k and the targets in the
+ * place of the eligible landmarks: the candidate pairs (a, b), a < b, of queries with mb mb <= d2 <= xb xb, ranked by descending
+ * d2 bits, then ascending (a, b), the first n_seeds = min(count, max_seeds) used; for the seed of rank s every ordered pair (g, h),
+ * g != h, of targets under the hypothesis clause in fp64 with mb mb as the baseline gate and pt as the length gate; the score of a
+ * hypothesis is the number of queries whose image has a target with d2 <= id id.  n_hyp counts the hypotheses.
+ * Winner: the hypothesis of highest score, ties to the lowest (s, g, h).  A best score below 2, or no hypothesis, is NO WINNER:
+ * flags = FX_FIND_NO_HYPOTHESIS (and FX_FIND_TRUNCATED when it applies), wc = 1, ws = wtx = wty = wtz = 0, score = runner_up = 0,
+ * seed_a = seed_b = lm_a = lm_b = 0xffffffff; the counts are what they are.
+ * Rivals and runner_up: fx_map_relocalize's clause with g = 2.0 id.
+ * With a winner: the target of a query is the target of lowest (d2 as uint64 bits, id) among those with d2 <= id id of its image
+ * (the SCORED queries are those that have one); wtz is the sequential sum, in ascending k, of Z[target] - z over the scored
+ * queries, divided once by (double)score; wc, ws, wtx, wty are the winner's transform, query frame -> target frame; seed_a,
+ * seed_b are the landmark ids of the winning seed's queries and lm_a, lm_b the targets g, h.  FX_FIND_VALID iff score >=
+ * min_inliers and score - runner_up >= min_margin; FX_FIND_AMBIGUOUS iff score >= min_inliers and the margin fails; neither below
+ * min_inliers.
+ * The head: with FX_FIND_VALID c, s, tx, ty, tz = wc, ws, wtx, wty, wtz.  Without it all five are the quiet NaN
+ * 0x7ff8000000000000, on purpose: a chained fx_map_close_loop or fx_map_join_segments then answers FX_LOOP_BAD_PRIOR or
+ * FX_JOIN_BAD_PRIOR and leaves the map bit for bit, so a loop that was not found can never move the map.
+ * match_of_landmark (when given): all max_landmarks words are written; word i is the target of query i for the scored queries of
+ * a FX_FIND_VALID result and -1 everywhere else.
+ * The chains: fx_map_find_loop, then fx_map_close_loop(NULL, (const double *)result, search_dist about 2 inlier_dist), then
+ * fx_map_loop_correct_poses, fx_map_merge and fx_map_compact; or fx_map_find_loop with target_segment = dst and segment = src,
+ * then fx_map_join_segments(src, dst, NULL, (const double *)result).
+ * FX_ERR_INVALID_ARG with the reason in fx_last_error(), nothing launched, no byte touched: a NULL ctx, map or result, a map of
+ * another context, inlier_dist, pair_tol or min_baseline not finite and positive, max_baseline not finite or below min_baseline,
+ * max_seeds outside 1..64, min_inliers < 3, min_margin == 0, min_landmark_obs == 0, segment or target_segment ==
+ * FX_LOC_ANY_SEGMENT, recent_scans >= min_loop_scans with target_segment == FX_FIND_SAME_SEGMENT, reserved != 0, result_device
+ * not 8-byte aligned, match_of_landmark_device not 4-byte aligned.
+ * The same bytes from run to run and with any number of contexts in flight: every decision is an integer (32- and 64-bit integer
+ * atomics only, sum and maximum) or a minimum over a total order, every fp64 value an ordered chain on one lane.  The two grids
+ * (fx_map_relocalize's) and the reduction never show in a result; numpy float64 reproduces the record and match_of_landmark bit
+ * for bit.
+ * Limits: as fx_map_relocalize: the transform is that of ONE two-point hypothesis, which the chained call refits over all
+ * correspondences; poles that repeat a pattern come back AMBIGUOUS; fewer than three twins cannot be VALID.  One call finds one
+ * loop.  New in 0.7 (added symbols only). */
+#define FX_FIND_MAX_QUERY 64u
+#define FX_FIND_SAME_SEGMENT 0xfffffffdu  /* target_segment: the targets are the old landmarks of opt.segment itself */
+typedef struct fx_map_find_loop_options {   /* 52 B */
+  float inlier_dist;      /* a query lands on a target within this xy distance, m; finite, > 0; default 0.30 */
+  float pair_tol;         /* allowed difference between a seed's length and a target pair's; finite, > 0; default 0.30 */
+  float min_baseline;     /* shortest seed pair, m; finite, > 0; default 2.0 */
+  float max_baseline;     /* longest seed pair, m; finite, >= min_baseline; default 60.0 */
+  uint32_t max_seeds;     /* seed pairs tried; 1..64, default 16 */
+  uint32_t min_inliers;   /* score needed for FX_FIND_VALID; >= 3, default 4 */
+  uint32_t min_margin;    /* lead needed over the best rival; >= 1, default 1 */
+  uint32_t min_landmark_obs; /* a landmark takes part with at least this many observations; >= 1, default 2 */
+  uint32_t segment;       /* the queries' segment: a global segment, or FX_LOC_LAST_SEGMENT (default); FX_LOC_ANY_SEGMENT is refused */
+  uint32_t target_segment; /* FX_FIND_SAME_SEGMENT (default), a global segment other than `segment`, or FX_LOC_LAST_SEGMENT */
+  uint32_t min_loop_scans; /* as fx_map_loop_options; ignored when the targets are another segment's; default 256 */
+  uint32_t recent_scans;  /* as fx_map_loop_options; < min_loop_scans with FX_FIND_SAME_SEGMENT; default 32 */
+  uint32_t reserved;      /* 0 */
+} fx_map_find_loop_options;
+#define FX_FIND_VALID 0x1u         /* score >= min_inliers and score - runner_up >= min_margin: c, s, tx, ty, tz are the transform */
+#define FX_FIND_TRUNCATED 0x2u     /* more than FX_FIND_MAX_QUERY candidate queries: the 64 of highest id were used */
+#define FX_FIND_NO_HYPOTHESIS 0x4u /* no hypothesis, or none that lands 2 queries */
+#define FX_FIND_AMBIGUOUS 0x8u     /* score >= min_inliers, but a rival transform scores within min_margin of it */
+#define FX_FIND_BAD_SEGMENT 0x10u  /* a segment is not below header.segments, the map has no scans, or target_segment names segment */
+typedef struct fx_map_loop_candidate {  /* 136 B */
+  double c, s, tx, ty, tz;          /* with FX_FIND_VALID the winner's transform, query frame -> target frame; else quiet NaNs */
+  double wc, ws, wtx, wty, wtz;     /* the winner's transform whenever there is one (AMBIGUOUS included); else the identity */
+  uint64_t n_hyp;                   /* hypotheses counted */
+  uint32_t n_query, n_targets, n_seeds, score, runner_up, flags;
+  uint32_t seed_a, seed_b;          /* landmark ids of the winning seed's queries, 0xffffffff: none */
+  uint32_t lm_a, lm_b;              /* the targets they were laid on, 0xffffffff: none */
+  uint32_t segment, target_segment; /* the resolved numbers */
+} fx_map_loop_candidate;
+void fx_map_find_loop_options_default(fx_map_find_loop_options *o);
+fx_status fx_map_find_loop(fx_ctx *ctx, fx_map *map, const fx_map_find_loop_options *opt /* NULL: defaults */,
+    fx_map_loop_candidate *result_device, int32_t *match_of_landmark_device /* [max_landmarks] or NULL */);
+
 /* Rotation matrix of rotateCloud (ref: node.cpp:161-164): R = Ry(pitch)*Rx(roll)
  * through Eigen's AngleAxisf -> Quaternionf -> toRotationMatrix, all float. Host only. */
 void fx_rotation_from_roll_pitch(double roll, double pitch, float R[9]);

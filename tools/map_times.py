@@ -53,6 +53,14 @@ prior.  Every repeat resets the map, updates it and closes (timed: one pair of H
 the consensus over the first 1024 correspondences, N / 3 landmarks moved), then corrects 1024 poses (timed).  The join of --join is
 timed on the same maps in the same run for the column beside it.  Reported per size: the medians and the closure's result.  No target
 is set.
+  timeout -k 10 600 python tools/map_times.py --find-loop [--sizes 10000,100000,1000000] [--warmup 1] [--repeats 5] [--out profiles/map_find_loop_times.txt]
+
+times fx_map_find_loop: for every size N a map of one segment taken in as a snapshot: N - 40 old landmarks uniform in a square at the
+loop world's density (1 pole per 160 m^2, scans 0-5) and 40 recent ones (scans 395-400, the highest ids): twins of the 40 poles
+nearest to a random position, moved by a drift of 0.13 rad and 7.8 m with 1 cm of noise.  Timed with one pair of HIP events each:
+fx_map_find_loop with default options (40 queries, 16 seeds), and on the same map fx_map_relocalize of one scan holding the same 40
+points as float keypoints (any segment: it sees both copies), whose walk the new call shares.  Reported per size: the medians, their
+ratio and the result.  No target is set.
 """
 import argparse
 import ctypes as C
@@ -462,6 +470,95 @@ def main_loop(a):
             f.write(s + "\n")
 
 
+def find_loop_case(n, rng, n_recent=40):
+    """(the snapshot of a one-segment map of n landmarks, the recent ones' x, y, z): n - n_recent old landmarks of two observations at 1
+    pole per 160 m^2 and n_recent recent twins of the poles nearest to a random position, drifted."""
+    n_old = n - n_recent
+    side = (n_old * 160.0) ** 0.5
+    old = np.concatenate([rng.uniform(0.0, side, (n_old, 2)), rng.uniform(0.0, 2.0, (n_old, 1))], axis=1).astype(np.float32).astype(np.float64)
+    at = rng.uniform(0.25 * side, 0.75 * side, 2)
+    near = np.argsort(((old[:, :2] - at) ** 2).sum(axis=1))[:n_recent]
+    yaw, t = 0.13, np.array([7.75, 0.53])
+    c, s = np.cos(yaw), np.sin(yaw)
+    d = old[near, :2] - t
+    rec = np.stack([c * d[:, 0] + s * d[:, 1], -s * d[:, 0] + c * d[:, 1], old[near, 2]], axis=1) + 0.01 * rng.standard_normal((n_recent, 3))
+    rec = rec.astype(np.float32).astype(np.float64)
+    xyz = np.concatenate([old, rec])
+    scans = [(0, 5)] * n_old + [(395, 400)] * n_recent
+    st = capi.map_state(n, 16)
+    st["landmarks"] = [dict(x=float(p[0]), y=float(p[1]), z=float(p[2]), rms_xy=np.float32(0.0), n_obs=2, first_scan=a, last_scan=b, segment=0, flags=0)
+                       for p, (a, b) in zip(xyz, scans)]
+    st["acc"] = np.concatenate([2.0 * xyz, xyz[:, :2], np.zeros((n, 3))], axis=1).tolist()
+    st["header"] = dict(st["header"], n_landmarks=n, n_needed=n, n_obs=2 * n, scans=401, batches=1, segments=1)
+    return capi.map_snapshot_pack(st), rec
+
+
+def measure_find_loop(ctx, n, warmup, repeats):
+    import torch
+    blob, rec = find_loop_case(n, np.random.default_rng(n))
+    mp = ctx.map_create(n, 16)
+    mp.import_state(blob)
+    K = len(rec)
+    k0, n_blk = capi.keypoint_block_layout(1, K)
+    sb = np.zeros((n_blk, 4), np.float32)
+    u = sb.view(np.uint32).reshape(-1)
+    u[:4] = (1, K, 0, K)
+    u[4:6] = (0, K)
+    sb[k0:k0 + K, :3] = rec
+    skp = (torch.from_numpy(sb.view(np.uint8).reshape(-1)).cuda(), 1, K)
+    res = torch.zeros((capi.FIND_DTYPE.itemsize // 8,), dtype=torch.float64, device="cuda")
+    match = torch.empty((n,), dtype=torch.int32, device="cuda")
+    stream = torch.cuda.ExternalStream(ctx.stream_ptr())
+    torch.cuda.synchronize()
+    t = {"find_ms": [], "relocalize_ms": []}
+    first = reloc = None
+    for rep in range(warmup + repeats):
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        e[0].record(stream)
+        mp.find_loop(result=res, match=match)
+        e[1].record(stream), e[2].record(stream)
+        recs, _ = mp.relocalize(skp, 1)
+        e[3].record(stream)
+        ctx.synchronize()
+        got, reloc = capi.find_loop_records(res), capi.relocalize_records(recs)[0]
+        first = got if first is None else first
+        assert got.tobytes() == first.tobytes(), (got, first)
+        if rep >= warmup:
+            for k, (a, b) in zip(t, ((0, 1), (2, 3))):
+                t[k].append(e[a].elapsed_time(e[b]))
+    mp.close()
+    out = {"landmarks": n, "result": {k: (float(first[k]) if first[k].dtype.kind == "f" else int(first[k])) for k in capi.FIND_DTYPE.names},
+           "relocalize": {k: int(reloc[k]) for k in ("n_hyp", "n_kp", "n_seeds", "score", "runner_up", "flags")}}
+    for k, v in t.items():
+        out[k] = statistics.median(v)
+        out[k + "_min_max"] = [min(v), max(v)]
+    return out
+
+
+def main_find_loop(a):
+    sizes = [int(x) for x in a.sizes.split(",")]
+    ctx = capi.Context(capi.params("launch"), capi.limits(2, 1024))
+    rows = [measure_find_loop(ctx, n, a.warmup, a.repeats) for n in sizes]
+    ctx.close()
+    lines = [f"fx_map_find_loop next to fx_map_relocalize on synthetic maps (tools/map_times.py --find-loop): 1 pole per 160 m^2, one segment, 40",
+             f"recent landmarks that are drifted twins of 40 old ones; find: default options (40 queries, 16 seeds); relocalize: one scan of the",
+             f"same 40 points, any segment; one context, HIP events around each call, median of {a.repeats} after {a.warmup} warm-up; ms",
+             f"{'landmarks':>10} {'targets':>8} {'n_hyp':>9} {'score':>6} {'runner':>7} {'flags':>6} {'find':>9} {'find / size before':>19} {'relocalize':>11} {'its n_hyp':>10} "
+             f"{'find / relocalize':>18}"]
+    for k, r in enumerate(rows):
+        ratio = f"{r['find_ms'] / rows[k - 1]['find_ms']:.2f}" if k else "-"
+        q = r["result"]
+        lines.append(f"{r['landmarks']:>10} {q['n_targets']:>8} {q['n_hyp']:>9} {q['score']:>6} {q['runner_up']:>7} {q['flags']:>#6x} {r['find_ms']:>9.3f} {ratio:>19} "
+                     f"{r['relocalize_ms']:>11.3f} {r['relocalize']['n_hyp']:>10} {r['find_ms'] / r['relocalize_ms']:>18.2f}")
+    s = "\n".join(lines)
+    print(s)
+    print(json.dumps(rows))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(s + "\n")
+
+
 def main_relocalize(a):
     sizes = [int(x) for x in a.sizes.split(",")]
     ctx = capi.Context(capi.params("launch"), capi.limits(2, 1024))
@@ -535,6 +632,7 @@ def main():
     ap.add_argument("--relocalize", action="store_true", help="time fx_map_relocalize on the synthetic maps instead (pass --sizes 10000,100000)")
     ap.add_argument("--join", action="store_true", help="time fx_map_join_segments on two-segment synthetic maps instead")
     ap.add_argument("--loop", action="store_true", help="time fx_map_close_loop on the synthetic maps taken as one loop instead")
+    ap.add_argument("--find-loop", action="store_true", help="time fx_map_find_loop next to fx_map_relocalize on one-segment synthetic maps instead")
     ap.add_argument("--sizes", default="1000,100000,1000000")
     ap.add_argument("--scans", type=int, default=1024)
     ap.add_argument("--batch", type=int, default=128)
@@ -555,6 +653,8 @@ def main():
         return main_join(a)
     if a.loop:
         return main_loop(a)
+    if a.find_loop:
+        return main_find_loop(a)
     N = 28800
     ctx = capi.Context(capi.params("launch"), capi.limits(a.batch, N, sparse=True))
     scenes = np.stack([capi.synth_scan(capi.synth_cfg(1000 + b)) for b in range(a.scans)])
