@@ -4,6 +4,7 @@ Plumbing for tests/ and bench.py only: the product is the C-ABI library and the 
 classes above it (csrc/fx_node.hpp).  Loading fails loudly when the library is missing —
 there is no Python/CPU fallback for the hot path.
 """
+import contextlib
 import ctypes as C
 import math
 import os
@@ -2092,6 +2093,52 @@ def map_find_loop_reference(state, **options):
     return {"rec": rec, "match_of_landmark": match, "hyp": hyp}
 
 
+@contextlib.contextmanager
+def _on_stream(stream_ptr, dev):
+    """The stream hand-over of every wrapper that enqueues on a context's stream: that stream (stream_ptr, a hipStream_t as an
+    integer) waits for what the caller's current stream on dev has queued, the body enqueues, and the caller's current stream
+    waits for it.  Nothing waits on the host; when the body raises, nothing was enqueued and nobody waits."""
+    import torch
+    cur = torch.cuda.current_stream(dev)
+    ext = torch.cuda.ExternalStream(stream_ptr, device=dev)
+    ext.wait_stream(cur)
+    yield
+    cur.wait_stream(ext)
+
+
+def _options(struct, defaults, what, opts):
+    """An options structure of include/fx.h from its *_DEFAULTS and the caller's **opts, field by field: a float field takes
+    float(value), a uint32 field the value's low 32 bits, `reserved` stays 0."""
+    bad = set(opts) - set(defaults)
+    if bad:
+        raise TypeError(f"unknown {what} options {sorted(bad)}")
+    o = dict(defaults, **opts)
+    opt = struct()
+    for name, ctype in struct._fields_:
+        if name != "reserved":
+            setattr(opt, name, float(o[name]) if ctype in (C.c_float, C.c_double) else int(o[name]) & 0xffffffff)
+    return opt
+
+
+def _out_tensor(t, shape, dtype, dev, error, typed=False):
+    """An output tensor the caller may give: None allocates `shape` of `dtype` on dev, False passes NULL (None is returned), a
+    tensor is used when it is contiguous, on dev and of the same bytes (typed: of the same dtype and shape), else ValueError(error)."""
+    import torch
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    if t is False:
+        return None
+    fits = (t.dtype == dtype and tuple(t.shape) == tuple(shape)) if typed else t.numel() * t.element_size() == math.prod(shape) * dtype.itemsize
+    if t.device != dev or not t.is_contiguous() or not fits:
+        raise ValueError(error)
+    return t
+
+
+def _ptr(t):
+    """The device address of an optional tensor as ctypes takes it: NULL for None."""
+    return C.c_void_p(t.data_ptr() if t is not None else None)
+
+
 def _np(ptr, shape, dtype):
     n = int(np.prod(shape))
     if n == 0 or not ptr:
@@ -2123,6 +2170,20 @@ class Map:
         """fx_map_reset: enqueues the state of a fresh map."""
         check(self.lib.fx_map_reset(self.ctx.handle, self.handle))
 
+    def _result_and_match(self, dtype, result, match):
+        """The two outputs of join_segments, close_loop and find_loop: a record of `dtype` as float64 words and match_of_landmark."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        error = f"outputs must be contiguous tensors of {dtype.itemsize} and {self.max_landmarks} * 4 bytes on {dev}"
+        return (_out_tensor(result, (dtype.itemsize // 8,), torch.float64, dev, error),
+                _out_tensor(match, (self.max_landmarks,), torch.int32, dev, error))
+
+    @staticmethod
+    def _prior(prior, prior_device):
+        """The prior of join_segments and close_loop as the library takes it: (byref of an fx_pose or None, a device address or None)."""
+        pose = C.byref(FxPose(*(float(v) for v in tuple(prior)[:5]), 0, 0)) if prior is not None else None
+        return pose, prior_device.data_ptr() if hasattr(prior_device, "data_ptr") else prior_device
+
     def update(self, kp, track_out, overlap=True, row_ids=None):
         """fx_map_update: kp is the keypoint block as (device tensor, max_scans, max_total_keypoints) and track_out the five device
         tensors Context.track_landmarks returned for it.  overlap: FX_MAP_OVERLAP (this batch's scan 0 is the last scan of the
@@ -2133,20 +2194,11 @@ class Map:
         poses, lor, obs, lms, hdr = track_out
         dev = torch.device("cuda", self.ctx.device)
         n_rows, max_landmarks = int(lor.shape[0]), int(lms.shape[0])
-        if row_ids is None:
-            row_ids = torch.empty((n_rows,), dtype=torch.int32, device=dev)
-        elif row_ids is False:
-            row_ids = None
-        elif row_ids.dtype != torch.int32 or row_ids.device != dev or tuple(row_ids.shape) != (n_rows,) or not row_ids.is_contiguous():
-            raise ValueError(f"row_ids must be a contiguous torch.int32 tensor [{n_rows}] on {dev}")
-        cur = torch.cuda.current_stream(dev)
-        ext = torch.cuda.ExternalStream(self.ctx.stream_ptr(), device=dev)
-        ext.wait_stream(cur)
-        check(self.lib.fx_map_update(self.ctx.handle, self.handle, C.c_void_p(kb.data_ptr()), int(scans), int(total), C.c_void_p(poses.data_ptr()),
-                                     C.c_void_p(lor.data_ptr()), C.c_void_p(obs.data_ptr()), n_rows, C.c_void_p(lms.data_ptr()), max_landmarks,
-                                     C.c_void_p(hdr.data_ptr()), FX_MAP_OVERLAP if overlap else 0,
-                                     C.c_void_p(row_ids.data_ptr() if row_ids is not None else None)))
-        cur.wait_stream(ext)
+        row_ids = _out_tensor(row_ids, (n_rows,), torch.int32, dev, f"row_ids must be a contiguous torch.int32 tensor [{n_rows}] on {dev}", typed=True)
+        with _on_stream(self.ctx.stream_ptr(), dev):
+            check(self.lib.fx_map_update(self.ctx.handle, self.handle, C.c_void_p(kb.data_ptr()), int(scans), int(total), C.c_void_p(poses.data_ptr()),
+                                         C.c_void_p(lor.data_ptr()), C.c_void_p(obs.data_ptr()), n_rows, C.c_void_p(lms.data_ptr()), max_landmarks,
+                                         C.c_void_p(hdr.data_ptr()), FX_MAP_OVERLAP if overlap else 0, _ptr(row_ids)))
         return row_ids
 
     def merge(self, merge_dist=0.30, max_gap_scans=64, result=None):
@@ -2155,18 +2207,10 @@ class Map:
         passes NULL (None is returned).  Stream-correct like update(); never waits for the stream."""
         import torch
         dev = torch.device("cuda", self.ctx.device)
-        if result is None:
-            result = torch.empty((4,), dtype=torch.int32, device=dev)
-        elif result is False:
-            result = None
-        elif result.dtype != torch.int32 or result.device != dev or tuple(result.shape) != (4,) or not result.is_contiguous():
-            raise ValueError(f"result must be a contiguous torch.int32 tensor [4] on {dev}")
+        result = _out_tensor(result, (4,), torch.int32, dev, f"result must be a contiguous torch.int32 tensor [4] on {dev}", typed=True)
         opt = FxMapMergeOptions(float(merge_dist), int(max_gap_scans))
-        cur = torch.cuda.current_stream(dev)
-        ext = torch.cuda.ExternalStream(self.ctx.stream_ptr(), device=dev)
-        ext.wait_stream(cur)
-        check(self.lib.fx_map_merge(self.ctx.handle, self.handle, C.byref(opt), C.c_void_p(result.data_ptr() if result is not None else None)))
-        cur.wait_stream(ext)
+        with _on_stream(self.ctx.stream_ptr(), dev):
+            check(self.lib.fx_map_merge(self.ctx.handle, self.handle, C.byref(opt), _ptr(result)))
         return result
 
     def localize(self, kp, prior_poses, n_scans, q_max_rows=None, out=None, nearest=None, **opts):
@@ -2181,29 +2225,16 @@ class Map:
         dev = torch.device("cuda", self.ctx.device)
         n_scans = int(n_scans)
         n_rows = int(total) if q_max_rows is None else int(q_max_rows)
-        bad = set(opts) - set(LOC_DEFAULTS)
-        if bad:
-            raise TypeError(f"unknown localize options {sorted(bad)}")
-        o = dict(LOC_DEFAULTS, **opts)
-        opt = FxLocalizeOptions(float(o["search_dist"]), float(o["inlier_dist"]), float(o["min_baseline"]), int(o["hyp_corr"]),
-                                int(o["min_inliers"]), int(o["min_landmark_obs"]), int(o["segment"]) & 0xffffffff, 0)
-        if out is None:
-            out = (torch.empty((n_scans, LOC_DTYPE.itemsize // 8), dtype=torch.float64, device=dev), torch.empty((n_rows,), dtype=torch.int32, device=dev))
-        recs, ids = out
-        if nearest is None:
-            nearest = torch.empty((n_rows,), dtype=torch.int32, device=dev)
-        elif nearest is False:
-            nearest = None
-        for t, size in ((recs, n_scans * LOC_DTYPE.itemsize), (ids, n_rows * 4), (nearest, n_rows * 4)):
-            if t is not None and (t.device != dev or not t.is_contiguous() or t.numel() * t.element_size() != size):
-                raise ValueError(f"outputs must be contiguous tensors of {n_scans} * 112 and {n_rows} * 4 bytes on {dev}")
-        cur = torch.cuda.current_stream(dev)
-        ext = torch.cuda.ExternalStream(self.ctx.stream_ptr(), device=dev)
-        ext.wait_stream(cur)
-        check(self.lib.fx_map_localize(self.ctx.handle, self.handle, C.c_void_p(kb.data_ptr()), int(scans), int(total),
-                                       C.c_void_p(prior_poses.data_ptr()), n_scans, n_rows, C.byref(opt), C.c_void_p(recs.data_ptr()),
-                                       C.c_void_p(ids.data_ptr() if n_rows else None), C.c_void_p(nearest.data_ptr() if nearest is not None and n_rows else None)))
-        cur.wait_stream(ext)
+        opt = _options(FxLocalizeOptions, LOC_DEFAULTS, "localize", opts)
+        error = f"outputs must be contiguous tensors of {n_scans} * 112 and {n_rows} * 4 bytes on {dev}"
+        recs, ids = (None, None) if out is None else out
+        recs = _out_tensor(recs, (n_scans, LOC_DTYPE.itemsize // 8), torch.float64, dev, error)
+        ids = _out_tensor(ids, (n_rows,), torch.int32, dev, error)
+        nearest = _out_tensor(nearest, (n_rows,), torch.int32, dev, error)
+        with _on_stream(self.ctx.stream_ptr(), dev):
+            check(self.lib.fx_map_localize(self.ctx.handle, self.handle, C.c_void_p(kb.data_ptr()), int(scans), int(total),
+                                           C.c_void_p(prior_poses.data_ptr()), n_scans, n_rows, C.byref(opt), C.c_void_p(recs.data_ptr()),
+                                           C.c_void_p(ids.data_ptr() if n_rows else None), _ptr(nearest if n_rows else None)))
         return recs, ids, nearest
 
     def relocalize(self, kp, n_scans, q_max_rows=None, out=None, **opts):
@@ -2217,25 +2248,16 @@ class Map:
         dev = torch.device("cuda", self.ctx.device)
         n_scans = int(n_scans)
         n_rows = int(total) if q_max_rows is None else int(q_max_rows)
-        bad = set(opts) - set(RELOC_DEFAULTS)
-        if bad:
-            raise TypeError(f"unknown relocalize options {sorted(bad)}")
-        o = dict(RELOC_DEFAULTS, **opts)
-        opt = FxRelocalizeOptions(float(o["inlier_dist"]), float(o["pair_tol"]), float(o["min_baseline"]), float(o["max_baseline"]),
-                                  int(o["max_seeds"]), int(o["min_inliers"]), int(o["min_margin"]), int(o["min_landmark_obs"]),
-                                  int(o["segment"]) & 0xffffffff, 0)
+        opt = _options(FxRelocalizeOptions, RELOC_DEFAULTS, "relocalize", opts)
         if out is None:
             out = (torch.empty((n_scans, RELOC_DTYPE.itemsize // 8), dtype=torch.float64, device=dev), torch.empty((n_rows,), dtype=torch.int32, device=dev))
         recs, ids = out
         for t, size in ((recs, n_scans * RELOC_DTYPE.itemsize), (ids, n_rows * 4)):
             if t.device != dev or not t.is_contiguous() or t.numel() * t.element_size() != size:
                 raise ValueError(f"outputs must be contiguous tensors of {n_scans} * 96 and {n_rows} * 4 bytes on {dev}")
-        cur = torch.cuda.current_stream(dev)
-        ext = torch.cuda.ExternalStream(self.ctx.stream_ptr(), device=dev)
-        ext.wait_stream(cur)
-        check(self.lib.fx_map_relocalize(self.ctx.handle, self.handle, C.c_void_p(kb.data_ptr()), int(scans), int(total), n_scans, n_rows,
-                                         C.byref(opt), C.c_void_p(recs.data_ptr()), C.c_void_p(ids.data_ptr() if n_rows else None)))
-        cur.wait_stream(ext)
+        with _on_stream(self.ctx.stream_ptr(), dev):
+            check(self.lib.fx_map_relocalize(self.ctx.handle, self.handle, C.c_void_p(kb.data_ptr()), int(scans), int(total), n_scans, n_rows,
+                                             C.byref(opt), C.c_void_p(recs.data_ptr()), C.c_void_p(ids.data_ptr() if n_rows else None)))
         return recs, ids
 
     def compact(self, min_obs=1, min_age_scans=64, remap=None, result=None):
@@ -2245,23 +2267,11 @@ class Map:
         Stream-correct like merge(); never waits for the stream."""
         import torch
         dev = torch.device("cuda", self.ctx.device)
-        outs = []
-        for t, n, name in ((remap, self.max_landmarks, "remap"), (result, 4, "result")):
-            if t is None:
-                t = torch.empty((n,), dtype=torch.int32, device=dev)
-            elif t is False:
-                t = None
-            elif t.dtype != torch.int32 or t.device != dev or tuple(t.shape) != (n,) or not t.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous torch.int32 tensor [{n}] on {dev}")
-            outs.append(t)
-        remap, result = outs
+        remap, result = (_out_tensor(t, (n,), torch.int32, dev, f"{name} must be a contiguous torch.int32 tensor [{n}] on {dev}", typed=True)
+                         for t, n, name in ((remap, self.max_landmarks, "remap"), (result, 4, "result")))
         opt = FxMapCompactOptions(int(min_obs), int(min_age_scans))
-        cur = torch.cuda.current_stream(dev)
-        ext = torch.cuda.ExternalStream(self.ctx.stream_ptr(), device=dev)
-        ext.wait_stream(cur)
-        check(self.lib.fx_map_compact(self.ctx.handle, self.handle, C.byref(opt), C.c_void_p(remap.data_ptr() if remap is not None else None),
-                                      C.c_void_p(result.data_ptr() if result is not None else None)))
-        cur.wait_stream(ext)
+        with _on_stream(self.ctx.stream_ptr(), dev):
+            check(self.lib.fx_map_compact(self.ctx.handle, self.handle, C.byref(opt), _ptr(remap), _ptr(result)))
         return remap, result
 
     def join_segments(self, src, dst, prior=None, prior_device=None, result=None, match=None, **opts):
@@ -2273,34 +2283,12 @@ class Map:
         like merge(); never waits for the stream."""
         import torch
         dev = torch.device("cuda", self.ctx.device)
-        bad = set(opts) - set(JOIN_DEFAULTS)
-        if bad:
-            raise TypeError(f"unknown join options {sorted(bad)}")
-        o = dict(JOIN_DEFAULTS, **opts)
-        opt = FxMapJoinOptions(float(o["search_dist"]), float(o["inlier_dist"]), float(o["min_baseline"]), int(o["hyp_corr"]),
-                               int(o["min_inliers"]), int(o["min_landmark_obs"]), int(o["mode"]) & 0xffffffff, 0)
-        if result is None:
-            result = torch.empty((JOIN_DTYPE.itemsize // 8,), dtype=torch.float64, device=dev)
-        elif result is False:
-            result = None
-        if match is None:
-            match = torch.empty((self.max_landmarks,), dtype=torch.int32, device=dev)
-        elif match is False:
-            match = None
-        for t, size in ((result, JOIN_DTYPE.itemsize), (match, self.max_landmarks * 4)):
-            if t is not None and (t.device != dev or not t.is_contiguous() or t.numel() * t.element_size() != size):
-                raise ValueError(f"outputs must be contiguous tensors of 120 and {self.max_landmarks} * 4 bytes on {dev}")
-        pose = FxPose(*(float(v) for v in tuple(prior)[:5]), 0, 0) if prior is not None else None
-        if hasattr(prior_device, "data_ptr"):
-            prior_device = prior_device.data_ptr()
-        cur = torch.cuda.current_stream(dev)
-        ext = torch.cuda.ExternalStream(self.ctx.stream_ptr(), device=dev)
-        ext.wait_stream(cur)
-        check(self.lib.fx_map_join_segments(self.ctx.handle, self.handle, int(src) & 0xffffffff, int(dst) & 0xffffffff,
-                                            C.byref(pose) if pose is not None else None, C.c_void_p(prior_device),
-                                            C.byref(opt), C.c_void_p(result.data_ptr() if result is not None else None),
-                                            C.c_void_p(match.data_ptr() if match is not None else None)))
-        cur.wait_stream(ext)
+        opt = _options(FxMapJoinOptions, JOIN_DEFAULTS, "join", opts)
+        result, match = self._result_and_match(JOIN_DTYPE, result, match)
+        pose, prior_device = self._prior(prior, prior_device)
+        with _on_stream(self.ctx.stream_ptr(), dev):
+            check(self.lib.fx_map_join_segments(self.ctx.handle, self.handle, int(src) & 0xffffffff, int(dst) & 0xffffffff,
+                                                pose, C.c_void_p(prior_device), C.byref(opt), _ptr(result), _ptr(match)))
         return result, match
 
     def close_loop(self, prior=None, prior_device=None, result=None, match=None, **opts):
@@ -2312,35 +2300,11 @@ class Map:
         merge(); never waits for the stream."""
         import torch
         dev = torch.device("cuda", self.ctx.device)
-        bad = set(opts) - set(LOOP_DEFAULTS)
-        if bad:
-            raise TypeError(f"unknown loop options {sorted(bad)}")
-        o = dict(LOOP_DEFAULTS, **opts)
-        u = lambda k: int(o[k]) & 0xffffffff
-        opt = FxMapLoopOptions(float(o["search_dist"]), float(o["inlier_dist"]), float(o["min_baseline"]), u("hyp_corr"), u("min_inliers"),
-                               u("min_landmark_obs"), u("segment"), u("min_loop_scans"), u("recent_scans"), u("mode"), u("loop_first_scan"),
-                               u("loop_last_scan"), float(o["pivot_x"]), float(o["pivot_y"]), 0)
-        if result is None:
-            result = torch.empty((LOOP_DTYPE.itemsize // 8,), dtype=torch.float64, device=dev)
-        elif result is False:
-            result = None
-        if match is None:
-            match = torch.empty((self.max_landmarks,), dtype=torch.int32, device=dev)
-        elif match is False:
-            match = None
-        for t, size in ((result, LOOP_DTYPE.itemsize), (match, self.max_landmarks * 4)):
-            if t is not None and (t.device != dev or not t.is_contiguous() or t.numel() * t.element_size() != size):
-                raise ValueError(f"outputs must be contiguous tensors of {LOOP_DTYPE.itemsize} and {self.max_landmarks} * 4 bytes on {dev}")
-        pose = FxPose(*(float(v) for v in tuple(prior)[:5]), 0, 0) if prior is not None else None
-        if hasattr(prior_device, "data_ptr"):
-            prior_device = prior_device.data_ptr()
-        cur = torch.cuda.current_stream(dev)
-        ext = torch.cuda.ExternalStream(self.ctx.stream_ptr(), device=dev)
-        ext.wait_stream(cur)
-        check(self.lib.fx_map_close_loop(self.ctx.handle, self.handle, C.byref(pose) if pose is not None else None, C.c_void_p(prior_device),
-                                         C.byref(opt), C.c_void_p(result.data_ptr() if result is not None else None),
-                                         C.c_void_p(match.data_ptr() if match is not None else None)))
-        cur.wait_stream(ext)
+        opt = _options(FxMapLoopOptions, LOOP_DEFAULTS, "loop", opts)
+        result, match = self._result_and_match(LOOP_DTYPE, result, match)
+        pose, prior_device = self._prior(prior, prior_device)
+        with _on_stream(self.ctx.stream_ptr(), dev):
+            check(self.lib.fx_map_close_loop(self.ctx.handle, self.handle, pose, C.c_void_p(prior_device), C.byref(opt), _ptr(result), _ptr(match)))
         return result, match
 
     def find_loop(self, result=None, match=None, **opts):
@@ -2351,29 +2315,10 @@ class Map:
         False passes NULL (None is returned in its place).  Stream-correct like merge(); never waits for the stream."""
         import torch
         dev = torch.device("cuda", self.ctx.device)
-        bad = set(opts) - set(FIND_DEFAULTS)
-        if bad:
-            raise TypeError(f"unknown find-loop options {sorted(bad)}")
-        o = dict(FIND_DEFAULTS, **opts)
-        u = lambda k: int(o[k]) & 0xffffffff
-        opt = FxMapFindLoopOptions(float(o["inlier_dist"]), float(o["pair_tol"]), float(o["min_baseline"]), float(o["max_baseline"]),
-                                   u("max_seeds"), u("min_inliers"), u("min_margin"), u("min_landmark_obs"), u("segment"), u("target_segment"),
-                                   u("min_loop_scans"), u("recent_scans"), 0)
-        if result is None:
-            result = torch.empty((FIND_DTYPE.itemsize // 8,), dtype=torch.float64, device=dev)
-        if match is None:
-            match = torch.empty((self.max_landmarks,), dtype=torch.int32, device=dev)
-        elif match is False:
-            match = None
-        for t, size in ((result, FIND_DTYPE.itemsize), (match, self.max_landmarks * 4)):
-            if t is not None and (t.device != dev or not t.is_contiguous() or t.numel() * t.element_size() != size):
-                raise ValueError(f"outputs must be contiguous tensors of {FIND_DTYPE.itemsize} and {self.max_landmarks} * 4 bytes on {dev}")
-        cur = torch.cuda.current_stream(dev)
-        ext = torch.cuda.ExternalStream(self.ctx.stream_ptr(), device=dev)
-        ext.wait_stream(cur)
-        check(self.lib.fx_map_find_loop(self.ctx.handle, self.handle, C.byref(opt), C.c_void_p(result.data_ptr()),
-                                        C.c_void_p(match.data_ptr() if match is not None else None)))
-        cur.wait_stream(ext)
+        opt = _options(FxMapFindLoopOptions, FIND_DEFAULTS, "find-loop", opts)
+        result, match = self._result_and_match(FIND_DTYPE, result, match)
+        with _on_stream(self.ctx.stream_ptr(), dev):
+            check(self.lib.fx_map_find_loop(self.ctx.handle, self.handle, C.byref(opt), C.c_void_p(result.data_ptr()), _ptr(match)))
         return result, match
 
     def loop_correct_poses(self, result, poses, first_global_scan, n_poses=None):
@@ -2386,12 +2331,9 @@ class Map:
         n = have if n_poses is None else int(n_poses)
         if poses.device != dev or result.device != dev or not poses.is_contiguous() or n > have or result.numel() * result.element_size() != LOOP_DTYPE.itemsize:
             raise ValueError(f"the result must hold {LOOP_DTYPE.itemsize} bytes and poses {n} contiguous fx_pose records on {dev}")
-        cur = torch.cuda.current_stream(dev)
-        ext = torch.cuda.ExternalStream(self.ctx.stream_ptr(), device=dev)
-        ext.wait_stream(cur)
-        check(self.lib.fx_map_loop_correct_poses(self.ctx.handle, C.c_void_p(result.data_ptr()), C.c_void_p(poses.data_ptr()),
-                                                 int(first_global_scan) & 0xffffffff, n))
-        cur.wait_stream(ext)
+        with _on_stream(self.ctx.stream_ptr(), dev):
+            check(self.lib.fx_map_loop_correct_poses(self.ctx.handle, C.c_void_p(result.data_ptr()), C.c_void_p(poses.data_ptr()),
+                                                     int(first_global_scan) & 0xffffffff, n))
         return poses
 
     def export_state(self):
@@ -2554,19 +2496,17 @@ class Context:
         grow = buf is None and capacity is None
         capacity = max_rows * 128 if capacity is None else int(capacity)
         dev = torch.device("cuda", self.device)
-        cur = torch.cuda.current_stream(dev)
-        ext = torch.cuda.ExternalStream(self.stream_ptr(), device=dev)
         while True:
             nbytes = int(self.lib.fx_descriptor_csr_bytes(max_rows, capacity))
             if buf is None:
                 buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             elif buf.dtype != torch.uint8 or buf.device != dev or buf.numel() < nbytes or not buf.is_contiguous() or buf.data_ptr() % 16:
                 raise ValueError(f"buf must be a contiguous, 16-byte aligned torch.uint8 tensor of >= {nbytes} bytes on {dev}")
-            ext.wait_stream(cur)  # (the buffer's allocation / the caller's last use of it)
-            self.pack_descriptors_csr(buf.data_ptr(), max_rows, capacity)
-            # (the caller's stream waits for the pack, so the buffer's later reuse on it comes after; no record_stream: the
-            #  allocator would record events on the context's stream when the tensor dies, after fx_destroy perhaps)
-            cur.wait_stream(ext)
+            # (the pack comes after the buffer's allocation / the caller's last use of it, and the caller's stream waits for the pack,
+            #  so the buffer's later reuse on it comes after; no record_stream: the allocator would record events on the context's
+            #  stream when the tensor dies, after fx_destroy perhaps)
+            with _on_stream(self.stream_ptr(), dev):
+                self.pack_descriptors_csr(buf.data_ptr(), max_rows, capacity)
             h = buf[:16].view(torch.int32).cpu().tolist()
             if not (grow and h[3] < min(h[0], max_rows)):
                 break
@@ -2602,12 +2542,9 @@ class Context:
         opt = FxMatchOptions()
         self.lib.fx_match_options_default(C.byref(opt))
         opt.azimuth_shifts, opt.max_dist2, opt.max_ratio, opt.mutual = int(shifts), float(max_dist2), float(max_ratio), int(bool(mutual))
-        cur = torch.cuda.current_stream(dev)
-        ext = torch.cuda.ExternalStream(self.stream_ptr(), device=dev)
-        ext.wait_stream(cur)
-        check(self.lib.fx_match_descriptors_csr(self.handle, C.c_void_p(qb.data_ptr()), int(q_rows), int(q_cap), C.c_void_p(tb.data_ptr()),
-                                                int(t_rows), int(t_cap), arr, len(pairs), C.byref(opt), C.c_void_p(out.data_ptr())))
-        cur.wait_stream(ext)
+        with _on_stream(self.stream_ptr(), dev):
+            check(self.lib.fx_match_descriptors_csr(self.handle, C.c_void_p(qb.data_ptr()), int(q_rows), int(q_cap), C.c_void_p(tb.data_ptr()),
+                                                    int(t_rows), int(t_cap), arr, len(pairs), C.byref(opt), C.c_void_p(out.data_ptr())))
         return out
 
     def register_matches(self, q_kp, t_kp, matches, pairs, out=None, inliers=None, **opts):
@@ -2632,12 +2569,7 @@ class Context:
             out = torch.empty((n_pairs, 8), dtype=torch.float64, device=dev)
         elif out.dtype != torch.float64 or out.device != dev or tuple(out.shape) != (n_pairs, 8) or not out.is_contiguous():
             raise ValueError(f"out must be a contiguous torch.float64 tensor [{n_pairs}, 8] on {dev}")
-        if inliers is None:
-            inliers = torch.empty((n_rows,), dtype=torch.int32, device=dev)
-        elif inliers is False:
-            inliers = None
-        elif inliers.dtype != torch.int32 or inliers.device != dev or tuple(inliers.shape) != (n_rows,) or not inliers.is_contiguous():
-            raise ValueError(f"inliers must be a contiguous torch.int32 tensor [{n_rows}] on {dev}")
+        inliers = _out_tensor(inliers, (n_rows,), torch.int32, dev, f"inliers must be a contiguous torch.int32 tensor [{n_rows}] on {dev}", typed=True)
         arr = (FxMatchPair * max(n_pairs, 1))()
         for i, pr in enumerate(pairs):
             arr[i].q_row0, arr[i].q_rows, arr[i].t_row0, arr[i].t_rows = (int(x) for x in pr)
@@ -2647,13 +2579,10 @@ class Context:
             if k not in REG_DEFAULTS:
                 raise TypeError(f"unknown option {k!r}")
             setattr(opt, k, float(v) if k in ("inlier_dist", "min_baseline") else int(v))
-        cur = torch.cuda.current_stream(dev)
-        ext = torch.cuda.ExternalStream(self.stream_ptr(), device=dev)
-        ext.wait_stream(cur)
-        check(self.lib.fx_register_matches(self.handle, C.c_void_p(qb.data_ptr()), int(q_scans), int(q_total), C.c_void_p(tb.data_ptr()),
-                                           int(t_scans), int(t_total), C.c_void_p(matches.data_ptr()), n_rows, arr, n_pairs, C.byref(opt),
-                                           C.c_void_p(out.data_ptr()), C.c_void_p(inliers.data_ptr() if inliers is not None else None)))
-        cur.wait_stream(ext)
+        with _on_stream(self.stream_ptr(), dev):
+            check(self.lib.fx_register_matches(self.handle, C.c_void_p(qb.data_ptr()), int(q_scans), int(q_total), C.c_void_p(tb.data_ptr()),
+                                               int(t_scans), int(t_total), C.c_void_p(matches.data_ptr()), n_rows, arr, n_pairs, C.byref(opt),
+                                               C.c_void_p(out.data_ptr()), _ptr(inliers)))
         return out, inliers
 
     def track_landmarks(self, kp, matches, inliers, reg, n_scans, init_pose=None, min_obs=2, max_landmarks=None, out=None):
@@ -2691,15 +2620,12 @@ class Context:
         opt = FxTrackOptions()
         self.lib.fx_track_options_default(C.byref(opt))
         opt.min_obs = int(min_obs)
-        cur = torch.cuda.current_stream(dev)
-        ext = torch.cuda.ExternalStream(self.stream_ptr(), device=dev)
-        ext.wait_stream(cur)
-        check(self.lib.fx_track_landmarks(self.handle, C.c_void_p(kb.data_ptr()), int(scans), int(total), C.c_void_p(matches.data_ptr()),
-                                          C.c_void_p(inliers.data_ptr()), n_rows, C.c_void_p(reg.data_ptr()), n_scans,
-                                          C.byref(ip) if ip is not None else None, C.byref(opt), C.c_void_p(poses.data_ptr()),
-                                          C.c_void_p(lor.data_ptr()), C.c_void_p(obs.data_ptr()), C.c_void_p(lms.data_ptr()), max_landmarks,
-                                          C.c_void_p(hdr.data_ptr())))
-        cur.wait_stream(ext)
+        with _on_stream(self.stream_ptr(), dev):
+            check(self.lib.fx_track_landmarks(self.handle, C.c_void_p(kb.data_ptr()), int(scans), int(total), C.c_void_p(matches.data_ptr()),
+                                              C.c_void_p(inliers.data_ptr()), n_rows, C.c_void_p(reg.data_ptr()), n_scans,
+                                              C.byref(ip) if ip is not None else None, C.byref(opt), C.c_void_p(poses.data_ptr()),
+                                              C.c_void_p(lor.data_ptr()), C.c_void_p(obs.data_ptr()), C.c_void_p(lms.data_ptr()), max_landmarks,
+                                              C.c_void_p(hdr.data_ptr())))
         return out
 
     def map_create(self, max_landmarks, max_carry_rows):

@@ -674,6 +674,89 @@ fx_status launch_graph(fx_ctx *c, hipStream_t s, uint32_t batch, bool front) {
   FX_HIP(hipGraphLaunch(exec, s));
   return FX_OK;
 }
+
+// What the calls on a map share (fx_map_reset ... fx_map_import_host).
+// the prologue: the handles, and whatever else the call cannot do without, are there, and the map is this
+// context's
+fx_status map_call_check(const fx_ctx *c, const fx_map *m, bool others_given = true) {
+  if (!c || !m || !others_given) return fail(FX_ERR_INVALID_ARG, "null argument");
+  if (m->ctx != c) return fail(FX_ERR_INVALID_ARG, "the map belongs to another context");
+  return FX_OK;
+}
+// What the map calls that run on the context's scratch share (fx_map_merge ... fx_map_find_loop).
+// a grid over the map m with the gate `dist`: the map's own memory, the gate in fp64 and the grid's cell edge, dist (1 + 2^-8),
+// exact (csrc/fx_map_grid.h proves the margin), and the table
+void map_grid_view(FxMapMergeArgs *G, const fx_map *m, double dist) {
+  G->header = m->a.header, G->records = m->a.records, G->acc = m->a.acc, G->carry = m->a.carry, G->alias = m->a.alias;
+  G->cap = m->a.cap, G->max_carry = m->a.max_carry;
+  G->md2 = dist * dist, G->inv_edge = 1.0 / (dist * (1.0 + 1.0 / 256.0));
+  G->table = fxk_map_merge_table(G->cap);
+}
+// the options of the consensus over a nearest search: fx_map_localize, fx_map_join_segments, fx_map_close_loop
+template <typename Options>
+fx_status consensus_options_check(const Options &o) {
+  if (!(std::isfinite(o.search_dist) && o.search_dist > 0.f)) return fail(FX_ERR_INVALID_ARG, "search_dist must be finite and positive");
+  if (!(o.inlier_dist > 0.f) || !std::isfinite(o.inlier_dist) || !(o.min_baseline > 0.f) || !std::isfinite(o.min_baseline))
+    return fail(FX_ERR_INVALID_ARG, "inlier_dist and min_baseline must be finite and positive");
+  if (o.hyp_corr < 2u || o.hyp_corr > 128u) return fail(FX_ERR_INVALID_ARG, "hyp_corr must be 2..128");
+  if (o.min_inliers < 2u) return fail(FX_ERR_INVALID_ARG, "min_inliers must be at least 2");
+  if (!o.min_landmark_obs) return fail(FX_ERR_INVALID_ARG, "min_landmark_obs must be at least 1");
+  return FX_OK;
+}
+// the options of the constellation search: fx_map_relocalize, fx_map_find_loop
+template <typename Options>
+fx_status constellation_options_check(const Options &o) {
+  auto positive = [](float v) { return std::isfinite(v) && v > 0.f; };
+  if (!positive(o.inlier_dist)) return fail(FX_ERR_INVALID_ARG, "inlier_dist must be finite and positive");
+  if (!positive(o.pair_tol)) return fail(FX_ERR_INVALID_ARG, "pair_tol must be finite and positive");
+  if (!positive(o.min_baseline)) return fail(FX_ERR_INVALID_ARG, "min_baseline must be finite and positive");
+  if (!(std::isfinite(o.max_baseline) && o.max_baseline >= o.min_baseline))
+    return fail(FX_ERR_INVALID_ARG, "max_baseline must be finite and at least min_baseline");
+  if (o.max_seeds < 1u || o.max_seeds > FX_RELOC_MAX_KP) return fail(FX_ERR_INVALID_ARG, "max_seeds must be 1..64");
+  if (o.min_inliers < 3u) return fail(FX_ERR_INVALID_ARG, "min_inliers must be at least 3");
+  if (!o.min_margin) return fail(FX_ERR_INVALID_ARG, "min_margin must be at least 1");
+  if (!o.min_landmark_obs) return fail(FX_ERR_INVALID_ARG, "min_landmark_obs must be at least 1");
+  return FX_OK;
+}
+static_assert(FX_FIND_MAX_QUERY == FX_RELOC_MAX_KP, "max_seeds' bound is one for both constellation searches");
+// the two grids of a constellation search, P for the pairs and Q for the score, and what both calls take from the options: the
+// gates in fp64 (csrc/fx_map_constellation.h derives the pair grid's gate (xb + pt)(1 + 2^-20) from the hypothesis's length gate)
+template <typename Args, typename Options>
+void constellation_args(Args *A, const fx_map *m, const Options &o) {
+  map_grid_view(&A->P, m, ((double)o.max_baseline + (double)o.pair_tol) * (1.0 + 1.0 / 1048576.0));
+  map_grid_view(&A->Q, m, (double)o.inlier_dist);
+  A->inlier_dist = o.inlier_dist, A->pair_tol = o.pair_tol, A->min_baseline = o.min_baseline, A->max_baseline = o.max_baseline;
+  A->max_seeds = o.max_seeds, A->min_inliers = o.min_inliers, A->min_margin = o.min_margin, A->min_landmark_obs = o.min_landmark_obs;
+  A->chunks = (A->P.cap + FXR_CHUNK - 1u) / FXR_CHUNK;
+}
+// the prior of the join and the loop: on the host or on the device, not both, and finite where the host can see it
+fx_status prior_check(const fx_pose *prior_host, const double *prior_device) {
+  if (prior_host && prior_device) return fail(FX_ERR_INVALID_ARG, "give the prior on the host or on the device, not both");
+  if (prior_host && !(std::isfinite(prior_host->c) && std::isfinite(prior_host->s) && std::isfinite(prior_host->tx) &&
+                      std::isfinite(prior_host->ty) && std::isfinite(prior_host->tz)))
+    return fail(FX_ERR_INVALID_ARG, "prior_host must be finite");
+  return FX_OK;
+}
+// the association's part of the join's and the loop's arguments (fx_device.h FxMapAssocArgs); no prior is the identity
+template <typename Options>
+void assoc_args(FxMapAssocArgs *S, const fx_map *m, const Options &o, const fx_pose *prior_host, const double *prior_device, int32_t *match) {
+  map_grid_view(&S->G, m, (double)o.search_dist);
+  S->mode = o.mode;
+  S->prior[0] = 1.0;
+  if (prior_host)
+    S->prior[0] = prior_host->c, S->prior[1] = prior_host->s, S->prior[2] = prior_host->tx, S->prior[3] = prior_host->ty, S->prior[4] = prior_host->tz;
+  S->prior_device = prior_device;
+  S->inlier_dist = o.inlier_dist, S->min_baseline = o.min_baseline;
+  S->hyp_corr = o.hyp_corr, S->min_inliers = o.min_inliers, S->min_landmark_obs = o.min_landmark_obs;
+  S->match = match;
+}
+// the tail of a call: room in the context's scratch for what `launch` needs of it, A's pointers carved out of it, the launches
+#define FX_MAP_RUN(launch, what)                                                      \
+  do {                                                                                \
+    FX_TRY(c->merge_scratch.reserve(c, launch##_scratch(&A, nullptr), what));         \
+    (void)launch##_scratch(&A, c->merge_scratch.d);                                   \
+    FX_HIP(launch(c->stream, A));                                                     \
+  } while (0)
 }  // namespace
 
 extern "C" {
@@ -1851,8 +1934,7 @@ void fx_map_destroy(fx_map *m) {
 }
 
 fx_status fx_map_reset(fx_ctx *c, fx_map *m) {
-  if (!c || !m) return fail(FX_ERR_INVALID_ARG, "null argument");
-  if (m->ctx != c) return fail(FX_ERR_INVALID_ARG, "the map belongs to another context");
+  FX_TRY(map_call_check(c, m));
   FX_HIP(hipSetDevice(c->device));
   FX_HIP(fxk_map_reset(c->stream, m->a));
   return FX_OK;
@@ -1861,9 +1943,8 @@ fx_status fx_map_reset(fx_ctx *c, fx_map *m) {
 fx_status fx_map_update(fx_ctx *c, fx_map *m, const void *kp, uint32_t max_scans, uint32_t max_total, const fx_pose *poses,
                         const int32_t *landmark_of_row, const uint32_t *obs_row, uint32_t q_max_rows, const fx_landmark *landmarks,
                         uint32_t max_landmarks, const fx_track_header *track_header, uint32_t flags, int32_t *map_id_of_row) {
-  if (!c || !m || !kp || !poses || !track_header || (q_max_rows && (!landmark_of_row || !obs_row)) || (max_landmarks && !landmarks))
-    return fail(FX_ERR_INVALID_ARG, "null argument");
-  if (m->ctx != c) return fail(FX_ERR_INVALID_ARG, "the map belongs to another context");
+  const bool tables = !(q_max_rows && (!landmark_of_row || !obs_row)) && !(max_landmarks && !landmarks);
+  FX_TRY(map_call_check(c, m, kp && poses && track_header && tables));
   if (flags & ~FX_MAP_OVERLAP) return fail(FX_ERR_INVALID_ARG, "unknown flags (only FX_MAP_OVERLAP is defined)");
   if (((uintptr_t)kp % 16) != 0 || ((uintptr_t)poses % 8) != 0 || ((uintptr_t)landmark_of_row % 4) != 0 || ((uintptr_t)obs_row % 4) != 0 ||
       ((uintptr_t)landmarks % 8) != 0 || ((uintptr_t)track_header % 4) != 0 || ((uintptr_t)map_id_of_row % 4) != 0)
@@ -1889,8 +1970,7 @@ fx_status fx_map_get(fx_map *m, const fx_map_header **header, const fx_map_landm
 }
 
 fx_status fx_map_read_header(fx_ctx *c, fx_map *m, fx_map_header *out) {
-  if (!c || !m || !out) return fail(FX_ERR_INVALID_ARG, "null argument");
-  if (m->ctx != c) return fail(FX_ERR_INVALID_ARG, "the map belongs to another context");
+  FX_TRY(map_call_check(c, m, out != nullptr));
   FX_HIP(hipSetDevice(c->device));
   FX_HIP(hipMemcpyAsync(out, m->a.header, sizeof(fx_map_header), hipMemcpyDeviceToHost, c->stream));
   FX_HIP(hipStreamSynchronize(c->stream));
@@ -1898,8 +1978,7 @@ fx_status fx_map_read_header(fx_ctx *c, fx_map *m, fx_map_header *out) {
 }
 
 fx_status fx_map_read_landmarks(fx_ctx *c, fx_map *m, uint32_t first, uint32_t count, fx_map_landmark *out) {
-  if (!c || !m || (count && !out)) return fail(FX_ERR_INVALID_ARG, "null argument");
-  if (m->ctx != c) return fail(FX_ERR_INVALID_ARG, "the map belongs to another context");
+  FX_TRY(map_call_check(c, m, !count || out));
   if (first > m->a.cap || count > m->a.cap - first) return fail(FX_ERR_INVALID_ARG, "records outside the map's max_landmarks");
   FX_HIP(hipSetDevice(c->device));
   if (count)
@@ -1916,8 +1995,7 @@ void fx_map_merge_options_default(fx_map_merge_options *o) {
 }
 
 fx_status fx_map_merge(fx_ctx *c, fx_map *m, const fx_map_merge_options *opt, fx_map_merge_result *result) {
-  if (!c || !m) return fail(FX_ERR_INVALID_ARG, "null argument");
-  if (m->ctx != c) return fail(FX_ERR_INVALID_ARG, "the map belongs to another context");
+  FX_TRY(map_call_check(c, m));
   fx_map_merge_options o;
   fx_map_merge_options_default(&o);
   if (opt) o = *opt;
@@ -1926,16 +2004,10 @@ fx_status fx_map_merge(fx_ctx *c, fx_map *m, const fx_map_merge_options *opt, fx
   if (((uintptr_t)result % 4) != 0) return fail(FX_ERR_INVALID_ARG, "the result must be 4-byte aligned");
   FX_HIP(hipSetDevice(c->device));
   FxMapMergeArgs A{};
-  A.header = m->a.header, A.records = m->a.records, A.acc = m->a.acc, A.carry = m->a.carry, A.alias = m->a.alias;
-  A.cap = m->a.cap, A.max_carry = m->a.max_carry;
-  // the gate in fp64 and the grid's cell edge: md (1 + 2^-8), exact (csrc/fx_map_grid.h proves the margin)
-  const double md = (double)o.merge_dist;
-  A.md2 = md * md, A.inv_edge = 1.0 / (md * (1.0 + 1.0 / 256.0));
-  A.max_gap = o.max_gap_scans, A.table = fxk_map_merge_table(A.cap);
+  map_grid_view(&A, m, (double)o.merge_dist);
+  A.max_gap = o.max_gap_scans;
   A.result = (uint32_t *)result;
-  FX_TRY(c->merge_scratch.reserve(c, fxk_map_merge_scratch(&A, nullptr), "map merge scratch"));
-  (void)fxk_map_merge_scratch(&A, c->merge_scratch.d);
-  FX_HIP(fxk_map_merge(c->stream, A));
+  FX_MAP_RUN(fxk_map_merge, "map merge scratch");
   return FX_OK;
 }
 
@@ -1954,8 +2026,7 @@ void fx_localize_options_default(fx_localize_options *o) {
 fx_status fx_map_localize(fx_ctx *c, fx_map *m, const void *kp, uint32_t max_scans, uint32_t max_total, const fx_pose *priors, uint32_t n_scans,
                           uint32_t q_max_rows, const fx_localize_options *opt, fx_localization *out, int32_t *map_id_of_row,
                           int32_t *nearest_of_row) {
-  if (!c || !m) return fail(FX_ERR_INVALID_ARG, "null argument");
-  if (m->ctx != c) return fail(FX_ERR_INVALID_ARG, "the map belongs to another context");
+  FX_TRY(map_call_check(c, m));
   if (!n_scans || n_scans > max_scans)
     return fail(FX_ERR_INVALID_ARG, "n_scans must be 1..max_scans (" + std::to_string(n_scans) + " of " + std::to_string(max_scans) + ")");
   if (!kp || !priors || !out || (q_max_rows && !map_id_of_row)) return fail(FX_ERR_INVALID_ARG, "null argument");
@@ -1965,29 +2036,17 @@ fx_status fx_map_localize(fx_ctx *c, fx_map *m, const void *kp, uint32_t max_sca
   fx_localize_options o;
   fx_localize_options_default(&o);
   if (opt) o = *opt;
-  if (!(std::isfinite(o.search_dist) && o.search_dist > 0.f)) return fail(FX_ERR_INVALID_ARG, "search_dist must be finite and positive");
-  if (!(o.inlier_dist > 0.f) || !std::isfinite(o.inlier_dist) || !(o.min_baseline > 0.f) || !std::isfinite(o.min_baseline))
-    return fail(FX_ERR_INVALID_ARG, "inlier_dist and min_baseline must be finite and positive");
-  if (o.hyp_corr < 2u || o.hyp_corr > 128u) return fail(FX_ERR_INVALID_ARG, "hyp_corr must be 2..128");
-  if (o.min_inliers < 2u) return fail(FX_ERR_INVALID_ARG, "min_inliers must be at least 2");
-  if (!o.min_landmark_obs) return fail(FX_ERR_INVALID_ARG, "min_landmark_obs must be at least 1");
+  FX_TRY(consensus_options_check(o));
   if (o.reserved) return fail(FX_ERR_INVALID_ARG, "reserved must be 0");
   FX_HIP(hipSetDevice(c->device));
   FxMapLocalizeArgs A{};
-  A.G.header = m->a.header, A.G.records = m->a.records, A.G.acc = m->a.acc, A.G.carry = m->a.carry, A.G.alias = m->a.alias;
-  A.G.cap = m->a.cap, A.G.max_carry = m->a.max_carry;
-  // the gate in fp64 and the grid's cell edge: sd (1 + 2^-8), exact (csrc/fx_map_grid.h proves the margin)
-  const double sd = (double)o.search_dist;
-  A.G.md2 = sd * sd, A.G.inv_edge = 1.0 / (sd * (1.0 + 1.0 / 256.0));
-  A.G.table = fxk_map_merge_table(A.G.cap);
+  map_grid_view(&A.G, m, (double)o.search_dist);
   A.kp = (const uint32_t *)kp, A.max_scans = max_scans, A.max_total = max_total;
   A.priors = priors, A.n_scans = n_scans, A.q_max_rows = q_max_rows;
   A.inlier_dist = o.inlier_dist, A.min_baseline = o.min_baseline;
   A.hyp_corr = o.hyp_corr, A.min_inliers = o.min_inliers, A.min_landmark_obs = o.min_landmark_obs, A.segment = o.segment;
   A.out = out, A.map_id_of_row = map_id_of_row, A.nearest_of_row = nearest_of_row;
-  FX_TRY(c->merge_scratch.reserve(c, fxk_map_localize_scratch(&A, nullptr), "map localize scratch"));
-  (void)fxk_map_localize_scratch(&A, c->merge_scratch.d);
-  FX_HIP(fxk_map_localize(c->stream, A));
+  FX_MAP_RUN(fxk_map_localize, "map localize scratch");
   return FX_OK;
 }
 
@@ -2007,8 +2066,7 @@ void fx_relocalize_options_default(fx_relocalize_options *o) {
 
 fx_status fx_map_relocalize(fx_ctx *c, fx_map *m, const void *kp, uint32_t max_scans, uint32_t max_total, uint32_t n_scans, uint32_t q_max_rows,
                             const fx_relocalize_options *opt, fx_relocalization *out, int32_t *map_id_of_row) {
-  if (!c || !m) return fail(FX_ERR_INVALID_ARG, "null argument");
-  if (m->ctx != c) return fail(FX_ERR_INVALID_ARG, "the map belongs to another context");
+  FX_TRY(map_call_check(c, m));
   if (!n_scans || n_scans > max_scans)
     return fail(FX_ERR_INVALID_ARG, "n_scans must be 1..max_scans (" + std::to_string(n_scans) + " of " + std::to_string(max_scans) + ")");
   if (!kp || !out || (q_max_rows && !map_id_of_row)) return fail(FX_ERR_INVALID_ARG, "null argument");
@@ -2017,39 +2075,16 @@ fx_status fx_map_relocalize(fx_ctx *c, fx_map *m, const void *kp, uint32_t max_s
   fx_relocalize_options o;
   fx_relocalize_options_default(&o);
   if (opt) o = *opt;
-  auto positive = [](float v) { return std::isfinite(v) && v > 0.f; };
-  if (!positive(o.inlier_dist)) return fail(FX_ERR_INVALID_ARG, "inlier_dist must be finite and positive");
-  if (!positive(o.pair_tol)) return fail(FX_ERR_INVALID_ARG, "pair_tol must be finite and positive");
-  if (!positive(o.min_baseline)) return fail(FX_ERR_INVALID_ARG, "min_baseline must be finite and positive");
-  if (!(std::isfinite(o.max_baseline) && o.max_baseline >= o.min_baseline))
-    return fail(FX_ERR_INVALID_ARG, "max_baseline must be finite and at least min_baseline");
-  if (o.max_seeds < 1u || o.max_seeds > FX_RELOC_MAX_KP) return fail(FX_ERR_INVALID_ARG, "max_seeds must be 1..64");
-  if (o.min_inliers < 3u) return fail(FX_ERR_INVALID_ARG, "min_inliers must be at least 3");
-  if (!o.min_margin) return fail(FX_ERR_INVALID_ARG, "min_margin must be at least 1");
-  if (!o.min_landmark_obs) return fail(FX_ERR_INVALID_ARG, "min_landmark_obs must be at least 1");
+  FX_TRY(constellation_options_check(o));
   if (o.reserved) return fail(FX_ERR_INVALID_ARG, "reserved must be 0");
   FX_HIP(hipSetDevice(c->device));
   FxMapRelocalizeArgs A{};
-  for (FxMapMergeArgs *G : {&A.P, &A.Q}) {
-    G->header = m->a.header, G->records = m->a.records, G->acc = m->a.acc, G->carry = m->a.carry, G->alias = m->a.alias;
-    G->cap = m->a.cap, G->max_carry = m->a.max_carry;
-    G->table = fxk_map_merge_table(G->cap);
-  }
-  // the two gates in fp64 and the grids' cell edges, gate (1 + 2^-8) (csrc/fx_map_grid.h proves the margin; csrc/fx_map_constellation.h
-  // derives the pair grid's gate (xb + pt)(1 + 2^-20) from the hypothesis's length gate)
-  const double pd = ((double)o.max_baseline + (double)o.pair_tol) * (1.0 + 1.0 / 1048576.0), id = (double)o.inlier_dist;
-  A.P.md2 = pd * pd, A.P.inv_edge = 1.0 / (pd * (1.0 + 1.0 / 256.0));
-  A.Q.md2 = id * id, A.Q.inv_edge = 1.0 / (id * (1.0 + 1.0 / 256.0));
+  constellation_args(&A, m, o);
   A.kp = (const uint32_t *)kp, A.max_scans = max_scans, A.max_total = max_total;
   A.n_scans = n_scans, A.q_max_rows = q_max_rows;
-  A.inlier_dist = o.inlier_dist, A.pair_tol = o.pair_tol, A.min_baseline = o.min_baseline, A.max_baseline = o.max_baseline;
-  A.max_seeds = o.max_seeds, A.min_inliers = o.min_inliers, A.min_margin = o.min_margin, A.min_landmark_obs = o.min_landmark_obs;
   A.segment = o.segment;
-  A.chunks = (A.P.cap + FXR_CHUNK - 1u) / FXR_CHUNK;
   A.out = out, A.map_id_of_row = map_id_of_row;
-  FX_TRY(c->merge_scratch.reserve(c, fxk_map_relocalize_scratch(&A, nullptr), "map relocalize scratch"));
-  (void)fxk_map_relocalize_scratch(&A, c->merge_scratch.d);
-  FX_HIP(fxk_map_relocalize(c->stream, A));
+  FX_MAP_RUN(fxk_map_relocalize, "map relocalize scratch");
   return FX_OK;
 }
 
@@ -2060,8 +2095,7 @@ fx_status fx_map_get_alias(fx_map *m, const int32_t **alias) {
 }
 
 fx_status fx_map_read_alias(fx_ctx *c, fx_map *m, uint32_t first, uint32_t count, int32_t *out) {
-  if (!c || !m || (count && !out)) return fail(FX_ERR_INVALID_ARG, "null argument");
-  if (m->ctx != c) return fail(FX_ERR_INVALID_ARG, "the map belongs to another context");
+  FX_TRY(map_call_check(c, m, !count || out));
   if (first > m->a.cap || count > m->a.cap - first) return fail(FX_ERR_INVALID_ARG, "entries outside the map's max_landmarks");
   FX_HIP(hipSetDevice(c->device));
   if (count) FX_HIP(hipMemcpyAsync(out, m->a.alias + first, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
@@ -2076,8 +2110,7 @@ void fx_map_compact_options_default(fx_map_compact_options *o) {
 }
 
 fx_status fx_map_compact(fx_ctx *c, fx_map *m, const fx_map_compact_options *opt, int32_t *remap, fx_map_compact_result *result) {
-  if (!c || !m) return fail(FX_ERR_INVALID_ARG, "null argument");
-  if (m->ctx != c) return fail(FX_ERR_INVALID_ARG, "the map belongs to another context");
+  FX_TRY(map_call_check(c, m));
   fx_map_compact_options o;
   fx_map_compact_options_default(&o);
   if (opt) o = *opt;
@@ -2089,9 +2122,7 @@ fx_status fx_map_compact(fx_ctx *c, fx_map *m, const fx_map_compact_options *opt
   A.cap = m->a.cap, A.max_carry = m->a.max_carry;
   A.min_obs = o.min_obs, A.min_age = o.min_age_scans;
   A.remap = remap, A.result = (uint32_t *)result;
-  FX_TRY(c->merge_scratch.reserve(c, fxk_map_compact_scratch(&A, nullptr), "map compact scratch"));
-  (void)fxk_map_compact_scratch(&A, c->merge_scratch.d);
-  FX_HIP(fxk_map_compact(c->stream, A));
+  FX_MAP_RUN(fxk_map_compact, "map compact scratch");
   return FX_OK;
 }
 
@@ -2109,45 +2140,23 @@ void fx_map_join_options_default(fx_map_join_options *o) {
 
 fx_status fx_map_join_segments(fx_ctx *c, fx_map *m, uint32_t src, uint32_t dst, const fx_pose *prior_host, const double *prior_device,
                                const fx_map_join_options *opt, fx_map_join_result *result, int32_t *match_of_landmark) {
-  if (!c || !m) return fail(FX_ERR_INVALID_ARG, "null argument");
-  if (m->ctx != c) return fail(FX_ERR_INVALID_ARG, "the map belongs to another context");
+  FX_TRY(map_call_check(c, m));
   if (src == dst) return fail(FX_ERR_INVALID_ARG, "src_segment and dst_segment must differ (" + std::to_string(src) + ")");
-  if (prior_host && prior_device) return fail(FX_ERR_INVALID_ARG, "give the prior on the host or on the device, not both");
-  if (prior_host && !(std::isfinite(prior_host->c) && std::isfinite(prior_host->s) && std::isfinite(prior_host->tx) &&
-                      std::isfinite(prior_host->ty) && std::isfinite(prior_host->tz)))
-    return fail(FX_ERR_INVALID_ARG, "prior_host must be finite");
+  FX_TRY(prior_check(prior_host, prior_device));
   fx_map_join_options o;
   fx_map_join_options_default(&o);
   if (opt) o = *opt;
-  if (!(std::isfinite(o.search_dist) && o.search_dist > 0.f)) return fail(FX_ERR_INVALID_ARG, "search_dist must be finite and positive");
-  if (!(o.inlier_dist > 0.f) || !std::isfinite(o.inlier_dist) || !(o.min_baseline > 0.f) || !std::isfinite(o.min_baseline))
-    return fail(FX_ERR_INVALID_ARG, "inlier_dist and min_baseline must be finite and positive");
-  if (o.hyp_corr < 2u || o.hyp_corr > 128u) return fail(FX_ERR_INVALID_ARG, "hyp_corr must be 2..128");
-  if (o.min_inliers < 2u) return fail(FX_ERR_INVALID_ARG, "min_inliers must be at least 2");
-  if (!o.min_landmark_obs) return fail(FX_ERR_INVALID_ARG, "min_landmark_obs must be at least 1");
+  FX_TRY(consensus_options_check(o));
   if (o.mode > FX_JOIN_DRY_RUN) return fail(FX_ERR_INVALID_ARG, "mode must be FX_JOIN_FIT, FX_JOIN_GIVEN or FX_JOIN_DRY_RUN");
   if (o.reserved) return fail(FX_ERR_INVALID_ARG, "reserved must be 0");
   if (((uintptr_t)prior_device % 8) != 0 || ((uintptr_t)result % 8) != 0 || ((uintptr_t)match_of_landmark % 4) != 0)
     return fail(FX_ERR_INVALID_ARG, "prior_device and the result must be 8-byte, match_of_landmark 4-byte aligned");
   FX_HIP(hipSetDevice(c->device));
   FxMapJoinArgs A{};
-  A.G.header = m->a.header, A.G.records = m->a.records, A.G.acc = m->a.acc, A.G.carry = m->a.carry, A.G.alias = m->a.alias;
-  A.G.cap = m->a.cap, A.G.max_carry = m->a.max_carry;
-  // the gate in fp64 and the grid's cell edge: sd (1 + 2^-8), exact (csrc/fx_map_grid.h proves the margin): the localise's
-  const double sd = (double)o.search_dist;
-  A.G.md2 = sd * sd, A.G.inv_edge = 1.0 / (sd * (1.0 + 1.0 / 256.0));
-  A.G.table = fxk_map_merge_table(A.G.cap);
-  A.src = src, A.dst = dst, A.mode = o.mode;
-  A.prior[0] = 1.0;
-  if (prior_host)
-    A.prior[0] = prior_host->c, A.prior[1] = prior_host->s, A.prior[2] = prior_host->tx, A.prior[3] = prior_host->ty, A.prior[4] = prior_host->tz;
-  A.prior_device = prior_device;
-  A.inlier_dist = o.inlier_dist, A.min_baseline = o.min_baseline;
-  A.hyp_corr = o.hyp_corr, A.min_inliers = o.min_inliers, A.min_landmark_obs = o.min_landmark_obs;
-  A.result = result, A.match = match_of_landmark;
-  FX_TRY(c->merge_scratch.reserve(c, fxk_map_join_scratch(&A, nullptr), "map join scratch"));
-  (void)fxk_map_join_scratch(&A, c->merge_scratch.d);
-  FX_HIP(fxk_map_join(c->stream, A));
+  assoc_args(&A.S, m, o, prior_host, prior_device, match_of_landmark);
+  A.src = src, A.dst = dst;
+  A.result = result;
+  FX_MAP_RUN(fxk_map_join, "map join scratch");
   return FX_OK;
 }
 
@@ -2168,21 +2177,12 @@ void fx_map_loop_options_default(fx_map_loop_options *o) {
 
 fx_status fx_map_close_loop(fx_ctx *c, fx_map *m, const fx_pose *prior_host, const double *prior_device, const fx_map_loop_options *opt,
                             fx_map_loop_result *result, int32_t *match_of_landmark) {
-  if (!c || !m) return fail(FX_ERR_INVALID_ARG, "null argument");
-  if (m->ctx != c) return fail(FX_ERR_INVALID_ARG, "the map belongs to another context");
-  if (prior_host && prior_device) return fail(FX_ERR_INVALID_ARG, "give the prior on the host or on the device, not both");
-  if (prior_host && !(std::isfinite(prior_host->c) && std::isfinite(prior_host->s) && std::isfinite(prior_host->tx) &&
-                      std::isfinite(prior_host->ty) && std::isfinite(prior_host->tz)))
-    return fail(FX_ERR_INVALID_ARG, "prior_host must be finite");
+  FX_TRY(map_call_check(c, m));
+  FX_TRY(prior_check(prior_host, prior_device));
   fx_map_loop_options o;
   fx_map_loop_options_default(&o);
   if (opt) o = *opt;
-  if (!(std::isfinite(o.search_dist) && o.search_dist > 0.f)) return fail(FX_ERR_INVALID_ARG, "search_dist must be finite and positive");
-  if (!(o.inlier_dist > 0.f) || !std::isfinite(o.inlier_dist) || !(o.min_baseline > 0.f) || !std::isfinite(o.min_baseline))
-    return fail(FX_ERR_INVALID_ARG, "inlier_dist and min_baseline must be finite and positive");
-  if (o.hyp_corr < 2u || o.hyp_corr > 128u) return fail(FX_ERR_INVALID_ARG, "hyp_corr must be 2..128");
-  if (o.min_inliers < 2u) return fail(FX_ERR_INVALID_ARG, "min_inliers must be at least 2");
-  if (!o.min_landmark_obs) return fail(FX_ERR_INVALID_ARG, "min_landmark_obs must be at least 1");
+  FX_TRY(consensus_options_check(o));
   if (o.recent_scans >= o.min_loop_scans) return fail(FX_ERR_INVALID_ARG, "recent_scans must be below min_loop_scans");
   if (o.segment == FX_LOC_ANY_SEGMENT) return fail(FX_ERR_INVALID_ARG, "segment must be one segment or FX_LOC_LAST_SEGMENT, not FX_LOC_ANY_SEGMENT");
   if (o.mode > FX_LOOP_DRY_RUN) return fail(FX_ERR_INVALID_ARG, "mode must be FX_LOOP_FIT, FX_LOOP_GIVEN or FX_LOOP_DRY_RUN");
@@ -2194,24 +2194,11 @@ fx_status fx_map_close_loop(fx_ctx *c, fx_map *m, const fx_pose *prior_host, con
     return fail(FX_ERR_INVALID_ARG, "prior_device and the result must be 8-byte, match_of_landmark 4-byte aligned");
   FX_HIP(hipSetDevice(c->device));
   FxMapLoopArgs A{};
-  A.G.header = m->a.header, A.G.records = m->a.records, A.G.acc = m->a.acc, A.G.carry = m->a.carry, A.G.alias = m->a.alias;
-  A.G.cap = m->a.cap, A.G.max_carry = m->a.max_carry;
-  // the gate in fp64 and the grid's cell edge: sd (1 + 2^-8), exact (csrc/fx_map_grid.h proves the margin): the localise's
-  const double sd = (double)o.search_dist;
-  A.G.md2 = sd * sd, A.G.inv_edge = 1.0 / (sd * (1.0 + 1.0 / 256.0));
-  A.G.table = fxk_map_merge_table(A.G.cap);
-  A.segment = o.segment, A.mode = o.mode, A.min_loop_scans = o.min_loop_scans, A.recent_scans = o.recent_scans;
+  assoc_args(&A.S, m, o, prior_host, prior_device, match_of_landmark);
+  A.segment = o.segment, A.min_loop_scans = o.min_loop_scans, A.recent_scans = o.recent_scans;
   A.given_s0 = o.loop_first_scan, A.given_s1 = o.loop_last_scan, A.given_px = o.pivot_x, A.given_py = o.pivot_y;
-  A.prior[0] = 1.0;
-  if (prior_host)
-    A.prior[0] = prior_host->c, A.prior[1] = prior_host->s, A.prior[2] = prior_host->tx, A.prior[3] = prior_host->ty, A.prior[4] = prior_host->tz;
-  A.prior_device = prior_device;
-  A.inlier_dist = o.inlier_dist, A.min_baseline = o.min_baseline;
-  A.hyp_corr = o.hyp_corr, A.min_inliers = o.min_inliers, A.min_landmark_obs = o.min_landmark_obs;
-  A.result = result, A.match = match_of_landmark;
-  FX_TRY(c->merge_scratch.reserve(c, fxk_map_loop_scratch(&A, nullptr), "map loop scratch"));
-  (void)fxk_map_loop_scratch(&A, c->merge_scratch.d);
-  FX_HIP(fxk_map_loop(c->stream, A));
+  A.result = result;
+  FX_MAP_RUN(fxk_map_loop, "map loop scratch");
   return FX_OK;
 }
 
@@ -2241,21 +2228,11 @@ void fx_map_find_loop_options_default(fx_map_find_loop_options *o) {
 }
 
 fx_status fx_map_find_loop(fx_ctx *c, fx_map *m, const fx_map_find_loop_options *opt, fx_map_loop_candidate *result, int32_t *match_of_landmark) {
-  if (!c || !m || !result) return fail(FX_ERR_INVALID_ARG, "null argument");
-  if (m->ctx != c) return fail(FX_ERR_INVALID_ARG, "the map belongs to another context");
+  FX_TRY(map_call_check(c, m, result != nullptr));
   fx_map_find_loop_options o;
   fx_map_find_loop_options_default(&o);
   if (opt) o = *opt;
-  auto positive = [](float v) { return std::isfinite(v) && v > 0.f; };
-  if (!positive(o.inlier_dist)) return fail(FX_ERR_INVALID_ARG, "inlier_dist must be finite and positive");
-  if (!positive(o.pair_tol)) return fail(FX_ERR_INVALID_ARG, "pair_tol must be finite and positive");
-  if (!positive(o.min_baseline)) return fail(FX_ERR_INVALID_ARG, "min_baseline must be finite and positive");
-  if (!(std::isfinite(o.max_baseline) && o.max_baseline >= o.min_baseline))
-    return fail(FX_ERR_INVALID_ARG, "max_baseline must be finite and at least min_baseline");
-  if (o.max_seeds < 1u || o.max_seeds > FX_FIND_MAX_QUERY) return fail(FX_ERR_INVALID_ARG, "max_seeds must be 1..64");
-  if (o.min_inliers < 3u) return fail(FX_ERR_INVALID_ARG, "min_inliers must be at least 3");
-  if (!o.min_margin) return fail(FX_ERR_INVALID_ARG, "min_margin must be at least 1");
-  if (!o.min_landmark_obs) return fail(FX_ERR_INVALID_ARG, "min_landmark_obs must be at least 1");
+  FX_TRY(constellation_options_check(o));
   if (o.segment == FX_LOC_ANY_SEGMENT) return fail(FX_ERR_INVALID_ARG, "segment must be one segment or FX_LOC_LAST_SEGMENT, not FX_LOC_ANY_SEGMENT");
   if (o.target_segment == FX_LOC_ANY_SEGMENT)
     return fail(FX_ERR_INVALID_ARG, "target_segment must be one segment, FX_LOC_LAST_SEGMENT or FX_FIND_SAME_SEGMENT, not FX_LOC_ANY_SEGMENT");
@@ -2266,23 +2243,10 @@ fx_status fx_map_find_loop(fx_ctx *c, fx_map *m, const fx_map_find_loop_options 
     return fail(FX_ERR_INVALID_ARG, "the result must be 8-byte, match_of_landmark 4-byte aligned");
   FX_HIP(hipSetDevice(c->device));
   FxMapFindLoopArgs A{};
-  for (FxMapMergeArgs *G : {&A.P, &A.Q}) {
-    G->header = m->a.header, G->records = m->a.records, G->acc = m->a.acc, G->carry = m->a.carry, G->alias = m->a.alias;
-    G->cap = m->a.cap, G->max_carry = m->a.max_carry;
-    G->table = fxk_map_merge_table(G->cap);
-  }
-  // the two gates and the grids' cell edges: fx_map_relocalize's (csrc/fx_map_constellation.h derives the pair grid's gate)
-  const double pd = ((double)o.max_baseline + (double)o.pair_tol) * (1.0 + 1.0 / 1048576.0), id = (double)o.inlier_dist;
-  A.P.md2 = pd * pd, A.P.inv_edge = 1.0 / (pd * (1.0 + 1.0 / 256.0));
-  A.Q.md2 = id * id, A.Q.inv_edge = 1.0 / (id * (1.0 + 1.0 / 256.0));
-  A.inlier_dist = o.inlier_dist, A.pair_tol = o.pair_tol, A.min_baseline = o.min_baseline, A.max_baseline = o.max_baseline;
-  A.max_seeds = o.max_seeds, A.min_inliers = o.min_inliers, A.min_margin = o.min_margin, A.min_landmark_obs = o.min_landmark_obs;
+  constellation_args(&A, m, o);
   A.segment = o.segment, A.target_segment = o.target_segment, A.min_loop_scans = o.min_loop_scans, A.recent_scans = o.recent_scans;
-  A.chunks = (A.P.cap + FXR_CHUNK - 1u) / FXR_CHUNK;
   A.result = result, A.match = match_of_landmark;
-  FX_TRY(c->merge_scratch.reserve(c, fxk_map_find_loop_scratch(&A, nullptr), "map find loop scratch"));
-  (void)fxk_map_find_loop_scratch(&A, c->merge_scratch.d);
-  FX_HIP(fxk_map_find_loop(c->stream, A));
+  FX_MAP_RUN(fxk_map_find_loop, "map find loop scratch");
   return FX_OK;
 }
 
@@ -2355,8 +2319,7 @@ fx_status fx_map_snapshot_check(const void *src, size_t bytes, uint32_t max_land
 }
 
 fx_status fx_map_export_host(fx_ctx *c, fx_map *m, void *dst, size_t capacity, size_t *bytes_out) {
-  if (!c || !m || (!dst && capacity)) return fail(FX_ERR_INVALID_ARG, "null argument");
-  if (m->ctx != c) return fail(FX_ERR_INVALID_ARG, "the map belongs to another context");
+  FX_TRY(map_call_check(c, m, dst || !capacity));
   FX_HIP(hipSetDevice(c->device));
   fx_map_header H;
   FX_HIP(hipMemcpyAsync(&H, m->a.header, sizeof H, hipMemcpyDeviceToHost, c->stream));
@@ -2386,8 +2349,7 @@ fx_status fx_map_export_host(fx_ctx *c, fx_map *m, void *dst, size_t capacity, s
 }
 
 fx_status fx_map_import_host(fx_ctx *c, fx_map *m, const void *src, size_t bytes) {
-  if (!c || !m || !src) return fail(FX_ERR_INVALID_ARG, "null argument");
-  if (m->ctx != c) return fail(FX_ERR_INVALID_ARG, "the map belongs to another context");
+  FX_TRY(map_call_check(c, m, src != nullptr));
   FX_TRY(fx_map_snapshot_check(src, bytes, m->a.cap, m->a.max_carry));
   FX_HIP(hipSetDevice(c->device));
   // the pinned staging: free to write once the copies of the import before are done

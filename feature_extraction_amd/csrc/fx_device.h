@@ -144,6 +144,18 @@ __device__ __forceinline__ void wg_scan2_blocks(uint32_t *bsum, uint32_t n_block
   }
   tot_a = base_a, tot_b = base_b;
 }
+// The carving of a call's arrays out of the context's scratch (the fxk_*_scratch functions; host only): take<T>(count) hands out the
+// next `count` elements and steps to the next 16-byte boundary.  With base null only the bytes are counted.
+struct FxCarve {
+  uint8_t *base;
+  size_t o;
+  template <typename T>
+  T *take(size_t count) {
+    const size_t at = o;
+    o += (count * sizeof(T) + 15u) & ~(size_t)15;
+    return base ? reinterpret_cast<T *>(base + at) : nullptr;
+  }
+};
 // fx_match_descriptors_csr (csrc/fx_match.hip): one pair of row ranges as the kernels see it, and a launch's arguments.
 struct FxMatchPairDev {
   uint32_t q_row0, q_rows, t_row0, t_rows;
@@ -323,49 +335,41 @@ struct FxMapCompactArgs {
   uint32_t *bsum;               // [2][blocks of landmarks]: the block's kept landmarks / dropped live observations, then their prefix
   uint4 *stage_rec, *stage_acc; // [cap][3], [cap][4]: the kept records and sums at their new ids, before they are copied back
 };
-// fx_map_join_segments (csrc/fx_map_join.hip): a launch set's arguments.  G describes the grid over the map (its gate is the search
-// distance; the merge's per-landmark arrays are null) and carries the map's own memory; the last group is the context's scratch,
-// sized by the map's max_landmarks (G.cap).
-#define FX_MAP_JOIN_ST_WORDS 4  // 0 queries, 1 queries with a target, 2 landmarks moved
-struct FxMapJoinArgs {
+// What fx_map_join_segments and fx_map_close_loop share (csrc/fx_map_assoc.h): the association of one set of landmarks with another
+// under a prior and the consensus over it.  G describes the grid over the map (its gate is the search distance; the merge's
+// per-landmark arrays are null) and carries the map's own memory; the last group is the context's scratch, sized by the map's
+// max_landmarks (G.cap).
+#define FX_MAP_ASSOC_ST_WORDS 4  // 0 queries, 1 queries with a target, 2 landmarks moved
+struct FxMapAssocArgs {
   FxMapMergeArgs G;
-  uint32_t src, dst, mode;
+  uint32_t mode;                // FX_JOIN_* / FX_LOOP_*: FIT, GIVEN or DRY_RUN
   double prior[5];              // c, s, tx, ty, tz: the host's prior, or the identity
   const double *prior_device;   // five doubles read on the device in its place, or null
   float inlier_dist, min_baseline;
   uint32_t hyp_corr, min_inliers, min_landmark_obs;
-  void *result;                 // fx_map_join_result or null
   int32_t *match;               // [cap] or null
-  void *fit;                    // fx_map_join_result: what the consensus decided, for the launches behind it
-  uint32_t *st;                 // [FX_MAP_JOIN_ST_WORDS]
+  void *fit;                    // the call's result record: what the consensus decided, for the launches behind it
+  uint32_t *st;                 // [FX_MAP_ASSOC_ST_WORDS]
   int32_t *near;                // [cap]: the query's target, -1: none or no query
   unsigned long long *d2;       // [cap]: its squared xy distance as bits
   uint32_t *local;              // [cap]: the exclusive prefix of the queries with a target within the block of 256
   uint32_t *bsum;               // [2][blocks of landmarks]: the block's queries / queries with a target, then their prefix
-  uint32_t *corr;               // [FX_JOIN_MAX_CORR]: the queries of the correspondences, in ascending id
+  uint32_t *corr;               // [FXC_MAP_MAX_CORR]: the queries of the correspondences, in ascending id
 };
-// fx_map_close_loop (csrc/fx_map_loop.hip): a launch set's arguments, shaped like the join's.  G describes the grid over the map (its
-// gate is the search distance) and carries the map's own memory; the last group is the context's scratch, sized by G.cap.
-#define FX_MAP_LOOP_ST_WORDS 4  // 0 queries, 1 queries with a target, 2 landmarks moved
+// fx_map_join_segments (csrc/fx_map_join.hip): a launch set's arguments.
+struct FxMapJoinArgs {
+  FxMapAssocArgs S;
+  uint32_t src, dst;
+  void *result;                 // fx_map_join_result or null
+};
+// fx_map_close_loop (csrc/fx_map_loop.hip): a launch set's arguments.
 struct FxMapLoopArgs {
-  FxMapMergeArgs G;
-  uint32_t segment, mode;       // the option's segment (FX_LOC_LAST_SEGMENT is resolved on the device)
+  FxMapAssocArgs S;
+  uint32_t segment;             // the option's segment (FX_LOC_LAST_SEGMENT is resolved on the device)
   uint32_t min_loop_scans, recent_scans;
   uint32_t given_s0, given_s1;  // FX_LOOP_GIVEN: the loop's bounds and the pivot
   double given_px, given_py;
-  double prior[5];              // c, s, tx, ty, tz: the host's prior, or the identity
-  const double *prior_device;   // five doubles read on the device in its place, or null
-  float inlier_dist, min_baseline;
-  uint32_t hyp_corr, min_inliers, min_landmark_obs;
   void *result;                 // fx_map_loop_result or null
-  int32_t *match;               // [cap] or null
-  void *fit;                    // fx_map_loop_result: what the consensus decided, for the launches behind it
-  uint32_t *st;                 // [FX_MAP_LOOP_ST_WORDS]
-  int32_t *near;                // [cap]: the query's target, -1: none or no query
-  unsigned long long *d2;       // [cap]: its squared xy distance as bits
-  uint32_t *local;              // [cap]: the exclusive prefix of the queries with a target within the block of 256
-  uint32_t *bsum;               // [2][blocks of landmarks]: the block's queries / queries with a target, then their prefix
-  uint32_t *corr;               // [FX_LOOP_MAX_CORR]: the queries of the correspondences, in ascending id
 };
 // fx_map_find_loop (csrc/fx_map_find_loop.hip): a launch set's arguments.  P and Q are fx_map_relocalize's two grids (the search
 // is csrc/fx_map_constellation.h's, with the loop's queries in the place of a scan's keypoints); the last group is the context's

@@ -151,17 +151,12 @@ extern "C" hipError_t fxk_map_compact(hipStream_t s, const FxMapCompactArgs &A) 
 // bytes of the context's scratch for a map of `cap` landmarks, and the pointers carved out of it
 extern "C" size_t fxk_map_compact_scratch(FxMapCompactArgs *A, uint8_t *base) {
   const size_t cap = A->cap, nb = (cap + FXMC_WG - 1u) / FXMC_WG;
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o += (bytes + 15u) & ~(size_t)15;
-    return base ? base + at : (uint8_t *)nullptr;
-  };
-  A->stage_rec = (uint4 *)take(cap * sizeof(fx_map_landmark));
-  A->stage_acc = (uint4 *)take(cap * FX_MAP_ACC * sizeof(double));
-  A->mark = (uint32_t *)take((cap + FX_MAP_COMPACT_ST_WORDS) * 4u);
+  FxCarve C{base, 0};
+  A->stage_rec = C.take<uint4>(cap * FXMC_REC_V);
+  A->stage_acc = C.take<uint4>(cap * FXMC_ACC_V);
+  A->mark = C.take<uint32_t>(cap + FX_MAP_COMPACT_ST_WORDS);
   A->st = base ? A->mark + cap : (uint32_t *)nullptr;
-  A->local = (int32_t *)take(cap * 4u);
-  A->bsum = (uint32_t *)take(2u * nb * 4u);
-  return o;
+  A->local = C.take<int32_t>(cap);
+  A->bsum = C.take<uint32_t>(2u * nb);
+  return C.o;
 }

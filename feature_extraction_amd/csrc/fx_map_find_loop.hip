@@ -238,24 +238,19 @@ extern "C" hipError_t fxk_map_find_loop(hipStream_t s, const FxMapFindLoopArgs &
 // bytes of the context's scratch for a map of A->P.cap landmarks, and the pointers carved out of it: the pair grid in the merge's
 // layout first, the score grid in the same layout behind it, then the call's own arrays
 extern "C" size_t fxk_map_find_loop_scratch(FxMapFindLoopArgs *A, uint8_t *base) {
-  size_t o = fxk_map_merge_scratch(&A->P, base);
-  o += fxk_map_merge_scratch(&A->Q, base ? base + o : nullptr);
+  FxCarve C{base, fxk_map_merge_scratch(&A->P, base)};
+  C.o += fxk_map_merge_scratch(&A->Q, base ? base + C.o : nullptr);
   A->P.prop = A->P.pred = A->P.succ = nullptr, A->P.keep = nullptr;  // (the grid's mark leaves the merge's words alone)
   A->Q.prop = A->Q.pred = A->Q.succ = nullptr, A->Q.keep = nullptr;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o += (bytes + 15u) & ~(size_t)15;
-    return base ? base + at : (uint8_t *)nullptr;
-  };
   const size_t K = FX_FIND_MAX_QUERY;
-  uint8_t *ctl = take(8u + FX_FIND_ST_WORDS * 4u);
+  uint8_t *ctl = C.take<uint8_t>(8u + FX_FIND_ST_WORDS * 4u);
   A->n_hyp = (unsigned long long *)ctl;
   A->st = (uint32_t *)(ctl ? ctl + 8 : nullptr);
-  A->kq = (double *)take(K * 3u * 8u);
-  A->win = (FxRelocWinner *)take(sizeof(FxRelocWinner));
-  A->partial = (FxRelocPartial *)take((size_t)A->max_seeds * A->chunks * sizeof(FxRelocPartial));
-  A->kid = (uint32_t *)take(K * 4u);
-  A->seeds = (uint32_t *)take(K * 4u);
-  A->elig = (uint8_t *)take(A->P.cap);
-  return o;
+  A->kq = C.take<double>(K * 3u);
+  A->win = C.take<FxRelocWinner>(1u);
+  A->partial = C.take<FxRelocPartial>((size_t)A->max_seeds * A->chunks);
+  A->kid = C.take<uint32_t>(K);
+  A->seeds = C.take<uint32_t>(K);
+  A->elig = C.take<uint8_t>(A->P.cap);
+  return C.o;
 }

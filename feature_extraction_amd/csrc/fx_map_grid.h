@@ -76,34 +76,21 @@ struct Near {
   uint32_t id;
   bool any;
 };
-// One bucket of the nearest search of fx_map_localize's association clause (include/fx.h), which fx_map_join_segments shares:
-// the candidates of bucket b within the gate of (wx, wy), of segment seg (any_seg: of any), with at least min_obs observations and
-// a finite z (the grid holds the merge's live set: the rest of the eligibility is here), by the lowest (d2 bits, id).
-__device__ __forceinline__ void walk_nearest(const FxMapMergeArgs &G, uint32_t min_obs, uint32_t b, double wx, double wy, uint32_t seg,
-                                             bool any_seg, Near &best) {
+// One bucket of the nearest search of fx_map_localize's association clause (include/fx.h), which fx_map_join_segments and
+// fx_map_close_loop share: the candidates of bucket b within the gate of (wx, wy) that the call accepts (accept(candidate):
+// fx_map_localize "of the segment, or of any", the join "of segment dst", the loop "of the segment and OLD"), with at least min_obs
+// observations and a finite z (the grid holds the merge's live set: the rest of the eligibility is here), by the lowest
+// (d2 bits, id).  The record is read only for a candidate that would win.
+template <typename Accept>
+__device__ __forceinline__ void walk_nearest(const FxMapMergeArgs &G, uint32_t min_obs, uint32_t b, double wx, double wy, Accept accept,
+                                             Near &best) {
   const uint32_t end = min(bucket_end(G, b), G.cap);
   for (uint32_t p = bucket_begin(G, b); p < end; ++p) {
     const FxMapMergeCand c = G.cand[p];
     const double dx = c.x - wx, dy = c.y - wy;
     const double d2 = dx * dx + dy * dy;
-    if (!(d2 <= G.md2) || !(any_seg || c.segment == seg) || c.id >= G.cap) continue;
-    const unsigned long long k = (unsigned long long)__double_as_longlong(d2);
-    if (best.any && !(k < best.d2 || (k == best.d2 && c.id < best.id))) continue;
-    const fx_map_landmark R = records(G)[c.id];
-    if (R.n_obs < min_obs || !isfinite(R.z)) continue;
-    best.any = true, best.d2 = k, best.id = c.id;
-  }
-}
-// The same bucket walk for fx_map_close_loop's association (include/fx.h): the candidates must be of segment seg and OLD,
-// (uint64)last_scan + min_loop <= last, beside walk_nearest's gate and eligibility; the order is the same (d2 bits, id).
-__device__ __forceinline__ void walk_nearest_old(const FxMapMergeArgs &G, uint32_t min_obs, uint32_t b, double wx, double wy, uint32_t seg,
-                                                 unsigned long long min_loop, unsigned long long last, Near &best) {
-  const uint32_t end = min(bucket_end(G, b), G.cap);
-  for (uint32_t p = bucket_begin(G, b); p < end; ++p) {
-    const FxMapMergeCand c = G.cand[p];
-    const double dx = c.x - wx, dy = c.y - wy;
-    const double d2 = dx * dx + dy * dy;
-    if (!(d2 <= G.md2) || c.segment != seg || !((unsigned long long)c.last_scan + min_loop <= last) || c.id >= G.cap) continue;
+    const bool accepted = accept(c);  // (a plain value before the test: the candidate is read whole, not field by field down a branch)
+    if (!(d2 <= G.md2) || !accepted || c.id >= G.cap) continue;
     const unsigned long long k = (unsigned long long)__double_as_longlong(d2);
     if (best.any && !(k < best.d2 || (k == best.d2 && c.id < best.id))) continue;
     const fx_map_landmark R = records(G)[c.id];

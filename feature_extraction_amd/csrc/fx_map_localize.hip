@@ -54,9 +54,6 @@ __device__ __forceinline__ bool wanted_segment(const FxMapLocalizeArgs &A, uint3
   }
   return true;
 }
-__device__ __forceinline__ void walk(const FxMapLocalizeArgs &A, uint32_t b, double wx, double wy, uint32_t seg, bool any_seg, Near &best) {
-  walk_nearest(A.G, A.min_landmark_obs, b, wx, wy, seg, any_seg, best);
-}
 __device__ __forceinline__ void write_no_fit(fx_localization *out, const fx_pose &prior, uint32_t n_corr, uint32_t flags) {
   fx_localization r;
   r.pose = prior;
@@ -91,7 +88,8 @@ extern "C" __global__ __launch_bounds__(FXL_WG) void k_loc_search(FxMapLocalizeA
         double wx, wy, wz;
         world_point(P, k, wx, wy, wz);
         const double tx = floor(wx * A.G.inv_edge), ty = floor(wy * A.G.inv_edge);
-        grid_neighbourhood(A.G, tx, ty, [&](uint32_t b) { walk(A, b, wx, wy, seg, any_seg, best); });
+        const auto wanted = [&](const FxMapMergeCand &c) { return any_seg || c.segment == seg; };
+        grid_neighbourhood(A.G, tx, ty, [&](uint32_t b) { walk_nearest(A.G, A.min_landmark_obs, b, wx, wy, wanted, best); });
       }
     }
   }
@@ -189,12 +187,9 @@ extern "C" hipError_t fxk_map_localize(hipStream_t s, const FxMapLocalizeArgs &A
 // bytes of the context's scratch for a map of A->G.cap landmarks and q_max_rows rows, and the pointers carved out of it: the grid's
 // part of the merge's layout first (the two calls share the buffer: they are ordered on one stream), then the per-row arrays
 extern "C" size_t fxk_map_localize_scratch(FxMapLocalizeArgs *A, uint8_t *base) {
-  size_t o = fxk_map_merge_scratch(&A->G, base);
+  FxCarve C{base, fxk_map_merge_scratch(&A->G, base)};
   A->G.prop = A->G.pred = A->G.succ = nullptr, A->G.keep = nullptr;  // (the grid's mark leaves the merge's words alone)
-  const size_t n = A->q_max_rows;
-  A->d2 = (unsigned long long *)(base ? base + o : nullptr);
-  o += (n * 8u + 15u) & ~(size_t)15;
-  A->near = (int32_t *)(base ? base + o : nullptr);
-  o += (n * 4u + 15u) & ~(size_t)15;
-  return o;
+  A->d2 = C.take<unsigned long long>(A->q_max_rows);
+  A->near = C.take<int32_t>(A->q_max_rows);
+  return C.o;
 }

@@ -165,23 +165,18 @@ extern "C" hipError_t fxk_map_merge(hipStream_t s, const FxMapMergeArgs &A) {
 // bytes of the context's scratch for a map of `cap` landmarks, and the pointers carved out of it
 extern "C" size_t fxk_map_merge_scratch(FxMapMergeArgs *A, uint8_t *base) {
   const size_t cap = A->cap, nbuckets = (size_t)A->table + 1u, nb = (nbuckets + FXMM_WG - 1u) / FXMM_WG;
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o += (bytes + 15u) & ~(size_t)15;
-    return base ? base + at : (uint8_t *)nullptr;
-  };
-  A->cand = (FxMapMergeCand *)take(cap * sizeof(FxMapMergeCand));
-  A->keep = (unsigned long long *)take(cap * 8u);
-  A->st = (uint32_t *)take(FX_MAP_MERGE_ST_WORDS * 4u);
-  A->count = (uint32_t *)take(nbuckets * 4u);
-  A->start = (uint32_t *)take(nbuckets * 4u);
-  A->bsum = (uint32_t *)take(2u * nb * 4u);
-  A->bucket = (uint32_t *)take(cap * 4u);
-  A->prop = (int32_t *)take(cap * 4u);
-  A->pred = (int32_t *)take(cap * 4u);
-  A->succ = (int32_t *)take(cap * 4u);
-  return o;
+  FxCarve C{base, 0};
+  A->cand = C.take<FxMapMergeCand>(cap);
+  A->keep = C.take<unsigned long long>(cap);
+  A->st = C.take<uint32_t>(FX_MAP_MERGE_ST_WORDS);
+  A->count = C.take<uint32_t>(nbuckets);
+  A->start = C.take<uint32_t>(nbuckets);
+  A->bsum = C.take<uint32_t>(2u * nb);
+  A->bucket = C.take<uint32_t>(cap);
+  A->prop = C.take<int32_t>(cap);
+  A->pred = C.take<int32_t>(cap);
+  A->succ = C.take<int32_t>(cap);
+  return C.o;
 }
 
 extern "C" uint32_t fxk_map_merge_wg(void) { return FXMM_WG; }

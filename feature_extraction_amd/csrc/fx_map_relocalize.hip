@@ -218,24 +218,19 @@ extern "C" hipError_t fxk_map_relocalize(hipStream_t s, const FxMapRelocalizeArg
 // bytes of the context's scratch for a map of A->P.cap landmarks and n_scans scans, and the pointers carved out of it: the pair
 // grid in the merge's layout first, the score grid in the same layout behind it, then the call's own arrays
 extern "C" size_t fxk_map_relocalize_scratch(FxMapRelocalizeArgs *A, uint8_t *base) {
-  size_t o = fxk_map_merge_scratch(&A->P, base);
-  o += fxk_map_merge_scratch(&A->Q, base ? base + o : nullptr);
+  FxCarve C{base, fxk_map_merge_scratch(&A->P, base)};
+  C.o += fxk_map_merge_scratch(&A->Q, base ? base + C.o : nullptr);
   A->P.prop = A->P.pred = A->P.succ = nullptr, A->P.keep = nullptr;  // (the grid's mark leaves the merge's words alone)
   A->Q.prop = A->Q.pred = A->Q.succ = nullptr, A->Q.keep = nullptr;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o += (bytes + 15u) & ~(size_t)15;
-    return base ? base + at : (uint8_t *)nullptr;
-  };
   const size_t n = A->n_scans, K = FX_RELOC_MAX_KP;
-  A->kq = (double *)take(n * K * 3u * 8u);
-  A->n_hyp = (unsigned long long *)take(n * 8u);
-  A->win = (FxRelocWinner *)take(n * sizeof(FxRelocWinner));
-  A->partial = (FxRelocPartial *)take(n * A->max_seeds * A->chunks * sizeof(FxRelocPartial));
-  A->krow = (uint32_t *)take(n * K * 4u);
-  A->seeds = (uint32_t *)take(n * K * 4u);
-  A->meta = (uint32_t *)take(n * 4u * 4u);
-  A->runner = (uint32_t *)take(n * 4u);
-  A->elig = (uint8_t *)take(A->P.cap);
-  return o;
+  A->kq = C.take<double>(n * K * 3u);
+  A->n_hyp = C.take<unsigned long long>(n);
+  A->win = C.take<FxRelocWinner>(n);
+  A->partial = C.take<FxRelocPartial>(n * A->max_seeds * A->chunks);
+  A->krow = C.take<uint32_t>(n * K);
+  A->seeds = C.take<uint32_t>(n * K);
+  A->meta = C.take<uint32_t>(n * 4u);
+  A->runner = C.take<uint32_t>(n);
+  A->elig = C.take<uint8_t>(A->P.cap);
+  return C.o;
 }
