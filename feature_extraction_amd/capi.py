@@ -207,6 +207,17 @@ MAP_COMPACT_RESULT_FIELDS = ("before", "kept", "dropped_absorbed", "dropped_live
 FX_MAP_SNAPSHOT_MAGIC, FX_MAP_SNAPSHOT_FORMAT, FX_MAP_SNAPSHOT_HEADER_BYTES, FX_MAP_ACC = 0x504D5846, 1, 64, 8
 
 
+class FxMapAppendResult(C.Structure):
+    _fields_ = [("id_base", C.c_uint32), ("scan_base", C.c_uint32), ("segment_base", C.c_uint32), ("appended", C.c_uint32),
+                ("flags", C.c_uint32), ("carry_rows", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+FX_APPEND_APPLIED, FX_APPEND_CARRY_DROPPED, FX_APPEND_EMPTY, FX_APPEND_OVERFLOWED, FX_APPEND_NO_ROOM, FX_APPEND_TOO_LONG = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
+# fx_map_append_result as a numpy record (append_records)
+APPEND_DTYPE = np.dtype([("id_base", "<u4"), ("scan_base", "<u4"), ("segment_base", "<u4"), ("appended", "<u4"), ("flags", "<u4"),
+                         ("carry_rows", "<u4"), ("reserved", "<u4", (2,))])
+
+
 class FxLocalizeOptions(C.Structure):
     _fields_ = [("search_dist", C.c_float), ("inlier_dist", C.c_float), ("min_baseline", C.c_float), ("hyp_corr", C.c_uint32),
                 ("min_inliers", C.c_uint32), ("min_landmark_obs", C.c_uint32), ("segment", C.c_uint32), ("reserved", C.c_uint32)]
@@ -360,6 +371,7 @@ EXPORTS = ("fx_version", "fx_check_abi", "fx_status_str", "fx_last_error", "fx_p
            "fx_map_merge_options_default", "fx_map_merge", "fx_map_get_alias", "fx_map_read_alias",
            "fx_localize_options_default", "fx_map_localize", "fx_relocalize_options_default", "fx_map_relocalize",
            "fx_map_compact_options_default", "fx_map_compact", "fx_map_export_host", "fx_map_import_host", "fx_map_snapshot_check",
+           "fx_map_append", "fx_map_append_host",
            "fx_map_join_options_default", "fx_map_join_segments",
            "fx_map_loop_options_default", "fx_map_close_loop", "fx_map_loop_correct_poses",
            "fx_map_find_loop_options_default", "fx_map_find_loop",
@@ -505,6 +517,8 @@ def load():
     lib.fx_map_export_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     lib.fx_map_import_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     lib.fx_map_snapshot_check.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32]
+    lib.fx_map_append.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.fx_map_append_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.fx_map_join_options_default.argtypes = [C.POINTER(FxMapJoinOptions)]
     lib.fx_map_join_options_default.restype = None
     lib.fx_map_join_segments.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(FxPose), C.c_void_p, C.POINTER(FxMapJoinOptions),
@@ -1296,6 +1310,63 @@ def map_compact_reference(state, min_obs=1, min_age_scans=64):
     for i in range(N):
         remap[i] = new_id[root(i)]
     return st, remap, {"before": N, "kept": K, "dropped_absorbed": absorbed, "dropped_live": N - K - absorbed}
+
+
+# ---- one map appended to another (include/fx.h fx_map_append)
+def append_records(out):
+    """The 32 bytes fx_map_append wrote (a device tensor, or an array) as one APPEND_DTYPE record."""
+    a = out.cpu().numpy() if hasattr(out, "cpu") else np.asarray(out)
+    return np.ascontiguousarray(a).view(np.uint8).reshape(-1)[:APPEND_DTYPE.itemsize].view(APPEND_DTYPE)[0]
+
+
+def map_append_reference(dst_state, src_state):
+    """The definition of fx_map_append and fx_map_append_host (include/fx.h) in plain loops over two map_reference /
+    map_merge_reference / ... states; neither is modified.  Returns (dst's new state, {"id_base", "scan_base", "segment_base",
+    "appended", "flags", "carry_rows", "reserved"})."""
+    D, S = dst_state["header"], src_state["header"]
+    cap, max_carry = int(dst_state["max_landmarks"]), int(dst_state["max_carry_rows"])
+    N, M, r = min(int(D["n_landmarks"]), cap), int(S["n_landmarks"]), int(S["carry_rows"])
+    Sd, Gd = int(D["scans"]), int(D["segments"])
+    top, flags = 0xffffffff, 0
+    if int(S["scans"]) == 0:
+        flags |= FX_APPEND_EMPTY
+    if int(D["n_needed"]) > int(D["n_landmarks"]) or int(S["n_needed"]) > int(S["n_landmarks"]):
+        flags |= FX_APPEND_OVERFLOWED
+    if N + M > cap:
+        flags |= FX_APPEND_NO_ROOM
+    if any(int(D[k]) + int(S[k]) > top for k in ("scans", "segments", "batches", "n_obs")):
+        flags |= FX_APPEND_TOO_LONG
+    res = {"id_base": N, "scan_base": Sd, "segment_base": Gd, "appended": 0, "flags": flags, "carry_rows": int(D["carry_rows"]), "reserved": 0}
+    st = dict(dst_state, header=dict(D), landmarks=[dict(R) for R in dst_state["landmarks"]], acc=[list(a) for a in dst_state["acc"]],
+              carry=[int(c) for c in dst_state["carry"]], carry_kp=dst_state["carry_kp"].copy())
+    alias = [int(a) for a in dst_state.get("alias", [])][:N]
+    st["alias"] = alias + [-1] * (N - len(alias))
+    if flags:
+        return st, res
+    src_alias = [int(a) for a in src_state.get("alias", [])][:M]
+    src_alias += [-1] * (M - len(src_alias))
+    for i in range(M):
+        R = dict(src_state["landmarks"][i])
+        R["first_scan"] = int(R["first_scan"]) + Sd
+        R["last_scan"] = int(R["last_scan"]) + Sd
+        R["segment"] = int(R["segment"]) + Gd
+        st["landmarks"].append(R), st["acc"].append(list(src_state["acc"][i]))
+        st["alias"].append(src_alias[i] + N if src_alias[i] >= 0 else -1)
+    H = st["header"]
+    if r <= max_carry:
+        st["carry"] = [int(c) + N if int(c) >= 0 else -1 for c in list(src_state["carry"])[:r]]
+        st["carry_kp"], H["carry_rows"] = np.array(src_state["carry_kp"][:r], np.uint32).reshape(r, 4), r
+        flags = FX_APPEND_APPLIED
+    else:
+        st["carry"], st["carry_kp"], H["carry_rows"] = [], np.zeros((0, 4), np.uint32), 0
+        flags = FX_APPEND_APPLIED | FX_APPEND_CARRY_DROPPED
+    H["n_landmarks"] = H["n_needed"] = N + M
+    for k in ("n_obs", "scans", "batches", "segments"):
+        H[k] = int(D[k]) + int(S[k])
+    H["flags"] = int(D["flags"]) | int(S["flags"])
+    H["last_joined"], H["last_new"], H["last_pose"] = int(S["last_joined"]), int(S["last_new"]), tuple(S["last_pose"])
+    res.update(appended=M, flags=flags, carry_rows=H["carry_rows"])
+    return st, res
 
 
 def _pad16(b):
@@ -2349,6 +2420,29 @@ class Map:
         raises FxError and leaves the map as it was."""
         data = bytes(data)
         check(self.lib.fx_map_import_host(self.ctx.handle, self.handle, data, len(data)))
+
+    def _append_result(self, result):
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        return dev, _out_tensor(result, (8,), torch.int32, dev, f"result must be a contiguous torch.int32 tensor [8] on {dev}", typed=True)
+
+    def append(self, src, result=None):
+        """fx_map_append: the Map `src` (of the same context; it is only read) appended behind this map's landmarks (include/fx.h).
+        Returns the fx_map_append_result as a device torch.int32 tensor [8] (append_records reads it); `result` reuses one,
+        result=False passes NULL (None is returned).  Stream-correct like merge(); never waits for the stream."""
+        dev, result = self._append_result(result)
+        with _on_stream(self.ctx.stream_ptr(), dev):
+            check(self.lib.fx_map_append(self.ctx.handle, self.handle, src.handle, _ptr(result)))
+        return result
+
+    def append_state(self, data, result=None):
+        """fx_map_append_host: the snapshot `data` (bytes: export_state() of a map of any context or device) appended behind this
+        map's landmarks; a block the check refuses raises FxError and leaves the map as it was.  Returns what append() returns."""
+        data = bytes(data)
+        dev, result = self._append_result(result)
+        with _on_stream(self.ctx.stream_ptr(), dev):
+            check(self.lib.fx_map_append_host(self.ctx.handle, self.handle, data, len(data), _ptr(result)))
+        return result
 
     def alias(self, first=0, count=None):
         """fx_map_read_alias (waits for the stream): alias[first, first + count) as int32, -1 for a live landmark, else the id of

@@ -99,6 +99,8 @@ hipError_t fxk_map_find_loop(hipStream_t s, const FxMapFindLoopArgs &A);
 size_t fxk_map_find_loop_scratch(FxMapFindLoopArgs *A, uint8_t *base);
 hipError_t fxk_map_compact(hipStream_t s, const FxMapCompactArgs &A);
 size_t fxk_map_compact_scratch(FxMapCompactArgs *A, uint8_t *base);
+hipError_t fxk_map_append(hipStream_t s, const FxMapAppendArgs &A);
+size_t fxk_map_append_scratch(FxMapAppendArgs *A, uint8_t *base);
 hipError_t fxk_map_join(hipStream_t s, const FxMapJoinArgs &A);
 size_t fxk_map_join_scratch(FxMapJoinArgs *A, uint8_t *base);
 hipError_t fxk_map_loop(hipStream_t s, const FxMapLoopArgs &A);
@@ -276,9 +278,10 @@ struct fx_ctx {
   DevScratch merge_scratch;  // fx_map_merge: the grid (bucket counts, landmarks in bucket order), proposals, kept links;
                              // fx_map_localize: the same grid, then each row's landmark and distance;
                              // fx_map_compact: the marks, the new ids, the blocks' counts, the kept records and sums staged;
+                             // fx_map_append: the state words; fx_map_append_host: the snapshot's bytes before them;
                              // fx_map_join_segments, fx_map_close_loop: the grid, each query's target and distance, the list of
                              // correspondences
-  // fx_map_import_host: the snapshot's bytes, pinned, until the copies enqueued from them are done (snap_ev)
+  // fx_map_import_host, fx_map_append_host: the snapshot's bytes, pinned, until the copies enqueued from them are done (snap_ev)
   uint8_t *snap_h = nullptr;
   size_t snap_bytes = 0;
   hipEvent_t snap_ev = nullptr;
@@ -2348,11 +2351,10 @@ fx_status fx_map_export_host(fx_ctx *c, fx_map *m, void *dst, size_t capacity, s
   return FX_OK;
 }
 
-fx_status fx_map_import_host(fx_ctx *c, fx_map *m, const void *src, size_t bytes) {
-  FX_TRY(map_call_check(c, m, src != nullptr));
-  FX_TRY(fx_map_snapshot_check(src, bytes, m->a.cap, m->a.max_carry));
-  FX_HIP(hipSetDevice(c->device));
-  // the pinned staging: free to write once the copies of the import before are done
+namespace {
+// the snapshot's bytes into the context's pinned staging (fx_map_import_host, fx_map_append_host): free to write once the copies
+// of the call before are done; the caller records snap_ev behind the copies it enqueues from it
+fx_status snap_stage(fx_ctx *c, const void *src, size_t bytes) {
   if (!c->snap_ev) FX_HIP(hipEventCreateWithFlags(&c->snap_ev, hipEventDisableTiming));
   FX_HIP(hipEventSynchronize(c->snap_ev));
   if (bytes > c->snap_bytes) {
@@ -2365,6 +2367,21 @@ fx_status fx_map_import_host(fx_ctx *c, fx_map *m, const void *src, size_t bytes
     c->snap_h = (uint8_t *)q, c->snap_bytes = want;
   }
   memcpy(c->snap_h, src, bytes);
+  return FX_OK;
+}
+// the target's part of an append's arguments
+void append_target(FxMapAppendArgs *A, const fx_map *m, fx_map_append_result *result) {
+  A->header = m->a.header, A->records = m->a.records, A->acc = m->a.acc, A->alias = m->a.alias, A->carry = m->a.carry, A->carry_kp = m->a.carry_kp;
+  A->cap = m->a.cap, A->max_carry = m->a.max_carry;
+  A->result = (uint32_t *)result;
+}
+}  // namespace
+
+fx_status fx_map_import_host(fx_ctx *c, fx_map *m, const void *src, size_t bytes) {
+  FX_TRY(map_call_check(c, m, src != nullptr));
+  FX_TRY(fx_map_snapshot_check(src, bytes, m->a.cap, m->a.max_carry));
+  FX_HIP(hipSetDevice(c->device));
+  FX_TRY(snap_stage(c, src, bytes));
   const uint8_t *p = c->snap_h;
   uint32_t n, r;
   memcpy(&n, p + 16, 4), memcpy(&r, p + 20, 4);
@@ -2381,6 +2398,47 @@ fx_status fx_map_import_host(fx_ctx *c, fx_map *m, const void *src, size_t bytes
     FX_HIP(hipMemcpyAsync(m->a.carry_kp, p + L.o_kp, (size_t)r * 16, hipMemcpyHostToDevice, c->stream));
   }
   FX_HIP(hipEventRecord(c->snap_ev, c->stream));
+  return FX_OK;
+}
+
+fx_status fx_map_append(fx_ctx *c, fx_map *dst, fx_map *src, fx_map_append_result *result) {
+  if (!c || !dst || !src) return fail(FX_ERR_INVALID_ARG, "null argument");
+  if (dst == src) return fail(FX_ERR_INVALID_ARG, "dst and src are the same map");
+  FX_TRY(map_call_check(c, dst));
+  if (src->ctx != c) return fail(FX_ERR_INVALID_ARG, "the source map belongs to another context (go through the snapshot: fx_map_append_host)");
+  if (((uintptr_t)result % 4) != 0) return fail(FX_ERR_INVALID_ARG, "the result must be 4-byte aligned");
+  FX_HIP(hipSetDevice(c->device));
+  FxMapAppendArgs A{};
+  append_target(&A, dst, result);
+  A.src.header = src->a.header, A.src.records = src->a.records, A.src.acc = src->a.acc, A.src.alias = src->a.alias, A.src.carry = src->a.carry,
+  A.src.carry_kp = src->a.carry_kp;
+  A.src_cap = src->a.cap, A.src_max_carry = src->a.max_carry;
+  FX_MAP_RUN(fxk_map_append, "map append scratch");
+  return FX_OK;
+}
+
+fx_status fx_map_append_host(fx_ctx *c, fx_map *dst, const void *src, size_t bytes, fx_map_append_result *result) {
+  FX_TRY(map_call_check(c, dst, src != nullptr));
+  if (((uintptr_t)result % 4) != 0) return fail(FX_ERR_INVALID_ARG, "the result must be 4-byte aligned");
+  FX_TRY(fx_map_snapshot_check(src, bytes, dst->a.cap, 0xffffffffu));
+  FX_HIP(hipSetDevice(c->device));
+  FxMapAppendArgs A{};
+  append_target(&A, dst, result);
+  A.stage_bytes = bytes;
+  FX_TRY(c->merge_scratch.reserve(c, fxk_map_append_scratch(&A, nullptr), "map append scratch"));
+  (void)fxk_map_append_scratch(&A, c->merge_scratch.d);
+  FX_TRY(snap_stage(c, src, bytes));
+  uint32_t n, r;
+  memcpy(&n, c->snap_h + 16, 4), memcpy(&r, c->snap_h + 20, 4);
+  const SnapLayout L = snap_layout(n, r);
+  // the sections start 16-byte aligned in the block and the block does in the scratch: the kernels read them as vectors
+  FX_HIP(hipMemcpyAsync(A.stage, c->snap_h, bytes, hipMemcpyHostToDevice, c->stream));
+  FX_HIP(hipEventRecord(c->snap_ev, c->stream));
+  A.src.header = A.stage + L.o_hdr, A.src.records = A.stage + L.o_rec, A.src.acc = (const double *)(A.stage + L.o_acc);
+  A.src.alias = (const int32_t *)(A.stage + L.o_alias), A.src.carry = (const int32_t *)(A.stage + L.o_carry);
+  A.src.carry_kp = (const uint4 *)(A.stage + L.o_kp);
+  A.src_cap = n, A.src_max_carry = r;
+  FX_HIP(fxk_map_append(c->stream, A));
   return FX_OK;
 }
 

@@ -335,6 +335,33 @@ struct FxMapCompactArgs {
   uint32_t *bsum;               // [2][blocks of landmarks]: the block's kept landmarks / dropped live observations, then their prefix
   uint4 *stage_rec, *stage_acc; // [cap][3], [cap][4]: the kept records and sums at their new ids, before they are copied back
 };
+// fx_map_append, fx_map_append_host (csrc/fx_map_append.hip): a launch set's arguments.  The source as the kernels read it is six
+// pointers: a map's own buffers, or the sections of a snapshot staged in the context's scratch; the two look the same.
+#define FX_MAP_APPEND_ST_WORDS 8  // 0 the result's flags, 1 N: the id base, 2 the scan base, 3 the segment base, 4 landmarks to move,
+                                  // 5 carry rows to move (4 and 5: 0 on a refusal)
+struct FxMapSrcView {
+  const void *header;           // fx_map_header
+  const void *records;          // fx_map_landmark [n_landmarks]
+  const double *acc;            // [n_landmarks][FX_MAP_ACC]
+  const int32_t *alias;         // [n_landmarks]
+  const int32_t *carry;         // [carry_rows]
+  const uint4 *carry_kp;        // [carry_rows]
+};
+struct FxMapAppendArgs {
+  void *header;                 // the target: fx_map_header
+  void *records;                // fx_map_landmark [cap]
+  double *acc;                  // [cap][FX_MAP_ACC]
+  int32_t *alias;               // [cap]
+  int32_t *carry;               // [max_carry]
+  uint4 *carry_kp;              // [max_carry]
+  uint32_t cap, max_carry;
+  FxMapSrcView src;
+  uint32_t src_cap, src_max_carry;  // landmarks and carry rows the source's pointers hold at least: its header's counts are clipped to them
+  uint32_t *result;             // fx_map_append_result or null
+  size_t stage_bytes;           // bytes of a snapshot to stage (0: the source is a map)
+  uint8_t *stage;               // [stage_bytes] of the context's scratch
+  uint32_t *st;                 // [FX_MAP_APPEND_ST_WORDS]
+};
 // What fx_map_join_segments and fx_map_close_loop share (csrc/fx_map_assoc.h): the association of one set of landmarks with another
 // under a prior and the consensus over it.  G describes the grid over the map (its gate is the search distance; the merge's
 // per-landmark arrays are null) and carries the map's own memory; the last group is the context's scratch, sized by the map's

@@ -643,7 +643,8 @@ fx_status fx_track_landmarks(fx_ctx *ctx,
  * scan in the map without a prior and fx_map_localize refines it, which gives the closure its prior.  The equality with one batch of the whole run
  * holds for min_obs == 2; with a larger min_obs a track that a batch edge cuts into pieces that are each too short is missed.
  * n_obs and n_needed are 32-bit counts.  FX_MAP_FULL is sticky and n_needed only rises under fx_map_update; fx_map_compact (below)
- * gives the room of absorbed and let-go landmarks back, fx_map_export_host / fx_map_import_host carry a map to another context.
+ * gives the room of absorbed and let-go landmarks back, fx_map_export_host / fx_map_import_host carry a map to another context,
+ * and fx_map_append / fx_map_append_host (below) put a second map behind this one instead of replacing it.
  * fx_map_create allocates all of the map's buffers and enqueues its first reset; fx_map_reset enqueues the state of a fresh map;
  * fx_map_update's scratch is a context-owned buffer that grows when a call has a larger max_landmarks.  fx_map_get returns the
  * device addresses of the header and the records (stable for the map's life; read them in stream order); fx_map_read_header and
@@ -973,7 +974,8 @@ fx_status fx_map_relocalize(fx_ctx *ctx, fx_map *map,
  * unchanged and nothing is enqueued.  On success it enqueues, on the stream, a reset (alias -1, state words 0) and the copies of
  * the sections; the bytes are staged in context-owned pinned memory before the call returns, so src_host may be freed at once.
  * Afterwards every call (fx_map_update with overlap, merge, localize, compact, export) behaves bit for bit as on the source map;
- * the target may be larger than the source and may live on another context or device.  Export and import also return
+ * the target may be larger than the source and may live on another context or device.  The import REPLACES the target; to keep
+ * the target's landmarks and add the snapshot's behind them use fx_map_append_host (below).  Export and import also return
  * FX_ERR_INVALID_ARG for a NULL ctx, map or src_host, dst_host == NULL with capacity != 0, and a map of another context.  New in
  * 0.7 (added symbols only). */
 typedef struct fx_map_compact_options {
@@ -987,6 +989,63 @@ fx_status fx_map_compact(fx_ctx *ctx, fx_map *map, const fx_map_compact_options 
 fx_status fx_map_export_host(fx_ctx *ctx, fx_map *map, void *dst_host, size_t capacity, size_t *bytes_out);
 fx_status fx_map_import_host(fx_ctx *ctx, fx_map *map, const void *src_host, size_t bytes);
 fx_status fx_map_snapshot_check(const void *src_host, size_t bytes, uint32_t max_landmarks, uint32_t max_carry_rows); /* Host only */
+
+/* ---- Appending one map to another: two maps in two frames become one map with two sets of segments ----
+ * Every call above works on ONE map; fx_map_import_host replaces its target and fx_map_update grows a map only from the run it is
+ * fed.  fx_map_append puts a second, finished map (another vehicle's, another session's, another rank's, or an old map a live run
+ * adopts) behind the first: `dst` afterwards is what it would have been had the source's run been FED to it, its batches through
+ * fx_map_update, the first of them without FX_MAP_OVERLAP.  For a source that was only updated this holds bit for bit (it is
+ * fx_map_update's own promise that the cut of a run into batches does not show); once the source has been merged, joined or closed
+ * the clauses below are the definition.  Both calls are enqueued on the context's stream: no host synchronisation, no allocation in
+ * the steady state (the scratch is the context-owned buffer fx_map_merge uses, grown as needed).  No floating-point operation
+ * occurs: records and sums move as bytes and only integers are patched, as in fx_map_compact.  The source is only read and every
+ * byte of it stays; dst's addresses (fx_map_get, fx_map_get_alias) stay what they were.
+ * ONE CALL, with the two maps as they are when the call runs on the stream.  N, Sd and Gd are dst's header.n_landmarks, scans and
+ * segments; M and r are the source's header.n_landmarks and carry_rows.
+ * Refusals on the device, each of which leaves dst bit for bit unchanged and reports its flag (more than one may be set),
+ * appended = 0 and the three bases as they would have been:
+ *   FX_APPEND_EMPTY       the source's header.scans == 0: there is no run to append.
+ *   FX_APPEND_OVERFLOWED  n_needed > n_landmarks in either map: ids would be numbered past a hole (the snapshot check's reason);
+ *                         fx_map_compact first.
+ *   FX_APPEND_NO_ROOM     N + M > dst's max_landmarks, in uint64.
+ *   FX_APPEND_TOO_LONG    the two maps' scans, segments, batches or n_obs sum to more than 2^32 - 1, in uint64.
+ * Otherwise FX_APPEND_APPLIED:
+ * Landmarks: the source's landmark i goes to id N + i.  Its 48-byte record and its 8 accumulator doubles are copied byte for byte
+ * except three integer fields: first_scan += Sd, last_scan += Sd, segment += Gd.  Its flags, n_obs, doubles and rms_xy keep their
+ * bits.  alias[N + i] = the source's alias[i] >= 0 ? alias[i] + N : -1.  Every landmark and every alias word of dst below N keeps
+ * every byte.
+ * Carry: when r <= dst's max_carry_rows, carry[j] = the source's carry[j] >= 0 ? carry[j] + N : -1 for j < r, the carry scan's
+ * rows are the source's and carry_rows = r.  Otherwise carry_rows = 0 and FX_APPEND_CARRY_DROPPED is set: fx_map_update's own rule
+ * for a last scan that does not fit.  dst's former carry is gone either way: its run has ended.
+ * header: n_landmarks = n_needed = N + M; n_obs, scans, batches and segments are the sums of the two maps' values; flags is the OR
+ * of the two maps' flags; last_joined, last_new and last_pose are the source's.
+ * result (when given), 32 B: id_base = N, scan_base = Sd, segment_base = Gd, appended = M (0 on a refusal), flags = FX_APPEND_*,
+ * carry_rows = dst's header.carry_rows after the call, two reserved words 0.  A caller adds the bases to the ids, global scan
+ * numbers and segment labels the source handed out earlier: map_id_of_row arrays, first_global_scan of
+ * fx_map_loop_correct_poses, opt.segment.
+ * FX_ERR_INVALID_ARG with the reason in fx_last_error(), nothing launched, no byte touched: a NULL ctx, dst, src or src_host;
+ * dst == src; a map of another context (for another context or device go through the snapshot); result_device not 4-byte aligned.
+ * fx_map_append_host takes the source as a snapshot (fx_map_export_host's bytes).  It runs fx_map_snapshot_check against dst's
+ * max_landmarks with no bound on the carry rows and passes its status on; then it stages the bytes in the context's pinned staging
+ * as fx_map_import_host does (src_host may be freed at once), copies them into the scratch on the stream and runs the same launch
+ * set on the staged sections: one definition and one set of kernels serve both entry points.
+ * Limits: nothing is re-framed.  The source's landmarks stay in the source's frame under new segment labels; to bring them into
+ * dst's frame: fx_map_find_loop (segment = a source label + segment_base, target_segment = a dst label, recent_scans =
+ * 0xffffffff: every landmark of the segment is a query), fx_map_join_segments with prior_device = the find's result,
+ * fx_map_merge with a max_gap_scans that covers both runs, fx_map_compact.  After the call the live run is the source's: its next
+ * fx_map_update with FX_MAP_OVERLAP is accepted and continues its landmarks under their new ids.  New in 0.7 (added symbols only). */
+#define FX_APPEND_APPLIED 0x1u        /* dst was changed: the source's landmarks, carry and counts are in it */
+#define FX_APPEND_CARRY_DROPPED 0x2u  /* applied, but the source's carry scan has more rows than dst's max_carry_rows: carry_rows = 0 */
+#define FX_APPEND_EMPTY 0x4u          /* refused: the source has seen no scan */
+#define FX_APPEND_OVERFLOWED 0x8u     /* refused: n_needed > n_landmarks in one of the maps */
+#define FX_APPEND_NO_ROOM 0x10u       /* refused: N + M > dst's max_landmarks */
+#define FX_APPEND_TOO_LONG 0x20u      /* refused: a 32-bit count of the header would wrap */
+typedef struct fx_map_append_result {  /* 32 B */
+  uint32_t id_base, scan_base, segment_base, appended, flags, carry_rows, reserved[2];
+} fx_map_append_result;
+fx_status fx_map_append(fx_ctx *ctx, fx_map *dst, fx_map *src, fx_map_append_result *result_device /* or NULL */);
+fx_status fx_map_append_host(fx_ctx *ctx, fx_map *dst, const void *src_host, size_t bytes,
+                             fx_map_append_result *result_device /* or NULL */);
 
 /* ---- Joining two segments of the map: one frame again after a bad link ----
  * fx_track_landmarks holds the pose over an unusable link and starts a new segment; fx_map_update numbers it globally, and from

@@ -61,6 +61,15 @@ nearest to a random position, moved by a drift of 0.13 rad and 7.8 m with 1 cm o
 fx_map_find_loop with default options (40 queries, 16 seeds), and on the same map fx_map_relocalize of one scan holding the same 40
 points as float keypoints (any segment: it sees both copies), whose walk the new call shares.  Reported per size: the medians, their
 ratio and the result.  No target is set.
+  timeout -k 10 600 python tools/map_times.py --append [--sizes 1000,100000,1000000] [--warmup 1] [--repeats 5] [--out profiles/map_append.md]
+
+times fx_map_append: for every size N a map of N landmarks (every landmark live, a carry scan of 16 rows) taken in as a snapshot
+into a target of 2 N landmarks and into a source of N.  Every repeat imports the snapshot into the target (timed: fx_map_import_host,
+the reset and the six copies from pinned memory), appends the source map (timed: fx_map_append of M = N landmarks into a map of N),
+imports again, appends the same snapshot from the host (timed: fx_map_append_host, the copy of the staged block and the same
+launches; the call's wall time with the staging memcpy is reported beside it) and copies 116 N bytes from one device buffer to
+another with one hipMemcpyAsync (timed: what moving the bytes costs).  One pair of HIP events around each.  Reported per size: the
+medians, the append over the plain copy, and the requirement the merge and the compaction meet: time(10^6) <= 15 x time(10^5).
 """
 import argparse
 import ctypes as C
@@ -559,6 +568,111 @@ def main_find_loop(a):
             f.write(s + "\n")
 
 
+def append_case(n, rng, r=16):
+    """The snapshot of a one-segment map of n live landmarks of two observations with a carry scan of r rows, built as arrays (the
+    layout is capi.map_snapshot_pack's)."""
+    import struct
+    xyz = np.concatenate([rng.uniform(0.0, (n * 250.0) ** 0.5, (n, 2)), rng.uniform(0.0, 2.0, (n, 1))], axis=1).astype(np.float32).astype(np.float64)
+    rec = np.zeros(n, capi.MAP_LANDMARK_DTYPE)
+    rec["x"], rec["y"], rec["z"], rec["n_obs"] = xyz[:, 0], xyz[:, 1], xyz[:, 2], 2
+    rec["first_scan"] = np.arange(n) % 4
+    rec["last_scan"] = rec["first_scan"] + 1
+    acc = np.concatenate([2.0 * xyz, xyz[:, :2], np.zeros((n, 3))], axis=1)
+    r = min(r, n)
+    H = dict(n_landmarks=n, n_needed=n, n_obs=2 * n, scans=5, batches=1, segments=1, flags=0, carry_rows=r, last_joined=0, last_new=n)
+    hdr = struct.pack("<10I", *(H[k] for k in capi.MAP_HEADER_FIELDS)) + struct.pack("<5d2I", 1.0, 0.0, 0.0, 0.0, 0.0, 0, 0)
+    body = [capi._pad16(hdr), rec.tobytes(), acc.astype("<f8").tobytes(), capi._pad16(np.full(n, -1, "<i4").tobytes()),
+            capi._pad16(np.arange(n - r, n, dtype="<i4").tobytes()), rng.integers(0, 1 << 32, (r, 4), dtype=np.uint64).astype("<u4").tobytes()]
+    total = capi.FX_MAP_SNAPSHOT_HEADER_BYTES + sum(len(b) for b in body)
+    head = struct.pack("<10IQ", capi.FX_MAP_SNAPSHOT_MAGIC, capi.FX_MAP_SNAPSHOT_FORMAT, capi.FX_HEADER_VERSION, capi.FX_MAP_SNAPSHOT_HEADER_BYTES, n, r,
+                       C.sizeof(capi.FxMapHeader), C.sizeof(capi.FxMapLandmark), capi.FX_MAP_ACC, 0, total)
+    return head + b"\0" * (capi.FX_MAP_SNAPSHOT_HEADER_BYTES - len(head)) + b"".join(body)
+
+
+def measure_append(ctx, n, warmup, repeats):
+    import time
+    import torch
+    blob = append_case(n, np.random.default_rng(n))
+    dst, src = ctx.map_create(2 * n, 16), ctx.map_create(n, 16)
+    src.import_state(blob)
+    res = torch.zeros((8,), dtype=torch.int32, device="cuda")
+    plain = torch.empty((2, 116 * n), dtype=torch.uint8, device="cuda")
+    stream = torch.cuda.ExternalStream(ctx.stream_ptr())
+    torch.cuda.synchronize()
+    t = {"import_ms": [], "append_ms": [], "import2_ms": [], "append_host_ms": [], "copy_ms": []}
+    wall, first = [], None
+    for rep in range(warmup + repeats):
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(10)]
+        e[0].record(stream)
+        dst.import_state(blob)
+        e[1].record(stream), e[2].record(stream)
+        dst.append(src, result=res)
+        e[3].record(stream)
+        ctx.synchronize()
+        got = capi.append_records(res).copy()
+        assert int(got["flags"]) == capi.FX_APPEND_APPLIED and int(got["appended"]) == n == int(got["id_base"]), got
+        state = dst.export_state() if n <= 100000 else None
+        e[4].record(stream)
+        dst.import_state(blob)
+        e[5].record(stream)
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        e[6].record(stream)
+        dst.append_state(blob, result=res)
+        e[7].record(stream)
+        ctx.synchronize()
+        wall.append((time.perf_counter() - t0) * 1e3)
+        assert capi.append_records(res).tobytes() == got.tobytes()
+        if state is not None:
+            assert dst.export_state() == state, "fx_map_append_host and fx_map_append leave the same map"
+        first = got if first is None else first
+        with torch.cuda.stream(stream):
+            e[8].record(stream)
+            plain[1].copy_(plain[0], non_blocking=True)
+            e[9].record(stream)
+        ctx.synchronize()
+        if rep >= warmup:
+            for k, (a, b) in zip(t, ((0, 1), (2, 3), (4, 5), (6, 7), (8, 9))):
+                t[k].append(e[a].elapsed_time(e[b]))
+    dst.close(), src.close()
+    out = {"landmarks": n, "snapshot_bytes": len(blob), "result": {k: int(first[k]) for k in ("id_base", "scan_base", "segment_base", "appended", "flags", "carry_rows")},
+           "append_host_wall_ms": statistics.median(wall[warmup:])}
+    for k, v in t.items():
+        out[k] = statistics.median(v)
+        out[k + "_min_max"] = [min(v), max(v)]
+    return out
+
+
+def main_append(a):
+    sizes = [int(x) for x in a.sizes.split(",")]
+    ctx = capi.Context(capi.params("launch"), capi.limits(2, 1024))
+    rows = [measure_append(ctx, n, a.warmup, a.repeats) for n in sizes]
+    ctx.close()
+    lines = ["# fx_map_append: device times", "",
+             "tools/map_times.py --append: a map of M = N landmarks (all live, 16 carry rows) appended to a map of N; one context, one pair of",
+             f"HIP events around each call, median of {a.repeats} after {a.warmup} warm-up; ms.  append: fx_map_append of the source map; append_host:",
+             "fx_map_append_host of its snapshot (events: the copy of the staged block and the launches; wall: the call and the wait for it,",
+             "the staging memcpy included); import: fx_map_import_host of the same snapshot; copy: one hipMemcpyAsync of 116 N bytes, device to device.",
+             "", "```",
+             f"{'landmarks':>10} {'append':>9} {'append / size before':>21} {'append_host':>12} {'its wall':>9} {'import':>9} {'copy':>9} {'append / copy':>14}"]
+    for k, r in enumerate(rows):
+        ratio = f"{r['append_ms'] / rows[k - 1]['append_ms']:.2f}" if k else "-"
+        lines.append(f"{r['landmarks']:>10} {r['append_ms']:>9.4f} {ratio:>21} {r['append_host_ms']:>12.4f} {r['append_host_wall_ms']:>9.3f} {r['import_ms']:>9.4f} "
+                     f"{r['copy_ms']:>9.4f} {r['append_ms'] / r['copy_ms']:>14.2f}")
+    lines.append("```")
+    by = {r["landmarks"]: r for r in rows}
+    if 100000 in by and 1000000 in by:
+        ratio = by[1000000]["append_ms"] / by[100000]["append_ms"]
+        lines += ["", f"requirement: append(10^6) <= 15 x append(10^5): {ratio:.2f} x, {'met' if ratio <= 15.0 else 'NOT met'}"]
+    s = "\n".join(lines)
+    print(s)
+    print(json.dumps(rows))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(s + "\n")
+
+
 def main_relocalize(a):
     sizes = [int(x) for x in a.sizes.split(",")]
     ctx = capi.Context(capi.params("launch"), capi.limits(2, 1024))
@@ -633,6 +747,7 @@ def main():
     ap.add_argument("--join", action="store_true", help="time fx_map_join_segments on two-segment synthetic maps instead")
     ap.add_argument("--loop", action="store_true", help="time fx_map_close_loop on the synthetic maps taken as one loop instead")
     ap.add_argument("--find-loop", action="store_true", help="time fx_map_find_loop next to fx_map_relocalize on one-segment synthetic maps instead")
+    ap.add_argument("--append", action="store_true", help="time fx_map_append and fx_map_append_host next to fx_map_import_host and a plain copy instead")
     ap.add_argument("--sizes", default="1000,100000,1000000")
     ap.add_argument("--scans", type=int, default=1024)
     ap.add_argument("--batch", type=int, default=128)
@@ -655,6 +770,8 @@ def main():
         return main_loop(a)
     if a.find_loop:
         return main_find_loop(a)
+    if a.append:
+        return main_append(a)
     N = 28800
     ctx = capi.Context(capi.params("launch"), capi.limits(a.batch, N, sparse=True))
     scenes = np.stack([capi.synth_scan(capi.synth_cfg(1000 + b)) for b in range(a.scans)])
