@@ -344,6 +344,14 @@ FIND_DEFAULTS = dict(inlier_dist=0.30, pair_tol=0.30, min_baseline=2.0, max_base
                      min_landmark_obs=2, segment=FX_LOC_LAST_SEGMENT, target_segment=FX_FIND_SAME_SEGMENT, min_loop_scans=256, recent_scans=32)
 
 
+class FxSpliceSource(C.Structure):
+    _fields_ = [("kp_block_device", C.c_void_p), ("max_scans", C.c_uint32), ("max_total_keypoints", C.c_uint32),
+                ("csr_block_device", C.c_void_p), ("max_rows", C.c_uint32), ("capacity", C.c_uint32), ("scan0", C.c_uint32), ("n_scans", C.c_uint32)]
+
+
+FX_SPLICE_LAST_SCAN = 0xffffffff  # scan0: the source's last scan, read on the device
+
+
 class FxTimings(C.Structure):
     _fields_ = [("ms", C.c_float * FX_N_STAGES), ("total_ms", C.c_float), ("k_prep_exec_ms", C.c_float)]
 
@@ -374,7 +382,7 @@ EXPORTS = ("fx_version", "fx_check_abi", "fx_status_str", "fx_last_error", "fx_p
            "fx_map_append", "fx_map_append_host",
            "fx_map_join_options_default", "fx_map_join_segments",
            "fx_map_loop_options_default", "fx_map_close_loop", "fx_map_loop_correct_poses",
-           "fx_map_find_loop_options_default", "fx_map_find_loop",
+           "fx_map_find_loop_options_default", "fx_map_find_loop", "fx_splice_blocks",
            "fx_rotation_from_roll_pitch", "fx_sc3d_tables", "fx_sc3d_xaxis", "fx_synth_cfg_vlp16",
            "fx_synth_scan", "fx_unpack_pointcloud2", "fx_pack_pointxyzi")
 # the header's FX_TEST_HOOKS section: exported by lib/libfx_hip_test.so only
@@ -530,6 +538,8 @@ def load():
     lib.fx_map_find_loop_options_default.argtypes = [C.POINTER(FxMapFindLoopOptions)]
     lib.fx_map_find_loop_options_default.restype = None
     lib.fx_map_find_loop.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(FxMapFindLoopOptions), C.c_void_p, C.c_void_p]
+    lib.fx_splice_blocks.argtypes = [C.c_void_p, C.POINTER(FxSpliceSource), C.POINTER(FxSpliceSource), C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+                                     C.c_uint32, C.c_uint32]
     lib.fx_rotation_from_roll_pitch.argtypes = [C.c_double, C.c_double, _F32P]
     lib.fx_rotation_from_roll_pitch.restype = None
     lib.fx_sc3d_tables.argtypes = [C.c_double, _F32P, _F32P, _F32P, _F32P]
@@ -2164,6 +2174,75 @@ def map_find_loop_reference(state, **options):
     return {"rec": rec, "match_of_landmark": match, "hyp": hyp}
 
 
+# ---- one block pair from scans of two (include/fx.h fx_splice_blocks)
+def _splice_scans(src):
+    """The selected scans of a source ((kp block bytes, max_scans, max_total), (CSR block bytes, max_rows, capacity) or None, scan0,
+    n_scans): a list of (flag word, [(keypoint row as 4 words, its CSR entries (col, val bits) or None: the row does not exist)])."""
+    (kb, max_scans, max_total), csr, scan0, n_scans = src
+    u = np.ascontiguousarray(kb).view(np.uint8).reshape(-1).view(np.uint32)
+    lay = keypoint_block_layout(max_scans, max_total)
+    S, K = min(int(u[0]), max_scans), min(int(u[1]), max_total)
+    off, flags, rows = u[4:5 + max_scans], u[lay.f0:lay.f0 + max_scans], u[4 * lay.k0:4 * lay.n_rows].reshape(-1, 4)
+    if csr is not None:
+        cb, max_rows, cap = csr
+        c = np.ascontiguousarray(cb).view(np.uint8).reshape(-1)
+        o_rp, o_col, o_val, _ = csr_layout(max_rows, cap)
+        exists, rp = min(int(c[:16].view(np.uint32)[3]), max_rows), c[o_rp:o_col].view(np.uint32)
+        col, val = c[o_col:o_val].view(np.uint32), c[o_val:].view(np.uint32)
+    if scan0 == FX_SPLICE_LAST_SCAN:
+        scan0, n_scans = (S - 1, n_scans) if S else (0, 0)
+    out = []
+    for i in range(min(scan0, S), min(scan0 + n_scans, S)):
+        lo, hi = min(int(off[i]), K), min(int(off[i + 1]), K)
+        out.append((int(flags[i]), [(rows[r].copy(), None if csr is None or r >= exists else (col[rp[r]:rp[r + 1]].copy(), val[rp[r]:rp[r + 1]].copy()))
+                                    for r in range(lo, max(lo, hi))]))
+    return out
+
+
+def splice_reference(a, b, dst_kp, dst_csr=None):
+    """The definition of fx_splice_blocks in plain loops: a and b are sources as _splice_scans reads them, dst_kp the destination's
+    (max_scans, max_total_keypoints), dst_csr its (max_rows, capacity) or None.  The virtual batch's scans are built row by row; the
+    two packs' rules are then stated on them.  Returns (the keypoint block as uint8, None or the CSR block's defined words as a dict:
+    "header" u32[4], "row_ptr" u32[max_rows + 1], "col" u32[nnz_stored], "val" u32[nnz_stored], the val words as bits)."""
+    scans = _splice_scans(a) + _splice_scans(b)
+    max_scans, max_total = dst_kp
+    lay = keypoint_block_layout(max_scans, max_total)
+    blk = np.zeros(4 * lay.n_rows, np.uint32)
+    voff = np.concatenate([[0], np.cumsum([len(rows) for _, rows in scans], dtype=np.int64)]).astype(np.int64)
+    n, nb = len(scans), min(len(scans), max_scans)
+    clip = np.minimum(voff, max_total)
+    blk[4:lay.f0] = clip[np.minimum(np.arange(lay.f0 - 4), nb)]
+    for i in range(nb):
+        o0, o1 = int(clip[i]), int(clip[i + 1])
+        blk[lay.f0 + i] = scans[i][0] | (0x4 if o1 - o0 < len(scans[i][1]) else 0)  # FX_FLAG_KP_OVERFLOW
+        for k in range(o1 - o0):
+            blk[4 * (lay.k0 + o0 + k):4 * (lay.k0 + o0 + k) + 4] = scans[i][1][k][0]
+    blk[:4] = (nb, clip[nb], np.bitwise_or.reduce(blk[lay.f0:lay.f0 + nb], initial=0) | (0x4 if n > max_scans else 0), max_total)
+    if dst_csr is None:
+        return blk.view(np.uint8), None
+    max_rows, cap = dst_csr
+    virt = [entries for _, rows in scans for _, entries in rows]
+    row_ptr, cols, vals, stored = [0], [], [], 0
+    for v, e in enumerate(virt):
+        if e is None or v >= max_rows or row_ptr[-1] + len(e[0]) > cap:
+            break
+        row_ptr.append(row_ptr[-1] + len(e[0])), cols.append(e[0]), vals.append(e[1])
+        stored += 1
+    nnz = row_ptr[-1]
+    needed = sum(len(e[0]) for e in virt if e is not None) & 0xffffffff
+    row_ptr = np.array(row_ptr + [nnz] * (max_rows - stored), np.uint32)
+    return blk.view(np.uint8), {"header": np.array([len(virt), nnz, needed, stored], np.uint32), "row_ptr": row_ptr,
+                                "col": np.concatenate(cols + [np.zeros(0, np.uint32)]).astype(np.uint32),
+                                "val": np.concatenate(vals + [np.zeros(0, np.uint32)]).astype(np.uint32)}
+
+
+def splice_kp_offset(off_a, off_b, a=(FX_SPLICE_LAST_SCAN, 1), b=(0, 0xffffffff)):
+    """The kp_offset of the block fx_splice_blocks builds from scans a = (scan0, n_scans) of the batch with h_kp_offset off_a and scans
+    b of the batch with off_b (neither block cut), for pairs_consecutive."""
+    n = [np.diff(np.asarray(o, np.int64))[(max(len(o) - 2, 0) if s == FX_SPLICE_LAST_SCAN else s):][:c] for o, (s, c) in ((off_a, a), (off_b, b))]
+    return np.concatenate([[0], np.cumsum(np.concatenate(n))]).astype(np.uint32)
+
+
 @contextlib.contextmanager
 def _on_stream(stream_ptr, dev):
     """The stream hand-over of every wrapper that enqueues on a context's stream: that stream (stream_ptr, a hipStream_t as an
@@ -2721,6 +2800,33 @@ class Context:
                                               C.c_void_p(lor.data_ptr()), C.c_void_p(obs.data_ptr()), C.c_void_p(lms.data_ptr()), max_landmarks,
                                               C.c_void_p(hdr.data_ptr())))
         return out
+
+    def splice_blocks(self, a, b, dst_kp, dst_csr=None):
+        """fx_splice_blocks: a and b are sources as ((kp tensor, max_scans, max_total_keypoints), (CSR tensor, max_rows, capacity) or
+        None, scan0, n_scans) — scan0 may be FX_SPLICE_LAST_SCAN, n_scans 0xffffffff —, dst_kp the destination keypoint block as
+        (device tensor, max_scans, max_total_keypoints) and dst_csr its CSR block as (torch.uint8 device tensor, max_rows, capacity) or
+        None: keypoints only.  The destination is what the two packs would write for a batch of a's selected scans, then b's
+        (include/fx.h).  Returns (dst_kp, dst_csr).  Stream-correct like match_descriptors; never waits for the stream."""
+        import torch
+        dev = torch.device("cuda", self.device)
+
+        def fits(t, nbytes):
+            if t.device != dev or t.numel() * t.element_size() < nbytes or not t.is_contiguous() or t.data_ptr() % 16:
+                raise ValueError(f"a block must be a contiguous, 16-byte aligned tensor of >= {nbytes} bytes on {dev}")
+            return t.data_ptr()
+        src = []
+        for (kb, scans, total), csr, scan0, n_scans in (a, b):
+            s = FxSpliceSource(fits(kb, int(self.lib.fx_keypoint_block_bytes(int(scans), int(total)))), int(scans), int(total), None, 0, 0,
+                               int(scan0) & 0xffffffff, int(n_scans) & 0xffffffff)
+            if csr is not None:
+                s.csr_block_device, s.max_rows, s.capacity = fits(csr[0], int(self.lib.fx_descriptor_csr_bytes(int(csr[1]), int(csr[2])))), int(csr[1]), int(csr[2])
+            src.append(s)
+        kp_ptr = fits(dst_kp[0], int(self.lib.fx_keypoint_block_bytes(int(dst_kp[1]), int(dst_kp[2]))))
+        csr_ptr, rows, cap = (fits(dst_csr[0], int(self.lib.fx_descriptor_csr_bytes(int(dst_csr[1]), int(dst_csr[2])))), int(dst_csr[1]), int(dst_csr[2])) if dst_csr is not None else (None, 0, 0)
+        with _on_stream(self.stream_ptr(), dev):
+            check(self.lib.fx_splice_blocks(self.handle, C.byref(src[0]), C.byref(src[1]), C.c_void_p(kp_ptr), int(dst_kp[1]), int(dst_kp[2]),
+                                            C.c_void_p(csr_ptr), rows, cap))
+        return dst_kp, dst_csr
 
     def map_create(self, max_landmarks, max_carry_rows):
         """fx_map_create: a persistent landmark map owned by this context (Map.update after every track_landmarks)."""

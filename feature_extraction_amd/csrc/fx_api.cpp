@@ -106,6 +106,7 @@ size_t fxk_map_join_scratch(FxMapJoinArgs *A, uint8_t *base);
 hipError_t fxk_map_loop(hipStream_t s, const FxMapLoopArgs &A);
 hipError_t fxk_map_loop_poses(hipStream_t s, const void *result, void *poses, uint32_t first, uint32_t n);
 size_t fxk_map_loop_scratch(FxMapLoopArgs *A, uint8_t *base);
+hipError_t fxk_splice(hipStream_t s, const FxSpliceArgs &A, uint32_t max_grid);
 #ifdef FX_TEST_HOOKS
 void fxk_test_sort_replay(hipStream_t s, const uint32_t *sizes, uint32_t n_seq, uint32_t n, uint32_t *perm);
 void fxk_test_elevation(hipStream_t s, const float *xyz, uint32_t n, const double *tab, float *fast, uint8_t *ok, float *exact);
@@ -281,6 +282,7 @@ struct fx_ctx {
                              // fx_map_append: the state words; fx_map_append_host: the snapshot's bytes before them;
                              // fx_map_join_segments, fx_map_close_loop: the grid, each query's target and distance, the list of
                              // correspondences
+  DevScratch splice_scratch; // fx_splice_blocks: the plan words
   // fx_map_import_host, fx_map_append_host: the snapshot's bytes, pinned, until the copies enqueued from them are done (snap_ev)
   uint8_t *snap_h = nullptr;
   size_t snap_bytes = 0;
@@ -1162,7 +1164,7 @@ void fx_destroy(fx_ctx *c) {
   if (c->d_csr) (void)hipFree(c->d_csr);
   if (c->h_csr) (void)hipHostFree(c->h_csr);
   c->match_stage.release(), c->match_scratch.release(), c->reg_stage.release(), c->track_scratch.release(), c->map_scratch.release(),
-      c->merge_scratch.release();
+      c->merge_scratch.release(), c->splice_scratch.release();
   if (c->snap_h) (void)hipHostFree(c->snap_h);
   if (c->snap_ev) (void)hipEventDestroy(c->snap_ev);
   for (int i = 0; i < kMetaSlots; ++i)
@@ -1722,6 +1724,43 @@ fx_status fx_pack_descriptors_csr(fx_ctx *c, void *dst_device, uint32_t max_rows
   if (!csr_pool_fits(c->lim)) return fail(FX_ERR_TOO_LARGE, "max_total_keypoints * 1989 exceeds 2^32 - 1");
   FX_HIP(hipSetDevice(c->device));
   return enqueue_csr(c, c->stream, dst_device, max_rows, capacity);
+}
+
+fx_status fx_splice_blocks(fx_ctx *c, const fx_splice_source *a, const fx_splice_source *b, void *dst_kp, uint32_t dst_max_scans,
+                           uint32_t dst_max_total, void *dst_csr, uint32_t dst_max_rows, uint32_t dst_cap) {
+  if (!c || !a || !b || !a->kp_block_device || !b->kp_block_device || !dst_kp) return fail(FX_ERR_INVALID_ARG, "null argument");
+  if (dst_csr && (!a->csr_block_device || !b->csr_block_device))
+    return fail(FX_ERR_INVALID_ARG, "a destination CSR block needs both sources' CSR blocks");
+  if (!a->max_scans || !b->max_scans || !dst_max_scans) return fail(FX_ERR_INVALID_ARG, "a keypoint block of no scans");
+  // the blocks' byte ranges, as their layouts give them; the sources' CSR blocks are not looked at without a destination for them
+  struct Range {
+    const void *p;
+    size_t bytes;
+  };
+  const Range src[4] = {{a->kp_block_device, fxk_kp_block_bytes(a->max_scans, a->max_total_keypoints)},
+                        {b->kp_block_device, fxk_kp_block_bytes(b->max_scans, b->max_total_keypoints)},
+                        {dst_csr ? a->csr_block_device : nullptr, fxk_csr_bytes(a->max_rows, a->capacity)},
+                        {dst_csr ? b->csr_block_device : nullptr, fxk_csr_bytes(b->max_rows, b->capacity)}};
+  const Range dst[2] = {{dst_kp, fxk_kp_block_bytes(dst_max_scans, dst_max_total)}, {dst_csr, fxk_csr_bytes(dst_max_rows, dst_cap)}};
+  for (const Range &r : {src[0], src[1], src[2], src[3], dst[0], dst[1]})
+    if (((uintptr_t)r.p % 16) != 0) return fail(FX_ERR_INVALID_ARG, "blocks must be 16-byte aligned");
+  for (const Range &d : dst)
+    for (const Range &s : src)
+      if (d.p && s.p && (uintptr_t)d.p < (uintptr_t)s.p + s.bytes && (uintptr_t)s.p < (uintptr_t)d.p + d.bytes)
+        return fail(FX_ERR_INVALID_ARG, "a destination block overlaps a source block");
+  FX_HIP(hipSetDevice(c->device));
+  FX_TRY(c->splice_scratch.reserve(c, FX_SPLICE_PLAN_WORDS * sizeof(uint32_t), "splice scratch"));
+  auto view = [&](const fx_splice_source &x) {
+    return FxSpliceSrc{(const uint32_t *)x.kp_block_device, x.max_scans, x.max_total_keypoints, dst_csr ? (const uint32_t *)x.csr_block_device : nullptr,
+                       x.max_rows, x.capacity, x.scan0, x.n_scans};
+  };
+  FxSpliceArgs A{};
+  A.a = view(*a), A.b = view(*b);
+  A.dst_kp = (uint32_t *)dst_kp, A.dst_max_scans = dst_max_scans, A.dst_max_total = dst_max_total;
+  A.dst_csr = (uint32_t *)dst_csr, A.dst_max_rows = dst_max_rows, A.dst_cap = dst_cap;
+  A.plan = (uint32_t *)c->splice_scratch.d;
+  FX_HIP(fxk_splice(c->stream, A, 8u * (uint32_t)c->n_cu));
+  return FX_OK;
 }
 
 fx_status fx_get_descriptors_csr(fx_ctx *c, fx_descriptor_csr_view *out) {

@@ -421,6 +421,24 @@ struct FxMapFindLoopArgs {
   FxRelocPartial *partial;      // [max_seeds][chunks]
   FxRelocWinner *win;           // [1]
 };
+// fx_splice_blocks (csrc/fx_splice.hip): a launch set's arguments.  A source is fx.h's fx_splice_source with its blocks as words; the
+// plan words are the context's scratch.
+#define FX_SPLICE_PLAN_WORDS 32  // what k_splice_plan resolves from the two sources' headers for the launch behind it (fx_splice.hip names them)
+struct FxSpliceSrc {
+  const uint32_t *kp;           // keypoint block (include/fx.h fx_pack_keypoint_block)
+  uint32_t max_scans, max_total;
+  const uint32_t *csr;          // CSR block (include/fx.h fx_descriptor_csr_bytes); not read when the destination has none
+  uint32_t max_rows, cap;
+  uint32_t scan0, n_scans;
+};
+struct FxSpliceArgs {
+  FxSpliceSrc a, b;
+  uint32_t *dst_kp;
+  uint32_t dst_max_scans, dst_max_total;
+  uint32_t *dst_csr;            // or null: keypoints only
+  uint32_t dst_max_rows, dst_cap;
+  uint32_t *plan;               // [FX_SPLICE_PLAN_WORDS]
+};
 #define FX_TRACK_NONE 0xffffffffu
 #define FX_N_HINTS 8   // tier_hint[]: 0 / 1 rings handed to the second run tier / the workgroup tier (largest XCD class), 2 big merges, 3 huge merges, 4 dense rows, 5 dense support points, 6 scans k_front handed to k_front_redo, 7 scans handed to the slow tier (k_slow)
 #define FX_CNT_QPOOL 32   // counters[32]: entries of the dense tier's query pool in use

@@ -1376,6 +1376,48 @@ void fx_map_find_loop_options_default(fx_map_find_loop_options *o);
 fx_status fx_map_find_loop(fx_ctx *ctx, fx_map *map, const fx_map_find_loop_options *opt /* NULL: defaults */,
     fx_map_loop_candidate *result_device, int32_t *match_of_landmark_device /* [max_landmarks] or NULL */);
 
+/* ---- Splicing two batches' blocks: every scan processed once ----
+ * fx_map_update continues tracks across a one-scan overlap: batch k + 1 must begin with the scan batch k ended with.  That scan's
+ * keypoints are rows of batch k's keypoint block and its descriptors rows of batch k's CSR block, and a scan's result does not
+ * depend on its batch (the map's bitwise overlap check rests on that), so the scan need not go through fx_process_batch again.
+ * fx_splice_blocks builds one block pair from scans of two existing block pairs: the destination is what fx_pack_keypoint_block
+ * and fx_pack_descriptors_csr would write for a batch of exactly those scans.  Match, register, track and fx_map_update run on it
+ * unchanged.  Splicing (previous, FX_SPLICE_LAST_SCAN, 1) with (current, 0, all) is the overlap; (previous, 0, all) with
+ * (current, 0, all) lays two batches side by side for a match across them.
+ * Selection.  For a source X: S = min(its header's scans, max_scans), K = min(its header's keypoints stored,
+ * max_total_keypoints).  scan0 == FX_SPLICE_LAST_SCAN stands for S - 1 and selects nothing in a block of no scans.  The selected
+ * scans are [scan0, min(scan0 + n_scans, S)), computed without 32-bit wrap: n_scans = 0xffffffff means "to the end", a scan0 at or
+ * beyond S selects nothing.  The rows of scan i are [min(kp_offset[i], K), min(kp_offset[i + 1], K)), taken as empty when they do
+ * not increase: a block of garbage is memory-safe and gives an unspecified destination.  Every count is read on the device: the
+ * call reads nothing on the host and does not synchronise.  a and b may be the same block.
+ * The virtual batch is a's selected scans in order, then b's: n scans, each with its rows, its source flag word and its source
+ * CSR rows under the same row numbers.  A source CSR row r exists iff r is below that CSR block's rows_stored.
+ * Keypoint block: byte for byte what fx_pack_keypoint_block writes for a batch of those n scans under (dst_max_scans,
+ * dst_max_total_keypoints).  Row 0 is {min(n, dst_max_scans), total, OR of the written flags, dst_max_total_keypoints}; the
+ * offsets are clipped to dst_max_total_keypoints and repeat the total beyond the batch; flags beyond the batch are 0; keypoint
+ * rows past the total are zero.  FX_FLAG_KP_OVERFLOW is set on every scan that holds fewer rows in dst than in its source, and
+ * in row 0; it is also set in row 0 when n > dst_max_scans.  All fx_keypoint_block_bytes bytes are written.
+ * CSR block (dst_csr_block_device, given only together with both sources' CSR blocks): rows is the number of virtual rows of all
+ * n scans; as in the pack it is not clipped by dst_max_scans or dst_max_total_keypoints.  Virtual row v is stored iff every row
+ * u <= v exists in its source, has u < dst_max_rows and a cumulative end <= dst_capacity.  row_ptr[0] = 0, the ends of the
+ * stored rows follow, the entries after them up to dst_max_rows repeat nnz_stored.  nnz_needed is the sum over all virtual rows
+ * that exist in their source: a lower bound when a source was itself cut.  col and val of the stored rows are copied bit for bit
+ * (-0.0 and any NaN payload included).  Nothing is written at or beyond nnz_stored, or in the sections' padding.
+ * FX_ERR_INVALID_ARG with the reason in fx_last_error(), nothing launched, no byte touched: a NULL ctx, source or dst keypoint
+ * block; a dst CSR block without both sources' CSR blocks; a block that is not 16-byte aligned; a max_scans of 0; a dst block
+ * whose byte range (fx_keypoint_block_bytes / fx_descriptor_csr_bytes of its layout) overlaps a source block's.
+ * Enqueued on the context's stream: two launches, no allocation in the steady state (the plan words live in a context-owned
+ * scratch that grows), integer operations only, the same bytes from run to run.  New in 0.7 (added symbols only). */
+#define FX_SPLICE_LAST_SCAN 0xffffffffu  /* scan0: the source's last scan (scans - 1, read on the device); nothing in a block of no scans */
+typedef struct fx_splice_source {
+  const void *kp_block_device;  uint32_t max_scans, max_total_keypoints;   /* layout as given to fx_pack_keypoint_block */
+  const void *csr_block_device; uint32_t max_rows, capacity;               /* layout as given to fx_pack_descriptors_csr; ignored when the dst CSR is NULL */
+  uint32_t scan0, n_scans;                                                 /* scans [scan0, scan0 + n_scans) of this source, clipped */
+} fx_splice_source;
+fx_status fx_splice_blocks(fx_ctx *ctx, const fx_splice_source *a, const fx_splice_source *b,
+    void *dst_kp_block_device, uint32_t dst_max_scans, uint32_t dst_max_total_keypoints,
+    void *dst_csr_block_device /* or NULL: keypoints only */, uint32_t dst_max_rows, uint32_t dst_capacity);
+
 /* Rotation matrix of rotateCloud (ref: node.cpp:161-164): R = Ry(pitch)*Rx(roll)
  * through Eigen's AngleAxisf -> Quaternionf -> toRotationMatrix, all float. Host only. */
 void fx_rotation_from_roll_pitch(double roll, double pitch, float R[9]);

@@ -70,6 +70,14 @@ imports again, appends the same snapshot from the host (timed: fx_map_append_hos
 launches; the call's wall time with the staging memcpy is reported beside it) and copies 116 N bytes from one device buffer to
 another with one hipMemcpyAsync (timed: what moving the bytes costs).  One pair of HIP events around each.  Reported per size: the
 medians, the append over the plain copy, and the requirement the merge and the compaction meet: time(10^6) <= 15 x time(10^5).
+  timeout -k 10 600 python tools/map_times.py --splice [--steps 200] [--warmup 1] [--repeats 5] [--out profiles/splice.md]
+
+times fx_splice_blocks.  (1) One new scan a call, host to host (time.perf_counter around the calls and the wait for the stream),
+the two routes to a block pair of [the scan before, the new scan] alternating over --steps VLP-16 scans resident on the device, one
+context of two scans: `twice`, fx_process_batch of both scans and the two packs; `once`, fx_process_batch of the new scan, the two
+packs and the splice behind the last scan of the block pair before.  Medians; the two routes' blocks are compared at every step.
+(2) 1 + 1023 scans: synthetic block pairs (54 rows a scan, 40 entries a row), the splice of (previous, last, 1) with (current, 0,
+1023) between one pair of HIP events, alternating with one hipMemcpyAsync, device to device, of the bytes the splice defines.
 """
 import argparse
 import ctypes as C
@@ -673,6 +681,145 @@ def main_append(a):
             f.write(s + "\n")
 
 
+def splice_source(kp, csr, scan0, n_scans):
+    """An fx_splice_source from (kp tensor, max_scans, max_total) and (CSR tensor, max_rows, capacity)."""
+    return capi.FxSpliceSource(kp[0].data_ptr(), kp[1], kp[2], csr[0].data_ptr(), csr[1], csr[2], scan0, n_scans)
+
+
+def measure_splice_one_scan(steps, warmup):
+    """One new scan a call: `twice` against `once`, alternating, host to host."""
+    import time
+    import torch
+    N = 28800
+    ctx = capi.Context(capi.params("launch"), capi.limits(2, N, sparse=True))
+    dev = torch.from_numpy(np.stack([capi.synth_scan(capi.synth_cfg(1000 + b)) for b in range(steps + 1)])).cuda()
+    S, R = 2, ctx.limits.max_total_keypoints
+    cap = R * 128
+    nk, nc = int(ctx.lib.fx_keypoint_block_bytes(S, R)), int(ctx.lib.fx_descriptor_csr_bytes(R, cap))
+    pair = lambda: ((torch.zeros(nk, dtype=torch.uint8, device="cuda"), S, R), (torch.zeros(nc, dtype=torch.uint8, device="cuda"), R, cap))
+    twice, cur, ring = pair(), pair(), [pair(), pair()]
+    P = C.c_void_p
+
+    def process(first, n):
+        descs = ctx.make_descs([dev.data_ptr() + (first + b) * N * 16 for b in range(n)], [N] * n, 16, 0.02, -0.015)
+        ctx.process_raw(descs, n, capi.FX_IN_DEVICE | capi.FX_OUT_HOST)
+
+    def packs(dst):
+        ctx.pack_keypoint_block(dst[0][0].data_ptr(), S, R)
+        ctx.pack_descriptors_csr(dst[1][0].data_ptr(), R, cap)
+    process(0, 1), packs(ring[0])  # the block pair "before" of step 1: scan 0 alone
+    ctx.synchronize()
+    t_twice, t_once = [], []
+    for k in range(1, steps + 1):
+        prev, dst = ring[(k - 1) % 2], ring[k % 2]
+        t0 = time.perf_counter()
+        process(k - 1, 2), packs(twice)
+        ctx.synchronize()
+        t1 = time.perf_counter()
+        process(k, 1), packs(cur)
+        a, b = splice_source(*prev, capi.FX_SPLICE_LAST_SCAN, 1), splice_source(*cur, 0, 1)
+        capi.check(ctx.lib.fx_splice_blocks(ctx.handle, C.byref(a), C.byref(b), P(dst[0][0].data_ptr()), S, R, P(dst[1][0].data_ptr()), R, cap))
+        ctx.synchronize()
+        t2 = time.perf_counter()
+        if k > warmup:
+            t_twice.append((t1 - t0) * 1e3), t_once.append((t2 - t1) * 1e3)
+        assert torch.equal(twice[0][0], dst[0][0]), f"step {k}: the keypoint blocks of the two routes differ"
+        g, w = capi.csr_parse(dst[1][0].cpu().numpy(), R, cap), capi.csr_parse(twice[1][0].cpu().numpy(), R, cap)
+        assert all(np.array_equal(g[f].view(np.uint32) if f == "val" else g[f], w[f].view(np.uint32) if f == "val" else w[f]) for f in g), f"step {k}: the CSR blocks differ"
+    ctx.close()
+    return {"steps": len(t_twice), "twice_ms": statistics.median(t_twice), "once_ms": statistics.median(t_once),
+            "twice_min_max": [min(t_twice), max(t_twice)], "once_min_max": [min(t_once), max(t_once)]}
+
+
+def splice_blocks_synthetic(rng, scans, rows_a_scan=54, entries_a_row=40):
+    """A block pair of `scans` scans as host arrays, built section by section (no dense rows): (kp bytes, max_scans, max_total), (CSR
+    bytes, max_rows, capacity), the layouts exactly what the content needs."""
+    n = scans * rows_a_scan
+    nnz = n * entries_a_row
+    lay = capi.keypoint_block_layout(scans, n)
+    kp = np.zeros(4 * lay.n_rows, np.uint32)
+    kp[:4] = (scans, n, 0, n)
+    kp[4:lay.f0] = np.minimum(np.arange(lay.f0 - 4), scans) * rows_a_scan
+    kp[4 * lay.k0:] = rng.integers(0, 1 << 32, 4 * n, dtype=np.uint64).astype(np.uint32)
+    o_rp, o_col, o_val, end = capi.csr_layout(n, nnz)
+    csr = np.zeros(end // 4, np.uint32)
+    csr[:4] = (n, nnz, nnz, n)
+    csr[4:4 + n + 1] = np.arange(n + 1) * entries_a_row
+    csr[o_col // 4:o_col // 4 + nnz] = np.tile(np.sort(rng.choice(capi.FX_DESC_FLOATS, entries_a_row, replace=False)), n)
+    csr[o_val // 4:o_val // 4 + nnz] = rng.integers(1, 1 << 32, nnz, dtype=np.uint64).astype(np.uint32)
+    return (kp.view(np.uint8), scans, n), (csr.view(np.uint8), n, nnz)
+
+
+def measure_splice_large(warmup, repeats, scans=1024):
+    """(previous, last, 1) spliced with (current, 0, scans - 1) against one copy of the bytes the splice defines."""
+    import torch
+    rng = np.random.default_rng(scans)
+    ctx = capi.Context(capi.params("launch"), capi.limits(2, 1024))
+    up = lambda blk: (torch.from_numpy(blk[0]).cuda(), blk[1], blk[2])
+    prev, cur = [tuple(up(b) for b in splice_blocks_synthetic(rng, s)) for s in (scans, scans - 1)]
+    whole_h = splice_blocks_synthetic(rng, scans)
+    (_, S, R), (_, _, cap) = whole_h
+    dk = torch.zeros(len(whole_h[0][0]), dtype=torch.uint8, device="cuda")
+    dc = torch.zeros(len(whole_h[1][0]), dtype=torch.uint8, device="cuda")
+    a, b = splice_source(*prev, capi.FX_SPLICE_LAST_SCAN, 1), splice_source(*cur, 0, scans - 1)
+    defined = len(whole_h[0][0]) + 16 + 4 * (R + 1) + 8 * cap
+    plain = torch.empty((2, defined), dtype=torch.uint8, device="cuda")
+    stream = torch.cuda.ExternalStream(ctx.stream_ptr())
+    P = C.c_void_p
+    torch.cuda.synchronize()
+    t_splice, t_copy = [], []
+    for rep in range(warmup + repeats):
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        e[0].record(stream)
+        capi.check(ctx.lib.fx_splice_blocks(ctx.handle, C.byref(a), C.byref(b), P(dk.data_ptr()), S, R, P(dc.data_ptr()), R, cap))
+        e[1].record(stream)
+        with torch.cuda.stream(stream):
+            e[2].record(stream)
+            plain[1].copy_(plain[0], non_blocking=True)
+            e[3].record(stream)
+        ctx.synchronize()
+        if rep >= warmup:
+            t_splice.append(e[0].elapsed_time(e[1])), t_copy.append(e[2].elapsed_time(e[3]))
+    # what was timed is the splice: against the reference's statement of it on the first and the last scans' sections
+    hdr = dc[:16].view(torch.int32).cpu().tolist()
+    assert hdr == [R, cap, cap, R] and dk[:16].view(torch.int32).cpu().tolist() == [S, R, 0, R], (hdr, S, R, cap)
+    ctx.close()
+    return {"scans": scans, "rows": R, "entries": cap, "bytes": defined, "splice_ms": statistics.median(t_splice), "copy_ms": statistics.median(t_copy),
+            "splice_min_max": [min(t_splice), max(t_splice)], "copy_min_max": [min(t_copy), max(t_copy)]}
+
+
+def main_splice(a):
+    one = measure_splice_one_scan(a.steps, max(a.warmup, 4))
+    big = measure_splice_large(a.warmup, a.repeats)
+    lines = ["# fx_splice_blocks: times", "",
+             "tools/map_times.py --splice, one run on one MI355X.", "",
+             "## One new scan a call, host to host", "",
+             f"VLP-16 scans resident on the device, a context of two scans (launch preset, fx_limits_sparse); the two routes alternate over {one['steps']}",
+             "steps, time.perf_counter around the calls and the wait for the stream, medians (min .. max); ms.  twice: fx_process_batch of [the",
+             "scan before, the new scan], fx_pack_keypoint_block, fx_pack_descriptors_csr.  once: fx_process_batch of the new scan, the two",
+             "packs, fx_splice_blocks behind the last scan of the block pair before.  Both with FX_OUT_HOST; the two routes' blocks are equal at",
+             "every step (asserted).", "", "```",
+             f"{'route':>6} {'median':>8} {'min':>8} {'max':>8}",
+             f"{'twice':>6} {one['twice_ms']:>8.4f} {one['twice_min_max'][0]:>8.4f} {one['twice_min_max'][1]:>8.4f}",
+             f"{'once':>6} {one['once_ms']:>8.4f} {one['once_min_max'][0]:>8.4f} {one['once_min_max'][1]:>8.4f}",
+             f"once / twice: {one['once_ms'] / one['twice_ms']:.3f}", "```", "",
+             f"## 1 + {big['scans'] - 1} scans", "",
+             f"Synthetic block pairs (54 rows a scan, 40 entries a row): (previous, last, 1) spliced with (current, 0, {big['scans'] - 1}) into {big['rows']} rows and",
+             f"{big['entries']} entries; one pair of HIP events around the call, alternating with one hipMemcpyAsync, device to device, of the {big['bytes']} bytes the",
+             f"splice defines; median of {a.repeats} after {a.warmup} warm-up (min .. max); ms.", "", "```",
+             f"{'':>7} {'median':>8} {'min':>8} {'max':>8}",
+             f"{'splice':>7} {big['splice_ms']:>8.4f} {big['splice_min_max'][0]:>8.4f} {big['splice_min_max'][1]:>8.4f}",
+             f"{'copy':>7} {big['copy_ms']:>8.4f} {big['copy_min_max'][0]:>8.4f} {big['copy_min_max'][1]:>8.4f}",
+             f"splice / copy: {big['splice_ms'] / big['copy_ms']:.2f}", "```"]
+    s = "\n".join(lines)
+    print(s)
+    print(json.dumps({"one_scan": one, "large": big}))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(s + "\n")
+
+
 def main_relocalize(a):
     sizes = [int(x) for x in a.sizes.split(",")]
     ctx = capi.Context(capi.params("launch"), capi.limits(2, 1024))
@@ -748,6 +895,8 @@ def main():
     ap.add_argument("--loop", action="store_true", help="time fx_map_close_loop on the synthetic maps taken as one loop instead")
     ap.add_argument("--find-loop", action="store_true", help="time fx_map_find_loop next to fx_map_relocalize on one-segment synthetic maps instead")
     ap.add_argument("--append", action="store_true", help="time fx_map_append and fx_map_append_host next to fx_map_import_host and a plain copy instead")
+    ap.add_argument("--splice", action="store_true", help="time fx_splice_blocks instead: one new scan a call against processing two, and 1 + 1023 scans against a plain copy")
+    ap.add_argument("--steps", type=int, default=200, help="--splice: scans of the one-scan-a-call comparison")
     ap.add_argument("--sizes", default="1000,100000,1000000")
     ap.add_argument("--scans", type=int, default=1024)
     ap.add_argument("--batch", type=int, default=128)
@@ -772,6 +921,8 @@ def main():
         return main_find_loop(a)
     if a.append:
         return main_append(a)
+    if a.splice:
+        return main_splice(a)
     N = 28800
     ctx = capi.Context(capi.params("launch"), capi.limits(a.batch, N, sparse=True))
     scenes = np.stack([capi.synth_scan(capi.synth_cfg(1000 + b)) for b in range(a.scans)])
