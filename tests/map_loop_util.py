@@ -30,8 +30,9 @@ MEASURED = dict(d_before=1.8594, d_after=0.0237)
 F32 = ju.F32
 
 
-def loop_world(seed=None, yaw_bias=None, along_bias=None):
-    """(w, pieces): a dict like track_util.world's for the layout above, its reg records biased, and its batches."""
+def loop_world(seed=None, yaw_bias=None, along_bias=None, step=None):
+    """(w, pieces): a dict like track_util.world's for the layout above, its reg records biased, and its batches (cut every `step`
+    scans, default WORLD's)."""
     f = WORLD
     seed = f["seed"] if seed is None else seed
     yaw_bias, along_bias = f["yaw_bias"] if yaw_bias is None else yaw_bias, f["along_bias"] if along_bias is None else along_bias
@@ -65,7 +66,7 @@ def loop_world(seed=None, yaw_bias=None, along_bias=None):
     # the heading is along the track: the sensor's x is the along-track direction
     motions = [(yaw + yaw_bias, tx + along_bias, ty, tz) for yaw, tx, ty, tz in tu.relative(truth)]
     w = dict(off=np.array(off, np.uint32), rows=rows, pole=pole, m=m, inlier=inlier, reg=tu.reg_records(motions), truth=truth, n_scans=n_scans)
-    return w, mu.split(w, mu.every(n_scans, f["step"]))
+    return w, mu.split(w, mu.every(n_scans, f["step"] if step is None else step))
 
 
 def run(w, pieces):

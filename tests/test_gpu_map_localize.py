@@ -54,15 +54,18 @@ def _call(ctx, mp, kp, pri, n_scans, q, nearest=True, **opts):
             "nearest_of_row": raw[2][:q].cpu().numpy() if nearest else None}
 
 
-def _localize(ctx, mp, st, off, rows, priors, what, n_scans=None, max_scans=None, max_total=None, q_max_rows=None, stored=None, nearest=True, **opts):
-    """One fx_map_localize against one map_localize_reference call; the map must come out as it went in."""
+def _localize(ctx, mp, st, off, rows, priors, what, n_scans=None, max_scans=None, max_total=None, q_max_rows=None, stored=None, nearest=True,
+              priors_device=None, **opts):
+    """One fx_map_localize against one map_localize_reference call; the map must come out as it went in.  priors_device: a device
+    tensor of n_scans fx_pose records the call reads in place of an upload of `priors` (a hand-over that no host read stands
+    between); `priors` is then what the reference is given and what the records are held to."""
     n_scans = len(off) - 1 if n_scans is None else n_scans
     max_scans = max(len(off) - 1, n_scans) + 2 if max_scans is None else max_scans
     max_total = len(rows) + 9 if max_total is None else max_total
     q = len(rows) if q_max_rows is None else q_max_rows
     kp, pri = _device(ctx, off, rows, priors, max_scans, max_total, stored)
     before = _map_bytes(mp)
-    got = _call(ctx, mp, kp, pri, n_scans, q, nearest, **opts)
+    got = _call(ctx, mp, kp, pri if priors_device is None else priors_device, n_scans, q, nearest, **opts)
     assert _map_bytes(mp) == before, f"{what}: the map is read, never written"
     ref = capi.map_localize_reference(st, off[:min(len(off) - 1, max_scans) + 1], rows[:len(rows) if stored is None else stored], priors, n_scans, q_max_rows=q, **opts)
     lu.assert_equal(got, ref, what)

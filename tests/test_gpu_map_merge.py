@@ -29,9 +29,12 @@ def ctx(fxlib):
     c.close()
 
 
-def _merge(ctx, mp, st, what, **kw):
-    """One fx_map_merge into a guarded result against one map_merge_reference call.  Returns (the new state, the result dict)."""
+def _merge(ctx, mp, st, what, shrunk=False, **kw):
+    """One fx_map_merge into a guarded result against one map_merge_reference call.  Returns (the new state, the result dict).
+    The records past the ones stored stay what they were, and are zero unless `shrunk`: a map that was compacted, reset or imported
+    into holds unspecified records there (include/fx.h)."""
     import torch
+    tail = mp.landmarks(st["header"]["n_landmarks"]).tobytes()
     raw = torch.full((4 + GUARD,), FILL, dtype=torch.int32, device=f"cuda:{ctx.device}")
     mp.merge(result=raw[:4], **kw)
     ctx.synchronize()
@@ -42,7 +45,8 @@ def _merge(ctx, mp, st, what, **kw):
     mu.assert_equal(mp.records(), capi.map_state_records(st), what)
     mm.assert_alias(mp.alias(), st, what)
     n = st["header"]["n_landmarks"]
-    assert not mp.landmarks(n).view(np.uint8).any(), f"{what}: records past the ones stored"
+    past = mp.landmarks(n)
+    assert past.tobytes() == tail and (shrunk or not past.view(np.uint8).any()), f"{what}: records past the ones stored"
     return st, got
 
 
