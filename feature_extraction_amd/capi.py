@@ -240,6 +240,21 @@ LOC_DEFAULTS = dict(search_dist=2.0, inlier_dist=0.30, min_baseline=2.0, hyp_cor
                     segment=FX_LOC_LAST_SEGMENT)
 
 
+class FxMapObserveOptions(C.Structure):
+    _fields_ = [("gate_dist", C.c_float), ("require_flags", C.c_uint32), ("mode", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class FxMapObserveResult(C.Structure):
+    _fields_ = [("scans_used", C.c_uint32), ("proposed", C.c_uint32), ("added", C.c_uint32), ("duplicates", C.c_uint32), ("gated", C.c_uint32),
+                ("stale", C.c_uint32), ("landmarks_touched", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+FX_MAP_LM_OBSERVED = 0x8  # fx_map_observe: the landmark gained at least one observation through it
+FX_OBS_APPLY, FX_OBS_DRY_RUN = 0, 1
+MAP_OBSERVE_RESULT_FIELDS = ("scans_used", "proposed", "added", "duplicates", "gated", "stale", "landmarks_touched", "reserved")
+OBS_DEFAULTS = dict(gate_dist=0.30, require_flags=FX_LOC_VALID, mode=FX_OBS_APPLY)
+
+
 class FxRelocalizeOptions(C.Structure):
     _fields_ = [("inlier_dist", C.c_float), ("pair_tol", C.c_float), ("min_baseline", C.c_float), ("max_baseline", C.c_float),
                 ("max_seeds", C.c_uint32), ("min_inliers", C.c_uint32), ("min_margin", C.c_uint32), ("min_landmark_obs", C.c_uint32),
@@ -378,6 +393,7 @@ EXPORTS = ("fx_version", "fx_check_abi", "fx_status_str", "fx_last_error", "fx_p
            "fx_map_create", "fx_map_destroy", "fx_map_reset", "fx_map_update", "fx_map_get", "fx_map_read_header", "fx_map_read_landmarks",
            "fx_map_merge_options_default", "fx_map_merge", "fx_map_get_alias", "fx_map_read_alias",
            "fx_localize_options_default", "fx_map_localize", "fx_relocalize_options_default", "fx_map_relocalize",
+           "fx_map_observe_options_default", "fx_map_observe",
            "fx_map_compact_options_default", "fx_map_compact", "fx_map_export_host", "fx_map_import_host", "fx_map_snapshot_check",
            "fx_map_append", "fx_map_append_host",
            "fx_map_join_options_default", "fx_map_join_segments",
@@ -519,6 +535,10 @@ def load():
     lib.fx_relocalize_options_default.restype = None
     lib.fx_map_relocalize.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                       C.POINTER(FxRelocalizeOptions), C.c_void_p, C.c_void_p]
+    lib.fx_map_observe_options_default.argtypes = [C.POINTER(FxMapObserveOptions)]
+    lib.fx_map_observe_options_default.restype = None
+    lib.fx_map_observe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                   C.POINTER(FxMapObserveOptions), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.fx_map_compact_options_default.argtypes = [C.POINTER(FxMapCompactOptions)]
     lib.fx_map_compact_options_default.restype = None
     lib.fx_map_compact.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(FxMapCompactOptions), C.c_void_p, C.c_void_p]
@@ -1602,6 +1622,119 @@ def map_localize_reference(state, kp_offset, kp_rows, prior_poses, n_scans, q_ma
     return {"rec": rec, "map_id_of_row": map_id, "nearest_of_row": nearest, "corr": corrs}
 
 
+# ---- localised scans folded into the map (include/fx.h fx_map_observe)
+def observe_records(out):
+    """The 32 bytes fx_map_observe wrote (a device tensor, or an array) as a dict of MAP_OBSERVE_RESULT_FIELDS."""
+    a = out.detach().cpu().numpy() if hasattr(out, "detach") else np.asarray(out)
+    w = np.ascontiguousarray(a).view(np.uint8).reshape(-1)[:32].view("<u4")
+    return dict(zip(MAP_OBSERVE_RESULT_FIELDS, (int(v) for v in w)))
+
+
+def map_observe_reference(state, kp_offset, kp_rows, loc_records, map_id_of_row, n_scans, q_max_rows=None, gate_dist=0.30,
+                          require_flags=FX_LOC_VALID, dry_run=False):
+    """The definition of fx_map_observe (include/fx.h) in numpy float64 over a map_reference / map_merge_reference / ... state, which
+    is not modified.  kp_offset / kp_rows: the block's kp_offset[scans + 1] and its [stored, >= 3] float32 rows, already cut to
+    min(stored, max_total_keypoints); loc_records: LOC_DTYPE [>= n_scans]; map_id_of_row: int32 [>= q_max_rows]; q_max_rows: the
+    length of the row arrays (default: the block's rows).  Every (row, row) pair of a scan is looked at and every clause is a mask
+    over all rows: nothing here knows of counts, cursors or a sort.  One ufunc an operation, so nothing is contracted.
+    Returns (the new state (the old one's content with dry_run), {"scans_used", "proposed", "added", "duplicates", "gated", "stale",
+    "landmarks_touched", "reserved"}, gained_of_landmark uint32 [max_landmarks], observed_id_of_row int32 [q_max_rows])."""
+    f64 = np.float64
+    off = [int(x) for x in kp_offset]
+    kp = np.ascontiguousarray(kp_rows, dtype=np.float32)
+    kp = kp.reshape(len(kp), -1)[:, :3] if kp.size else np.zeros((0, 3), np.float32)
+    n_scans = int(n_scans)
+    R = len(kp) if q_max_rows is None else int(q_max_rows)
+    gd32, req = np.float32(gate_dist), int(require_flags) & 0xffffffff
+    known = FX_LOC_VALID | FX_LOC_TRUNCATED | FX_LOC_NO_HYPOTHESIS | FX_LOC_BAD_PRIOR | FX_LOC_NO_SCAN
+    if not (n_scans >= 1 and np.isfinite(gd32) and gd32 > 0 and not req & ~known):
+        raise ValueError("arguments outside what fx_map_observe accepts")
+    gd = f64(gd32)
+    gd2 = gd * gd
+    st = dict(state, header=dict(state["header"]), landmarks=[dict(r) for r in state["landmarks"]], acc=[list(a) for a in state["acc"]],
+              carry=list(state["carry"]), carry_kp=state["carry_kp"].copy())
+    if "alias" in state:
+        st["alias"] = list(state["alias"])
+    lms, accs = st["landmarks"], st["acc"]
+    N = min(int(st["header"]["n_landmarks"]), len(lms), int(st["max_landmarks"]))
+    alias = np.array([int(a) for a in state.get("alias", [])][:N] + [-1] * max(0, N - len(state.get("alias", []))), np.int64)
+    lx, ly, lz = (np.array([float(r[f]) for r in lms[:N]], f64) for f in ("x", "y", "z"))
+    ln = np.array([int(r["n_obs"]) for r in lms[:N]], np.int64)
+    loc = np.asarray(loc_records)[:n_scans]
+    S, rows = min(n_scans, len(off) - 1), min(len(kp), R)
+    ids = np.asarray(map_id_of_row)[:rows].astype(np.int64)
+    # the scan of every row, -1: a non-row; the used scans
+    scan = np.full(rows, -1, np.int64)
+    for b in range(S):
+        lo = min(off[b], rows)
+        scan[lo:max(min(off[b + 1], rows), lo)] = b
+    P = loc["pose"][:S]
+    used = np.array([(int(loc["flags"][b]) & req) == req and all(np.isfinite(f64(P[f][b])) for f in ("c", "s", "tx", "ty", "tz")) for b in range(S)], bool)
+    with np.errstate(all="ignore"):
+        sc = np.where(scan >= 0, scan, 0)
+        in_used = (scan >= 0) & (used[sc] if S else np.zeros(rows, bool))
+        proposes = in_used & np.isfinite(kp[:rows]).all(axis=1) & (ids >= 0) & (ids < N)
+        idc = np.where(proposes, ids, 0)
+        via = alias[idc] if N else np.zeros(rows, np.int64)
+        g = np.where(via >= 0, via, idc)
+        gc = np.where(g < N, g, 0)
+        if N:
+            live = (g < N) & (alias[gc] == -1) & (ln[gc] >= 1) & np.isfinite(lx[gc]) & np.isfinite(ly[gc]) & np.isfinite(lz[gc])
+        else:
+            live = np.zeros(rows, bool)
+        stale = proposes & ~live
+        # the world points under the scans' poses, the gate against the records as they are
+        x, y, z = (kp[:rows, k].astype(f64) for k in range(3))
+        pc, ps, ptx, pty, ptz = ((P[f][sc].astype(f64) if S else np.zeros(rows, f64)) for f in ("c", "s", "tx", "ty", "tz"))
+        wx, wy, wz = (pc * x - ps * y) + ptx, (ps * x + pc * y) + pty, z + ptz
+        if N:
+            dx, dy = lx[gc] - wx, ly[gc] - wy
+        else:
+            dx = dy = np.zeros(rows, f64)
+        d2 = dx * dx + dy * dy
+        passes = proposes & live & (d2 <= gd2)
+        gated = proposes & live & ~passes
+    # one observation a scan a landmark: a passing proposal is kept unless another of its scan and its landmark is lower in (d2 bits, row)
+    bits = np.ascontiguousarray(d2).view(np.uint64)
+    kept = passes.copy()
+    r_all = np.arange(rows)
+    for b in np.unique(scan[passes]).tolist():
+        i = np.flatnonzero(passes & (scan == b))
+        same = g[i][:, None] == g[i][None, :]
+        lower = (bits[i][None, :] < bits[i][:, None]) | ((bits[i][None, :] == bits[i][:, None]) & (r_all[i][None, :] < r_all[i][:, None]))
+        kept[i] = ~(same & lower).any(axis=1)
+    observed = np.full(R, -1, np.int32)
+    observed[:rows][kept] = g[kept]
+    gained = np.zeros(int(st["max_landmarks"]), np.uint32)
+    touched = 0
+    W = np.stack([wx, wy, wz], axis=1).tolist() if rows else []
+    for t in sorted(set(g[kept].tolist())):
+        mine = np.flatnonzero(kept & (g == t)).tolist()  # (ascending row)
+        gained[t] = len(mine)
+        touched += 1
+        if dry_run:
+            continue
+        acc, rec = accs[t], lms[t]
+        for r in mine:
+            ox, oy, oz = W[r]
+            ddx, ddy = ox - acc[3], oy - acc[4]
+            acc[0] += ox
+            acc[1] += oy
+            acc[2] += oz
+            acc[5] += ddx
+            acc[6] += ddy
+            acc[7] += (ddx * ddx + ddy * ddy)
+        rec["n_obs"] += len(mine)
+        _map_record_from_sums(rec, acc)
+        rec["flags"] |= FX_MAP_LM_OBSERVED
+    added = int(kept.sum())
+    if not dry_run:
+        st["header"]["n_obs"] = (int(st["header"]["n_obs"]) + added) & 0xffffffff
+    res = {"scans_used": int(used.sum()), "proposed": int(proposes.sum()), "added": added, "duplicates": int(passes.sum()) - added,
+           "gated": int(gated.sum()), "stale": int(stale.sum()), "landmarks_touched": touched, "reserved": 0}
+    return st, res, gained, observed
+
+
 # ---- two segments of the map made one (include/fx.h fx_map_join_segments)
 def join_records(out):
     """A host copy of fx_map_join_segments's result (a torch tensor, or any array of 120 bytes) as a JOIN_DTYPE record array [1]."""
@@ -2386,6 +2519,29 @@ class Map:
                                            C.c_void_p(prior_poses.data_ptr()), n_scans, n_rows, C.byref(opt), C.c_void_p(recs.data_ptr()),
                                            C.c_void_p(ids.data_ptr() if n_rows else None), _ptr(nearest if n_rows else None)))
         return recs, ids, nearest
+
+    def observe(self, kp, loc, n_scans, map_id_of_row, q_max_rows=None, out=None, gained=None, observed=None, **opts):
+        """fx_map_observe: the inlier rows of localised scans folded into the landmarks they were matched to (include/fx.h).  kp is
+        the keypoint block the localise was given, as (device tensor, max_scans, max_total_keypoints); loc and map_id_of_row are the
+        first two tensors localize() returned, read in place on the device.  opts: the fields of fx_map_observe_options
+        (OBS_DEFAULTS).  Returns (result, gained_of_landmark, observed_id_of_row): device torch.int32 tensors [8] (observe_records
+        reads it), [max_landmarks] and [q_max_rows]; out / gained / observed reuse one, False passes NULL (None is returned in its
+        place).  Stream-correct like update(); never waits for the stream."""
+        import torch
+        kb, scans, total = kp
+        dev = torch.device("cuda", self.ctx.device)
+        n_scans = int(n_scans)
+        n_rows = int(total) if q_max_rows is None else int(q_max_rows)
+        opt = _options(FxMapObserveOptions, OBS_DEFAULTS, "observe", opts)
+        error = f"outputs must be contiguous torch.int32 tensors [8], [{self.max_landmarks}] and [{n_rows}] on {dev}"
+        out = _out_tensor(out, (8,), torch.int32, dev, error, typed=True)
+        gained = _out_tensor(gained, (self.max_landmarks,), torch.int32, dev, error, typed=True)
+        observed = _out_tensor(observed, (n_rows,), torch.int32, dev, error, typed=True)
+        with _on_stream(self.ctx.stream_ptr(), dev):
+            check(self.lib.fx_map_observe(self.ctx.handle, self.handle, C.c_void_p(kb.data_ptr()), int(scans), int(total), C.c_void_p(loc.data_ptr()),
+                                          n_scans, C.c_void_p(map_id_of_row.data_ptr() if n_rows else None), n_rows, C.byref(opt), _ptr(out),
+                                          _ptr(gained), _ptr(observed if n_rows else None)))
+        return out, gained, observed
 
     def relocalize(self, kp, n_scans, q_max_rows=None, out=None, **opts):
         """fx_map_relocalize: the pose of the scans of the keypoint block kp = (device tensor, max_scans, max_total_keypoints) in this

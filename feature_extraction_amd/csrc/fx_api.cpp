@@ -95,6 +95,8 @@ hipError_t fxk_map_localize(hipStream_t s, const FxMapLocalizeArgs &A);
 size_t fxk_map_localize_scratch(FxMapLocalizeArgs *A, uint8_t *base);
 hipError_t fxk_map_relocalize(hipStream_t s, const FxMapRelocalizeArgs &A);
 size_t fxk_map_relocalize_scratch(FxMapRelocalizeArgs *A, uint8_t *base);
+hipError_t fxk_map_observe(hipStream_t s, const FxMapObserveArgs &A);
+size_t fxk_map_observe_scratch(FxMapObserveArgs *A, uint8_t *base);
 hipError_t fxk_map_find_loop(hipStream_t s, const FxMapFindLoopArgs &A);
 size_t fxk_map_find_loop_scratch(FxMapFindLoopArgs *A, uint8_t *base);
 hipError_t fxk_map_compact(hipStream_t s, const FxMapCompactArgs &A);
@@ -278,6 +280,7 @@ struct fx_ctx {
   DevScratch map_scratch;    // fx_map_update: the batch landmark's map id, the blocks' counts
   DevScratch merge_scratch;  // fx_map_merge: the grid (bucket counts, landmarks in bucket order), proposals, kept links;
                              // fx_map_localize: the same grid, then each row's landmark and distance;
+                             // fx_map_observe: the landmarks' list counts, cursors and prefix, each row's target and distance, the lists;
                              // fx_map_compact: the marks, the new ids, the blocks' counts, the kept records and sums staged;
                              // fx_map_append: the state words; fx_map_append_host: the snapshot's bytes before them;
                              // fx_map_join_segments, fx_map_close_loop: the grid, each query's target and distance, the list of
@@ -2127,6 +2130,42 @@ fx_status fx_map_relocalize(fx_ctx *c, fx_map *m, const void *kp, uint32_t max_s
   A.segment = o.segment;
   A.out = out, A.map_id_of_row = map_id_of_row;
   FX_MAP_RUN(fxk_map_relocalize, "map relocalize scratch");
+  return FX_OK;
+}
+
+void fx_map_observe_options_default(fx_map_observe_options *o) {
+  if (!o) return;
+  o->gate_dist = 0.30f;
+  o->require_flags = FX_LOC_VALID;
+  o->mode = FX_OBS_APPLY;
+  o->reserved = 0u;
+}
+
+fx_status fx_map_observe(fx_ctx *c, fx_map *m, const void *kp, uint32_t max_scans, uint32_t max_total, const fx_localization *loc, uint32_t n_scans,
+                         const int32_t *map_id_of_row, uint32_t q_max_rows, const fx_map_observe_options *opt, fx_map_observe_result *result,
+                         uint32_t *gained_of_landmark, int32_t *observed_id_of_row) {
+  FX_TRY(map_call_check(c, m, kp && loc && !(q_max_rows && !map_id_of_row)));
+  if (!n_scans || n_scans > max_scans)
+    return fail(FX_ERR_INVALID_ARG, "n_scans must be 1..max_scans (" + std::to_string(n_scans) + " of " + std::to_string(max_scans) + ")");
+  fx_map_observe_options o;
+  fx_map_observe_options_default(&o);
+  if (opt) o = *opt;
+  if (!(std::isfinite(o.gate_dist) && o.gate_dist > 0.f)) return fail(FX_ERR_INVALID_ARG, "gate_dist must be finite and positive");
+  const uint32_t known = FX_LOC_VALID | FX_LOC_TRUNCATED | FX_LOC_NO_HYPOTHESIS | FX_LOC_BAD_PRIOR | FX_LOC_NO_SCAN;
+  if (o.require_flags & ~known) return fail(FX_ERR_INVALID_ARG, "unknown require_flags bits (only the FX_LOC_* flags are defined)");
+  if (o.mode != FX_OBS_APPLY && o.mode != FX_OBS_DRY_RUN) return fail(FX_ERR_INVALID_ARG, "unknown mode (FX_OBS_APPLY or FX_OBS_DRY_RUN)");
+  if (o.reserved) return fail(FX_ERR_INVALID_ARG, "reserved must be 0");
+  if (((uintptr_t)kp % 16) != 0 || ((uintptr_t)loc % 8) != 0 || ((uintptr_t)map_id_of_row % 4) != 0 || ((uintptr_t)result % 4) != 0 ||
+      ((uintptr_t)gained_of_landmark % 4) != 0 || ((uintptr_t)observed_id_of_row % 4) != 0)
+    return fail(FX_ERR_INVALID_ARG, "the keypoint block must be 16-byte, the records 8-byte, the words 4-byte aligned");
+  FX_HIP(hipSetDevice(c->device));
+  FxMapObserveArgs A{};
+  A.header = m->a.header, A.records = m->a.records, A.acc = m->a.acc, A.alias = m->a.alias, A.cap = m->a.cap;
+  A.kp = (const uint32_t *)kp, A.max_scans = max_scans, A.max_total = max_total;
+  A.loc = loc, A.n_scans = n_scans, A.map_id_of_row = map_id_of_row, A.q_max_rows = q_max_rows;
+  A.gd2 = (double)o.gate_dist * (double)o.gate_dist, A.require_flags = o.require_flags, A.mode = o.mode;
+  A.result = (uint32_t *)result, A.gained = gained_of_landmark, A.observed = observed_id_of_row;
+  FX_MAP_RUN(fxk_map_observe, "map observe scratch");
   return FX_OK;
 }
 

@@ -283,6 +283,35 @@ struct FxMapLocalizeArgs {
   int32_t *near;                // the row's landmark, -1: none
   unsigned long long *d2;       // its squared xy distance as bits
 };
+// fx_map_observe (csrc/fx_map_observe.hip): a launch set's arguments.  The first group is the map's own memory, the last the
+// context's scratch, sized by the map's max_landmarks (cap) and by q_max_rows.
+#define FX_MAP_OBSERVE_ST_WORDS 8  // 0 scans_used, 1 proposed, 2 added, 3 duplicates, 4 gated, 5 stale, 6 landmarks_touched, 7 list entries
+struct FxMapObserveArgs {
+  void *header;                 // fx_map_header
+  void *records;                // fx_map_landmark [cap]
+  double *acc;                  // [cap][FX_MAP_ACC]
+  const int32_t *alias;         // [cap]
+  uint32_t cap;
+  const uint32_t *kp;           // keypoint block (include/fx.h fx_pack_keypoint_block)
+  uint32_t max_scans, max_total;
+  const void *loc;              // fx_localization [n_scans]
+  uint32_t n_scans, q_max_rows;
+  const int32_t *map_id_of_row; // [q_max_rows]
+  double gd2;                   // the gate: (double)gate_dist squared
+  uint32_t require_flags, mode;
+  uint32_t *result;             // fx_map_observe_result or null
+  uint32_t *gained;             // [cap] or null
+  int32_t *observed;            // [q_max_rows] or null
+  uint32_t *cnt;                // [cap]: entries of the landmark's list; cur and st follow it (one memset clears the three)
+  uint32_t *cur;                // [cap]: the scatter's cursor into the list
+  uint32_t *st;                 // [FX_MAP_OBSERVE_ST_WORDS]
+  uint32_t *local;              // [cap]: the exclusive prefix of cnt within the block of 256
+  uint32_t *bsum;               // [2][blocks of landmarks]: the block's entries, then their prefix (the second row is unused: 0)
+  int32_t *tgt;                 // [q_max_rows]: the landmark the row's proposal passed the gate of, -1: none
+  unsigned long long *d2;       // [q_max_rows]: its squared xy distance as bits
+  uint4 *ent, *sorted;          // [q_max_rows] each: the lists as the scatter left them, and in ascending row; an entry is a proposal
+                                // that passed the gate: x its row, y its scan, (w << 32) | z its d2 bits (one 16-byte vector: no struct copies)
+};
 // fx_map_relocalize (csrc/fx_map_relocalize.hip): a launch set's arguments.  P and Q describe the two grids over the map, alive
 // together in the context's scratch (the merge's per-landmark arrays are null in both): P, the pair grid, finds the landmarks h
 // whose distance from g can pass the length gate of a seed; Q, the score grid, the landmark a keypoint's image lands on.  The last

@@ -794,7 +794,8 @@ fx_status fx_map_read_alias(fx_ctx *ctx, fx_map *map, uint32_t first, uint32_t c
  * sd (1 + 2^-8)) never shows in the result.
  * Limits: a prior is needed: fx_map_relocalize (below) produces one from the map's geometry alone (the map stores no descriptors),
  * and this call refines it; the call joins no segments (fx_map_join_segments, below, does, and takes a record's dc as its prior) and
- * re-estimates no landmark: it produces the poses and the row-to-landmark table both would start from.  A cell of the grid that
+ * re-estimates no landmark (fx_map_observe, below, does, from this call's records and its row-to-landmark table): it produces the
+ * poses and the table both start from.  A cell of the grid that
  * holds very many landmarks is walked by one lane a row.  New in 0.7 (added symbols only). */
 #define FX_LOC_MAX_CORR 1024u
 #define FX_LOC_ANY_SEGMENT  0xffffffffu
@@ -918,6 +919,70 @@ fx_status fx_map_relocalize(fx_ctx *ctx, fx_map *map,
     const void *kp_block_device, uint32_t max_scans, uint32_t max_total_keypoints,
     uint32_t n_scans, uint32_t q_max_rows, const fx_relocalize_options *opt /* NULL: defaults */,
     fx_relocalization *out_device /* [n_scans] */, int32_t *map_id_of_row_device /* [q_max_rows] */);
+
+/* ---- Folding localised scans into the map: the landmarks re-estimated from what fx_map_localize matched ----
+ * A landmark's mean otherwise moves only through a track handed to fx_map_update: a localisation run against a finished map ("map
+ * once, localise later") leaves every landmark's sums, n_obs, x, y, z and rms_xy as the mapping run left them, however often the
+ * poles are seen again.  fx_map_observe folds the inlier rows of localised scans into the landmarks they were matched to.  It takes
+ * what the fx_map_localize (or fx_map_relocalize: its records begin with the same fx_pose, but carry other flags) call before it was
+ * given and what it wrote, reads both on the device, and is enqueued on the context's stream: no host read stands between the two
+ * calls, no host synchronisation, no allocation in the steady state (its scratch is the context-owned buffer of fx_map_merge, sized
+ * by the map's max_landmarks and by q_max_rows).  One call covers the whole (row, landmark) table as it is when the call runs on
+ * the stream.
+ * Sizes: S, rows, scan(r) and the non-rows exactly as in fx_map_localize; N = header.n_landmarks, clipped to the map's
+ * max_landmarks.
+ * Used scans: scan b < S is used iff (loc[b].flags & require_flags) == require_flags and c, s, tx, ty and tz of loc[b].pose are all
+ * finite.  require_flags == 0 uses every scan of a finite pose; a pose that is not finite is never used.  scans_used counts them.
+ * Proposals: row r < rows of a used scan proposes iff its x, y and z are finite and id = map_id_of_row[r] satisfies 0 <= id < N.
+ * Anything else is not a proposal: -1, garbage, ids at or beyond N, a table from before a compaction.  That makes the call
+ * memory-safe on any table.  `proposed` counts the proposals.
+ * Target: g = alias[id] >= 0 ? alias[id] : id: a merge since the localise is followed, and two ids of one root are one landmark
+ * from here on.  The proposal is STALE, and counted in `stale`, unless g < N, alias[g] == -1, n_obs[g] >= 1 and the record's x, y
+ * and z are finite.
+ * Gate: (wx, wy, wz) is the row under loc[b].pose, fx_track_landmarks's fusing clause word for word (the same device function).
+ * With the record as it is when the call starts: dx = x[g] - wx, dy = y[g] - wy, d2 = dx dx + dy dy in fp64, no contraction; the
+ * proposal passes iff d2 <= gd gd, gd = (double)gate_dist; one that fails counts in `gated`.  Observations of an earlier scan of the
+ * same call do not move the gate of a later one.
+ * One observation a scan a landmark: among the passing proposals of one scan with the same g the one of lowest (d2 as uint64 bits,
+ * row) is kept, the others count in `duplicates`; `added` is the number kept.  proposed = added + duplicates + gated + stale.
+ * Fold: every landmark g with k >= 1 kept observations takes them in ascending row, which is ascending scan: fx_map_update's
+ * "Adding an observation" clause word for word on g's sums with g's anchor, one fp64 chain on one lane.  Then n_obs[g] += k; x, y,
+ * z and rms_xy are recomputed by fx_map_update's "Records" clause; flags |= FX_MAP_LM_OBSERVED; first_scan, last_scan, segment and
+ * the anchor are untouched.  landmarks_touched counts these landmarks.
+ * Header: n_obs += added, and nothing else.  Alias, carry, the carry scan and every untouched record and its sums keep their bytes.
+ * Outputs, every word written in both modes: observed_id_of_row[r], all q_max_rows words: g for a kept observation, else -1;
+ * gained_of_landmark[i], all max_landmarks words: the k of landmark i, else 0; result: eight words, reserved = 0.
+ * FX_OBS_DRY_RUN: the three outputs are what the applying call would have written, and the map is bit for bit what it was.
+ * FX_ERR_INVALID_ARG with the reason in fx_last_error(), nothing launched, no output byte touched, the map unchanged: a NULL ctx,
+ * map, kp_block_device or loc_device; a NULL map_id_of_row_device with q_max_rows != 0; a map of another context; n_scans == 0 or
+ * n_scans > max_scans; gate_dist not finite and positive; unknown require_flags bits; an unknown mode; reserved != 0; a keypoint
+ * block not 16-byte, records not 8-byte, word arrays not 4-byte aligned.
+ * The same bytes from run to run and with any number of contexts in flight: every decision is an integer or a minimum over a total
+ * order (32-bit integer atomics only, sums), every fp64 sum an ordered chain on one lane; no floating-point atomics anywhere.
+ * Limits: the call creates no landmark: unmatched rows are ignored.  It does not touch scan numbers: first_scan and last_scan
+ * place a landmark in the mapping run's trajectory (the merge's disjointness and the loop closure's weights rest on that), and a
+ * localised scan is not part of that trajectory.  Scans that also go through fx_map_update are counted twice, and nothing detects
+ * that.  n_obs is a 32-bit count.  One lane folds a landmark's list and every entry of a list is ranked against the whole list:
+ * time, not the result, grows with the longest list.  New in 0.7 (added symbols only). */
+#define FX_MAP_LM_OBSERVED 0x8u   /* fx_map_landmark flags: gained at least one observation through fx_map_observe */
+#define FX_OBS_APPLY 0u
+#define FX_OBS_DRY_RUN 1u         /* report everything, change no byte of the map */
+typedef struct fx_map_observe_options {   /* 16 B */
+  float gate_dist;        /* an observation must lie within this xy distance of its landmark's mean; finite, > 0; default 0.30 */
+  uint32_t require_flags; /* FX_LOC_* bits a scan's record must carry to be used; default FX_LOC_VALID */
+  uint32_t mode;          /* FX_OBS_APPLY (default), FX_OBS_DRY_RUN */
+  uint32_t reserved;      /* 0 */
+} fx_map_observe_options;
+typedef struct fx_map_observe_result {    /* 32 B */
+  uint32_t scans_used, proposed, added, duplicates, gated, stale, landmarks_touched, reserved;
+} fx_map_observe_result;
+void fx_map_observe_options_default(fx_map_observe_options *o);
+fx_status fx_map_observe(fx_ctx *ctx, fx_map *map,
+    const void *kp_block_device, uint32_t max_scans, uint32_t max_total_keypoints,   /* what the localise was given */
+    const fx_localization *loc_device, uint32_t n_scans,                            /* what it wrote */
+    const int32_t *map_id_of_row_device, uint32_t q_max_rows,
+    const fx_map_observe_options *opt /* NULL: defaults */, fx_map_observe_result *result_device /* or NULL */,
+    uint32_t *gained_of_landmark_device /* [max_landmarks] or NULL */, int32_t *observed_id_of_row_device /* [q_max_rows] or NULL */);
 
 /* ---- Compacting the map: the absorbed fragments and the let-go landmarks taken out, the others renumbered ----
  * fx_map_merge leaves every absorbed fragment in place: its record, its sums and its alias entry; every grid build marks and skips

@@ -45,6 +45,12 @@ localises 8 scans of 64 keypoints against it (timed: fx_map_localize on the same
 joins segment 1 into segment 0 (timed: one pair of HIP events around the call: the grid, N / 3 queries, the consensus over the
 first 1024 correspondences, N / 3 landmarks moved, N relabelled).  Reported per size: the medians and the join's result.  No
 target is set.
+  timeout -k 10 600 python tools/map_times.py --observe [--sizes 1000,100000,1000000] [--warmup 1] [--repeats 5] [--out profiles/map_observe.md]
+
+times fx_map_observe on the synthetic maps of --join (the link left usable: one segment): every repeat resets the map, updates it,
+localises 8 scans of 64 keypoints against it (timed: fx_map_localize, any segment, the true poses as priors) and folds the inlier
+rows into their landmarks (timed: fx_map_observe reading the localise's records and table where they are: the memset, the seven
+launches).  One pair of HIP events around each call.  Reported per size: the medians and the observe's result.  No target is set.
   timeout -k 10 600 python tools/map_times.py --loop [--sizes 1000,100000,1000000] [--warmup 1] [--repeats 5] [--out profiles/map_loop_times.txt]
 
 times fx_map_close_loop on the same synthetic maps as one segment: the first fragments (scans 0-1) are the old landmarks, the second
@@ -332,10 +338,15 @@ def measure_relocalize(ctx, n, warmup, repeats, n_scans=8):
             "valid": int((rec["flags"] & capi.FX_RELOC_VALID != 0).sum()), "n_hyp_mean": float(rec["n_hyp"].mean()), "n_seeds": rec["n_seeds"].tolist()}
 
 
-def measure_join(ctx, n, warmup, repeats, n_scans=8):
+def localize_scene(ctx, n, n_scans, cut_link):
+    """What --join and --observe localise against: merge_case(n) through one track and one update into a map of n landmarks
+    (cut_link: the link scan 2 -> scan 1 made unusable, the second fragments a segment of their own), and n_scans scans of the 64
+    poles nearest to a random position inside the map, seen from a random pose there, with the true poses as priors.  Returns (the
+    map, the batch's block, the track's outputs, the scans' block, the priors): device tensors."""
     import torch
     blk, (S, T), m, inl, reg, M = merge_case(n, np.random.default_rng(n))
-    reg["flags"][1] = 0  # the link scan 2 -> scan 1: the second fragments are a segment of their own
+    if cut_link:
+        reg["flags"][1] = 0
     kp = (torch.from_numpy(blk).cuda(), S, T)
     md, inl_t = torch.from_numpy(m.view(np.int32).reshape(-1, 8).copy()).cuda(), torch.from_numpy(inl).cuda()
     reg_t = torch.from_numpy(reg.view(np.float64).reshape(-1, 8).copy()).cuda()
@@ -363,6 +374,12 @@ def measure_join(ctx, n, warmup, repeats, n_scans=8):
     sb[k0:k0 + T2] = rows
     skp = (torch.from_numpy(sb.view(np.uint8).reshape(-1)).cuda(), n_scans, T2)
     pri_t = torch.from_numpy(pri.view(np.float64).reshape(-1, 6).copy()).cuda()
+    return mp, kp, out, skp, pri_t
+
+
+def measure_join(ctx, n, warmup, repeats, n_scans=8):
+    import torch
+    mp, kp, out, skp, pri_t = localize_scene(ctx, n, n_scans, cut_link=True)
     res = torch.zeros((capi.JOIN_DTYPE.itemsize // 8,), dtype=torch.float64, device="cuda")
     match = torch.empty((n,), dtype=torch.int32, device="cuda")
     stream = torch.cuda.ExternalStream(ctx.stream_ptr())
@@ -394,6 +411,62 @@ def measure_join(ctx, n, warmup, repeats, n_scans=8):
         out[k] = statistics.median(v)
         out[k + "_min_max"] = [min(v), max(v)]
     return out
+
+
+def measure_observe(ctx, n, warmup, repeats, n_scans=8):
+    import torch
+    mp, kp, out, skp, pri_t = localize_scene(ctx, n, n_scans, cut_link=False)
+    res = torch.zeros((8,), dtype=torch.int32, device="cuda")
+    stream = torch.cuda.ExternalStream(ctx.stream_ptr())
+    torch.cuda.synchronize()
+    t = {"localize_ms": [], "observe_ms": []}
+    first, valid = None, 0
+    for rep in range(warmup + repeats):
+        mp.reset()
+        mp.update(kp, out, overlap=False, row_ids=False)
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        e[0].record(stream)
+        recs, ids, _ = mp.localize(skp, pri_t, n_scans, nearest=False, segment=capi.FX_LOC_ANY_SEGMENT)
+        e[1].record(stream), e[2].record(stream)
+        mp.observe(skp, recs, n_scans, ids, out=res, gained=False, observed=False)
+        e[3].record(stream)
+        ctx.synchronize()
+        got = capi.observe_records(res)
+        valid = int((capi.localize_records(recs)["flags"] & capi.FX_LOC_VALID != 0).sum())
+        first = got if first is None else first
+        assert got == first and got["added"] > 0, (got, first)
+        if rep >= warmup:
+            for k, (a, b) in zip(t, ((0, 1), (2, 3))):
+                t[k].append(e[a].elapsed_time(e[b]))
+    mp.close()
+    out = {"landmarks": n, "localize_valid": valid, "result": first}
+    for k, v in t.items():
+        out[k] = statistics.median(v)
+        out[k + "_min_max"] = [min(v), max(v)]
+    return out
+
+
+def main_observe(a):
+    sizes = [int(x) for x in a.sizes.split(",")]
+    ctx = capi.Context(capi.params("launch"), capi.limits(2, 1024))
+    rows = [measure_observe(ctx, n, a.warmup, a.repeats) for n in sizes]
+    ctx.close()
+    lines = [f"fx_map_observe behind fx_map_localize on synthetic maps (tools/map_times.py --observe): 1 pole per 250 m^2, one segment; a call:",
+             f"8 scans of 64 keypoints localised (any segment, the true poses as priors), then observed from the localise's device outputs; one",
+             f"context, HIP events around each call, median of {a.repeats} after {a.warmup} warm-up; ms",
+             f"{'landmarks':>10} {'used':>5} {'proposed':>9} {'added':>6} {'dup':>4} {'gated':>6} {'stale':>6} {'touched':>8} {'observe':>9} {'min':>8} {'max':>8} {'localize':>9} {'valid':>6}"]
+    for r in rows:
+        q = r["result"]
+        lines.append(f"{r['landmarks']:>10} {q['scans_used']:>5} {q['proposed']:>9} {q['added']:>6} {q['duplicates']:>4} {q['gated']:>6} {q['stale']:>6} "
+                     f"{q['landmarks_touched']:>8} {r['observe_ms']:>9.3f} {r['observe_ms_min_max'][0]:>8.3f} {r['observe_ms_min_max'][1]:>8.3f} "
+                     f"{r['localize_ms']:>9.3f} {r['localize_valid']:>6}")
+    s = "\n".join(lines)
+    print(s)
+    print(json.dumps(rows))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(s + "\n")
 
 
 def main_join(a):
@@ -892,6 +965,7 @@ def main():
     ap.add_argument("--compact", action="store_true", help="time fx_map_compact on the merged synthetic maps instead")
     ap.add_argument("--relocalize", action="store_true", help="time fx_map_relocalize on the synthetic maps instead (pass --sizes 10000,100000)")
     ap.add_argument("--join", action="store_true", help="time fx_map_join_segments on two-segment synthetic maps instead")
+    ap.add_argument("--observe", action="store_true", help="time fx_map_observe behind fx_map_localize on the synthetic maps of --join instead")
     ap.add_argument("--loop", action="store_true", help="time fx_map_close_loop on the synthetic maps taken as one loop instead")
     ap.add_argument("--find-loop", action="store_true", help="time fx_map_find_loop next to fx_map_relocalize on one-segment synthetic maps instead")
     ap.add_argument("--append", action="store_true", help="time fx_map_append and fx_map_append_host next to fx_map_import_host and a plain copy instead")
@@ -915,6 +989,8 @@ def main():
         return main_relocalize(a)
     if a.join:
         return main_join(a)
+    if a.observe:
+        return main_observe(a)
     if a.loop:
         return main_loop(a)
     if a.find_loop:
