@@ -255,6 +255,35 @@ MAP_OBSERVE_RESULT_FIELDS = ("scans_used", "proposed", "added", "duplicates", "g
 OBS_DEFAULTS = dict(gate_dist=0.30, require_flags=FX_LOC_VALID, mode=FX_OBS_APPLY)
 
 
+class FxMapExpectOptions(C.Structure):
+    _fields_ = [("x_min", C.c_float), ("x_max", C.c_float), ("y_min", C.c_float), ("y_max", C.c_float), ("min_range", C.c_float),
+                ("max_range", C.c_float), ("shadow_width", C.c_float), ("require_flags", C.c_uint32), ("min_landmark_obs", C.c_uint32),
+                ("segment", C.c_uint32), ("mode", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class FxMapExpectResult(C.Structure):
+    _fields_ = [("scans_used", C.c_uint32), ("in_range", C.c_uint32), ("in_box", C.c_uint32), ("shadowed", C.c_uint32), ("expected", C.c_uint32),
+                ("seen", C.c_uint32), ("stale", C.c_uint32), ("landmarks_expected", C.c_uint32)]
+
+
+class FxMapRetireOptions(C.Structure):
+    _fields_ = [("min_expected", C.c_uint32), ("seen_num", C.c_uint32), ("seen_den", C.c_uint32), ("mode", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class FxMapRetireResult(C.Structure):
+    _fields_ = [("before", C.c_uint32), ("kept", C.c_uint32), ("dropped_absorbed", C.c_uint32), ("retired", C.c_uint32), ("retired_obs", C.c_uint32),
+                ("protected_by_carry", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+FX_EXPECT_WRITE, FX_EXPECT_ADD = 0, 1
+FX_RETIRE_APPLY, FX_RETIRE_DRY_RUN = 0, 1
+MAP_EXPECT_RESULT_FIELDS = ("scans_used", "in_range", "in_box", "shadowed", "expected", "seen", "stale", "landmarks_expected")
+MAP_RETIRE_RESULT_FIELDS = ("before", "kept", "dropped_absorbed", "retired", "retired_obs", "protected_by_carry")
+EXPECT_DEFAULTS = dict(x_min=1.0, x_max=74.0, y_min=-29.0, y_max=29.0, min_range=2.0, max_range=60.0, shadow_width=0.5,
+                       require_flags=FX_LOC_VALID, min_landmark_obs=2, segment=FX_LOC_ANY_SEGMENT, mode=FX_EXPECT_WRITE)
+RETIRE_DEFAULTS = dict(min_expected=16, seen_num=1, seen_den=8, mode=FX_RETIRE_APPLY)
+
+
 class FxRelocalizeOptions(C.Structure):
     _fields_ = [("inlier_dist", C.c_float), ("pair_tol", C.c_float), ("min_baseline", C.c_float), ("max_baseline", C.c_float),
                 ("max_seeds", C.c_uint32), ("min_inliers", C.c_uint32), ("min_margin", C.c_uint32), ("min_landmark_obs", C.c_uint32),
@@ -394,6 +423,8 @@ EXPORTS = ("fx_version", "fx_check_abi", "fx_status_str", "fx_last_error", "fx_p
            "fx_map_merge_options_default", "fx_map_merge", "fx_map_get_alias", "fx_map_read_alias",
            "fx_localize_options_default", "fx_map_localize", "fx_relocalize_options_default", "fx_map_relocalize",
            "fx_map_observe_options_default", "fx_map_observe",
+           "fx_map_expect_options_default", "fx_map_expect_options_from_params", "fx_map_expect",
+           "fx_map_retire_options_default", "fx_map_retire",
            "fx_map_compact_options_default", "fx_map_compact", "fx_map_export_host", "fx_map_import_host", "fx_map_snapshot_check",
            "fx_map_append", "fx_map_append_host",
            "fx_map_join_options_default", "fx_map_join_segments",
@@ -539,6 +570,15 @@ def load():
     lib.fx_map_observe_options_default.restype = None
     lib.fx_map_observe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
                                    C.POINTER(FxMapObserveOptions), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.fx_map_expect_options_default.argtypes = [C.POINTER(FxMapExpectOptions)]
+    lib.fx_map_expect_options_default.restype = None
+    lib.fx_map_expect_options_from_params.argtypes = [C.POINTER(FxParams), C.c_float, C.POINTER(FxMapExpectOptions)]
+    lib.fx_map_expect_options_from_params.restype = None
+    lib.fx_map_expect.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                  C.POINTER(FxMapExpectOptions), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.fx_map_retire_options_default.argtypes = [C.POINTER(FxMapRetireOptions)]
+    lib.fx_map_retire_options_default.restype = None
+    lib.fx_map_retire.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(FxMapRetireOptions), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.fx_map_compact_options_default.argtypes = [C.POINTER(FxMapCompactOptions)]
     lib.fx_map_compact_options_default.restype = None
     lib.fx_map_compact.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(FxMapCompactOptions), C.c_void_p, C.c_void_p]
@@ -1307,6 +1347,13 @@ def map_compact_reference(state, min_obs=1, min_age_scans=64):
     """The definition of fx_map_compact (include/fx.h) in plain loops over a map_reference / map_merge_reference state, which is
     not modified; a state without "alias" has every landmark live.  Returns (the new state, remap int32 [max_landmarks], {"before",
     "kept", "dropped_absorbed", "dropped_live"})."""
+    return _map_compact(state, min_obs, min_age_scans)[:3]
+
+
+def _map_compact(state, min_obs, min_age_scans, condemned=None):
+    """fx_map_compact's clauses, which fx_map_retire runs too: condemned(i) (None: no rule) says whether the counters condemn the live
+    landmark i; one that no carry word holds is then not kept.  Returns map_compact_reference's three and {"new_id": per old id, -1
+    dropped, "retired": the old ids retired, "protected": those the carry held, "retired_obs"}."""
     min_obs, min_age = int(min_obs), int(min_age_scans) & 0xffffffff
     if min_obs < 1:
         raise ValueError("min_obs must be at least 1")
@@ -1321,12 +1368,18 @@ def map_compact_reference(state, min_obs=1, min_age_scans=64):
     carry = [int(c) for c in state["carry"]]
     carried = set(root(c) for c in carry[:int(H["carry_rows"])] if 0 <= c < N)
     new_id, K, absorbed, lost_obs = [-1] * N, 0, 0, 0
+    retired, protected, retired_obs = [], [], 0
     for i in range(N):
         if alias[i] != -1:
             absorbed += 1
             continue
         age = ((int(H["scans"]) - 1) - int(lms[i]["last_scan"])) & 0xffffffff
-        if int(lms[i]["n_obs"]) >= min_obs or age < min_age or i in carried:
+        if condemned is not None and condemned(i):
+            (protected if i in carried else retired).append(i)
+        if retired and retired[-1] == i:
+            lost_obs += int(lms[i]["n_obs"])
+            retired_obs = (retired_obs + int(lms[i]["n_obs"])) & 0xffffffff
+        elif int(lms[i]["n_obs"]) >= min_obs or age < min_age or i in carried:
             new_id[i] = K
             K += 1
         else:
@@ -1339,7 +1392,38 @@ def map_compact_reference(state, min_obs=1, min_age_scans=64):
     remap = np.full(int(state["max_landmarks"]), -1, np.int32)
     for i in range(N):
         remap[i] = new_id[root(i)]
-    return st, remap, {"before": N, "kept": K, "dropped_absorbed": absorbed, "dropped_live": N - K - absorbed}
+    return (st, remap, {"before": N, "kept": K, "dropped_absorbed": absorbed, "dropped_live": N - K - absorbed},
+            {"new_id": new_id, "retired": retired, "protected": protected, "retired_obs": retired_obs})
+
+
+def map_retire_reference(state, expected, seen, min_expected=16, seen_num=1, seen_den=8, dry_run=False):
+    """The definition of fx_map_retire (include/fx.h) over a map_reference / ... state, which is not modified: the rule on the
+    counters in Python integers (no width to overflow), then map_compact_reference's own clauses with min_obs = 1 (_map_compact: the
+    same code).  expected / seen: uint32 [max_landmarks].  Returns (the new state (the old one's content with dry_run), remap int32
+    [max_landmarks], retired_of_landmark uint8 [max_landmarks], {"before", "kept", "dropped_absorbed", "retired", "retired_obs",
+    "protected_by_carry"}, the new expected, the new seen (copies of the old with dry_run))."""
+    min_expected, num, den = int(min_expected), int(seen_num), int(seen_den)
+    if not (min_expected >= 1 and 1 <= num <= den):
+        raise ValueError("arguments outside what fx_map_retire accepts")
+    cap = int(state["max_landmarks"])
+    e, sn = (np.asarray(a).astype(np.uint32).reshape(-1) for a in (expected, seen))
+    if len(e) != cap or len(sn) != cap:
+        raise ValueError("the counter arrays have max_landmarks words")
+
+    def condemned(i):
+        return int(e[i]) >= min_expected and int(sn[i]) * den < int(e[i]) * num
+    st, remap, res, more = _map_compact(state, 1, 64, condemned)
+    mask = np.zeros(cap, np.uint8)
+    mask[more["retired"]] = 1
+    new_e, new_s = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32)
+    for i, k in enumerate(more["new_id"]):
+        if k >= 0:
+            new_e[k], new_s[k] = e[i], sn[i]
+    out = {"before": res["before"], "kept": res["kept"], "dropped_absorbed": res["dropped_absorbed"], "retired": len(more["retired"]),
+           "retired_obs": more["retired_obs"], "protected_by_carry": len(more["protected"])}
+    if dry_run:
+        return state, remap, mask, out, e.copy(), sn.copy()
+    return st, remap, mask, out, new_e, new_s
 
 
 # ---- one map appended to another (include/fx.h fx_map_append)
@@ -1733,6 +1817,119 @@ def map_observe_reference(state, kp_offset, kp_rows, loc_records, map_id_of_row,
     res = {"scans_used": int(used.sum()), "proposed": int(proposes.sum()), "added": added, "duplicates": int(passes.sum()) - added,
            "gated": int(gated.sum()), "stale": int(stale.sum()), "landmarks_touched": touched, "reserved": 0}
     return st, res, gained, observed
+
+
+# ---- negative evidence: how often a landmark should have been seen and how often it was (include/fx.h fx_map_expect)
+def expect_records(out):
+    """The 32 bytes fx_map_expect wrote (a device tensor, or an array) as a dict of MAP_EXPECT_RESULT_FIELDS."""
+    a = out.detach().cpu().numpy() if hasattr(out, "detach") else np.asarray(out)
+    w = np.ascontiguousarray(a).view(np.uint8).reshape(-1)[:32].view("<u4")
+    return dict(zip(MAP_EXPECT_RESULT_FIELDS, (int(v) for v in w)))
+
+
+def retire_records(out):
+    """The 32 bytes fx_map_retire wrote (a device tensor, or an array) as a dict of MAP_RETIRE_RESULT_FIELDS; the reserved words must be 0."""
+    a = out.detach().cpu().numpy() if hasattr(out, "detach") else np.asarray(out)
+    w = np.ascontiguousarray(a).view(np.uint8).reshape(-1)[:32].view("<u4")
+    if w[6] or w[7]:
+        raise ValueError("fx_map_retire_result.reserved is not 0")
+    return dict(zip(MAP_RETIRE_RESULT_FIELDS, (int(v) for v in w[:6])))
+
+
+def map_expect_reference(state, kp_offset, kp_rows, loc_records, map_id_of_row, n_scans, q_max_rows=None, expected=None, seen=None, **opts):
+    """The definition of fx_map_expect (include/fx.h) in numpy float64 over a map_reference / ... state, which is only read.  The
+    arguments are map_observe_reference's; opts: the fields of fx_map_expect_options (EXPECT_DEFAULTS).  expected / seen: the arrays
+    an FX_EXPECT_ADD call adds to (uint32 [max_landmarks]; not modified).  Every (used scan, eligible landmark) pair and every (pair,
+    row) triple is looked at: nothing here knows of a grid, a cell or a bucket.  One ufunc an operation, so nothing is contracted.
+    Returns ({"scans_used", "in_range", "in_box", "shadowed", "expected", "seen", "stale", "landmarks_expected"}, expected_of_landmark,
+    seen_of_landmark uint32 [max_landmarks])."""
+    f64 = np.float64
+    bad = set(opts) - set(EXPECT_DEFAULTS)
+    if bad:
+        raise TypeError(f"unknown expect options {sorted(bad)}")
+    o = dict(EXPECT_DEFAULTS, **opts)
+    off = [int(x) for x in kp_offset]
+    kp = np.ascontiguousarray(kp_rows, dtype=np.float32)
+    kp = kp.reshape(len(kp), -1)[:, :3] if kp.size else np.zeros((0, 3), np.float32)
+    n_scans = int(n_scans)
+    R = len(kp) if q_max_rows is None else int(q_max_rows)
+    x_min, x_max, y_min, y_max, r_lo, r_hi, sw = (np.float32(o[k]) for k in ("x_min", "x_max", "y_min", "y_max", "min_range", "max_range", "shadow_width"))
+    req, min_obs, segment, mode = (int(o[k]) & 0xffffffff for k in ("require_flags", "min_landmark_obs", "segment", "mode"))
+    known = FX_LOC_VALID | FX_LOC_TRUNCATED | FX_LOC_NO_HYPOTHESIS | FX_LOC_BAD_PRIOR | FX_LOC_NO_SCAN
+    if not (n_scans >= 1 and x_min <= x_max and y_min <= y_max and np.isfinite(r_lo) and r_lo >= 0 and np.isfinite(r_hi) and r_hi > 0 and
+            r_hi >= r_lo and np.isfinite(sw) and sw >= 0 and not req & ~known and min_obs >= 1 and mode <= 1):
+        raise ValueError("arguments outside what fx_map_expect accepts")
+    bx0, bx1, by0, by1 = f64(x_min), f64(x_max), f64(y_min), f64(y_max)
+    lo2, hi2, w2 = f64(r_lo) * f64(r_lo), f64(r_hi) * f64(r_hi), f64(sw) * f64(sw)
+    lms, H = state["landmarks"], state["header"]
+    cap = int(state["max_landmarks"])
+    N = min(int(H["n_landmarks"]), len(lms), cap)
+    alias = np.array([int(a) for a in state.get("alias", [])][:N] + [-1] * max(0, N - len(state.get("alias", []))), np.int64)
+    X, Y, Z = (np.array([float(r[f]) for r in lms[:N]], f64) for f in ("x", "y", "z"))
+    ln = np.array([int(r["n_obs"]) for r in lms[:N]], np.int64)
+    lseg = np.array([int(r["segment"]) for r in lms[:N]], np.int64)
+    if segment == FX_LOC_ANY_SEGMENT:
+        seg_ok = np.ones(N, bool)
+    elif segment == FX_LOC_LAST_SEGMENT:
+        seg_ok = (lseg == int(H["segments"]) - 1) if int(H["segments"]) else np.zeros(N, bool)
+    else:
+        seg_ok = lseg == segment
+    eligible = (alias == -1) & (ln >= min_obs) & np.isfinite(X) & np.isfinite(Y) & np.isfinite(Z) & seg_ok
+    loc = np.asarray(loc_records)[:n_scans]
+    S, rows = min(n_scans, len(off) - 1), min(len(kp), R)
+    ids = np.asarray(map_id_of_row)[:rows].astype(np.int64)
+    P = loc["pose"][:S]
+    used = [(int(loc["flags"][b]) & req) == req and all(np.isfinite(f64(P[f][b])) for f in ("c", "s", "tx", "ty", "tz")) for b in range(S)]
+    cnt_e, cnt_s = np.zeros(cap, np.int64), np.zeros(cap, np.int64)
+    res = {k: 0 for k in MAP_EXPECT_RESULT_FIELDS}
+    G = np.flatnonzero(eligible)
+    with np.errstate(all="ignore"):
+        for b in range(S):
+            if not used[b]:
+                continue
+            res["scans_used"] += 1
+            q_lo = min(off[b], rows)
+            q_hi = max(min(off[b + 1], rows), q_lo)
+            k = kp[q_lo:q_hi]
+            fin = np.isfinite(k).all(axis=1)
+            idb = ids[q_lo:q_hi]
+            proposes = fin & (idb >= 0) & (idb < N)
+            idc = np.where(proposes, idb, 0)
+            via = alias[idc] if N else np.zeros(len(idc), np.int64)
+            tgt = np.where(via >= 0, via, idc)
+            ok = proposes & (tgt < N) & (eligible[np.where(tgt < N, tgt, 0)] if N else False)
+            res["stale"] += int((proposes & ~ok).sum())
+            name = np.where(ok, tgt, -1)  # the landmark a row names, -1: none
+            c, s, tx, ty = (f64(P[f][b]) for f in ("c", "s", "tx", "ty"))
+            dx, dy = X[G] - tx, Y[G] - ty
+            d2 = (dx * dx) + (dy * dy)
+            lx, ly = (c * dx) + (s * dy), (c * dy) - (s * dx)
+            l2 = (lx * lx) + (ly * ly)
+            in_range = (lo2 <= d2) & (d2 <= hi2)
+            in_box = (bx0 <= lx) & (lx <= bx1) & (by0 <= ly) & (ly <= by1)
+            names_g = name[None, :] == G[:, None]  # [landmark, row]
+            seen_g = in_range & names_g.any(axis=1)
+            kx, ky = k[:, 0].astype(f64), k[:, 1].astype(f64)
+            k2 = (kx * kx) + (ky * ky)
+            along = (kx[None, :] * lx[:, None]) + (ky[None, :] * ly[:, None])
+            crs = (kx[None, :] * ly[:, None]) - (ky[None, :] * lx[:, None])
+            shadow = fin[None, :] & ~names_g & (k2[None, :] < l2[:, None]) & (along > 0) & ((crs * crs) <= (w2 * l2)[:, None])
+            shadowed = shadow.any(axis=1) if sw > 0 else np.zeros(len(G), bool)
+            exp_g = in_range & (seen_g | (in_box & ~shadowed))
+            res["in_range"] += int(in_range.sum())
+            res["in_box"] += int((in_range & in_box).sum())
+            res["shadowed"] += int((in_range & in_box & ~seen_g & shadowed).sum())
+            res["expected"] += int(exp_g.sum())
+            res["seen"] += int(seen_g.sum())
+            cnt_e[G[exp_g]] += 1
+            cnt_s[G[seen_g]] += 1
+    res["landmarks_expected"] = int((cnt_e > 0).sum())
+    if mode == FX_EXPECT_ADD:
+        base_e, base_s = (np.asarray(a).astype(np.int64).reshape(-1) for a in (expected, seen))
+        if len(base_e) != cap or len(base_s) != cap:
+            raise ValueError("the counter arrays have max_landmarks words")
+        cnt_e, cnt_s = (base_e + cnt_e) & 0xffffffff, (base_s + cnt_s) & 0xffffffff
+    return res, cnt_e.astype(np.uint32), cnt_s.astype(np.uint32)
 
 
 # ---- two segments of the map made one (include/fx.h fx_map_join_segments)
@@ -2579,6 +2776,47 @@ class Map:
         with _on_stream(self.ctx.stream_ptr(), dev):
             check(self.lib.fx_map_compact(self.ctx.handle, self.handle, C.byref(opt), _ptr(remap), _ptr(result)))
         return remap, result
+
+    def expect(self, kp, loc, n_scans, map_id_of_row, q_max_rows=None, out=None, expected=None, seen=None, **opts):
+        """fx_map_expect: per landmark, how many of the localised scans should have seen it and how many did (include/fx.h).  kp, loc,
+        n_scans, map_id_of_row and q_max_rows are observe()'s.  opts: the fields of fx_map_expect_options (EXPECT_DEFAULTS).
+        expected / seen: device torch.int32 tensors [max_landmarks] to write (mode FX_EXPECT_WRITE) or to add to (FX_EXPECT_ADD: give
+        them); None allocates them, zeroed.  Returns (result, expected, seen): result a device torch.int32 tensor [8] (expect_records
+        reads it); out reuses one, False passes NULL.  Stream-correct like update(); never waits for the stream."""
+        import torch
+        kb, scans, total = kp
+        dev = torch.device("cuda", self.ctx.device)
+        n_rows = int(total) if q_max_rows is None else int(q_max_rows)
+        opt = _options(FxMapExpectOptions, EXPECT_DEFAULTS, "expect", opts)
+        error = f"outputs must be contiguous torch.int32 tensors [8], [{self.max_landmarks}] and [{self.max_landmarks}] on {dev}"
+        out = _out_tensor(out, (8,), torch.int32, dev, error, typed=True)
+        expected, seen = (torch.zeros(self.max_landmarks, dtype=torch.int32, device=dev) if t is None else
+                          _out_tensor(t, (self.max_landmarks,), torch.int32, dev, error, typed=True) for t in (expected, seen))
+        with _on_stream(self.ctx.stream_ptr(), dev):
+            check(self.lib.fx_map_expect(self.ctx.handle, self.handle, C.c_void_p(kb.data_ptr()), int(scans), int(total), C.c_void_p(loc.data_ptr()),
+                                         int(n_scans), C.c_void_p(map_id_of_row.data_ptr() if n_rows else None), n_rows, C.byref(opt), _ptr(out),
+                                         _ptr(expected), _ptr(seen)))
+        return out, expected, seen
+
+    def retire(self, expected, seen, remap=None, retired=None, result=None, **opts):
+        """fx_map_retire: the landmarks that expect()'s counters condemn taken out, the others renumbered as compact() does, the
+        counters renumbered with them (include/fx.h).  expected / seen: the device torch.int32 tensors [max_landmarks] that
+        expect() accumulated.  opts: the fields of fx_map_retire_options (RETIRE_DEFAULTS).  Returns (remap, retired, result): device
+        tensors torch.int32 [max_landmarks], torch.uint8 [max_landmarks] (1: a retired old id) and torch.int32 [8] (retire_records
+        reads it); a tensor given reuses it, False passes NULL (None is returned in its place).  Never waits for the stream."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        n = self.max_landmarks
+        opt = _options(FxMapRetireOptions, RETIRE_DEFAULTS, "retire", opts)
+        for t in (expected, seen):
+            _out_tensor(t, (n,), torch.int32, dev, f"the counters must be contiguous torch.int32 tensors [{n}] on {dev}", typed=True)
+        remap = _out_tensor(remap, (n,), torch.int32, dev, f"remap must be a contiguous torch.int32 tensor [{n}] on {dev}", typed=True)
+        retired = _out_tensor(retired, (n,), torch.uint8, dev, f"retired must be a contiguous torch.uint8 tensor [{n}] on {dev}", typed=True)
+        result = _out_tensor(result, (8,), torch.int32, dev, f"result must be a contiguous torch.int32 tensor [8] on {dev}", typed=True)
+        with _on_stream(self.ctx.stream_ptr(), dev):
+            check(self.lib.fx_map_retire(self.ctx.handle, self.handle, _ptr(expected), _ptr(seen), C.byref(opt), _ptr(remap), _ptr(retired),
+                                         _ptr(result)))
+        return remap, retired, result
 
     def join_segments(self, src, dst, prior=None, prior_device=None, result=None, match=None, **opts):
         """fx_map_join_segments: the landmarks of segment src brought into segment dst's frame, the two segments made one

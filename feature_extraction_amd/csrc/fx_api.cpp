@@ -97,6 +97,8 @@ hipError_t fxk_map_relocalize(hipStream_t s, const FxMapRelocalizeArgs &A);
 size_t fxk_map_relocalize_scratch(FxMapRelocalizeArgs *A, uint8_t *base);
 hipError_t fxk_map_observe(hipStream_t s, const FxMapObserveArgs &A);
 size_t fxk_map_observe_scratch(FxMapObserveArgs *A, uint8_t *base);
+hipError_t fxk_map_expect(hipStream_t s, const FxMapExpectArgs &A);
+size_t fxk_map_expect_scratch(FxMapExpectArgs *A, uint8_t *base);
 hipError_t fxk_map_find_loop(hipStream_t s, const FxMapFindLoopArgs &A);
 size_t fxk_map_find_loop_scratch(FxMapFindLoopArgs *A, uint8_t *base);
 hipError_t fxk_map_compact(hipStream_t s, const FxMapCompactArgs &A);
@@ -281,7 +283,9 @@ struct fx_ctx {
   DevScratch merge_scratch;  // fx_map_merge: the grid (bucket counts, landmarks in bucket order), proposals, kept links;
                              // fx_map_localize: the same grid, then each row's landmark and distance;
                              // fx_map_observe: the landmarks' list counts, cursors and prefix, each row's target and distance, the lists;
+                             // fx_map_expect: the grid, this call's counts of both kinds, each row's named landmark;
                              // fx_map_compact: the marks, the new ids, the blocks' counts, the kept records and sums staged;
+                             // fx_map_retire: the same, and the kept landmarks' counters staged;
                              // fx_map_append: the state words; fx_map_append_host: the snapshot's bytes before them;
                              // fx_map_join_segments, fx_map_close_loop: the grid, each query's target and distance, the list of
                              // correspondences
@@ -2169,6 +2173,62 @@ fx_status fx_map_observe(fx_ctx *c, fx_map *m, const void *kp, uint32_t max_scan
   return FX_OK;
 }
 
+void fx_map_expect_options_default(fx_map_expect_options *o) {
+  if (!o) return;
+  o->x_min = 1.f, o->x_max = 74.f, o->y_min = -29.f, o->y_max = 29.f;
+  o->min_range = 2.0f, o->max_range = 60.0f;
+  o->shadow_width = 0.5f;
+  o->require_flags = FX_LOC_VALID;
+  o->min_landmark_obs = 2u;
+  o->segment = FX_LOC_ANY_SEGMENT;
+  o->mode = FX_EXPECT_WRITE;
+  o->reserved = 0u;
+}
+
+void fx_map_expect_options_from_params(const fx_params *p, float margin, fx_map_expect_options *o) {
+  if (!o) return;
+  fx_map_expect_options_default(o);
+  if (!p) return;
+  o->x_min = (float)p->x_min + margin, o->x_max = (float)p->x_max - margin;
+  o->y_min = (float)p->y_min + margin, o->y_max = (float)p->y_max - margin;
+}
+
+fx_status fx_map_expect(fx_ctx *c, fx_map *m, const void *kp, uint32_t max_scans, uint32_t max_total, const fx_localization *loc, uint32_t n_scans,
+                        const int32_t *map_id_of_row, uint32_t q_max_rows, const fx_map_expect_options *opt, fx_map_expect_result *result,
+                        uint32_t *expected_of_landmark, uint32_t *seen_of_landmark) {
+  FX_TRY(map_call_check(c, m, kp && loc && !(q_max_rows && !map_id_of_row) && expected_of_landmark && seen_of_landmark));
+  if (!n_scans || n_scans > max_scans)
+    return fail(FX_ERR_INVALID_ARG, "n_scans must be 1..max_scans (" + std::to_string(n_scans) + " of " + std::to_string(max_scans) + ")");
+  fx_map_expect_options o;
+  fx_map_expect_options_default(&o);
+  if (opt) o = *opt;
+  if (!(o.x_min <= o.x_max) || !(o.y_min <= o.y_max)) return fail(FX_ERR_INVALID_ARG, "the box needs x_min <= x_max and y_min <= y_max, and no NaN");
+  if (!(std::isfinite(o.min_range) && o.min_range >= 0.f)) return fail(FX_ERR_INVALID_ARG, "min_range must be finite and not negative");
+  if (!(std::isfinite(o.max_range) && o.max_range > 0.f && o.max_range >= o.min_range))
+    return fail(FX_ERR_INVALID_ARG, "max_range must be finite, positive and at least min_range");
+  if (!(std::isfinite(o.shadow_width) && o.shadow_width >= 0.f)) return fail(FX_ERR_INVALID_ARG, "shadow_width must be finite and not negative");
+  const uint32_t known = FX_LOC_VALID | FX_LOC_TRUNCATED | FX_LOC_NO_HYPOTHESIS | FX_LOC_BAD_PRIOR | FX_LOC_NO_SCAN;
+  if (o.require_flags & ~known) return fail(FX_ERR_INVALID_ARG, "unknown require_flags bits (only the FX_LOC_* flags are defined)");
+  if (!o.min_landmark_obs) return fail(FX_ERR_INVALID_ARG, "min_landmark_obs must be at least 1");
+  if (o.mode != FX_EXPECT_WRITE && o.mode != FX_EXPECT_ADD) return fail(FX_ERR_INVALID_ARG, "unknown mode (FX_EXPECT_WRITE or FX_EXPECT_ADD)");
+  if (o.reserved) return fail(FX_ERR_INVALID_ARG, "reserved must be 0");
+  if (((uintptr_t)kp % 16) != 0 || ((uintptr_t)loc % 8) != 0 || ((uintptr_t)map_id_of_row % 4) != 0 || ((uintptr_t)result % 4) != 0 ||
+      ((uintptr_t)expected_of_landmark % 4) != 0 || ((uintptr_t)seen_of_landmark % 4) != 0)
+    return fail(FX_ERR_INVALID_ARG, "the keypoint block must be 16-byte, the records 8-byte, the words 4-byte aligned");
+  FX_HIP(hipSetDevice(c->device));
+  FxMapExpectArgs A{};
+  map_grid_view(&A.G, m, (double)o.max_range);
+  A.kp = (const uint32_t *)kp, A.max_scans = max_scans, A.max_total = max_total;
+  A.loc = loc, A.n_scans = n_scans, A.map_id_of_row = map_id_of_row, A.q_max_rows = q_max_rows;
+  A.x_min = (double)o.x_min, A.x_max = (double)o.x_max, A.y_min = (double)o.y_min, A.y_max = (double)o.y_max;
+  A.lo2 = (double)o.min_range * (double)o.min_range, A.hi2 = (double)o.max_range * (double)o.max_range;
+  A.w2 = (double)o.shadow_width * (double)o.shadow_width;
+  A.require_flags = o.require_flags, A.min_landmark_obs = o.min_landmark_obs, A.segment = o.segment, A.mode = o.mode;
+  A.result = (uint32_t *)result, A.expected = expected_of_landmark, A.seen = seen_of_landmark;
+  FX_MAP_RUN(fxk_map_expect, "map expect scratch");
+  return FX_OK;
+}
+
 fx_status fx_map_get_alias(fx_map *m, const int32_t **alias) {
   if (!m || !alias) return fail(FX_ERR_INVALID_ARG, "null argument");
   *alias = m->a.alias;
@@ -2204,6 +2264,42 @@ fx_status fx_map_compact(fx_ctx *c, fx_map *m, const fx_map_compact_options *opt
   A.min_obs = o.min_obs, A.min_age = o.min_age_scans;
   A.remap = remap, A.result = (uint32_t *)result;
   FX_MAP_RUN(fxk_map_compact, "map compact scratch");
+  return FX_OK;
+}
+
+void fx_map_retire_options_default(fx_map_retire_options *o) {
+  if (!o) return;
+  o->min_expected = 16u;
+  o->seen_num = 1u, o->seen_den = 8u;
+  o->mode = FX_RETIRE_APPLY;
+  o->reserved[0] = o->reserved[1] = 0u;
+}
+
+fx_status fx_map_retire(fx_ctx *c, fx_map *m, uint32_t *expected_of_landmark, uint32_t *seen_of_landmark, const fx_map_retire_options *opt,
+                        int32_t *remap, uint8_t *retired_of_landmark, fx_map_retire_result *result) {
+  FX_TRY(map_call_check(c, m, expected_of_landmark && seen_of_landmark));
+  fx_map_retire_options o;
+  fx_map_retire_options_default(&o);
+  if (opt) o = *opt;
+  if (!o.min_expected) return fail(FX_ERR_INVALID_ARG, "min_expected must be at least 1");
+  if (!o.seen_den || !o.seen_num || o.seen_num > o.seen_den) return fail(FX_ERR_INVALID_ARG, "the ratio needs 1 <= seen_num <= seen_den");
+  if (o.mode != FX_RETIRE_APPLY && o.mode != FX_RETIRE_DRY_RUN) return fail(FX_ERR_INVALID_ARG, "unknown mode (FX_RETIRE_APPLY or FX_RETIRE_DRY_RUN)");
+  if (o.reserved[0] || o.reserved[1]) return fail(FX_ERR_INVALID_ARG, "reserved must be 0");
+  if (((uintptr_t)expected_of_landmark % 4) != 0 || ((uintptr_t)seen_of_landmark % 4) != 0 || ((uintptr_t)remap % 4) != 0 ||
+      ((uintptr_t)result % 4) != 0)
+    return fail(FX_ERR_INVALID_ARG, "the counters, remap and the result must be 4-byte aligned");
+  FX_HIP(hipSetDevice(c->device));
+  fx_map_compact_options k;
+  fx_map_compact_options_default(&k);  // min_obs 1: the compaction itself drops nothing live
+  FxMapCompactArgs A{};
+  A.header = m->a.header, A.records = m->a.records, A.acc = m->a.acc, A.carry = m->a.carry, A.alias = m->a.alias;
+  A.cap = m->a.cap, A.max_carry = m->a.max_carry;
+  A.min_obs = k.min_obs, A.min_age = k.min_age_scans;
+  A.remap = remap, A.result = (uint32_t *)result;
+  A.expected = expected_of_landmark, A.seen = seen_of_landmark;
+  A.min_expected = o.min_expected, A.seen_num = o.seen_num, A.seen_den = o.seen_den, A.dry_run = o.mode == FX_RETIRE_DRY_RUN ? 1u : 0u;
+  A.retired = retired_of_landmark;
+  FX_MAP_RUN(fxk_map_compact, "map retire scratch");
   return FX_OK;
 }
 

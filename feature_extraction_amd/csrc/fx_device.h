@@ -347,7 +347,10 @@ struct FxMapRelocalizeArgs {
 };
 // fx_map_compact (csrc/fx_map_compact.hip): a launch set's arguments.  The first group is the map's own memory, the last the
 // context's scratch, sized by the map's max_landmarks (cap).
-#define FX_MAP_COMPACT_ST_WORDS 4  // 0 K: landmarks kept, 1 observations of the dropped live landmarks, 2 absorbed landmarks dropped
+// fx_map_retire runs the same launches with a rule (expected given): a landmark the counters condemn is not kept, and the counters
+// move with the landmarks; fx_map_compact passes no rule.
+#define FX_MAP_COMPACT_ST_WORDS 8  // 0 K: landmarks kept, 1 observations of the dropped live landmarks, 2 absorbed landmarks dropped,
+                                   // 3 retired landmarks, 4 their observations, 5 protected by the carry (3 .. 5: fx_map_retire)
 struct FxMapCompactArgs {
   void *header;                 // fx_map_header
   void *records;                // fx_map_landmark [cap]
@@ -363,6 +366,32 @@ struct FxMapCompactArgs {
   int32_t *local;               // [cap]: a kept landmark's exclusive prefix within its block of 256, -1: dropped
   uint32_t *bsum;               // [2][blocks of landmarks]: the block's kept landmarks / dropped live observations, then their prefix
   uint4 *stage_rec, *stage_acc; // [cap][3], [cap][4]: the kept records and sums at their new ids, before they are copied back
+  // fx_map_retire's rule; expected null: no rule (fx_map_compact), and nothing below is read
+  uint32_t *expected, *seen;    // [cap]: the caller's counters, read by the rule and renumbered with the landmarks
+  uint32_t min_expected, seen_num, seen_den, dry_run;
+  uint8_t *retired;             // [cap] or null: 1 for a retired old id
+  uint32_t *stage_cnt;          // [2][cap]: the kept landmarks' counters at their new ids
+};
+// fx_map_expect (csrc/fx_map_expect.hip): a launch set's arguments.  G describes the grid over the map (its gate is max_range; the
+// merge's per-landmark arrays are null); the last group is the context's scratch, sized by the map's max_landmarks (G.cap) and by
+// q_max_rows.
+#define FX_MAP_EXPECT_ST_WORDS 8  // the words of fx_map_expect_result, in its order
+struct FxMapExpectArgs {
+  FxMapMergeArgs G;
+  const uint32_t *kp;           // keypoint block (include/fx.h fx_pack_keypoint_block)
+  uint32_t max_scans, max_total;
+  const void *loc;              // fx_localization [n_scans]
+  uint32_t n_scans, q_max_rows;
+  const int32_t *map_id_of_row; // [q_max_rows]
+  double x_min, x_max, y_min, y_max;  // the options' floats widened
+  double lo2, hi2, w2;          // (double)min_range, max_range and shadow_width squared
+  uint32_t require_flags, min_landmark_obs, segment, mode;
+  uint32_t *result;             // fx_map_expect_result or null
+  uint32_t *expected, *seen;    // [cap]: the caller's arrays
+  uint32_t *cnt_e;              // [cap]: this call's expected counts; cnt_s and st follow it (one memset clears the three)
+  uint32_t *cnt_s;              // [cap]: ... seen counts
+  uint32_t *st;                 // [FX_MAP_EXPECT_ST_WORDS]
+  int32_t *tgt;                 // [q_max_rows]: the landmark the row names, -1: a finite row of a used scan that names none, -2: any other
 };
 // fx_map_append, fx_map_append_host (csrc/fx_map_append.hip): a launch set's arguments.  The source as the kernels read it is six
 // pointers: a map's own buffers, or the sections of a snapshot staged in the context's scratch; the two look the same.

@@ -22,6 +22,12 @@
 //   k_mc_stage   a thread a 16-byte vector of a landmark: a kept one's vector to its new id's place in the scratch
 //   k_mc_remap   a thread a landmark / carry row: remap[], and every carry word >= 0 to its root's new id
 //   k_mc_finish  a thread a vector: the scratch back into the map; alias[i] = -1; one lane: the header and the result
+//
+// fx_map_retire (include/fx.h) is this compaction with a rule: A.expected / A.seen given, k_mc_flag also drops the live landmarks the
+// counters condemn (unless a carry row holds them) and writes the byte mask; two more launches move the counters with the landmarks,
+// staged like the records (k_mc_stage_counters behind k_mc_top, k_mc_finish_counters last).  A dry run launches the mark, the flags,
+// the prefix, the remap without its carry half and one lane of the finish.  Without a rule (fx_map_compact) every branch on it is a
+// uniform scalar test and nothing else runs.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -36,7 +42,7 @@
 #define FXMC_V (FXMC_REC_V + FXMC_ACC_V)
 
 static_assert(sizeof(fx_map_landmark) == FXMC_REC_V * 16 && FX_MAP_ACC * sizeof(double) == FXMC_ACC_V * 16 && sizeof(fx_map_header) == 88 &&
-                  sizeof(fx_map_compact_result) == 16,
+                  sizeof(fx_map_compact_result) == 16 && sizeof(fx_map_retire_result) == 32 && sizeof(fx_map_retire_options) == 24,
               "include/fx.h");
 
 namespace {
@@ -53,6 +59,11 @@ __device__ __forceinline__ int32_t new_id(const FxMapCompactArgs &A, uint32_t i)
   const int32_t local = A.local[i];
   return local >= 0 ? (int32_t)(A.bsum[i / FXMC_WG] + (uint32_t)local) : -1;
 }
+// fx_map_retire's result (one lane, behind k_mc_top)
+__device__ __forceinline__ void write_retire_result(const FxMapCompactArgs &A, uint32_t N, uint32_t K) {
+  A.result[0] = N, A.result[1] = K, A.result[2] = A.st[2], A.result[3] = A.st[3], A.result[4] = A.st[4], A.result[5] = A.st[5];
+  A.result[6] = A.result[7] = 0u;
+}
 }  // namespace
 
 extern "C" __global__ __launch_bounds__(FXMC_WG) void k_mc_mark(FxMapCompactArgs A) {
@@ -68,13 +79,25 @@ extern "C" __global__ __launch_bounds__(FXMC_WG) void k_mc_flag(FxMapCompactArgs
   const uint32_t i = blockIdx.x * FXMC_WG + threadIdx.x;
   const uint32_t N = n_landmarks(A);
   uint32_t kept = 0u, lost_obs = 0u;
-  bool absorbed = false;
+  bool absorbed = false, retired = false, held = false;
   if (i < N) {
     const fx_map_landmark *R = reinterpret_cast<const fx_map_landmark *>(A.records) + i;
     absorbed = A.alias[i] != -1;
     const uint32_t n_obs = R->n_obs, age = (header(A)->scans - 1u) - R->last_scan;
     kept = !absorbed && (n_obs >= A.min_obs || age < A.min_age || A.mark[i] != 0u) ? 1u : 0u;
+    if (A.expected && !absorbed) {  // fx_map_retire's rule: expected often enough, seen too rarely, and no carry row holds it
+      const uint32_t e = A.expected[i], sn = A.seen[i];
+      const bool condemned = e >= A.min_expected && (unsigned long long)sn * A.seen_den < (unsigned long long)e * A.seen_num;
+      retired = condemned && A.mark[i] == 0u, held = condemned && A.mark[i] != 0u;
+      if (retired) kept = 0u, atomicAdd(&A.st[4], n_obs);
+    }
     lost_obs = !absorbed && !kept ? n_obs : 0u;
+  }
+  if (A.expected) {
+    if (A.retired && i < A.cap) A.retired[i] = retired ? 1u : 0u;
+    const unsigned long long r = __ballot(retired), h = __ballot(held);
+    if ((threadIdx.x & 63u) == 0u && r) atomicAdd(&A.st[3], (uint32_t)__popcll(r));
+    if ((threadIdx.x & 63u) == 0u && h) atomicAdd(&A.st[5], (uint32_t)__popcll(h));
   }
   uint32_t ea, eb, ta, tb;
   wg_scan2<FXMC_NWAVE>(kept, lost_obs, s_w, ea, eb, ta, tb);
@@ -108,7 +131,7 @@ extern "C" __global__ __launch_bounds__(FXMC_WG) void k_mc_remap(FxMapCompactArg
   const uint32_t i = blockIdx.x * FXMC_WG + threadIdx.x;
   const uint32_t N = n_landmarks(A);
   if (A.remap && i < A.cap) A.remap[i] = i < N ? new_id(A, root_of(A, i, N)) : -1;  // (a dropped live one is its own root: -1)
-  if (i < n_carry(A)) {
+  if (i < n_carry(A) && !A.dry_run) {
     const int32_t c = A.carry[i];
     if (c >= 0) A.carry[i] = (uint32_t)c < N ? new_id(A, root_of(A, (uint32_t)c, N)) : -1;
   }
@@ -117,6 +140,10 @@ extern "C" __global__ __launch_bounds__(FXMC_WG) void k_mc_remap(FxMapCompactArg
 extern "C" __global__ __launch_bounds__(FXMC_WG) void k_mc_finish(FxMapCompactArgs A) {
   const size_t t = (size_t)blockIdx.x * FXMC_WG + threadIdx.x;
   const uint32_t K = min(A.st[0], A.cap);
+  if (A.dry_run) {  // (fx_map_retire alone: one workgroup, and only the result is written)
+    if (!t && A.result) write_retire_result(A, n_landmarks(A), K);
+    return;
+  }
   if (t < (size_t)K * FXMC_REC_V) reinterpret_cast<uint4 *>(A.records)[t] = A.stage_rec[t];
   if (t < (size_t)K * FXMC_ACC_V) reinterpret_cast<uint4 *>(A.acc)[t] = A.stage_acc[t];
   if (t < A.cap) A.alias[t] = -1;
@@ -126,7 +153,26 @@ extern "C" __global__ __launch_bounds__(FXMC_WG) void k_mc_finish(FxMapCompactAr
   const uint32_t N = min(H->n_landmarks, A.cap);
   H->n_landmarks = H->n_needed = K;
   H->n_obs -= A.st[1];
-  if (A.result) A.result[0] = N, A.result[1] = K, A.result[2] = A.st[2], A.result[3] = N - K - A.st[2];
+  if (A.result && !A.expected) A.result[0] = N, A.result[1] = K, A.result[2] = A.st[2], A.result[3] = N - K - A.st[2];
+  if (A.result && A.expected) write_retire_result(A, N, K);
+}
+
+// fx_map_retire: a thread a landmark, a kept one's two counters to its new id's place in the scratch
+extern "C" __global__ __launch_bounds__(FXMC_WG) void k_mc_stage_counters(FxMapCompactArgs A) {
+  const uint32_t i = blockIdx.x * FXMC_WG + threadIdx.x;
+  if (i >= n_landmarks(A)) return;
+  const int32_t id = new_id(A, i);
+  if (id < 0) return;  // (id <= i < cap: inside the scratch)
+  A.stage_cnt[id] = A.expected[i], A.stage_cnt[(size_t)A.cap + (uint32_t)id] = A.seen[i];
+}
+
+// fx_map_retire: a thread a word of each counter array: the staged counters back, 0 from K on
+extern "C" __global__ __launch_bounds__(FXMC_WG) void k_mc_finish_counters(FxMapCompactArgs A) {
+  const uint32_t t = blockIdx.x * FXMC_WG + threadIdx.x;
+  const uint32_t K = min(A.st[0], A.cap);
+  if (t >= A.cap) return;
+  A.expected[t] = t < K ? A.stage_cnt[t] : 0u;
+  A.seen[t] = t < K ? A.stage_cnt[(size_t)A.cap + t] : 0u;
 }
 
 extern "C" hipError_t fxk_map_compact(hipStream_t s, const FxMapCompactArgs &A) {
@@ -142,9 +188,16 @@ extern "C" hipError_t fxk_map_compact(hipStream_t s, const FxMapCompactArgs &A) 
   if (nc) hipLaunchKernelGGL(k_mc_mark, dim3(nc), wg, 0, s, A);
   hipLaunchKernelGGL(k_mc_flag, dim3(nl), wg, 0, s, A, nl);
   hipLaunchKernelGGL(k_mc_top, dim3(1), wg, 0, s, A, nl);
+  if (A.dry_run) {  // (fx_map_retire alone)
+    hipLaunchKernelGGL(k_mc_remap, dim3(nl), wg, 0, s, A);
+    hipLaunchKernelGGL(k_mc_finish, dim3(1), wg, 0, s, A);
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL(k_mc_stage, dim3(nv), wg, 0, s, A);
+  if (A.expected) hipLaunchKernelGGL(k_mc_stage_counters, dim3(nl), wg, 0, s, A);
   hipLaunchKernelGGL(k_mc_remap, dim3(nr), wg, 0, s, A);
   hipLaunchKernelGGL(k_mc_finish, dim3(nf), wg, 0, s, A);
+  if (A.expected) hipLaunchKernelGGL(k_mc_finish_counters, dim3(nl), wg, 0, s, A);
   return hipGetLastError();
 }
 
@@ -158,5 +211,6 @@ extern "C" size_t fxk_map_compact_scratch(FxMapCompactArgs *A, uint8_t *base) {
   A->st = base ? A->mark + cap : (uint32_t *)nullptr;
   A->local = C.take<int32_t>(cap);
   A->bsum = C.take<uint32_t>(2u * nb);
+  A->stage_cnt = A->expected ? C.take<uint32_t>(2u * cap) : (uint32_t *)nullptr;
   return C.o;
 }

@@ -963,7 +963,9 @@ fx_status fx_map_relocalize(fx_ctx *ctx, fx_map *map,
  * place a landmark in the mapping run's trajectory (the merge's disjointness and the loop closure's weights rest on that), and a
  * localised scan is not part of that trajectory.  Scans that also go through fx_map_update are counted twice, and nothing detects
  * that.  n_obs is a 32-bit count.  One lane folds a landmark's list and every entry of a list is ranked against the whole list:
- * time, not the result, grows with the longest list.  New in 0.7 (added symbols only). */
+ * time, not the result, grows with the longest list.  New in 0.7 (added symbols only).
+ * The call removes no landmark either: fx_map_expect (below) counts, from the same inputs, how often each landmark should have
+ * been seen and how often it was, and fx_map_retire (below fx_map_compact) takes out the ones those counts condemn. */
 #define FX_MAP_LM_OBSERVED 0x8u   /* fx_map_landmark flags: gained at least one observation through fx_map_observe */
 #define FX_OBS_APPLY 0u
 #define FX_OBS_DRY_RUN 1u         /* report everything, change no byte of the map */
@@ -983,6 +985,83 @@ fx_status fx_map_observe(fx_ctx *ctx, fx_map *map,
     const int32_t *map_id_of_row_device, uint32_t q_max_rows,
     const fx_map_observe_options *opt /* NULL: defaults */, fx_map_observe_result *result_device /* or NULL */,
     uint32_t *gained_of_landmark_device /* [max_landmarks] or NULL */, int32_t *observed_id_of_row_device /* [q_max_rows] or NULL */);
+
+/* ---- Negative evidence: per landmark, how often localised scans should have seen it and how often they did ----
+ * A pole that was cut down, a sign that was moved, a false landmark from a parked lorry: fx_map_compact lets go only of short, old
+ * landmarks, and a real pole that stood for a thousand scans passes both tests for ever.  fx_map_expect counts, for every landmark,
+ * the scans of a localised run that should have seen it (expected) and the scans that did (seen); fx_map_retire (below
+ * fx_map_compact) takes out the landmarks that are expected again and again and never seen.  The inputs are exactly
+ * fx_map_observe's, so the two calls can follow one fx_map_localize in either order (fx_map_relocalize records under the same
+ * caveat as there).  The call is enqueued on the context's stream: no host read, no host synchronisation, no allocation in the
+ * steady state (its scratch is the context-owned buffer of fx_map_merge, sized by the map's max_landmarks and by q_max_rows).  It
+ * READS the map only: a snapshot before and after is byte-identical.  Every floating-point step is fp64 with no contraction and
+ * no fma, and every float (a keypoint's x and y, the options) is widened to double first.
+ * Sizes: S, rows, scan(r) and the non-rows exactly as in fx_map_localize; N = header.n_landmarks, clipped to the map's
+ * max_landmarks.
+ * Used scans: scan b < S is used iff (loc[b].flags & require_flags) == require_flags and c, s, tx, ty and tz of loc[b].pose are all
+ * finite.  require_flags == 0 uses every scan of a finite pose; a pose that is not finite is never used.  scans_used counts them.
+ * Eligible landmarks: with N = header.n_landmarks as it is when the call runs, g < N is eligible iff alias[g] == -1, n_obs >=
+ * min_landmark_obs, its x, y and z are finite and its segment passes opt.segment: FX_LOC_ANY_SEGMENT passes every segment,
+ * FX_LOC_LAST_SEGMENT stands for header.segments - 1 read on the device (nothing is eligible in a map of no segment), any other
+ * value is the global segment number itself.
+ * Naming: row r < rows of a used scan proposes iff its x, y and z are finite and id = map_id_of_row[r] satisfies 0 <= id < N
+ * (anything else proposes nothing: -1, garbage, ids at or beyond N; that makes the call memory-safe on any table).  Its target is
+ * g = alias[id] >= 0 ? alias[id] : id.  If g is eligible the row NAMES g; otherwise it counts in `stale` and names nothing.
+ * Geometry of an eligible g at (X, Y) under the used scan b of pose (c, s, tx, ty): dx = X - tx, dy = Y - ty, d2 = (dx dx) + (dy dy),
+ * lx = (c dx) + (s dy), ly = (c dy) - (s dx), l2 = (lx lx) + (ly ly): (lx, ly) is the landmark in the scan's levelled sensor frame.
+ * In range iff lo2 <= d2 <= hi2, lo2 = (double)min_range (double)min_range, hi2 = (double)max_range (double)max_range.  d2 is taken
+ * in the map frame on purpose: it is the form the grid's one-cell-apart proof covers.  A NaN fails.
+ * In box iff x_min <= lx <= x_max and y_min <= ly <= y_max.  Keypoints are centroids of points that survived the pass-through box
+ * in the levelled sensor frame, so the box, not a cone, is this sensor's field of view.
+ * Seen(b, g) iff in range and some row of scan b names g.
+ * Shadowed(b, g) iff shadow_width > 0 and some row k of scan b, at (kx, ky) widened, meets all of: kx, ky and kz are finite (its id
+ * does not matter); it does not name g; k2 = (kx kx) + (ky ky) < l2; (kx lx) + (ky ly) > 0; with crs = (kx ly) - (ky lx): (crs crs)
+ * <= (w2 l2), w2 = (double)shadow_width (double)shadow_width.  In words: a detected object stands nearer on the same ray (within
+ * shadow_width of it), so not seeing g is no evidence.
+ * Expected(b, g) iff in range and (Seen or (in box and not Shadowed)).  Hence seen <= expected for every landmark, always.
+ * Counts: expected[g] = the number of used scans b with Expected(b, g), seen[g] the number with Seen(b, g).  FX_EXPECT_WRITE: all
+ * max_landmarks words of both arrays are written, 0 where nothing counts.  FX_EXPECT_ADD: a word whose count is non-zero gains it in
+ * uint32 arithmetic (wrapping); every other word keeps its bytes: the caller zeroes the arrays once and accumulates over many calls.
+ * Result (when given), 32 B: scans_used; in_range, in_box, shadowed, expected and seen are counts of pairs (b, g), b used and g
+ * eligible: in_range the pairs in range, in_box those in range and in box, shadowed those in range, in box, not seen and shadowed;
+ * stale as above; landmarks_expected the number of landmarks with a non-zero expected count from this call.
+ * FX_ERR_INVALID_ARG with the reason in fx_last_error(), nothing launched, no output byte touched: a NULL ctx, map,
+ * kp_block_device or loc_device; a NULL map_id_of_row_device with q_max_rows != 0; either count array NULL; a map of another
+ * context; n_scans == 0 or n_scans > max_scans; x_min > x_max or y_min > y_max or a bound that is NaN; min_range not finite or
+ * negative; max_range not finite, not positive or below min_range; shadow_width not finite or negative; unknown require_flags bits;
+ * min_landmark_obs == 0; mode > 1; reserved != 0; a keypoint block not 16-byte, records not 8-byte, word arrays not 4-byte aligned.
+ * The same bytes from run to run and with any number of contexts in flight: every decision is a comparison of correctly rounded
+ * fp64 values, every count a 32-bit integer sum (integer atomics only; no floating-point atomics anywhere), and the search
+ * structure (fx_map_merge's hashed grid with the cell edge max_range (1 + 2^-8)) never shows in a byte.
+ * Limits: z takes no part: a centroid's z depends on the rings that hit it.  Occlusion by things that are not keypoints (a wall, a
+ * lorry) is unknowable here: it is what fx_map_retire's ratio is for.  Scans also folded by fx_map_update are counted like any
+ * other.  The counters are the caller's, not the map's: the snapshot format does not change.  One lane takes a landmark in range
+ * and walks the scan's rows: time, not the result, grows with rows x landmarks in range.  New in 0.7 (added symbols only). */
+#define FX_EXPECT_WRITE 0u
+#define FX_EXPECT_ADD 1u          /* add this call's non-zero counts to the arrays, leave every other word alone */
+typedef struct fx_map_expect_options {    /* 48 B */
+  float x_min, x_max, y_min, y_max;  /* the field of view in the levelled sensor frame; default 1, 74, -29, 29: fx_params_default's box drawn in by 1 m */
+  float min_range, max_range;        /* xy distance sensor to landmark; finite, 0 <= min <= max, max > 0; default 2.0, 60.0 */
+  float shadow_width;                /* half width of a nearer keypoint's shadow; finite, >= 0, 0: no shadows; default 0.5 */
+  uint32_t require_flags;            /* FX_LOC_* bits a scan's record must carry to be used; default FX_LOC_VALID */
+  uint32_t min_landmark_obs;         /* >= 1; default 2 */
+  uint32_t segment;                  /* FX_LOC_ANY_SEGMENT (default), FX_LOC_LAST_SEGMENT or a segment number */
+  uint32_t mode;                     /* FX_EXPECT_WRITE (default), FX_EXPECT_ADD */
+  uint32_t reserved;                 /* 0 */
+} fx_map_expect_options;
+typedef struct fx_map_expect_result {     /* 32 B */
+  uint32_t scans_used, in_range, in_box, shadowed, expected, seen, stale, landmarks_expected;
+} fx_map_expect_result;
+void fx_map_expect_options_default(fx_map_expect_options *o);
+/* Host only: the context's pass-through box (fx_params x_min .. y_max) drawn in by `margin` on every side, computed in float
+ * ((float)x_min + margin, (float)x_max - margin, ...), and the defaults otherwise. */
+void fx_map_expect_options_from_params(const fx_params *params, float margin, fx_map_expect_options *o);
+fx_status fx_map_expect(fx_ctx *ctx, fx_map *map,
+    const void *kp_block_device, uint32_t max_scans, uint32_t max_total_keypoints,   /* what the localise was given */
+    const fx_localization *loc_device, uint32_t n_scans,                            /* what it wrote */
+    const int32_t *map_id_of_row_device, uint32_t q_max_rows,
+    const fx_map_expect_options *opt /* NULL: defaults */, fx_map_expect_result *result_device /* or NULL */,
+    uint32_t *expected_of_landmark_device /* [max_landmarks] */, uint32_t *seen_of_landmark_device /* [max_landmarks] */);
 
 /* ---- Compacting the map: the absorbed fragments and the let-go landmarks taken out, the others renumbered ----
  * fx_map_merge leaves every absorbed fragment in place: its record, its sums and its alias entry; every grid build marks and skips
@@ -1042,7 +1121,10 @@ fx_status fx_map_observe(fx_ctx *ctx, fx_map *map,
  * the target may be larger than the source and may live on another context or device.  The import REPLACES the target; to keep
  * the target's landmarks and add the snapshot's behind them use fx_map_append_host (below).  Export and import also return
  * FX_ERR_INVALID_ARG for a NULL ctx, map or src_host, dst_host == NULL with capacity != 0, and a map of another context.  New in
- * 0.7 (added symbols only). */
+ * 0.7 (added symbols only).
+ * Limits: fx_map_compact drops a live landmark only for being short and old; one that stood long and has since gone passes both
+ * tests for ever.  fx_map_retire (below) runs this same compaction with the landmarks taken out that fx_map_expect's counts
+ * condemn. */
 typedef struct fx_map_compact_options {
   uint32_t min_obs;        /* a live landmark of fewer observations may be dropped (see above); >= 1; default 1: drop nothing live */
   uint32_t min_age_scans;  /* ... but only when it was last seen at least this many scans ago; default 64 (fx_map_merge's max_gap_scans) */
@@ -1054,6 +1136,52 @@ fx_status fx_map_compact(fx_ctx *ctx, fx_map *map, const fx_map_compact_options 
 fx_status fx_map_export_host(fx_ctx *ctx, fx_map *map, void *dst_host, size_t capacity, size_t *bytes_out);
 fx_status fx_map_import_host(fx_ctx *ctx, fx_map *map, const void *src_host, size_t bytes);
 fx_status fx_map_snapshot_check(const void *src_host, size_t bytes, uint32_t max_landmarks, uint32_t max_carry_rows); /* Host only */
+
+/* ---- Retiring landmarks on evidence: the ones fx_map_expect's counters condemn taken out of the map ----
+ * fx_map_retire reads the two counter arrays the caller accumulated with fx_map_expect (FX_EXPECT_ADD over many localised calls),
+ * decides which landmarks are expected again and again and never seen, and runs ONE fx_map_compact with those taken out: the same
+ * device code, not a copy of it.  Enqueued on the context's stream, no host synchronisation, no allocation in the steady state,
+ * integer operations and byte moves only.  With N = header.n_landmarks and the state as it is when the call runs on the stream:
+ * Retired: landmark i < N is retired iff all of: alias[i] == -1; expected[i] >= min_expected; (uint64)seen[i] seen_den <
+ * (uint64)expected[i] seen_num (seen / expected < seen_num / seen_den, exactly); no carry[j], j < header.carry_rows, resolves to i
+ * (fx_map_compact's clause: the next fx_map_update continues it).
+ * Protected: a landmark that meets the first three but is held by the carry counts in protected_by_carry and stays.
+ * Then one compaction: fx_map_compact's clauses word for word with min_obs = 1 (and its default min_age_scans), where "kept"
+ * additionally requires "not retired": no other live landmark is dropped (every live landmark has n_obs >= 1), and every absorbed
+ * one is.  New ids, Move, alias, Carry, header and remap are exactly as there: header.n_obs falls by the n_obs of the retired,
+ * remap of a retired landmark (and of an absorbed one whose root is retired) is -1, FX_MAP_FULL stays sticky.
+ * Counters follow the landmarks: for a kept i, expected[new id] = expected[i] and seen[new id] = seen[i] (staged through the
+ * scratch as the records are: new ids are never above old ones, but the move is parallel); words [K, max_landmarks) become 0.
+ * result (when given), 32 B: before = N, kept = K, dropped_absorbed, retired, retired_obs = the sum of n_obs over the retired (in
+ * uint32), protected_by_carry, reserved = 0, 0.  retired_of_landmark (when given), all max_landmarks bytes: 1 for a retired OLD id,
+ * else 0.
+ * FX_RETIRE_DRY_RUN: remap, the byte mask and the result are what the applying call would write; the map and both counter arrays
+ * keep every byte.
+ * A call in which nothing is retired leaves the map, and remap, byte for byte what fx_map_compact with {min_obs 1} leaves.  A second
+ * call changes no byte.  The same bytes from run to run and with any number of contexts in flight.
+ * FX_ERR_INVALID_ARG with the reason in fx_last_error(), nothing launched, nothing touched: a NULL ctx, map or counter array; a map
+ * of another context; min_expected == 0; seen_den == 0, seen_num == 0 or seen_num > seen_den; mode > 1; reserved != 0; the
+ * counters, remap_device or result_device not 4-byte aligned.
+ * Limits: the counters of dropped landmarks, absorbed ones included, are discarded: what fx_map_expect counted on an absorbed id
+ * before the merge does not pass to its root (expect follows the alias table from the merge on).  The call knows nothing of why a
+ * landmark was not seen: occlusion by things that are no keypoints lowers seen / expected of a pole that still stands, and the
+ * ratio and min_expected are the caller's guard against that.  New in 0.7 (added symbols only). */
+#define FX_RETIRE_APPLY 0u
+#define FX_RETIRE_DRY_RUN 1u      /* report everything, change no byte of the map or of the counters */
+typedef struct fx_map_retire_options {    /* 24 B */
+  uint32_t min_expected;       /* a landmark expected fewer times is never retired; >= 1; default 16 */
+  uint32_t seen_num, seen_den; /* retired when seen / expected < seen_num / seen_den; 1 <= num <= den; default 1 / 8 */
+  uint32_t mode;               /* FX_RETIRE_APPLY (default), FX_RETIRE_DRY_RUN */
+  uint32_t reserved[2];        /* 0 */
+} fx_map_retire_options;
+typedef struct fx_map_retire_result {     /* 32 B */
+  uint32_t before, kept, dropped_absorbed, retired, retired_obs, protected_by_carry, reserved[2];
+} fx_map_retire_result;
+void fx_map_retire_options_default(fx_map_retire_options *o);
+fx_status fx_map_retire(fx_ctx *ctx, fx_map *map,
+    uint32_t *expected_of_landmark_device, uint32_t *seen_of_landmark_device,   /* [max_landmarks], read and renumbered */
+    const fx_map_retire_options *opt /* NULL: defaults */, int32_t *remap_device /* [max_landmarks] or NULL */,
+    uint8_t *retired_of_landmark_device /* [max_landmarks], old ids, or NULL */, fx_map_retire_result *result_device /* or NULL */);
 
 /* ---- Appending one map to another: two maps in two frames become one map with two sets of segments ----
  * Every call above works on ONE map; fx_map_import_host replaces its target and fx_map_update grows a map only from the run it is

@@ -1,0 +1,329 @@
+"""fx_map_expect and fx_map_retire on the GPU.  Every call of every case is compared with capi.map_expect_reference (an all-pairs
+statement of include/fx.h's definition in numpy float64 that knows nothing of a grid) and capi.map_retire_reference bit for bit: the
+result words, both counter arrays, remap and the byte mask whole, with guard words behind each, and the map's whole private state
+through the snapshot: Map.export_state() against capi.map_snapshot_pack, byte for byte."""
+import ctypes as C
+import threading
+
+import numpy as np
+import pytest
+
+from feature_extraction_amd import capi
+from tests import map_compact_util as mc
+from tests import map_expect_util as eu
+from tests import map_localize_util as lu
+from tests import map_merge_util as mm
+from tests.test_gpu_map import _run
+from tests.test_gpu_map_compact import _compact, _same_state
+from tests.test_gpu_map_merge import _merge_to_fixpoint, _one_batch
+from tests.test_gpu_map_observe import _localized, _map_of, _upload
+from tests.test_gpu_track import FILL, GUARD
+
+pytestmark = pytest.mark.gpu
+ANY = capi.FX_LOC_ANY_SEGMENT
+SENTINEL = 0x01020304  # what the counter arrays of an FX_EXPECT_ADD call hold before it
+BYTE = 0x5A
+
+
+@pytest.fixture
+def ctx(fxlib):
+    c = capi.Context(capi.params("launch"), capi.limits(2, 1024))  # (no batch is ever processed on it)
+    yield c
+    c.close()
+
+
+def _counters(ctx, mp, fill=0):
+    """Two guarded counter arrays on the device, filled."""
+    import torch
+    return [torch.full((mp.max_landmarks + GUARD,), fill, dtype=torch.int32, device=f"cuda:{ctx.device}") for _ in range(2)]
+
+
+def _host(t, n):
+    return t[:n].cpu().numpy().view(np.uint32).copy()
+
+
+def _call(ctx, mp, kp, loc, ids, n_scans, q, raw_e, raw_s, **opts):
+    """Map.expect into guarded outputs.  Returns (result dict, expected, seen)."""
+    import torch
+    cap = mp.max_landmarks
+    res = torch.full((8 + GUARD,), FILL, dtype=torch.int32, device=f"cuda:{ctx.device}")
+    guards = [t[cap:].clone() for t in (raw_e, raw_s)]
+    mp.expect(kp, loc, n_scans, ids, q_max_rows=q, out=res[:8], expected=raw_e[:cap], seen=raw_s[:cap], **opts)
+    ctx.synchronize()
+    assert (res[8:] == FILL).all().item(), "the guard behind the result"
+    assert all((t[cap:] == g).all().item() for t, g in zip((raw_e, raw_s), guards)), "the guards behind the counter arrays"
+    return capi.expect_records(res[:8]), _host(raw_e, cap), _host(raw_s, cap)
+
+
+def _expect(ctx, mp, st, c, what, counters=None, n_scans=None, q_max_rows=None, stored=None, max_scans=None, max_total=None, **opts):
+    """One fx_map_expect of a case against one map_expect_reference call; the map must keep every byte.  counters: the device
+    arrays of an FX_EXPECT_ADD call (else the call writes, into arrays filled with a sentinel).  Returns (result, expected, seen)."""
+    n_scans = len(c["off"]) - 1 if n_scans is None else n_scans
+    q = len(c["rows"]) if q_max_rows is None else q_max_rows
+    opts = dict(c["opts"], **opts)
+    kp, loc_d, ids_d, loc, ids = _upload(ctx, c, n_scans, q, max_scans, max_total, stored)
+    add = counters is not None
+    raw_e, raw_s = counters if add else _counters(ctx, mp, SENTINEL)
+    before = (_host(raw_e, mp.max_landmarks), _host(raw_s, mp.max_landmarks))
+    got = _call(ctx, mp, kp, loc_d, ids_d, n_scans, q, raw_e, raw_s, mode=capi.FX_EXPECT_ADD if add else capi.FX_EXPECT_WRITE, **opts)
+    off = c["off"][:min(len(c["off"]) - 1, kp[1]) + 1]
+    ref = capi.map_expect_reference(st, off, c["rows"][:len(c["rows"]) if stored is None else stored], loc, ids, n_scans, q_max_rows=q,
+                                    expected=before[0], seen=before[1], mode=capi.FX_EXPECT_ADD if add else capi.FX_EXPECT_WRITE, **opts)
+    eu.assert_counts(got, ref, what)
+    _same_state(mp, st, what + ": the map is only read")
+    return got
+
+
+def _retire(ctx, mp, st, counters, what, dry_run=False, **opts):
+    """One fx_map_retire into guarded outputs against one map_retire_reference call, the map through its snapshot and the counter
+    arrays whole.  Returns (the new state, remap, mask, result)."""
+    import torch
+    cap, dev = mp.max_landmarks, f"cuda:{ctx.device}"
+    raw_e, raw_s = counters
+    e, s = _host(raw_e, cap), _host(raw_s, cap)
+    remap = torch.full((cap + GUARD,), FILL, dtype=torch.int32, device=dev)
+    mask = torch.full((cap + GUARD,), BYTE, dtype=torch.uint8, device=dev)
+    res = torch.full((8 + GUARD,), FILL, dtype=torch.int32, device=dev)
+    mp.retire(raw_e[:cap], raw_s[:cap], remap=remap[:cap], retired=mask[:cap], result=res[:8],
+              mode=capi.FX_RETIRE_DRY_RUN if dry_run else capi.FX_RETIRE_APPLY, **opts)
+    ctx.synchronize()
+    new, ref_remap, ref_mask, ref, ref_e, ref_s = capi.map_retire_reference(st, e, s, dry_run=dry_run, **opts)
+    assert (remap[cap:] == FILL).all().item() and (mask[cap:] == BYTE).all().item() and (res[8:] == FILL).all().item(), f"{what}: the guards"
+    assert (raw_e[cap:] == raw_e[cap]).all().item() and (raw_s[cap:] == raw_s[cap]).all().item(), f"{what}: the guards behind the counters"
+    got = capi.retire_records(res[:8])
+    assert got == ref, f"{what}: result {got}, reference {ref}"
+    for name, a, b in (("remap", remap[:cap].cpu().numpy(), ref_remap), ("retired_of_landmark", mask[:cap].cpu().numpy(), ref_mask),
+                       ("expected", _host(raw_e, cap), ref_e), ("seen", _host(raw_s, cap), ref_s)):
+        bad = np.flatnonzero(a != b)
+        assert not len(bad), f"{what}: {name} differs at {bad[:8].tolist()}: got {a[bad[:8]]}, reference {b[bad[:8]]}"
+    _same_state(mp, new, what)
+    if not dry_run:
+        assert (mp.alias() == -1).all(), f"{what}: the whole alias table is -1"
+    return new, remap[:cap].cpu().numpy(), mask[:cap].cpu().numpy(), got
+
+
+# ---- 1. the chain on the device
+def test_01_localize_expect_observe_expect_retire_localize(ctx):
+    """The flicker world mapped and merged; two poles are cut down before the localised run (their rows leave the scans).  The
+    counters of two expects (one before and one behind an observe, both adding) condemn their landmarks; after the retire a new
+    localise names none of them.  tests/test_map_expect_reference.py walks the same chain through the references."""
+    w, pieces, rows, left = eu.cut_world()
+    f = mm.FLICKER
+    S, q, cap = f["n_scans"], len(rows), f["cap"]
+    mp = ctx.map_create(cap, f["carry"])
+    st, _, _, _ = _run(ctx, pieces, "(1)", cap, f["carry"], mp=mp)
+    st, _ = _merge_to_fixpoint(ctx, mp, st, "(1)", **eu.CHAIN["merge"])
+    priors = lu.poses_of(w["truth"], seed=1072)
+    kp, recs, ids = _localized(ctx, mp, w, rows, priors, segment=ANY)
+    loc, table = capi.localize_records(recs), ids.cpu().numpy()
+    args = (w["off"], rows, loc, table, S)
+    opts = dict(eu.CHAIN["expect"], mode=capi.FX_EXPECT_ADD)
+    counters = _counters(ctx, mp)
+    first = _call(ctx, mp, kp, recs, ids, S, q, *counters, **opts)  # (reads the localise's outputs where they are)
+    ref = capi.map_expect_reference(st, *args, expected=np.zeros(cap, np.uint32), seen=np.zeros(cap, np.uint32), **opts)
+    eu.assert_counts(first, ref, "(1) expect")
+    mp.observe(kp, recs, S, ids, q_max_rows=q)
+    st = capi.map_observe_reference(st, *args)[0]
+    _same_state(mp, st, "(1) observe")
+    second = _call(ctx, mp, kp, recs, ids, S, q, *counters, **opts)
+    ref2 = capi.map_expect_reference(st, *args, expected=ref[1], seen=ref[2], **opts)
+    eu.assert_counts(second, ref2, "(1) expect behind the observe, adding")
+    assert first[0]["expected"] > first[0]["seen"] > 5 * S
+    new, remap, mask, res = _retire(ctx, mp, st, counters, "(1) retire", **eu.CHAIN["retire"])
+    doomed = eu.doomed_landmarks(st, w, left, priors)
+    assert doomed and mask[doomed].all() and (remap[doomed] == -1).all() and res["retired"] >= len(doomed)
+    _, recs2, ids2 = _localized(ctx, mp, w, rows, priors, segment=ANY)
+    again = capi.map_localize_reference(new, w["off"], rows, priors, S, segment=ANY)
+    table2 = ids2.cpu().numpy()
+    assert (table2 == again["map_id_of_row"]).all() and (table2 < res["kept"]).all() and (table2 >= 0).sum() > 5 * S
+    print("(1)", first[0], second[0], res)
+    mp.close()
+
+
+# ---- 2. every case of the util module: counts of 3, 255 / 256 / 257 and 1100 landmarks; scans of 0, 1, 63 / 64 / 65, 257 and
+#         511 / 512 / 513 rows (the kernel's LDS chunk is 512); 0, 1 and more than 300 landmarks in range; a sensor on a cell border
+#         and one that searches the far bucket alone; shadow_width 0; stale and garbage ids
+@pytest.mark.parametrize("name", sorted(eu.CPU_CASES))
+def test_02_every_case_expect_accumulate_retire_and_compact(ctx, name):
+    c = eu.CPU_CASES[name]()
+    mp, st = _map_of(ctx, c, f"({name})")
+    twin, _ = _map_of(ctx, c, f"({name}) the twin")
+    got = _expect(ctx, mp, st, c, f"({name}) write")
+    counters = _counters(ctx, mp)
+    for k in range(c["repeat"]):
+        _expect(ctx, mp, st, c, f"({name}) add {k}", counters=counters)
+    res, e, s = eu.accumulated(st, c)
+    eu.assert_counts((got[0], _host(counters[0], mp.max_landmarks), _host(counters[1], mp.max_landmarks)), (res, e, s), f"({name}) accumulated")
+    before = mp.export_state()
+    _, _, _, dry = _retire(ctx, mp, st, counters, f"({name}) dry run", dry_run=True, **c["retire"])
+    assert mp.export_state() == before
+    new, remap, mask, wet = _retire(ctx, mp, st, counters, f"({name}) retire", **c["retire"])
+    assert wet == dry
+    _retire(ctx, mp, new, counters, f"({name}) a second retire", **c["retire"])
+    assert mp.export_state() == capi.map_snapshot_pack(new), "a second call changes no byte"
+    _compact(ctx, twin, st, f"({name}) fx_map_compact on the same state")
+    if not wet["retired"]:
+        assert mp.export_state() == twin.export_state(), "nothing retired: the compaction's bytes"
+    mp.close(), twin.close()
+
+
+# ---- 3. sizes
+def test_03_sizes_as_in_the_localise(ctx):
+    c = eu.CPU_CASES["n255"]()
+    mp, st = _map_of(ctx, c, "(3)")
+    n, rows = len(c["off"]) - 1, len(c["rows"])
+    _expect(ctx, mp, st, c, "(3) scans beyond the block", n_scans=n + 2, max_scans=n + 2)
+    _expect(ctx, mp, st, c, "(3) max_scans scans", max_scans=n, max_total=rows)
+    res, _, _ = _expect(ctx, mp, st, c, "(3) fewer scans than the block", n_scans=2)
+    assert res["scans_used"] == 2
+    for q in (rows - 70, rows - 1, rows + 1, rows + 300):
+        _expect(ctx, mp, st, c, f"(3) q_max_rows {q}", q_max_rows=q)
+    _expect(ctx, mp, st, c, "(3) a block that stores fewer rows", stored=rows - 5)
+    res, e, s = _expect(ctx, mp, st, c, "(3) no rows at all", q_max_rows=0)
+    assert res["seen"] == 0 == res["stale"] and res["expected"] == res["in_box"] > 0
+    mp.close()
+    empty = ctx.map_create(8, 8)
+    res, e, s = _expect(ctx, empty, capi.map_state(8, 8), c, "(3) an empty map")
+    assert res["scans_used"] == 3 and res["in_range"] == 0 and not e.any() and not s.any()
+    empty.close()
+
+
+# ---- 4. tables older than the map
+def test_04_a_table_from_before_a_merge_and_from_before_a_compaction(ctx):
+    w, pieces, _ = mm.flicker()
+    f = mm.FLICKER
+    mp = ctx.map_create(f["cap"], f["carry"])
+    st, _, _, _ = _run(ctx, pieces, "(4)", f["cap"], f["carry"], mp=mp)
+    kp, recs, ids = _localized(ctx, mp, w, w["rows"], lu.poses_of(w["truth"], seed=1072), segment=ANY)
+    st, results = _merge_to_fixpoint(ctx, mp, st, "(4)", max_gap_scans=mc.GAP)
+    assert sum(r["merged"] for r in results) > 0
+    loc, table = capi.localize_records(recs), ids.cpu().numpy()
+    c = dict(off=w["off"], rows=w["rows"], loc=loc, ids=table, opts=dict(eu.WIDE, min_range=0.0), edit=None)
+    alias = np.array(st["alias"])
+    assert (alias[table[table >= 0]] >= 0).any(), "the table names absorbed landmarks"
+    res, e, s = _expect(ctx, mp, st, c, "(4) after the merge")
+    assert res["stale"] == 0 and not e[:len(alias)][alias >= 0].any() and res["seen"] > 0
+    mp.compact(remap=False, result=False)
+    st, _, _ = capi.map_compact_reference(st)
+    res, e, s = _expect(ctx, mp, st, c, "(4) after a compaction without remap")
+    N = st["header"]["n_landmarks"]
+    assert (table >= N).any() and not e[N:].any() and not s[N:].any()
+    garbage = dict(c, ids=np.random.default_rng(5).integers(-2 ** 31, 2 ** 31, len(table)).astype(np.int32))
+    _expect(ctx, mp, st, garbage, "(4) a table of garbage")
+    mp.close()
+
+
+# ---- 5. refusals
+def test_05_host_refusals_touch_no_output_byte(ctx, fxlib):
+    import torch
+    c = eu.hand4()
+    mp, st = _map_of(ctx, c, "(5)")
+    other = capi.Context(capi.params("launch"), capi.limits(2, 1024))
+    theirs = other.map_create(8, 8)
+    n, q = 2, len(c["rows"])
+    (kb, S, T), loc, ids, _, _ = _upload(ctx, c, n, q, max_scans=4)
+    dev = f"cuda:{ctx.device}"
+    cap = mp.max_landmarks
+    res, e, s, remap = (torch.full((k,), FILL, dtype=torch.int32, device=dev) for k in (8 + 2, cap + 2, cap + 2, cap + 2))
+    mask = torch.full((cap + 2,), BYTE, dtype=torch.uint8, device=dev)
+    before = mp.export_state()
+    ok = dict(capi.EXPECT_DEFAULTS, reserved=0)
+    opt = lambda **kw: C.byref(capi.FxMapExpectOptions(**dict(ok, **kw)))
+    good = dict(c=ctx.handle, m=mp.handle, kp=kb.data_ptr(), S=S, T=T, loc=loc.data_ptr(), n=n, ids=ids.data_ptr(), q=q, opt=opt(), res=res.data_ptr(),
+                e=e.data_ptr(), s=s.data_ptr())
+    nan, inf = float("nan"), float("inf")
+    cases = [(dict(c=None), b"null"), (dict(m=None), b"null"), (dict(kp=None), b"null"), (dict(loc=None), b"null"), (dict(ids=None), b"null"),
+             (dict(e=None), b"null"), (dict(s=None), b"null"),
+             (dict(m=theirs.handle), b"another context"), (dict(c=other.handle), b"another context"), (dict(n=0), b"n_scans"), (dict(n=S + 1), b"n_scans")]
+    cases += [(dict(opt=opt(**kw)), b"box") for kw in (dict(x_min=2.0, x_max=1.0), dict(y_min=2.0, y_max=1.0), dict(x_min=nan), dict(x_max=nan),
+                                                      dict(y_min=nan), dict(y_max=nan))]
+    cases += [(dict(opt=opt(min_range=v)), b"min_range") for v in (-1.0, nan, inf)]
+    cases += [(dict(opt=opt(max_range=v)), b"max_range") for v in (0.0, -1.0, nan, inf, 1.0)]
+    cases += [(dict(opt=opt(shadow_width=v)), b"shadow_width") for v in (-0.5, nan, inf)]
+    cases += [(dict(opt=opt(require_flags=0x20)), b"require_flags"), (dict(opt=opt(require_flags=0x80000001)), b"require_flags"),
+              (dict(opt=opt(min_landmark_obs=0)), b"min_landmark_obs"), (dict(opt=opt(mode=2)), b"mode"), (dict(opt=opt(reserved=1)), b"reserved"),
+              (dict(kp=kb.data_ptr() + 4), b"aligned"), (dict(loc=loc.data_ptr() + 4), b"aligned"), (dict(ids=ids.data_ptr() + 2), b"aligned"),
+              (dict(res=res.data_ptr() + 2), b"aligned"), (dict(e=e.data_ptr() + 1), b"aligned"), (dict(s=s.data_ptr() + 2), b"aligned")]
+    call = lambda a: fxlib.fx_map_expect(a["c"], a["m"], a["kp"], a["S"], a["T"], a["loc"], a["n"], a["ids"], a["q"], a["opt"], a["res"], a["e"], a["s"])
+    for change, word in cases:
+        assert call(dict(good, **change)) == 1 and word in fxlib.fx_last_error(), (change, word, fxlib.fx_last_error())
+    rok = dict(min_expected=1, seen_num=1, seen_den=1, mode=0)
+    ropt = lambda reserved=(0, 0), **kw: C.byref(capi.FxMapRetireOptions(reserved=(C.c_uint32 * 2)(*reserved), **dict(rok, **kw)))
+    rgood = dict(c=ctx.handle, m=mp.handle, e=e.data_ptr(), s=s.data_ptr(), opt=ropt(), remap=remap.data_ptr(), mask=mask.data_ptr(), res=res.data_ptr())
+    rcases = [(dict(c=None), b"null"), (dict(m=None), b"null"), (dict(e=None), b"null"), (dict(s=None), b"null"),
+              (dict(m=theirs.handle), b"another context"), (dict(c=other.handle), b"another context"),
+              (dict(opt=ropt(min_expected=0)), b"min_expected"), (dict(opt=ropt(seen_den=0)), b"ratio"), (dict(opt=ropt(seen_num=0)), b"ratio"),
+              (dict(opt=ropt(seen_num=3, seen_den=2)), b"ratio"), (dict(opt=ropt(mode=2)), b"mode"), (dict(opt=ropt(reserved=(1, 0))), b"reserved"),
+              (dict(opt=ropt(reserved=(0, 1))), b"reserved"), (dict(e=e.data_ptr() + 2), b"aligned"), (dict(s=s.data_ptr() + 1), b"aligned"),
+              (dict(remap=remap.data_ptr() + 2), b"aligned"), (dict(res=res.data_ptr() + 2), b"aligned")]
+    rcall = lambda a: fxlib.fx_map_retire(a["c"], a["m"], a["e"], a["s"], a["opt"], a["remap"], a["mask"], a["res"])
+    for change, word in rcases:
+        assert rcall(dict(rgood, **change)) == 1 and word in fxlib.fx_last_error(), (change, word, fxlib.fx_last_error())
+    ctx.synchronize()
+    assert all((t == FILL).all().item() for t in (res, e, s, remap)) and (mask == BYTE).all().item() and mp.export_state() == before
+    # a NULL result is legal, and so is a NULL table with q_max_rows == 0; opt == NULL: the defaults
+    assert call(dict(good, ids=None, q=0, opt=None, res=None)) == capi.FX_OK
+    assert call(dict(good, opt=None)) == capi.FX_OK
+    ctx.synchronize()
+    ref = eu.reference(st, c)
+    eu.assert_counts((capi.expect_records(res[:8]), _host(e, cap), _host(s, cap)), ref, "(5) defaults")
+    assert all((t[k:] == FILL).all().item() for t, k in ((res, 8), (e, cap), (s, cap))) and mp.export_state() == before
+    # every optional output of the retire NULL, the default options: expected [2, 2, 0, 0] is below min_expected 16
+    assert rcall(dict(rgood, opt=None, remap=None, mask=None, res=None)) == capi.FX_OK
+    ctx.synchronize()
+    _same_state(mp, capi.map_retire_reference(st, ref[1], ref[2])[0], "(5) retire without outputs")
+    theirs.close(), other.close(), mp.close()
+
+
+# ---- 6. the scratch grows between the calls of one context
+def test_06_the_scratch_grows_mid_sequence(ctx):
+    small, big = eu.CPU_CASES["three"](), eu.CPU_CASES["n257"]()
+    a, st_a = _map_of(ctx, small, "(6) small")
+    b, st_b = _map_of(ctx, big, "(6) big")
+    first = _expect(ctx, a, st_a, small, "(6) the small map first")
+    _expect(ctx, b, st_b, big, "(6) the big map: the scratch grows")
+    again = _expect(ctx, a, st_a, small, "(6) the small map again")
+    assert first[0] == again[0] and first[1].tobytes() == again[1].tobytes()
+    counters = _counters(ctx, b)
+    _expect(ctx, b, st_b, big, "(6) add", counters=counters)
+    _retire(ctx, b, st_b, counters, "(6) retire on the grown scratch", min_expected=1, seen_num=1, seen_den=2)
+    a.close(), b.close()
+
+
+# ---- 7. the same bytes from run to run and across contexts
+def test_07_identical_bytes_across_runs_and_four_contexts(ctx):
+    c = eu.CPU_CASES["n257"]()
+    w = mm.fragments(c["frags"], c["n_scans_map"])
+    n, q = len(c["off"]) - 1, len(c["rows"])
+
+    def once(cx, repeat=1):
+        outs = []
+        for _ in range(repeat):
+            mp, _ = _one_batch(cx, w, "(7)", cap=len(c["frags"]), carry=8)
+            kp, loc, ids, _, _ = _upload(cx, c, n, q)
+            counters = _counters(cx, mp)
+            res, e, s = _call(cx, mp, kp, loc, ids, n, q, *counters, mode=capi.FX_EXPECT_ADD, **c["opts"])
+            remap, mask, out = mp.retire(counters[0][:mp.max_landmarks], counters[1][:mp.max_landmarks], min_expected=1, seen_num=1, seen_den=2)
+            cx.synchronize()
+            outs.append(repr(sorted(res.items())).encode() + e.tobytes() + s.tobytes() + remap.cpu().numpy().tobytes() + mask.cpu().numpy().tobytes() +
+                        out.cpu().numpy().tobytes() + mp.export_state() + _host(counters[0], mp.max_landmarks).tobytes())
+            mp.close()
+        assert len(set(outs)) == 1, "the same bytes twice"
+        return outs[0]
+    first = once(ctx, repeat=2)
+    res, errs = {}, []
+
+    def run(i):
+        try:
+            cx = capi.Context(capi.params("launch"), capi.limits(2, 1024))
+            cx.set_batches_in_flight(4)
+            res[i] = once(cx, repeat=3)
+            cx.close()
+        except Exception as e:  # (reported below)
+            errs.append(e)
+    ths = [threading.Thread(target=run, args=(i,)) for i in range(3)]
+    [x.start() for x in ths]
+    mine = once(ctx, repeat=3)  # (this context works while the others are busy on the device)
+    [x.join() for x in ths]
+    assert not errs, errs
+    assert mine == first and all(res[i] == first for i in range(3))

@@ -51,6 +51,14 @@ times fx_map_observe on the synthetic maps of --join (the link left usable: one 
 localises 8 scans of 64 keypoints against it (timed: fx_map_localize, any segment, the true poses as priors) and folds the inlier
 rows into their landmarks (timed: fx_map_observe reading the localise's records and table where they are: the memset, the seven
 launches).  One pair of HIP events around each call.  Reported per size: the medians and the observe's result.  No target is set.
+  timeout -k 10 600 python tools/map_times.py --expect [--sizes 1000,100000,1000000] [--warmup 1] [--repeats 5] [--out profiles/map_expect.md]
+
+times fx_map_expect and fx_map_retire on the synthetic maps of --join (one segment): every repeat resets the map, updates and merges
+it, localises 128 scans of 64 keypoints against it (timed: fx_map_localize, any segment, the true poses as priors), counts expected
+and seen from the localise's device outputs (timed: fx_map_expect, FX_EXPECT_ADD into zeroed counters, a box and a range of 80 m
+so that landmarks beyond the 64 a scan sees are expected: the grid build, the memset, the three launches) and retires on those
+counters (timed: fx_map_retire, min_expected 1, seen / expected below 1 / 2); then it resets, updates and merges again and compacts
+(timed: fx_map_compact, the same launches without the rule).  One pair of HIP events around each call.  No target is set.
   timeout -k 10 600 python tools/map_times.py --loop [--sizes 1000,100000,1000000] [--warmup 1] [--repeats 5] [--out profiles/map_loop_times.txt]
 
 times fx_map_close_loop on the same synthetic maps as one segment: the first fragments (scans 0-1) are the old landmarks, the second
@@ -444,6 +452,82 @@ def measure_observe(ctx, n, warmup, repeats, n_scans=8):
         out[k] = statistics.median(v)
         out[k + "_min_max"] = [min(v), max(v)]
     return out
+
+
+EXPECT_OPTS = dict(x_min=-80.0, x_max=80.0, y_min=-80.0, y_max=80.0, min_range=0.0, max_range=80.0)
+
+
+def measure_expect(ctx, n, warmup, repeats, n_scans=128):
+    import torch
+    mp, kp, out, skp, pri_t = localize_scene(ctx, n, n_scans, cut_link=False)
+    res, rres = (torch.zeros((8,), dtype=torch.int32, device="cuda") for _ in range(2))
+    cres, mres = (torch.zeros((4,), dtype=torch.int32, device="cuda") for _ in range(2))
+    counters = [torch.zeros((n,), dtype=torch.int32, device="cuda") for _ in range(2)]
+    remap = torch.empty((n,), dtype=torch.int32, device="cuda")
+    stream = torch.cuda.ExternalStream(ctx.stream_ptr())
+    torch.cuda.synchronize()
+    t = {"localize_ms": [], "expect_ms": [], "retire_ms": [], "compact_ms": []}
+    first = None
+    for rep in range(warmup + repeats):
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(8)]
+        mp.reset()
+        mp.update(kp, out, overlap=False, row_ids=False)
+        mp.merge(result=mres)
+        for c in counters:
+            c.zero_()
+        e[0].record(stream)
+        recs, ids, _ = mp.localize(skp, pri_t, n_scans, nearest=False, segment=capi.FX_LOC_ANY_SEGMENT)
+        e[1].record(stream), e[2].record(stream)
+        mp.expect(skp, recs, n_scans, ids, out=res, expected=counters[0], seen=counters[1], mode=capi.FX_EXPECT_ADD, **EXPECT_OPTS)
+        e[3].record(stream), e[4].record(stream)
+        mp.retire(counters[0], counters[1], remap=remap, retired=False, result=rres, min_expected=1, seen_num=1, seen_den=2)
+        e[5].record(stream)
+        mp.reset()
+        mp.update(kp, out, overlap=False, row_ids=False)
+        mp.merge(result=mres)
+        e[6].record(stream)
+        mp.compact(remap=remap, result=cres)
+        e[7].record(stream)
+        ctx.synchronize()
+        got = (capi.expect_records(res), capi.retire_records(rres), cres.cpu().numpy().tolist())
+        first = got if first is None else first
+        assert got == first and got[0]["seen"] > 0 and got[1]["before"] == got[2][0] and got[1]["dropped_absorbed"] == got[2][2], (got, first)
+        if rep >= warmup:
+            for k, (a, b) in zip(t, ((0, 1), (2, 3), (4, 5), (6, 7))):
+                t[k].append(e[a].elapsed_time(e[b]))
+    mp.close()
+    out = {"landmarks": n, "scans": n_scans, "expect": first[0], "retire": first[1], "compact": dict(zip(capi.MAP_COMPACT_RESULT_FIELDS, first[2]))}
+    for k, v in t.items():
+        out[k] = statistics.median(v)
+        out[k + "_min_max"] = [min(v), max(v)]
+    return out
+
+
+def main_expect(a):
+    sizes = [int(x) for x in a.sizes.split(",")]
+    ctx = capi.Context(capi.params("launch"), capi.limits(2, 1024))
+    rows = [measure_expect(ctx, n, a.warmup, a.repeats) for n in sizes]
+    ctx.close()
+    lines = [f"fx_map_expect behind fx_map_localize, and fx_map_retire next to fx_map_compact, on synthetic maps (tools/map_times.py --expect):",
+             f"1 pole per 250 m^2, one segment, merged; a call: 128 scans of 64 keypoints localised (any segment, the true poses as priors), then",
+             f"expected / seen counted from the localise's device outputs (box and range 80 m, adding), then retired (min_expected 1, seen /",
+             f"expected < 1 / 2); the compaction on the same merged map; one context, HIP events around each call, median of {a.repeats} after",
+             f"{a.warmup} warm-up; ms",
+             f"{'landmarks':>10} {'used':>5} {'in_range':>9} {'shadowed':>9} {'expected':>9} {'seen':>7} {'lm_exp':>7} {'retired':>8} {'absorbed':>9} "
+             f"{'expect':>8} {'min':>7} {'max':>7} {'localize':>9} {'retire':>8} {'min':>7} {'max':>7} {'compact':>8} {'min':>7} {'max':>7}"]
+    for r in rows:
+        q, v = r["expect"], r["retire"]
+        lines.append(f"{r['landmarks']:>10} {q['scans_used']:>5} {q['in_range']:>9} {q['shadowed']:>9} {q['expected']:>9} {q['seen']:>7} {q['landmarks_expected']:>7} "
+                     f"{v['retired']:>8} {v['dropped_absorbed']:>9} {r['expect_ms']:>8.3f} {r['expect_ms_min_max'][0]:>7.3f} {r['expect_ms_min_max'][1]:>7.3f} "
+                     f"{r['localize_ms']:>9.3f} {r['retire_ms']:>8.3f} {r['retire_ms_min_max'][0]:>7.3f} {r['retire_ms_min_max'][1]:>7.3f} "
+                     f"{r['compact_ms']:>8.3f} {r['compact_ms_min_max'][0]:>7.3f} {r['compact_ms_min_max'][1]:>7.3f}")
+    s = "\n".join(lines)
+    print(s)
+    print(json.dumps(rows))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(s + "\n")
 
 
 def main_observe(a):
@@ -966,6 +1050,7 @@ def main():
     ap.add_argument("--relocalize", action="store_true", help="time fx_map_relocalize on the synthetic maps instead (pass --sizes 10000,100000)")
     ap.add_argument("--join", action="store_true", help="time fx_map_join_segments on two-segment synthetic maps instead")
     ap.add_argument("--observe", action="store_true", help="time fx_map_observe behind fx_map_localize on the synthetic maps of --join instead")
+    ap.add_argument("--expect", action="store_true", help="time fx_map_expect behind fx_map_localize and fx_map_retire next to fx_map_compact on the synthetic maps of --join instead")
     ap.add_argument("--loop", action="store_true", help="time fx_map_close_loop on the synthetic maps taken as one loop instead")
     ap.add_argument("--find-loop", action="store_true", help="time fx_map_find_loop next to fx_map_relocalize on one-segment synthetic maps instead")
     ap.add_argument("--append", action="store_true", help="time fx_map_append and fx_map_append_host next to fx_map_import_host and a plain copy instead")
@@ -991,6 +1076,8 @@ def main():
         return main_join(a)
     if a.observe:
         return main_observe(a)
+    if a.expect:
+        return main_expect(a)
     if a.loop:
         return main_loop(a)
     if a.find_loop:
