@@ -17,7 +17,7 @@
 #include <vector>
 
 #include "../../include/fx.h"
-#include "fx_device.h"
+#include "fx_scan_query.h"
 
 extern "C" {
 size_t fxk_ring_large_lds_bytes(uint32_t cap, uint32_t ccap);
@@ -744,10 +744,29 @@ void constellation_args(Args *A, const fx_map *m, const Options &o) {
 // the prior of the join and the loop: on the host or on the device, not both, and finite where the host can see it
 fx_status prior_check(const fx_pose *prior_host, const double *prior_device) {
   if (prior_host && prior_device) return fail(FX_ERR_INVALID_ARG, "give the prior on the host or on the device, not both");
-  if (prior_host && !(std::isfinite(prior_host->c) && std::isfinite(prior_host->s) && std::isfinite(prior_host->tx) &&
-                      std::isfinite(prior_host->ty) && std::isfinite(prior_host->tz)))
-    return fail(FX_ERR_INVALID_ARG, "prior_host must be finite");
+  if (prior_host && !finite_pose(*prior_host)) return fail(FX_ERR_INVALID_ARG, "prior_host must be finite");
   return FX_OK;
+}
+// What the calls that read a keypoint block as a query share (fx_track_landmarks, fx_map_localize ... fx_map_expect; fx_device.h
+// FxKpQuery): the refusal of the caller's scans, and the query in the launch arguments
+fx_status query_check(uint32_t max_scans, uint32_t n_scans) {
+  if (!n_scans || n_scans > max_scans)
+    return fail(FX_ERR_INVALID_ARG, "n_scans must be 1..max_scans (" + std::to_string(n_scans) + " of " + std::to_string(max_scans) + ")");
+  return FX_OK;
+}
+void query_args(FxKpQuery *K, const void *kp, uint32_t max_scans, uint32_t max_total, uint32_t n_scans, uint32_t q_max_rows) {
+  K->kp = (const uint32_t *)kp, K->max_scans = max_scans, K->max_total = max_total, K->n_scans = n_scans, K->q_max_rows = q_max_rows;
+}
+// require_flags of the calls that read localisations (fx_map_observe, fx_map_expect)
+fx_status loc_flags_check(uint32_t require_flags) {
+  const uint32_t known = FX_LOC_VALID | FX_LOC_TRUNCATED | FX_LOC_NO_HYPOTHESIS | FX_LOC_BAD_PRIOR | FX_LOC_NO_SCAN;
+  if (require_flags & ~known) return fail(FX_ERR_INVALID_ARG, "unknown require_flags bits (only the FX_LOC_* flags are defined)");
+  return FX_OK;
+}
+// the map's own memory in the arguments of fx_map_compact and fx_map_retire
+void map_compact_view(FxMapCompactArgs *A, const fx_map *m) {
+  A->header = m->a.header, A->records = m->a.records, A->acc = m->a.acc, A->carry = m->a.carry, A->alias = m->a.alias;
+  A->cap = m->a.cap, A->max_carry = m->a.max_carry;
 }
 // the association's part of the join's and the loop's arguments (fx_device.h FxMapAssocArgs); no prior is the identity
 template <typename Options>
@@ -1906,8 +1925,7 @@ fx_status fx_track_landmarks(fx_ctx *c, const void *kp, uint32_t max_scans, uint
                              fx_pose *poses, int32_t *landmark_of_row, uint32_t *obs_row, fx_landmark *landmarks, uint32_t max_landmarks,
                              fx_track_header *header) {
   if (!c) return fail(FX_ERR_INVALID_ARG, "null argument");
-  if (!n_scans || n_scans > max_scans)
-    return fail(FX_ERR_INVALID_ARG, "n_scans must be 1..max_scans (" + std::to_string(n_scans) + " of " + std::to_string(max_scans) + ")");
+  FX_TRY(query_check(max_scans, n_scans));
   if (!kp || !poses || !header || (q_max_rows && (!matches || !inlier || !landmark_of_row || !obs_row)) || (n_scans > 1u && !reg) ||
       (max_landmarks && !landmarks))
     return fail(FX_ERR_INVALID_ARG, "null argument");
@@ -1938,9 +1956,9 @@ fx_status fx_track_landmarks(fx_ctx *c, const void *kp, uint32_t max_scans, uint
     A.bsum = w + 7 * n;
     A.counters = A.bsum + 2 * n_blocks;
   }
-  A.kp = (const uint32_t *)kp, A.max_scans = max_scans, A.max_total = max_total;
-  A.matches = matches, A.inlier = inlier, A.q_max_rows = q_max_rows;
-  A.reg = reg, A.n_scans = n_scans, A.min_obs = o.min_obs, A.max_landmarks = max_landmarks;
+  query_args(&A.K, kp, max_scans, max_total, n_scans, q_max_rows);
+  A.matches = matches, A.inlier = inlier;
+  A.reg = reg, A.min_obs = o.min_obs, A.max_landmarks = max_landmarks;
   A.poses = poses, A.landmark_of_row = landmark_of_row, A.obs_row = obs_row, A.landmarks = landmarks, A.header = header;
   FX_HIP(fxk_track(c->stream, A));
   return FX_OK;
@@ -2076,8 +2094,7 @@ fx_status fx_map_localize(fx_ctx *c, fx_map *m, const void *kp, uint32_t max_sca
                           uint32_t q_max_rows, const fx_localize_options *opt, fx_localization *out, int32_t *map_id_of_row,
                           int32_t *nearest_of_row) {
   FX_TRY(map_call_check(c, m));
-  if (!n_scans || n_scans > max_scans)
-    return fail(FX_ERR_INVALID_ARG, "n_scans must be 1..max_scans (" + std::to_string(n_scans) + " of " + std::to_string(max_scans) + ")");
+  FX_TRY(query_check(max_scans, n_scans));
   if (!kp || !priors || !out || (q_max_rows && !map_id_of_row)) return fail(FX_ERR_INVALID_ARG, "null argument");
   if (((uintptr_t)kp % 16) != 0 || ((uintptr_t)priors % 8) != 0 || ((uintptr_t)out % 8) != 0 || ((uintptr_t)map_id_of_row % 4) != 0 ||
       ((uintptr_t)nearest_of_row % 4) != 0)
@@ -2090,8 +2107,8 @@ fx_status fx_map_localize(fx_ctx *c, fx_map *m, const void *kp, uint32_t max_sca
   FX_HIP(hipSetDevice(c->device));
   FxMapLocalizeArgs A{};
   map_grid_view(&A.G, m, (double)o.search_dist);
-  A.kp = (const uint32_t *)kp, A.max_scans = max_scans, A.max_total = max_total;
-  A.priors = priors, A.n_scans = n_scans, A.q_max_rows = q_max_rows;
+  query_args(&A.K, kp, max_scans, max_total, n_scans, q_max_rows);
+  A.priors = priors;
   A.inlier_dist = o.inlier_dist, A.min_baseline = o.min_baseline;
   A.hyp_corr = o.hyp_corr, A.min_inliers = o.min_inliers, A.min_landmark_obs = o.min_landmark_obs, A.segment = o.segment;
   A.out = out, A.map_id_of_row = map_id_of_row, A.nearest_of_row = nearest_of_row;
@@ -2116,8 +2133,7 @@ void fx_relocalize_options_default(fx_relocalize_options *o) {
 fx_status fx_map_relocalize(fx_ctx *c, fx_map *m, const void *kp, uint32_t max_scans, uint32_t max_total, uint32_t n_scans, uint32_t q_max_rows,
                             const fx_relocalize_options *opt, fx_relocalization *out, int32_t *map_id_of_row) {
   FX_TRY(map_call_check(c, m));
-  if (!n_scans || n_scans > max_scans)
-    return fail(FX_ERR_INVALID_ARG, "n_scans must be 1..max_scans (" + std::to_string(n_scans) + " of " + std::to_string(max_scans) + ")");
+  FX_TRY(query_check(max_scans, n_scans));
   if (!kp || !out || (q_max_rows && !map_id_of_row)) return fail(FX_ERR_INVALID_ARG, "null argument");
   if (((uintptr_t)kp % 16) != 0 || ((uintptr_t)out % 8) != 0 || ((uintptr_t)map_id_of_row % 4) != 0)
     return fail(FX_ERR_INVALID_ARG, "the keypoint block must be 16-byte, the records 8-byte, the words 4-byte aligned");
@@ -2129,8 +2145,7 @@ fx_status fx_map_relocalize(fx_ctx *c, fx_map *m, const void *kp, uint32_t max_s
   FX_HIP(hipSetDevice(c->device));
   FxMapRelocalizeArgs A{};
   constellation_args(&A, m, o);
-  A.kp = (const uint32_t *)kp, A.max_scans = max_scans, A.max_total = max_total;
-  A.n_scans = n_scans, A.q_max_rows = q_max_rows;
+  query_args(&A.K, kp, max_scans, max_total, n_scans, q_max_rows);
   A.segment = o.segment;
   A.out = out, A.map_id_of_row = map_id_of_row;
   FX_MAP_RUN(fxk_map_relocalize, "map relocalize scratch");
@@ -2149,14 +2164,12 @@ fx_status fx_map_observe(fx_ctx *c, fx_map *m, const void *kp, uint32_t max_scan
                          const int32_t *map_id_of_row, uint32_t q_max_rows, const fx_map_observe_options *opt, fx_map_observe_result *result,
                          uint32_t *gained_of_landmark, int32_t *observed_id_of_row) {
   FX_TRY(map_call_check(c, m, kp && loc && !(q_max_rows && !map_id_of_row)));
-  if (!n_scans || n_scans > max_scans)
-    return fail(FX_ERR_INVALID_ARG, "n_scans must be 1..max_scans (" + std::to_string(n_scans) + " of " + std::to_string(max_scans) + ")");
+  FX_TRY(query_check(max_scans, n_scans));
   fx_map_observe_options o;
   fx_map_observe_options_default(&o);
   if (opt) o = *opt;
   if (!(std::isfinite(o.gate_dist) && o.gate_dist > 0.f)) return fail(FX_ERR_INVALID_ARG, "gate_dist must be finite and positive");
-  const uint32_t known = FX_LOC_VALID | FX_LOC_TRUNCATED | FX_LOC_NO_HYPOTHESIS | FX_LOC_BAD_PRIOR | FX_LOC_NO_SCAN;
-  if (o.require_flags & ~known) return fail(FX_ERR_INVALID_ARG, "unknown require_flags bits (only the FX_LOC_* flags are defined)");
+  FX_TRY(loc_flags_check(o.require_flags));
   if (o.mode != FX_OBS_APPLY && o.mode != FX_OBS_DRY_RUN) return fail(FX_ERR_INVALID_ARG, "unknown mode (FX_OBS_APPLY or FX_OBS_DRY_RUN)");
   if (o.reserved) return fail(FX_ERR_INVALID_ARG, "reserved must be 0");
   if (((uintptr_t)kp % 16) != 0 || ((uintptr_t)loc % 8) != 0 || ((uintptr_t)map_id_of_row % 4) != 0 || ((uintptr_t)result % 4) != 0 ||
@@ -2165,8 +2178,8 @@ fx_status fx_map_observe(fx_ctx *c, fx_map *m, const void *kp, uint32_t max_scan
   FX_HIP(hipSetDevice(c->device));
   FxMapObserveArgs A{};
   A.header = m->a.header, A.records = m->a.records, A.acc = m->a.acc, A.alias = m->a.alias, A.cap = m->a.cap;
-  A.kp = (const uint32_t *)kp, A.max_scans = max_scans, A.max_total = max_total;
-  A.loc = loc, A.n_scans = n_scans, A.map_id_of_row = map_id_of_row, A.q_max_rows = q_max_rows;
+  query_args(&A.K, kp, max_scans, max_total, n_scans, q_max_rows);
+  A.loc = loc, A.map_id_of_row = map_id_of_row;
   A.gd2 = (double)o.gate_dist * (double)o.gate_dist, A.require_flags = o.require_flags, A.mode = o.mode;
   A.result = (uint32_t *)result, A.gained = gained_of_landmark, A.observed = observed_id_of_row;
   FX_MAP_RUN(fxk_map_observe, "map observe scratch");
@@ -2197,8 +2210,7 @@ fx_status fx_map_expect(fx_ctx *c, fx_map *m, const void *kp, uint32_t max_scans
                         const int32_t *map_id_of_row, uint32_t q_max_rows, const fx_map_expect_options *opt, fx_map_expect_result *result,
                         uint32_t *expected_of_landmark, uint32_t *seen_of_landmark) {
   FX_TRY(map_call_check(c, m, kp && loc && !(q_max_rows && !map_id_of_row) && expected_of_landmark && seen_of_landmark));
-  if (!n_scans || n_scans > max_scans)
-    return fail(FX_ERR_INVALID_ARG, "n_scans must be 1..max_scans (" + std::to_string(n_scans) + " of " + std::to_string(max_scans) + ")");
+  FX_TRY(query_check(max_scans, n_scans));
   fx_map_expect_options o;
   fx_map_expect_options_default(&o);
   if (opt) o = *opt;
@@ -2207,8 +2219,7 @@ fx_status fx_map_expect(fx_ctx *c, fx_map *m, const void *kp, uint32_t max_scans
   if (!(std::isfinite(o.max_range) && o.max_range > 0.f && o.max_range >= o.min_range))
     return fail(FX_ERR_INVALID_ARG, "max_range must be finite, positive and at least min_range");
   if (!(std::isfinite(o.shadow_width) && o.shadow_width >= 0.f)) return fail(FX_ERR_INVALID_ARG, "shadow_width must be finite and not negative");
-  const uint32_t known = FX_LOC_VALID | FX_LOC_TRUNCATED | FX_LOC_NO_HYPOTHESIS | FX_LOC_BAD_PRIOR | FX_LOC_NO_SCAN;
-  if (o.require_flags & ~known) return fail(FX_ERR_INVALID_ARG, "unknown require_flags bits (only the FX_LOC_* flags are defined)");
+  FX_TRY(loc_flags_check(o.require_flags));
   if (!o.min_landmark_obs) return fail(FX_ERR_INVALID_ARG, "min_landmark_obs must be at least 1");
   if (o.mode != FX_EXPECT_WRITE && o.mode != FX_EXPECT_ADD) return fail(FX_ERR_INVALID_ARG, "unknown mode (FX_EXPECT_WRITE or FX_EXPECT_ADD)");
   if (o.reserved) return fail(FX_ERR_INVALID_ARG, "reserved must be 0");
@@ -2218,8 +2229,8 @@ fx_status fx_map_expect(fx_ctx *c, fx_map *m, const void *kp, uint32_t max_scans
   FX_HIP(hipSetDevice(c->device));
   FxMapExpectArgs A{};
   map_grid_view(&A.G, m, (double)o.max_range);
-  A.kp = (const uint32_t *)kp, A.max_scans = max_scans, A.max_total = max_total;
-  A.loc = loc, A.n_scans = n_scans, A.map_id_of_row = map_id_of_row, A.q_max_rows = q_max_rows;
+  query_args(&A.K, kp, max_scans, max_total, n_scans, q_max_rows);
+  A.loc = loc, A.map_id_of_row = map_id_of_row;
   A.x_min = (double)o.x_min, A.x_max = (double)o.x_max, A.y_min = (double)o.y_min, A.y_max = (double)o.y_max;
   A.lo2 = (double)o.min_range * (double)o.min_range, A.hi2 = (double)o.max_range * (double)o.max_range;
   A.w2 = (double)o.shadow_width * (double)o.shadow_width;
@@ -2259,8 +2270,7 @@ fx_status fx_map_compact(fx_ctx *c, fx_map *m, const fx_map_compact_options *opt
   if (((uintptr_t)remap % 4) != 0 || ((uintptr_t)result % 4) != 0) return fail(FX_ERR_INVALID_ARG, "remap and the result must be 4-byte aligned");
   FX_HIP(hipSetDevice(c->device));
   FxMapCompactArgs A{};
-  A.header = m->a.header, A.records = m->a.records, A.acc = m->a.acc, A.carry = m->a.carry, A.alias = m->a.alias;
-  A.cap = m->a.cap, A.max_carry = m->a.max_carry;
+  map_compact_view(&A, m);
   A.min_obs = o.min_obs, A.min_age = o.min_age_scans;
   A.remap = remap, A.result = (uint32_t *)result;
   FX_MAP_RUN(fxk_map_compact, "map compact scratch");
@@ -2292,8 +2302,7 @@ fx_status fx_map_retire(fx_ctx *c, fx_map *m, uint32_t *expected_of_landmark, ui
   fx_map_compact_options k;
   fx_map_compact_options_default(&k);  // min_obs 1: the compaction itself drops nothing live
   FxMapCompactArgs A{};
-  A.header = m->a.header, A.records = m->a.records, A.acc = m->a.acc, A.carry = m->a.carry, A.alias = m->a.alias;
-  A.cap = m->a.cap, A.max_carry = m->a.max_carry;
+  map_compact_view(&A, m);
   A.min_obs = k.min_obs, A.min_age = k.min_age_scans;
   A.remap = remap, A.result = (uint32_t *)result;
   A.expected = expected_of_landmark, A.seen = seen_of_landmark;

@@ -185,15 +185,19 @@ struct FxRegisterArgs {
   float inlier_dist, min_baseline;
   uint32_t hyp_corr, min_inliers, require_flags;
 };
-// fx_track_landmarks (csrc/fx_track.hip): a launch set's arguments.  The scratch arrays are the context's, [q_max_rows] each.
-struct FxTrackArgs {
+// A keypoint block read as a query (csrc/fx_scan_query.h): the block, the sizes it was packed with, and the caller's scans and rows.
+struct FxKpQuery {
   const uint32_t *kp;           // keypoint block (include/fx.h fx_pack_keypoint_block)
   uint32_t max_scans, max_total;
+  uint32_t n_scans, q_max_rows;
+};
+// fx_track_landmarks (csrc/fx_track.hip): a launch set's arguments.  The scratch arrays are the context's, [q_max_rows] each.
+struct FxTrackArgs {
+  FxKpQuery K;
   const void *matches;          // fx_match [q_max_rows]
   const uint32_t *inlier;       // [q_max_rows]
-  uint32_t q_max_rows;
   const void *reg;              // fx_registration [n_scans - 1]
-  uint32_t n_scans, min_obs, max_landmarks;
+  uint32_t min_obs, max_landmarks;
   double init[5];               // P_0: c, s, tx, ty, tz
   void *poses;                  // fx_pose [n_scans]
   int32_t *landmark_of_row;     // [q_max_rows]
@@ -271,10 +275,8 @@ struct FxMapMergeArgs {
 // search distance; the merge's per-landmark arrays are null); the last group is the context's scratch, [q_max_rows] each.
 struct FxMapLocalizeArgs {
   FxMapMergeArgs G;
-  const uint32_t *kp;           // keypoint block (include/fx.h fx_pack_keypoint_block)
-  uint32_t max_scans, max_total;
+  FxKpQuery K;
   const void *priors;           // fx_pose [n_scans]
-  uint32_t n_scans, q_max_rows;
   float inlier_dist, min_baseline;
   uint32_t hyp_corr, min_inliers, min_landmark_obs, segment;
   void *out;                    // fx_localization [n_scans]
@@ -292,10 +294,8 @@ struct FxMapObserveArgs {
   double *acc;                  // [cap][FX_MAP_ACC]
   const int32_t *alias;         // [cap]
   uint32_t cap;
-  const uint32_t *kp;           // keypoint block (include/fx.h fx_pack_keypoint_block)
-  uint32_t max_scans, max_total;
+  FxKpQuery K;
   const void *loc;              // fx_localization [n_scans]
-  uint32_t n_scans, q_max_rows;
   const int32_t *map_id_of_row; // [q_max_rows]
   double gd2;                   // the gate: (double)gate_dist squared
   uint32_t require_flags, mode;
@@ -326,9 +326,7 @@ struct FxRelocWinner {          // the winner of a scan: 48 B
 };
 struct FxMapRelocalizeArgs {
   FxMapMergeArgs P, Q;
-  const uint32_t *kp;           // keypoint block (include/fx.h fx_pack_keypoint_block)
-  uint32_t max_scans, max_total;
-  uint32_t n_scans, q_max_rows;
+  FxKpQuery K;
   float inlier_dist, pair_tol, min_baseline, max_baseline;
   uint32_t max_seeds, min_inliers, min_margin, min_landmark_obs, segment;
   uint32_t chunks;              // workgroups of the hypothesis kernel a (scan, seed): ceil(cap / FXR_CHUNK)
@@ -378,10 +376,8 @@ struct FxMapCompactArgs {
 #define FX_MAP_EXPECT_ST_WORDS 8  // the words of fx_map_expect_result, in its order
 struct FxMapExpectArgs {
   FxMapMergeArgs G;
-  const uint32_t *kp;           // keypoint block (include/fx.h fx_pack_keypoint_block)
-  uint32_t max_scans, max_total;
+  FxKpQuery K;
   const void *loc;              // fx_localization [n_scans]
-  uint32_t n_scans, q_max_rows;
   const int32_t *map_id_of_row; // [q_max_rows]
   double x_min, x_max, y_min, y_max;  // the options' floats widened
   double lo2, hi2, w2;          // (double)min_range, max_range and shadow_width squared

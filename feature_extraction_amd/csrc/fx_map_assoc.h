@@ -23,6 +23,7 @@
 
 #include "fx_map_consensus.h"
 #include "fx_map_grid.h"
+#include "fx_scan_query.h"
 
 #define FXA_WG FXC_MAP_WG
 #define FXA_NWAVE FXC_MAP_NWAVE
@@ -71,7 +72,7 @@ __device__ __forceinline__ void prior_point(const Rigid &P, const fx_map_landmar
 }
 // the part of a query's eligibility every call asks for
 __device__ __forceinline__ bool eligible(const FxMapAssocArgs &S, uint32_t i, const fx_map_landmark &R) {
-  return S.G.alias[i] == -1 && R.n_obs >= S.min_landmark_obs && isfinite(R.x) && isfinite(R.y) && isfinite(R.z);
+  return S.G.alias[i] == -1 && record_eligible(R, S.min_landmark_obs);
 }
 
 // The body of a call's search kernel.  N, refuse, prior: the call's control; is_query(i, record): is landmark i a query;
@@ -146,10 +147,7 @@ __device__ __forceinline__ void move_landmark(double *a, fx_map_landmark &R, con
   if (R.n_obs) map_record_from_sums(R, sx, sy, sz, dx, dy, a[7]);
 }
 // the moved landmarks counted into st[2], a wavefront's at once (every lane of the workgroup calls it)
-__device__ __forceinline__ void count_moved(const FxMapAssocArgs &S, bool moved) {
-  const unsigned long long vote = __ballot(moved);
-  if ((threadIdx.x & 63u) == 0u && vote) atomicAdd(&S.st[2], (uint32_t)__popcll(vote));
-}
+__device__ __forceinline__ void count_moved(const FxMapAssocArgs &S, bool moved) { count_wave(moved, &S.st[2]); }
 
 // A call's launches (the list above).  Args: the call's arguments, whose member S is the shared part; the kernels are the call's.
 template <typename Args>

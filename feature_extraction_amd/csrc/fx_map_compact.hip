@@ -32,7 +32,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "fx_device.h"
+#include "fx_scan_query.h"
 #include "../../include/fx.h"
 
 #define FXMC_WG 256
@@ -95,16 +95,14 @@ extern "C" __global__ __launch_bounds__(FXMC_WG) void k_mc_flag(FxMapCompactArgs
   }
   if (A.expected) {
     if (A.retired && i < A.cap) A.retired[i] = retired ? 1u : 0u;
-    const unsigned long long r = __ballot(retired), h = __ballot(held);
-    if ((threadIdx.x & 63u) == 0u && r) atomicAdd(&A.st[3], (uint32_t)__popcll(r));
-    if ((threadIdx.x & 63u) == 0u && h) atomicAdd(&A.st[5], (uint32_t)__popcll(h));
+    count_wave(retired, &A.st[3]);
+    count_wave(held, &A.st[5]);
   }
   uint32_t ea, eb, ta, tb;
   wg_scan2<FXMC_NWAVE>(kept, lost_obs, s_w, ea, eb, ta, tb);
   if (i < A.cap) A.local[i] = kept ? (int32_t)ea : -1;
   if (threadIdx.x == 0u) A.bsum[blockIdx.x] = ta, A.bsum[n_blocks + blockIdx.x] = tb;
-  const unsigned long long vote = __ballot(absorbed);
-  if ((threadIdx.x & 63u) == 0u && vote) atomicAdd(&A.st[2], (uint32_t)__popcll(vote));
+  count_wave(absorbed, &A.st[2]);
 }
 
 extern "C" __global__ __launch_bounds__(FXMC_WG) void k_mc_top(FxMapCompactArgs A, uint32_t n_blocks) {

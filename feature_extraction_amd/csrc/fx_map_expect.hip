@@ -13,9 +13,10 @@
 //
 // Launches, in stream order, after fxk_map_grid_build's five (the merge's live set: alias -1, n_obs >= 1, finite x and y):
 //   (a memset: this call's counts of both kinds and the state words to 0)
-//   k_exp_name   a thread a row r < q_max_rows: the row's scan by binary search in kp_offset (as k_loc_search), whether the scan is
-//                used, the proposal, its target through the alias table, eligible or stale.  Writes tgt[r]: the landmark named, -1:
-//                a finite row of a used scan that names none (it can still shadow), -2: anything else
+//   k_exp_name   a thread a row r < q_max_rows: the row's scan, whether the scan is used, the proposal, its target through the alias
+//                table (fx_scan_query.h: scan_of_row, scan_used, named_landmark), eligible (record_eligible) or stale.  Writes
+//                tgt[r]: the landmark named, -1: a finite row of a used scan that names none (it can still shadow), -2: anything
+//                else
 //   k_exp_scan   one workgroup of FXE_WG = 256 lanes a scan: the scan's rows staged in LDS in chunks of FXE_CHUNK = 512 (x, y
 //                widened, k2, the target: 28 B a row, 14 KB); the landmarks of the walked buckets flattened over the lanes, 256 a
 //                round; a lane tests its landmark's eligibility on the record, the range and the box, then walks the staged rows
@@ -30,6 +31,7 @@
 #include <stdint.h>
 
 #include "fx_map_grid.h"
+#include "fx_scan_query.h"
 #include "../../include/fx.h"
 
 using namespace fxg;
@@ -46,33 +48,7 @@ extern "C" hipError_t fxk_map_grid_build(hipStream_t s, const FxMapMergeArgs &A)
 extern "C" size_t fxk_map_merge_scratch(FxMapMergeArgs *A, uint8_t *base);
 
 namespace {
-// scans and rows that take part (include/fx.h: as in fx_map_localize)
-__device__ __forceinline__ uint32_t exp_scans(const FxMapExpectArgs &A) { return min(min(A.n_scans, A.kp[0]), A.max_scans); }
-__device__ __forceinline__ uint32_t exp_rows(const FxMapExpectArgs &A) { return min(min(A.kp[1], A.max_total), A.q_max_rows); }
-__device__ __forceinline__ const fx_localization *loc_of(const FxMapExpectArgs &A, uint32_t b) {
-  return reinterpret_cast<const fx_localization *>(A.loc) + b;
-}
-__device__ __forceinline__ bool scan_used(const FxMapExpectArgs &A, uint32_t b) {
-  const fx_localization *L = loc_of(A, b);
-  const fx_pose P = L->pose;
-  return (L->flags & A.require_flags) == A.require_flags && isfinite(P.c) && isfinite(P.s) && isfinite(P.tx) && isfinite(P.ty) && isfinite(P.tz);
-}
-// the segment a landmark must have: false, nothing is eligible; any: every segment passes (fx_map_localize's clause)
-__device__ __forceinline__ bool wanted_segment(const FxMapExpectArgs &A, uint32_t &seg, bool &any) {
-  any = A.segment == FX_LOC_ANY_SEGMENT;
-  seg = A.segment;
-  if (A.segment == FX_LOC_LAST_SEGMENT) {
-    const uint32_t n = reinterpret_cast<const fx_map_header *>(A.G.header)->segments;
-    if (!n) return false;
-    seg = n - 1u;
-  }
-  return true;
-}
-// what eligibility asks of the record of a live landmark (alias -1 is the caller's test)
-__device__ __forceinline__ bool record_eligible(const FxMapExpectArgs &A, const fx_map_landmark &R, bool any_seg, uint32_t seg) {
-  return R.n_obs >= A.min_landmark_obs && isfinite(R.x) && isfinite(R.y) && isfinite(R.z) && (any_seg || R.segment == seg);
-}
-// a wavefront's count of v into a state word
+// a wavefront's sum of v into a state word
 __device__ __forceinline__ void add_wave(uint32_t v, uint32_t *word) {
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) v += (uint32_t)__shfl_down((int)v, o, 64);
@@ -82,34 +58,25 @@ __device__ __forceinline__ void add_wave(uint32_t v, uint32_t *word) {
 
 extern "C" __global__ __launch_bounds__(FXE_WG) void k_exp_name(FxMapExpectArgs A) {
   const uint32_t r = blockIdx.x * FXE_WG + threadIdx.x;
-  const uint32_t S = exp_scans(A), rows = exp_rows(A), N = n_landmarks(A.G);
-  const uint32_t *off = kp_block_offsets(A.kp);
+  const KpView V = query_view(A.K);
+  const uint32_t N = n_landmarks(A.G);
   int32_t t = -2;
   bool stale = false;
-  if (r < rows && S) {
-    uint32_t lo = 0u, hi = S;  // the largest b in [0, S] with kp_offset[b] <= r (kp_offset[0] = 0)
-    while (lo < hi) {
-      const uint32_t mid = (lo + hi + 1u) >> 1;
-      if (off[mid] <= r) lo = mid;
-      else hi = mid - 1u;
-    }
-    if (lo < S && off[lo] <= r && r < off[lo + 1u] && scan_used(A, lo) && finite3(kp_block_rows<float4>(A.kp, A.max_scans)[r])) {
-      t = -1;
-      const int32_t id = A.map_id_of_row[r];
-      if (id >= 0 && (uint32_t)id < N) {
-        const int32_t a = A.G.alias[id];
-        const uint32_t g = a >= 0 ? (uint32_t)a : (uint32_t)id;  // a merge since the localise is followed
-        uint32_t seg;
-        bool any_seg;
-        bool ok = g < N && A.G.alias[g] == -1 && wanted_segment(A, seg, any_seg);
-        if (ok) ok = record_eligible(A, records(A.G)[g], any_seg, seg);
-        if (ok) t = (int32_t)g;
-        else stale = true;
-      }
+  uint32_t b;
+  if (r < V.rows && V.S && scan_of_row(V.off, V.S, r, b) && scan_used(A.loc, b, A.require_flags) && finite3(V.kp[r])) {
+    t = -1;
+    const int32_t id = A.map_id_of_row[r];
+    if (id >= 0 && (uint32_t)id < N) {
+      uint32_t g, seg;
+      bool any_seg;
+      bool ok = named_landmark(A.G.alias, N, (uint32_t)id, g) && wanted_segment(A.G.header, A.segment, seg, any_seg);
+      if (ok) ok = record_eligible(records(A.G)[g], A.min_landmark_obs, any_seg, seg);
+      if (ok) t = (int32_t)g;
+      else stale = true;
     }
   }
-  if (r < A.q_max_rows) A.tgt[r] = t;
-  add_wave(stale ? 1u : 0u, &A.st[6]);
+  if (r < A.K.q_max_rows) A.tgt[r] = t;
+  count_wave(stale, &A.st[6]);
 }
 
 extern "C" __global__ __launch_bounds__(FXE_WG) void k_exp_scan(FxMapExpectArgs A) {
@@ -118,15 +85,14 @@ extern "C" __global__ __launch_bounds__(FXE_WG) void k_exp_scan(FxMapExpectArgs 
   __shared__ uint32_t s_begin[FXE_BUCKETS], s_first[FXE_BUCKETS + 1u];
 
   const uint32_t tid = threadIdx.x, b = blockIdx.x;
-  const uint32_t S = exp_scans(A), rows = exp_rows(A);
-  if (b >= S || !scan_used(A, b)) return;  // (uniform)
+  const KpView V = query_view(A.K);
+  if (b >= V.S || !scan_used(A.loc, b, A.require_flags)) return;  // (uniform)
   uint32_t seg;
   bool any_seg;
-  const bool some_segment = wanted_segment(A, seg, any_seg);  // (uniform)
-  const fx_pose P = loc_of(A, b)->pose;
-  const uint32_t *off = kp_block_offsets(A.kp);
-  const float4 *kp = kp_block_rows<float4>(A.kp, A.max_scans);
-  const uint32_t q_lo = min(off[b], rows), q_hi = max(min(off[b + 1u], rows), q_lo);
+  const bool some_segment = wanted_segment(A.G.header, A.segment, seg, any_seg);  // (uniform)
+  const fx_pose P = loc_of(A.loc, b)->pose;
+  uint32_t q_lo, q_hi;
+  scan_rows(V, b, q_lo, q_hi);
   const uint32_t n_rows = q_hi - q_lo, n_chunks = (n_rows + FXE_CHUNK - 1u) / FXE_CHUNK;
 
   // the buckets to walk, each once, and where each one's landmarks begin in the flattened order
@@ -163,7 +129,7 @@ extern "C" __global__ __launch_bounds__(FXE_WG) void k_exp_scan(FxMapExpectArgs 
   auto stage = [&](uint32_t ch) {
     const uint32_t lo = q_lo + ch * FXE_CHUNK, n = min(FXE_CHUNK, q_hi - lo);
     for (uint32_t i = tid; i < n; i += FXE_WG) {
-      const float4 k = kp[lo + i];
+      const float4 k = V.kp[lo + i];
       const double kx = (double)k.x, ky = (double)k.y;
       s_x[i] = kx, s_y[i] = ky, s_k2[i] = kx * kx + ky * ky, s_t[i] = A.tgt[lo + i];
     }
@@ -184,7 +150,7 @@ extern "C" __global__ __launch_bounds__(FXE_WG) void k_exp_scan(FxMapExpectArgs 
 #pragma unroll
       for (uint32_t q = 1u; q < FXE_BUCKETS; ++q) k += s_first[q] <= j ? 1u : 0u;  // (empty buckets share a first slot: the last one at or below j holds it)
       const FxMapMergeCand c = A.G.cand[s_begin[k] + (j - s_first[k])];
-      if (c.id < A.G.cap && record_eligible(A, records(A.G)[c.id], any_seg, seg)) {
+      if (c.id < A.G.cap && record_eligible(records(A.G)[c.id], A.min_landmark_obs, any_seg, seg)) {
         g = c.id;
         const double dx = c.x - P.tx, dy = c.y - P.ty;
         const double d2 = dx * dx + dy * dy;
@@ -254,8 +220,8 @@ extern "C" hipError_t fxk_map_expect(hipStream_t s, const FxMapExpectArgs &A) {
   // both kinds of counts and the state words behind them are one region of the scratch (fxk_map_expect_scratch)
   const hipError_t e = hipMemsetAsync(A.cnt_e, 0, (2u * (size_t)A.G.cap + FX_MAP_EXPECT_ST_WORDS) * sizeof(uint32_t), s);
   if (e != hipSuccess) return e;
-  if (A.q_max_rows) hipLaunchKernelGGL(k_exp_name, dim3((A.q_max_rows + FXE_WG - 1u) / FXE_WG), wg, 0, s, A);
-  hipLaunchKernelGGL(k_exp_scan, dim3(A.n_scans), wg, 0, s, A);
+  if (A.K.q_max_rows) hipLaunchKernelGGL(k_exp_name, dim3((A.K.q_max_rows + FXE_WG - 1u) / FXE_WG), wg, 0, s, A);
+  hipLaunchKernelGGL(k_exp_scan, dim3(A.K.n_scans), wg, 0, s, A);
   hipLaunchKernelGGL(k_exp_emit, dim3((A.G.cap + FXE_WG - 1u) / FXE_WG), wg, 0, s, A);
   return hipGetLastError();
 }
@@ -269,6 +235,6 @@ extern "C" size_t fxk_map_expect_scratch(FxMapExpectArgs *A, uint8_t *base) {
   A->cnt_e = C.take<uint32_t>(2u * cap + FX_MAP_EXPECT_ST_WORDS);
   A->cnt_s = base ? A->cnt_e + cap : (uint32_t *)nullptr;
   A->st = base ? A->cnt_s + cap : (uint32_t *)nullptr;
-  A->tgt = C.take<int32_t>(A->q_max_rows);
+  A->tgt = C.take<int32_t>(A->K.q_max_rows);
   return C.o;
 }

@@ -9,11 +9,11 @@
 // -ffp-contract=off): the same bytes from run to run and with any number of contexts in flight.  The map is only read.
 //
 // Launches, in stream order, after a memset of n_hyp and the state words and fxk_map_grid_build's five for P and five for Q:
-//   k_fl_elig     a thread a landmark: its byte (alias -1, n_obs >= min_landmark_obs, finite x, y, z, the segment, the window),
+//   k_fl_elig     a thread a landmark: its byte (alias -1, fx_scan_query.h's record_eligible, the segment, the window),
 //                 match_of_landmark = -1, n_targets by ballot and a 32-bit integer atomic add; the resolved segments and the
 //                 refusal go to the state words
 //   k_fl_select   one workgroup: the candidate queries in descending id, found by walking the eligibility BYTES downwards from N
-//                 (16 bytes a thread at a glance, then a workgroup's 256 at a time with ballot + prefix where a query lies)
+//                 (16 bytes a thread at a glance, then a workgroup's 256 at a time with wg_ordered_slot where a query lies)
 //                 until a 65th or id 0; the 48-byte records are read for the used queries alone; then the seeds (rank_seeds)
 //   k_fl_hyp<0>   a workgroup a (seed, FXR_CHUNK slots of P): hyp_block<0>
 //   k_fl_reduce   one workgroup: reduce_block
@@ -26,6 +26,7 @@
 #include <stdint.h>
 
 #include "fx_map_constellation.h"
+#include "fx_scan_query.h"
 #include "../../include/fx.h"
 
 using namespace fxs;
@@ -87,7 +88,7 @@ extern "C" __global__ __launch_bounds__(FXR_WG) void k_fl_elig(FxMapFindLoopArgs
   uint8_t kind = 0;
   if (i < C.N && !C.refuse) {
     const fx_map_landmark R = records(A.P)[i];
-    if (A.P.alias[i] == -1 && R.n_obs >= A.min_landmark_obs && isfinite(R.x) && isfinite(R.y) && isfinite(R.z)) {
+    if (A.P.alias[i] == -1 && record_eligible(R, A.min_landmark_obs)) {
       const bool old = !C.same || (unsigned long long)R.last_scan + A.min_loop_scans <= C.last;
       if (R.segment == C.tseg && old) kind = 1;
       else if (R.segment == C.qseg && (unsigned long long)R.first_scan + A.recent_scans >= C.last) kind = 2;
@@ -97,8 +98,7 @@ extern "C" __global__ __launch_bounds__(FXR_WG) void k_fl_elig(FxMapFindLoopArgs
     A.elig[i] = kind;
     if (A.match) A.match[i] = -1;
   }
-  const unsigned long long bal = __ballot(kind == 1);
-  if ((threadIdx.x & 63u) == 0u && bal) atomicAdd(&A.st[0], (uint32_t)__popcll(bal));
+  count_wave(kind == 1, &A.st[0]);
 }
 
 extern "C" __global__ __launch_bounds__(FXR_WG) void k_fl_select(FxMapFindLoopArgs A) {
@@ -107,7 +107,7 @@ extern "C" __global__ __launch_bounds__(FXR_WG) void k_fl_select(FxMapFindLoopAr
   __shared__ uint32_t s_wave[FXR_NWAVE];
   __shared__ uint32_t s_count;
 
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint32_t tid = threadIdx.x;
   if (tid == 0u) s_count = 0u;
   const uint32_t N = n_landmarks(A.P);
   // ---- the used queries: the bytes of value 2 in descending id, the first FX_FIND_MAX_QUERY kept (a refused call has none).  The
@@ -127,17 +127,8 @@ extern "C" __global__ __launch_bounds__(FXR_WG) void k_fl_select(FxMapFindLoopAr
         const bool in = tid < hi - lo;
         const uint32_t i = in ? hi - 1u - tid : 0u;  // (thread order is descending id)
         const bool ok = in && A.elig[i] == 2;
-        const unsigned long long bal = __ballot(ok);
-        if (lane == 0u) s_wave[wave] = (uint32_t)__popcll(bal);
-        __syncthreads();
-        uint32_t before = 0u, all = 0u;
-#pragma unroll
-        for (uint32_t w = 0; w < FXR_NWAVE; ++w) {
-          const uint32_t n = s_wave[w];
-          before += w < wave ? n : 0u;
-          all += n;
-        }
-        const uint32_t slot = found + before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+        uint32_t slot, all;
+        wg_ordered_slot<FXR_NWAVE>(ok, s_wave, found, slot, all);
         if (ok && slot < FX_FIND_MAX_QUERY) {
           const fx_map_landmark R = records(A.P)[i];
           double *q = A.kq + (size_t)slot * 3u;

@@ -7,13 +7,13 @@
 // of contexts in flight.  The map is only read.
 //
 // Launches, in stream order, after fxk_map_grid_build's five (the merge's live set: alias -1, n_obs >= 1, finite x and y):
-//   k_loc_search     a thread a row r < q_max_rows: the row's scan by binary search in kp_offset (as k_track_init), the world
+//   k_loc_search     a thread a row r < q_max_rows: the row's scan (fx_scan_query.h scan_of_row), the world
 //                    point under the scan's prior (world_point), the walk over its 3 x 3 cells and the far bucket; the walk
 //                    applies min_landmark_obs, the finite z and the segment to the candidates in reach and keeps the lowest
 //                    (d2 bits, id).  Writes near[r] and d2[r] (scratch), nearest_of_row[r] when given, map_id_of_row[r] = -1
 //   k_loc_consensus  one 256-thread workgroup a scan: fx_map_consensus.h's body (rank, hypotheses, refit: shared with
 //                    fx_map_join_segments) over this gather:
-//     gather      the scan's rows with a landmark into LDS in ascending row by ballot + prefix (at most FX_LOC_MAX_CORR)
+//     gather      the scan's rows with a landmark into LDS in ascending row (wg_ordered_slot; at most FX_LOC_MAX_CORR)
 // LDS of k_loc_consensus: fx_map_consensus.h's 57.9 KB.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -22,6 +22,7 @@
 
 #include "fx_map_consensus.h"
 #include "fx_map_grid.h"
+#include "fx_scan_query.h"
 #include "../../include/fx.h"
 
 using namespace fxc;
@@ -37,23 +38,6 @@ extern "C" hipError_t fxk_map_grid_build(hipStream_t s, const FxMapMergeArgs &A)
 extern "C" size_t fxk_map_merge_scratch(FxMapMergeArgs *A, uint8_t *base);
 
 namespace {
-// scans and rows that take part (include/fx.h: as in fx_track_landmarks)
-__device__ __forceinline__ uint32_t loc_scans(const FxMapLocalizeArgs &A) { return min(min(A.n_scans, A.kp[0]), A.max_scans); }
-__device__ __forceinline__ uint32_t loc_rows(const FxMapLocalizeArgs &A) { return min(min(A.kp[1], A.max_total), A.q_max_rows); }
-__device__ __forceinline__ bool finite_pose(const fx_pose &P) {
-  return isfinite(P.c) && isfinite(P.s) && isfinite(P.tx) && isfinite(P.ty) && isfinite(P.tz);
-}
-// the segment a landmark must have: false, nothing is eligible; any: every segment passes
-__device__ __forceinline__ bool wanted_segment(const FxMapLocalizeArgs &A, uint32_t &seg, bool &any) {
-  any = A.segment == FX_LOC_ANY_SEGMENT;
-  seg = A.segment;
-  if (A.segment == FX_LOC_LAST_SEGMENT) {
-    const uint32_t n = reinterpret_cast<const fx_map_header *>(A.G.header)->segments;
-    if (!n) return false;
-    seg = n - 1u;
-  }
-  return true;
-}
 __device__ __forceinline__ void write_no_fit(fx_localization *out, const fx_pose &prior, uint32_t n_corr, uint32_t flags) {
   fx_localization r;
   r.pose = prior;
@@ -67,30 +51,21 @@ __device__ __forceinline__ void write_no_fit(fx_localization *out, const fx_pose
 
 extern "C" __global__ __launch_bounds__(FXL_WG) void k_loc_search(FxMapLocalizeArgs A) {
   const uint32_t r = blockIdx.x * FXL_WG + threadIdx.x;
-  if (r >= A.q_max_rows) return;
-  const uint32_t S = loc_scans(A), rows = loc_rows(A);
-  const uint32_t *off = kp_block_offsets(A.kp);
+  if (r >= A.K.q_max_rows) return;
+  const KpView V = query_view(A.K);
   Near best;
   best.any = false, best.d2 = 0ull, best.id = 0u;
-  uint32_t seg;
+  uint32_t seg, scan;
   bool any_seg;
-  if (r < rows && S && wanted_segment(A, seg, any_seg)) {
-    uint32_t lo = 0u, hi = S;  // the largest b in [0, S] with kp_offset[b] <= r (kp_offset[0] = 0)
-    while (lo < hi) {
-      const uint32_t mid = (lo + hi + 1u) >> 1;
-      if (off[mid] <= r) lo = mid;
-      else hi = mid - 1u;
-    }
-    if (lo < S && off[lo] <= r && r < off[lo + 1u]) {
-      const fx_pose P = reinterpret_cast<const fx_pose *>(A.priors)[lo];
-      const float4 k = kp_block_rows<float4>(A.kp, A.max_scans)[r];
-      if (finite_pose(P) && finite3(k)) {
-        double wx, wy, wz;
-        world_point(P, k, wx, wy, wz);
-        const double tx = floor(wx * A.G.inv_edge), ty = floor(wy * A.G.inv_edge);
-        const auto wanted = [&](const FxMapMergeCand &c) { return any_seg || c.segment == seg; };
-        grid_neighbourhood(A.G, tx, ty, [&](uint32_t b) { walk_nearest(A.G, A.min_landmark_obs, b, wx, wy, wanted, best); });
-      }
+  if (r < V.rows && V.S && wanted_segment(A.G.header, A.segment, seg, any_seg) && scan_of_row(V.off, V.S, r, scan)) {
+    const fx_pose P = reinterpret_cast<const fx_pose *>(A.priors)[scan];
+    const float4 k = V.kp[r];
+    if (finite_pose(P) && finite3(k)) {
+      double wx, wy, wz;
+      world_point(P, k, wx, wy, wz);
+      const double tx = floor(wx * A.G.inv_edge), ty = floor(wy * A.G.inv_edge);
+      const auto wanted = [&](const FxMapMergeCand &c) { return any_seg || c.segment == seg; };
+      grid_neighbourhood(A.G, tx, ty, [&](uint32_t b) { walk_nearest(A.G, A.min_landmark_obs, b, wx, wy, wanted, best); });
     }
   }
   const int32_t g = best.any ? (int32_t)best.id : -1;
@@ -103,18 +78,17 @@ extern "C" __global__ __launch_bounds__(FXL_WG) void k_loc_search(FxMapLocalizeA
 extern "C" __global__ __launch_bounds__(FXL_WG) void k_loc_consensus(FxMapLocalizeArgs A) {
   __shared__ MapConsensusLds L;
 
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, b = blockIdx.x;
-  const uint32_t S = loc_scans(A), rows = loc_rows(A);
+  const uint32_t tid = threadIdx.x, b = blockIdx.x;
+  const KpView V = query_view(A.K);
   const fx_pose prior = reinterpret_cast<const fx_pose *>(A.priors)[b];
   fx_localization *out = reinterpret_cast<fx_localization *>(A.out) + b;
-  if (b >= S || !finite_pose(prior)) {  // (uniform)
-    if (tid == 0u) write_no_fit(out, prior, 0u, b >= S ? FX_LOC_NO_SCAN : FX_LOC_BAD_PRIOR);
+  if (b >= V.S || !finite_pose(prior)) {  // (uniform)
+    if (tid == 0u) write_no_fit(out, prior, 0u, b >= V.S ? FX_LOC_NO_SCAN : FX_LOC_BAD_PRIOR);
     return;
   }
-  const uint32_t *off = kp_block_offsets(A.kp);
-  const float4 *kp = kp_block_rows<float4>(A.kp, A.max_scans);
   const fx_map_landmark *rec = records(A.G);
-  const uint32_t q_lo = min(off[b], rows), q_hi = max(min(off[b + 1u], rows), q_lo);
+  uint32_t q_lo, q_hi;
+  scan_rows(V, b, q_lo, q_hi);
 
   // ---- gather: the correspondences in ascending row, the first FX_LOC_MAX_CORR kept
   auto gather = [&](MapConsensusLds &L) {
@@ -124,21 +98,12 @@ extern "C" __global__ __launch_bounds__(FXL_WG) void k_loc_consensus(FxMapLocali
       int32_t g = -1;
       if (i < q_hi) g = A.near[i];
       const bool ok = g >= 0 && (uint32_t)g < A.G.cap;
-      const unsigned long long bal = __ballot(ok);
-      if (lane == 0u) L.wave[wave] = (uint32_t)__popcll(bal);
-      __syncthreads();
-      uint32_t before = 0u, all = 0u;
-#pragma unroll
-      for (uint32_t w = 0; w < FXL_NWAVE; ++w) {
-        const uint32_t n = L.wave[w];
-        before += w < wave ? n : 0u;
-        all += n;
-      }
-      const uint32_t slot = found + before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+      uint32_t slot, all;
+      wg_ordered_slot<FXL_NWAVE>(ok, L.wave, found, slot, all);
       if (ok && slot < FX_LOC_MAX_CORR) {
         const fx_map_landmark R = rec[g];
         double wx, wy, wz;
-        world_point(prior, kp[i], wx, wy, wz);
+        world_point(prior, V.kp[i], wx, wy, wz);
         L.xy[slot] = make_double4(wx, wy, R.x, R.y);
         L.dz[slot] = R.z - wz;
         L.d2[slot] = A.d2[i];
@@ -179,8 +144,8 @@ extern "C" __global__ __launch_bounds__(FXL_WG) void k_loc_consensus(FxMapLocali
 
 extern "C" hipError_t fxk_map_localize(hipStream_t s, const FxMapLocalizeArgs &A) {
   (void)fxk_map_grid_build(s, A.G);
-  if (A.q_max_rows) hipLaunchKernelGGL(k_loc_search, dim3((A.q_max_rows + FXL_WG - 1u) / FXL_WG), dim3(FXL_WG), 0, s, A);
-  hipLaunchKernelGGL(k_loc_consensus, dim3(A.n_scans), dim3(FXL_WG), 0, s, A);
+  if (A.K.q_max_rows) hipLaunchKernelGGL(k_loc_search, dim3((A.K.q_max_rows + FXL_WG - 1u) / FXL_WG), dim3(FXL_WG), 0, s, A);
+  hipLaunchKernelGGL(k_loc_consensus, dim3(A.K.n_scans), dim3(FXL_WG), 0, s, A);
   return hipGetLastError();
 }
 
@@ -189,7 +154,7 @@ extern "C" hipError_t fxk_map_localize(hipStream_t s, const FxMapLocalizeArgs &A
 extern "C" size_t fxk_map_localize_scratch(FxMapLocalizeArgs *A, uint8_t *base) {
   FxCarve C{base, fxk_map_merge_scratch(&A->G, base)};
   A->G.prop = A->G.pred = A->G.succ = nullptr, A->G.keep = nullptr;  // (the grid's mark leaves the merge's words alone)
-  A->d2 = C.take<unsigned long long>(A->q_max_rows);
-  A->near = C.take<int32_t>(A->q_max_rows);
+  A->d2 = C.take<unsigned long long>(A->K.q_max_rows);
+  A->near = C.take<int32_t>(A->K.q_max_rows);
   return C.o;
 }

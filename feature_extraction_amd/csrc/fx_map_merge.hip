@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "fx_map_grid.h"
+#include "fx_scan_query.h"
 #include "../../include/fx.h"
 
 using namespace fxg;
@@ -70,8 +71,7 @@ extern "C" __global__ __launch_bounds__(FXMM_WG) void k_mm_search(FxMapMergeArgs
       atomicMin(&A.keep[best.id], ((unsigned long long)R.first_scan << 32) | h);
     }
   }
-  const unsigned long long vote = __ballot(proposes);
-  if ((threadIdx.x & 63u) == 0u && vote) atomicAdd(&A.st[0], (uint32_t)__popcll(vote));
+  count_wave(proposes, &A.st[0]);
 }
 
 extern "C" __global__ __launch_bounds__(FXMM_WG) void k_mm_link(FxMapMergeArgs A) {
@@ -81,8 +81,7 @@ extern "C" __global__ __launch_bounds__(FXMM_WG) void k_mm_link(FxMapMergeArgs A
     const int32_t g = A.prop[h];
     if (g >= 0 && (uint32_t)(A.keep[g] & 0xffffffffull) == h) kept = true, A.pred[h] = g, A.succ[g] = (int32_t)h;
   }
-  const unsigned long long vote = __ballot(kept);
-  if ((threadIdx.x & 63u) == 0u && vote) atomicAdd(&A.st[1], (uint32_t)__popcll(vote));
+  count_wave(kept, &A.st[1]);
 }
 
 extern "C" __global__ __launch_bounds__(FXMM_WG) void k_mm_fold(FxMapMergeArgs A) {
@@ -140,8 +139,7 @@ extern "C" __global__ __launch_bounds__(FXMM_WG) void k_mm_repoint(FxMapMergeArg
       }
     }
   }
-  const unsigned long long vote = __ballot(live);
-  if ((threadIdx.x & 63u) == 0u && vote) atomicAdd(&A.st[2], (uint32_t)__popcll(vote));
+  count_wave(live, &A.st[2]);
 }
 
 extern "C" __global__ __launch_bounds__(64) void k_mm_finish(FxMapMergeArgs A) {

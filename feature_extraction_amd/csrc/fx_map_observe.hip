@@ -10,9 +10,10 @@
 //
 // Launches, in stream order (FXO_WG = 256 rows, landmarks or list entries a workgroup; N = the header's n_landmarks):
 //   (a memset: the lists' counts, the cursors and the state words to 0)
-//   k_obs_classify  a thread a row r < q_max_rows: the row's scan by binary search in kp_offset (as k_loc_search), whether the scan
-//                   is used, the proposal, its target through the alias table, stale or not, the world point (world_point) and the
-//                   gate.  Writes tgt[r], d2[r], observed_id_of_row[r] = -1; counts the row in its landmark's list
+//   k_obs_classify  a thread a row r < q_max_rows: the row's scan, whether the scan is used, the proposal, its target through the
+//                   alias table (fx_scan_query.h: scan_of_row, scan_used, named_landmark), stale or not, the world point
+//                   (world_point) and the gate.  Writes tgt[r], d2[r], observed_id_of_row[r] = -1; counts the row in its
+//                   landmark's list
 //   k_obs_count     a thread a landmark: the list lengths' exclusive prefix within the block, the block's total; gained[i] = 0
 //   k_obs_top       one workgroup: the exclusive prefix of the blocks' totals, the entries of all lists, the used scans
 //   k_obs_scatter   a thread a row with a target: its (row, scan, d2 bits) entry to the next free slot of its landmark's list
@@ -26,7 +27,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "fx_device.h"
+#include "fx_scan_query.h"
 #include "../../include/fx.h"
 
 #define FXO_WG 256
@@ -37,67 +38,41 @@ static_assert(sizeof(fx_localization) == 112 && sizeof(fx_map_observe_options) =
               "include/fx.h");
 
 namespace {
-// scans, rows and landmarks that take part (include/fx.h: as in fx_map_localize)
-__device__ __forceinline__ uint32_t obs_scans(const FxMapObserveArgs &A) { return min(min(A.n_scans, A.kp[0]), A.max_scans); }
-__device__ __forceinline__ uint32_t obs_rows(const FxMapObserveArgs &A) { return min(min(A.kp[1], A.max_total), A.q_max_rows); }
+// landmarks that take part
 __device__ __forceinline__ uint32_t obs_landmarks(const FxMapObserveArgs &A) {
   return min(reinterpret_cast<const fx_map_header *>(A.header)->n_landmarks, A.cap);
-}
-__device__ __forceinline__ const fx_localization *loc_of(const FxMapObserveArgs &A, uint32_t b) {
-  return reinterpret_cast<const fx_localization *>(A.loc) + b;
-}
-__device__ __forceinline__ bool scan_used(const FxMapObserveArgs &A, uint32_t b) {
-  const fx_localization *L = loc_of(A, b);
-  const fx_pose P = L->pose;
-  return (L->flags & A.require_flags) == A.require_flags && isfinite(P.c) && isfinite(P.s) && isfinite(P.tx) && isfinite(P.ty) && isfinite(P.tz);
-}
-// the scan of row r < rows among S >= 1 scans; false: a non-row
-__device__ __forceinline__ bool scan_of_row(const uint32_t *off, uint32_t S, uint32_t r, uint32_t &b) {
-  uint32_t lo = 0u, hi = S;  // the largest b in [0, S] with kp_offset[b] <= r (kp_offset[0] = 0)
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi + 1u) >> 1;
-    if (off[mid] <= r) lo = mid;
-    else hi = mid - 1u;
-  }
-  b = lo;
-  return lo < S && off[lo] <= r && r < off[lo + 1u];
 }
 // the first slot of landmark g's list (after k_obs_top)
 __device__ __forceinline__ uint32_t list_start(const FxMapObserveArgs &A, uint32_t g) { return A.bsum[g / FXO_WG] + A.local[g]; }
 // an entry's d2 bits
 __device__ __forceinline__ unsigned long long entry_d2(uint4 e) { return ((unsigned long long)e.w << 32) | e.z; }
-// the wavefronts' counts of a verdict into a state word
-__device__ __forceinline__ void count_votes(bool v, uint32_t *word) {
-  const unsigned long long vote = __ballot(v);
-  if ((threadIdx.x & 63u) == 0u && vote) atomicAdd(word, (uint32_t)__popcll(vote));
-}
 }  // namespace
 
 extern "C" __global__ __launch_bounds__(FXO_WG) void k_obs_classify(FxMapObserveArgs A) {
   const uint32_t r = blockIdx.x * FXO_WG + threadIdx.x;
-  const uint32_t S = obs_scans(A), rows = obs_rows(A), N = obs_landmarks(A);
+  const KpView V = query_view(A.K);
+  const uint32_t N = obs_landmarks(A);
   int32_t g = -1;
   unsigned long long d2 = 0ull;
   bool proposed = false, stale = false, gated = false;
   uint32_t b;
-  if (r < rows && S && scan_of_row(kp_block_offsets(A.kp), S, r, b) && scan_used(A, b)) {
-    const float4 k = kp_block_rows<float4>(A.kp, A.max_scans)[r];
+  if (r < V.rows && V.S && scan_of_row(V.off, V.S, r, b) && scan_used(A.loc, b, A.require_flags)) {
+    const float4 k = V.kp[r];
     const int32_t id = A.map_id_of_row[r];
     if (finite3(k) && id >= 0 && (uint32_t)id < N) {
       proposed = true;
-      const int32_t a = A.alias[id];
-      const uint32_t t = a >= 0 ? (uint32_t)a : (uint32_t)id;  // a merge since the localise is followed
-      bool live = t < N && A.alias[t] == -1;
+      uint32_t t;
+      bool live = named_landmark(A.alias, N, (uint32_t)id, t);
       fx_map_landmark R;
       if (live) {
         R = reinterpret_cast<const fx_map_landmark *>(A.records)[t];
-        live = R.n_obs >= 1u && isfinite(R.x) && isfinite(R.y) && isfinite(R.z);
+        live = record_eligible(R, 1u);
       }
       if (!live) {
         stale = true;
       } else {
         double wx, wy, wz;
-        world_point(loc_of(A, b)->pose, k, wx, wy, wz);
+        world_point(loc_of(A.loc, b)->pose, k, wx, wy, wz);
         const double dx = R.x - wx, dy = R.y - wy;
         const double dd = dx * dx + dy * dy;
         if (dd <= A.gd2) g = (int32_t)t, d2 = (unsigned long long)__double_as_longlong(dd);
@@ -105,15 +80,15 @@ extern "C" __global__ __launch_bounds__(FXO_WG) void k_obs_classify(FxMapObserve
       }
     }
   }
-  if (r < A.q_max_rows) {
+  if (r < A.K.q_max_rows) {
     A.tgt[r] = g;
     A.d2[r] = d2;
     if (A.observed) A.observed[r] = -1;
     if (g >= 0) atomicAdd(&A.cnt[g], 1u);
   }
-  count_votes(proposed, &A.st[1]);
-  count_votes(gated, &A.st[4]);
-  count_votes(stale, &A.st[5]);
+  count_wave(proposed, &A.st[1]);
+  count_wave(gated, &A.st[4]);
+  count_wave(stale, &A.st[5]);
 }
 
 extern "C" __global__ __launch_bounds__(FXO_WG) void k_obs_count(FxMapObserveArgs A, uint32_t n_blocks) {
@@ -133,9 +108,9 @@ extern "C" __global__ __launch_bounds__(FXO_WG) void k_obs_top(FxMapObserveArgs 
   __shared__ uint32_t s_w[2 * FXO_NWAVE];
   uint32_t entries, unused;
   wg_scan2_blocks<FXO_NWAVE>(A.bsum, n_blocks, s_w, entries, unused);
-  const uint32_t S = obs_scans(A);
+  const uint32_t S = query_scans(A.K);
   uint32_t used = 0u;
-  for (uint32_t b = threadIdx.x; b < S; b += FXO_WG) used += scan_used(A, b) ? 1u : 0u;
+  for (uint32_t b = threadIdx.x; b < S; b += FXO_WG) used += scan_used(A.loc, b, A.require_flags) ? 1u : 0u;
   uint32_t ea, eb, ta, tb;
   wg_scan2<FXO_NWAVE>(used, 0u, s_w, ea, eb, ta, tb);
   if (threadIdx.x == 0u) A.st[0] = ta, A.st[7] = entries;
@@ -143,20 +118,20 @@ extern "C" __global__ __launch_bounds__(FXO_WG) void k_obs_top(FxMapObserveArgs 
 
 extern "C" __global__ __launch_bounds__(FXO_WG) void k_obs_scatter(FxMapObserveArgs A) {
   const uint32_t r = blockIdx.x * FXO_WG + threadIdx.x;
-  if (r >= A.q_max_rows) return;
+  if (r >= A.K.q_max_rows) return;
   const int32_t g = A.tgt[r];
   if (g < 0) return;
   uint32_t b = 0u;
-  (void)scan_of_row(kp_block_offsets(A.kp), obs_scans(A), r, b);  // (a row with a target has a scan)
+  (void)scan_of_row(kp_block_offsets(A.K.kp), query_scans(A.K), r, b);  // (a row with a target has a scan)
   const uint32_t slot = list_start(A, (uint32_t)g) + atomicAdd(&A.cur[g], 1u);
-  if (slot >= A.q_max_rows) return;  // (never: the lists hold as many entries as rows have a target)
+  if (slot >= A.K.q_max_rows) return;  // (never: the lists hold as many entries as rows have a target)
   const unsigned long long d2 = A.d2[r];
   A.ent[slot] = make_uint4(r, b, (uint32_t)d2, (uint32_t)(d2 >> 32));
 }
 
 extern "C" __global__ __launch_bounds__(FXO_WG) void k_obs_rank(FxMapObserveArgs A) {
   const uint32_t s = blockIdx.x * FXO_WG + threadIdx.x;
-  if (s >= min(A.st[7], A.q_max_rows)) return;
+  if (s >= min(A.st[7], A.K.q_max_rows)) return;
   const uint32_t row = A.ent[s].x;
   const uint32_t g = (uint32_t)A.tgt[row];
   const uint32_t base = list_start(A, g), n = A.cnt[g];
@@ -167,11 +142,11 @@ extern "C" __global__ __launch_bounds__(FXO_WG) void k_obs_rank(FxMapObserveArgs
 
 extern "C" __global__ __launch_bounds__(FXO_WG) void k_obs_fold(FxMapObserveArgs A) {
   const uint32_t s = blockIdx.x * FXO_WG + threadIdx.x;
-  if (s >= min(A.st[7], A.q_max_rows)) return;
+  if (s >= min(A.st[7], A.K.q_max_rows)) return;
   const uint32_t g = (uint32_t)A.tgt[A.sorted[s].x];
   if (list_start(A, g) != s) return;  // (the list's head works)
   const uint32_t n = A.cnt[g];
-  const float4 *kp = kp_block_rows<float4>(A.kp, A.max_scans);
+  const float4 *kp = kp_block_rows<float4>(A.K.kp, A.K.max_scans);
   fx_map_landmark *rec = reinterpret_cast<fx_map_landmark *>(A.records) + g;
   double *acc = A.acc + (size_t)g * FX_MAP_ACC;
   fx_map_landmark R;  // (only what changes: first_scan, last_scan and segment are neither read nor written)
@@ -190,7 +165,7 @@ extern "C" __global__ __launch_bounds__(FXO_WG) void k_obs_fold(FxMapObserveArgs
       if (entry_d2(f) < best_d2) best_d2 = entry_d2(f), best_row = f.x;
     }
     double wx, wy, wz;
-    world_point(loc_of(A, scan)->pose, kp[best_row], wx, wy, wz);
+    world_point(loc_of(A.loc, scan)->pose, kp[best_row], wx, wy, wz);
     const double dx = wx - ax, dy = wy - ay;
     sx += wx, sy += wy, sz += wz;
     dsx += dx, dsy += dy;
@@ -223,7 +198,7 @@ extern "C" __global__ __launch_bounds__(64) void k_obs_finish(FxMapObserveArgs A
 
 extern "C" hipError_t fxk_map_observe(hipStream_t s, const FxMapObserveArgs &A) {
   const dim3 wg(FXO_WG);
-  const uint32_t nl = (A.cap + FXO_WG - 1u) / FXO_WG, nr = (A.q_max_rows + FXO_WG - 1u) / FXO_WG;
+  const uint32_t nl = (A.cap + FXO_WG - 1u) / FXO_WG, nr = (A.K.q_max_rows + FXO_WG - 1u) / FXO_WG;
   // the counts, the cursors and the state words behind them are one region of the scratch (fxk_map_observe_scratch)
   const hipError_t e = hipMemsetAsync(A.cnt, 0, (2u * (size_t)A.cap + FX_MAP_OBSERVE_ST_WORDS) * sizeof(uint32_t), s);
   if (e != hipSuccess) return e;
@@ -241,7 +216,7 @@ extern "C" hipError_t fxk_map_observe(hipStream_t s, const FxMapObserveArgs &A) 
 
 // bytes of the context's scratch for a map of `cap` landmarks and q_max_rows rows, and the pointers carved out of it
 extern "C" size_t fxk_map_observe_scratch(FxMapObserveArgs *A, uint8_t *base) {
-  const size_t cap = A->cap, nb = (cap + FXO_WG - 1u) / FXO_WG, rows = A->q_max_rows;
+  const size_t cap = A->cap, nb = (cap + FXO_WG - 1u) / FXO_WG, rows = A->K.q_max_rows;
   FxCarve C{base, 0};
   A->cnt = C.take<uint32_t>(2u * cap + FX_MAP_OBSERVE_ST_WORDS);
   A->cur = base ? A->cnt + cap : (uint32_t *)nullptr;

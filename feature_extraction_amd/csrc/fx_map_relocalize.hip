@@ -9,9 +9,9 @@
 // any number of contexts in flight.  The map is only read.
 //
 // Launches, in stream order, after fxk_map_grid_build's five for P and five for Q:
-//   k_rl_elig     a thread a landmark: eligible or not (alias -1, n_obs >= min_landmark_obs, finite x, y, z, the segment)
+//   k_rl_elig     a thread a landmark: eligible or not (alias -1 and fx_scan_query.h's wanted_segment and record_eligible)
 //   k_rl_prep     a workgroup a scan: map_id_of_row = -1 (all workgroups share the rows), the first FX_RELOC_MAX_KP finite rows in
-//                 ascending row by ballot + prefix, the candidate pairs' d2 in LDS, their ranks by counting, the first max_seeds
+//                 ascending row (wg_ordered_slot), the candidate pairs' d2 in LDS, their ranks by counting, the first max_seeds
 //   k_rl_hyp<0>   a workgroup a (scan, seed, FXR_CHUNK slots of P): a lane a landmark g; it walks the h about g, forms the
 //                 hypothesis a -> g, b -> h and scores it: the scan's keypoints come from LDS, each image walks Q's 3 x 3 cells.
 //                 The lane keeps its best (score, lowest h); the workgroup's best (score, lowest g, lowest h) goes to `partial`,
@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "fx_map_constellation.h"
+#include "fx_scan_query.h"
 #include "../../include/fx.h"
 
 using namespace fxs;
@@ -38,8 +39,6 @@ extern "C" hipError_t fxk_map_grid_build(hipStream_t s, const FxMapMergeArgs &A)
 extern "C" size_t fxk_map_merge_scratch(FxMapMergeArgs *A, uint8_t *base);
 
 namespace {
-__device__ __forceinline__ uint32_t rl_scans(const FxMapRelocalizeArgs &A) { return min(min(A.n_scans, A.kp[0]), A.max_scans); }
-__device__ __forceinline__ uint32_t rl_rows(const FxMapRelocalizeArgs &A) { return min(min(A.kp[1], A.max_total), A.q_max_rows); }
 // the search of scan b
 __device__ __forceinline__ Search search_of(const FxMapRelocalizeArgs &A, uint32_t b) {
   Search S;
@@ -58,18 +57,10 @@ __device__ __forceinline__ Search search_of(const FxMapRelocalizeArgs &A, uint32
 extern "C" __global__ __launch_bounds__(FXR_WG) void k_rl_elig(FxMapRelocalizeArgs A) {
   const uint32_t i = blockIdx.x * FXR_WG + threadIdx.x;
   if (i >= A.P.cap) return;
-  bool ok = false;
-  if (i < n_landmarks(A.P)) {
-    const fx_map_landmark R = records(A.P)[i];
-    uint32_t seg = A.segment;
-    bool any_seg = A.segment == FX_LOC_ANY_SEGMENT, some = true;
-    if (A.segment == FX_LOC_LAST_SEGMENT) {
-      const uint32_t n = reinterpret_cast<const fx_map_header *>(A.P.header)->segments;
-      some = n != 0u, seg = n - 1u;
-    }
-    ok = some && A.P.alias[i] == -1 && R.n_obs >= A.min_landmark_obs && isfinite(R.x) && isfinite(R.y) && isfinite(R.z) &&
-         (any_seg || R.segment == seg);
-  }
+  uint32_t seg;
+  bool any_seg;
+  const bool ok = i < n_landmarks(A.P) && wanted_segment(A.P.header, A.segment, seg, any_seg) && A.P.alias[i] == -1 &&
+                  record_eligible(records(A.P)[i], A.min_landmark_obs, any_seg, seg);
   A.elig[i] = ok ? 1 : 0;
 }
 
@@ -79,38 +70,28 @@ extern "C" __global__ __launch_bounds__(FXR_WG) void k_rl_prep(FxMapRelocalizeAr
   __shared__ uint32_t s_wave[FXR_NWAVE];
   __shared__ uint32_t s_count;
 
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, b = blockIdx.x;
-  for (unsigned long long r = (unsigned long long)b * FXR_WG + tid; r < A.q_max_rows; r += (unsigned long long)A.n_scans * FXR_WG)
+  const uint32_t tid = threadIdx.x, b = blockIdx.x;
+  for (unsigned long long r = (unsigned long long)b * FXR_WG + tid; r < A.K.q_max_rows; r += (unsigned long long)A.K.n_scans * FXR_WG)
     A.map_id_of_row[r] = -1;
   if (tid == 0u) A.n_hyp[b] = 0ull, A.runner[b] = 0u, s_count = 0u;
-  const uint32_t S = rl_scans(A), rows = rl_rows(A);
+  const KpView V = query_view(A.K);
   uint32_t *meta = A.meta + 4u * b;
-  if (b >= S) {  // (uniform)
+  if (b >= V.S) {  // (uniform)
     if (tid < 4u) meta[tid] = 0u;
     return;
   }
-  const uint32_t *off = kp_block_offsets(A.kp);
-  const float4 *kp = kp_block_rows<float4>(A.kp, A.max_scans);
-  const uint32_t q_lo = min(off[b], rows), q_hi = max(min(off[b + 1u], rows), q_lo);
+  uint32_t q_lo, q_hi;
+  scan_rows(V, b, q_lo, q_hi);
 
   // ---- the used keypoints: the finite rows in ascending row, the first FX_RELOC_MAX_KP kept
   uint32_t found = 0u;  // (uniform)
   for (unsigned long long r0 = q_lo; r0 < q_hi && found <= FX_RELOC_MAX_KP; r0 += FXR_WG) {
     const uint32_t i = (uint32_t)min(r0 + tid, (unsigned long long)q_hi);
     float4 k = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (i < q_hi) k = kp[i];
+    if (i < q_hi) k = V.kp[i];
     const bool ok = i < q_hi && finite3(k);
-    const unsigned long long bal = __ballot(ok);
-    if (lane == 0u) s_wave[wave] = (uint32_t)__popcll(bal);
-    __syncthreads();
-    uint32_t before = 0u, all = 0u;
-#pragma unroll
-    for (uint32_t w = 0; w < FXR_NWAVE; ++w) {
-      const uint32_t n = s_wave[w];
-      before += w < wave ? n : 0u;
-      all += n;
-    }
-    const uint32_t slot = found + before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+    uint32_t slot, all;
+    wg_ordered_slot<FXR_NWAVE>(ok, s_wave, found, slot, all);
     if (ok && slot < FX_RELOC_MAX_KP) {
       double *q = A.kq + ((size_t)b * FX_RELOC_MAX_KP + slot) * 3u;
       q[0] = (double)k.x, q[1] = (double)k.y, q[2] = (double)k.z;
@@ -141,7 +122,7 @@ extern "C" __global__ __launch_bounds__(64) void k_rl_finish(FxMapRelocalizeArgs
   __shared__ int32_t s_lm[FX_RELOC_MAX_KP];
   __shared__ uint32_t s_valid;
   const uint32_t tid = threadIdx.x, b = blockIdx.x;
-  const uint32_t S = rl_scans(A);
+  const uint32_t S = query_scans(A.K);
   const uint32_t n_kp = min(A.meta[4u * b], FX_RELOC_MAX_KP), n_seeds = A.meta[4u * b + 1u], trunc = A.meta[4u * b + 2u];
   const FxRelocWinner W = A.win[b];
   const double idd = (double)A.inlier_dist;
@@ -190,7 +171,7 @@ extern "C" __global__ __launch_bounds__(64) void k_rl_finish(FxMapRelocalizeArgs
   __syncthreads();
   if (s_valid && lm >= 0) {
     const uint32_t row = A.krow[(size_t)b * FX_RELOC_MAX_KP + tid];
-    if (row < A.q_max_rows) A.map_id_of_row[row] = lm;
+    if (row < A.K.q_max_rows) A.map_id_of_row[row] = lm;
   }
 }
 
@@ -198,20 +179,20 @@ extern "C" hipError_t fxk_map_relocalize(hipStream_t s, const FxMapRelocalizeArg
   (void)fxk_map_grid_build(s, A.P);
   (void)fxk_map_grid_build(s, A.Q);
   hipLaunchKernelGGL(k_rl_elig, dim3((A.P.cap + FXR_WG - 1u) / FXR_WG), dim3(FXR_WG), 0, s, A);
-  hipLaunchKernelGGL(k_rl_prep, dim3(A.n_scans), dim3(FXR_WG), 0, s, A);
+  hipLaunchKernelGGL(k_rl_prep, dim3(A.K.n_scans), dim3(FXR_WG), 0, s, A);
   auto hyp = [&](int pass) {  // (a grid's z holds 65535 scans)
     FxMapRelocalizeArgs B = A;
-    for (B.scan0 = 0u; B.scan0 < A.n_scans; B.scan0 += 65535u) {
-      const uint32_t n = A.n_scans - B.scan0 < 65535u ? A.n_scans - B.scan0 : 65535u;
+    for (B.scan0 = 0u; B.scan0 < A.K.n_scans; B.scan0 += 65535u) {
+      const uint32_t n = A.K.n_scans - B.scan0 < 65535u ? A.K.n_scans - B.scan0 : 65535u;
       const dim3 grid(A.chunks, A.max_seeds, n);
       if (pass == 0) hipLaunchKernelGGL(k_rl_hyp<0>, grid, dim3(FXR_WG), 0, s, B);
       else hipLaunchKernelGGL(k_rl_hyp<1>, grid, dim3(FXR_WG), 0, s, B);
     }
   };
   hyp(0);
-  hipLaunchKernelGGL(k_rl_reduce, dim3(A.n_scans), dim3(FXR_WG), 0, s, A);
+  hipLaunchKernelGGL(k_rl_reduce, dim3(A.K.n_scans), dim3(FXR_WG), 0, s, A);
   hyp(1);
-  hipLaunchKernelGGL(k_rl_finish, dim3(A.n_scans), dim3(64), 0, s, A);
+  hipLaunchKernelGGL(k_rl_finish, dim3(A.K.n_scans), dim3(64), 0, s, A);
   return hipGetLastError();
 }
 
@@ -222,7 +203,7 @@ extern "C" size_t fxk_map_relocalize_scratch(FxMapRelocalizeArgs *A, uint8_t *ba
   C.o += fxk_map_merge_scratch(&A->Q, base ? base + C.o : nullptr);
   A->P.prop = A->P.pred = A->P.succ = nullptr, A->P.keep = nullptr;  // (the grid's mark leaves the merge's words alone)
   A->Q.prop = A->Q.pred = A->Q.succ = nullptr, A->Q.keep = nullptr;
-  const size_t n = A->n_scans, K = FX_RELOC_MAX_KP;
+  const size_t n = A->K.n_scans, K = FX_RELOC_MAX_KP;
   A->kq = C.take<double>(n * K * 3u);
   A->n_hyp = C.take<unsigned long long>(n);
   A->win = C.take<FxRelocWinner>(n);

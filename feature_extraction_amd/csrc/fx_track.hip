@@ -6,7 +6,7 @@
 // on one lane (the build's -ffp-contract=off): the same bytes from run to run and with any number of contexts in flight.
 //
 // Launches, in stream order (FXT_WG = 256 rows a workgroup everywhere a thread is a row):
-//   k_track_init     a thread a row: the row's scan by binary search in kp_offset, child = none, the two row outputs to their
+//   k_track_init     a thread a row: the row's scan (fx_scan_query.h scan_of_row), child = none, the two row outputs to their
 //                    "nothing" words
 //   k_track_poses    one workgroup, tiles of FXT_WG links: the records and their good flags into LDS; one lane folds (c, s),
 //                    every thread forms its link's rotated translation from the (c, s) before it, three lanes of three
@@ -23,12 +23,13 @@
 //   k_track_scatter  a thread a row: landmark_of_row, obs_row[obs0 + depth] = r
 //   k_track_fuse     a lane a landmark: two sequential passes over its contiguous obs_row segment
 // The block's layout, the workgroup scan and the world-frame point of an observation are fx_device.h's (kp_block_*, wg_scan2,
-// world_point): fx_map.hip uses the same ones.
+// world_point): fx_map.hip uses the same ones.  The block read as a query (the scans and rows that take part, a row's scan) is
+// fx_scan_query.h's, as in the map's calls that read scans.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
-#include "fx_device.h"
+#include "fx_scan_query.h"
 #include "../../include/fx.h"
 
 #define FXT_WG 256
@@ -37,26 +38,12 @@
 static_assert(sizeof(fx_pose) == 48 && sizeof(fx_landmark) == 48 && sizeof(fx_track_header) == 32 && sizeof(fx_track_options) == 8, "include/fx.h");
 
 namespace {
-// the block's header words, kp_offset[max_scans + 1] and (x, y, z, elevation) rows (include/fx.h fx_pack_keypoint_block)
-struct Block {
-  const uint32_t *off;
-  const float4 *kp;
-  uint32_t S, rows;  // scans and rows that take part
-};
-__device__ __forceinline__ Block block_view(const FxTrackArgs &A) {
-  Block b;
-  b.off = kp_block_offsets(A.kp);
-  b.kp = kp_block_rows<float4>(A.kp, A.max_scans);
-  b.S = min(min(A.n_scans, A.kp[0]), A.max_scans);
-  b.rows = min(min(A.kp[1], A.max_total), A.q_max_rows);
-  return b;
-}
 __device__ __forceinline__ bool good_link(const fx_registration &r) {
   return (r.flags & FX_REG_VALID) && isfinite(r.c) && isfinite(r.s) && isfinite(r.tx) && isfinite(r.ty) && isfinite(r.tz);
 }
 // is row r the first row of a landmark, and of how many observations
 __device__ __forceinline__ uint32_t landmark_len(const FxTrackArgs &A, const uint2 *jump, uint32_t r) {
-  if (r >= A.q_max_rows || A.scan_of[r] == FX_TRACK_NONE || jump[r].x != r) return 0u;
+  if (r >= A.K.q_max_rows || A.scan_of[r] == FX_TRACK_NONE || jump[r].x != r) return 0u;
   const uint32_t n = A.len[r];
   return n >= A.min_obs ? n : 0u;
 }
@@ -65,19 +52,10 @@ __device__ __forceinline__ uint32_t landmark_len(const FxTrackArgs &A, const uin
 extern "C" __global__ __launch_bounds__(FXT_WG) void k_track_init(FxTrackArgs A) {
   const uint32_t r = blockIdx.x * FXT_WG + threadIdx.x;
   if (r == 0u) A.counters[0] = 0u;
-  if (r >= A.q_max_rows) return;
-  const Block B = block_view(A);
-  uint32_t b = FX_TRACK_NONE;
-  if (r < B.rows && B.S) {
-    uint32_t lo = 0u, hi = B.S;  // the largest b in [0, S] with kp_offset[b] <= r (kp_offset[0] = 0)
-    while (lo < hi) {
-      const uint32_t mid = (lo + hi + 1u) >> 1;
-      if (B.off[mid] <= r) lo = mid;
-      else hi = mid - 1u;
-    }
-    if (lo < B.S && B.off[lo] <= r && r < B.off[lo + 1u]) b = lo;
-  }
-  A.scan_of[r] = b;
+  if (r >= A.K.q_max_rows) return;
+  const KpView B = query_view(A.K);
+  uint32_t b;
+  A.scan_of[r] = r < B.rows && B.S && scan_of_row(B.off, B.S, r, b) ? b : FX_TRACK_NONE;
   A.child[r] = FX_TRACK_NONE;
   A.landmark_of_row[r] = -1;
   A.obs_row[r] = FX_TRACK_NONE;
@@ -91,7 +69,7 @@ extern "C" __global__ __launch_bounds__(FXT_WG) void k_track_poses(FxTrackArgs A
   __shared__ uint32_t s_seg[FXT_WG + 1];
   __shared__ uint32_t s_gaps;
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-  const uint32_t S = min(min(A.n_scans, A.kp[0]), A.max_scans);
+  const uint32_t S = query_scans(A.K);
   const fx_registration *reg = reinterpret_cast<const fx_registration *>(A.reg);
   fx_pose *poses = reinterpret_cast<fx_pose *>(A.poses);
   if (tid == 0u) {
@@ -102,8 +80,8 @@ extern "C" __global__ __launch_bounds__(FXT_WG) void k_track_poses(FxTrackArgs A
     p.segment = 0u, p.flags = S ? 0u : FX_POSE_NO_SCAN;
     poses[0] = p;
   }
-  for (uint32_t b0 = 1u; b0 < A.n_scans; b0 += FXT_WG) {  // the tile's poses are b0 + i, their links b0 + i - 1
-    const uint32_t n = min((uint32_t)FXT_WG, A.n_scans - b0);
+  for (uint32_t b0 = 1u; b0 < A.K.n_scans; b0 += FXT_WG) {  // the tile's poses are b0 + i, their links b0 + i - 1
+    const uint32_t n = min((uint32_t)FXT_WG, A.K.n_scans - b0);
     __syncthreads();  // (the tile before is written out, its carry is in slot 0)
     if (tid < n) {
       const uint32_t b = b0 + tid;
@@ -176,8 +154,8 @@ extern "C" __global__ __launch_bounds__(FXT_WG) void k_track_poses(FxTrackArgs A
 
 extern "C" __global__ __launch_bounds__(FXT_WG) void k_track_link(FxTrackArgs A) {
   const uint32_t r = blockIdx.x * FXT_WG + threadIdx.x;
-  if (r >= A.q_max_rows) return;
-  const Block B = block_view(A);
+  if (r >= A.K.q_max_rows) return;
+  const KpView B = query_view(A.K);
   const uint32_t b = A.scan_of[r];
   int32_t prop = -1;
   if (b != FX_TRACK_NONE && b >= 1u && A.inlier[r] == 1u) {
@@ -195,15 +173,14 @@ extern "C" __global__ __launch_bounds__(FXT_WG) void k_track_link(FxTrackArgs A)
 extern "C" __global__ __launch_bounds__(FXT_WG) void k_track_parent(FxTrackArgs A) {
   const uint32_t r = blockIdx.x * FXT_WG + threadIdx.x;
   bool lost = false;
-  if (r < A.q_max_rows) {
+  if (r < A.K.q_max_rows) {
     const int32_t t = A.prop[r];
     const bool kept = t >= 0 && A.child[t] == r;
     lost = t >= 0 && !kept;
     A.jump[0][r] = kept ? make_uint2((uint32_t)t, 1u) : make_uint2(r, 0u);
     A.len[r] = 0u;
   }
-  const unsigned long long bal = __ballot(lost);
-  if ((threadIdx.x & 63u) == 0u && bal) atomicAdd(&A.counters[0], (uint32_t)__popcll(bal));
+  count_wave(lost, &A.counters[0]);
 }
 
 extern "C" __global__ __launch_bounds__(FXT_WG) void k_track_jump(const uint2 *src, uint2 *dst, uint32_t n) {
@@ -216,7 +193,7 @@ extern "C" __global__ __launch_bounds__(FXT_WG) void k_track_jump(const uint2 *s
 
 extern "C" __global__ __launch_bounds__(FXT_WG) void k_track_len(FxTrackArgs A, const uint2 *jump) {
   const uint32_t r = blockIdx.x * FXT_WG + threadIdx.x;
-  if (r >= A.q_max_rows || A.scan_of[r] == FX_TRACK_NONE || A.child[r] != FX_TRACK_NONE) return;
+  if (r >= A.K.q_max_rows || A.scan_of[r] == FX_TRACK_NONE || A.child[r] != FX_TRACK_NONE) return;
   const uint2 j = jump[r];  // a leaf: the one row of its track nobody kept as a parent
   A.len[j.x] = j.y + 1u;
 }
@@ -234,7 +211,7 @@ extern "C" __global__ __launch_bounds__(FXT_WG) void k_track_top(FxTrackArgs A, 
   uint32_t base_a, base_b;
   wg_scan2_blocks<FXT_NWAVE>(A.bsum, n_blocks, s_w, base_a, base_b);
   if (threadIdx.x == 0u) {
-    const Block B = block_view(A);
+    const KpView B = query_view(A.K);
     fx_track_header h;
     h.scans = B.S, h.rows = B.rows;
     h.n_landmarks = base_a, h.n_obs = base_b, h.n_conflicts = A.counters[0], h.n_gaps = A.counters[1];
@@ -249,7 +226,7 @@ extern "C" __global__ __launch_bounds__(FXT_WG) void k_track_number(FxTrackArgs 
   const uint32_t n = landmark_len(A, jump, r);
   uint32_t ea, eb, ta, tb;
   wg_scan2<FXT_NWAVE>(n ? 1u : 0u, n, s_w, ea, eb, ta, tb);
-  if (r >= A.q_max_rows) return;
+  if (r >= A.K.q_max_rows) return;
   if (n) {
     const uint32_t id = A.bsum[blockIdx.x] + ea;
     A.lm_id[r] = (int32_t)id;
@@ -262,7 +239,7 @@ extern "C" __global__ __launch_bounds__(FXT_WG) void k_track_number(FxTrackArgs 
 
 extern "C" __global__ __launch_bounds__(FXT_WG) void k_track_scatter(FxTrackArgs A, const uint2 *jump) {
   const uint32_t r = blockIdx.x * FXT_WG + threadIdx.x;
-  if (r >= A.q_max_rows || A.scan_of[r] == FX_TRACK_NONE) return;
+  if (r >= A.K.q_max_rows || A.scan_of[r] == FX_TRACK_NONE) return;
   const uint2 j = jump[r];
   const int32_t id = A.lm_id[j.x];
   if (id < 0) return;
@@ -274,7 +251,7 @@ extern "C" __global__ __launch_bounds__(FXT_WG) void k_track_fuse(FxTrackArgs A)
   const uint32_t i = blockIdx.x * FXT_WG + threadIdx.x;
   const fx_track_header *h = reinterpret_cast<const fx_track_header *>(A.header);
   if (i >= A.max_landmarks || i >= h->n_landmarks) return;
-  const Block B = block_view(A);
+  const KpView B = query_view(A.K);
   const fx_pose *poses = reinterpret_cast<const fx_pose *>(A.poses);
   const uint32_t root = A.lm_root[i], n = A.len[root], o = A.obs0[root], first_scan = A.scan_of[root];
   double sx = 0.0, sy = 0.0, sz = 0.0;
@@ -302,7 +279,7 @@ extern "C" __global__ __launch_bounds__(FXT_WG) void k_track_fuse(FxTrackArgs A)
 }
 
 extern "C" hipError_t fxk_track(hipStream_t s, const FxTrackArgs &A) {
-  const uint32_t R = A.q_max_rows, nb = (R + FXT_WG - 1u) / FXT_WG;
+  const uint32_t R = A.K.q_max_rows, nb = (R + FXT_WG - 1u) / FXT_WG;
   const dim3 wg(FXT_WG), grid(nb);
   if (nb) hipLaunchKernelGGL(k_track_init, grid, wg, 0, s, A);
   else (void)hipMemsetAsync(A.counters, 0, sizeof(uint32_t), s);
@@ -313,7 +290,7 @@ extern "C" hipError_t fxk_track(hipStream_t s, const FxTrackArgs &A) {
   if (nb) {
     hipLaunchKernelGGL(k_track_link, grid, wg, 0, s, A);
     hipLaunchKernelGGL(k_track_parent, grid, wg, 0, s, A);
-    for (uint32_t span = 1u; span < A.n_scans; span <<= 1, cur ^= 1u)  // a chain has at most n_scans - 1 links
+    for (uint32_t span = 1u; span < A.K.n_scans; span <<= 1, cur ^= 1u)  // a chain has at most n_scans - 1 links
       hipLaunchKernelGGL(k_track_jump, grid, wg, 0, s, A.jump[cur], A.jump[cur ^ 1u], R);
     hipLaunchKernelGGL(k_track_len, grid, wg, 0, s, A, A.jump[cur]);
     hipLaunchKernelGGL(k_track_sums, grid, wg, 0, s, A, A.jump[cur], nb);

@@ -13,6 +13,7 @@ from tests import map_compact_util as mc
 from tests import map_expect_util as eu
 from tests import map_localize_util as lu
 from tests import map_merge_util as mm
+from tests import track_util as tu
 from tests.test_gpu_map import _run
 from tests.test_gpu_map_compact import _compact, _same_state
 from tests.test_gpu_map_merge import _merge_to_fixpoint, _one_batch
@@ -55,13 +56,16 @@ def _call(ctx, mp, kp, loc, ids, n_scans, q, raw_e, raw_s, **opts):
     return capi.expect_records(res[:8]), _host(raw_e, cap), _host(raw_s, cap)
 
 
-def _expect(ctx, mp, st, c, what, counters=None, n_scans=None, q_max_rows=None, stored=None, max_scans=None, max_total=None, **opts):
+def _expect(ctx, mp, st, c, what, counters=None, n_scans=None, q_max_rows=None, stored=None, max_scans=None, max_total=None, edge=None, **opts):
     """One fx_map_expect of a case against one map_expect_reference call; the map must keep every byte.  counters: the device
-    arrays of an FX_EXPECT_ADD call (else the call writes, into arrays filled with a sentinel).  Returns (result, expected, seen)."""
+    arrays of an FX_EXPECT_ADD call (else the call writes, into arrays filled with a sentinel).  edge: one of
+    tu.edge_blocks(c["rows"]) in the place of the case's block.  Returns (result, expected, seen)."""
     n_scans = len(c["off"]) - 1 if n_scans is None else n_scans
     q = len(c["rows"]) if q_max_rows is None else q_max_rows
     opts = dict(c["opts"], **opts)
-    kp, loc_d, ids_d, loc, ids = _upload(ctx, c, n_scans, q, max_scans, max_total, stored)
+    if edge:
+        c, max_scans, max_total = dict(c, off=edge["off"], rows=edge["rows"]), edge["max_scans"], edge["max_total"]
+    kp, loc_d, ids_d, loc, ids = _upload(ctx, c, n_scans, q, max_scans, max_total, stored, edge and edge["blk"])
     add = counters is not None
     raw_e, raw_s = counters if add else _counters(ctx, mp, SENTINEL)
     before = (_host(raw_e, mp.max_landmarks), _host(raw_s, mp.max_landmarks))
@@ -181,6 +185,14 @@ def test_03_sizes_as_in_the_localise(ctx):
     _expect(ctx, mp, st, c, "(3) a block that stores fewer rows", stored=rows - 5)
     res, e, s = _expect(ctx, mp, st, c, "(3) no rows at all", q_max_rows=0)
     assert res["seen"] == 0 == res["stale"] and res["expected"] == res["in_box"] > 0
+    mp.close()
+    # the edges only a hand-made block reaches, on a map of four landmarks: scans of 2, 0 and 3 rows, every row on its landmark
+    frags = lu.lattice(4, pitch=7.0)
+    four = eu.case(frags, [lu.rows_at(frags, [0, 1], 0.02), [], lu.rows_at(frags, [1, 2, 3], -0.03, 0.01)], [0, 1, 1, 2, 3], min_range=0.0, **eu.WIDE)
+    mp, st = _map_of(ctx, four, "(3) a map of four")
+    for edge in tu.edge_blocks(four["rows"]):
+        res, _, _ = _expect(ctx, mp, st, four, f"(3) {edge['what']}", edge=edge)
+        assert res["scans_used"] == 3 and res["stale"] == 0 and res["seen"] == len(edge["rows"])
     mp.close()
     empty = ctx.map_create(8, 8)
     res, e, s = _expect(ctx, empty, capi.map_state(8, 8), c, "(3) an empty map")

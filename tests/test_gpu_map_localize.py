@@ -34,10 +34,10 @@ def _map_bytes(mp):
     return repr(sorted(mp.header().items())).encode() + mp.landmarks().tobytes() + mp.alias().tobytes()
 
 
-def _device(ctx, off, rows, priors, max_scans, max_total, stored=None):
+def _device(ctx, off, rows, priors, max_scans, max_total, stored=None, blk=None):
     import torch
     dev = f"cuda:{ctx.device}"
-    blk = tu.block(off, rows, max_scans, max_total, stored)
+    blk = tu.block(off, rows, max_scans, max_total, stored) if blk is None else blk
     return (torch.from_numpy(blk).to(dev), max_scans, max_total), torch.from_numpy(np.ascontiguousarray(priors).view(np.float64).reshape(-1, 6).copy()).to(dev)
 
 
@@ -55,15 +55,18 @@ def _call(ctx, mp, kp, pri, n_scans, q, nearest=True, **opts):
 
 
 def _localize(ctx, mp, st, off, rows, priors, what, n_scans=None, max_scans=None, max_total=None, q_max_rows=None, stored=None, nearest=True,
-              priors_device=None, **opts):
+              priors_device=None, edge=None, **opts):
     """One fx_map_localize against one map_localize_reference call; the map must come out as it went in.  priors_device: a device
     tensor of n_scans fx_pose records the call reads in place of an upload of `priors` (a hand-over that no host read stands
-    between); `priors` is then what the reference is given and what the records are held to."""
+    between); `priors` is then what the reference is given and what the records are held to.  edge: one of tu.edge_blocks(rows) in
+    the place of the block."""
     n_scans = len(off) - 1 if n_scans is None else n_scans
     max_scans = max(len(off) - 1, n_scans) + 2 if max_scans is None else max_scans
     max_total = len(rows) + 9 if max_total is None else max_total
     q = len(rows) if q_max_rows is None else q_max_rows
-    kp, pri = _device(ctx, off, rows, priors, max_scans, max_total, stored)
+    if edge:
+        off, rows, max_scans, max_total = edge["off"], edge["rows"], edge["max_scans"], edge["max_total"]
+    kp, pri = _device(ctx, off, rows, priors, max_scans, max_total, stored, edge and edge["blk"])
     before = _map_bytes(mp)
     got = _call(ctx, mp, kp, pri if priors_device is None else priors_device, n_scans, q, nearest, **opts)
     assert _map_bytes(mp) == before, f"{what}: the map is read, never written"
@@ -155,6 +158,13 @@ def test_b_a_block_of_max_scans_empty_scans_and_row_arrays_of_other_lengths(big_
     _localize(c, mp, st, off, rows, priors, "(b) a block that stores fewer rows", stored=len(rows) - 40)
     got, _ = _localize(c, mp, st, off, rows[:0], priors, "(b) no rows at all", q_max_rows=0, max_total=4, stored=0, n_scans=2)
     assert (got["rec"]["flags"] == capi.FX_LOC_NO_HYPOTHESIS).all()
+    # the edges only a hand-made block reaches, on a map of four landmarks: scans of 2, 0 and 3 rows next to them
+    frags = lu.lattice(4, pitch=7.0)
+    small, st4 = _one_batch(c, mm.fragments(frags, 3), "(b) a map of four", carry=8)
+    off, rows = lu.scans([lu.rows_at(frags, [0, 1], 0.1), [], lu.rows_at(frags, [1, 2, 3], -0.05, 0.1)])
+    for edge in tu.edge_blocks(rows):
+        _localize(c, small, st4, off, rows, lu.identity(3, ty=0.25), f"(b) {edge['what']}", edge=edge, min_inliers=2, min_baseline=0.5)
+    small.close()
 
 
 # ---- (c) the grid

@@ -32,15 +32,16 @@ def ctx(fxlib):
     c.close()
 
 
-def _upload(ctx, c, n_scans, q, max_scans=None, max_total=None, stored=None):
+def _upload(ctx, c, n_scans, q, max_scans=None, max_total=None, stored=None, blk=None):
     """A case's block, records and table on the device: the records padded to n_scans with VALID identities, the table to q words
-    with landmark 0 (a non-row's word must not matter)."""
+    with landmark 0 (a non-row's word must not matter).  blk: the block's bytes, laid out for max_scans and max_total, in the place
+    of the one built from the case."""
     import torch
     dev = f"cuda:{ctx.device}"
     scans = len(c["off"]) - 1
     max_scans = max(scans, n_scans) + 2 if max_scans is None else max_scans
     max_total = len(c["rows"]) + 9 if max_total is None else max_total
-    blk = tu.block(c["off"], c["rows"], max_scans, max_total, stored)
+    blk = tu.block(c["off"], c["rows"], max_scans, max_total, stored) if blk is None else blk
     loc = np.concatenate([c["loc"], ou.loc_records(max(0, n_scans - len(c["loc"])))])
     ids = np.concatenate([c["ids"], np.zeros(max(0, q - len(c["ids"])), np.int32)])
     return ((torch.from_numpy(blk).to(dev), max_scans, max_total), torch.from_numpy(loc.view(np.float64).reshape(-1, LOC_WORDS).copy()).to(dev),
@@ -62,13 +63,15 @@ def _call(ctx, mp, kp, loc, ids, n_scans, q, optional=True, **opts):
             raw[2][:q].cpu().numpy() if optional else None)
 
 
-def _observe(ctx, mp, st, c, what, n_scans=None, q_max_rows=None, stored=None, max_scans=None, max_total=None, dry_run=False, **opts):
+def _observe(ctx, mp, st, c, what, n_scans=None, q_max_rows=None, stored=None, max_scans=None, max_total=None, dry_run=False, edge=None, **opts):
     """One fx_map_observe of a case against one map_observe_reference call, the map's state through the snapshot.  Returns (the
-    reference's new state, (result, gained, observed))."""
+    reference's new state, (result, gained, observed)).  edge: one of tu.edge_blocks(c["rows"]) in the place of the case's block."""
     n_scans = len(c["off"]) - 1 if n_scans is None else n_scans
     q = len(c["rows"]) if q_max_rows is None else q_max_rows
     opts = dict(c["opts"], **opts)
-    kp, loc_d, ids_d, loc, ids = _upload(ctx, c, n_scans, q, max_scans, max_total, stored)
+    if edge:
+        c, max_scans, max_total = dict(c, off=edge["off"], rows=edge["rows"]), edge["max_scans"], edge["max_total"]
+    kp, loc_d, ids_d, loc, ids = _upload(ctx, c, n_scans, q, max_scans, max_total, stored, edge and edge["blk"])
     got = _call(ctx, mp, kp, loc_d, ids_d, n_scans, q, mode=capi.FX_OBS_DRY_RUN if dry_run else capi.FX_OBS_APPLY, **opts)
     off = c["off"][:min(len(c["off"]) - 1, kp[1]) + 1]
     new, *ref = capi.map_observe_reference(st, off, c["rows"][:len(c["rows"]) if stored is None else stored], loc, ids, n_scans, q_max_rows=q,
@@ -236,6 +239,14 @@ def test_06_scan_filters_bad_rows_and_sizes(ctx):
     st, _ = _observe(ctx, mp, st, c, "(6) a block that stores fewer rows", stored=rows - 5)
     st, (res, _, _) = _observe(ctx, mp, st, c, "(6) no rows at all", q_max_rows=0)
     assert res == dict(zip(capi.MAP_OBSERVE_RESULT_FIELDS, (5, 0, 0, 0, 0, 0, 0, 0)))
+    mp.close()
+    # the edges only a hand-made block reaches, on a map of four landmarks: scans of 2, 0 and 3 rows, every row on its landmark
+    frags = lu.lattice(4, pitch=7.0)
+    four = ou.case(frags, [lu.rows_at(frags, [0, 1], 0.02), [], lu.rows_at(frags, [1, 2, 3], -0.03, 0.01)], [0, 1, 1, 2, 3])
+    mp, st = _map_of(ctx, four, "(6) a map of four")
+    for edge in tu.edge_blocks(four["rows"]):
+        st, (res, _, observed) = _observe(ctx, mp, st, four, f"(6) {edge['what']}", edge=edge)
+        assert res["scans_used"] == 3 and res["added"] == len(edge["rows"]) and observed.tolist() == [0, 1, 1, 2, 3][:res["added"]] + [-1] * (5 - res["added"])
     mp.close()
     empty = ctx.map_create(8, 8)
     _, (res, gained, observed) = _observe(ctx, empty, capi.map_state(8, 8), c, "(6) an empty map")

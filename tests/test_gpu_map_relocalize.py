@@ -31,9 +31,10 @@ def ctx(fxlib):
     c.close()
 
 
-def _block(ctx, off, rows, max_scans, max_total, stored=None):
+def _block(ctx, off, rows, max_scans, max_total, stored=None, blk=None):
     import torch
-    return (torch.from_numpy(tu.block(off, rows, max_scans, max_total, stored)).to(f"cuda:{ctx.device}"), max_scans, max_total)
+    blk = tu.block(off, rows, max_scans, max_total, stored) if blk is None else blk
+    return (torch.from_numpy(blk).to(f"cuda:{ctx.device}"), max_scans, max_total)
 
 
 def _call(ctx, mp, kp, n_scans, q, **opts):
@@ -48,13 +49,16 @@ def _call(ctx, mp, kp, n_scans, q, **opts):
     return {"rec": capi.relocalize_records(raw[0][:n_scans * REC_WORDS]), "map_id_of_row": raw[1][:q].cpu().numpy(), "raw": raw[0]}
 
 
-def _reloc(ctx, mp, st, off, rows, what, n_scans=None, max_scans=None, max_total=None, q_max_rows=None, stored=None, **opts):
-    """One fx_map_relocalize against one map_relocalize_reference call; the map's snapshot must come out as it went in."""
+def _reloc(ctx, mp, st, off, rows, what, n_scans=None, max_scans=None, max_total=None, q_max_rows=None, stored=None, edge=None, **opts):
+    """One fx_map_relocalize against one map_relocalize_reference call; the map's snapshot must come out as it went in.  edge: one of
+    tu.edge_blocks(rows) in the place of the block."""
     n_scans = len(off) - 1 if n_scans is None else n_scans
     max_scans = max(len(off) - 1, n_scans) + 2 if max_scans is None else max_scans
     max_total = len(rows) + 9 if max_total is None else max_total
     q = len(rows) if q_max_rows is None else q_max_rows
-    kp = _block(ctx, off, rows, max_scans, max_total, stored)
+    if edge:
+        off, rows, max_scans, max_total = edge["off"], edge["rows"], edge["max_scans"], edge["max_total"]
+    kp = _block(ctx, off, rows, max_scans, max_total, stored, edge and edge["blk"])
     before = mp.export_state()
     got = _call(ctx, mp, kp, n_scans, q, **opts)
     assert mp.export_state() == before, f"{what}: the map is read, never written"
@@ -139,6 +143,14 @@ def test_b_scans_beyond_the_block_and_row_arrays_of_other_lengths(ctx):
     _reloc(ctx, mp, st, off, kp, "(b) a block that stores fewer rows", stored=len(kp) - 5)
     got, _ = _reloc(ctx, mp, st, off, kp[:0], "(b) no rows at all", q_max_rows=0, max_total=4, stored=0, n_scans=2)
     assert (got["rec"]["flags"] == ru.NOHYP).all()
+    mp.close()
+    # the edges only a hand-made block reaches, on a map of four landmarks (no two pairs of one length): scans of 2, 0 and 3 rows
+    frags = [(0, 0.0, 0.0), (0, 9.0, 0.0), (0, 0.0, 5.0), (0, 11.0, 8.0)]
+    mp, st = _one_batch(ctx, mm.fragments(frags, 3), "(b) a map of four", carry=8)
+    off, kp = lu.scans([ru.view_of(frags, [0, 1], 0.3, 2.0, 1.0), [], ru.view_of(frags, [1, 2, 3], -0.2, 4.0, 3.0)])
+    for edge in tu.edge_blocks(kp):
+        got, _ = _reloc(ctx, mp, st, off, kp, f"(b) {edge['what']}", edge=edge, min_inliers=3)
+        assert got["rec"]["flags"][1] == ru.NOHYP and got["rec"]["n_kp"][2] == len(edge["rows"]) - edge["off"][2]
     mp.close()
 
 

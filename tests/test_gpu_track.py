@@ -56,9 +56,9 @@ def _call(ctx, kp, md, inl, reg, n_scans, max_landmarks=None, **kw):
     return got
 
 
-def _upload(w, max_scans, max_total, q_max_rows=None, stored=None, n_reg=None):
+def _upload(w, max_scans, max_total, q_max_rows=None, stored=None, n_reg=None, blk=None):
     import torch
-    blk = tu.block(w["off"], w["rows"], max_scans, max_total, stored)
+    blk = tu.block(w["off"], w["rows"], max_scans, max_total, stored) if blk is None else blk
     m, inl = tu.padded(w, q_max_rows)
     reg = np.zeros(max(len(w["reg"]), n_reg or 0, 1), capi.REG_DTYPE)
     reg.view(np.uint8)[:] = 0xA5  # (records beyond the block's links: never read)
@@ -67,15 +67,17 @@ def _upload(w, max_scans, max_total, q_max_rows=None, stored=None, n_reg=None):
             torch.from_numpy(inl.copy()).cuda(), torch.from_numpy(reg.view(np.float64).reshape(-1, 8).copy()).cuda())
 
 
-def _run(ctx, w, what, n_scans=None, q_max_rows=None, stored=None, max_scans=None, max_total=None, max_landmarks=None, **kw):
+def _run(ctx, w, what, n_scans=None, q_max_rows=None, stored=None, max_scans=None, max_total=None, max_landmarks=None, edge=None, **kw):
     """A case dict of track_util on the device (its block laid out for max_scans / max_total, storing `stored` rows), compared with
-    the reference."""
+    the reference.  edge: one of tu.edge_blocks(w["rows"]) in the place of the block (the per-row inputs stay w's)."""
     n_scans = w["n_scans"] if n_scans is None else n_scans
     max_scans = max(w["n_scans"], n_scans) + 2 if max_scans is None else max_scans
     max_total = len(w["rows"]) + 9 if max_total is None else max_total
-    kp, md, inl, reg = _upload(w, max_scans, max_total, q_max_rows, stored, n_scans - 1)
+    if edge:
+        max_scans, max_total, q_max_rows = edge["max_scans"], edge["max_total"], len(w["m"])
+    kp, md, inl, reg = _upload(w, max_scans, max_total, q_max_rows, stored, n_scans - 1, edge and edge["blk"])
     got = _call(ctx, kp, md, inl, reg, n_scans, max_landmarks, **kw)
-    ref = tu.reference(w, n_scans=n_scans, q_max_rows=q_max_rows, stored=stored, **kw)
+    ref = tu.reference(dict(w, off=edge["off"], rows=edge["rows"]) if edge else w, n_scans=n_scans, q_max_rows=q_max_rows, stored=stored, **kw)
     tu.assert_equal(got, ref, what, max_landmarks)
     n = ref["landmarks"]["n_obs"]
     print(f"{what}: {ref['header']}, longest track {int(n.max()) if len(n) else 0}")
@@ -143,6 +145,17 @@ def test_a_every_special_case_in_one_block(ctx):
     got, ref = _run(ctx, w, "(a) stored N - 2", stored=N - 2)
     assert ref["header"]["rows"] == N - 2
     _run(ctx, w, "(a) exact layout", max_scans=70, max_total=N)
+    # the edges only a hand-made block reaches: three scans of 2, 0 and 3 rows whose records all propose (none may be kept: the scan
+    # before is empty); with min_obs 1 every row that has a scan is a landmark of its own, so the scan of every row shows
+    h = tu.Hand(3)
+    first, last = [h.new(0) for _ in range(2)], [h.new(2) for _ in range(3)]
+    e = h.finish(np.random.default_rng(32))
+    for k, r in enumerate(last):
+        e["m"]["pair"][e["at"](r)], e["m"]["train_row"][e["at"](r)], e["inlier"][e["at"](r)] = 1, k % 2, 1
+    assert tuple(e["off"]) == tu.EDGE_OFF
+    for edge in tu.edge_blocks(e["rows"]):
+        got, ref = _run(ctx, e, f"(a) {edge['what']}", edge=edge, min_obs=1)
+        assert ref["header"]["scans"] == 3 and ref["header"]["rows"] == len(edge["rows"]) == ref["header"]["n_landmarks"]
 
 
 @pytest.mark.parametrize("rows", [ROWS_WG - 1, ROWS_WG, ROWS_WG + 1, 2 * SCAN_BLOCK + 1])

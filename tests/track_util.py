@@ -212,6 +212,25 @@ def block(off, rows, max_scans, max_total, stored=None):
     return blk.view(np.uint8).reshape(-1)
 
 
+EDGE_OFF = (0, 2, 2, 5)  # three scans, the one in the middle empty
+
+
+def edge_blocks(rows):
+    """The smallest block at the edges that block() cannot build, for every call that reads a block as a query (fx_track_landmarks,
+    fx_map_localize, fx_map_relocalize, fx_map_observe, fx_map_expect: one device definition, csrc/fx_scan_query.h, serves them all).
+    rows: [5, 4] float32, the rows of three scans at EDGE_OFF.  Yields dicts: what, blk (the block's bytes), max_scans, max_total (its
+    layout), and off, rows: what the call's numpy reference is given (the rows cut to min(stored, max_total))."""
+    rows = np.ascontiguousarray(rows, np.float32)
+    assert rows.shape == (5, 4)
+    blk = block(EDGE_OFF, rows, 3, 5)
+    blk.view(np.uint32)[0] = 4
+    yield dict(what="a header of 4 scans in a block of max_scans 3", blk=blk, max_scans=3, max_total=5, off=list(EDGE_OFF), rows=rows)
+    blk = block(EDGE_OFF, rows[:4], 3, 4)
+    blk.view(np.uint32)[1] = 5
+    yield dict(what="max_total 4 below the 5 rows stored", blk=blk, max_scans=3, max_total=4, off=list(EDGE_OFF), rows=rows[:4])
+    yield dict(what="kp_offset 0 3 2 5", blk=block((0, 3, 2, 5), rows, 3, 5), max_scans=3, max_total=5, off=[0, 3, 2, 5], rows=rows)
+
+
 # ---- the whole chain on rotated copies of a golden scan (tests/test_track_reference.py on the CPU, tests/test_gpu_track.py (f))
 def yaw_err(a, b):
     return abs((a - b + math.pi) % (2 * math.pi) - math.pi)
