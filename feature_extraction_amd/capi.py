@@ -30,13 +30,14 @@ FX_N_STAGES = 9
 STAGE_NAMES = ("k_prep", "k_bucket", "k_rings_runs", "k_rings_large", "k_merge", "k_gather", "k_desc_group", "k_desc_mid",
                "k_desc_rare")
 # stages that are one kernel launch (eligible as the roofline line's dominant kernel: their HIP-event span is that kernel)
-SINGLE_LAUNCH_STAGES = ("k_prep", "k_bucket", "k_rings_runs", "k_gather", "k_desc_group", "k_desc_mid")
+SINGLE_LAUNCH_STAGES = ("k_prep", "k_bucket", "k_rings_runs", "k_gather", "k_desc_group")
 # kernels launched inside each timed stage (rocprofv3 / PMC rows are per kernel name)
 STAGE_KERNELS = {"k_prep": ("k_prep", "k_front", "k_front_ab"),  # (k_front: stages 0-4 of scans that fit its LDS tables, in one launch)
                  "k_bucket": ("k_bucket", "k_bucket_many"),  # (k_bucket_many: sensors of more than 24 rings)
                  "k_rings_large": ("k_rings_runs2", "k_rings_large"),  # (k_rings_runs2: sensors of more than 16 rings)
                  "k_merge": ("k_merge_small", "k_merge_big", "k_merge_huge", "k_front_redo", "k_slow"),
-                 "k_desc_mid": ("k_desc_mid",),
+                 "k_desc_group": ("k_desc",),  # (every descriptor tier but the dense tier's own kernels, in one launch)
+                 "k_desc_mid": (),  # (the slot brackets nothing since k_desc took its rows)
                  "k_gather": ("k_gather", "k_rng_ord"),  # (k_rng_ord only when several workgroups share a scan: small batches)
                  "k_desc_rare": ("k_dense_sort", "k_dense_density", "k_dense_finish")}
 

@@ -67,8 +67,7 @@ hipError_t fxk_configure_front(void);
 uint32_t fxk_gather_slices(uint32_t batch);
 uint32_t fxk_gather(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, float box_margin, uint32_t counted);
 uint32_t fxk_gather_counted_max(void);
-void fxk_desc_group(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, uint32_t grid);
-void fxk_desc_mid(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, uint32_t cap, uint32_t n_wg, uint32_t n_wave,
+void fxk_desc(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, uint32_t cap, uint32_t n_wg, uint32_t n_wave, uint32_t n_group,
                   uint32_t n_dslow);
 void fxk_pack_kp_records(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, void *dst,
                          uint32_t rec_kp);
@@ -194,8 +193,8 @@ struct fx_ctx {
   int meta_next = 0;
   FxScanMeta *d_meta = nullptr;
   float box_margin = 0.f;
-  uint32_t desc_wgs_per_cu = 0;  // k_desc_group's workgroups a CU (0: by batches_in_flight; FX_DESC_WGS_PER_CU in the test build)
-  uint32_t desc_grid_abs = 0;      // test hook (FX_DESC_GRID): k_desc_group's grid, absolute
+  uint32_t desc_wgs_per_cu = 0;  // the group workgroups of k_desc's launch a CU (0: by batches_in_flight; FX_DESC_WGS_PER_CU in the test build)
+  uint32_t desc_grid_abs = 0;      // test hook (FX_DESC_GRID): the group workgroups of k_desc's launch, absolute
   uint32_t batches_in_flight = 1;  // fx_set_batches_in_flight: the caller's contexts busy on this device at a time
   uint32_t ring_lds_cap = 0;     // points a ring may have in the workgroup ring tier's LDS (<= max_ring_points; beyond: k_slow)
   uint32_t merge_big_cap = 0;    // candidates the LDS merge tier holds as points (<= max_candidates)
@@ -256,14 +255,14 @@ struct fx_ctx {
   uint32_t fail_after = 0;     // test hook (FX_FAIL_AFTER_ENQUEUE = n: the n-th batch returns an error after its kernels were enqueued)
   uint32_t front_pause = 0;    // batches left on the separate kernels
   // The dense descriptor tier: its own kernels (k_dense_sort, k_dense_density, k_dense_finish) when a recent batch had rows for it (or nothing is known), else a handful of
-  // workgroups in k_desc_mid's launch (dense_slow_loop) that compute whatever does turn up, slower — the same results either way.
+  // workgroups in k_desc's launch (dense_slow_loop) that compute whatever does turn up, slower — the same results either way.
   uint32_t dense_fast_left = 0;            // batches that still get the tier's kernels after the last one that needed them
   static constexpr uint32_t dense_linger = 64;
   int gather_slices = -1;                  // test hook (FX_GATHER_COUNTED): workgroups a scan in the support gather's counted slices (1: one workgroup a scan)
   int merge_slices = -1;                   // test hook (FX_MERGE_SLICES): workgroups a scan in the large merge tier's pair loop (1: the one launch)
   int prep_slices = -1;                    // test hook (FX_PREP_SLICES): workgroups a scan in the separate kernels' streaming pass and ring split
-  int dense_force = -1;                    // test hook (FX_DENSE_SLOW): 1 always k_desc_mid's workgroups, 0 always the tier's own kernels
-  uint32_t skip_mask = 0;      // experiment hook (FX_SKIP_EMPTY, test build): bit 0 no k_front_redo, bit 1 no dense tier — only for workloads that need neither; bits 2 / 3: no k_dense_finish / k_dense_density (measurement: results wrong)
+  int dense_force = -1;                    // test hook (FX_DENSE_SLOW): 1 always k_desc's stand-in workgroups, 0 always the tier's own kernels
+  uint32_t skip_mask = 0;      // experiment hook (FX_SKIP_EMPTY, test build): bit 0 no k_front_redo, bit 1 no dense tier — only for workloads that need neither (a dense row that does turn up is then neither computed NOR CLEARED: every tier clears its own rows, so such a row keeps what the last batch left in it); bits 2 / 3: no k_dense_finish / k_dense_density (measurement: results wrong)
   static constexpr uint32_t front_retry = 64;
   // FX_OUT_DESC_CSR: the context's CSR block of descriptor rows (max_total_keypoints rows, csr_cap entries) and its pinned
   // mirror, allocated at the first batch that asks for it and grown (never shrunk) when a batch needs more entries
@@ -507,7 +506,7 @@ fx_status enqueue_stages(fx_ctx *c, hipStream_t s, uint32_t batch, bool prof, bo
   if (!batch) FX_HIP(hipMemsetAsync(B.counters, 0, FX_N_COUNTERS * sizeof(uint32_t), s));  // (k_prep clears them otherwise)
   if (batch) {
     const uint32_t merge_small = L.max_candidates < kMergeCapSmall ? L.max_candidates : kMergeCapSmall;
-    // k_desc_group strides over the rows: ten workgroups a CU (resident all at once, 32 KB of LDS each) when the batch has the
+    // k_desc's group workgroups stride over the rows: ten a CU when the batch has the
     // chip to itself; with batches in flight fewer, longer-lived ones (measured, 1 / 2 / 3 / 4 batches in flight, scans/s with
     // 10 against 1 a CU: 1.64 / 1.47, 2.11 / 2.04, 2.25 / 2.27 — 2.29 with 3 —, 2.32 / 2.38e6: profiles/r05_experiments.md)
     const uint32_t desc_per_cu = c->desc_wgs_per_cu ? c->desc_wgs_per_cu : (c->batches_in_flight >= 4u ? 1u : (c->batches_in_flight == 3u ? 3u : 10u));
@@ -624,19 +623,20 @@ fx_status enqueue_stages(fx_ctx *c, hipStream_t s, uint32_t batch, bool prof, bo
         counted = 3u * big_grid / (batch * c->batches_in_flight);
       if (fxk_gather(s, P, B, batch, c->box_margin, counted) > 1) fxk_rng_ord(s, P, B, batch);  // (one workgroup per scan settles the RNG ordinals itself)
       FX_HIP(mark(6));
-      fxk_desc_group(s, P, B, batch, desc_grid);
-      FX_HIP(mark(7));
       // The dense tier (larger support sets and overflowed lists; nothing on sparse scans): its own three kernels, or a handful of
-      // workgroups of k_desc_mid's launch — the previous batches decide speed, never results.
-      // (beside k_desc_mid on a second stream of the context: measured and dropped, profiles/r04_front_experiments.md)
+      // workgroups of k_desc's launch — the previous batches decide speed, never results.
+      // (beside k_desc_mid, as it then was, on a second stream of the context: measured and dropped, profiles/r04_front_experiments.md)
       bool fast = capture || hint[4] != 0u;  // (0xffffffff: nothing known yet)
       if (fast && !capture && hint[4] != 0xffffffffu) c->dense_fast_left = fx_ctx::dense_linger;
       if (!fast && c->dense_fast_left) --c->dense_fast_left, fast = true;
       if (c->dense_force >= 0) fast = c->dense_force == 0;
       const bool skip_dense = (c->skip_mask & 2u) != 0u;
-      // wave rows and list rows (lists of up to dense_min entries, four keypoints per CU in flight) share a launch
-      fxk_desc_mid(s, P, B, batch, P.list_cap < P.dense_min ? P.list_cap : P.dense_min, std::max(1u, std::min(big_grid * 4, rows_bound)),
-                   std::max(1u, std::min(big_grid * 4, (rows_bound + 3u) / 4u)), fast || skip_dense ? 0u : (c->tier_min_grid ? c->tier_min_grid : 8u));
+      // every tier in ONE launch, timed in the group tier's slot (the next slot brackets nothing): list rows (lists of up to
+      // dense_min entries, four keypoints per CU in flight), wave rows, the group rows' striding workgroups, the dense stand-in —
+      // the gather has classified every row, so no tier waits for another (k_desc)
+      fxk_desc(s, P, B, batch, P.list_cap < P.dense_min ? P.list_cap : P.dense_min, std::max(1u, std::min(big_grid * 4, rows_bound)),
+               std::max(1u, std::min(big_grid * 4, (rows_bound + 3u) / 4u)), desc_grid, fast || skip_dense ? 0u : (c->tier_min_grid ? c->tier_min_grid : 8u));
+      FX_HIP(mark(7));
       FX_HIP(mark(8));
       if (fast && !skip_dense) {
         const uint32_t max_rows = batch * L.max_keypoints < L.max_total_keypoints ? batch * L.max_keypoints : L.max_total_keypoints;
@@ -1015,7 +1015,8 @@ fx_status fx_create(const fx_params *params, const fx_limits *limits, int device
   FX_A(dev_alloc(c, &b.desc, (size_t)L.max_total_keypoints * FX_DESC_FLOATS + 4));
   FX_A(dev_alloc(c, &b.desc_nbins, (size_t)L.max_total_keypoints));
   FX_A(dev_alloc(c, &b.desc_bins, (size_t)L.max_total_keypoints * fxk_group_cap()));
-  // rows start out zero with nothing recorded in them: k_desc_group then clears a row by un-writing what it wrote last time
+  FX_A(dev_alloc(c, &b.row_class, (size_t)L.max_total_keypoints));  // (written for every row of a batch before it is read)
+  // rows start out zero with nothing recorded in them: a row's owner then clears it by un-writing what was recorded last time
   if (hipMemset(b.desc, 0, ((size_t)L.max_total_keypoints * FX_DESC_FLOATS + 4) * sizeof(float)) != hipSuccess ||
       hipMemset(b.desc_nbins, 0, (size_t)L.max_total_keypoints * sizeof(uint32_t)) != hipSuccess)
     return bail(fail(FX_ERR_HIP, "hipMemset"));
@@ -1335,8 +1336,8 @@ fx_status fx_get_stage_bytes(fx_ctx *c, fx_stage_bytes *out) {
   }
   if (desc) {
     rd[5] = 16.0 * near_pts + 16.0 * nk, wr[5] = 16.0 * (s_small + s_mid + s_dense) + 40.0 * nk;  // k_gather: near sectors; support lists + row tables
-    rd[6] = 16.0 * s_small + 44.0 * total_kp, wr[6] = 7956.0 * total_kp;       // k_desc_group: short lists; every row (cleared here)
-    rd[7] = 16.0 * s_mid, wr[7] = 0.0 * rows_mid;                               // k_desc_mid: lists; (non-empty bins of rows already counted)
+    rd[6] = 16.0 * s_small + 44.0 * total_kp, wr[6] = 7956.0 * total_kp;       // k_desc (timed in the k_desc_group slot), group tier: short lists; every row (cleared by its tier)
+    rd[7] = 16.0 * s_mid, wr[7] = 0.0 * rows_mid;                               // k_desc, wave and list tiers (the k_desc_mid slot of the accounting): lists; (non-empty bins of rows already counted)
     rd[8] = 16.0 * s_dense, wr[8] = 0.0 * rows_dense;                           // dense tier: lists
   }
   return FX_OK;

@@ -67,6 +67,12 @@ struct FxScTables {
 #define FX_ATAN_N 64      // table step of k_prep's arctangent: 1 / 64 over [0, 1]
 #define FX_ATAN_DEG 6     // degree of the expansion about a table point (|offset| <= 1 / 128: truncation below 2^-51)
 #define FX_ROW_DIRTY 0xffffffffu
+// FxBuffers::row_class: which workgroups of k_desc own a row — clear it, compute it, record what they left in it
+#define FX_ROW_GROUP 0u       // support sets of up to FX_GROUP_CAP points
+#define FX_ROW_WAVE 1u        // up to FX_WAVE_CAP
+#define FX_ROW_LIST 2u        // up to dense_min
+#define FX_ROW_DENSE 3u       // beyond that, and every overflowed list: the dense tier (its own kernels or k_desc's stand-in workgroups)
+#define FX_ROW_DENSE_FAIL 4u  // a dense row the pools have no room for: flagged, NaN-filled by the group workgroups
 // CSR block of descriptor rows (include/fx.h fx_descriptor_csr_bytes): words of row_ptr[max_rows + 1] and of col / val[cap],
 // each rounded up to 16 bytes; header 16 B, then row_ptr, col, val
 __host__ __device__ inline size_t csr_rp_words(uint32_t max_rows) { return ((size_t)max_rows + 1u + 3u) & ~(size_t)3; }
@@ -537,10 +543,11 @@ struct FxBuffers {
   // stage 5
   float *desc;            // [max_total_kp][1989]
   // What the previous batches left in each descriptor row (rows outlive a batch: the buffer is zeroed when the context is
-  // made, and a row is cleared by un-writing what was written to it): the number of non-zero bins k_desc_group wrote, or
+  // made, and a row is cleared by un-writing what was written to it): the number of non-zero bins a group workgroup of k_desc wrote, or
   // FX_ROW_DIRTY when another tier (or a NaN fill) wrote the row — such a row is cleared whole.
   uint32_t *desc_nbins;   // [max_total_kp]
   uint16_t *desc_bins;    // [max_total_kp][FX_GROUP_CAP]: those bins
+  uint8_t *row_class;     // [max_total_kp]  FX_ROW_*: the tier that computes the row in this batch (the support gather classifies every row)
   uint32_t *flags;        // [B]
   // work lists for the large-capacity tiers
   uint32_t *huge_rings;   // [B*n_rings]  rings for the workgroup tier (k_rings_large), by XCD class
@@ -585,7 +592,7 @@ struct FxBuffers {
   float2 *row_xa;         //                 per-keypoint kernels fetch everything a row needs in one round trip
   unsigned long long *clk;     // [FX_CLK_SLOTS][2] k_prep's first start / last end on the device's constant-rate clock, by batch
   unsigned long long *stamps;  // [32] diagnostic build only (-DFX_STAMPS)
-  uint32_t *tier_hint;    // [FX_N_HINTS], pinned HOST memory: the batch's counts of work for the rarely used tiers, which the host sizes the next batch's launches of those tiers by (k_offsets, k_desc_mid write them; grid sizes only — never what is computed)
+  uint32_t *tier_hint;    // [FX_N_HINTS], pinned HOST memory: the batch's counts of work for the rarely used tiers, which the host sizes the next batch's launches of those tiers by (k_offsets, k_desc write them; grid sizes only — never what is computed)
   uint32_t *counters;     // [FX_N_COUNTER_WORDS]: 16.. / 24.. rings handed on per XCD class; 1 big_merge, 4 list_desc, 6 dense rows (2 / 3 / 7 / 10: by size class), 8 wave_desc, 9 huge_merge, 12 key pool used, 13 sorted pool used, 14 density items, 15 / 11 / 5 / 0 tickets of k_dense_density / sort / finish_s / finish_l
 };
 

@@ -4116,10 +4116,10 @@ __device__ __forceinline__ void offsets_body(const FxDevParams &P, const FxBuffe
 //   k_gather        one pass over each scan tests every (rotated) point against the keypoints of the
 //                   scan (binned along x) and appends the points within R + R/5 of a keypoint to that
 //                   keypoint's support list (a superset of the neighbour query and of every density query);
-//                   (the rows themselves are cleared by k_desc_group, which sees every row once)
-//   k_desc_group    4 keypoints per wavefront: support sets of <= 64 points (the bulk)
-//   k_desc_mid      one launch: one wavefront per keypoint (65..192 support points: FX_WAVE_CAP) and one 256-thread
-//                   workgroup per keypoint (lists of up to 1024 entries)
+//                   and, the support counts being final at its end, sends every row to its tier's work list (classify_rows);
+//   k_desc          every tier in one launch, a kind of workgroup each: 4 keypoints per wavefront (support sets of <= 64 points:
+//                   the bulk), one wavefront per keypoint (65..192 support points: FX_WAVE_CAP), one 256-thread workgroup per
+//                   keypoint (lists of up to 1024 entries); every tier clears the rows it computes (desc_clear_row)
 //                   -- all three: bins + density + weight per neighbour, sort by (bin, d2, index) ==
 //                      PCL's accumulation order, sequential fp32 sum per bin; angles in fp32, exact next to a bin edge --
 //   k_dense_*       larger support sets (dense many-ring scans) and overflowed lists: cell-sorted support sets in HBM
@@ -4248,6 +4248,76 @@ __device__ __forceinline__ bool sc3d_is_origin(float d2) { return fabsf(d2 - 0.0
 #endif
 __device__ __forceinline__ unsigned long long sc3d_key(uint32_t bin, float d2, uint32_t idx) {
   return ((unsigned long long)bin << 52) | ((unsigned long long)__float_as_uint(d2) << 20) | (unsigned long long)idx;
+}
+
+// ---------------------------------------------------------------- row classes
+// Which tier computes a row follows from its support count alone, and the counts are final when the support gather ends: the
+// gather classifies (its own tail when one workgroup has the scan to itself, k_rng_ord otherwise), so that every work list is
+// complete before k_desc — all tiers in one launch — starts, and no workgroup of that launch waits for another.
+// (the tiers' capacities are defined here, once: the classification needs them ahead of the tiers themselves)
+#ifndef FX_GROUP_CAP
+#define FX_GROUP_CAP 64   // support points a group row holds (the group tier: FX_GLANES lanes a row, four slots a lane)
+#endif
+#ifndef FX_WAVE_CAP
+#define FX_WAVE_CAP 192  // support points a wave row holds (multiples of 64; measured 128 / 192 / 256 / 320: the wave and list tiers' launch 0.118 / 0.099 / 0.119 / 0.153 ms)
+#endif
+// One row a lane (has: this lane holds one), called by whole wavefronts: too long for a group -> wavefront rows (<= FX_WAVE_CAP
+// support points), list rows (<= dense_min), and the dense tier beyond that — also every row whose list overflowed its list_cap
+// slots (the rest of it sits in the scan's overflow region).  The rows of a wavefront draw their list positions together: one
+// atomic per list and wavefront instead of one (dense rows: three) per row — on config 3 half of the 40 000 rows of a batch are
+// handed on, and their atomics, all on two cache lines of counters, went through the L2 one after the other.
+// (kp_nbrs of a row without room in the pools is set by the group workgroup that fills the row with NaN: here the word may still
+//  hold the has-a-neighbour flag the RNG ordinals are counted from.)
+__device__ __forceinline__ void classify_rows(const FxDevParams &P, const FxBuffers &B, bool has, uint32_t row, uint32_t scan, uint32_t nS) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const bool too_long = has && (nS > FX_GROUP_CAP || nS > P.list_cap);
+  const bool to_dense = too_long && (nS > P.dense_min || nS > P.list_cap);
+  const bool to_list = too_long && !to_dense && nS > FX_WAVE_CAP, to_wave = too_long && !to_dense && !to_list;
+  // positions [base, base + n) of counter c for the lanes of m (wave-uniform call); returns this lane's
+  auto draw = [&](unsigned long long m, bool mine, uint32_t c, uint32_t amount, uint32_t before) -> uint32_t {
+    if (!m) return 0u;
+    const uint32_t first = (uint32_t)__ffsll((long long)m) - 1u;
+    uint32_t b0 = 0;
+    if (lane == first) b0 = atomicAdd(&B.counters[c], amount);
+    b0 = (uint32_t)__shfl((int)b0, (int)first, 64);
+    return mine ? b0 + before : 0u;
+  };
+  const unsigned long long m_list = __ballot(to_list), m_wave = __ballot(to_wave), m_dense = __ballot(to_dense);
+  const uint32_t p_list = draw(m_list, to_list, 4u, (uint32_t)__popcll(m_list), lanes_below(m_list));
+  const uint32_t p_wave = draw(m_wave, to_wave, 8u, (uint32_t)__popcll(m_wave), lanes_below(m_wave));
+  if (to_list) B.list_desc[p_list] = row;
+  if (to_wave) B.wave_desc[p_wave] = row;
+  uint32_t cls_row = to_list ? FX_ROW_LIST : (to_wave ? FX_ROW_WAVE : (to_dense ? FX_ROW_DENSE : FX_ROW_GROUP));
+  if (m_dense) {  // (wave-uniform)
+    // a slot in the dense-row list and nS entries of the sorted pool (k_dense_sort fills them)
+    const uint32_t mine = to_dense ? nS : 0u, incl = wave_incl_scan(mine);
+    const uint32_t tot = (uint32_t)__shfl((int)incl, 63, 64);
+    const uint32_t slot = draw(m_dense, to_dense, 6u, (uint32_t)__popcll(m_dense), lanes_below(m_dense));
+    const uint32_t off = draw(m_dense, to_dense, 13u, tot, incl - mine);
+    // the tier's kernels take the rows largest first (four size classes), so that the big ones do not end up alone at the tail
+    const uint32_t cls = dense_class(nS);
+    uint32_t p_cls = 0;
+#pragma unroll
+    for (uint32_t c2 = 0; c2 < 4u; ++c2) {
+      const bool in = to_dense && slot < P.max_dense_rows && cls == c2;  // (a row without a slot is in no class list)
+      const unsigned long long m_c = __ballot(in);
+      const uint32_t v = draw(m_c, in, dense_class_counter(c2), (uint32_t)__popcll(m_c), lanes_below(m_c));
+      p_cls = in ? v : p_cls;
+    }
+    if (to_dense) {
+      const bool ok = slot < P.max_dense_rows && off <= P.dense_cap && nS <= P.dense_cap - off;
+      if (slot < P.max_dense_rows) {
+        B.dense_rows[slot] = ok ? row : FX_NONE;
+        B.dense_off[slot] = off;
+        B.dense_order[cls * P.max_dense_rows + p_cls] = slot;
+      }
+      if (!ok) {  // pools exhausted (limits.max_dense_points): flagged, never silent
+        atomicOr(&B.flags[scan], FX_FLAG_NBR_OVERFLOW);
+        cls_row = FX_ROW_DENSE_FAIL;
+      }
+    }
+  }
+  if (has) B.row_class[row] = (uint8_t)cls_row;
 }
 
 // ---------------------------------------------------------------- k_gather
@@ -4610,6 +4680,11 @@ __device__ __forceinline__ void gather_body(const FxDevParams &P, const FxBuffer
   }
   if (solo) {
     for (uint32_t k = tid; k < K; k += NT) B.s_cnt[row0 + k] = s_kpos[k];
+    // the counts are final: every row to its tier's work list (a row a lane, whole wavefronts: see classify_rows)
+    for (uint32_t k0 = wave * 64u; k0 < K; k0 += NT) {
+      const uint32_t k = k0 + lane;
+      classify_rows(P, B, k < K, row0 + k, scan, k < K ? s_kpos[k] : 0u);
+    }
     // RNG ordinals: keypoint k takes the x-axis number (keypoints before it that have a neighbour)
     __syncthreads();
     if (wave == 0 && !passes) {
@@ -4662,11 +4737,8 @@ extern "C" __global__ __launch_bounds__(FX_GATHER_WIDE_T) void k_gather_passes(F
   gather_body<FX_GATHER_WIDE_T, true>(P, B, box_margin, smem);
 }
 
-// ---------------------------------------------------------------- wavefront tier (runs inside k_desc_mid)
-#ifndef FX_WAVE_CAP
-#define FX_WAVE_CAP 192  // support points a wave row holds (multiples of 64; measured 128 / 192 / 256 / 320: k_desc_mid 0.118 / 0.099 / 0.119 / 0.153 ms)
-#endif
-#define FX_WAVE_WORDS (FX_WAVE_CAP * 8)
+// ---------------------------------------------------------------- wavefront tier (runs inside k_desc)
+#define FX_WAVE_WORDS (FX_WAVE_CAP * 8)  // (FX_WAVE_CAP: defined with the row classes, above)
 // Clears one descriptor row (1989 floats, 4-byte aligned) with `stride` lanes: 16-byte stores over its aligned body.
 __device__ __forceinline__ void desc_zero_row(float *out, uint32_t lane, uint32_t stride) {
   const uint32_t head = (uint32_t)((16u - ((uintptr_t)out & 15u)) & 15u) / 4u;  // floats before the first 16-byte boundary
@@ -4678,6 +4750,20 @@ __device__ __forceinline__ void desc_zero_row(float *out, uint32_t lane, uint32_
 }
 __device__ __forceinline__ void desc_fill_nan(float *out, uint32_t lane, uint32_t stride) {
   for (uint32_t t = lane; t < FX_DESC_FLOATS; t += stride) out[t] = t < FX_DESC_BINS ? NAN : 0.0f;
+}
+// A row is cleared exactly once a batch, by the workgroup or wavefront that then computes it, before its first store to the
+// row: nb_prev = desc_nbins[row] is what the last batch left — up to FX_GROUP_CAP bins recorded in desc_bins,
+// which are un-written (some tens of 4-byte stores instead of 7956 bytes), or FX_ROW_DIRTY, and the row is zeroed whole.
+// `stride` (>= 4) lanes.  The caller puts a release fence (workgroup scope: the stores are acknowledged) between this and
+// its own stores to the row, and records what it leaves behind in desc_nbins.
+__device__ __forceinline__ void desc_clear_row(const FxBuffers &B, uint32_t row, uint32_t nb_prev, uint32_t lane, uint32_t stride) {
+  float *out = B.desc + (size_t)row * FX_DESC_FLOATS;
+  if (nb_prev > FX_GROUP_CAP) {
+    desc_zero_row(out, lane, stride);
+  } else {
+    const uint16_t *bins = B.desc_bins + (size_t)row * FX_GROUP_CAP;
+    for (uint32_t t = lane; t < nb_prev; t += stride) out[bins[t]] = 0.0f;
+  }
 }
 
 // The 3DSC edge tables and weight table (206 floats) are copied to LDS once per workgroup: the bin
@@ -4726,8 +4812,12 @@ __device__ __forceinline__ void desc_wave_body(const FxDevParams &P, const FxBuf
 #pragma unroll
     for (uint32_t u = 0; u < FX_WAVE_CAP / 64; ++u)
       if (lane + u * 64 < P.list_cap) lv[u] = B.s_pts[(size_t)row * P.list_cap + lane + u * 64];
-    if (nS > FX_WAVE_CAP || nS > P.list_cap) continue;  // (never listed here: k_desc_group sends those rows to their tiers)
+    const uint32_t nb_prev = B.desc_nbins[row];
+    if (nS > FX_WAVE_CAP || nS > P.list_cap) continue;  // (never listed here: classify_rows sends those rows to their tiers)
     float *out = B.desc + (size_t)row * FX_DESC_FLOATS;
+    // the row is this wavefront's in this batch: cleared here, before anything is written to it, and left dirty
+    desc_clear_row(B, row, nb_prev, lane, 64u);
+    if (lane == 0) B.desc_nbins[row] = FX_ROW_DIRTY;
     __builtin_amdgcn_wave_barrier();
     // The support set is staged with its neighbours (d2 < R^2) in front, [0, nAll), and the rest — the shell out to the
     // support radius, 30-55 % of a set, which only the density counts read — filled in from the back: the pass below then
@@ -4783,11 +4873,13 @@ __device__ __forceinline__ void desc_wave_body(const FxDevParams &P, const FxBuf
       nM += (uint32_t)__popcll(um);
     }
     if (lane == 0) B.kp_nbrs[(size_t)scan * P.max_keypoints + k] = nAll;
+    // (s_waitcnt vmcnt(0): the clearing stores are acknowledged before anything else is written to the row)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     if (nAll == 0) {  // no neighbours: NaN descriptor, no RNG draw (A.8-3)
       desc_fill_nan(out, lane, 64);
       continue;
     }
-    // the output rows were cleared by k_desc_group; only the non-empty bins are written here.
+    // the row was cleared at the top of this trip; only the non-empty bins are written here.
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -4823,19 +4915,17 @@ __device__ __forceinline__ void desc_wave_body(const FxDevParams &P, const FxBuf
   }
 }
 
-// ---------------------------------------------------------------- k_desc_group
+// ---------------------------------------------------------------- group tier (runs inside k_desc)
 // Most keypoints have a small support set (median < 10 points on the VLP-16 scenes, 90 % < 64):
 // a whole wavefront per keypoint leaves its lanes idle and pays the per-keypoint latency 64-wide.
 // Here a wavefront works on FX_GROUPS keypoints at once, FX_GLANES lanes each (fp32 angles, same
-// exactness contract as the wavefront tier).  Rows with more than FX_GROUP_CAP support points go to the
-// wave list, rows with an angle near a bin edge to the exact list.
+// exactness contract as the wavefront tier).  Rows with more than FX_GROUP_CAP support points are the other tiers'
+// (classify_rows): the workgroups here stride over all rows and skip those.
 #ifndef FX_GLANES
 #define FX_GLANES 16
 #endif
 #define FX_GROUPS (64 / FX_GLANES)
-#ifndef FX_GROUP_CAP
-#define FX_GROUP_CAP 64
-#endif
+// (FX_GROUP_CAP: defined with the row classes, above)
 #define FX_GROUP_WORDS (FX_GROUP_CAP * 8 + 8)  // per group: support float4, keys, weights, indices + 8 counters
 #ifndef FX_GROUP_UNROLL
 #define FX_GROUP_UNROLL 8
@@ -4843,8 +4933,9 @@ __device__ __forceinline__ void desc_wave_body(const FxDevParams &P, const FxBuf
 #ifndef FX_GROUP_OCC
 #define FX_GROUP_OCC 4
 #endif
-extern "C" __global__ __launch_bounds__(FX_WG, FX_GROUP_OCC) void k_desc_group(FxDevParams P, FxBuffers B, uint32_t batch) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+// (workgroup bid of the nblk of k_desc's launch that stride over all rows and take the group rows among them)
+__device__ __forceinline__ void desc_group_body(const FxDevParams &P, const FxBuffers &B, uint32_t batch, uint32_t *smem, uint32_t bid,
+                                                uint32_t nblk) {
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const uint32_t gl = lane % FX_GLANES, g = lane / FX_GLANES;
   const WithinR2 within(P.r2_density);
@@ -4860,23 +4951,25 @@ extern "C" __global__ __launch_bounds__(FX_WG, FX_GROUP_OCC) void k_desc_group(F
 
   uint32_t total = B.kp_offset[batch];
   if (total > P.max_total_kp) total = P.max_total_kp;
-  const uint32_t stride = gridDim.x * FX_NWAVE * FX_GROUPS;
-  // Everything a row needs is fetched in one round trip — keypoint, x-axis, the list entries before the list length is known
-  // (slots past the length hold stale data and are ignored), and what the row holds from last time (its bin count and all 64
+  const uint32_t stride = nblk * FX_NWAVE * FX_GROUPS;
+  // Everything a row needs is fetched in one round trip — its class, keypoint, x-axis, the list entries before the list length is
+  // known (slots past the length hold stale data and are ignored), and what the row holds from last time (its bin count and all 64
   // slots of its bin list, four per lane) — and a TRIP AHEAD: the next trip's loads go out before this trip's last step (few
   // registers are live there) and are taken at the top of the next trip.  (With one workgroup a CU a wavefront has a SIMD to
   // itself, and every trip began with that round trip.)
   static_assert(FX_GROUP_CAP == 4 * FX_GLANES, "a lane fetches four slots of the row's bin list");
   uint2 f_rm = make_uint2(0u, 0u), f_pb = make_uint2(0u, 0u);
-  uint32_t f_nS = 0, f_nb = 0;
+  uint32_t f_nS = 0, f_nb = 0, f_cls = FX_ROW_GROUP;
   float4 f_kp = make_float4(0, 0, 0, 0), f_lv[FX_GROUP_CAP / FX_GLANES];
   float2 f_xa = make_float2(1.f, 0.f);
   auto fetch = [&](uint32_t row) {
     // (every value is defined anew on both paths: nothing of the previous fetch stays live across a trip)
     f_rm = make_uint2(0u, 0u), f_pb = make_uint2(0u, 0u), f_nS = 0, f_nb = 0, f_kp = make_float4(0, 0, 0, 0), f_xa = make_float2(1.f, 0.f);
+    f_cls = FX_ROW_GROUP;
 #pragma unroll
     for (uint32_t u = 0; u < FX_GROUP_CAP / FX_GLANES; ++u) f_lv[u] = make_float4(0, 0, 0, 0);
     if (row < total) {
+      f_cls = B.row_class[row];
       f_rm = B.row_map[row];
       f_nS = B.s_cnt[row];
       f_kp = B.row_kp[row];
@@ -4888,11 +4981,15 @@ extern "C" __global__ __launch_bounds__(FX_WG, FX_GROUP_OCC) void k_desc_group(F
       f_pb = *reinterpret_cast<const uint2 *>(B.desc_bins + (size_t)row * FX_GROUP_CAP + 4u * gl);
     }
   };
-  fetch((blockIdx.x * FX_NWAVE + wave) * FX_GROUPS + g);
+  fetch((bid * FX_NWAVE + wave) * FX_GROUPS + g);
   // all groups of a wavefront make the same number of trips (wave-level fences inside)
-  for (uint32_t r0 = (blockIdx.x * FX_NWAVE + wave) * FX_GROUPS; r0 < total; r0 += stride) {
+  for (uint32_t r0 = (bid * FX_NWAVE + wave) * FX_GROUPS; r0 < total; r0 += stride) {
     const uint32_t row = r0 + g;
-    bool live = row < total;
+    // rows of the other tiers are theirs alone — not read, not cleared, not written here — but for a dense row the pools had no
+    // room for (classify_rows): cleared, filled with NaN and left dirty below
+    const uint32_t cls = f_cls;
+    const bool dense_fail = row < total && cls == FX_ROW_DENSE_FAIL;
+    bool live = row < total && (cls == FX_ROW_GROUP || dense_fail);
     uint32_t scan = 0, k = 0, nS = 0;
     float4 kp = make_float4(0, 0, 0, 0);
     float2 xa = make_float2(1.f, 0.f);
@@ -4905,12 +5002,11 @@ extern "C" __global__ __launch_bounds__(FX_WG, FX_GROUP_OCC) void k_desc_group(F
       for (uint32_t u = 0; u < FX_GROUP_CAP / FX_GLANES; ++u) lv[u] = f_lv[u];
     }
     float *out = B.desc + (size_t)row * FX_DESC_FLOATS;
-    // Every descriptor row is cleared here, whichever tier ends up computing it (the keypoint kernels write
-    // non-empty bins only): this kernel sees every row once and waits on latencies with its memory pipe idle.
-    // A row this kernel itself filled last time — nine in ten — is cleared by zeroing the bins it wrote then (recorded in
-    // desc_bins): some tens of 4-byte stores instead of 7956 bytes.  (The descriptor rows are half of the batch's
-    // algorithmic bytes and all of them writes; the dirty lines they leave in L2 / MALL are written back under the next
-    // kernels — k_prep ran 0.17 ms behind a batch's row clears and 0.13 ms without.)
+    // The row is cleared here, before anything is written to it (every tier clears its own rows: desc_clear_row, whose work
+    // this is with the recorded bins already fetched).  A row a group filled last time — nine in ten — is cleared by zeroing
+    // the bins written then (recorded in desc_bins): some tens of 4-byte stores instead of 7956 bytes.  (The descriptor rows
+    // are half of the batch's algorithmic bytes and all of them writes; the dirty lines they leave in L2 / MALL are written
+    // back under the next kernels — k_prep ran 0.17 ms behind a batch's row clears and 0.13 ms without.)
     uint16_t *my_bins = B.desc_bins + (size_t)row * FX_GROUP_CAP;
     if (live) {
       if (nb_prev > FX_GROUP_CAP) {
@@ -4923,74 +5019,15 @@ extern "C" __global__ __launch_bounds__(FX_WG, FX_GROUP_OCC) void k_desc_group(F
         if (t0 + 3u < nb_prev) out[pb.y >> 16] = 0.0f;
       }
     }
-    // too long for a group: wavefront rows (<= FX_WAVE_CAP support points), list rows (<= dense_min), and the dense tier beyond
-    // that — also every row whose list overflowed its list_cap slots (the rest of it sits in the scan's overflow region)
-    const bool too_long = live && (nS > FX_GROUP_CAP || nS > P.list_cap);
-    uint32_t dense_fail = 0;
-    {
-      // The rows a wavefront hands on draw their list positions together: one atomic per list and wavefront instead of one
-      // (dense rows: three) per row — on config 3 half of the 40 000 rows of a batch are handed on, and their atomics, all on
-      // two cache lines of counters, went through the L2 one after the other.
-      const bool lead = too_long && gl == 0;
-      const bool to_dense = lead && (nS > P.dense_min || nS > P.list_cap);
-      const bool to_list = lead && !to_dense && nS > FX_WAVE_CAP, to_wave = lead && !to_dense && !to_list;
-      // positions [base, base + n) of counter c for the lanes of m (wave-uniform call); returns this lane's
-      auto draw = [&](unsigned long long m, bool mine, uint32_t c, uint32_t amount, uint32_t before) -> uint32_t {
-        if (!m) return 0u;
-        const uint32_t first = (uint32_t)__ffsll((long long)m) - 1u;
-        uint32_t b0 = 0;
-        if (lane == first) b0 = atomicAdd(&B.counters[c], amount);
-        b0 = (uint32_t)__shfl((int)b0, (int)first, 64);
-        return mine ? b0 + before : 0u;
-      };
-      const unsigned long long m_list = __ballot(to_list), m_wave = __ballot(to_wave), m_dense = __ballot(to_dense);
-      const uint32_t p_list = draw(m_list, to_list, 4u, (uint32_t)__popcll(m_list), lanes_below(m_list));
-      const uint32_t p_wave = draw(m_wave, to_wave, 8u, (uint32_t)__popcll(m_wave), lanes_below(m_wave));
-      if (to_list) B.list_desc[p_list] = row;
-      if (to_wave) B.wave_desc[p_wave] = row;
-      if (m_dense) {  // (wave-uniform)
-        // a slot in the dense-row list and nS entries of the sorted pool (k_dense_sort fills them)
-        uint32_t pre = 0, tot = 0;
-#pragma unroll
-        for (uint32_t g2 = 0; g2 < FX_GROUPS; ++g2) {
-          const uint32_t v = (uint32_t)__shfl((int)(to_dense ? nS : 0u), (int)(g2 * FX_GLANES), 64);
-          pre += g2 < g ? v : 0u;
-          tot += v;
-        }
-        const uint32_t slot = draw(m_dense, to_dense, 6u, (uint32_t)__popcll(m_dense), lanes_below(m_dense));
-        const uint32_t off = draw(m_dense, to_dense, 13u, tot, pre);
-        // the tier's kernels take the rows largest first (four size classes), so that the big ones do not end up alone at the tail
-        const uint32_t cls = dense_class(nS);
-        uint32_t p_cls = 0;
-#pragma unroll
-        for (uint32_t c2 = 0; c2 < 4u; ++c2) {
-          const bool in = to_dense && slot < P.max_dense_rows && cls == c2;  // (a row without a slot is in no class list)
-          const unsigned long long m_c = __ballot(in);
-          const uint32_t v = draw(m_c, in, dense_class_counter(c2), (uint32_t)__popcll(m_c), lanes_below(m_c));
-          p_cls = in ? v : p_cls;
-        }
-        if (to_dense) {
-          const bool ok = slot < P.max_dense_rows && off <= P.dense_cap && nS <= P.dense_cap - off;
-          if (slot < P.max_dense_rows) {
-            B.dense_rows[slot] = ok ? row : FX_NONE;
-            B.dense_off[slot] = off;
-            B.dense_order[cls * P.max_dense_rows + p_cls] = slot;
-          }
-          if (!ok) {  // pools exhausted (limits.max_dense_points): flagged, never silent
-            atomicOr(&B.flags[scan], FX_FLAG_NBR_OVERFLOW);
-            B.kp_nbrs[(size_t)scan * P.max_keypoints + k] = FX_NONE;
-            dense_fail = 1;
-          }
-        }
-      }
-    }
-    dense_fail = (uint32_t)__shfl((int)dense_fail, (int)(g * FX_GLANES), 64);
-    if (dense_fail) {
+    if (dense_fail) {  // pools exhausted (limits.max_dense_points): flagged by classify_rows, never silent
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");  // (the clearing stores first)
       desc_fill_nan(out, gl, FX_GLANES);
+      if (gl == 0) {
+        B.kp_nbrs[(size_t)scan * P.max_keypoints + k] = FX_NONE;
+        B.desc_nbins[row] = FX_ROW_DIRTY;  // cleared whole next time
+      }
+      live = false;
     }
-    if (too_long && gl == 0) B.desc_nbins[row] = FX_ROW_DIRTY;  // written by another tier: cleared whole next time
-    if (too_long) live = false;
     if (!live) nS = 0;
     __builtin_amdgcn_wave_barrier();
     // Neighbours (d2 < R^2) in front, [0, nAll), the rest of the support set filled in from the back, as in the wavefront
@@ -5163,11 +5200,16 @@ __device__ __forceinline__ bool desc_body(const FxDevParams &P, const FxBuffers 
       if (tid + u * NT < P.list_cap) lv[u] = B.s_pts[(size_t)row * P.list_cap + tid + u * NT];
   }
 
+  // the row is this workgroup's in this batch: cleared here, before anything is written to it (the release fence in front of
+  // the barrier before the first store to it, below), and left dirty
+  desc_clear_row(B, row, B.desc_nbins[row], tid, NT);
+
   if (tid < 4) L.s_w[tid] = 0;  // 0: support count, 1: binned neighbours, 2: all neighbours
   // the 3DSC tables ride in the image until the bins are known (the image is cleared after that)
   uint32_t *tl = reinterpret_cast<uint32_t *>(L.img) + FX_DGRID3 * FX_DGRID3 * FX_DGRID3;  // behind the cell table
   for (uint32_t t = tid; t < sizeof(FxScTables) / 4; t += NT) tl[t] = __float_as_uint(reinterpret_cast<const float *>(B.tables)[t]);
   wg_sync<GS>();
+  if (tid == 0) B.desc_nbins[row] = FX_ROW_DIRTY;  // (every thread has read what the last batch left)
   uint32_t nS;
   // Density grid: a list-fed support set is stored sorted by cell (12 x 12 x 12 cells of width >= R/5
   // over the support sphere's box), so the density query of a neighbour only scans the nine rows of
@@ -5348,6 +5390,7 @@ __device__ __forceinline__ bool desc_body(const FxDevParams &P, const FxBuffers 
       L.nw[m] = (1.0f / (float)d) * lut;
     }
   }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");  // (the clearing stores are acknowledged before anything else is written to the row)
   wg_sync<GS>();
   FX_STAMP(2);
   for (uint32_t t = tid; t < FX_DESC_BINS; t += NT) L.img[t] = 0.0f;  // (cell table and 3DSC tables are done with)
@@ -5411,7 +5454,7 @@ __device__ __forceinline__ bool desc_body(const FxDevParams &P, const FxBuffers 
   }
   wg_sync<GS>();
   FX_STAMP(3);
-  // ---- sequential fp32 accumulation per bin, in sorted order; the row was cleared by k_desc_group (rf stays zero)
+  // ---- sequential fp32 accumulation per bin, in sorted order; the row was cleared at the top (rf stays zero)
   for (uint32_t bin = tid; bin < FX_DESC_BINS; bin += NT) {
     const uint32_t s0 = bin ? bin_end[bin - 1u] : 0u, s1 = bin_end[bin];
     if (s0 == s1) continue;
@@ -5435,7 +5478,7 @@ __device__ __forceinline__ void desc_wg_loop(const FxDevParams &P, const FxBuffe
     const uint32_t row = B.list_desc[i];
     const uint2 rm = B.row_map[row];
     const uint32_t nS = B.s_cnt[row];
-    if (nS > P.list_cap || nS > cap) continue;  // (never listed here: k_desc_group sends those rows to the dense tier)
+    if (nS > P.list_cap || nS > cap) continue;  // (never listed here: classify_rows sends those rows to the dense tier)
     desc_body<FAST, NT>(P, B, row, rm.x, rm.y, cap, smem, true);
     __syncthreads();
   }
@@ -5444,7 +5487,7 @@ __device__ __forceinline__ void desc_wg_loop(const FxDevParams &P, const FxBuffe
 // latency chains that leave lanes idle, so concurrency beats width).
 #define FX_DESC_WG_FAST_T 256
 // The dense tier's rows WITHOUT its launches (four in round 5, three since k_dense_finish takes every row): a batch whose predecessors had no dense row (every VLP-16-class batch) gets
-// a handful of workgroups of k_desc_mid's launch instead — 256 threads and 8 KB of LDS place anywhere, where the tier's own kernels'
+// a handful of workgroups of k_desc's launch instead — 256 threads and 8 KB of LDS place anywhere, where the tier's own kernels'
 // workgroups each wait for a large LDS slot behind the other batches' kernels (+3.7 % on the headline with them gone,
 // profiles/r05_experiments.md).  A row that does turn up is computed here by the list tier's body on scratch in HBM, its
 // support set re-gathered from the scan: slower, the same result (each row counts its neighbours' densities itself: what the
@@ -5456,32 +5499,44 @@ __device__ __forceinline__ void dense_slow_loop(const FxDevParams &P, const FxBu
   uint32_t *gs = B.gsd_pool + (size_t)bid * P.gsd_words;
   for (uint32_t slot = bid; slot < n_rows; slot += nblk) {
     const uint32_t row = B.dense_rows[slot];
-    if (row == FX_NONE) continue;  // (no room in the pools: flagged by k_desc_group, as for the fast kernels)
+    if (row == FX_NONE) continue;  // (no room in the pools: flagged by classify_rows, as for the fast kernels)
     const uint2 rm = B.row_map[row];
     desc_body<true, FX_DSLOW_T, true>(P, B, row, rm.x, rm.y, P.max_points, smem, false, gs);
     wg_global_sync();
   }
 }
-// Both middle tiers in one launch: the first n_wg workgroups take list rows (193..cap support points, one keypoint per
-// workgroup at a time), the others take wave rows (65..192, one keypoint per wavefront).  Neither tier fills the chip
-// alone (1600 and 900 of the 8192 wave slots on the VLP-16 bench) and neither depends on the other: one after the
-// other they cost 0.135 + 0.075 ms, together about the longer of the two.  The last n_dslow workgroups (when the dense
-// tier's own kernels are not launched) take the dense tier's rows: k_desc_group, which lists them, has completed.
-static_assert(FX_DSLOW_T == FX_WG && FX_DESC_WG_FAST_T == FX_WG, "k_desc_mid's three kinds of workgroups");
-extern "C" __global__ __launch_bounds__(FX_WG) void k_desc_mid(FxDevParams P, FxBuffers B, uint32_t batch, uint32_t cap,
-                                                                uint32_t n_wg, uint32_t n_dslow) {
-  if (blockIdx.x == 0 && threadIdx.x == 0) {  // (k_desc_group, which fills the dense tier's row list, has completed)
+// Every tier in one launch, by (rotated: see below) block index: n_wg workgroups take list rows (193..cap support points, one
+// keypoint per workgroup at a time), n_wave take wave rows (65..192, one keypoint per wavefront), n_group stride over all
+// rows and take the group rows (the bulk), and the last n_dslow (when the dense tier's own kernels are not launched) take the
+// dense tier's rows.  No tier
+// fills the chip alone (1600, 900 and — one workgroup a CU with four batches in flight — 1024 of the 8192 wave slots on the
+// VLP-16 bench) and none depends on another: the work lists were completed by the support gather (classify_rows), every row is
+// cleared by the workgroup that computes it, and no workgroup waits for another.  List and wave tier one after the other cost
+// 0.135 + 0.075 ms, together about the longer of the two; the group tier in a launch of its own in front of them made every
+// batch's stream drain once more (profiles/desc_one_launch.md).
+static_assert(FX_DSLOW_T == FX_WG && FX_DESC_WG_FAST_T == FX_WG, "k_desc's four kinds of workgroups");
+extern "C" __global__ __launch_bounds__(FX_WG, FX_GROUP_OCC) void k_desc(FxDevParams P, FxBuffers B, uint32_t batch, uint32_t cap,
+                                                                          uint32_t n_wg, uint32_t n_wave, uint32_t n_dslow) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {  // (the support gather, which fills the dense tier's row list, has completed)
     B.tier_hint[4] = B.counters[6];
     B.tier_hint[5] = B.counters[13];
   }
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-  const uint32_t n_mid = gridDim.x - n_dslow;
-  if (blockIdx.x >= n_mid)
-    dense_slow_loop(P, B, smem, blockIdx.x - n_mid, n_dslow);
-  else if (blockIdx.x < n_wg)
-    desc_wg_loop<true, FX_DESC_WG_FAST_T>(P, B, batch, cap, smem, blockIdx.x, n_wg);
+  const uint32_t n_mid = n_wg + n_wave, n_all = gridDim.x - n_dslow;
+  // The group workgroups are DISPATCHED first (the first n_group block indices), then list, wave, stand-in: measured against
+  // the long rows first, the headline is 2.28e6 against 2.18e6 scans/s (the parent's two launches: 2.21e6) — the striding group
+  // workgroups are the launch's longest-lived, and behind 2048 list and wave workgroups they started last
+  // (profiles/desc_one_launch.md).
+  uint32_t bx = blockIdx.x;
+  bx = bx < n_all - n_mid ? n_mid + bx : (bx < n_all ? bx - (n_all - n_mid) : bx);
+  if (bx < n_wg)
+    desc_wg_loop<true, FX_DESC_WG_FAST_T>(P, B, batch, cap, smem, bx, n_wg);
+  else if (bx < n_mid)
+    desc_wave_body<true>(P, B, batch, smem, bx - n_wg, n_wave);
+  else if (bx < n_all)
+    desc_group_body(P, B, batch, smem, bx - n_mid, n_all - n_mid);
   else
-    desc_wave_body<true>(P, B, batch, smem, blockIdx.x - n_wg, n_mid - n_wg);
+    dense_slow_loop(P, B, smem, bx - n_all, n_dslow);
 }
 
 // ---------------------------------------------------------------- dense tier
@@ -5525,7 +5580,7 @@ extern "C" __global__ __launch_bounds__(FX_WG) void k_desc_mid(FxDevParams P, Fx
 #ifndef FX_DFIN_OCC
 #define FX_DFIN_OCC 1
 #endif
-// size classes of the tier's rows and the batch counters that count them (k_desc_group fills the class lists)
+// size classes of the tier's rows and the batch counters that count them (classify_rows fills the class lists)
 __device__ __forceinline__ uint32_t dense_class(uint32_t nS) { return nS > 8192u ? 0u : (nS > 4096u ? 1u : (nS > 2048u ? 2u : 3u)); }
 __device__ __forceinline__ uint32_t dense_class_counter(uint32_t cls) { return cls == 0u ? 2u : (cls == 1u ? 3u : (cls == 2u ? 7u : 10u)); }
 // i-th row of the tier, largest class first (FX_NONE past the end)
@@ -5624,7 +5679,7 @@ extern "C" __global__ __launch_bounds__(FX_DSORT_T) void k_dense_sort(FxDevParam
     const uint32_t slot = dense_next(P, B, 11u, &s_slot);
     if (slot == FX_NONE) break;
     const uint32_t row = B.dense_rows[slot];
-    if (row == FX_NONE) {  // (no room in the pools: k_desc_group flagged it)
+    if (row == FX_NONE) {  // (no room in the pools: classify_rows flagged it)
       if (tid == 0) B.dense_nq[slot] = 0u, B.dense_nm[slot] = FX_NONE;
       continue;
     }
@@ -6344,7 +6399,7 @@ __device__ __forceinline__ void dense_finish_row(const FxDevParams &P, const FxB
   for (int u = 0; u < PER; ++u)
     if (dst[u] != FX_NONE) sw[dst[u]] = wgt[u];
   __syncthreads();
-  // one lane per bin adds the bin's weights in order (the row was cleared by k_desc_group)
+  // one lane per bin adds the bin's weights in order (the row was cleared by dense_finish_loop)
   for (uint32_t bin = tid; bin < FX_DESC_BINS; bin += NT) {
     const uint32_t s0 = bin ? bin_end[bin - 1u] : 0u, s1 = bin_end[bin];
     if (s0 == s1) continue;
@@ -6378,8 +6433,20 @@ __device__ __forceinline__ void dense_finish_loop(const FxDevParams &P, const Fx
     const uint32_t slot = dense_next(P, B, 0u, s_slot);
     if (slot == FX_NONE) break;
     const uint32_t nM = B.dense_nm[slot];
-    if (nM == FX_NONE) continue;  // failed row (flagged)
     const uint32_t row = B.dense_rows[slot];
+    if (row == FX_NONE) continue;  // no room in the pools (flagged by classify_rows; the row is the group workgroups')
+    // the row is this workgroup's in this batch: cleared here, before anything is written to it, and left dirty (dense_next's
+    // barriers are between every thread's read of what the last batch left and the mark)
+    const uint32_t nb_prev = B.desc_nbins[row];
+    if (nM == FX_NONE) {  // failed row (flagged): k_dense_sort filled every word of it
+      __syncthreads();
+      if (threadIdx.x == 0) B.desc_nbins[row] = FX_ROW_DIRTY;
+      continue;
+    }
+    desc_clear_row(B, row, nb_prev, threadIdx.x, NT);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");  // (the clearing stores are acknowledged before anything else is written to the row)
+    __syncthreads();
+    if (threadIdx.x == 0) B.desc_nbins[row] = FX_ROW_DIRTY;
     const uint2 rm = B.row_map[row];
     if (B.kp_nbrs[(size_t)rm.x * P.max_keypoints + rm.y] == 0u) {  // no point within R: NaN descriptor, no RNG draw (A.8-3)
       desc_fill_nan(B.desc + (size_t)row * FX_DESC_FLOATS, threadIdx.x, NT);
@@ -6395,6 +6462,8 @@ extern "C" __global__ __launch_bounds__(FX_DFIN_T, FX_DFIN_OCC) void k_dense_fin
 
 // RNG ordinals when several workgroups of k_gather shared a scan (small batches): 3DSC draws its three numbers only for
 // keypoints that have neighbours; k_gather left a flag per keypoint in kp_nbrs (the descriptor kernels then store the counts).
+// The same wavefront then classifies the scan's rows (classify_rows): with several workgroups a scan the support counts are
+// final only once the gather's launch is.
 extern "C" __global__ __launch_bounds__(FX_WG) void k_rng_ord(FxDevParams P, FxBuffers B, uint32_t batch) {
   // one wavefront per scan: ordinal of keypoint k = number of earlier keypoints that have neighbours
   const uint32_t b = (blockIdx.x * FX_WG + threadIdx.x) >> 6, lane = threadIdx.x & 63;
@@ -6409,6 +6478,8 @@ extern "C" __global__ __launch_bounds__(FX_WG) void k_rng_ord(FxDevParams P, FxB
     const unsigned long long m = __ballot(k < K && B.kp_nbrs[(size_t)b * P.max_keypoints + k] != 0u);
     if (k < K) B.row_xa[row0 + k] = B.xaxis[base + lanes_below(m)];
     base += (uint32_t)__popcll(m);
+    // ... and, the scan's support counts being final only now that all its workgroups are done, every row to its tier's list
+    classify_rows(P, B, k < K, row0 + k, b, k < K ? B.s_cnt[row0 + k] : 0u);
   }
 }
 
@@ -6506,14 +6577,15 @@ extern "C" __global__ __launch_bounds__(FX_WG) void k_pack_kp_block(FxDevParams 
 // workgroup) turns those into offsets and cuts at the capacity, k_csr_write fills the rows that fit.
 //
 // Two ways to read a row, both a wavefront a row:
-//  - a row k_desc_group filled in this batch (desc_nbins[row] <= FX_GROUP_CAP): only its recorded bins (desc_bins) and the 9
-//    rf words are read.  The recorded list is a SUPERSET of the row's non-zero bins: k_desc_group clears a row at the top of
-//    its trip (whole when desc_nbins was FX_ROW_DIRTY, else the bins recorded last time — by induction all the row held), then
-//    writes `out[bin]` only for the bins it records in desc_bins, and sets desc_nbins to their count only for a live row with
-//    nAll != 0.  Every other row of the batch gets FX_ROW_DIRTY from it: too_long rows (the wave / list / dense tiers and the
-//    NaN fill of an exhausted dense pool, the only other writers of a row) and nAll == 0 (its NaN fill; desc_nbins is then
-//    not rewritten by the closing `nAll != 0` store, it was set dirty just before).  Bins recorded with a weight that summed
-//    to zero bits are dropped by the storage rule.  desc_bins is in atomicAdd order: sorted here by rank within the wavefront.
+//  - a row a group workgroup of k_desc filled in this batch (desc_nbins[row] <= FX_GROUP_CAP): only its recorded bins (desc_bins)
+//    and the 9 rf words are read.  The recorded list is a SUPERSET of the row's non-zero bins: desc_group_body clears a row of its
+//    own at the top of its trip (whole when desc_nbins was FX_ROW_DIRTY, else the bins recorded last time — by induction all the
+//    row held), then writes `out[bin]` only for the bins it records in desc_bins, and sets desc_nbins to their count only for a
+//    live row with nAll != 0; nAll == 0 (its NaN fill; desc_nbins is then not rewritten by the closing `nAll != 0` store, it was
+//    set dirty just before) and a dense row without room in the pools (NaN fill) get FX_ROW_DIRTY from it.  Every other row of the
+//    batch gets FX_ROW_DIRTY from its own tier (the wave / list / dense tiers, the only other writers of a row), which clears it
+//    by the same rule before its first store (desc_clear_row).  Bins recorded with a weight that summed to zero bits are dropped
+//    by the storage rule.  desc_bins is in atomicAdd order: sorted here by rank within the wavefront.
 //  - any other row (FX_ROW_DIRTY; the test build's FX_CSR_FULL_ROWS=1 forces this for every row): the whole row with 16-byte
 //    loads over its aligned span (rows start 4-byte aligned; the pool has 4 words of padding behind its last row), the
 //    non-zero words found with a ballot per component of the float4 and their positions by popcount / mbcnt.
@@ -6535,7 +6607,7 @@ __device__ __forceinline__ uint32_t csr_row(const FxBuffers &B, uint32_t row, ui
     const unsigned long long m = __ballot(v != 0u), mr = __ballot(r != 0u);
     const uint32_t n_bins = (uint32_t)__popcll(m);
     if (col) {
-      uint32_t pos = 0;  // rank among the kept bins (they are distinct: one lane of k_desc_group per bin run)
+      uint32_t pos = 0;  // rank among the kept bins (they are distinct: one lane of desc_group_body per bin run)
       for (unsigned long long q = m; q; q &= q - 1ull) {
         const uint32_t b2 = (uint32_t)__shfl((int)bin, __ffsll((long long)q) - 1, 64);
         pos += b2 < bin ? 1u : 0u;
@@ -6733,7 +6805,7 @@ size_t fxk_dense_finish_lds_bytes(void) {
 }
 uint32_t fxk_dense_cells(void) { return FX_DCELLS; }
 // build parameters of this translation unit the host sizes buffers by (a build with other values must not outrun them)
-uint32_t fxk_group_cap(void) { return FX_GROUP_CAP; }  // bins k_desc_group records per row (FxBuffers::desc_bins)
+uint32_t fxk_group_cap(void) { return FX_GROUP_CAP; }  // bins a group workgroup of k_desc records per row (FxBuffers::desc_bins)
 uint32_t fxk_dfin_k(void) { return FX_DFIN_K; }        // binned neighbours k_dense_finish sorts in LDS
 size_t fxk_desc_lds_bytes(uint32_t cap) { return (size_t)(16 + FX_DESC_WORDS_PER_POINT * cap + FX_DESC_BINS) * 4; }
 
@@ -6761,7 +6833,8 @@ hipError_t fxk_configure(size_t ring_big, size_t merge_big, size_t merge_huge, s
   if (e != hipSuccess) return e;
   e = hipFuncSetAttribute((const void *)k_merge_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)merge_big);
   if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute((const void *)k_desc_mid, hipFuncAttributeMaxDynamicSharedMemorySize, (int)desc_big);
+  desc_big = std::max(desc_big, (size_t)(FX_NWAVE * FX_GROUPS * FX_GROUP_WORDS + FX_TABLE_WORDS) * 4);  // (the group tier's image: any cap)
+  e = hipFuncSetAttribute((const void *)k_desc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)desc_big);
   if (e != hipSuccess) return e;
   e = hipFuncSetAttribute((const void *)k_dense_finish, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fxk_dense_finish_lds_bytes());
   return e;
@@ -6893,15 +6966,16 @@ uint32_t fxk_gather(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uin
   }
   return slices;
 }
-void fxk_desc_group(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, uint32_t grid) {
-  hipLaunchKernelGGL(k_desc_group, dim3(grid), dim3(FX_WG), (size_t)(FX_NWAVE * FX_GROUPS * FX_GROUP_WORDS + FX_TABLE_WORDS) * 4, s, P, B, batch);
-}
-void fxk_desc_mid(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, uint32_t cap, uint32_t n_wg,
-                  uint32_t n_wave, uint32_t n_dslow) {
+// the descriptor tiers' one launch: n_wg list, n_wave wave, n_group group and n_dslow dense stand-in workgroups (see k_desc); its
+// dynamic LDS is the largest of the tiers' images
+void fxk_desc(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, uint32_t cap, uint32_t n_wg, uint32_t n_wave,
+              uint32_t n_group, uint32_t n_dslow) {
   const size_t lds_wave = (size_t)(FX_NWAVE * FX_WAVE_WORDS + FX_TABLE_WORDS) * 4, lds_wg = fxk_desc_lds_bytes(cap);
-  static_assert((16 + FX_DESC_BINS + 16) * 4 <= (FX_NWAVE * FX_WAVE_WORDS + FX_TABLE_WORDS) * 4, "the dense tier's rows in k_desc_mid's LDS");
+  const size_t lds_group = (size_t)(FX_NWAVE * FX_GROUPS * FX_GROUP_WORDS + FX_TABLE_WORDS) * 4;
+  static_assert((16 + FX_DESC_BINS + 16) * 4 <= (FX_NWAVE * FX_WAVE_WORDS + FX_TABLE_WORDS) * 4, "the dense tier's rows in k_desc's LDS");
   n_dslow = std::min(n_dslow, P.gsd_slots);  // (a scratch region each)
-  hipLaunchKernelGGL(k_desc_mid, dim3(n_wg + n_wave + n_dslow), dim3(FX_WG), lds_wave > lds_wg ? lds_wave : lds_wg, s, P, B, batch, cap, n_wg, n_dslow);
+  hipLaunchKernelGGL(k_desc, dim3(n_wg + n_wave + n_group + n_dslow), dim3(FX_WG), std::max({lds_wave, lds_wg, lds_group}), s, P, B, batch, cap,
+                     n_wg, n_wave, n_dslow);
 }
 size_t fxk_dense_slow_words(uint32_t max_points) { return ((size_t)FX_DESC_WORDS_PER_POINT * max_points + 3) & ~(size_t)3; }
 // (rows and items are taken by ticket: any grid is correct; the full ones are what is resident at once)

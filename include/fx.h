@@ -187,8 +187,9 @@ typedef struct fx_batch_view {
 #define FX_N_STAGES 9
 typedef struct fx_timings {
   /* k_prep, k_bucket, k_rings_runs (one wavefront per ring), k_rings_large (the second run tier of many-ring sensors + the workgroup ring tier), k_merge (merge tiers
-   * small / big / large, k_offsets), k_gather (+ k_rng_ord on small batches), k_desc_group, k_desc_mid (wave rows and list
-   * rows in one launch; + the longest lists), k_desc_rare (re-gather, whole-CU and slab tiers) */
+   * small / big / large, k_offsets), k_gather (+ k_rng_ord on small batches; classifies the rows), k_desc_group (k_desc: the
+   * group, wave and list rows and the dense stand-in in ONE launch, timed in this slot), k_desc_mid (brackets nothing since
+   * that launch took its rows: 0), k_desc_rare (the dense tier's own kernels) */
   float ms[FX_N_STAGES];
   float total_ms;
   /* k_prep's execution span on the device's constant-rate clock: first workgroup's start to last workgroup's end — what
@@ -239,7 +240,7 @@ fx_status fx_get_stream(fx_ctx *ctx, void **hip_stream);
 fx_status fx_set_graph_batch(fx_ctx *ctx, uint32_t max_batch);
 /* How many contexts the caller keeps busy on this device at a time (default 1; bench.py and fx::MultiGpu run four).  A
  * launch-policy hint only — results never depend on it: with several batches in flight the grid-stride kernels take
- * smaller grids, so that the batches share the chip instead of each claiming all of it (k_desc_group: one workgroup a CU
+ * smaller grids, so that the batches share the chip instead of each claiming all of it (k_desc's group workgroups: one a CU
  * instead of ten is +2 % on four batches in flight and -10 % on a batch alone).  New in 0.6 */
 fx_status fx_set_batches_in_flight(fx_ctx *ctx, uint32_t n);
 /* depth > 0: record HIP events around every stage kernel for the next batches, keeping the
