@@ -10,7 +10,7 @@ LIB = os.path.join(HERE, "lib", "libfx_hip.so")
 # rarely used tiers and kernels — the product library has none of them compiled in
 LIB_TEST = os.path.join(HERE, "lib", "libfx_hip_test.so")
 SOURCES = ["fx_kernels.hip", "fx_match.hip", "fx_register.hip", "fx_track.hip", "fx_map.hip", "fx_map_grid.hip", "fx_map_merge.hip", "fx_map_localize.hip", "fx_map_relocalize.hip", "fx_map_observe.hip", "fx_map_expect.hip", "fx_map_compact.hip", "fx_map_append.hip", "fx_splice.hip", "fx_map_assoc.hip", "fx_map_join.hip", "fx_map_loop.hip", "fx_map_find_loop.hip", "fx_api.cpp", "fx_host.cpp"]
-HEADERS = ["fx_device.h", "fx_scan_query.h", "fx_consensus.h", "fx_map_consensus.h", "fx_map_grid.h", "fx_map_assoc.h", "fx_map_constellation.h", "fx_sort_replay.h", os.path.join("..", "..", "include", "fx.h")]
+HEADERS = ["fx_device.h", "fx_launch.h", "fx_launch_plan.h", "fx_scan_query.h", "fx_consensus.h", "fx_map_consensus.h", "fx_map_grid.h", "fx_map_assoc.h", "fx_map_constellation.h", "fx_sort_replay.h", os.path.join("..", "..", "include", "fx.h")]
 # -ffp-contract=off: the numerics contract forbids FMA contraction (results must follow
 # PCL/FLANN/Eigen operation order); fp32 divide/sqrt stay at hipcc's correctly rounded default.
 # -O2, not -O3: the kernels are big (k_front 60 KB, k_rings_runs 42 KB of code against a 64 KB instruction cache that two CUs
@@ -137,6 +137,22 @@ def build_multi(force=False, verbose=False):
     return MULTI
 
 
+PLAN_SELFTEST = os.path.join(HERE, "bin", "fx_plan_selftest")
+
+
+def build_plan_selftest(force=False, verbose=False):
+    """CPU self-test of the launch policy (csrc/fx_launch_plan.h: which kernels a batch runs, with what grids): plain g++, no
+    HIP, no GPU."""
+    deps = [os.path.join(CSRC, s) for s in ("fx_plan_selftest.cpp", "fx_launch_plan.h")]
+    if force or not _newer(PLAN_SELFTEST, deps):
+        os.makedirs(os.path.dirname(PLAN_SELFTEST), exist_ok=True)
+        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-o", PLAN_SELFTEST, os.path.join(CSRC, "fx_plan_selftest.cpp")]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+    return PLAN_SELFTEST
+
+
 BATCHER = os.path.join(HERE, "bin", "fx_batcher_cli")
 BATCHER_TEST = os.path.join(HERE, "bin", "fx_batcher_cli_test")
 
@@ -185,6 +201,7 @@ def build(force=False, verbose=False):
     build_skip_epsilon(force, verbose)
     build_cli(force, verbose)
     build_batcher(force, verbose)
+    build_plan_selftest(force, verbose)
     try:  # the multi-GPU driver needs RCCL's development files: without them the library and everything else still build
         build_multi(force, verbose)
     except (subprocess.CalledProcessError, OSError) as e:

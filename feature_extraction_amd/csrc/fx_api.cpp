@@ -17,110 +17,8 @@
 #include <vector>
 
 #include "../../include/fx.h"
+#include "fx_launch.h"
 #include "fx_scan_query.h"
-
-extern "C" {
-size_t fxk_ring_large_lds_bytes(uint32_t cap, uint32_t ccap);
-void fxk_rings_large(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t cap, uint32_t ccap, uint32_t grid,
-                     uint32_t after_runs2);
-void fxk_rings_runs2(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t max_pts, uint32_t grid);
-size_t fxk_merge_lds_bytes(uint32_t cap, uint32_t n_rings);
-size_t fxk_desc_lds_bytes(uint32_t cap);
-size_t fxk_gather_lds_bytes(uint32_t max_keypoints);
-uint32_t fxk_dense_cells(void);
-uint32_t fxk_group_cap(void);
-uint32_t fxk_dfin_k(void);
-void fxk_dense(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t n_cu, uint32_t rows, uint32_t items, uint32_t skip);
-size_t fxk_dense_slow_words(uint32_t max_points);
-size_t fxk_merge_huge_lds_bytes(uint32_t cap, uint32_t ccap, uint32_t n_rings);
-hipError_t fxk_configure(size_t ring_big, size_t merge_big, size_t merge_huge, size_t desc_big, size_t gather);
-uint32_t fxk_near_words(uint32_t max_points);
-void fxk_prep(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, float near_margin, float el0, float inv_step,
-              uint32_t clk_slot);
-void fxk_bucket(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, float el0, float inv_step, uint32_t clk_next);
-uint32_t fxk_prep_slices_max(void);
-void fxk_prep_sliced(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, uint32_t slices, float near_margin, float el0, float inv_step,
-                     uint32_t clk_slot);
-void fxk_bucket_sliced(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, uint32_t slices, float el0, float inv_step,
-                       uint32_t clk_next);
-size_t fxk_ring_runs_lds_bytes(void);
-void fxk_rings_runs(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, uint32_t max_pts, uint32_t grid);
-void fxk_merge_small(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, uint32_t cap);
-void fxk_merge_big(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t cap, uint32_t grid, uint32_t last);
-void fxk_merge_huge(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t cap, uint32_t ccap, uint32_t grid);
-size_t fxk_merge_hp_words(uint32_t cap);
-uint32_t fxk_merge_slices_max(void);
-void fxk_merge_huge_split(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t cap, uint32_t ccap, uint32_t grid, uint32_t slices);
-uint32_t fxk_front_max_rings(void);
-uint32_t fxk_front_merge_cap(void);
-void fxk_front(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, float near_margin, float el0, float inv_step,
-               uint32_t clk_slot, uint32_t merge_cap, uint32_t force_redo);
-void fxk_front_ab(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, float near_margin, float el0, float inv_step,
-                  uint32_t clk_slot, uint32_t force_redo);
-void fxk_front_cd(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, uint32_t clk_slot, uint32_t merge_cap, uint32_t lean,
-                  uint32_t self_n, uint32_t force_redo);
-void fxk_front_redo(hipStream_t s, const FxDevParams &P, const FxBuffers &B, float el0, float inv_step, uint32_t huge_ccap, uint32_t force_slow,
-                    uint32_t grid);
-size_t fxk_slow_words(uint32_t max_ring_points, uint32_t max_candidates, uint32_t huge_ccap);
-void fxk_slow(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t huge_ccap, uint32_t grid, uint32_t batch, uint32_t clk_next);
-hipError_t fxk_configure_front(void);
-uint32_t fxk_gather_slices(uint32_t batch);
-uint32_t fxk_gather(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, float box_margin, uint32_t counted);
-uint32_t fxk_gather_counted_max(void);
-void fxk_desc(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, uint32_t cap, uint32_t n_wg, uint32_t n_wave, uint32_t n_group,
-                  uint32_t n_dslow);
-void fxk_pack_kp_records(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, void *dst,
-                         uint32_t rec_kp);
-size_t fxk_kp_block_bytes(uint32_t max_scans, uint32_t max_total);
-void fxk_pack_kp_block(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, void *dst, uint32_t max_scans, uint32_t max_total,
-                       uint32_t grid);
-void fxk_rng_ord(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch);
-size_t fxk_csr_bytes(uint32_t max_rows, uint32_t cap);
-hipError_t fxk_pack_csr(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, void *dst, uint32_t max_rows, uint32_t cap,
-                        uint32_t grid, uint32_t full_rows);
-hipError_t fxk_match(hipStream_t s, const FxMatchArgs &A, uint32_t n_items, uint32_t mut_n, uint32_t shifts);
-uint32_t fxk_match_tile_rows(void);
-hipError_t fxk_register(hipStream_t s, const FxRegisterArgs &A, uint32_t n_pairs);
-hipError_t fxk_track(hipStream_t s, const FxTrackArgs &A);
-uint32_t fxk_track_wg_rows(void);
-hipError_t fxk_map_reset(hipStream_t s, const FxMapArgs &A);
-hipError_t fxk_map_update(hipStream_t s, const FxMapArgs &A);
-uint32_t fxk_map_wg(void);
-hipError_t fxk_map_merge(hipStream_t s, const FxMapMergeArgs &A);
-uint32_t fxk_map_merge_table(uint32_t cap);
-size_t fxk_map_merge_scratch(FxMapMergeArgs *A, uint8_t *base);
-uint32_t fxk_map_merge_wg(void);
-hipError_t fxk_map_localize(hipStream_t s, const FxMapLocalizeArgs &A);
-size_t fxk_map_localize_scratch(FxMapLocalizeArgs *A, uint8_t *base);
-hipError_t fxk_map_relocalize(hipStream_t s, const FxMapRelocalizeArgs &A);
-size_t fxk_map_relocalize_scratch(FxMapRelocalizeArgs *A, uint8_t *base);
-hipError_t fxk_map_observe(hipStream_t s, const FxMapObserveArgs &A);
-size_t fxk_map_observe_scratch(FxMapObserveArgs *A, uint8_t *base);
-hipError_t fxk_map_expect(hipStream_t s, const FxMapExpectArgs &A);
-size_t fxk_map_expect_scratch(FxMapExpectArgs *A, uint8_t *base);
-hipError_t fxk_map_find_loop(hipStream_t s, const FxMapFindLoopArgs &A);
-size_t fxk_map_find_loop_scratch(FxMapFindLoopArgs *A, uint8_t *base);
-hipError_t fxk_map_compact(hipStream_t s, const FxMapCompactArgs &A);
-size_t fxk_map_compact_scratch(FxMapCompactArgs *A, uint8_t *base);
-hipError_t fxk_map_append(hipStream_t s, const FxMapAppendArgs &A);
-size_t fxk_map_append_scratch(FxMapAppendArgs *A, uint8_t *base);
-hipError_t fxk_map_join(hipStream_t s, const FxMapJoinArgs &A);
-size_t fxk_map_join_scratch(FxMapJoinArgs *A, uint8_t *base);
-hipError_t fxk_map_loop(hipStream_t s, const FxMapLoopArgs &A);
-hipError_t fxk_map_loop_poses(hipStream_t s, const void *result, void *poses, uint32_t first, uint32_t n);
-size_t fxk_map_loop_scratch(FxMapLoopArgs *A, uint8_t *base);
-hipError_t fxk_splice(hipStream_t s, const FxSpliceArgs &A, uint32_t max_grid);
-#ifdef FX_TEST_HOOKS
-void fxk_test_sort_replay(hipStream_t s, const uint32_t *sizes, uint32_t n_seq, uint32_t n, uint32_t *perm);
-void fxk_test_elevation(hipStream_t s, const float *xyz, uint32_t n, const double *tab, float *fast, uint8_t *ok, float *exact);
-void fxk_test_within(hipStream_t s, const float4 *sp, uint32_t n, const float4 *queries, uint32_t nq, float r2, uint32_t *packed, uint32_t *plain);
-#endif
-void fxk_unpack_pc2(hipStream_t s, const void *src, uint32_t n, uint32_t point_step, uint32_t ox, uint32_t oy, uint32_t oz,
-                    uint32_t oi, uint32_t big_endian, void *dst, uint32_t grid);
-void fxk_pack_xyzi32(hipStream_t s, const void *src, uint32_t n, void *dst, uint32_t grid);
-void fxk_pack_features(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, void *dst,
-                       uint32_t capacity, uint32_t grid);
-}
 
 namespace {
 thread_local std::string g_last_error;
@@ -149,7 +47,7 @@ inline const char *test_hook(const char *name) {
   return nullptr;
 #endif
 }
-constexpr uint32_t kMergeCapSmall = 512, kListCap = 4096, kDenseMin = 1024;
+constexpr uint32_t kListCap = 4096, kDenseMin = 1024;
 // default CSR block: 128 entries a row (1 KB: the dense pool's 7956 B / 8; the test scenes average 15 to 77 non-zero words)
 constexpr uint32_t kCsrRowEntries = 128;
 
@@ -180,7 +78,10 @@ struct fx_ctx {
   fx_params params;
   fx_limits lim;
   int device = 0;
-  int n_cu = 256;
+  // the launch policy (csrc/fx_launch_plan.h): what is fixed for the context or set by a setter or a test hook, and what one
+  // batch leaves for the next
+  FxPlanConfig plan_cfg;
+  FxPlanState plan_state;
   FxDevParams dp;
   FxBuffers buf;
   std::vector<void *> dev_allocs;
@@ -193,11 +94,7 @@ struct fx_ctx {
   int meta_next = 0;
   FxScanMeta *d_meta = nullptr;
   float box_margin = 0.f;
-  uint32_t desc_wgs_per_cu = 0;  // the group workgroups of k_desc's launch a CU (0: by batches_in_flight; FX_DESC_WGS_PER_CU in the test build)
-  uint32_t desc_grid_abs = 0;      // test hook (FX_DESC_GRID): the group workgroups of k_desc's launch, absolute
-  uint32_t batches_in_flight = 1;  // fx_set_batches_in_flight: the caller's contexts busy on this device at a time
   uint32_t ring_lds_cap = 0;     // points a ring may have in the workgroup ring tier's LDS (<= max_ring_points; beyond: k_slow)
-  uint32_t merge_big_cap = 0;    // candidates the LDS merge tier holds as points (<= max_candidates)
   uint32_t merge_huge_cap = 0;   // candidates the large merge tier (coordinates in HBM, tables in LDS) holds (<= max_candidates; beyond: k_slow)
   uint32_t merge_huge_ccap = 0;  // clusters the large merge tier can order (>= max_keypoints)
   // host-input staging
@@ -222,48 +119,18 @@ struct fx_ctx {
   uint64_t batch_seq = 0;          // batches enqueued so far
   double clk_khz = 100000.0;       // rate of the device's constant clock
   hipEvent_t *ev = nullptr;  // set of the batch being enqueued
-  uint32_t last_batch = 0;
   // HIP graphs of the stage sequence, one per batch size (batches up to graph_max_batch)
   std::vector<std::pair<uint32_t, hipGraphExec_t>> graphs;
   uint32_t graph_max_batch = 0;
   bool debug_sync = false;
   // the previous batch's work for the rarely used tiers (pinned; written by the device: FxBuffers::tier_hint)
   volatile uint32_t *tier_hint = nullptr;
-  uint32_t tier_min_grid = 8;  // FX_TIER_MIN_GRID: workgroups those tiers get at least (0: always the full grids)
-  // what the tiers were handed lately: the largest count of the last hint_hold_batches batches (a workload that alternates
-  // between batches with and without work for a tier keeps the tier's grid)
-  uint32_t hint_hold[FX_N_HINTS] = {}, hint_age[FX_N_HINTS] = {};
-  static constexpr uint32_t hint_hold_batches = 64;
-  // The fused front kernel (k_front: filter to keypoints in one launch, for scans whose filtered cloud fits LDS) with
-  // k_front_redo behind it.  A batch that hands more than an eighth of its scans to k_front_redo sends the next front_retry
-  // batches through the separate kernels (k_prep ... k_merge_*), which are the fast way for large scans.
-  bool front_ok = false;       // sensor within k_front's ring capacity
-  bool front_last = false;     // what the last batch ran
-  uint32_t front_force = 0;    // test hook (FX_FRONT_FORCE)
-  // k_front as TWO launches (k_front_ab: streaming pass + ring split, the ring-major records through HBM; k_front_cd:
-  // clustering + merge).  Built, parity-green, and NOT the default: alone the two take what the one takes
-  // (0.134 + 0.156 against 0.286 ms), with four batches in flight the headline is 3 % lower (profiles/r06_experiments.md §1).
-  // The test build's FX_FRONT_SPLIT=1 runs it (tests/test_gpu_front_split.py, the fuzz's front-split path).
-  int front_stream = -1;       // test hook (FX_FRONT_STREAM): 1 always the sliced streaming pass + k_front_cd, 0 never; -1: batches of up to front_stream_max_batch scans
-  static constexpr uint32_t front_stream_max_batch = 8;
-  int front_split = 0;         // 1: the two launches; 2: the same with k_front_cd's lean image (the points left in HBM); 0: the one fused launch
   // A batch that failed after its kernels were enqueued leaves state the next batch would build on: descriptor rows are
   // cleared by un-writing what the last batch recorded for them (desc_nbins / desc_bins), the work-list counters are
   // cleared by the batch's first kernel, the tier hints size the next grids.  The next batch then starts from scratch:
   // every row is cleared whole, counters and hints are reset (fx_process_batch).
   bool state_suspect = false;
   uint32_t fail_after = 0;     // test hook (FX_FAIL_AFTER_ENQUEUE = n: the n-th batch returns an error after its kernels were enqueued)
-  uint32_t front_pause = 0;    // batches left on the separate kernels
-  // The dense descriptor tier: its own kernels (k_dense_sort, k_dense_density, k_dense_finish) when a recent batch had rows for it (or nothing is known), else a handful of
-  // workgroups in k_desc's launch (dense_slow_loop) that compute whatever does turn up, slower — the same results either way.
-  uint32_t dense_fast_left = 0;            // batches that still get the tier's kernels after the last one that needed them
-  static constexpr uint32_t dense_linger = 64;
-  int gather_slices = -1;                  // test hook (FX_GATHER_COUNTED): workgroups a scan in the support gather's counted slices (1: one workgroup a scan)
-  int merge_slices = -1;                   // test hook (FX_MERGE_SLICES): workgroups a scan in the large merge tier's pair loop (1: the one launch)
-  int prep_slices = -1;                    // test hook (FX_PREP_SLICES): workgroups a scan in the separate kernels' streaming pass and ring split
-  int dense_force = -1;                    // test hook (FX_DENSE_SLOW): 1 always k_desc's stand-in workgroups, 0 always the tier's own kernels
-  uint32_t skip_mask = 0;      // experiment hook (FX_SKIP_EMPTY, test build): bit 0 no k_front_redo, bit 1 no dense tier — only for workloads that need neither (a dense row that does turn up is then neither computed NOR CLEARED: every tier clears its own rows, so such a row keeps what the last batch left in it); bits 2 / 3: no k_dense_finish / k_dense_density (measurement: results wrong)
-  static constexpr uint32_t front_retry = 64;
   // FX_OUT_DESC_CSR: the context's CSR block of descriptor rows (max_total_keypoints rows, csr_cap entries) and its pinned
   // mirror, allocated at the first batch that asks for it and grown (never shrunk) when a batch needs more entries
   uint8_t *d_csr = nullptr, *h_csr = nullptr;
@@ -401,8 +268,8 @@ size_t csr_val_offset(uint32_t max_rows, uint32_t cap) { return csr_col_offset(m
 // k_csr_count / k_csr_write: grid-stride, a wavefront a row, up to eight workgroups a CU
 fx_status enqueue_csr(fx_ctx *c, hipStream_t s, void *dst, uint32_t max_rows, uint32_t cap) {
   const uint32_t rows_bound = std::min(c->lim.max_total_keypoints, 0xffffffffu - 3u);
-  const uint32_t grid = std::max(1u, std::min((rows_bound + 3u) / 4u, 8u * (uint32_t)c->n_cu));
-  FX_HIP(fxk_pack_csr(s, c->dp, c->buf, c->last_batch, dst, max_rows, cap, grid, c->csr_full_rows));
+  const uint32_t grid = std::max(1u, std::min((rows_bound + 3u) / 4u, 8u * c->plan_cfg.n_cu));
+  FX_HIP(fxk_pack_csr(s, c->dp, c->buf, c->plan_state.last_batch, dst, max_rows, cap, grid, c->csr_full_rows));
   return FX_OK;
 }
 // The context's block with room for `cap` entries (max_total_keypoints rows).  An existing block is freed once the stream
@@ -455,37 +322,12 @@ std::vector<double> atan_table() {
 }
 
 // Enqueues the stage kernels of one batch on stream s (the whole device-side pipeline between the
-// scan-table upload and the result copies).  Also what a HIP graph of the batch is captured from.
-fx_status enqueue_stages(fx_ctx *c, hipStream_t s, uint32_t batch, bool prof, bool front, bool capture = false) {
+// scan-table upload and the result copies), as `plan` says (csrc/fx_launch_plan.h decides; nothing is decided here).  Also
+// what a HIP graph of the batch is captured from.
+fx_status enqueue_stages(fx_ctx *c, hipStream_t s, uint32_t batch, bool prof, const FxLaunchPlan &plan) {
   const fx_limits &L = c->lim;
   const FxDevParams &P = c->dp;
   const FxBuffers &B = c->buf;
-  const uint32_t big_grid = (uint32_t)c->n_cu;
-  // The tiers behind the common ones (workgroup-per-ring, LDS-sized merges, the dense descriptor tier) take their work from
-  // lists by stride or ticket, so any grid computes the same; a launch that finds its list empty still has to place every
-  // workgroup, and these want most of a CU each.  Their grids follow what the context's previous batch handed them (twice
-  // that, at least tier_min_grid, at most the full grid; the full grid while nothing is known): a sparse batch costs
-  // eight workgroups a tier instead of 256, and a batch that is suddenly dense runs its tiers narrow once.
-  uint32_t hint[FX_N_HINTS];
-  for (int i = 0; i < FX_N_HINTS; ++i) {
-    hint[i] = (capture || !c->tier_min_grid) ? 0xffffffffu : c->tier_hint[i];
-    if (capture || !c->tier_min_grid) continue;
-    // (held: the largest count of the last hint_hold_batches batches; "nothing known yet" stays that only until something
-    //  is known — held like a count it kept every rare tier at its full grid for the first 64 batches of a context, and
-    //  after every reset)
-    if (hint[i] == 0xffffffffu || c->hint_hold[i] == 0xffffffffu || hint[i] >= c->hint_hold[i] || ++c->hint_age[i] > fx_ctx::hint_hold_batches)
-      c->hint_hold[i] = hint[i], c->hint_age[i] = 0;
-    hint[i] = c->hint_hold[i];
-  }
-  // (min_wg: the scans k_front hands on — k_front_redo, k_slow — get ONE workgroup when the last 64 batches handed on
-  //  nothing: an empty launch of eight k_front-shaped workgroups instead costs the headline 1 %, profiles/r05_experiments.md §9)
-  auto tier_grid = [&](uint32_t work, uint32_t full, uint32_t bound, uint32_t per = 1, uint32_t min_wg = 0) -> uint32_t {
-    uint32_t g = work > full / 2 ? full : 2 * work;  // (also: unknown)
-    const uint32_t floor_wg = min_wg ? std::min(min_wg, c->tier_min_grid) : c->tier_min_grid;
-    if (g < (floor_wg + per - 1) / per) g = (floor_wg + per - 1) / per;
-    if (g > bound) g = bound ? bound : 1;            // never more workgroups than the batch could have items for
-    return g < full ? g : full;
-  };
   if (prof) {
     c->ev = &c->ev_ring[(size_t)(c->ev_count % c->ev_depth) * (FX_N_STAGES + 1)];
     c->ev_mask[c->ev_count % c->ev_depth] = c->prof_mask;
@@ -503,156 +345,76 @@ fx_status enqueue_stages(fx_ctx *c, hipStream_t s, uint32_t batch, bool prof, bo
     return (prof && wanted) ? hipEventRecord(c->ev[i], s) : hipSuccess;
   };
   FX_HIP(mark(0));
-  if (!batch) FX_HIP(hipMemsetAsync(B.counters, 0, FX_N_COUNTERS * sizeof(uint32_t), s));  // (k_prep clears them otherwise)
-  if (batch) {
-    const uint32_t merge_small = L.max_candidates < kMergeCapSmall ? L.max_candidates : kMergeCapSmall;
-    // k_desc's group workgroups stride over the rows: ten a CU when the batch has the
-    // chip to itself; with batches in flight fewer, longer-lived ones (measured, 1 / 2 / 3 / 4 batches in flight, scans/s with
-    // 10 against 1 a CU: 1.64 / 1.47, 2.11 / 2.04, 2.25 / 2.27 — 2.29 with 3 —, 2.32 / 2.38e6: profiles/r05_experiments.md)
-    const uint32_t desc_per_cu = c->desc_wgs_per_cu ? c->desc_wgs_per_cu : (c->batches_in_flight >= 4u ? 1u : (c->batches_in_flight == 3u ? 3u : 10u));
-    // (never more workgroups than the batch can have rows for: sixteen rows a workgroup and trip — one scan per call launched
-    //  2560 workgroups for its fifty rows)
-    const uint32_t rows_bound = std::min<uint64_t>((uint64_t)batch * L.max_keypoints, L.max_total_keypoints);
-    uint32_t desc_grid = std::max(1u, std::min((uint32_t)c->n_cu * desc_per_cu, (rows_bound + 15u) / 16u));
-    if (c->desc_grid_abs) desc_grid = c->desc_grid_abs;  // (test hook)
-    const uint32_t clk_slot = (uint32_t)(c->batch_seq % FX_CLK_SLOTS), clk_next = (uint32_t)((c->batch_seq + 1) % FX_CLK_SLOTS);
-    const float el0 = (float)c->params.el0_deg, inv_step = (float)(1.0 / c->params.el_step_deg);
-    if (front) {
-      // stages 0-4 in three launches: k_front; k_front_redo — workgroups of k_front's shape, a few of them unless the
-      // previous batch had work for it — for the scans that do not fit k_front's tables; and k_slow (256 threads, 9 KB of
-      // LDS: an empty launch of it places anywhere) for what exceeds that shape's LDS too, on scratch in HBM.  All three go
-      // with EVERY batch: the hints size grids, they never decide whether a scan gets what it needs.
-      const uint32_t mcap = std::min(fxk_front_merge_cap(), L.max_candidates);
-      const bool split = c->front_split != 0;
-      // A handful of scans per call (the reference's own mode: one scan per callback, ref: node.cpp:72, :386): k_front's streaming
-      // pass would be ONE workgroup a scan on a chip of 256 CUs — 0.036 of a scan's 0.093 ms in k_front.  So the streaming pass
-      // and the ring split go out SLICED, sixteen workgroups a scan (the counting pass, k_prep_sliced, k_bucket_sliced: the
-      // separate kernels' own, whose ring-major records are what k_front_ab writes), and k_front_cd clusters and merges in one.
-      const bool stream = c->front_stream >= 0 ? c->front_stream != 0 : batch <= fx_ctx::front_stream_max_batch;
-      if (stream && !split) {  // (stage 0: the streaming pass, stage 1: ring split + k_front_cd)
-        fxk_prep_sliced(s, P, B, batch, fxk_prep_slices_max(), c->box_margin, el0, inv_step, clk_slot);
-        FX_HIP(mark(1));
-        fxk_bucket_sliced(s, P, B, batch, fxk_prep_slices_max(), el0, inv_step, clk_next);
-        fxk_front_cd(s, P, B, batch, clk_slot, mcap, 0u, 1u, c->front_force >= 1u ? 1u : 0u);
-      } else if (split) {  // (stage 0: k_front_ab, stage 1: k_front_cd)
-        fxk_front_ab(s, P, B, batch, c->box_margin, el0, inv_step, clk_slot, c->front_force >= 1u ? 1u : 0u);
-        FX_HIP(mark(1));
-        fxk_front_cd(s, P, B, batch, clk_slot, mcap, c->front_split >= 2 ? 1u : 0u, 0u, 0u);
-      } else {
-        fxk_front(s, P, B, batch, c->box_margin, el0, inv_step, clk_slot, mcap, c->front_force >= 1u ? 1u : 0u);
-        FX_HIP(mark(1));
-      }
-      for (int i = 2; i <= 4; ++i) FX_HIP(mark(i));
-      // (the grid k_front_redo gets when the last 64 batches handed it nothing: ONE workgroup when the caller keeps four
-      //  batches in flight — an empty launch of k_front-shaped workgroups waits for whole free CUs in the other batches' way:
-      //  four of them cost the headline 0.6 %, eight 1.1 % —, four otherwise: a stream with the chip to itself pays nothing for
-      //  them, and a batch that suddenly hands on many scans is not dealt through a single workgroup — ADVICE r5)
-      const uint32_t redo_floor = c->batches_in_flight >= 4u ? 1u : 4u;
-      if (!(c->skip_mask & 1u))
-      fxk_front_redo(s, P, B, el0, inv_step, c->merge_huge_ccap, c->front_force >= 2u ? 1u : 0u, tier_grid(hint[6], 2 * big_grid, batch, 1, redo_floor));
-      fxk_slow(s, P, B, c->merge_huge_ccap, tier_grid(hint[7], big_grid, batch), batch, clk_next);  // (its last workgroup does the batch's keypoint offsets too)
-      FX_HIP(mark(5));
-    } else {
-    // one workgroup a scan when the batch fills the chip with that, several (a counting pass first) when it does not and the
-    // scans are big enough to be worth a second read: 64 scans of 262 144 points are 64 workgroups on 256 CUs
-    uint32_t slices = 1;
-    if (c->prep_slices >= 0) {
-      slices = (uint32_t)c->prep_slices;  // (test hook)
-    } else if (4u * batch <= 2u * big_grid && L.max_points >= 65536u) {
-      // (from four workgroups a scan on: with two — 256 scans of 131 072 points — the second read of the scan costs more
-      //  than the wider grid gains: k_prep 0.15 -> 0.23 ms; with eight — 64 scans of 262 144 points — 0.23 -> 0.125 ms.
-      //  Three workgroups a CU in all: what k_bucket_sliced's scalar registers (106: six wavefronts a SIMD) let be resident at once — 64 scans: the ring split
-      //  0.092 / 0.065 / 0.109 ms with 8 / 12 / 16 a scan; 128 scans: 0.16 / 0.109 / 0.206 with 4 / 6 / 8,
-      //  profiles/r06_experiments.md §12)
-      slices = 3u * big_grid / batch;
-    }
-    slices = std::max(1u, std::min(slices, fxk_prep_slices_max()));
-    if (slices > 1) {
-      fxk_prep_sliced(s, P, B, batch, slices, c->box_margin, el0, inv_step, clk_slot);
+  if (!batch) {
+    FX_HIP(hipMemsetAsync(B.counters, 0, FX_N_COUNTERS * sizeof(uint32_t), s));  // (k_prep clears them otherwise)
+    for (int i = 1; i <= FX_N_STAGES; ++i) FX_HIP(mark(i));
+    return FX_OK;
+  }
+  const uint32_t clk_slot = (uint32_t)(c->batch_seq % FX_CLK_SLOTS), clk_next = (uint32_t)((c->batch_seq + 1) % FX_CLK_SLOTS);
+  const float el0 = (float)c->params.el0_deg, inv_step = (float)(1.0 / c->params.el_step_deg);
+  if (plan.front != FX_FRONT_SEPARATE) {
+    // stages 0-4: the front in one of its launch sets, then k_front_redo for the scans that do not fit k_front's tables and
+    // k_slow for what exceeds that shape's LDS too.  All go with EVERY batch: the plan sizes grids, it never decides whether
+    // a scan gets what it needs.
+    if (plan.front == FX_FRONT_STREAMED) {  // (stage 0: the streaming pass, stage 1: ring split + k_front_cd)
+      fxk_prep_sliced(s, P, B, batch, plan.prep_slices, c->box_margin, el0, inv_step, clk_slot);
       FX_HIP(mark(1));
-      fxk_bucket_sliced(s, P, B, batch, slices, el0, inv_step, clk_next);
+      fxk_bucket_sliced(s, P, B, batch, plan.prep_slices, el0, inv_step, clk_next);
+      fxk_front_cd(s, P, B, batch, clk_slot, plan.front_merge_cap, 0u, 1u, plan.force_redo);
+    } else if (plan.front == FX_FRONT_FUSED) {
+      fxk_front(s, P, B, batch, c->box_margin, el0, inv_step, clk_slot, plan.front_merge_cap, plan.force_redo);
+      FX_HIP(mark(1));
+    } else {  // (stage 0: k_front_ab, stage 1: k_front_cd)
+      fxk_front_ab(s, P, B, batch, c->box_margin, el0, inv_step, clk_slot, plan.force_redo);
+      FX_HIP(mark(1));
+      fxk_front_cd(s, P, B, batch, clk_slot, plan.front_merge_cap, plan.front == FX_FRONT_TWO_LEAN ? 1u : 0u, 0u, 0u);
+    }
+    for (int i = 2; i <= 4; ++i) FX_HIP(mark(i));
+    if (plan.redo_grid) fxk_front_redo(s, P, B, el0, inv_step, c->merge_huge_ccap, plan.force_slow, plan.redo_grid);
+    fxk_slow(s, P, B, c->merge_huge_ccap, plan.slow_grid, batch, clk_next);  // (its last workgroup does the batch's keypoint offsets too)
+    FX_HIP(mark(5));
+  } else {
+    if (plan.prep_slices > 1) {
+      fxk_prep_sliced(s, P, B, batch, plan.prep_slices, c->box_margin, el0, inv_step, clk_slot);
+      FX_HIP(mark(1));
+      fxk_bucket_sliced(s, P, B, batch, plan.prep_slices, el0, inv_step, clk_next);
     } else {
       fxk_prep(s, P, B, batch, c->box_margin, el0, inv_step, clk_slot);
       FX_HIP(mark(1));
-      fxk_bucket(s, P, B, batch, el0, inv_step, clk_next);
+      fxk_bucket(s, P, B, batch, el0, inv_step, clk_next, plan.many_rings ? 1u : 0u);
     }
     FX_HIP(mark(2));
-    // one wavefront per (scan, ring): the hardware dispatcher balances the rings, whose costs differ a lot
-    // (persistent wavefronts striding over the items: 0.18 ms instead of 0.14)
-    fxk_rings_runs(s, P, B, batch, L.max_ring_points, (batch * (uint32_t)c->params.n_rings + 7) / 8 * 8);
+    fxk_rings_runs(s, P, B, batch, L.max_ring_points, plan.runs_grid);
     FX_HIP(mark(3));
-    // sensors of more than the reference's 16 rings: dense rings, many of which need longer run tables than the first tier's
-    const bool runs2 = c->params.n_rings > 16;
-    // (these two take the list of XCD class blockIdx % 8: grids are multiples of 8, the hints the longest class list)
-    const uint32_t n_items = batch * (uint32_t)c->params.n_rings;
-    if (runs2) fxk_rings_runs2(s, P, B, L.max_ring_points, 8 * tier_grid(hint[0], (big_grid * 7 + 7) / 8, (n_items + 7) / 8, 8));  // (seven a CU: 21 KB of LDS each)
-    fxk_rings_large(s, P, B, c->ring_lds_cap, c->ring_lds_cap, 8 * tier_grid(hint[runs2 ? 1 : 0], (big_grid + 7) / 8, (n_items + 7) / 8, 8),
-                    runs2 ? 1u : 0u);
+    if (plan.runs2_grid) fxk_rings_runs2(s, P, B, L.max_ring_points, plan.runs2_grid);
+    fxk_rings_large(s, P, B, c->ring_lds_cap, c->ring_lds_cap, plan.large_grid, plan.runs2_grid ? 1u : 0u);
     FX_HIP(mark(4));
-    fxk_merge_small(s, P, B, batch, merge_small);
-    fxk_merge_big(s, P, B, c->merge_big_cap, tier_grid(hint[2], big_grid, batch), c->merge_big_cap >= L.max_candidates);
-    if (c->merge_big_cap < L.max_candidates) {
-      // one workgroup a scan in one launch — or, when the batches before had so few scans for this tier that those leave most
-      // of the chip idle (64 scans of config 5 on 256 CUs), three launches with several workgroups a scan in the pair loop,
-      // which is 97 % of the tier (merge_body's PHASE).  The hint decides speed, never a result.
-      const uint32_t g = tier_grid(hint[3], big_grid, batch);
-      uint32_t slices = 1;
-      if (c->merge_slices >= 0)
-        slices = (uint32_t)c->merge_slices;  // (test hook)
-      else if (!capture && hint[3] != 0xffffffffu && hint[3] > 0 && 2u * hint[3] * c->batches_in_flight <= big_grid)
-        slices = big_grid / (hint[3] * c->batches_in_flight);  // (the caller's other batches fill the chip as well: config 5 with four in flight 8.6e4 scans/s in one launch, 8.0e4 in three)
-      slices = std::min(slices, fxk_merge_slices_max());
-      if (slices > 1 && B.merge_hp)
-        fxk_merge_huge_split(s, P, B, c->merge_huge_cap, c->merge_huge_ccap, g, slices);
+    fxk_merge_small(s, P, B, batch, plan.merge_small_cap);
+    fxk_merge_big(s, P, B, c->plan_cfg.merge_big_cap, plan.merge_big_grid, plan.merge_big_last);
+    if (plan.merge_huge_grid) {
+      if (plan.merge_huge_slices > 1)
+        fxk_merge_huge_split(s, P, B, c->merge_huge_cap, c->merge_huge_ccap, plan.merge_huge_grid, plan.merge_huge_slices);
       else
-        fxk_merge_huge(s, P, B, c->merge_huge_cap, c->merge_huge_ccap, g);
+        fxk_merge_huge(s, P, B, c->merge_huge_cap, c->merge_huge_ccap, plan.merge_huge_grid);
     }
-    fxk_slow(s, P, B, c->merge_huge_ccap, tier_grid(hint[7], big_grid, batch), batch, clk_next);  // (rings / merges beyond the LDS tiers, and the batch's keypoint offsets: see the front path)
+    fxk_slow(s, P, B, c->merge_huge_ccap, plan.slow_grid, batch, clk_next);  // (rings / merges beyond the LDS tiers, and the batch's keypoint offsets: see the front path)
     FX_HIP(mark(5));
-    }
-    if (P.estimate_descriptors) {
-      // one workgroup a scan — or, for batches of few big scans with the chip to themselves (64 scans of 262 144 points: 64
-      // workgroups on 256 CUs), several a scan in two launches: a counting pass, then the scatter with every slice's list
-      // positions known (from four a scan on: the near sectors are read and tested twice)
-      uint32_t counted = 1;
-      if (c->gather_slices >= 0)
-        counted = (uint32_t)c->gather_slices;  // (test hook)
-      else if (!capture && 10u * batch * c->batches_in_flight <= 3u * big_grid && L.max_points >= 65536u)
-        // (256-thread workgroups, three a CU: all resident at once.  From ten a scan on: config 5 — 64 scans — 0.255 ms with one
-        //  wide workgroup a scan, 0.405 / 0.246 / 0.197 / 0.273 with 4 / 8 / 12 / 16 counted slices, profiles/r06_experiments.md §4)
-        counted = 3u * big_grid / (batch * c->batches_in_flight);
-      if (fxk_gather(s, P, B, batch, c->box_margin, counted) > 1) fxk_rng_ord(s, P, B, batch);  // (one workgroup per scan settles the RNG ordinals itself)
-      FX_HIP(mark(6));
-      // The dense tier (larger support sets and overflowed lists; nothing on sparse scans): its own three kernels, or a handful of
-      // workgroups of k_desc's launch — the previous batches decide speed, never results.
-      // (beside k_desc_mid, as it then was, on a second stream of the context: measured and dropped, profiles/r04_front_experiments.md)
-      bool fast = capture || hint[4] != 0u;  // (0xffffffff: nothing known yet)
-      if (fast && !capture && hint[4] != 0xffffffffu) c->dense_fast_left = fx_ctx::dense_linger;
-      if (!fast && c->dense_fast_left) --c->dense_fast_left, fast = true;
-      if (c->dense_force >= 0) fast = c->dense_force == 0;
-      const bool skip_dense = (c->skip_mask & 2u) != 0u;
-      // every tier in ONE launch, timed in the group tier's slot (the next slot brackets nothing): list rows (lists of up to
-      // dense_min entries, four keypoints per CU in flight), wave rows, the group rows' striding workgroups, the dense stand-in —
-      // the gather has classified every row, so no tier waits for another (k_desc)
-      fxk_desc(s, P, B, batch, P.list_cap < P.dense_min ? P.list_cap : P.dense_min, std::max(1u, std::min(big_grid * 4, rows_bound)),
-               std::max(1u, std::min(big_grid * 4, (rows_bound + 3u) / 4u)), desc_grid, fast || skip_dense ? 0u : (c->tier_min_grid ? c->tier_min_grid : 8u));
-      FX_HIP(mark(7));
-      FX_HIP(mark(8));
-      if (fast && !skip_dense) {
-        const uint32_t max_rows = batch * L.max_keypoints < L.max_total_keypoints ? batch * L.max_keypoints : L.max_total_keypoints;
-        const uint32_t rows = tier_grid(hint[4], 3 * big_grid, max_rows);
-        // density items: 1024 queries each, at most one a row more than the support points fill
-        const uint32_t items = hint[5] == 0xffffffffu ? 3 * big_grid : tier_grid(hint[4] + hint[5] / 1024u, 3 * big_grid, 0xffffffffu);
-        fxk_dense(s, P, B, big_grid, rows, items, (c->skip_mask >> 2) & 3u);
-      }
-    } else {
-      for (int i = 6; i <= 8; ++i) FX_HIP(mark(i));
-    }
-    FX_HIP(mark(9));
-    FX_HIP(hipGetLastError());
-  } else {
-    for (int i = 1; i <= FX_N_STAGES; ++i) FX_HIP(mark(i));
   }
+  if (plan.descriptors) {
+    fxk_gather(s, P, B, batch, c->box_margin, plan.gather, plan.gather_n);
+    if (plan.rng_ord) fxk_rng_ord(s, P, B, batch);
+    FX_HIP(mark(6));
+    // every descriptor tier in ONE launch, timed in the group tier's slot (the next slot brackets nothing) — the gather has
+    // classified every row, so no tier waits for another (k_desc)
+    fxk_desc(s, P, B, batch, plan.desc_cap, plan.desc_wg, plan.desc_wave, plan.desc_group, plan.desc_dslow);
+    FX_HIP(mark(7));
+    FX_HIP(mark(8));
+    if (plan.dense) fxk_dense(s, P, B, plan.dense_sort_grid, plan.dense_density_grid, plan.dense_finish_grid, plan.dense_skip);
+  } else {
+    for (int i = 6; i <= 8; ++i) FX_HIP(mark(i));
+  }
+  FX_HIP(mark(9));
+  FX_HIP(hipGetLastError());
   return FX_OK;
 }
 
@@ -667,7 +429,12 @@ fx_status launch_graph(fx_ctx *c, hipStream_t s, uint32_t batch, bool front) {
   if (!exec) {
     hipGraph_t graph = nullptr;
     FX_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    fx_status st = enqueue_stages(c, s, batch, false, front, true);  // (a graph's grids are fixed: the full ones, bounded by the batch)
+    // (a graph's grids are fixed: the full ones, bounded by the batch; its front is what this batch was given)
+    FxPlanConfig cfg = c->plan_cfg;
+    cfg.front_ok = front;
+    const uint32_t no_hints[FX_N_HINTS] = {};  // (not read under capture, and the state is not touched)
+    const FxLaunchPlan plan = fx_plan_batch(cfg, &c->plan_state, no_hints, batch, true);
+    fx_status st = enqueue_stages(c, s, batch, false, plan);
     hipError_t e = hipStreamEndCapture(s, &graph);
     if (st != FX_OK) {
       if (graph) (void)hipGraphDestroy(graph);
@@ -872,21 +639,22 @@ fx_status fx_create(const fx_params *params, const fx_limits *limits, int device
   c->lim = L;
   c->device = device_id;
   c->ring_lds_cap = ring_lds_cap;
-  c->merge_big_cap = merge_big_cap;
+  FxPlanConfig &pc = c->plan_cfg;
+  pc.merge_big_cap = merge_big_cap;
   c->merge_huge_cap = merge_huge_cap;
   c->merge_huge_ccap = merge_huge_ccap;
   if (const char *e = test_hook("FX_DESC_WGS_PER_CU")) {  // experiment hook: ignored outside 1..32
     const int v = atoi(e);
-    if (v >= 1 && v <= 32) c->desc_wgs_per_cu = (uint32_t)v;
+    if (v >= 1 && v <= 32) pc.desc_wgs_per_cu = (uint32_t)v;
   }
-  if (const char *e = test_hook("FX_DESC_GRID")) c->desc_grid_abs = (uint32_t)std::max(0, atoi(e));
+  if (const char *e = test_hook("FX_DESC_GRID")) pc.desc_grid_abs = (uint32_t)std::max(0, atoi(e));
   if (const char *e = test_hook("FX_DEBUG_SYNC")) c->debug_sync = atoi(e) != 0;
   if (const char *e = test_hook("FX_GRAPH_MAX_BATCH")) {
     const int v = atoi(e);
     if (v >= 0) c->graph_max_batch = (uint32_t)v;
   }
   hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device_id) == hipSuccess) c->n_cu = prop.multiProcessorCount;
+  if (hipGetDeviceProperties(&prop, device_id) == hipSuccess) pc.n_cu = (uint32_t)prop.multiProcessorCount;
 
   // ---- constants, narrowed where PCL narrows them
   FxDevParams &P = c->dp;
@@ -1035,7 +803,7 @@ fx_status fx_create(const fx_params *params, const fx_limits *limits, int device
     // the slow tier's scratch: a region per workgroup of its largest grid — a CU's worth of workgroups, fewer for small
     // contexts or huge limits (256 MB at most)
     const size_t words = fxk_slow_words(L.max_ring_points, L.max_candidates, c->merge_huge_ccap);
-    size_t slots = std::min<size_t>((size_t)c->n_cu, B);
+    size_t slots = std::min<size_t>((size_t)c->plan_cfg.n_cu, B);
     while (slots > 1 && slots * words * 4 > ((size_t)256 << 20)) --slots;
     P.gs_words = (uint32_t)words;
     P.gs_slots = (uint32_t)slots;
@@ -1054,7 +822,7 @@ fx_status fx_create(const fx_params *params, const fx_limits *limits, int device
   //  than k_merge_big's — whenever a scan has more candidates than that)
   FX_A(dev_alloc(c, &b.merge_sorted, (size_t)B * L.max_candidates));
   // (the large merge tier as three launches: a region per scan, when the tier exists and the regions stay within 256 MB)
-  if (c->merge_big_cap < L.max_candidates && (size_t)B * fxk_merge_hp_words(c->merge_huge_cap) * 4 <= ((size_t)256 << 20))
+  if (c->plan_cfg.merge_big_cap < L.max_candidates && (size_t)B * fxk_merge_hp_words(c->merge_huge_cap) * 4 <= ((size_t)256 << 20))
     FX_A(dev_alloc(c, &b.merge_hp, (size_t)B * fxk_merge_hp_words(c->merge_huge_cap)));
   FX_A(dev_alloc(c, &b.list_desc, L.max_total_keypoints));
   FX_A(dev_alloc(c, &b.s_pts, (size_t)L.max_total_keypoints * P.list_cap));
@@ -1094,7 +862,7 @@ fx_status fx_create(const fx_params *params, const fx_limits *limits, int device
     if (hipHostGetDevicePointer(&dv, h, 0) != hipSuccess) return bail(fail(FX_ERR_HIP, "hipHostGetDevicePointer"));
     b.tier_hint = (uint32_t *)dv;
     c->tier_hint = h;
-    if (const char *e = test_hook("FX_TIER_MIN_GRID")) c->tier_min_grid = (uint32_t)std::max(0, atoi(e));
+    if (const char *e = test_hook("FX_TIER_MIN_GRID")) pc.tier_min_grid = (uint32_t)std::max(0, atoi(e));
   }
   FX_A(dev_alloc(c, &b.clk, 2 * FX_CLK_SLOTS));
   {
@@ -1150,26 +918,35 @@ fx_status fx_create(const fx_params *params, const fx_limits *limits, int device
     return bail(fail(FX_ERR_HIP, "hipStreamCreate"));
   c->stream = c->own_stream;
   {
-    hipError_t ce = fxk_configure(fxk_ring_large_lds_bytes(c->ring_lds_cap, c->ring_lds_cap), fxk_merge_lds_bytes(c->merge_big_cap, params->n_rings),
-                                  c->merge_big_cap < L.max_candidates ? fxk_merge_huge_lds_bytes(c->merge_huge_cap, c->merge_huge_ccap, params->n_rings) : 0,
+    hipError_t ce = fxk_configure(fxk_ring_large_lds_bytes(c->ring_lds_cap, c->ring_lds_cap), fxk_merge_lds_bytes(c->plan_cfg.merge_big_cap, params->n_rings),
+                                  c->plan_cfg.merge_big_cap < L.max_candidates ? fxk_merge_huge_lds_bytes(c->merge_huge_cap, c->merge_huge_ccap, params->n_rings) : 0,
                                   fxk_desc_lds_bytes(P.list_cap < P.dense_min ? P.list_cap : P.dense_min), fxk_gather_lds_bytes(L.max_keypoints));
     if (ce != hipSuccess) return bail(fail(FX_ERR_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(ce)));
   }
   if (hipMemset(b.counters, 0, FX_N_COUNTER_WORDS * sizeof(uint32_t)) != hipSuccess) return bail(fail(FX_ERR_HIP, "hipMemset"));
-  c->front_ok = (uint32_t)params->n_rings <= fxk_front_max_rings();
-  if (const char *e = test_hook("FX_FRONT")) c->front_ok = c->front_ok && atoi(e) != 0;  // 0 = the separate kernels (measurements; tests of those kernels)
+  // ---- the launch policy's view of the context (csrc/fx_launch_plan.h)
+  pc.n_rings = (uint32_t)params->n_rings, pc.estimate_descriptors = P.estimate_descriptors != 0;
+  pc.max_points = L.max_points, pc.max_keypoints = L.max_keypoints, pc.max_total_keypoints = L.max_total_keypoints;
+  pc.max_candidates = L.max_candidates, pc.max_ring_points = L.max_ring_points;
+  pc.list_cap = P.list_cap, pc.dense_min = P.dense_min, pc.gs_slots = P.gs_slots, pc.gsd_slots = P.gsd_slots;
+  pc.merge_hp = b.merge_hp != nullptr, pc.gather_cnt = b.gather_cnt != nullptr;
+  pc.prep_slices_max = fxk_prep_slices_max(), pc.merge_slices_max = fxk_merge_slices_max(), pc.gather_counted_max = fxk_gather_counted_max();
+  pc.front_merge_cap = fxk_front_merge_cap(), pc.gather_kcap = fxk_gather_kcap(), pc.gather_slices_big = fxk_gather_slices_big();
+  pc.dsort_per_cu = fxk_dsort_per_cu(), pc.ddens_per_cu = fxk_ddens_per_cu();
+  pc.front_ok = (uint32_t)params->n_rings <= fxk_front_max_rings();
+  if (const char *e = test_hook("FX_FRONT")) pc.front_ok = pc.front_ok && atoi(e) != 0;  // 0 = the separate kernels (measurements; tests of those kernels)
   // 1: k_front hands every scan to k_front_redo; 2: and that one every ring and merge to the slow tier, k_slow (tests of those two)
-  if (const char *e = test_hook("FX_FRONT_FORCE")) c->front_force = (uint32_t)std::max(0, atoi(e));
-  if (const char *e = test_hook("FX_FRONT_STREAM")) c->front_stream = atoi(e) != 0 ? 1 : 0;
-  if (const char *e = test_hook("FX_FRONT_SPLIT")) c->front_split = std::max(0, std::min(2, atoi(e)));  // (2: k_front_cd with the lean image)
+  if (const char *e = test_hook("FX_FRONT_FORCE")) pc.front_force = (uint32_t)std::max(0, atoi(e));
+  if (const char *e = test_hook("FX_FRONT_STREAM")) pc.front_stream = atoi(e) != 0 ? 1 : 0;
+  if (const char *e = test_hook("FX_FRONT_SPLIT")) pc.front_split = std::max(0, std::min(2, atoi(e)));  // (2: k_front_cd with the lean image)
   if (const char *e = test_hook("FX_FAIL_AFTER_ENQUEUE")) c->fail_after = (uint32_t)std::max(0, atoi(e));
-  if (const char *e = test_hook("FX_SKIP_EMPTY")) c->skip_mask = (uint32_t)std::max(0, atoi(e));
-  if (const char *e = test_hook("FX_DENSE_SLOW")) c->dense_force = atoi(e) != 0 ? 1 : 0;
-  if (const char *e = test_hook("FX_PREP_SLICES")) c->prep_slices = std::max(1, atoi(e));
-  if (const char *e = test_hook("FX_MERGE_SLICES")) c->merge_slices = std::max(1, atoi(e));
-  if (const char *e = test_hook("FX_GATHER_COUNTED")) c->gather_slices = std::max(1, atoi(e));
+  if (const char *e = test_hook("FX_SKIP_EMPTY")) pc.skip_mask = (uint32_t)std::max(0, atoi(e));
+  if (const char *e = test_hook("FX_DENSE_SLOW")) pc.dense_force = atoi(e) != 0 ? 1 : 0;
+  if (const char *e = test_hook("FX_PREP_SLICES")) pc.prep_slices = std::max(1, atoi(e));
+  if (const char *e = test_hook("FX_MERGE_SLICES")) pc.merge_slices = std::max(1, atoi(e));
+  if (const char *e = test_hook("FX_GATHER_COUNTED")) pc.gather_slices = std::max(1, atoi(e));
   if (const char *e = test_hook("FX_CSR_FULL_ROWS")) c->csr_full_rows = atoi(e) != 0 ? 1u : 0u;
-  if (c->front_ok) {
+  if (pc.front_ok) {
     hipError_t ce = fxk_configure_front();
     if (ce != hipSuccess) return bail(fail(FX_ERR_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(ce)));
   }
@@ -1214,7 +991,7 @@ fx_status fx_get_stream(fx_ctx *c, void **hip_stream) {
 }
 fx_status fx_set_batches_in_flight(fx_ctx *c, uint32_t n) {
   if (!c) return fail(FX_ERR_INVALID_ARG, "null ctx");
-  c->batches_in_flight = n ? n : 1u;
+  c->plan_cfg.batches_in_flight = n ? n : 1u;
   if (!c->graphs.empty()) {  // (captured grids are fixed: graphs are rebuilt with the new ones — once no replay of an old one is still running)
     FX_HIP(hipSetDevice(c->device));
     FX_HIP(hipStreamSynchronize(c->stream));
@@ -1279,7 +1056,7 @@ fx_status fx_get_timings(fx_ctx *c, uint32_t back, fx_timings *t) {
 fx_status fx_get_stage_bytes(fx_ctx *c, fx_stage_bytes *out) {
   if (!c || !out) return fail(FX_ERR_INVALID_ARG, "null argument");
   std::memset(out, 0, sizeof(*out));
-  const uint32_t B = c->last_batch;
+  const uint32_t B = c->plan_state.last_batch;
   if (!B) return FX_OK;
   FX_HIP(hipSetDevice(c->device));
   FX_HIP(hipStreamSynchronize(c->stream));
@@ -1330,7 +1107,7 @@ fx_status fx_get_stage_bytes(fx_ctx *c, fx_stage_bytes *out) {
   rd[2] = 16.0 * n_ring, wr[2] = 20.0 * n_rc + 20.0 * n_mem;                   // ring tiers: ring points; candidates + sizes, members + their candidate
   rd[3] = 0, wr[3] = 0;                                                         // (the larger ring tiers' share is counted with the first)
   rd[4] = 20.0 * n_rc + 20.0 * n_mem, wr[4] = 24.0 * nc + 20.0 * nk + 20.0 * nkpc;  // merge: candidates, members; keypoints_full + maps, keypoints, keypoint_cloud
-  if (c->front_last) {  // k_front: the scan in; ~cloud, near bits, ring counts, keypoints_full + maps, keypoints, keypoint_cloud out — no intermediates
+  if (c->plan_state.front_last) {  // k_front: the scan in; ~cloud, near bits, ring counts, keypoints_full + maps, keypoints, keypoint_cloud out — no intermediates
     wr[0] += wr[4];
     for (int i = 1; i <= 4; ++i) rd[i] = wr[i] = 0;
   }
@@ -1437,8 +1214,8 @@ fx_status fx_process_batch(fx_ctx *c, const fx_scan_desc *scans, uint32_t batch,
     FX_HIP(hipMemsetAsync(c->buf.slow_state, 0, (size_t)L.max_batch * sizeof(uint32_t), s));  // (the slow tier's list markers: k_slow clears what it has done)
     FX_HIP(hipMemsetAsync(c->buf.ring_pending, 0, (size_t)L.max_batch * (((size_t)c->params.n_rings + 31) / 32) * sizeof(uint32_t), s));
     FX_HIP(hipStreamSynchronize(s));  // (the hints are host memory the device writes: nothing of the failed batch may land after the reset)
-    for (int i = 0; i < FX_N_HINTS; ++i) c->tier_hint[i] = 0xffffffffu, c->hint_hold[i] = 0xffffffffu, c->hint_age[i] = 0;
-    c->front_pause = 0;
+    for (int i = 0; i < FX_N_HINTS; ++i) c->tier_hint[i] = FX_HINT_UNKNOWN;
+    c->plan_state.reset();
     c->state_suspect = false;
   }
   struct Suspect {  // armed from the first launch to the successful return
@@ -1453,22 +1230,14 @@ fx_status fx_process_batch(fx_ctx *c, const fx_scan_desc *scans, uint32_t batch,
   const FxDevParams &P = c->dp;
   const FxBuffers &B = c->buf;
   const bool prof = c->profiling;
-  // front kernel or separate kernels (see fx_ctx::front_pause): tier_hint[6] is what the last COMPLETED batch of this context
-  // handed to k_front_redo (with batches in flight: an older batch's count, possibly of another size — this decides speed
-  // only, never a result)
-  bool front = c->front_ok;
-  if (front && c->front_pause) {
-    --c->front_pause;
-    front = false;
-  } else if (front && !c->front_force && c->front_last && c->tier_hint[6] != 0xffffffffu && c->tier_hint[6] > (c->last_batch + 7u) / 8u) {
-    c->front_pause = fx_ctx::front_retry;
-    front = false;
-  }
-  if (!prof && !c->debug_sync && batch && batch <= c->graph_max_batch && s != nullptr)
-    FX_TRY(launch_graph(c, s, batch, front));
+  // what the last COMPLETED batch of this context left for the rarely used tiers (with batches in flight: an older batch's
+  // counts, possibly of another size — they decide speed only, never a result), read once
+  uint32_t hints[FX_N_HINTS];
+  for (int i = 0; i < FX_N_HINTS; ++i) hints[i] = c->tier_hint[i];
+  if (!prof && !c->debug_sync && batch && batch <= c->graph_max_batch && s != nullptr)  // (a graph replays a plan made at its capture: only the front is decided per batch)
+    FX_TRY(launch_graph(c, s, batch, fx_plan_front(c->plan_cfg, &c->plan_state, hints[FX_HINT_REDO_SCANS], batch)));
   else
-    FX_TRY(enqueue_stages(c, s, batch, prof, front));
-  c->front_last = front;
+    FX_TRY(enqueue_stages(c, s, batch, prof, fx_plan_batch(c->plan_cfg, &c->plan_state, hints, batch, false)));
 #ifdef FX_TEST_HOOKS
   if (c->fail_after && c->batch_seq + 1 == c->fail_after) {  // a failure after the kernels went out
     ++c->batch_seq;
@@ -1477,7 +1246,6 @@ fx_status fx_process_batch(fx_ctx *c, const fx_scan_desc *scans, uint32_t batch,
 #endif
   if (prof) ++c->ev_count;
   ++c->batch_seq;
-  c->last_batch = batch;
 
   // ---- view
   std::memset(out, 0, sizeof(*out));
@@ -1681,7 +1449,7 @@ fx_status fx_debug_tier_hints(fx_ctx *c, uint32_t *out /* FX_N_HINTS = 8 words *
   return FX_OK;
 }
 // Diagnostic: 1 when the last batch went through the fused front kernel (k_front), 0 when through the separate kernels.
-int fx_debug_front(fx_ctx *c) { return c && c->front_last ? 1 : 0; }
+int fx_debug_front(fx_ctx *c) { return c && c->plan_state.front_last ? 1 : 0; }
 // Diagnostic: the work-list counters of the last batch (rings / scans / keypoint rows deferred to larger tiers).
 fx_status fx_debug_counters(fx_ctx *c, uint32_t *out8 /* 16 words */) {
   if (!c || !out8) return fail(FX_ERR_INVALID_ARG, "null argument");
@@ -1725,7 +1493,7 @@ fx_status fx_debug_stamps_raw(fx_ctx *c, unsigned long long *out4096) {
 fx_status fx_pack_keypoint_records(fx_ctx *c, void *dst_device, uint32_t rec_keypoints) {
   if (!c || !dst_device || !rec_keypoints) return fail(FX_ERR_INVALID_ARG, "null argument");
   FX_HIP(hipSetDevice(c->device));
-  if (c->last_batch) fxk_pack_kp_records(c->stream, c->dp, c->buf, c->last_batch, dst_device, rec_keypoints);
+  if (c->plan_state.last_batch) fxk_pack_kp_records(c->stream, c->dp, c->buf, c->plan_state.last_batch, dst_device, rec_keypoints);
   FX_HIP(hipGetLastError());
   return FX_OK;
 }
@@ -1737,8 +1505,8 @@ fx_status fx_pack_keypoint_block(fx_ctx *c, void *dst_device, uint32_t max_scans
   FX_HIP(hipSetDevice(c->device));
   // a workgroup a scan up to four a CU (the block's zero tail is dealt by stride; an empty batch — kp_offset[0] is 0 — gives
   // the empty block)
-  const uint32_t grid = std::max(1u, std::min(c->last_batch, 4u * (uint32_t)c->n_cu));
-  fxk_pack_kp_block(c->stream, c->dp, c->buf, c->last_batch, dst_device, max_scans, max_total_keypoints, grid);
+  const uint32_t grid = std::max(1u, std::min(c->plan_state.last_batch, 4u * c->plan_cfg.n_cu));
+  fxk_pack_kp_block(c->stream, c->dp, c->buf, c->plan_state.last_batch, dst_device, max_scans, max_total_keypoints, grid);
   FX_HIP(hipGetLastError());
   return FX_OK;
 }
@@ -1786,7 +1554,7 @@ fx_status fx_splice_blocks(fx_ctx *c, const fx_splice_source *a, const fx_splice
   A.dst_kp = (uint32_t *)dst_kp, A.dst_max_scans = dst_max_scans, A.dst_max_total = dst_max_total;
   A.dst_csr = (uint32_t *)dst_csr, A.dst_max_rows = dst_max_rows, A.dst_cap = dst_cap;
   A.plan = (uint32_t *)c->splice_scratch.d;
-  FX_HIP(fxk_splice(c->stream, A, 8u * (uint32_t)c->n_cu));
+  FX_HIP(fxk_splice(c->stream, A, 8u * c->plan_cfg.n_cu));
   return FX_OK;
 }
 
@@ -2638,7 +2406,7 @@ fx_status fx_unpack_pointcloud2(fx_ctx *c, const void *data_device, uint32_t n_p
   FX_HIP(hipSetDevice(c->device));
   if (n_points)
     fxk_unpack_pc2(c->stream, data_device, n_points, lay->point_step, lay->offset_x, lay->offset_y, lay->offset_z,
-                   lay->offset_intensity, lay->is_bigendian, dst_device_xyzi, (uint32_t)c->n_cu * 8u);
+                   lay->offset_intensity, lay->is_bigendian, dst_device_xyzi, c->plan_cfg.n_cu * 8u);
   FX_HIP(hipGetLastError());
   return FX_OK;
 }
@@ -2646,7 +2414,7 @@ fx_status fx_unpack_pointcloud2(fx_ctx *c, const void *data_device, uint32_t n_p
 fx_status fx_pack_pointxyzi(fx_ctx *c, uint32_t which, uint32_t scan, void *dst_device, uint32_t capacity_points,
                             uint32_t *n_points_out) {
   if (!c || !dst_device || !n_points_out) return fail(FX_ERR_INVALID_ARG, "null argument");
-  if (scan >= c->last_batch) return fail(FX_ERR_INVALID_ARG, "scan index outside the last batch");
+  if (scan >= c->plan_state.last_batch) return fail(FX_ERR_INVALID_ARG, "scan index outside the last batch");
   if (((uintptr_t)dst_device % 16) != 0) return fail(FX_ERR_INVALID_ARG, "dst must be 16-byte aligned");
   FX_HIP(hipSetDevice(c->device));
   const FxBuffers &B = c->buf;
@@ -2663,7 +2431,7 @@ fx_status fx_pack_pointxyzi(fx_ctx *c, uint32_t which, uint32_t scan, void *dst_
   FX_HIP(hipMemcpyAsync(&n, cnt, 4, hipMemcpyDeviceToHost, c->stream));
   FX_HIP(hipStreamSynchronize(c->stream));
   if (n > capacity_points) return fail(FX_ERR_TOO_LARGE, "destination too small for the cloud");
-  if (n) fxk_pack_xyzi32(c->stream, src, n, dst_device, (uint32_t)c->n_cu * 4u);
+  if (n) fxk_pack_xyzi32(c->stream, src, n, dst_device, c->plan_cfg.n_cu * 4u);
   FX_HIP(hipGetLastError());
   *n_points_out = n;
   return FX_OK;
@@ -2672,7 +2440,7 @@ fx_status fx_pack_pointxyzi(fx_ctx *c, uint32_t which, uint32_t scan, void *dst_
 fx_status fx_pack_features(fx_ctx *c, void *dst_device, uint32_t capacity_records) {
   if (!c || !dst_device) return fail(FX_ERR_INVALID_ARG, "null argument");
   FX_HIP(hipSetDevice(c->device));
-  fxk_pack_features(c->stream, c->dp, c->buf, c->last_batch, dst_device, capacity_records, (uint32_t)c->n_cu * 8u);
+  fxk_pack_features(c->stream, c->dp, c->buf, c->plan_state.last_batch, dst_device, capacity_records, c->plan_cfg.n_cu * 8u);
   FX_HIP(hipGetLastError());
   return FX_OK;
 }

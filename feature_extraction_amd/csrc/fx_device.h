@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/fx.h"
+#include "fx_launch_plan.h"  // FX_N_HINTS and the names of tier_hint[]'s slots (FxHint)
 
 // One scan of the batch as the kernels see it.
 struct FxScanMeta {
@@ -500,7 +501,6 @@ struct FxSpliceArgs {
   uint32_t *plan;               // [FX_SPLICE_PLAN_WORDS]
 };
 #define FX_TRACK_NONE 0xffffffffu
-#define FX_N_HINTS 8   // tier_hint[]: 0 / 1 rings handed to the second run tier / the workgroup tier (largest XCD class), 2 big merges, 3 huge merges, 4 dense rows, 5 dense support points, 6 scans k_front handed to k_front_redo, 7 scans handed to the slow tier (k_slow)
 #define FX_CNT_QPOOL 32   // counters[32]: entries of the dense tier's query pool in use
 #define FX_CNT_LARGE2 16  // counters[16 + c]: rings of XCD class c the second run tier hands to the workgroup tier
 #define FX_CNT_LARGE 24  // counters[24 + c]: ... to the large tier

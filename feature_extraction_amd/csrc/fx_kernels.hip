@@ -18,11 +18,13 @@
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <math.h>
+#include <assert.h>
 #include <type_traits>
 #include <algorithm>
 
 #include "fx_device.h"
 #include "fx_sort_replay.h"
+#include "fx_launch.h"
 #include "../../include/fx.h"
 
 #pragma clang fp contract(off)
@@ -4096,12 +4098,12 @@ __device__ __forceinline__ void offsets_body(const FxDevParams &P, const FxBuffe
     // CU's LDS waits for 256 CUs to drain, in the way of the other batches in flight
     uint32_t l1 = 0, l2 = 0;
     for (uint32_t c = 0; c < 8u; ++c) l1 = max(l1, B.counters[FX_CNT_LARGE + c]), l2 = max(l2, B.counters[FX_CNT_LARGE2 + c]);
-    B.tier_hint[0] = l1;
-    B.tier_hint[1] = l2;
-    B.tier_hint[2] = B.counters[1];
-    B.tier_hint[3] = B.counters[9];
-    B.tier_hint[6] = B.counters[FX_CNT_REDO];  // scans k_front handed to k_front_redo (which has read the count by now)
-    B.tier_hint[7] = B.counters[FX_CNT_REDO + 1];  // scans handed to the slow tier (k_slow has read the count by now)
+    B.tier_hint[FX_HINT_RINGS_FIRST] = l1;
+    B.tier_hint[FX_HINT_RINGS_SECOND] = l2;
+    B.tier_hint[FX_HINT_BIG_MERGES] = B.counters[1];
+    B.tier_hint[FX_HINT_HUGE_MERGES] = B.counters[9];
+    B.tier_hint[FX_HINT_REDO_SCANS] = B.counters[FX_CNT_REDO];  // scans k_front handed to k_front_redo (which has read the count by now)
+    B.tier_hint[FX_HINT_SLOW_SCANS] = B.counters[FX_CNT_REDO + 1];  // scans handed to the slow tier (k_slow has read the count by now)
     B.counters[FX_CNT_REDO] = 0u;
     B.counters[FX_CNT_REDO + 1] = 0u;
     B.clk[2 * clk_next] = ~0ull;  // the clock slot the next batch's first kernel stamps
@@ -5518,8 +5520,8 @@ static_assert(FX_DSLOW_T == FX_WG && FX_DESC_WG_FAST_T == FX_WG, "k_desc's four 
 extern "C" __global__ __launch_bounds__(FX_WG, FX_GROUP_OCC) void k_desc(FxDevParams P, FxBuffers B, uint32_t batch, uint32_t cap,
                                                                           uint32_t n_wg, uint32_t n_wave, uint32_t n_dslow) {
   if (blockIdx.x == 0 && threadIdx.x == 0) {  // (the support gather, which fills the dense tier's row list, has completed)
-    B.tier_hint[4] = B.counters[6];
-    B.tier_hint[5] = B.counters[13];
+    B.tier_hint[FX_HINT_DENSE_ROWS] = B.counters[6];
+    B.tier_hint[FX_HINT_DENSE_POINTS] = B.counters[13];
   }
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
   const uint32_t n_mid = n_wg + n_wave, n_all = gridDim.x - n_dslow;
@@ -6859,9 +6861,9 @@ void fxk_bucket_sliced(hipStream_t s, const FxDevParams &P, const FxBuffers &B, 
   hipLaunchKernelGGL(k_bucket_sliced, dim3(slices, batch), dim3(FX_BUCKET_T), lds, s, P, B, el0, inv_step, clk_next);
 }
 void fxk_bucket(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, float el0, float inv_step,
-                uint32_t clk_next) {
+                uint32_t clk_next, uint32_t many_rings) {
   const size_t lds = (48 + (size_t)P.n_rings * (2 + FX_BUCKET_NW) + 1) * 4;
-  if (P.n_rings > 24)
+  if (many_rings)
     hipLaunchKernelGGL(k_bucket_many, dim3(batch), dim3(FX_BUCKET_T), lds, s, P, B, el0, inv_step, clk_next);
   else
     hipLaunchKernelGGL(k_bucket, dim3(batch), dim3(FX_BUCKET_T), lds, s, P, B, el0, inv_step, clk_next);
@@ -6873,7 +6875,6 @@ void fxk_rings_runs2(hipStream_t s, const FxDevParams &P, const FxBuffers &B, ui
 }
 void fxk_rings_runs(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, uint32_t max_pts, uint32_t grid) {
   const uint32_t n_items = batch * (uint32_t)P.n_rings;
-  if (grid > n_items) grid = (n_items + 7) / 8 * 8;
   hipLaunchKernelGGL(k_rings_runs, dim3(grid), dim3(64), fxk_ring_runs_lds_bytes(), s, P, B, max_pts, n_items);
 }
 void fxk_merge_small(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, uint32_t cap) {
@@ -6891,7 +6892,9 @@ uint32_t fxk_merge_slices_max(void) { return FX_MERGE_SLICES; }
 void fxk_merge_huge_split(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t cap, uint32_t ccap, uint32_t grid, uint32_t slices) {
   const size_t lds = fxk_merge_huge_lds_bytes(cap, ccap, P.n_rings);
   hipLaunchKernelGGL(k_merge_huge_a, dim3(grid), dim3(FX_MBIG_T), lds, s, P, B, cap, ccap);
-  hipLaunchKernelGGL(k_merge_huge_b, dim3(std::min(slices, (uint32_t)FX_MERGE_SLICES), grid), dim3(FX_MBIG_T), lds, s, P, B, cap, ccap);
+  const uint32_t slices_max = FX_MERGE_SLICES;
+  assert(slices <= slices_max);  // (FxBuffers::merge_hp has a scan's roots for that many slices)
+  hipLaunchKernelGGL(k_merge_huge_b, dim3(slices, grid), dim3(FX_MBIG_T), lds, s, P, B, cap, ccap);
   hipLaunchKernelGGL(k_merge_huge_c, dim3(grid), dim3(FX_MBIG_T), lds, s, P, B, cap, ccap);
 }
 // the fused front kernel takes sensors of up to FX_FRONT_RMAX rings (scans that do not fit its tables go on to k_front_redo)
@@ -6912,8 +6915,8 @@ size_t fxk_slow_words(uint32_t max_ring_points, uint32_t max_candidates, uint32_
 // (also computes the batch's keypoint offsets: its last workgroup, see k_slow)
 void fxk_slow(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t huge_ccap, uint32_t grid, uint32_t batch, uint32_t clk_next) {
   const size_t lds = std::max((size_t)SegCfg<FX_SLOW_T>::kWords, (size_t)FX_MERGE_HEAD + ((2 * ((size_t)P.n_rings + 1) + 3) & ~(size_t)3)) * 4;
-  const uint32_t g = std::max(1u, std::min(grid, P.gs_slots));
-  hipLaunchKernelGGL(k_slow, dim3(g), dim3(FX_SLOW_T), lds, s, P, B, huge_ccap, batch, clk_next);
+  assert(grid >= 1u && grid <= P.gs_slots);  // (a scratch region each)
+  hipLaunchKernelGGL(k_slow, dim3(grid), dim3(FX_SLOW_T), lds, s, P, B, huge_ccap, batch, clk_next);
 }
 void fxk_front_ab(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, float near_margin, float el0, float inv_step,
                   uint32_t clk_slot, uint32_t force_redo) {
@@ -6935,36 +6938,38 @@ hipError_t fxk_configure_front(void) {
   if (e != hipSuccess) return e;
   return hipFuncSetAttribute((const void *)k_front_redo, hipFuncAttributeMaxDynamicSharedMemorySize, (int)front_lds_bytes());
 }
-// one workgroup per scan when the batch fills the GPU anyway (it is then the only writer of the scan's lists: no
-// global atomics, and it settles the RNG ordinals itself), several when it does not (streaming)
 #ifndef FX_GATHER_SLICES
 #define FX_GATHER_SLICES 1u
 #endif
-// One workgroup per scan (the sole writer of the scan's lists: no global atomics) from 64 scans on — 256 threads when
-// the batch alone fills the GPU, 1024 (k_gather_wide) when it does not; only a handful of scans (streaming) is split
-// over several workgroups per scan.
-uint32_t fxk_gather_slices(uint32_t batch) { return batch >= 64u ? FX_GATHER_SLICES : (batch >= 16u ? 4u : 16u); }
+uint32_t fxk_gather_slices_big(void) { return FX_GATHER_SLICES; }  // workgroups a scan of k_gather from 64 scans on
+uint32_t fxk_gather_kcap(void) { return FX_GATHER_KCAP; }
 #define FX_GATHER_COUNTED_MAX 16u
 uint32_t fxk_gather_counted_max(void) { return FX_GATHER_COUNTED_MAX; }
-// counted: > 1 = that many workgroups a scan in two launches (a counting pass, then the scatter with every slice's list
-// positions known: gather_body's MODE) — batches of few big scans; needs FxBuffers::gather_cnt.  Returns the workgroups a scan
-// the lists were written by (> 1: the RNG ordinals are k_rng_ord's).
-uint32_t fxk_gather(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, float box_margin, uint32_t counted) {
-  const uint32_t slices = fxk_gather_slices(batch);
+// per_scan workgroups a scan of the planned kind (csrc/fx_launch_plan.h).  One workgroup per scan is the only writer of the
+// scan's lists: no global atomics, and it settles the RNG ordinals itself; with several, the RNG ordinals are k_rng_ord's.
+// FX_GATHER_COUNTED: two launches, a counting pass, then the scatter with every slice's list positions known (gather_body's
+// MODE) — batches of few big scans; needs FxBuffers::gather_cnt.
+void fxk_gather(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, float box_margin, FxGatherKind kind, uint32_t per_scan) {
   const size_t lds = (size_t)gather_words(std::min(P.max_keypoints, (uint32_t)FX_GATHER_KCAP), FX_GATHER_T) * 4;
-  if (P.max_keypoints > FX_GATHER_KCAP) {
-    hipLaunchKernelGGL(k_gather_passes, dim3(slices, batch), dim3(FX_GATHER_WIDE_T), (size_t)gather_words(FX_GATHER_KCAP, FX_GATHER_WIDE_T) * 4, s, P, B, box_margin);
-  } else if (counted > 1u && B.gather_cnt) {
-    counted = std::min(counted, (uint32_t)FX_GATHER_COUNTED_MAX);
-    hipLaunchKernelGGL(k_gather_count, dim3(counted, batch), dim3(FX_GATHER_T), lds, s, P, B, box_margin);
-    hipLaunchKernelGGL(k_gather_scatter, dim3(counted, batch), dim3(FX_GATHER_T), lds, s, P, B, box_margin);
-    return counted;
-  } else if (slices == 1 && batch < 1024u) {
-    hipLaunchKernelGGL(k_gather_wide, dim3(1, batch), dim3(FX_GATHER_WIDE_T), (size_t)gather_words(std::min(P.max_keypoints, (uint32_t)FX_GATHER_KCAP), FX_GATHER_WIDE_T) * 4, s, P, B, box_margin);
-  } else {
-    hipLaunchKernelGGL(k_gather, dim3(slices, batch), dim3(FX_GATHER_T), lds, s, P, B, box_margin);
+  const size_t lds_wide = (size_t)gather_words(std::min(P.max_keypoints, (uint32_t)FX_GATHER_KCAP), FX_GATHER_WIDE_T) * 4;
+  const uint32_t kcap = FX_GATHER_KCAP, counted_max = FX_GATHER_COUNTED_MAX;
+  assert((kind == FX_GATHER_PASSES) == (P.max_keypoints > kcap));  // (only the passes instance loops over the LDS tables' capacity)
+  switch (kind) {
+    case FX_GATHER_PASSES:
+      hipLaunchKernelGGL(k_gather_passes, dim3(per_scan, batch), dim3(FX_GATHER_WIDE_T), lds_wide, s, P, B, box_margin);
+      break;
+    case FX_GATHER_COUNTED:
+      assert(B.gather_cnt && per_scan <= counted_max);  // (gather_cnt has a scan's counts for that many slices)
+      hipLaunchKernelGGL(k_gather_count, dim3(per_scan, batch), dim3(FX_GATHER_T), lds, s, P, B, box_margin);
+      hipLaunchKernelGGL(k_gather_scatter, dim3(per_scan, batch), dim3(FX_GATHER_T), lds, s, P, B, box_margin);
+      break;
+    case FX_GATHER_WIDE:
+      hipLaunchKernelGGL(k_gather_wide, dim3(1, batch), dim3(FX_GATHER_WIDE_T), lds_wide, s, P, B, box_margin);
+      break;
+    case FX_GATHER_SLICED:
+      hipLaunchKernelGGL(k_gather, dim3(per_scan, batch), dim3(FX_GATHER_T), lds, s, P, B, box_margin);
+      break;
   }
-  return slices;
 }
 // the descriptor tiers' one launch: n_wg list, n_wave wave, n_group group and n_dslow dense stand-in workgroups (see k_desc); its
 // dynamic LDS is the largest of the tiers' images
@@ -6973,18 +6978,19 @@ void fxk_desc(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t 
   const size_t lds_wave = (size_t)(FX_NWAVE * FX_WAVE_WORDS + FX_TABLE_WORDS) * 4, lds_wg = fxk_desc_lds_bytes(cap);
   const size_t lds_group = (size_t)(FX_NWAVE * FX_GROUPS * FX_GROUP_WORDS + FX_TABLE_WORDS) * 4;
   static_assert((16 + FX_DESC_BINS + 16) * 4 <= (FX_NWAVE * FX_WAVE_WORDS + FX_TABLE_WORDS) * 4, "the dense tier's rows in k_desc's LDS");
-  n_dslow = std::min(n_dslow, P.gsd_slots);  // (a scratch region each)
+  assert(n_dslow <= P.gsd_slots);  // (a scratch region each)
   hipLaunchKernelGGL(k_desc, dim3(n_wg + n_wave + n_group + n_dslow), dim3(FX_WG), std::max({lds_wave, lds_wg, lds_group}), s, P, B, batch, cap,
                      n_wg, n_wave, n_dslow);
 }
 size_t fxk_dense_slow_words(uint32_t max_points) { return ((size_t)FX_DESC_WORDS_PER_POINT * max_points + 3) & ~(size_t)3; }
-// (rows and items are taken by ticket: any grid is correct; the full ones are what is resident at once)
-void fxk_dense(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t n_cu, uint32_t rows, uint32_t items, uint32_t skip) {
-  auto grid = [](uint32_t want, uint32_t full) { return want < full ? (want ? want : 1u) : full; };
-  hipLaunchKernelGGL(k_dense_sort, dim3(grid(rows, n_cu * FX_DSORT_PER_CU)), dim3(FX_DSORT_T), 0, s, P, B);
+uint32_t fxk_dsort_per_cu(void) { return FX_DSORT_PER_CU; }
+uint32_t fxk_ddens_per_cu(void) { return FX_DDENS_PER_CU; }
+// (rows and items are taken by ticket: any grid is correct)
+void fxk_dense(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t sort_grid, uint32_t density_grid, uint32_t finish_grid, uint32_t skip) {
+  hipLaunchKernelGGL(k_dense_sort, dim3(sort_grid), dim3(FX_DSORT_T), 0, s, P, B);
   // (skip: measurement only — a test build's FX_SKIP_EMPTY bits 2 / 3: the tier's share of a step with batches in flight)
-  if (!(skip & 2u)) hipLaunchKernelGGL(k_dense_density, dim3(grid(items, n_cu * FX_DDENS_PER_CU)), dim3(FX_DDENS_T), 0, s, P, B);
-  if (!(skip & 1u)) hipLaunchKernelGGL(k_dense_finish, dim3(grid(rows, n_cu)), dim3(FX_DFIN_T), fxk_dense_finish_lds_bytes(), s, P, B);
+  if (!(skip & 2u)) hipLaunchKernelGGL(k_dense_density, dim3(density_grid), dim3(FX_DDENS_T), 0, s, P, B);
+  if (!(skip & 1u)) hipLaunchKernelGGL(k_dense_finish, dim3(finish_grid), dim3(FX_DFIN_T), fxk_dense_finish_lds_bytes(), s, P, B);
 }
 #ifdef FX_TEST_HOOKS
 extern "C" __global__ __launch_bounds__(FX_WG) void k_test_elevation(const float *xyz, uint32_t n, const double *tab, float *fast, uint8_t *ok,

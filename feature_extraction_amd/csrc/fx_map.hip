@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "fx_device.h"
+#include "fx_launch.h"
 #include "../../include/fx.h"
 
 #define FXMAP_WG 256

@@ -22,6 +22,7 @@
 #include <stdint.h>
 
 #include "fx_device.h"
+#include "fx_launch.h"
 #include "../../include/fx.h"
 
 #define FXMA_WG 256

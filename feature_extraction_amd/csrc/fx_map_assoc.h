@@ -23,15 +23,13 @@
 
 #include "fx_map_consensus.h"
 #include "fx_map_grid.h"
+#include "fx_launch.h"
 #include "fx_scan_query.h"
 
 #define FXA_WG FXC_MAP_WG
 #define FXA_NWAVE FXC_MAP_NWAVE
 #define FXA_NONE 0xffffffffu
 
-extern "C" hipError_t fxk_map_grid_build(hipStream_t s, const FxMapMergeArgs &A);
-extern "C" void fxk_map_assoc_rank(hipStream_t s, const FxMapAssocArgs &S, uint32_t n_blocks);
-extern "C" size_t fxk_map_assoc_scratch(FxMapAssocArgs *S, uint8_t *base, size_t fit_bytes);
 
 namespace fxa {
 struct Rigid {

@@ -7,7 +7,6 @@
 
 #include "fx_map_assoc.h"
 
-extern "C" size_t fxk_map_merge_scratch(FxMapMergeArgs *A, uint8_t *base);
 
 extern "C" __global__ __launch_bounds__(FXA_WG) void k_ma_top(FxMapAssocArgs S, uint32_t n_blocks) {
   __shared__ uint32_t s_w[2 * FXA_NWAVE];

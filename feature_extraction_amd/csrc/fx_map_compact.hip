@@ -33,6 +33,7 @@
 #include <stdint.h>
 
 #include "fx_scan_query.h"
+#include "fx_launch.h"
 #include "../../include/fx.h"
 
 #define FXMC_WG 256

@@ -32,6 +32,7 @@
 
 #include "fx_map_grid.h"
 #include "fx_scan_query.h"
+#include "fx_launch.h"
 #include "../../include/fx.h"
 
 using namespace fxg;
@@ -44,8 +45,6 @@ static_assert(sizeof(fx_localization) == 112 && sizeof(fx_map_expect_options) ==
                   sizeof(fx_map_landmark) == 48 && sizeof(fx_map_header) == 88 && FX_MAP_EXPECT_ST_WORDS * 4 == sizeof(fx_map_expect_result),
               "include/fx.h");
 
-extern "C" hipError_t fxk_map_grid_build(hipStream_t s, const FxMapMergeArgs &A);
-extern "C" size_t fxk_map_merge_scratch(FxMapMergeArgs *A, uint8_t *base);
 
 namespace {
 // a wavefront's sum of v into a state word

@@ -27,6 +27,7 @@
 
 #include "fx_map_constellation.h"
 #include "fx_scan_query.h"
+#include "fx_launch.h"
 #include "../../include/fx.h"
 
 using namespace fxs;
@@ -35,8 +36,6 @@ static_assert(sizeof(fx_map_loop_candidate) == 136 && sizeof(fx_map_find_loop_op
 static_assert(FX_FIND_MAX_QUERY == FXR_MAX_PT, "fx_map_constellation.h");
 static_assert(FX_FIND_ST_WORDS == 8, "fx_device.h");
 
-extern "C" hipError_t fxk_map_grid_build(hipStream_t s, const FxMapMergeArgs &A);
-extern "C" size_t fxk_map_merge_scratch(FxMapMergeArgs *A, uint8_t *base);
 
 namespace {
 #define FXF_NONE 0xffffffffu

@@ -14,6 +14,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "fx_launch.h"
 #include "fx_map_grid.h"
 
 using namespace fxg;

@@ -23,6 +23,7 @@
 #include "fx_map_consensus.h"
 #include "fx_map_grid.h"
 #include "fx_scan_query.h"
+#include "fx_launch.h"
 #include "../../include/fx.h"
 
 using namespace fxc;
@@ -34,8 +35,6 @@ using namespace fxg;
 static_assert(sizeof(fx_localization) == 112 && sizeof(fx_localize_options) == 32 && sizeof(fx_pose) == 48, "include/fx.h");
 static_assert(FX_LOC_MAX_CORR == FXC_MAP_MAX_CORR, "fx_map_consensus.h");
 
-extern "C" hipError_t fxk_map_grid_build(hipStream_t s, const FxMapMergeArgs &A);
-extern "C" size_t fxk_map_merge_scratch(FxMapMergeArgs *A, uint8_t *base);
 
 namespace {
 __device__ __forceinline__ void write_no_fit(fx_localization *out, const fx_pose &prior, uint32_t n_corr, uint32_t flags) {

@@ -22,6 +22,7 @@
 #include <stdint.h>
 
 #include "fx_map_assoc.h"
+#include "fx_launch.h"
 #include "../../include/fx.h"
 
 using namespace fxc;

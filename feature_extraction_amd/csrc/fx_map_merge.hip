@@ -26,11 +26,11 @@
 
 #include "fx_map_grid.h"
 #include "fx_scan_query.h"
+#include "fx_launch.h"
 #include "../../include/fx.h"
 
 using namespace fxg;
 
-extern "C" hipError_t fxk_map_grid_build(hipStream_t s, const FxMapMergeArgs &A);
 
 static_assert(sizeof(fx_map_landmark) == 48 && sizeof(FxMapMergeCand) == 32 && sizeof(fx_map_merge_result) == 16, "include/fx.h");
 

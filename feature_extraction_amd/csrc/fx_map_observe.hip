@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "fx_scan_query.h"
+#include "fx_launch.h"
 #include "../../include/fx.h"
 
 #define FXO_WG 256

@@ -28,6 +28,7 @@
 
 #include "fx_map_constellation.h"
 #include "fx_scan_query.h"
+#include "fx_launch.h"
 #include "../../include/fx.h"
 
 using namespace fxs;
@@ -35,8 +36,6 @@ using namespace fxs;
 static_assert(sizeof(fx_relocalization) == 96 && sizeof(fx_relocalize_options) == 40 && sizeof(fx_pose) == 48, "include/fx.h");
 static_assert(FX_RELOC_MAX_KP == FXR_MAX_PT, "fx_map_constellation.h");
 
-extern "C" hipError_t fxk_map_grid_build(hipStream_t s, const FxMapMergeArgs &A);
-extern "C" size_t fxk_map_merge_scratch(FxMapMergeArgs *A, uint8_t *base);
 
 namespace {
 // the search of scan b

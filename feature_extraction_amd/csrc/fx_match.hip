@@ -24,6 +24,7 @@
 #include <stdint.h>
 
 #include "fx_device.h"
+#include "fx_launch.h"
 #include "../../include/fx.h"
 
 #define FXM_WG 512

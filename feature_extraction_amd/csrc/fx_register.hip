@@ -20,6 +20,7 @@
 
 #include "fx_consensus.h"
 #include "fx_device.h"
+#include "fx_launch.h"
 #include "../../include/fx.h"
 
 using namespace fxc;

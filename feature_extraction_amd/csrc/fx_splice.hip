@@ -26,6 +26,7 @@
 #include <stdint.h>
 
 #include "fx_device.h"
+#include "fx_launch.h"
 #include "../../include/fx.h"
 
 #define FXS_WG 256

@@ -30,6 +30,7 @@
 #include <stdint.h>
 
 #include "fx_scan_query.h"
+#include "fx_launch.h"
 #include "../../include/fx.h"
 
 #define FXT_WG 256
