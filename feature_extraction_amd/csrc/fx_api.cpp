@@ -832,6 +832,7 @@ fx_status fx_create(const fx_params *params, const fx_limits *limits, int device
   FX_A(dev_alloc(c, &b.row_kp, L.max_total_keypoints));
   FX_A(dev_alloc(c, &b.row_xa, L.max_total_keypoints));
   FX_A(dev_alloc(c, &b.wave_desc, L.max_total_keypoints));
+  FX_A(dev_alloc(c, &b.group_desc, (size_t)FX_GROUP_CLASSES * L.max_total_keypoints));
   // dense tier
   FX_A(dev_alloc(c, &b.dense_rows, P.max_dense_rows));
   FX_A(dev_alloc(c, &b.dense_order, (size_t)4 * P.max_dense_rows));
@@ -1464,6 +1465,16 @@ fx_status fx_debug_counters(fx_ctx *c, uint32_t *out8 /* 16 words */) {
     if (runs2) out8[0] += all[FX_CNT_LARGE + k];
     out8[5] += all[(runs2 ? FX_CNT_LARGE2 : FX_CNT_LARGE) + k];
   }
+  return FX_OK;
+}
+
+// Diagnostic: the group rows of the last batch by size class (<= 16, <= 32, <= 64 support points; a dense row without room in the
+// pools counts with the last).
+fx_status fx_debug_group_classes(fx_ctx *c, uint32_t *out3 /* FX_GROUP_CLASSES words */) {
+  if (!c || !out3) return fail(FX_ERR_INVALID_ARG, "null argument");
+  FX_HIP(hipSetDevice(c->device));
+  FX_HIP(hipStreamSynchronize(c->stream));
+  FX_HIP(hipMemcpy(out3, c->buf.counters + FX_CNT_GROUP, FX_GROUP_CLASSES * sizeof(uint32_t), hipMemcpyDeviceToHost));
   return FX_OK;
 }
 

@@ -65,6 +65,8 @@ struct FxScTables {
 #define FX_CNT_SLOW_TICKET 50  // counters[50]: workgroups of k_slow's launch that are done (the last one computes the batch's keypoint offsets and puts it back to 0)
 #define FX_N_COUNTER_WORDS 56
 #define FX_CNT_RUNS2_TICKET 40  // counters[40 + c]: next ring of XCD class c's list for k_rings_runs2
+#define FX_CNT_GROUP 33  // counters[33 + c]: group rows of size class c (FxBuffers::group_desc; 0: <= 16 support points, 1: <= 32, 2: <= 64)
+#define FX_GROUP_CLASSES 3
 #define FX_ATAN_N 64      // table step of k_prep's arctangent: 1 / 64 over [0, 1]
 #define FX_ATAN_DEG 6     // degree of the expansion about a table point (|offset| <= 1 / 128: truncation below 2^-51)
 #define FX_ROW_DIRTY 0xffffffffu
@@ -565,6 +567,7 @@ struct FxBuffers {
   float4 *merge_sorted;   // [B][max_candidates] (x, y, pseudo z, id) in bin order: k_merge_huge's pair tests (allocated only when that tier exists)
   uint32_t *list_desc;    // [max_total_kp]  rows whose list is too long for one wavefront (257 .. dense_min support points)
   uint32_t *wave_desc;    // [max_total_kp]  rows with 65..256 support points (one wavefront each)
+  uint32_t *group_desc;   // [FX_GROUP_CLASSES][max_total_kp]  group rows by size class (16 / 8 / 4 rows a wavefront of k_desc's group workgroups); FX_ROW_DENSE_FAIL rows ride in the widest class's list
   // dense tier (k_dense_*)
   uint32_t *dense_rows;   // [max_dense_rows]  rows of the tier (FX_NONE: no room in the pools, flagged)
   uint32_t *dense_order;  // [4][max_dense_rows]  slots by size class (largest rows first)
@@ -593,7 +596,7 @@ struct FxBuffers {
   unsigned long long *clk;     // [FX_CLK_SLOTS][2] k_prep's first start / last end on the device's constant-rate clock, by batch
   unsigned long long *stamps;  // [32] diagnostic build only (-DFX_STAMPS)
   uint32_t *tier_hint;    // [FX_N_HINTS], pinned HOST memory: the batch's counts of work for the rarely used tiers, which the host sizes the next batch's launches of those tiers by (k_offsets, k_desc write them; grid sizes only — never what is computed)
-  uint32_t *counters;     // [FX_N_COUNTER_WORDS]: 16.. / 24.. rings handed on per XCD class; 1 big_merge, 4 list_desc, 6 dense rows (2 / 3 / 7 / 10: by size class), 8 wave_desc, 9 huge_merge, 12 key pool used, 13 sorted pool used, 14 density items, 15 / 11 / 5 / 0 tickets of k_dense_density / sort / finish_s / finish_l
+  uint32_t *counters;     // [FX_N_COUNTER_WORDS]: 16.. / 24.. rings handed on per XCD class; 1 big_merge, 4 list_desc, 6 dense rows (2 / 3 / 7 / 10: by size class), 8 wave_desc, 33 / 34 / 35 group_desc by size class, 9 huge_merge, 12 key pool used, 13 sorted pool used, 14 density items, 15 / 11 / 5 / 0 tickets of k_dense_density / sort / finish_s / finish_l
 };
 
 #endif

@@ -4258,16 +4258,25 @@ __device__ __forceinline__ unsigned long long sc3d_key(uint32_t bin, float d2, u
 // complete before k_desc — all tiers in one launch — starts, and no workgroup of that launch waits for another.
 // (the tiers' capacities are defined here, once: the classification needs them ahead of the tiers themselves)
 #ifndef FX_GROUP_CAP
-#define FX_GROUP_CAP 64   // support points a group row holds (the group tier: FX_GLANES lanes a row, four slots a lane)
+#define FX_GROUP_CAP 64   // support points a group row holds (the group tier: 4, 8 or 16 lanes a row by its size class, four slots a lane)
 #endif
 #ifndef FX_WAVE_CAP
 #define FX_WAVE_CAP 192  // support points a wave row holds (multiples of 64; measured 128 / 192 / 256 / 320: the wave and list tiers' launch 0.118 / 0.099 / 0.119 / 0.153 ms)
 #endif
+// The group tier's size classes — the rule's one statement, which the classification and the tier (desc_group_body<LANES>) both
+// call: a row of class c gets 4 << c lanes, four support slots a lane, so rows of up to 16 / 32 / 64 support points run 16 / 8 /
+// 4 to a wavefront.  (Half of the VLP-16 bench's rows have 8 support points or fewer; at four rows a wavefront, whatever they
+// hold, most of a trip's 256 slots were empty and every trip still paid its fixed chain: profiles/desc_group_classes.md.)
+__host__ __device__ constexpr uint32_t group_class_lanes(uint32_t c) { return 4u << c; }
+__host__ __device__ constexpr uint32_t group_class_cap(uint32_t c) { return 4u * group_class_lanes(c); }
+__device__ __forceinline__ uint32_t group_class(uint32_t nS) { return nS <= group_class_cap(0) ? 0u : (nS <= group_class_cap(1) ? 1u : 2u); }
+static_assert(group_class_cap(FX_GROUP_CLASSES - 1) == FX_GROUP_CAP, "the widest class holds every group row");
 // One row a lane (has: this lane holds one), called by whole wavefronts: too long for a group -> wavefront rows (<= FX_WAVE_CAP
 // support points), list rows (<= dense_min), and the dense tier beyond that — also every row whose list overflowed its list_cap
-// slots (the rest of it sits in the scan's overflow region).  The rows of a wavefront draw their list positions together: one
-// atomic per list and wavefront instead of one (dense rows: three) per row — on config 3 half of the 40 000 rows of a batch are
-// handed on, and their atomics, all on two cache lines of counters, went through the L2 one after the other.
+// slots (the rest of it sits in the scan's overflow region); short enough: the group workgroups' list of its size class.  The
+// rows of a wavefront draw their list positions together: one atomic per list and wavefront instead of one (dense rows: three)
+// per row — on config 3 half of the 40 000 rows of a batch are handed on, and their atomics, all on two cache lines of
+// counters, went through the L2 one after the other.
 // (kp_nbrs of a row without room in the pools is set by the group workgroup that fills the row with NaN: here the word may still
 //  hold the has-a-neighbour flag the RNG ordinals are counted from.)
 __device__ __forceinline__ void classify_rows(const FxDevParams &P, const FxBuffers &B, bool has, uint32_t row, uint32_t scan, uint32_t nS) {
@@ -4284,11 +4293,7 @@ __device__ __forceinline__ void classify_rows(const FxDevParams &P, const FxBuff
     b0 = (uint32_t)__shfl((int)b0, (int)first, 64);
     return mine ? b0 + before : 0u;
   };
-  const unsigned long long m_list = __ballot(to_list), m_wave = __ballot(to_wave), m_dense = __ballot(to_dense);
-  const uint32_t p_list = draw(m_list, to_list, 4u, (uint32_t)__popcll(m_list), lanes_below(m_list));
-  const uint32_t p_wave = draw(m_wave, to_wave, 8u, (uint32_t)__popcll(m_wave), lanes_below(m_wave));
-  if (to_list) B.list_desc[p_list] = row;
-  if (to_wave) B.wave_desc[p_wave] = row;
+  const unsigned long long m_dense = __ballot(to_dense);
   uint32_t cls_row = to_list ? FX_ROW_LIST : (to_wave ? FX_ROW_WAVE : (to_dense ? FX_ROW_DENSE : FX_ROW_GROUP));
   if (m_dense) {  // (wave-uniform)
     // a slot in the dense-row list and nS entries of the sorted pool (k_dense_sort fills them)
@@ -4320,6 +4325,30 @@ __device__ __forceinline__ void classify_rows(const FxDevParams &P, const FxBuff
     }
   }
   if (has) B.row_class[row] = (uint8_t)cls_row;
+  // The list rows, the wave rows and the group workgroups' rows by size class (a dense row without room in the pools goes with
+  // the widest: they clear it, fill it with NaN and leave it dirty; row_class keeps its five values, the size class lives in the
+  // lists alone) draw their positions in ONE instruction: lane j adds list j's count to its counter, so the wavefront waits for
+  // one round trip to the L2, not for five one after the other (the three class lists drawn one by one behind the other two
+  // made k_gather 11 us longer on the VLP-16 bench: profiles/desc_group_classes.md).
+  const bool to_group = has && (cls_row == FX_ROW_GROUP || cls_row == FX_ROW_DENSE_FAIL);
+  const uint32_t gcls = cls_row == FX_ROW_GROUP ? group_class(nS) : FX_GROUP_CLASSES - 1u;
+  constexpr uint32_t kLists = 2u + FX_GROUP_CLASSES;
+  const uint32_t my_list = to_list ? 0u : (to_wave ? 1u : (to_group ? 2u + gcls : kLists));  // (kLists: none — the dense tier's, above)
+  unsigned long long m_mine = 0ull;
+  uint32_t n_lane = 0, c_lane = 0;  // lane j < kLists: rows for list j, its counter
+#pragma unroll
+  for (uint32_t j = 0; j < kLists; ++j) {
+    const unsigned long long m_j = __ballot(my_list == j);
+    if (my_list == j) m_mine = m_j;
+    if (lane == j) n_lane = (uint32_t)__popcll(m_j), c_lane = j == 0u ? 4u : (j == 1u ? 8u : FX_CNT_GROUP + (j - 2u));
+  }
+  uint32_t b0 = 0;
+  if (n_lane) b0 = atomicAdd(&B.counters[c_lane], n_lane);
+  const uint32_t pos = (uint32_t)__shfl((int)b0, (int)min(my_list, kLists - 1u), 64) + lanes_below(m_mine);
+  if (my_list < kLists) {
+    uint32_t *dst = my_list == 0u ? B.list_desc : (my_list == 1u ? B.wave_desc : B.group_desc + (size_t)(my_list - 2u) * P.max_total_kp);
+    dst[pos] = row;
+  }
 }
 
 // ---------------------------------------------------------------- k_gather
@@ -4920,99 +4949,117 @@ __device__ __forceinline__ void desc_wave_body(const FxDevParams &P, const FxBuf
 // ---------------------------------------------------------------- group tier (runs inside k_desc)
 // Most keypoints have a small support set (median < 10 points on the VLP-16 scenes, 90 % < 64):
 // a whole wavefront per keypoint leaves its lanes idle and pays the per-keypoint latency 64-wide.
-// Here a wavefront works on FX_GROUPS keypoints at once, FX_GLANES lanes each (fp32 angles, same
-// exactness contract as the wavefront tier).  Rows with more than FX_GROUP_CAP support points are the other tiers'
-// (classify_rows): the workgroups here stride over all rows and skip those.
-#ifndef FX_GLANES
-#define FX_GLANES 16
-#endif
-#define FX_GROUPS (64 / FX_GLANES)
+// Here a wavefront works on 64 / LANES keypoints at once, LANES lanes and 4 LANES support slots each (fp32 angles, same
+// exactness contract as the wavefront tier): LANES = 4, 8 or 16 by the row's size class (group_class, above), so that a trip's
+// 256 slots hold sixteen rows of up to 16 support points, eight of up to 32 or four of up to 64.  Rows with more than
+// FX_GROUP_CAP support points are the other tiers'.  The rows come from the classes' work lists (classify_rows; B.group_desc).
 // (FX_GROUP_CAP: defined with the row classes, above)
-#define FX_GROUP_WORDS (FX_GROUP_CAP * 8 + 8)  // per group: support float4, keys, weights, indices + 8 counters
+#define FX_GROUP_SLOTS 256                            // support slots a wavefront: four a lane, whatever the class
+#define FX_GROUP_WAVE_WORDS (FX_GROUP_SLOTS * 8 + 32)  // per wavefront: support float4, keys, weights, indices a slot + 2 counters a group (at most 16 groups)
+static_assert(FX_GROUP_CAP == 64 && FX_GROUP_SLOTS == 4 * FX_GROUP_CAP, "the group tier's LDS image and the 64-slot bin record");
 #ifndef FX_GROUP_UNROLL
 #define FX_GROUP_UNROLL 8
 #endif
 #ifndef FX_GROUP_OCC
 #define FX_GROUP_OCC 4
 #endif
-// (workgroup bid of the nblk of k_desc's launch that stride over all rows and take the group rows among them)
-__device__ __forceinline__ void desc_group_body(const FxDevParams &P, const FxBuffers &B, uint32_t batch, uint32_t *smem, uint32_t bid,
-                                                uint32_t nblk) {
+// (workgroup bid of the nblk group workgroups of k_desc's launch, which share the items of the class's list: an item is one
+//  trip's worth of rows, 64 / LANES consecutive list entries; T: the 3DSC tables in LDS)
+template <uint32_t LANES>
+__device__ __forceinline__ uint32_t desc_group_body(const FxDevParams &P, const FxBuffers &B, uint32_t *smem, const FxScTables *T, uint32_t bid,
+                                                    uint32_t nblk, uint32_t first) {
+  constexpr uint32_t GROUPS = 64u / LANES, CAP = 4u * LANES;  // rows a wavefront; support slots (and bins recorded) a row
+  // (The row's bin record has FX_GROUP_CAP slots whichever class wrote it last time.  A lane un-writes four of the first CAP,
+  //  fetched a trip ahead with the rest of the row; those behind them are read where they are un-written, only for a row that
+  //  recorded more than CAP bins: fetched a trip ahead they cost the kernel 112 instead of 32 bytes of scratch a lane —
+  //  profiles/desc_group_classes.md, which also has the one body with a wave-uniform LANES: 48 bytes.)
+  constexpr uint32_t CLS = LANES == 4u ? 0u : (LANES == 8u ? 1u : 2u);
+  static_assert(group_class_lanes(CLS) == LANES && group_class_cap(CLS) == CAP && CAP <= FX_GROUP_CAP, "one size class an instantiation");
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint32_t gl = lane % FX_GLANES, g = lane / FX_GLANES;
+  const uint32_t gl = lane % LANES, g = lane / LANES;
   const WithinR2 within(P.r2_density);
-  uint32_t *base = smem + (wave * FX_GROUPS + g) * FX_GROUP_WORDS;
-  float4 *sp = reinterpret_cast<float4 *>(base);                                                   // 4 * CAP words
-  unsigned long long *nkey = reinterpret_cast<unsigned long long *>(base + 4 * FX_GROUP_CAP);      // 2 * CAP
-  float *nw = reinterpret_cast<float *>(base + 6 * FX_GROUP_CAP);
-  uint32_t *sidx = base + 7 * FX_GROUP_CAP;
-  uint32_t *cnt = base + 8 * FX_GROUP_CAP;  // [1] binned neighbours, [2] bins written to the row
+  uint32_t *wbase = smem + wave * FX_GROUP_WAVE_WORDS, *base = wbase + g * (8u * CAP);
+  float4 *sp = reinterpret_cast<float4 *>(base);                                          // 4 * CAP words
+  unsigned long long *nkey = reinterpret_cast<unsigned long long *>(base + 4 * CAP);      // 2 * CAP
+  float *nw = reinterpret_cast<float *>(base + 6 * CAP);
+  uint32_t *sidx = base + 7 * CAP;
+  uint32_t *cnt = wbase + 8u * FX_GROUP_SLOTS + 2u * g;  // [0] binned neighbours, [1] bins written to the row
   unsigned long long *skey = reinterpret_cast<unsigned long long *>(base);  // aliases sp
-  float *sw = reinterpret_cast<float *>(base + 2 * FX_GROUP_CAP);           // aliases sp
-  const FxScTables *T = tables_to_lds(B, smem + FX_NWAVE * FX_GROUPS * FX_GROUP_WORDS);
+  float *sw = reinterpret_cast<float *>(base + 2 * CAP);                    // aliases sp
 
-  uint32_t total = B.kp_offset[batch];
-  if (total > P.max_total_kp) total = P.max_total_kp;
-  const uint32_t stride = nblk * FX_NWAVE * FX_GROUPS;
-  // Everything a row needs is fetched in one round trip — its class, keypoint, x-axis, the list entries before the list length is
-  // known (slots past the length hold stale data and are ignored), and what the row holds from last time (its bin count and all 64
-  // slots of its bin list, four per lane) — and a TRIP AHEAD: the next trip's loads go out before this trip's last step (few
-  // registers are live there) and are taken at the top of the next trip.  (With one workgroup a CU a wavefront has a SIMD to
-  // itself, and every trip began with that round trip.)
-  static_assert(FX_GROUP_CAP == 4 * FX_GLANES, "a lane fetches four slots of the row's bin list");
-  uint2 f_rm = make_uint2(0u, 0u), f_pb = make_uint2(0u, 0u);
-  uint32_t f_nS = 0, f_nb = 0, f_cls = FX_ROW_GROUP;
-  float4 f_kp = make_float4(0, 0, 0, 0), f_lv[FX_GROUP_CAP / FX_GLANES];
+  // (the class counters are final: the support gather has completed)
+  const uint32_t n_rows = min(B.counters[FX_CNT_GROUP + CLS], P.max_total_kp);
+  const uint32_t *list = B.group_desc + (size_t)CLS * P.max_total_kp;
+  // (the classes' items form one sequence, `first` this class's place in it, dealt to the wavefronts in turn: a class does not
+  //  start at wavefront 0 again, which would then get the extra item of every class)
+  const uint32_t n_items = (n_rows + GROUPS - 1u) / GROUPS, istride = nblk * FX_NWAVE;
+  const uint32_t it0 = (bid * FX_NWAVE + wave + istride - first % istride) % istride;
+  if (it0 >= n_items) return first + n_items;  // (wave-uniform)
+  auto entry = [&](uint32_t it) -> uint32_t {  // this group's row of item it (FX_NONE: none)
+    const uint32_t i = it * GROUPS + g;
+    return i < n_rows ? list[i] : FX_NONE;
+  };
+  // Everything a row needs is fetched in one round trip — its keypoint, x-axis, the list entries before the list length is
+  // known (slots past the length hold stale data and are ignored), and what the row holds from last time (its bin count and the
+  // first CAP slots of its bin record, four per lane) — and a TRIP AHEAD: the next trip's loads go out before this trip's last
+  // step (few registers are live there) and are taken at the top of the next trip.  The row index itself comes from the
+  // class's list and is fetched TWO trips ahead, so that the chain does not gain a round trip.  (With one workgroup a CU a
+  // wavefront has a SIMD to itself, and every trip began with that round trip.)
+  uint2 f_rm = make_uint2(0u, 0u);
+  uint32_t f_row = FX_NONE, f_nS = 0, f_nb = 0, f_cls = FX_ROW_GROUP;
+  uint2 f_pb = make_uint2(0u, 0u);
+  float4 f_kp = make_float4(0, 0, 0, 0), f_lv[4];
   float2 f_xa = make_float2(1.f, 0.f);
   auto fetch = [&](uint32_t row) {
     // (every value is defined anew on both paths: nothing of the previous fetch stays live across a trip)
-    f_rm = make_uint2(0u, 0u), f_pb = make_uint2(0u, 0u), f_nS = 0, f_nb = 0, f_kp = make_float4(0, 0, 0, 0), f_xa = make_float2(1.f, 0.f);
-    f_cls = FX_ROW_GROUP;
+    f_row = row, f_rm = make_uint2(0u, 0u), f_pb = make_uint2(0u, 0u), f_nS = 0, f_nb = 0, f_cls = FX_ROW_GROUP;
+    f_kp = make_float4(0, 0, 0, 0), f_xa = make_float2(1.f, 0.f);
 #pragma unroll
-    for (uint32_t u = 0; u < FX_GROUP_CAP / FX_GLANES; ++u) f_lv[u] = make_float4(0, 0, 0, 0);
-    if (row < total) {
-      f_cls = B.row_class[row];
+    for (uint32_t u = 0; u < 4u; ++u) f_lv[u] = make_float4(0, 0, 0, 0);
+    if (row != FX_NONE) {
+      if (CLS == FX_GROUP_CLASSES - 1u) f_cls = B.row_class[row];  // (dense rows without room in the pools ride in the widest class's list)
       f_rm = B.row_map[row];
       f_nS = B.s_cnt[row];
       f_kp = B.row_kp[row];
       f_xa = B.row_xa[row];
 #pragma unroll
-      for (uint32_t u = 0; u < FX_GROUP_CAP / FX_GLANES; ++u)
-        if (gl + u * FX_GLANES < P.list_cap) f_lv[u] = B.s_pts[(size_t)row * P.list_cap + gl + u * FX_GLANES];
+      for (uint32_t u = 0; u < 4u; ++u)
+        if (gl + u * LANES < P.list_cap) f_lv[u] = B.s_pts[(size_t)row * P.list_cap + gl + u * LANES];
       f_nb = B.desc_nbins[row];
       f_pb = *reinterpret_cast<const uint2 *>(B.desc_bins + (size_t)row * FX_GROUP_CAP + 4u * gl);
     }
   };
-  fetch((bid * FX_NWAVE + wave) * FX_GROUPS + g);
+  fetch(entry(it0));
+  uint32_t row_next = entry(it0 + istride);
+  __builtin_amdgcn_wave_barrier();  // (the wavefront's LDS image may be a wider class's until here)
   // all groups of a wavefront make the same number of trips (wave-level fences inside)
-  for (uint32_t r0 = (bid * FX_NWAVE + wave) * FX_GROUPS; r0 < total; r0 += stride) {
-    const uint32_t row = r0 + g;
-    // rows of the other tiers are theirs alone — not read, not cleared, not written here — but for a dense row the pools had no
-    // room for (classify_rows): cleared, filled with NaN and left dirty below
-    const uint32_t cls = f_cls;
-    const bool dense_fail = row < total && cls == FX_ROW_DENSE_FAIL;
-    bool live = row < total && (cls == FX_ROW_GROUP || dense_fail);
+  for (uint32_t it = it0; it < n_items; it += istride) {
+    const uint32_t row = f_row;
+    // a dense row the pools had no room for (classify_rows) is cleared, filled with NaN and left dirty below; every other listed
+    // row is a group row of this class (nS > CAP: never listed here)
+    const bool dense_fail = row != FX_NONE && f_cls == FX_ROW_DENSE_FAIL;
+    bool live = row != FX_NONE && (dense_fail || f_nS <= CAP);
     uint32_t scan = 0, k = 0, nS = 0;
     float4 kp = make_float4(0, 0, 0, 0);
     float2 xa = make_float2(1.f, 0.f);
-    float4 lv[FX_GROUP_CAP / FX_GLANES];
+    float4 lv[4];
     uint32_t nb_prev = 0;
     uint2 pb = make_uint2(0u, 0u);
     if (live) {
       scan = f_rm.x, k = f_rm.y, nS = f_nS, kp = f_kp, xa = f_xa, nb_prev = f_nb, pb = f_pb;
 #pragma unroll
-      for (uint32_t u = 0; u < FX_GROUP_CAP / FX_GLANES; ++u) lv[u] = f_lv[u];
+      for (uint32_t u = 0; u < 4u; ++u) lv[u] = f_lv[u];
     }
-    float *out = B.desc + (size_t)row * FX_DESC_FLOATS;
+    float *out = B.desc + (size_t)(live ? row : 0u) * FX_DESC_FLOATS;
     // The row is cleared here, before anything is written to it (every tier clears its own rows: desc_clear_row, whose work
     // this is with the recorded bins already fetched).  A row a group filled last time — nine in ten — is cleared by zeroing
     // the bins written then (recorded in desc_bins): some tens of 4-byte stores instead of 7956 bytes.  (The descriptor rows
     // are half of the batch's algorithmic bytes and all of them writes; the dirty lines they leave in L2 / MALL are written
     // back under the next kernels — k_prep ran 0.17 ms behind a batch's row clears and 0.13 ms without.)
-    uint16_t *my_bins = B.desc_bins + (size_t)row * FX_GROUP_CAP;
+    uint16_t *my_bins = B.desc_bins + (size_t)(live ? row : 0u) * FX_GROUP_CAP;
     if (live) {
       if (nb_prev > FX_GROUP_CAP) {
-        desc_zero_row(out, gl, FX_GLANES);
+        desc_zero_row(out, gl, LANES);
       } else {
         const uint32_t t0 = 4u * gl;
         if (t0 + 0u < nb_prev) out[pb.x & 0xffffu] = 0.0f;
@@ -5021,9 +5068,14 @@ __device__ __forceinline__ void desc_group_body(const FxDevParams &P, const FxBu
         if (t0 + 3u < nb_prev) out[pb.y >> 16] = 0.0f;
       }
     }
+    // (a record longer than this class's CAP — the row index was a wider class's row last time: its slots behind CAP)
+    if constexpr (CAP < FX_GROUP_CAP) {
+      if (live && nb_prev > CAP && nb_prev <= FX_GROUP_CAP)
+        for (uint32_t t = CAP + gl; t < nb_prev; t += LANES) out[my_bins[t]] = 0.0f;
+    }
     if (dense_fail) {  // pools exhausted (limits.max_dense_points): flagged by classify_rows, never silent
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");  // (the clearing stores first)
-      desc_fill_nan(out, gl, FX_GLANES);
+      desc_fill_nan(out, gl, LANES);
       if (gl == 0) {
         B.kp_nbrs[(size_t)scan * P.max_keypoints + k] = FX_NONE;
         B.desc_nbins[row] = FX_ROW_DIRTY;  // cleared whole next time
@@ -5037,8 +5089,8 @@ __device__ __forceinline__ void desc_group_body(const FxDevParams &P, const FxBu
     // groups' neighbours are packed into as few trips as they fit.
     uint32_t nAll = 0;
 #pragma unroll
-    for (uint32_t u = 0; u < FX_GROUP_CAP / FX_GLANES; ++u) {
-      const uint32_t e = gl + u * FX_GLANES;
+    for (uint32_t u = 0; u < 4u; ++u) {
+      const uint32_t e = gl + u * LANES;
       float4 v = make_float4(0, 0, 0, 0);
       float d2 = INFINITY;
       if (e < nS) {
@@ -5047,7 +5099,7 @@ __device__ __forceinline__ void desc_group_body(const FxDevParams &P, const FxBu
       }
       const bool nb = d2 < P.r2_search;
       const unsigned long long m = __ballot(nb);
-      const uint32_t gm = (uint32_t)(m >> (g * FX_GLANES)) & ((1u << FX_GLANES) - 1u);  // this group's lanes
+      const uint32_t gm = (uint32_t)(m >> (g * LANES)) & ((1u << LANES) - 1u);  // this group's lanes
       if (e < nS) {
         const uint32_t before = nAll + (uint32_t)__popc(gm & ((1u << gl) - 1u));  // neighbours among the entries in front of this one
         const uint32_t pos = nb ? before : nS - 1u - (e - before);
@@ -5056,11 +5108,12 @@ __device__ __forceinline__ void desc_group_body(const FxDevParams &P, const FxBu
       }
       nAll += (uint32_t)__popc(gm);
     }
-    if (gl == 1 || gl == 2) cnt[gl] = 0;  // (slot 0 is free: the neighbour count is the partition's)
+    if (gl < 2) cnt[gl] = 0;  // binned neighbours, bins written to the row
+    if (live && gl == 0) B.kp_nbrs[(size_t)scan * P.max_keypoints + k] = nAll;  // (here: scan and k are not held across the density loop)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    for (uint32_t e = gl; e < nAll; e += FX_GLANES) {
+    for (uint32_t e = gl; e < nAll; e += LANES) {
       const float4 b = sp[e];
       const float d2 = b.w;
       if (sc3d_is_origin(d2)) continue;
@@ -5068,33 +5121,38 @@ __device__ __forceinline__ void desc_group_body(const FxDevParams &P, const FxBu
       bool amb = false;
       const uint32_t bin = sc3d_bin<true>(kp, b.x, b.y, b.z, d2, xa, T, lut, amb);
       const uint32_t dens = within.count(sp, 0u, nS, b.x, b.y, b.z);  // support points within R/5 of this neighbour (itself included)
-      const uint32_t pos = atomicAdd(&cnt[1], 1u);
+      const uint32_t pos = atomicAdd(&cnt[0], 1u);
       nkey[pos] = sc3d_key(bin, d2, sidx[e]);
       nw[pos] = (1.0f / (float)dens) * lut;
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    uint32_t nM = live ? cnt[1] : 0u;
+    uint32_t nM = live ? cnt[0] : 0u;
+    {  // the row's two addresses are derived anew (the empty statement hides where the index comes from): held across the
+       // density loop — sc3d_bin's exact path is where the kernel's registers run out — they were four more spilled VGPRs
+      uint32_t r2 = live ? row : 0u;
+      asm volatile("" : "+v"(r2));
+      out = B.desc + (size_t)r2 * FX_DESC_FLOATS;
+      my_bins = B.desc_bins + (size_t)r2 * FX_GROUP_CAP;
+    }
     // (s_waitcnt vmcnt(0): the clearing stores are acknowledged before anything else is written to the row; a wider
     //  scope would write the whole L2 back)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     if (live) {
-      if (gl == 0) B.kp_nbrs[(size_t)scan * P.max_keypoints + k] = nAll;
       if (nAll == 0) {  // no neighbours: NaN descriptor, no RNG draw (A.8-3)
-        desc_fill_nan(out, gl, FX_GLANES);
+        desc_fill_nan(out, gl, LANES);
         nM = 0;
         if (gl == 0) B.desc_nbins[row] = FX_ROW_DIRTY;
       }
     }
-    if (gl == 0) cnt[2] = 0;  // bins written to the row
     // rank sort (keys are unique: they end in the point index); the sorted arrays reuse the support storage
-    unsigned long long my_key[FX_GROUP_CAP / FX_GLANES];
-    float my_w[FX_GROUP_CAP / FX_GLANES];
-    uint32_t my_rank[FX_GROUP_CAP / FX_GLANES];
+    unsigned long long my_key[4];
+    float my_w[4];
+    uint32_t my_rank[4];
 #pragma unroll
-    for (uint32_t u = 0; u < FX_GROUP_CAP / FX_GLANES; ++u) {
-      const uint32_t e = gl + u * FX_GLANES;
+    for (uint32_t u = 0; u < 4u; ++u) {
+      const uint32_t e = gl + u * LANES;
       my_rank[u] = FX_NONE;
       if (e < nM) {
         my_key[u] = nkey[e];
@@ -5109,7 +5167,7 @@ __device__ __forceinline__ void desc_group_body(const FxDevParams &P, const FxBu
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll
-    for (uint32_t u = 0; u < FX_GROUP_CAP / FX_GLANES; ++u)
+    for (uint32_t u = 0; u < 4u; ++u)
       if (my_rank[u] != FX_NONE) {
         skey[my_rank[u]] = my_key[u];
         sw[my_rank[u]] = my_w[u];
@@ -5117,9 +5175,10 @@ __device__ __forceinline__ void desc_group_body(const FxDevParams &P, const FxBu
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    fetch(r0 + stride + g);  // (the next trip's rows: see the top)
+    fetch(row_next);  // (the next trip's rows, and the list entries of the trip after it: see the top)
+    row_next = entry(it + 2u * istride);
     // one lane per bin run adds its weights in sorted order (the row was cleared at the top of this trip)
-    for (uint32_t e = gl; e < nM; e += FX_GLANES) {
+    for (uint32_t e = gl; e < nM; e += LANES) {
       const uint32_t bin = (uint32_t)(skey[e] >> 52);
       if (e > 0 && (uint32_t)(skey[e - 1] >> 52) == bin) continue;
       float acc = 0.0f;
@@ -5129,13 +5188,14 @@ __device__ __forceinline__ void desc_group_body(const FxDevParams &P, const FxBu
         ++q;
       } while (q < nM && (uint32_t)(skey[q] >> 52) == bin);
       out[bin] = acc;
-      my_bins[atomicAdd(&cnt[2], 1u)] = (uint16_t)bin;  // (at most nM <= FX_GROUP_CAP of them)
+      my_bins[atomicAdd(&cnt[1], 1u)] = (uint16_t)bin;  // (at most nM <= CAP <= FX_GROUP_CAP of them)
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (live && nAll != 0 && gl == 0) B.desc_nbins[row] = cnt[2];
+    if (live && nAll != 0 && gl == 0) B.desc_nbins[row] = cnt[1];
   }
+  return first + n_items;
 }
 
 // ---------------------------------------------------------------- workgroup tiers
@@ -5508,14 +5568,14 @@ __device__ __forceinline__ void dense_slow_loop(const FxDevParams &P, const FxBu
   }
 }
 // Every tier in one launch, by (rotated: see below) block index: n_wg workgroups take list rows (193..cap support points, one
-// keypoint per workgroup at a time), n_wave take wave rows (65..192, one keypoint per wavefront), n_group stride over all
-// rows and take the group rows (the bulk), and the last n_dslow (when the dense tier's own kernels are not launched) take the
-// dense tier's rows.  No tier
-// fills the chip alone (1600, 900 and — one workgroup a CU with four batches in flight — 1024 of the 8192 wave slots on the
-// VLP-16 bench) and none depends on another: the work lists were completed by the support gather (classify_rows), every row is
-// cleared by the workgroup that computes it, and no workgroup waits for another.  List and wave tier one after the other cost
-// 0.135 + 0.075 ms, together about the longer of the two; the group tier in a launch of its own in front of them made every
-// batch's stream drain once more (profiles/desc_one_launch.md).
+// keypoint per workgroup at a time), n_wave take wave rows (65..192, one keypoint per wavefront), n_group share the group rows
+// (the bulk), by size class from the classes' lists, 4 / 8 / 16 keypoints per wavefront, and the last n_dslow (when the dense
+// tier's own kernels are not launched) take the dense tier's rows.  No tier fills the chip alone (1600, 900 and — one workgroup
+// a CU with four batches in flight — 1024 of the 8192 wave slots on the VLP-16 bench) and none depends on another: the work
+// lists were completed by the support gather (classify_rows), every row is cleared by the workgroup that computes it, and no
+// workgroup waits for another.  List and wave tier one after the other cost 0.135 + 0.075 ms, together about the longer of the
+// two; the group tier in a launch of its own in front of them made every batch's stream drain once more
+// (profiles/desc_one_launch.md).
 static_assert(FX_DSLOW_T == FX_WG && FX_DESC_WG_FAST_T == FX_WG, "k_desc's four kinds of workgroups");
 extern "C" __global__ __launch_bounds__(FX_WG, FX_GROUP_OCC) void k_desc(FxDevParams P, FxBuffers B, uint32_t batch, uint32_t cap,
                                                                           uint32_t n_wg, uint32_t n_wave, uint32_t n_dslow) {
@@ -5535,9 +5595,13 @@ extern "C" __global__ __launch_bounds__(FX_WG, FX_GROUP_OCC) void k_desc(FxDevPa
     desc_wg_loop<true, FX_DESC_WG_FAST_T>(P, B, batch, cap, smem, bx, n_wg);
   else if (bx < n_mid)
     desc_wave_body<true>(P, B, batch, smem, bx - n_wg, n_wave);
-  else if (bx < n_all)
-    desc_group_body(P, B, batch, smem, bx - n_mid, n_all - n_mid);
-  else
+  else if (bx < n_all) {
+    // the widest class first and the narrowest last: the long-lived work starts first
+    const FxScTables *T = tables_to_lds(B, smem + FX_NWAVE * FX_GROUP_WAVE_WORDS);
+    uint32_t first = desc_group_body<group_class_lanes(2)>(P, B, smem, T, bx - n_mid, n_all - n_mid, 0u);
+    first = desc_group_body<group_class_lanes(1)>(P, B, smem, T, bx - n_mid, n_all - n_mid, first);
+    desc_group_body<group_class_lanes(0)>(P, B, smem, T, bx - n_mid, n_all - n_mid, first);
+  } else
     dense_slow_loop(P, B, smem, bx - n_all, n_dslow);
 }
 
@@ -6835,7 +6899,7 @@ hipError_t fxk_configure(size_t ring_big, size_t merge_big, size_t merge_huge, s
   if (e != hipSuccess) return e;
   e = hipFuncSetAttribute((const void *)k_merge_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)merge_big);
   if (e != hipSuccess) return e;
-  desc_big = std::max(desc_big, (size_t)(FX_NWAVE * FX_GROUPS * FX_GROUP_WORDS + FX_TABLE_WORDS) * 4);  // (the group tier's image: any cap)
+  desc_big = std::max(desc_big, (size_t)(FX_NWAVE * FX_GROUP_WAVE_WORDS + FX_TABLE_WORDS) * 4);  // (the group tier's image: any cap)
   e = hipFuncSetAttribute((const void *)k_desc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)desc_big);
   if (e != hipSuccess) return e;
   e = hipFuncSetAttribute((const void *)k_dense_finish, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fxk_dense_finish_lds_bytes());
@@ -6976,7 +7040,7 @@ void fxk_gather(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_
 void fxk_desc(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, uint32_t cap, uint32_t n_wg, uint32_t n_wave,
               uint32_t n_group, uint32_t n_dslow) {
   const size_t lds_wave = (size_t)(FX_NWAVE * FX_WAVE_WORDS + FX_TABLE_WORDS) * 4, lds_wg = fxk_desc_lds_bytes(cap);
-  const size_t lds_group = (size_t)(FX_NWAVE * FX_GROUPS * FX_GROUP_WORDS + FX_TABLE_WORDS) * 4;
+  const size_t lds_group = (size_t)(FX_NWAVE * FX_GROUP_WAVE_WORDS + FX_TABLE_WORDS) * 4;
   static_assert((16 + FX_DESC_BINS + 16) * 4 <= (FX_NWAVE * FX_WAVE_WORDS + FX_TABLE_WORDS) * 4, "the dense tier's rows in k_desc's LDS");
   assert(n_dslow <= P.gsd_slots);  // (a scratch region each)
   hipLaunchKernelGGL(k_desc, dim3(n_wg + n_wave + n_group + n_dslow), dim3(FX_WG), std::max({lds_wave, lds_wg, lds_group}), s, P, B, batch, cap,

@@ -21,6 +21,12 @@ names = ["rings -> second run tier", "scans -> big merge", "-", "-", "rows -> li
 print(f"batch {B} scans, {v.total_keypoints} keypoint rows, {B * 16} rings")
 for n, c in zip(names, out):
     print(f"  {n:28s} {c}")
+if hasattr(lib, "fx_debug_group_classes"):  # (an older build under lib/ has no size classes)
+    cls = (C.c_uint32 * 3)()
+    lib.fx_debug_group_classes.argtypes = [C.c_void_p, C.c_void_p]
+    capi.check(lib.fx_debug_group_classes(ctx.handle, cls))
+    for cap, c in zip((16, 32, 64), cls):
+        print(f"  {'group rows, <= %d support points' % cap:28s} {c}  ({100.0 * c / max(1, v.total_keypoints):.1f} % of the rows)")
 hints = (C.c_uint32 * 8)()
 lib.fx_debug_tier_hints.argtypes = [C.c_void_p, C.c_void_p]
 capi.check(lib.fx_debug_tier_hints(ctx.handle, hints))
