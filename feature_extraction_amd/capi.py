@@ -285,6 +285,23 @@ EXPECT_DEFAULTS = dict(x_min=1.0, x_max=74.0, y_min=-29.0, y_max=29.0, min_range
 RETIRE_DEFAULTS = dict(min_expected=16, seen_num=1, seen_den=8, mode=FX_RETIRE_APPLY)
 
 
+class FxMapDiscoverOptions(C.Structure):
+    _fields_ = [("known_dist", C.c_float), ("join_dist", C.c_float), ("min_obs", C.c_uint32), ("require_flags", C.c_uint32),
+                ("segment", C.c_uint32), ("mode", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class FxMapDiscoverResult(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("scans_used", "unmatched", "known", "free_rows", "leaders", "orphans", "duplicates", "weak", "added",
+                                          "lost", "created", "not_stored", "first_id", "refused")] + [("reserved", C.c_uint32 * 2)]
+
+
+FX_MAP_LM_DISCOVERED = 0x10  # fx_map_discover: the landmark was created by it
+FX_DISC_APPLY, FX_DISC_DRY_RUN = 0, 1
+MAP_DISCOVER_RESULT_FIELDS = ("scans_used", "unmatched", "known", "free_rows", "leaders", "orphans", "duplicates", "weak", "added", "lost",
+                              "created", "not_stored", "first_id", "refused")
+DISCOVER_DEFAULTS = dict(known_dist=1.0, join_dist=0.30, min_obs=3, require_flags=FX_LOC_VALID, segment=FX_LOC_LAST_SEGMENT, mode=FX_DISC_APPLY)
+
+
 class FxRelocalizeOptions(C.Structure):
     _fields_ = [("inlier_dist", C.c_float), ("pair_tol", C.c_float), ("min_baseline", C.c_float), ("max_baseline", C.c_float),
                 ("max_seeds", C.c_uint32), ("min_inliers", C.c_uint32), ("min_margin", C.c_uint32), ("min_landmark_obs", C.c_uint32),
@@ -426,6 +443,7 @@ EXPORTS = ("fx_version", "fx_check_abi", "fx_status_str", "fx_last_error", "fx_p
            "fx_map_observe_options_default", "fx_map_observe",
            "fx_map_expect_options_default", "fx_map_expect_options_from_params", "fx_map_expect",
            "fx_map_retire_options_default", "fx_map_retire",
+           "fx_map_discover_options_default", "fx_map_discover",
            "fx_map_compact_options_default", "fx_map_compact", "fx_map_export_host", "fx_map_import_host", "fx_map_snapshot_check",
            "fx_map_append", "fx_map_append_host",
            "fx_map_join_options_default", "fx_map_join_segments",
@@ -580,6 +598,10 @@ def load():
     lib.fx_map_retire_options_default.argtypes = [C.POINTER(FxMapRetireOptions)]
     lib.fx_map_retire_options_default.restype = None
     lib.fx_map_retire.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(FxMapRetireOptions), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.fx_map_discover_options_default.argtypes = [C.POINTER(FxMapDiscoverOptions)]
+    lib.fx_map_discover_options_default.restype = None
+    lib.fx_map_discover.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                    C.POINTER(FxMapDiscoverOptions), C.c_void_p, C.c_void_p]
     lib.fx_map_compact_options_default.argtypes = [C.POINTER(FxMapCompactOptions)]
     lib.fx_map_compact_options_default.restype = None
     lib.fx_map_compact.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(FxMapCompactOptions), C.c_void_p, C.c_void_p]
@@ -1933,6 +1955,141 @@ def map_expect_reference(state, kp_offset, kp_rows, loc_records, map_id_of_row, 
     return res, cnt_e.astype(np.uint32), cnt_s.astype(np.uint32)
 
 
+# ---- new poles learnt from the unexplained rows of localised scans (include/fx.h fx_map_discover)
+def discover_records(out):
+    """The 64 bytes fx_map_discover wrote (a device tensor, or an array) as a dict of MAP_DISCOVER_RESULT_FIELDS; the reserved words must be 0."""
+    a = out.detach().cpu().numpy() if hasattr(out, "detach") else np.asarray(out)
+    w = np.ascontiguousarray(a).view(np.uint8).reshape(-1)[:64].view("<u4")
+    if w[14] or w[15]:
+        raise ValueError("fx_map_discover_result.reserved is not 0")
+    return dict(zip(MAP_DISCOVER_RESULT_FIELDS, (int(v) for v in w[:14])))
+
+
+def map_discover_reference(state, kp_offset, kp_rows, loc_records, map_id_of_row, n_scans, q_max_rows=None, dry_run=False, **opts):
+    """The definition of fx_map_discover (include/fx.h) in numpy float64 over a map_reference / ... state, which is not modified.  The
+    arguments are map_observe_reference's; opts: the fields of fx_map_discover_options (DISCOVER_DEFAULTS) but mode, which is dry_run.
+    Every (row, landmark) pair and every (free row, free row) pair is looked at and every clause is a mask over all of them: nothing
+    here knows of a grid, a prefix or a list.  One ufunc an operation, so nothing is contracted.
+    Returns (the new state (the old one's content with dry_run, or when the call is refused), a dict of MAP_DISCOVER_RESULT_FIELDS,
+    new_id_of_row int32 [q_max_rows])."""
+    f64 = np.float64
+    bad = set(opts) - (set(DISCOVER_DEFAULTS) - {"mode"})
+    if bad:
+        raise TypeError(f"unknown discover options {sorted(bad)}")
+    o = dict(DISCOVER_DEFAULTS, **opts)
+    off = [int(x) for x in kp_offset]
+    kp = np.ascontiguousarray(kp_rows, dtype=np.float32)
+    kp = kp.reshape(len(kp), -1)[:, :3] if kp.size else np.zeros((0, 3), np.float32)
+    n_scans = int(n_scans)
+    R = len(kp) if q_max_rows is None else int(q_max_rows)
+    kd32, jd32 = np.float32(o["known_dist"]), np.float32(o["join_dist"])
+    min_obs, req, segment = (int(o[k]) & 0xffffffff for k in ("min_obs", "require_flags", "segment"))
+    flags_known = FX_LOC_VALID | FX_LOC_TRUNCATED | FX_LOC_NO_HYPOTHESIS | FX_LOC_BAD_PRIOR | FX_LOC_NO_SCAN
+    if not (n_scans >= 1 and np.isfinite(kd32) and kd32 > 0 and np.isfinite(jd32) and jd32 > 0 and f64(kd32) >= f64(2.0) * f64(jd32) and
+            min_obs >= 1 and not req & ~flags_known and segment != FX_LOC_ANY_SEGMENT):
+        raise ValueError("arguments outside what fx_map_discover accepts")
+    kd2, jd2 = f64(kd32) * f64(kd32), f64(jd32) * f64(jd32)
+    st = dict(state, header=dict(state["header"]), landmarks=[dict(r) for r in state["landmarks"]], acc=[list(a) for a in state["acc"]],
+              carry=list(state["carry"]), carry_kp=state["carry_kp"].copy())
+    if "alias" in state:
+        st["alias"] = list(state["alias"])
+    H, lms, cap = st["header"], st["landmarks"], int(st["max_landmarks"])
+    first_id = int(H["n_needed"])
+    res = dict({k: 0 for k in MAP_DISCOVER_RESULT_FIELDS}, first_id=first_id)
+    new_id = np.full(R, -1, np.int32)
+    seg = int(H["segments"]) - 1 if segment == FX_LOC_LAST_SEGMENT else segment
+    if seg < 0 or seg >= int(H["segments"]):
+        res["refused"] = 1
+        return st, res, new_id
+    N = min(int(H["n_landmarks"]), len(lms), cap)
+    alias = np.array([int(a) for a in state.get("alias", [])][:N] + [-1] * max(0, N - len(state.get("alias", []))), np.int64)
+    lx, ly = (np.array([float(r[f]) for r in lms[:N]], f64) for f in ("x", "y"))
+    ln, lseg = (np.array([int(r[f]) for r in lms[:N]], np.int64) for f in ("n_obs", "segment"))
+    loc = np.asarray(loc_records)[:n_scans]
+    S, rows = min(n_scans, len(off) - 1), min(len(kp), R)
+    ids = np.asarray(map_id_of_row)[:rows].astype(np.int64)
+    scan = np.full(rows, -1, np.int64)  # the scan of every row, -1: a non-row
+    for b in range(S):
+        lo = min(off[b], rows)
+        scan[lo:max(min(off[b + 1], rows), lo)] = b
+    P = loc["pose"][:S]
+    used = np.array([(int(loc["flags"][b]) & req) == req and all(np.isfinite(f64(P[f][b])) for f in ("c", "s", "tx", "ty", "tz")) for b in range(S)], bool)
+    with np.errstate(all="ignore"):
+        sc = np.where(scan >= 0, scan, 0)
+        in_used = (scan >= 0) & (used[sc] if S else np.zeros(rows, bool))
+        x, y, z = (kp[:rows, k].astype(f64) for k in range(3))
+        pc, ps, ptx, pty, ptz = ((P[f][sc].astype(f64) if S else np.zeros(rows, f64)) for f in ("c", "s", "tx", "ty", "tz"))
+        wx, wy, wz = (pc * x - ps * y) + ptx, (ps * x + pc * y) + pty, z + ptz
+        unmatched = in_used & np.isfinite(kp[:rows]).all(axis=1) & (ids < 0) & np.isfinite(wx) & np.isfinite(wy) & np.isfinite(wz)
+        # known: some live landmark of the segment within kd
+        live = np.flatnonzero((alias == -1) & (ln >= 1) & np.isfinite(lx) & np.isfinite(ly) & (lseg == seg))
+        U = np.flatnonzero(unmatched)
+        dx, dy = lx[live][None, :] - wx[U][:, None], ly[live][None, :] - wy[U][:, None]
+        known = ((dx * dx + dy * dy) <= kd2).any(axis=1)
+        F = U[~known]  # the free rows, ascending
+        n = len(F)
+        # every pair of free rows: [r, r'] is the d2 of r' from r
+        dx, dy = wx[F][None, :] - wx[F][:, None], wy[F][None, :] - wy[F][:, None]
+        d2 = dx * dx + dy * dy
+        near = d2 <= jd2
+    bits = np.ascontiguousarray(d2).view(np.uint64).reshape(n, n)
+    idx = np.arange(n)
+    leader = ~(near & (idx[None, :] < idx[:, None])).any(axis=1)
+    # attachment: the leader within jd of lowest (d2 bits, leader row); argmin takes the first of equals, which is the lowest row
+    cand = near & leader[None, :]
+    attached = cand.any(axis=1)
+    att = np.where(attached, np.where(cand, bits, np.uint64(0xffffffffffffffff)).argmin(axis=1) if n else idx, -1)
+    abits = bits[idx, np.where(attached, att, 0)] if n else np.zeros(0, np.uint64)
+    # one observation a scan a leader: the lowest (d2 bits, row)
+    fscan = scan[F]
+    same = attached[:, None] & attached[None, :] & (att[:, None] == att[None, :]) & (fscan[:, None] == fscan[None, :])
+    lower = (abits[None, :] < abits[:, None]) | ((abits[None, :] == abits[:, None]) & (idx[None, :] < idx[:, None]))
+    kept = attached & ~(same & lower).any(axis=1)
+    support = np.array([int((kept & (att == l)).sum()) for l in range(n)], np.int64)
+    confirmed = [l for l in range(n) if leader[l] and support[l] >= min_obs]
+    res.update(scans_used=int(used.sum()), unmatched=len(U), known=int(known.sum()), free_rows=n, leaders=int(leader.sum()),
+               orphans=int((~attached).sum()), duplicates=int((attached & ~kept).sum()),
+               weak=int(sum(support[l] for l in range(n) if leader[l] and support[l] < min_obs)))
+    scan_now = int(H["scans"]) - 1 if int(H["scans"]) else 0
+    W = np.stack([wx, wy, wz], axis=1).tolist() if rows else []
+    for i, l in enumerate(confirmed):
+        lid = first_id + i
+        mine = np.flatnonzero(kept & (att == l)).tolist()  # (ascending row; the first is the leader)
+        if lid >= cap:
+            res["not_stored"] += 1
+            res["lost"] += len(mine)
+            continue
+        res["created"] += 1
+        res["added"] += len(mine)
+        new_id[F[mine]] = lid
+        if dry_run:
+            continue
+        acc = [0.0] * 8
+        acc[3], acc[4] = W[F[mine[0]]][0], W[F[mine[0]]][1]
+        for j in mine:
+            ox, oy, oz = W[F[j]]
+            ddx, ddy = ox - acc[3], oy - acc[4]
+            acc[0] += ox
+            acc[1] += oy
+            acc[2] += oz
+            acc[5] += ddx
+            acc[6] += ddy
+            acc[7] += (ddx * ddx + ddy * ddy)
+        rec = {"n_obs": len(mine), "first_scan": scan_now, "last_scan": scan_now, "segment": seg, "flags": FX_MAP_LM_DISCOVERED}
+        _map_record_from_sums(rec, acc)
+        assert lid == len(lms), "a stored id is the next landmark"
+        lms.append(rec), st["acc"].append(acc)
+        if "alias" in st:
+            st["alias"] = (st["alias"][:lid] + [-1] * lid)[:lid] + [-1]
+    if not dry_run:
+        H["n_needed"] = (first_id + len(confirmed)) & 0xffffffff
+        H["n_landmarks"] = min(H["n_needed"], cap)
+        H["n_obs"] = (int(H["n_obs"]) + res["added"]) & 0xffffffff
+        if res["not_stored"]:
+            H["flags"] |= FX_MAP_FULL
+    return st, res, new_id
+
+
 # ---- two segments of the map made one (include/fx.h fx_map_join_segments)
 def join_records(out):
     """A host copy of fx_map_join_segments's result (a torch tensor, or any array of 120 bytes) as a JOIN_DTYPE record array [1]."""
@@ -2798,6 +2955,26 @@ class Map:
                                          int(n_scans), C.c_void_p(map_id_of_row.data_ptr() if n_rows else None), n_rows, C.byref(opt), _ptr(out),
                                          _ptr(expected), _ptr(seen)))
         return out, expected, seen
+
+    def discover(self, kp, loc, n_scans, map_id_of_row, q_max_rows=None, out=None, new_id=None, **opts):
+        """fx_map_discover: the unexplained rows of localised scans that fall on one spot in min_obs scans of this call made landmarks
+        (include/fx.h).  kp, loc, n_scans, map_id_of_row and q_max_rows are observe()'s.  opts: the fields of
+        fx_map_discover_options (DISCOVER_DEFAULTS).  Returns (result, new_id_of_row): device torch.int32 tensors [16]
+        (discover_records reads it) and [q_max_rows]; out / new_id reuse one, False passes NULL (None is returned in its place).
+        Stream-correct like update(); never waits for the stream."""
+        import torch
+        kb, scans, total = kp
+        dev = torch.device("cuda", self.ctx.device)
+        n_rows = int(total) if q_max_rows is None else int(q_max_rows)
+        opt = _options(FxMapDiscoverOptions, DISCOVER_DEFAULTS, "discover", opts)
+        error = f"outputs must be contiguous torch.int32 tensors [16] and [{n_rows}] on {dev}"
+        out = _out_tensor(out, (16,), torch.int32, dev, error, typed=True)
+        new_id = _out_tensor(new_id, (n_rows,), torch.int32, dev, error, typed=True)
+        with _on_stream(self.ctx.stream_ptr(), dev):
+            check(self.lib.fx_map_discover(self.ctx.handle, self.handle, C.c_void_p(kb.data_ptr()), int(scans), int(total), C.c_void_p(loc.data_ptr()),
+                                           int(n_scans), C.c_void_p(map_id_of_row.data_ptr() if n_rows else None), n_rows, C.byref(opt), _ptr(out),
+                                           _ptr(new_id if n_rows else None)))
+        return out, new_id
 
     def retire(self, expected, seen, remap=None, retired=None, result=None, **opts):
         """fx_map_retire: the landmarks that expect()'s counters condemn taken out, the others renumbered as compact() does, the

@@ -150,6 +150,8 @@ struct fx_ctx {
                              // fx_map_localize: the same grid, then each row's landmark and distance;
                              // fx_map_observe: the landmarks' list counts, cursors and prefix, each row's target and distance, the lists;
                              // fx_map_expect: the grid, this call's counts of both kinds, each row's named landmark;
+                             // fx_map_discover: the grid, a second grid over the free rows, their staged points and sources, each
+                             // one's leader, distance and verdicts, the leaders' supports and prefix;
                              // fx_map_compact: the marks, the new ids, the blocks' counts, the kept records and sums staged;
                              // fx_map_retire: the same, and the kept landmarks' counters staged;
                              // fx_map_append: the state words; fx_map_append_host: the snapshot's bytes before them;
@@ -2017,6 +2019,53 @@ fx_status fx_map_expect(fx_ctx *c, fx_map *m, const void *kp, uint32_t max_scans
   A.require_flags = o.require_flags, A.min_landmark_obs = o.min_landmark_obs, A.segment = o.segment, A.mode = o.mode;
   A.result = (uint32_t *)result, A.expected = expected_of_landmark, A.seen = seen_of_landmark;
   FX_MAP_RUN(fxk_map_expect, "map expect scratch");
+  return FX_OK;
+}
+
+void fx_map_discover_options_default(fx_map_discover_options *o) {
+  if (!o) return;
+  o->known_dist = 1.0f;
+  o->join_dist = 0.30f;
+  o->min_obs = 3u;
+  o->require_flags = FX_LOC_VALID;
+  o->segment = FX_LOC_LAST_SEGMENT;
+  o->mode = FX_DISC_APPLY;
+  o->reserved[0] = o->reserved[1] = 0u;
+}
+
+fx_status fx_map_discover(fx_ctx *c, fx_map *m, const void *kp, uint32_t max_scans, uint32_t max_total, const fx_localization *loc, uint32_t n_scans,
+                          const int32_t *map_id_of_row, uint32_t q_max_rows, const fx_map_discover_options *opt, fx_map_discover_result *result,
+                          int32_t *new_id_of_row) {
+  FX_TRY(map_call_check(c, m, kp && loc && !(q_max_rows && !map_id_of_row)));
+  FX_TRY(query_check(max_scans, n_scans));
+  fx_map_discover_options o;
+  fx_map_discover_options_default(&o);
+  if (opt) o = *opt;
+  if (!(std::isfinite(o.known_dist) && o.known_dist > 0.f)) return fail(FX_ERR_INVALID_ARG, "known_dist must be finite and positive");
+  if (!(std::isfinite(o.join_dist) && o.join_dist > 0.f)) return fail(FX_ERR_INVALID_ARG, "join_dist must be finite and positive");
+  if ((double)o.known_dist < 2.0 * (double)o.join_dist)
+    return fail(FX_ERR_INVALID_ARG, "known_dist must be at least twice join_dist (a second call must find the rows of a new landmark known)");
+  if (!o.min_obs) return fail(FX_ERR_INVALID_ARG, "min_obs must be at least 1");
+  FX_TRY(loc_flags_check(o.require_flags));
+  if (o.segment == FX_LOC_ANY_SEGMENT) return fail(FX_ERR_INVALID_ARG, "segment must be a segment number or FX_LOC_LAST_SEGMENT: a new landmark has one segment");
+  if (o.mode != FX_DISC_APPLY && o.mode != FX_DISC_DRY_RUN) return fail(FX_ERR_INVALID_ARG, "unknown mode (FX_DISC_APPLY or FX_DISC_DRY_RUN)");
+  if (o.reserved[0] || o.reserved[1]) return fail(FX_ERR_INVALID_ARG, "reserved must be 0");
+  if (((uintptr_t)kp % 16) != 0 || ((uintptr_t)loc % 8) != 0 || ((uintptr_t)map_id_of_row % 4) != 0 || ((uintptr_t)result % 4) != 0 ||
+      ((uintptr_t)new_id_of_row % 4) != 0)
+    return fail(FX_ERR_INVALID_ARG, "the keypoint block must be 16-byte, the records 8-byte, the words 4-byte aligned");
+  FX_HIP(hipSetDevice(c->device));
+  FxMapDiscoverArgs A{};
+  map_grid_view(&A.G, m, (double)o.known_dist);
+  // the grid over the free rows: no map behind it (the launches read the staged points), one item a row at the most
+  const double jd = (double)o.join_dist;
+  A.F.cap = q_max_rows, A.F.table = fxk_map_merge_table(q_max_rows);
+  A.F.md2 = jd * jd, A.F.inv_edge = 1.0 / (jd * (1.0 + 1.0 / 256.0));
+  A.header = m->a.header, A.records = m->a.records, A.acc = m->a.acc;
+  query_args(&A.K, kp, max_scans, max_total, n_scans, q_max_rows);
+  A.loc = loc, A.map_id_of_row = map_id_of_row;
+  A.min_obs = o.min_obs, A.require_flags = o.require_flags, A.segment = o.segment, A.mode = o.mode;
+  A.result = (uint32_t *)result, A.new_id = new_id_of_row;
+  FX_MAP_RUN(fxk_map_discover, "map discover scratch");
   return FX_OK;
 }
 

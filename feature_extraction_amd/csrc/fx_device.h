@@ -279,6 +279,9 @@ struct FxMapMergeArgs {
   int32_t *prop;                // [cap]: the g landmark h proposes, -1: none
   unsigned long long *keep;     // [cap]: (first_scan << 32) | h of g's proposers, atomic min
   int32_t *pred, *succ;         // [cap]: the kept link into / out of the landmark, -1: none
+  // a grid over points that are no landmarks (fx_map_discover's free rows); points null: the grid is over the map's landmarks
+  const double2 *points;        // [cap]: (x, y) of item i; every one takes part
+  const uint32_t *n_points;     // how many there are, read on the device and clipped to cap
 };
 // fx_map_localize (csrc/fx_map_localize.hip): a launch set's arguments.  G describes the grid over the map (its gate is the
 // search distance; the merge's per-landmark arrays are null); the last group is the context's scratch, [q_max_rows] each.
@@ -397,6 +400,35 @@ struct FxMapExpectArgs {
   uint32_t *cnt_s;              // [cap]: ... seen counts
   uint32_t *st;                 // [FX_MAP_EXPECT_ST_WORDS]
   int32_t *tgt;                 // [q_max_rows]: the landmark the row names, -1: a finite row of a used scan that names none, -2: any other
+};
+// fx_map_discover (csrc/fx_map_discover.hip): a launch set's arguments.  G describes the grid over the map (its gate is known_dist;
+// the merge's per-landmark arrays are null), F the grid over the free rows' world points (its gate is join_dist; it reads `pts`,
+// not the map); the last group is the context's scratch, sized by the map's max_landmarks (G.cap) and by q_max_rows.  A free row
+// is known by its number j in ascending row order from k_disc_stage on.
+#define FX_MAP_DISCOVER_ST_WORDS 16  // 0 .. 13 the words of fx_map_discover_result up to `refused`, in its order; 14 confirmed leaders
+#define FX_DISC_NONE 0xffffffffu
+struct FxMapDiscoverArgs {
+  FxMapMergeArgs G, F;
+  void *header;                 // fx_map_header
+  void *records;                // fx_map_landmark [cap]
+  double *acc;                  // [cap][FX_MAP_ACC]
+  FxKpQuery K;
+  const void *loc;              // fx_localization [n_scans]
+  const int32_t *map_id_of_row; // [q_max_rows]
+  uint32_t min_obs, require_flags, segment, mode;
+  uint32_t *result;             // fx_map_discover_result or null
+  int32_t *new_id;              // [q_max_rows] or null
+  uint32_t *st;                 // [FX_MAP_DISCOVER_ST_WORDS]; sup follows it (one memset clears both)
+  uint32_t *sup;                // [q_max_rows]: kept rows attached to leader j, the scans that saw it
+  int32_t *fidx;                // [q_max_rows]: row r is free row fidx[r]; -1: not free.  Until k_disc_stage: r's place among its block's free rows
+  uint32_t *bsum_f, *bsum_c;    // [2][blocks of rows] each: the block's free rows / confirmed leaders, then their prefix (the second row is unused: 0)
+  double2 *pts;                 // [q_max_rows]: the world (x, y) of free row j
+  uint2 *src;                   // [q_max_rows]: (row, scan) of free row j
+  uint32_t *lead;               // [q_max_rows]: 1: free row j is a leader
+  uint32_t *att;                // [q_max_rows]: the leader free row j attaches to, FX_DISC_NONE: an orphan
+  unsigned long long *ad2;      // [q_max_rows]: its squared xy distance from that leader as bits
+  uint32_t *kept;               // [q_max_rows]: 1: free row j is its scan's observation of its leader
+  uint32_t *rank_c;             // [q_max_rows]: a confirmed leader's place among its block's, FX_DISC_NONE: not one
 };
 // fx_map_append, fx_map_append_host (csrc/fx_map_append.hip): a launch set's arguments.  The source as the kernels read it is six
 // pointers: a map's own buffers, or the sections of a snapshot staged in the context's scratch; the two look the same.

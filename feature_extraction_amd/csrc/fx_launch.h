@@ -113,6 +113,8 @@ hipError_t fxk_map_observe(hipStream_t s, const FxMapObserveArgs &A);
 size_t fxk_map_observe_scratch(FxMapObserveArgs *A, uint8_t *base);
 hipError_t fxk_map_expect(hipStream_t s, const FxMapExpectArgs &A);
 size_t fxk_map_expect_scratch(FxMapExpectArgs *A, uint8_t *base);
+hipError_t fxk_map_discover(hipStream_t s, const FxMapDiscoverArgs &A);
+size_t fxk_map_discover_scratch(FxMapDiscoverArgs *A, uint8_t *base);
 hipError_t fxk_map_find_loop(hipStream_t s, const FxMapFindLoopArgs &A);
 size_t fxk_map_find_loop_scratch(FxMapFindLoopArgs *A, uint8_t *base);
 hipError_t fxk_map_compact(hipStream_t s, const FxMapCompactArgs &A);

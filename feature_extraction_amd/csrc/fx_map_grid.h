@@ -26,6 +26,8 @@
 // The proof asks nothing of p and q but that they are doubles that pass the gate, so it covers a query point that is no landmark
 // (fx_map_localize's world point of a keypoint row) as it covers a landmark: a query below 2^41 searches its 3 x 3 cells and the
 // far bucket, one beyond searches the far bucket alone.  A query coordinate that is not finite passes no gate and finds nothing.
+// For the same reason the items of a grid need not be landmarks: fx_map_discover (csrc/fx_map_discover.hip) builds a second grid
+// over the world points of its free rows (FxMapMergeArgs::points, the same build launches) and walks it with grid_neighbourhood.
 #ifndef FX_MAP_GRID_H_
 #define FX_MAP_GRID_H_
 #include <hip/hip_runtime.h>

@@ -1,6 +1,8 @@
 // fx_map_grid.hip — building the hashed grid over the map's live landmarks (fx_map_grid.h) for fx_map_merge and fx_map_localize.
+// The same launches build a grid over points that are no landmarks (A.points given: fx_map_discover's free rows): grid_item is the
+// one place that knows which of the two an item is.
 //
-// Launches, in stream order (FXMM_WG = 256 landmarks or buckets a workgroup; N = the header's n_landmarks):
+// Launches, in stream order (FXMM_WG = 256 landmarks or buckets a workgroup; N = the header's n_landmarks, or *A.n_points):
 //   k_mm_clear    the buckets' counts and the state words to 0
 //   k_mm_mark     a thread a landmark: does it take part (alias -1, n_obs >= 1, x and y finite), its bucket, the bucket's count
 //                 (32-bit atomic add); when the caller is the merge (A.prop given) it resets the landmark's proposal, its
@@ -21,6 +23,23 @@ using namespace fxg;
 
 static_assert(sizeof(fx_map_landmark) == 48 && sizeof(FxMapMergeCand) == 32, "include/fx.h");
 
+namespace {
+// the items the grid is built over: the map's landmarks, or the points of A.points
+__device__ __forceinline__ uint32_t grid_items(const FxMapMergeArgs &A) { return A.points ? min(*A.n_points, A.cap) : n_landmarks(A); }
+// item i < grid_items as the search reads it; false: it takes no part.  A point takes part always and carries no scan and no segment
+__device__ __forceinline__ bool grid_item(const FxMapMergeArgs &A, uint32_t i, FxMapMergeCand &c) {
+  c.id = i, c.pad_ = 0u;
+  if (A.points) {
+    const double2 p = A.points[i];
+    c.x = p.x, c.y = p.y, c.last_scan = 0u, c.segment = 0u;
+    return true;
+  }
+  const fx_map_landmark R = records(A)[i];
+  c.x = R.x, c.y = R.y, c.last_scan = R.last_scan, c.segment = R.segment;
+  return takes_part(A, i, R);
+}
+}  // namespace
+
 extern "C" __global__ __launch_bounds__(FXMM_WG) void k_mm_clear(FxMapMergeArgs A) {
   const uint32_t b = blockIdx.x * FXMM_WG + threadIdx.x;
   if (b <= A.table) A.count[b] = 0u;
@@ -29,11 +48,11 @@ extern "C" __global__ __launch_bounds__(FXMM_WG) void k_mm_clear(FxMapMergeArgs 
 
 extern "C" __global__ __launch_bounds__(FXMM_WG) void k_mm_mark(FxMapMergeArgs A) {
   const uint32_t i = blockIdx.x * FXMM_WG + threadIdx.x;
-  if (i >= n_landmarks(A)) return;
-  const fx_map_landmark R = records(A)[i];
+  if (i >= grid_items(A)) return;
+  FxMapMergeCand c;
   uint32_t b = FXMM_NONE;
-  if (takes_part(A, i, R)) {
-    const double tx = floor(R.x * A.inv_edge), ty = floor(R.y * A.inv_edge);
+  if (grid_item(A, i, c)) {
+    const double tx = floor(c.x * A.inv_edge), ty = floor(c.y * A.inv_edge);
     const bool far = !(fabs(tx) < kFar && fabs(ty) < kFar);
     b = far ? A.table : bucket_of_cell((long long)tx, (long long)ty, A.table);
     atomicAdd(&A.count[b], 1u);
@@ -63,14 +82,13 @@ extern "C" __global__ __launch_bounds__(FXMM_WG) void k_mm_top(FxMapMergeArgs A,
 
 extern "C" __global__ __launch_bounds__(FXMM_WG) void k_mm_scatter(FxMapMergeArgs A) {
   const uint32_t i = blockIdx.x * FXMM_WG + threadIdx.x;
-  if (i >= n_landmarks(A)) return;
+  if (i >= grid_items(A)) return;
   const uint32_t b = A.bucket[i];
   if (b == FXMM_NONE) return;
   const uint32_t slot = bucket_begin(A, b) + (atomicSub(&A.count[b], 1u) - 1u);  // any order inside the bucket
   if (slot >= A.cap) return;  // (cannot happen: the counts are of landmarks below cap)
-  const fx_map_landmark R = records(A)[i];
   FxMapMergeCand c;
-  c.x = R.x, c.y = R.y, c.last_scan = R.last_scan, c.segment = R.segment, c.id = i, c.pad_ = 0u;
+  (void)grid_item(A, i, c);
   A.cand[slot] = c;
 }
 

@@ -966,7 +966,8 @@ fx_status fx_map_relocalize(fx_ctx *ctx, fx_map *map,
  * that.  n_obs is a 32-bit count.  One lane folds a landmark's list and every entry of a list is ranked against the whole list:
  * time, not the result, grows with the longest list.  New in 0.7 (added symbols only).
  * The call removes no landmark either: fx_map_expect (below) counts, from the same inputs, how often each landmark should have
- * been seen and how often it was, and fx_map_retire (below fx_map_compact) takes out the ones those counts condemn. */
+ * been seen and how often it was, and fx_map_retire (below fx_map_compact) takes out the ones those counts condemn.
+ * The landmarks this call does not create, fx_map_discover (below fx_map_expect) does: from the unmatched rows of the same inputs. */
 #define FX_MAP_LM_OBSERVED 0x8u   /* fx_map_landmark flags: gained at least one observation through fx_map_observe */
 #define FX_OBS_APPLY 0u
 #define FX_OBS_DRY_RUN 1u         /* report everything, change no byte of the map */
@@ -1063,6 +1064,91 @@ fx_status fx_map_expect(fx_ctx *ctx, fx_map *map,
     const int32_t *map_id_of_row_device, uint32_t q_max_rows,
     const fx_map_expect_options *opt /* NULL: defaults */, fx_map_expect_result *result_device /* or NULL */,
     uint32_t *expected_of_landmark_device /* [max_landmarks] */, uint32_t *seen_of_landmark_device /* [max_landmarks] */);
+
+/* ---- Learning new poles: the unexplained rows of localised scans that fall on one spot again and again made landmarks ----
+ * fx_map_observe re-estimates the landmarks the scans matched and fx_map_expect / fx_map_retire take out the ones that are gone;
+ * a pole put up after the mapping run stays an unmatched row in every scan for ever.  fx_map_discover lets it enter the map: the
+ * rows of used scans that name no landmark and stand nowhere near a known one, yet fall within join_dist of one spot of the map
+ * frame in at least min_obs scans of the call, become a landmark.  The inputs are exactly fx_map_observe's and fx_map_expect's, so
+ * the three calls can follow one fx_map_localize.  The call is enqueued on the context's stream: no host read, no host
+ * synchronisation, no allocation in the steady state (its scratch is the context-owned buffer of fx_map_merge, sized by the map's
+ * max_landmarks and by q_max_rows).  Every floating-point step is fp64 with no contraction and no fma; kd = (double)known_dist,
+ * jd = (double)join_dist; a d2 is dx dx + dy dy; "d2 bits" is its uint64 pattern.
+ * Sizes: S, rows, scan(r) and the non-rows exactly as in fx_map_localize; N = header.n_landmarks, clipped to the map's
+ * max_landmarks.
+ * Segment: seg is opt.segment, FX_LOC_LAST_SEGMENT standing for header.segments - 1 read on the device.  The call is REFUSED when
+ * that resolves to nothing (a map of no segment) or seg >= header.segments: refused = 1, every other result word 0 except first_id
+ * (below), every word of new_id_of_row -1, and the map keeps every byte.
+ * Used scans: scan b < S is used iff (loc[b].flags & require_flags) == require_flags and c, s, tx, ty and tz of loc[b].pose are all
+ * finite (fx_map_observe's clause).  scans_used counts them.
+ * Unmatched rows: row r < rows of a used scan is unmatched iff its x, y and z are finite, map_id_of_row[r] < 0 and its world point
+ * (wx, wy, wz) under loc[b].pose (fx_track_landmarks's fusing clause word for word, the same device function) is finite in all
+ * three.  An id >= 0 is never dereferenced: the call is memory-safe on any table.  `unmatched` counts these rows.
+ * Known: an unmatched row is known iff some g < N has alias[g] == -1, n_obs[g] >= 1, finite x[g] and y[g], segment[g] == seg and,
+ * with dx = x[g] - wx, dy = y[g] - wy, d2 <= kd kd: the merge's live set, and the segment.  There is no min_landmark_obs: young
+ * landmarks explain rows too.  `known` counts these rows; the other unmatched rows are FREE (free_rows).
+ * Leaders: a free row r is a leader iff no free row r' < r has d2 <= jd jd, dx = wx[r'] - wx[r], dy = wy[r'] - wy[r].  Leaders are
+ * pairwise further than jd apart and the predicate is a pure function of the set of free rows.  `leaders` counts them.
+ * Attachment: every free row attaches to the leader l of lowest (d2 bits, l) among the leaders with d2 <= jd jd; a leader
+ * attaches to itself at d2 = 0.  A free row with no such leader is an ORPHAN (orphans): it lies within jd of an earlier non-leader
+ * only, and a later call picks it up.
+ * One observation a scan a leader: among the rows of one scan attached to the same leader the one of lowest (d2 bits, row) is
+ * kept; the others count in `duplicates`.  k[l] is the number kept: the number of distinct scans that saw l.
+ * Confirmation: l is confirmed iff k[l] >= min_obs.  The kept rows of unconfirmed leaders count in `weak`.
+ * Ids: first_id = header.n_needed as the call finds it.  The confirmed leaders, in ascending leader row, get first_id, first_id +
+ * 1, ...  An id is stored iff it is below the map's max_landmarks; fx_map_update's rule applies to the others: they are counted in
+ * n_needed and in not_stored, FX_MAP_FULL is set, their kept rows report -1 and count in `lost`.  `created` counts the stored ids,
+ * `added` the kept rows of stored ids.  unmatched = known + free_rows, and free_rows = orphans + duplicates + weak + added + lost.
+ * Record of a stored id: fx_map_update's clause for a new landmark: the sums start at 0, the anchor is the (wx, wy) of its first
+ * kept row, which is the leader, and every kept row is added in ascending row by "Adding an observation", one fp64 chain on one
+ * lane.  n_obs = k; x, y, z and rms_xy by the "Records" clause; first_scan = last_scan = header.scans - 1 (0 when header.scans is
+ * 0): the end of the mapping run, the map's "now"; segment = seg; flags = FX_MAP_LM_DISCOVERED; alias stays -1.
+ * Header: n_needed += the number of confirmed leaders, n_landmarks = min(n_needed, max_landmarks), n_obs += added, FX_MAP_FULL is
+ * set when not_stored > 0.  Nothing else changes: the carry, the carry scan and every existing record, sum and alias entry keep
+ * their bytes.
+ * Outputs, every word written in both modes: new_id_of_row[r], all q_max_rows words: the stored id for a kept row of a stored
+ * landmark, else -1; result: sixteen words, reserved = 0, 0.
+ * FX_DISC_DRY_RUN: both outputs are what the applying call would write, and the map is bit for bit what it was.
+ * FX_ERR_INVALID_ARG with the reason in fx_last_error(), nothing launched, no output byte touched, the map unchanged: a NULL ctx,
+ * map, kp_block_device or loc_device; a NULL map_id_of_row_device with q_max_rows != 0; a map of another context; n_scans == 0 or
+ * n_scans > max_scans; known_dist or join_dist not finite and positive; (double)known_dist < 2.0 (double)join_dist; min_obs == 0;
+ * unknown require_flags bits; segment == FX_LOC_ANY_SEGMENT; mode > 1; reserved != 0; a keypoint block not 16-byte, records not
+ * 8-byte, word arrays not 4-byte aligned.
+ * Why known_dist >= 2 join_dist: every kept row lies within jd of its leader and so does the landmark's mean, so a kept row lies
+ * within 2 jd of the landmark: a second call on the same inputs finds those rows known and creates no twin.
+ * The same bytes from run to run and with any number of contexts in flight: every decision is an integer or a minimum over a total
+ * order (32-bit integer atomics only, sums), every fp64 sum an ordered chain on one lane; no floating-point atomics anywhere, and
+ * the search structures (two hashed grids, fx_map_merge's, with the cell edges known_dist (1 + 2^-8) over the landmarks and
+ * join_dist (1 + 2^-8) over the free rows) never show in a byte.
+ * The defaults are choices, not measurements: 0.30 is inlier_dist / merge_dist, and 1.0 m is a little over 2 join_dist twice.
+ * Limits: a pole must appear in min_obs scans of ONE call: a caller that hands over a scan a call discovers nothing with the
+ * default.  A new pole closer than known_dist to a live landmark of the segment is never discovered.  Discovered landmarks share
+ * one scan number: fx_map_merge therefore never joins two of them, and fx_map_close_loop moves them with the loop's end.  Feeding
+ * the same scans through fx_map_update as well counts them twice.  A crowded cell is walked by one lane a row: time, not the
+ * result, grows with the square of a cell's population.  New in 0.7 (added symbols only). */
+#define FX_MAP_LM_DISCOVERED 0x10u   /* fx_map_landmark flags: created by fx_map_discover */
+#define FX_DISC_APPLY 0u
+#define FX_DISC_DRY_RUN 1u           /* report everything, change no byte of the map */
+typedef struct fx_map_discover_options {   /* 32 B */
+  float known_dist;       /* a row this close (xy) to a live landmark of the segment is explained; finite, > 0; default 1.0 */
+  float join_dist;        /* rows of one new pole lie within this of its leader; finite, > 0; default 0.30 */
+  uint32_t min_obs;       /* distinct scans a new pole needs within this call; >= 1; default 3 */
+  uint32_t require_flags; /* as fx_map_observe; default FX_LOC_VALID */
+  uint32_t segment;       /* a global segment number or FX_LOC_LAST_SEGMENT (default); FX_LOC_ANY_SEGMENT is refused */
+  uint32_t mode;          /* FX_DISC_APPLY (default), FX_DISC_DRY_RUN */
+  uint32_t reserved[2];   /* 0 */
+} fx_map_discover_options;
+typedef struct fx_map_discover_result {    /* 64 B */
+  uint32_t scans_used, unmatched, known, free_rows, leaders, orphans, duplicates, weak,
+           added, lost, created, not_stored, first_id, refused, reserved[2];
+} fx_map_discover_result;
+void fx_map_discover_options_default(fx_map_discover_options *o);
+fx_status fx_map_discover(fx_ctx *ctx, fx_map *map,
+    const void *kp_block_device, uint32_t max_scans, uint32_t max_total_keypoints,   /* what the localise was given */
+    const fx_localization *loc_device, uint32_t n_scans,                            /* what it wrote */
+    const int32_t *map_id_of_row_device, uint32_t q_max_rows,
+    const fx_map_discover_options *opt /* NULL: defaults */, fx_map_discover_result *result_device /* or NULL */,
+    int32_t *new_id_of_row_device /* [q_max_rows] or NULL */);
 
 /* ---- Compacting the map: the absorbed fragments and the let-go landmarks taken out, the others renumbered ----
  * fx_map_merge leaves every absorbed fragment in place: its record, its sums and its alias entry; every grid build marks and skips

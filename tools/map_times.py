@@ -59,6 +59,13 @@ and seen from the localise's device outputs (timed: fx_map_expect, FX_EXPECT_ADD
 so that landmarks beyond the 64 a scan sees are expected: the grid build, the memset, the three launches) and retires on those
 counters (timed: fx_map_retire, min_expected 1, seen / expected below 1 / 2); then it resets, updates and merges again and compacts
 (timed: fx_map_compact, the same launches without the rule).  One pair of HIP events around each call.  No target is set.
+  timeout -k 10 600 python tools/map_times.py --discover [--sizes 1000,100000,1000000] [--warmup 1] [--repeats 5] [--out profiles/map_discover_times.txt]
+
+times fx_map_discover next to fx_map_observe on the synthetic maps of --observe, with room for 8 more landmarks: the 8 scans are taken
+at one place, each 64 keypoints on the map's poles and 8 on poles the map does not hold (2 cm of jitter).  Every repeat resets the map,
+updates it, localises (timed), observes (timed: the yardstick, on the same inputs) and discovers (timed: fx_map_discover with its
+defaults reading the localise's records and table where they are: the two grid builds, the memset, the ten launches).  One pair of
+HIP events around each call.  Reported per size: the medians and both results.  No target is set.
   timeout -k 10 600 python tools/map_times.py --loop [--sizes 1000,100000,1000000] [--warmup 1] [--repeats 5] [--out profiles/map_loop_times.txt]
 
 times fx_map_close_loop on the same synthetic maps as one segment: the first fragments (scans 0-1) are the old landmarks, the second
@@ -346,11 +353,13 @@ def measure_relocalize(ctx, n, warmup, repeats, n_scans=8):
             "valid": int((rec["flags"] & capi.FX_RELOC_VALID != 0).sum()), "n_hyp_mean": float(rec["n_hyp"].mean()), "n_seeds": rec["n_seeds"].tolist()}
 
 
-def localize_scene(ctx, n, n_scans, cut_link):
+def localize_scene(ctx, n, n_scans, cut_link, new_poles=0):
     """What --join and --observe localise against: merge_case(n) through one track and one update into a map of n landmarks
     (cut_link: the link scan 2 -> scan 1 made unusable, the second fragments a segment of their own), and n_scans scans of the 64
-    poles nearest to a random position inside the map, seen from a random pose there, with the true poses as priors.  Returns (the
-    map, the batch's block, the track's outputs, the scans' block, the priors): device tensors."""
+    poles nearest to a random position inside the map, seen from a random pose there, with the true poses as priors.  new_poles
+    (--discover): the map has room for that many more landmarks, every scan is taken at ONE position (another yaw each) and ends in
+    that many rows on poles the map does not hold, within 30 m of the position and 2 cm of jitter.  Returns (the map, the batch's
+    block, the track's outputs, the scans' block, the priors): device tensors."""
     import torch
     blk, (S, T), m, inl, reg, M = merge_case(n, np.random.default_rng(n))
     if cut_link:
@@ -359,26 +368,33 @@ def localize_scene(ctx, n, n_scans, cut_link):
     md, inl_t = torch.from_numpy(m.view(np.int32).reshape(-1, 8).copy()).cuda(), torch.from_numpy(inl).cuda()
     reg_t = torch.from_numpy(reg.view(np.float64).reshape(-1, 8).copy()).cuda()
     out = ctx.track_landmarks(kp, md, inl_t, reg_t, S, max_landmarks=n)
-    mp = ctx.map_create(n, 16)
+    mp = ctx.map_create(n + new_poles, 16)
     mp.update(kp, out, overlap=False, row_ids=False)
     lm = mp.landmarks(0, mp.header()["n_landmarks"])
     xy = np.stack([lm["x"], lm["y"]], axis=1)
     rng = np.random.default_rng(n + 1)
     K = capi.FX_RELOC_MAX_KP
-    rows, pri = np.zeros((n_scans * K, 4), np.float32), np.zeros(n_scans, capi.POSE_DTYPE)
+    per = K + new_poles
+    rows, pri = np.zeros((n_scans * per, 4), np.float32), np.zeros(n_scans, capi.POSE_DTYPE)
+    one_place = xy[rng.integers(len(xy))] + rng.uniform(-5.0, 5.0, 2) if new_poles else None
+    new_xy = one_place + rng.uniform(-30.0, 30.0, (new_poles, 2)) if new_poles else None
     for b in range(n_scans):
         at, yaw = xy[rng.integers(len(xy))] + rng.uniform(-5.0, 5.0, 2), rng.uniform(-np.pi, np.pi)
+        if new_poles:
+            at = one_place
         near = np.argsort(((xy - at) ** 2).sum(axis=1))[:K]
         d = xy[near] - at
+        if new_poles:
+            d = np.concatenate([d, new_xy + rng.normal(0.0, 0.02, new_xy.shape) - at])
         c, s = np.cos(yaw), np.sin(yaw)
-        rows[b * K:(b + 1) * K, 0], rows[b * K:(b + 1) * K, 1], rows[b * K:(b + 1) * K, 2] = c * d[:, 0] + s * d[:, 1], -s * d[:, 0] + c * d[:, 1], 1.0
+        rows[b * per:(b + 1) * per, 0], rows[b * per:(b + 1) * per, 1], rows[b * per:(b + 1) * per, 2] = c * d[:, 0] + s * d[:, 1], -s * d[:, 0] + c * d[:, 1], 1.0
         pri[b] = (c, s, at[0], at[1], 0.0, 0, 0)
     T2 = len(rows)
     k0, n_blk = capi.keypoint_block_layout(n_scans, T2)
     sb = np.zeros((n_blk, 4), np.float32)
     u = sb.view(np.uint32).reshape(-1)
     u[:4] = (n_scans, T2, 0, T2)
-    u[4:4 + n_scans + 1] = np.arange(n_scans + 1) * K
+    u[4:4 + n_scans + 1] = np.arange(n_scans + 1) * per
     sb[k0:k0 + T2] = rows
     skp = (torch.from_numpy(sb.view(np.uint8).reshape(-1)).cuda(), n_scans, T2)
     pri_t = torch.from_numpy(pri.view(np.float64).reshape(-1, 6).copy()).cuda()
@@ -452,6 +468,66 @@ def measure_observe(ctx, n, warmup, repeats, n_scans=8):
         out[k] = statistics.median(v)
         out[k + "_min_max"] = [min(v), max(v)]
     return out
+
+
+def measure_discover(ctx, n, warmup, repeats, n_scans=8, new_poles=8):
+    import torch
+    mp, kp, out, skp, pri_t = localize_scene(ctx, n, n_scans, cut_link=False, new_poles=new_poles)
+    ores = torch.zeros((8,), dtype=torch.int32, device="cuda")
+    dres = torch.zeros((16,), dtype=torch.int32, device="cuda")
+    stream = torch.cuda.ExternalStream(ctx.stream_ptr())
+    torch.cuda.synchronize()
+    t = {"localize_ms": [], "observe_ms": [], "discover_ms": []}
+    first = None
+    for rep in range(warmup + repeats):
+        mp.reset()
+        mp.update(kp, out, overlap=False, row_ids=False)
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
+        e[0].record(stream)
+        recs, ids, _ = mp.localize(skp, pri_t, n_scans, nearest=False, segment=capi.FX_LOC_ANY_SEGMENT)
+        e[1].record(stream), e[2].record(stream)
+        mp.observe(skp, recs, n_scans, ids, out=ores, gained=False, observed=False)
+        e[3].record(stream), e[4].record(stream)
+        mp.discover(skp, recs, n_scans, ids, out=dres, new_id=False)
+        e[5].record(stream)
+        ctx.synchronize()
+        got = (capi.discover_records(dres), capi.observe_records(ores))
+        first = got if first is None else first
+        assert got == first and got[0]["created"] > 0, (got, first)
+        if rep >= warmup:
+            for k, (a, b) in zip(t, ((0, 1), (2, 3), (4, 5))):
+                t[k].append(e[a].elapsed_time(e[b]))
+    mp.close()
+    out = {"landmarks": n, "scans": n_scans, "discover": first[0], "observe": first[1]}
+    for k, v in t.items():
+        out[k] = statistics.median(v)
+        out[k + "_min_max"] = [min(v), max(v)]
+    return out
+
+
+def main_discover(a):
+    sizes = [int(x) for x in a.sizes.split(",")]
+    ctx = capi.Context(capi.params("launch"), capi.limits(2, 1024))
+    rows = [measure_discover(ctx, n, a.warmup, a.repeats) for n in sizes]
+    ctx.close()
+    lines = [f"fx_map_discover next to fx_map_observe, both behind one fx_map_localize, on synthetic maps (tools/map_times.py --discover): 1 pole",
+             f"per 250 m^2, one segment; a call: 8 scans taken at one place, 64 keypoints on the map's poles and 8 on poles it does not hold each,",
+             f"localised (any segment, the true poses as priors), then observed and then discovered from the localise's device outputs (default",
+             f"options); one context, HIP events around each call, median of {a.repeats} after {a.warmup} warm-up; ms",
+             f"{'landmarks':>10} {'used':>5} {'unmatched':>10} {'known':>6} {'free':>5} {'leaders':>8} {'dup':>4} {'weak':>5} {'added':>6} {'created':>8} "
+             f"{'discover':>9} {'min':>8} {'max':>8} {'observe':>9} {'min':>8} {'max':>8} {'localize':>9}"]
+    for r in rows:
+        q = r["discover"]
+        lines.append(f"{r['landmarks']:>10} {q['scans_used']:>5} {q['unmatched']:>10} {q['known']:>6} {q['free_rows']:>5} {q['leaders']:>8} {q['duplicates']:>4} "
+                     f"{q['weak']:>5} {q['added']:>6} {q['created']:>8} {r['discover_ms']:>9.3f} {r['discover_ms_min_max'][0]:>8.3f} {r['discover_ms_min_max'][1]:>8.3f} "
+                     f"{r['observe_ms']:>9.3f} {r['observe_ms_min_max'][0]:>8.3f} {r['observe_ms_min_max'][1]:>8.3f} {r['localize_ms']:>9.3f}")
+    s = "\n".join(lines)
+    print(s)
+    print(json.dumps(rows))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(s + "\n")
 
 
 EXPECT_OPTS = dict(x_min=-80.0, x_max=80.0, y_min=-80.0, y_max=80.0, min_range=0.0, max_range=80.0)
@@ -1051,6 +1127,7 @@ def main():
     ap.add_argument("--join", action="store_true", help="time fx_map_join_segments on two-segment synthetic maps instead")
     ap.add_argument("--observe", action="store_true", help="time fx_map_observe behind fx_map_localize on the synthetic maps of --join instead")
     ap.add_argument("--expect", action="store_true", help="time fx_map_expect behind fx_map_localize and fx_map_retire next to fx_map_compact on the synthetic maps of --join instead")
+    ap.add_argument("--discover", action="store_true", help="time fx_map_discover next to fx_map_observe behind fx_map_localize on the synthetic maps of --join instead")
     ap.add_argument("--loop", action="store_true", help="time fx_map_close_loop on the synthetic maps taken as one loop instead")
     ap.add_argument("--find-loop", action="store_true", help="time fx_map_find_loop next to fx_map_relocalize on one-segment synthetic maps instead")
     ap.add_argument("--append", action="store_true", help="time fx_map_append and fx_map_append_host next to fx_map_import_host and a plain copy instead")
@@ -1078,6 +1155,8 @@ def main():
         return main_observe(a)
     if a.expect:
         return main_expect(a)
+    if a.discover:
+        return main_discover(a)
     if a.loop:
         return main_loop(a)
     if a.find_loop:
