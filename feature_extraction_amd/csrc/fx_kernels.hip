@@ -4350,6 +4350,18 @@ __device__ __forceinline__ void classify_rows(const FxDevParams &P, const FxBuff
     dst[pos] = row;
   }
 }
+// RNG ordinals of one scan, by one whole wavefront: 3DSC draws its three numbers only for keypoints that have
+// neighbours, so keypoint k of the scan's K (rows row0 ..) takes the x-axis number (keypoints before it that have a neighbour).
+// nbr[k] != 0: keypoint k has one (the gather's flags: in LDS, or the scan's slice of kp_nbrs).
+__device__ __forceinline__ void rng_ordinals(const FxBuffers &B, uint32_t row0, uint32_t K, uint32_t lane, const uint32_t *nbr) {
+  uint32_t base = 0;
+  for (uint32_t k0 = 0; k0 < K; k0 += 64) {
+    const uint32_t k = k0 + lane;
+    const unsigned long long m = __ballot(k < K && nbr[k] != 0u);
+    if (k < K) B.row_xa[row0 + k] = B.xaxis[base + lanes_below(m)];
+    base += (uint32_t)__popcll(m);
+  }
+}
 
 // ---------------------------------------------------------------- k_gather
 // Keypoints of the scan are binned into xy cells at least one support radius wide, and every cell lists the
@@ -4357,6 +4369,26 @@ __device__ __forceinline__ void classify_rows(const FxDevParams &P, const FxBuff
 // be within reach.  Points with candidates are parked in a per-wavefront LDS queue and tested with all lanes busy
 // (in firing order only some lanes of a wavefront hold such points).  Groups of 64 points that k_prep found
 // wholly out of the filter box's reach are not even loaded.
+//
+// gather_body<NT, PASSES, MODE> is the algorithm; a pass over the scan (one, but for PASSES) calls these phases in order:
+//   gather_tables           keypoints -> LDS, their box, the cells' counts, prefix and fill; returns the grid (GatherGrid: the box,
+//                           the cells' widths and numbers, the point-to-cell rule)
+//   gather_slice_positions  MODE 2: this slice's first position in every list, the prefix over the counting pass's gather_cnt
+//   GatherStream            the slice's range and step, the near-sector words (one load per 64 tiles, a readlane a tile), the
+//                           predicated tile loads — the next tile's are in flight while this one is parked
+//   gather_park             a load's points: rotated, tested against the box, those whose cell lists keypoints parked in the
+//                           wavefront's queue; gather_drain once more than 64 wait: each against its cell's keypoints
+//   the hit sink            what becomes of a hit (keypoint, point): hit_count (MODE 1), hit_direct (the list position is an LDS
+//                           counter of this workgroup's: MODE 2, and MODE 0 alone on its scan), hit_staged (MODE 0, several
+//                           workgroups a scan: gather_flush appends in bulk; the stage full, one global atomic) — chosen in gather_drain
+//   gather_tail             MODE 1: the slice's counts; alone on the scan: the counts written back, classify_rows, rng_ordinals
+// Instances:
+//   k_gather          <256, -, 0>   1 workgroup a scan (direct, its own tail) or several (staged; k_rng_ord is the tail)
+//   k_gather_wide     <1024, -, 0>  1 workgroup a scan, always direct
+//   k_gather_count    <256, -, 1>   several workgroups a scan; then
+//   k_gather_scatter  <256, -, 2>   the same slices, direct (k_rng_ord is the tail)
+//   k_gather_passes   <1024, +, 0>  max_keypoints beyond FX_GATHER_KCAP: 1 workgroup a scan (direct; the ordinals after the last pass,
+//                                   over kp_nbrs) or several (staged)
 #ifndef FX_GATHER_T
 #define FX_GATHER_T 256  // (384 and 512 threads measured: see DESIGN.md)
 #endif
@@ -4366,9 +4398,6 @@ __device__ __forceinline__ void classify_rows(const FxDevParams &P, const FxBuff
 #ifndef FX_GATHER_STAGE
 #define FX_GATHER_STAGE 384  // hits one workgroup stages between flushes (a larger stage costs more in occupancy than it saves in flushes)
 #endif
-#ifndef FX_GATHER_DIRECT
-#define FX_GATHER_DIRECT 1   // one workgroup per scan: hits go straight to their list slots (positions are LDS counters)
-#endif
 #ifndef FX_GATHER_QUEUE
 #define FX_GATHER_QUEUE 128  // points one wavefront of k_gather parks before it drains them (drained once more than 64 are waiting:
                              // measured 72 .. 192 — 96 to 160 are level, 1.2 % above 80; k_gather_wide keeps 80: sixteen queues)
@@ -4376,103 +4405,116 @@ __device__ __forceinline__ void classify_rows(const FxDevParams &P, const FxBuff
 #define FX_GATHER_QUEUE_WIDE 80
 #define FX_GATHER_KCAP 2048  // keypoints the LDS tables hold (148 KB with the wide workgroup's queues); scans with more are gathered in passes
 __host__ __device__ constexpr uint32_t gather_queue(uint32_t nt) { return nt <= 256u ? (uint32_t)FX_GATHER_QUEUE : (uint32_t)FX_GATHER_QUEUE_WIDE; }
-__host__ __device__ inline uint32_t gather_words(uint32_t mk, uint32_t nt) {
-  uint32_t w = 32 + 4 * mk;                                   // scratch, keypoints
-  w += FX_GATHER_CELLS + 4;                                   // cell table (the fill cursors borrow the staging area)
-  w += ((9 * mk + 1) / 2 + 3) & ~3u;                          // cell lists (uint16)
-  w += (5 * mk + 3) & ~3u;                                    // staged hits per keypoint, reserved list positions, list lengths, has-a-neighbour flags, overflow slots
-  w += FX_GATHER_STAGE + 4 * FX_GATHER_STAGE;                 // staged hits: meta, points
-  w += (nt / 64) * gather_queue(nt) * 5;                      // per-wavefront queues: points, cell info
-  return w;
+// Word offsets into the LDS image of a workgroup of nt threads whose tables hold mk keypoints: the device's carve (GatherMem) and the
+// host's size (end) both come from here.
+//   w       [32] scratch words, see GW_*                      kp     float4 [mk] keypoints
+//   cell    [CELLS + 4] list start | entries << 20            flat   uint16 [9 mk] keypoint ids, cell by cell
+//   per keypoint, [mk] each: kcnt staged hits, kbase reserved list position, kpos list length so far (list positions of the
+//           workgroup's own), knbr 1: some point lies within the search radius (one workgroup per scan), kovf overflow-region
+//           slot of the keypoint's staged ordinal 0 (entries beyond list_cap)
+//   the stage (hits are staged in LDS and appended to the keypoints' lists in bulk: one global atomic per (keypoint, flush) reserves
+//           the slots instead of one returning atomic per hit): smeta [STAGE] keypoint << 16 | staged ordinal, spt float4 [STAGE] points
+//   cur     [CELLS] fill cursors while the lists are built: they borrow the staged points
+//   q_pt    float4 [nt / 64][queue], q_info [nt / 64][queue]: the per-wavefront queues, points and their cell words
+struct GatherLds {
+  uint32_t w, kp, cell, flat, kcnt, kbase, kpos, knbr, kovf, smeta, spt, cur, q_pt, q_info, end;
+  __host__ __device__ constexpr GatherLds(uint32_t mk, uint32_t nt)
+      : w(0), kp(32), cell(kp + 4 * mk), flat(cell + FX_GATHER_CELLS + 4),
+        kcnt(flat + a4((9 * mk + 1) / 2)), kbase(kcnt + mk), kpos(kbase + mk), knbr(kpos + mk), kovf(knbr + mk),
+        smeta(kcnt + a4(5 * mk)), spt(smeta + FX_GATHER_STAGE), cur(spt),
+        q_pt(spt + 4 * FX_GATHER_STAGE), q_info(q_pt + 4 * (nt / 64) * gather_queue(nt)), end(q_info + (nt / 64) * gather_queue(nt)) {}
+};
+// scratch words: [0..5] the keypoints' box (ordered uints: min, max of x, of y, of z); hits in the stage; entries in the scan's
+// overflow region (a workgroup with list positions of its own)
+enum : uint32_t { GW_BOX = 0, GW_STAGED = 8, GW_OVF = 9 };
+// whatever mk up to FX_GATHER_KCAP: every float4 region starts on four words, the cursors end within the stage they borrow, the image
+// fits a CU's 160 KiB (the wide instance's at FX_GATHER_KCAP keypoints is the largest)
+__host__ __device__ constexpr bool gather_lds_ok(uint32_t nt) {
+  for (uint32_t mk = 0; mk <= FX_GATHER_KCAP; ++mk) {
+    const GatherLds L(mk, nt);
+    if (L.kp % 4 || L.spt % 4 || L.q_pt % 4 || L.cur + FX_GATHER_CELLS > L.q_pt || L.end * 4 > 160 * 1024) return false;
+  }
+  return true;
 }
-// PASSES: contexts whose max_keypoints exceeds FX_GATHER_KCAP (the instance without the pass loop keeps its registers)
-// MODE (batches of few big scans: 64 scans of config 5 are 64 workgroups on 256 CUs): several workgroups a scan WITHOUT the
-// staged appends and their global atomics (which serialise on a dense scan's hot keypoints: 5 x slower, see drain below) — two
-// launches over the same slices.  1: the counting pass — every hit adds one to its keypoint's LDS counter, nothing is stored;
-// the slice's counts go to B.gather_cnt.  2: the scatter pass — a keypoint's first list position for this slice is the sum
-// of the earlier slices' counts, so its hits go straight to their slots as with one workgroup a scan; the overflow region's
-// positions (entries beyond list_cap) follow from the same counts.  The near sectors are read and tested twice, by several
-// times as many workgroups.  0: as before (one workgroup a scan, or the streaming mode's staged appends).
-template <int NT, bool PASSES, int MODE = 0>
-__device__ __forceinline__ void gather_body(const FxDevParams &P, const FxBuffers &B, float box_margin, uint32_t *smem) {
-  static_assert(MODE == 0 || !PASSES, "the counted slices hold a scan's keypoints in one pass");
-  static_assert(MODE == 0 || FX_GATHER_DIRECT, "the scatter pass writes its hits straight to their slots");
-  constexpr uint32_t FX_GATHER_NW = NT / 64;
-  // keypoints the LDS tables hold at a time: a scan with more (a forest under the launch preset) is gathered in passes —
-  // the scan's near sectors are streamed once per FX_GATHER_KCAP keypoints
-  const uint32_t MK = PASSES ? (uint32_t)FX_GATHER_KCAP : P.max_keypoints;  // (the host launches the PASSES instance beyond FX_GATHER_KCAP)
-  uint32_t *s_w = smem;                                          // 0..5 keypoint box, 8 staged hits
-  float4 *s_kp = reinterpret_cast<float4 *>(smem + 32);          // 16-byte aligned
-  uint32_t *s_cell = smem + 32 + 4 * MK;                         // [CELLS + 4] list start | entries << 20
-  uint16_t *s_flat = reinterpret_cast<uint16_t *>(s_cell + FX_GATHER_CELLS + 4);  // [9 MK] keypoint ids, cell by cell
-  // hits are staged in LDS and appended to the keypoints' lists in bulk: one global atomic per
-  // (keypoint, flush) reserves the slots instead of one returning atomic per hit
-  uint32_t *s_kcnt = reinterpret_cast<uint32_t *>(s_flat) + (((9 * MK + 1) / 2 + 3) & ~3u);  // [MK] staged hits per keypoint
-  uint32_t *s_kbase = s_kcnt + MK;                               // [MK] reserved list position
-  uint32_t *s_kpos = s_kbase + MK;                               // [MK] list length so far (one workgroup per scan)
-  uint32_t *s_knbr = s_kpos + MK;                                // [MK] 1: some point lies within the search radius (one workgroup per scan)
-  uint32_t *s_kovf = s_knbr + MK;                                // [MK] overflow-region slot of the keypoint's staged ordinal 0 (entries beyond list_cap)
-  uint32_t *s_smeta = s_kcnt + ((5 * MK + 3) & ~3u);             // [STAGE] keypoint << 16 | staged ordinal
-  const bool solo = gridDim.x == 1 && MODE == 0;
-  const bool own = solo || MODE == 2;  // list positions are this workgroup's own LDS counters
-  float4 *s_spt = reinterpret_cast<float4 *>(s_smeta + FX_GATHER_STAGE);
-  uint32_t *s_cur = reinterpret_cast<uint32_t *>(s_spt);        // [CELLS] fill cursors while the lists are built (4 STAGE >= CELLS words)
-  const uint32_t scan = blockIdx.y, slice = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  constexpr uint32_t kQueue = gather_queue(NT);
-  float4 *q_pt = s_spt + FX_GATHER_STAGE + wave * kQueue;                                                  // this wavefront's queue
-  uint32_t *q_info = reinterpret_cast<uint32_t *>(s_spt + FX_GATHER_STAGE + FX_GATHER_NW * kQueue) + wave * kQueue;
-  uint32_t K_all = B.n_kp[scan];
-  if (K_all == 0) return;
-  const uint32_t row_first = B.kp_offset[scan];
-  if (row_first >= P.max_total_kp) return;
-  if (row_first + K_all > P.max_total_kp) K_all = P.max_total_kp - row_first;
-  const FxScanMeta M = B.meta[scan];
-  const bool passes = PASSES && K_all > MK;  // (then the has-a-neighbour flags of all keypoints meet in HBM, as with several workgroups a scan)
-  if (tid == 0) s_w[9] = 0;  // entries in the scan's overflow region (one workgroup per scan)
-  uint32_t kb = 0;
-  do {
-  const uint32_t K = PASSES ? min(MK, K_all - kb) : K_all, row0 = row_first + kb;
+static_assert(gather_lds_ok(FX_GATHER_T) && gather_lds_ok(FX_GATHER_WIDE_T), "k_gather: alignment, overlay, a CU's LDS");
+struct GatherMem {  // the image's regions as pointers; q_pt and q_info: the calling wavefront's queue
+  uint32_t *w, *cell, *kcnt, *kbase, *kpos, *knbr, *kovf, *smeta, *cur, *q_info;
+  float4 *kp, *spt, *q_pt;
+  uint16_t *flat;
+  __device__ __forceinline__ GatherMem(uint32_t *smem, const GatherLds &L, uint32_t wave, uint32_t queue)
+      : w(smem + L.w), cell(smem + L.cell), kcnt(smem + L.kcnt), kbase(smem + L.kbase), kpos(smem + L.kpos), knbr(smem + L.knbr),
+        kovf(smem + L.kovf), smeta(smem + L.smeta), cur(smem + L.cur), q_info(smem + L.q_info + wave * queue),
+        kp(reinterpret_cast<float4 *>(smem + L.kp)), spt(reinterpret_cast<float4 *>(smem + L.spt)),
+        q_pt(reinterpret_cast<float4 *>(smem + L.q_pt) + wave * queue), flat(reinterpret_cast<uint16_t *>(smem + L.flat)) {}
+};
+// What every phase knows: the launch, the scan, the LDS image, who this thread is, the pass.
+//   solo    MODE 0 and the only workgroup of its scan: it settles counts, classes and ordinals itself (gather_tail)
+//   own     list positions are this workgroup's own LDS counters (solo, or MODE 2)
+//   passes  the scan takes more than one pass (then the has-a-neighbour flags of all keypoints meet in HBM, as with several workgroups
+//           a scan)
+//   ovf_*   Entries beyond a list's list_cap slots go to the scan's overflow region (B.ovf_pts / B.ovf_kp, ovf_cap entries a
+//           scan, unordered): the dense tier (k_dense_sort) collects a row's entries from there, so no support set is truncated.
+struct GatherWg {
+  const FxDevParams &P;
+  const FxBuffers &B;
+  const FxScanMeta &M;
+  GatherMem s;
+  uint32_t scan, slice, tid, lane, wave;
+  bool solo, own, passes;
+  float4 *ovf_pts;
+  uint32_t *ovf_kp, K, kb, row0;  // K, kb, row0: this pass, the keypoints [kb, kb + K) of the scan, rows row0 .. of the batch
+};
+struct GatherGrid {  // the keypoints' box with its margin, its xy cells, and the cell of a point
+  float bx0, bx1, by0, by1, bz0, bz1, inv_wx, inv_wy;
+  int ncx, ncy;
+  __device__ __forceinline__ int cell_x(float x) const { return min(max((int)floorf((x - bx0) * inv_wx), 0), ncx - 1); }
+  __device__ __forceinline__ int cell_y(float y) const { return min(max((int)floorf((y - by0) * inv_wy), 0), ncy - 1); }
+};
+
+// Tables.  The pass's keypoints -> LDS (slice 0 also writes their rows' records), their bounding box, then the cells: counts, prefix, fill.
+template <int NT, int MODE>
+__device__ __forceinline__ GatherGrid gather_tables(const GatherWg &G, float box_margin) {
+  const FxBuffers &B = G.B;
+  const GatherMem &s = G.s;
+  const uint32_t tid = G.tid, K = G.K;
   __syncthreads();  // (the previous pass is done with the tables)
   // row -> (scan, keypoint) map for the per-keypoint kernels (one load instead of a binary search)
-  if (slice == 0 && MODE != 1)
-    for (uint32_t k = tid; k < K; k += NT) B.row_map[row0 + k] = make_uint2(scan, kb + k);
+  if (G.slice == 0 && MODE != 1)
+    for (uint32_t k = tid; k < K; k += NT) B.row_map[G.row0 + k] = make_uint2(G.scan, G.kb + k);
   // keypoints of the scan -> LDS; their bounding box (ordered-uint atomics) for a cheap reject
-  if (tid < 6) s_w[tid] = (tid & 1) ? f2ord(-INFINITY) : f2ord(INFINITY);
-  if (tid == 0) s_w[8] = 0;  // staged hits
-  for (uint32_t c = tid; c < FX_GATHER_CELLS; c += NT) s_cell[c] = 0;
+  if (tid < 6) s.w[GW_BOX + tid] = (tid & 1) ? f2ord(-INFINITY) : f2ord(INFINITY);
+  if (tid == 0) s.w[GW_STAGED] = 0;
+  for (uint32_t c = tid; c < FX_GATHER_CELLS; c += NT) s.cell[c] = 0;
   __syncthreads();
   for (uint32_t k = tid; k < K; k += NT) {
-    const float4 kp = B.keypoints[(size_t)scan * P.max_keypoints + kb + k];
-    s_kp[k] = kp;
-    s_kcnt[k] = 0;
-    s_kpos[k] = 0;
-    s_knbr[k] = 0;
-    if (slice == 0 && MODE != 1) B.row_kp[row0 + k] = kp;
-    atomicMin(&s_w[0], f2ord(kp.x));
-    atomicMax(&s_w[1], f2ord(kp.x));
-    atomicMin(&s_w[2], f2ord(kp.y));
-    atomicMax(&s_w[3], f2ord(kp.y));
-    atomicMin(&s_w[4], f2ord(kp.z));
-    atomicMax(&s_w[5], f2ord(kp.z));
+    const float4 kp = B.keypoints[(size_t)G.scan * G.P.max_keypoints + G.kb + k];
+    s.kp[k] = kp;
+    s.kcnt[k] = 0;
+    s.kpos[k] = 0;
+    s.knbr[k] = 0;
+    if (G.slice == 0 && MODE != 1) B.row_kp[G.row0 + k] = kp;
+    atomicMin(&s.w[GW_BOX + 0], f2ord(kp.x)), atomicMax(&s.w[GW_BOX + 1], f2ord(kp.x));
+    atomicMin(&s.w[GW_BOX + 2], f2ord(kp.y)), atomicMax(&s.w[GW_BOX + 3], f2ord(kp.y));
+    atomicMin(&s.w[GW_BOX + 4], f2ord(kp.z)), atomicMax(&s.w[GW_BOX + 5], f2ord(kp.z));
   }
   __syncthreads();
-  const float kx0 = ord2f(s_w[0]), kx1 = ord2f(s_w[1]), ky0 = ord2f(s_w[2]), ky1 = ord2f(s_w[3]);
-  const float bx0 = kx0 - box_margin, bx1 = kx1 + box_margin;
-  const float by0 = ky0 - box_margin, by1 = ky1 + box_margin;
-  const float bz0 = ord2f(s_w[4]) - box_margin, bz1 = ord2f(s_w[5]) + box_margin;
+  GatherGrid g;
+  const float kx0 = ord2f(s.w[GW_BOX + 0]), kx1 = ord2f(s.w[GW_BOX + 1]), ky0 = ord2f(s.w[GW_BOX + 2]), ky1 = ord2f(s.w[GW_BOX + 3]);
+  g.bx0 = kx0 - box_margin, g.bx1 = kx1 + box_margin;
+  g.by0 = ky0 - box_margin, g.by1 = ky1 + box_margin;
+  g.bz0 = ord2f(s.w[GW_BOX + 4]) - box_margin, g.bz1 = ord2f(s.w[GW_BOX + 5]) + box_margin;
   // cell width >= the support radius (+ margin): a point within reach of a keypoint is in the keypoint's cell or
   // in one next to it; wider when the keypoints spread over more than G cells of that width
-  const float wx = fmaxf(box_margin, (bx1 - bx0) / (float)(FX_GATHER_G - 1) * 1.0001f + 1e-6f);
-  const float wy = fmaxf(box_margin, (by1 - by0) / (float)(FX_GATHER_G - 1) * 1.0001f + 1e-6f);
-  const float inv_wx = 1.0f / wx, inv_wy = 1.0f / wy;
-  const int ncx = min((int)((bx1 - bx0) * inv_wx) + 1, FX_GATHER_G), ncy = min((int)((by1 - by0) * inv_wy) + 1, FX_GATHER_G);
-  auto cell_x = [&](float x) { return min(max((int)floorf((x - bx0) * inv_wx), 0), ncx - 1); };
-  auto cell_y = [&](float y) { return min(max((int)floorf((y - by0) * inv_wy), 0), ncy - 1); };
+  const float wx = fmaxf(box_margin, (g.bx1 - g.bx0) / (float)(FX_GATHER_G - 1) * 1.0001f + 1e-6f);
+  const float wy = fmaxf(box_margin, (g.by1 - g.by0) / (float)(FX_GATHER_G - 1) * 1.0001f + 1e-6f);
+  g.inv_wx = 1.0f / wx, g.inv_wy = 1.0f / wy;
+  g.ncx = min((int)((g.bx1 - g.bx0) * g.inv_wx) + 1, FX_GATHER_G), g.ncy = min((int)((g.by1 - g.by0) * g.inv_wy) + 1, FX_GATHER_G);
+  const int ncx = g.ncx, ncy = g.ncy;
   for (uint32_t k = tid; k < K; k += NT) {
-    const int cx = cell_x(s_kp[k].x), cy = cell_y(s_kp[k].y);
+    const int cx = g.cell_x(s.kp[k].x), cy = g.cell_y(s.kp[k].y);
     for (int dy = -1; dy <= 1; ++dy)
       for (int dx = -1; dx <= 1; ++dx)
-        if (cx + dx >= 0 && cx + dx < ncx && cy + dy >= 0 && cy + dy < ncy) atomicAdd(&s_cell[(cy + dy) * ncx + cx + dx], 1u);
+        if (cx + dx >= 0 && cx + dx < ncx && cy + dy >= 0 && cy + dy < ncy) atomicAdd(&s.cell[(cy + dy) * ncx + cx + dx], 1u);
   }
   __syncthreads();
   if (tid < 64) {  // counts -> start | count << 20, and the fill cursors, by one wavefront
@@ -4480,7 +4522,7 @@ __device__ __forceinline__ void gather_body(const FxDevParams &P, const FxBuffer
     uint32_t sum = 0;
     for (uint32_t u = 0; u < per; ++u) {
       const uint32_t ci = tid * per + u;
-      sum += ci < n_cells ? s_cell[ci] : 0u;
+      sum += ci < n_cells ? s.cell[ci] : 0u;
     }
     uint32_t incl = sum;
     incl = wave_incl_scan(incl);
@@ -4488,285 +4530,305 @@ __device__ __forceinline__ void gather_body(const FxDevParams &P, const FxBuffer
     for (uint32_t u = 0; u < per; ++u) {
       const uint32_t ci = tid * per + u;
       if (ci < n_cells) {
-        const uint32_t c = s_cell[ci];
-        s_cell[ci] = run | (c << 20);
-        s_cur[ci] = run;
+        const uint32_t c = s.cell[ci];
+        s.cell[ci] = run | (c << 20);
+        s.cur[ci] = run;
         run += c;
       }
     }
   }
   __syncthreads();
   for (uint32_t k = tid; k < K; k += NT) {
-    const int cx = cell_x(s_kp[k].x), cy = cell_y(s_kp[k].y);
+    const int cx = g.cell_x(s.kp[k].x), cy = g.cell_y(s.kp[k].y);
     for (int dy = -1; dy <= 1; ++dy)
       for (int dx = -1; dx <= 1; ++dx)
         if (cx + dx >= 0 && cx + dx < ncx && cy + dy >= 0 && cy + dy < ncy)
-          s_flat[atomicAdd(&s_cur[(cy + dy) * ncx + cx + dx], 1u)] = (uint16_t)k;
+          s.flat[atomicAdd(&s.cur[(cy + dy) * ncx + cx + dx], 1u)] = (uint16_t)k;
   }
   __syncthreads();
-
-  if (MODE == 2) {  // this slice's first position in every list, and in the scan's overflow region, from the counting pass
-    const uint32_t S = gridDim.x;
-    const uint32_t *cnt = B.gather_cnt + (size_t)scan * S * P.max_keypoints;
-    uint32_t ovf_before = 0, ovf_all = 0;
-    for (uint32_t k = tid; k < K; k += NT) {
-      uint32_t run = 0, mine = 0;
-      for (uint32_t sl = 0; sl < S; ++sl) {
-        const uint32_t c = cnt[(size_t)sl * P.max_keypoints + k];
-        const uint32_t o = run + c > P.list_cap ? run + c - max(run, P.list_cap) : 0u;  // this slice's entries beyond the list
-        if (sl == slice) mine = run;
-        if (sl < slice) ovf_before += o;
-        ovf_all += o;
-        run += c;
-      }
-      s_kpos[k] = mine;
-      if (slice == 0) B.s_cnt[row0 + k] = run;  // (the TRUE support size, as with one workgroup a scan)
+  return g;
+}
+// Slice positions (the scatter pass, MODE 2): this slice's first position in every list, and in the scan's overflow region, from
+// the counting pass
+template <int NT>
+__device__ __forceinline__ void gather_slice_positions(const GatherWg &G) {
+  const uint32_t S = gridDim.x;
+  const uint32_t *cnt = G.B.gather_cnt + (size_t)G.scan * S * G.P.max_keypoints;
+  uint32_t ovf_before = 0, ovf_all = 0;
+  for (uint32_t k = G.tid; k < G.K; k += NT) {
+    uint32_t run = 0, mine = 0;
+    for (uint32_t sl = 0; sl < S; ++sl) {
+      const uint32_t c = cnt[(size_t)sl * G.P.max_keypoints + k];
+      const uint32_t o = run + c > G.P.list_cap ? run + c - max(run, G.P.list_cap) : 0u;  // this slice's entries beyond the list
+      if (sl == G.slice) mine = run;
+      if (sl < G.slice) ovf_before += o;
+      ovf_all += o;
+      run += c;
     }
-    if (ovf_before) atomicAdd(&s_w[9], ovf_before);
-    if (slice == 0 && ovf_all) atomicAdd(&B.ovf_cnt[scan], ovf_all);  // (cleared by the front kernels)
-    __syncthreads();
+    G.s.kpos[k] = mine;
+    if (G.slice == 0) G.B.s_cnt[G.row0 + k] = run;  // (the TRUE support size, as with one workgroup a scan)
   }
-  constexpr uint32_t kTile = NT * 4;  // 1024 points: wave w owns [256 w, 256 w + 256), 64 consecutive points per load
-  const uint32_t n = M.n;
-  uint32_t chunk = (n + gridDim.x - 1) / gridDim.x;
-  chunk = (chunk + kTile - 1) / kTile * kTile;
-  // (the counted slices take the scan's tiles in turn — tile t is slice t mod S's —: a pole's hits lie in a few consecutive
-  //  tiles, and contiguous ranges gave them all to one slice)
-  const uint32_t tstep = MODE != 0 ? gridDim.x * kTile : kTile;
-  const uint32_t lo = MODE != 0 ? slice * kTile : slice * chunk;
-  const uint32_t hi = MODE != 0 ? n : (lo + chunk < n ? lo + chunk : n);
-  const uint32_t *near_bits = B.near_bits + (size_t)scan * P.near_words;
-  // called by the whole workgroup, after a barrier: reserve list positions, write the staged hits out
-  // Entries beyond a list's list_cap slots go to the scan's overflow region (B.ovf_pts / B.ovf_kp, ovf_cap entries a
-  // scan, unordered): the dense tier (k_dense_sort) collects a row's entries from there, so no support set is truncated.
-  float4 *ovf_pts = B.ovf_pts + (size_t)scan * P.ovf_cap;
-  uint32_t *ovf_kp = B.ovf_kp + (size_t)scan * P.ovf_cap;
-  auto ovf_reserve = [&](uint32_t n) -> uint32_t { return own ? atomicAdd(&s_w[9], n) : atomicAdd(&B.ovf_cnt[scan], n); };
-  auto flush = [&](uint32_t staged) {
-    staged = min(staged, (uint32_t)FX_GATHER_STAGE);
-    for (uint32_t k = tid; k < K; k += NT) {
-      const uint32_t c = s_kcnt[k];
-      if (c) {
-        uint32_t base;
-        if (solo) {  // this workgroup is the only writer of the scan's lists: positions are its own running counts
-          base = s_kpos[k];
-          s_kpos[k] = base + c;
-        } else {
-          base = atomicAdd(&B.s_cnt[row0 + k], c);
-        }
-        s_kbase[k] = base;
-        if (base + c > P.list_cap) {  // ordinals from `first` on overflow the list
-          const uint32_t first = base < P.list_cap ? P.list_cap - base : 0u;
-          s_kovf[k] = ovf_reserve(c - first) - first;  // (wraps below zero for ordinals that stay in the list: unused there)
-        }
-      }
-      s_kcnt[k] = 0;
-    }
-    __syncthreads();
-    for (uint32_t e = tid; e < staged; e += NT) {
-      const uint32_t meta = s_smeta[e], k = meta >> 16;
-      const uint32_t pos = s_kbase[k] + (meta & 0xffffu);
-      if (pos < P.list_cap) {
-        B.s_pts[(size_t)(row0 + k) * P.list_cap + pos] = s_spt[e];
-      } else {
-        const uint32_t slot = s_kovf[k] + (meta & 0xffffu);
-        if (slot < P.ovf_cap) {
-          ovf_pts[slot] = s_spt[e];
-          ovf_kp[slot] = k;
-        }
-      }
-    }
-    if (tid == 0) s_w[8] = 0;
-    __syncthreads();
-  };
-  // this wavefront's parked points against the keypoints of their cells' lists, one point per lane
-  uint32_t qn = 0;
-  auto drain = [&]() {
-    wave_sync_lds();
-    for (uint32_t t = lane; t < qn; t += 64) {
-      const float4 pq = q_pt[t];
-      const uint32_t info = q_info[t], st = info & 0xfffffu, cnt = info >> 20;
-      for (uint32_t e = 0; e < cnt; ++e) {
-        const uint32_t k = s_flat[st + e];
-        const float4 kp = s_kp[k];
-        const float d2 = dist2(kp.x, kp.y, kp.z, pq.x, pq.y, pq.z);
-        if (d2 < P.r2_support) {
-          // 3DSC draws its x-axis only for keypoints that have a neighbour (d2 < R^2: the descriptor kernels' count)
-          if (d2 < P.r2_search && MODE != 2) {
-            if (solo && !passes)
-              s_knbr[k] = 1u;
-            else
-              B.kp_nbrs[(size_t)scan * P.max_keypoints + kb + k] = 1u;  // (cleared by the merge stage; k_rng_ord reads it)
-          }
-          if (MODE == 1) {  // the counting pass: one more entry for this keypoint from this slice
-            atomicAdd(&s_kpos[k], 1u);
-            continue;
-          }
-          // One workgroup per scan: the list position is the workgroup's own LDS counter, so the hit goes straight to
-          // its slot (no staging, no flush, no workgroup barrier in the tile loop).  Several workgroups per scan
-          // (small batches): hits are staged and a flush reserves positions with one global atomic per keypoint —
-          // fine for a handful of sparse scans, hopeless for dense ones (hundreds of flushes: BASELINE config 3 with four
-          // workgroups per scan 5.4 ms against 0.66 with one; a global atomic per hit: 7.3 ms, the hot keypoints' counters
-          // serialise), which is why dense scans get one WIDE workgroup instead (k_gather_wide).
-          const uint32_t slot = (FX_GATHER_DIRECT && own) ? FX_GATHER_STAGE : atomicAdd(&s_w[8], 1u);
-          if (slot < FX_GATHER_STAGE) {
-            s_spt[slot] = pq;
-            s_smeta[slot] = (k << 16) | atomicAdd(&s_kcnt[k], 1u);
-          } else {  // (also: stage full — a burst of hits within one tile)
-            const uint32_t pos = own ? atomicAdd(&s_kpos[k], 1u) : atomicAdd(&B.s_cnt[row0 + k], 1u);
-            if (pos < P.list_cap) {
-              B.s_pts[(size_t)(row0 + k) * P.list_cap + pos] = pq;
-            } else {
-              const uint32_t os = ovf_reserve(1u);
-              if (os < P.ovf_cap) {
-                ovf_pts[os] = pq;
-                ovf_kp[os] = k;
-              }
-            }
-          }
-        }
-      }
-    }
-    wave_sync_lds();
-    qn = 0;
-  };
-  // the 64-byte sectors (four points) of a tile that hold a point within reach of the filter box (k_prep): this
-  // wavefront's 256 points = the 64 sector bits one wavefront of k_prep wrote (its tiles are two of these)
+  if (ovf_before) atomicAdd(&G.s.w[GW_OVF], ovf_before);
+  if (G.slice == 0 && ovf_all) atomicAdd(&G.B.ovf_cnt[G.scan], ovf_all);  // (cleared by the front kernels)
+  __syncthreads();
+}
+// Tile stream.  A tile is NT * 4 points: wave w owns [256 w, 256 w + 256) of it, 64 consecutive points per load.
+template <int NT, int MODE>
+struct GatherStream {
+  static constexpr uint32_t kTile = NT * 4;
+  uint32_t lo, hi, tstep, nb_first;  // the slice's tiles: [lo, hi) in steps of tstep; the tile whose sector words lane 0 holds
+  const uint32_t *near_bits;  // the 64-byte sectors (four points) of the scan that hold a point within reach of the filter box (k_prep):
+                              // this wavefront's 256 points = the 64 sector bits one wavefront of k_prep wrote (its tiles are two of these)
   // (The wavefront's sector words of 64 tiles at a time, lane t those of tile t — ONE load, then a readlane per tile: fetched
   //  tile by tile, the two words were a global round trip in front of every tile's loads, which they predicate.)
-  uint2 nb_words = make_uint2(0u, 0u);
-  uint32_t nb_first = lo;  // the tile lane 0 holds
-  auto nb_fill = [&](uint32_t i_first) {
+  uint2 nb_words;
+  __device__ __forceinline__ GatherStream(const GatherWg &G) {
+    const uint32_t n = G.M.n;
+    uint32_t chunk = (n + gridDim.x - 1) / gridDim.x;
+    chunk = (chunk + kTile - 1) / kTile * kTile;
+    // (the counted slices take the scan's tiles in turn — tile t is slice t mod S's —: a pole's hits lie in a few consecutive
+    //  tiles, and contiguous ranges gave them all to one slice)
+    tstep = MODE != 0 ? gridDim.x * kTile : kTile;
+    lo = MODE != 0 ? G.slice * kTile : G.slice * chunk;
+    hi = MODE != 0 ? n : (lo + chunk < n ? lo + chunk : n);
+    near_bits = G.B.near_bits + (size_t)G.scan * G.P.near_words;
+    nb_fill(G, lo);
+  }
+  __device__ __forceinline__ void nb_fill(const GatherWg &G, uint32_t i_first) {
     nb_first = i_first;
-    const uint32_t i = i_first + lane * tstep;
+    const uint32_t i = i_first + G.lane * tstep;
     nb_words = make_uint2(0u, 0u);
     if (i < hi) {
-      const uint32_t w = (i + wave * 256u) / 128u;  // (sector order: this wavefront's 256 points are 64 sectors = two words; w is even)
+      const uint32_t w = (i + G.wave * 256u) / 128u;  // (sector order: this wavefront's 256 points are 64 sectors = two words; w is even)
       nb_words = *reinterpret_cast<const uint2 *>(near_bits + w);
     }
-  };
-  nb_fill(lo);
-  auto near_sectors = [&](uint32_t i0) -> unsigned long long {
+  }
+  __device__ __forceinline__ unsigned long long near_sectors(const GatherWg &G, uint32_t i0) {
     if (i0 >= hi) return 0ull;
     uint32_t t = (i0 - nb_first) / tstep;  // (workgroup-uniform)
-    if (t >= 64u) nb_fill(i0), t = 0u;
+    if (t >= 64u) nb_fill(G, i0), t = 0u;
     const uint32_t ts = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
     return (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)nb_words.x, (int)ts) |
            ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)nb_words.y, (int)ts) << 32);
-  };
-  auto load_tile = [&](uint32_t i0, unsigned long long sect, float4 (&v)[4]) {
+  }
+  __device__ __forceinline__ void load_tile(const GatherWg &G, uint32_t i0, unsigned long long sect, float4 (&v)[4]) const {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      const uint32_t i = i0 + wave * 256 + u * 64 + lane;
+      const uint32_t i = i0 + G.wave * 256 + u * 64 + G.lane;
       v[u] = make_float4(NAN, NAN, NAN, 0);
-      if (((sect >> (16 * u + (lane >> 2))) & 1ull) && i < hi) v[u] = *reinterpret_cast<const float4 *>(M.pts + (size_t)i * M.stride_f);
+      if (((sect >> (16 * u + (G.lane >> 2))) & 1ull) && i < hi) v[u] = *reinterpret_cast<const float4 *>(G.M.pts + (size_t)i * G.M.stride_f);
     }
-  };
-  float4 v[4], nv[4];
-  unsigned long long nib = near_sectors(lo), nnib = 0;
-  load_tile(lo, nib, v);
-  for (uint32_t i0 = lo; i0 < hi; i0 += tstep) {
-    nnib = near_sectors(i0 + tstep);
-    load_tile(i0 + tstep, nnib, nv);  // the next tile's loads are in flight while this one is tested
-    if (MODE == 0 && i0 != lo && !(FX_GATHER_DIRECT && solo)) {  // flush when the next tile might not fit any more (workgroup-uniform decision)
-      __syncthreads();
-      const uint32_t staged = s_w[8];
-      __syncthreads();
-      if (staged > FX_GATHER_STAGE / 2) flush(staged);
+  }
+};
+// Hit sink.
+// count — the counting pass: one more entry for this keypoint from this slice
+__device__ __forceinline__ void hit_count(const GatherWg &G, uint32_t k) { atomicAdd(&G.s.kpos[k], 1u); }
+// direct — the hit goes straight to its slot, beyond list_cap to the overflow region.  With list positions of its own the position
+// is the workgroup's LDS counter (no staging, no flush, no workgroup barrier in the tile loop); without, one global atomic
+__device__ __forceinline__ void hit_direct(const GatherWg &G, uint32_t k, const float4 &pq) {
+  const uint32_t pos = G.own ? atomicAdd(&G.s.kpos[k], 1u) : atomicAdd(&G.B.s_cnt[G.row0 + k], 1u);
+  if (pos < G.P.list_cap) {
+    G.B.s_pts[(size_t)(G.row0 + k) * G.P.list_cap + pos] = pq;
+  } else {
+    const uint32_t os = G.own ? atomicAdd(&G.s.w[GW_OVF], 1u) : atomicAdd(&G.B.ovf_cnt[G.scan], 1u);
+    if (os < G.P.ovf_cap) {
+      G.ovf_pts[os] = pq;
+      G.ovf_kp[os] = k;
     }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      if (!((nib >> (16 * u)) & 0xffffull)) continue;  // (wave-uniform: none of the load's sixteen sectors was loaded)
-      const float x = v[u].x, y = v[u].y, z = v[u].z;
-      const float rx = ((M.R[0] * x + M.R[1] * y) + M.R[2] * z) + 0.0f;
-      const float ry = ((M.R[3] * x + M.R[4] * y) + M.R[5] * z) + 0.0f;
-      const float rz = ((M.R[6] * x + M.R[7] * y) + M.R[8] * z) + 0.0f;
-      // non-finite points are not part of the search surface; NaN fails every comparison
-      const bool near = rx >= bx0 && rx <= bx1 && ry >= by0 && ry <= by1 && rz >= bz0 && rz <= bz1 &&
-                        isfinite(rx) && isfinite(ry) && isfinite(rz);
-      uint32_t info = 0;
-      if (near) info = s_cell[cell_y(ry) * ncx + cell_x(rx)];
-      const bool has = (info >> 20) != 0u;
-      const unsigned long long m = __ballot(has);
-      if (m) {  // wave-uniform
-        if (has) {
-          const uint32_t slot = qn + lanes_below(m);
-          q_pt[slot] = make_float4(rx, ry, rz, __uint_as_float(i0 + wave * 256 + u * 64 + lane));
-          q_info[slot] = info;
-        }
-        qn += (uint32_t)__popcll(m);
-        if (qn > kQueue - 64) drain();
+  }
+}
+// staged — several workgroups per scan (small batches): hits are staged and a flush reserves positions with one global atomic per
+// keypoint — fine for a handful of sparse scans, hopeless for dense ones (hundreds of flushes: BASELINE config 3 with four
+// workgroups per scan 5.4 ms against 0.66 with one; a global atomic per hit: 7.3 ms, the hot keypoints' counters
+// serialise), which is why dense scans get one WIDE workgroup instead (k_gather_wide).  false: the stage is full (a burst of hits
+// within one tile), the hit is the caller's still
+__device__ __forceinline__ bool hit_staged(const GatherWg &G, uint32_t k, const float4 &pq) {
+  const uint32_t slot = atomicAdd(&G.s.w[GW_STAGED], 1u);
+  if (slot >= FX_GATHER_STAGE) return false;
+  G.s.spt[slot] = pq;
+  G.s.smeta[slot] = (k << 16) | atomicAdd(&G.s.kcnt[k], 1u);
+  return true;
+}
+// called by the whole workgroup, after a barrier: reserve list positions, write the staged hits out.  (Only workgroups that share
+// their scan stage hits: the positions are global atomics, in the lists and in the overflow region.)
+template <int NT>
+__device__ __forceinline__ void gather_flush(const GatherWg &G, uint32_t staged) {
+  staged = min(staged, (uint32_t)FX_GATHER_STAGE);
+  for (uint32_t k = G.tid; k < G.K; k += NT) {
+    const uint32_t c = G.s.kcnt[k];
+    if (c) {
+      const uint32_t base = atomicAdd(&G.B.s_cnt[G.row0 + k], c);
+      G.s.kbase[k] = base;
+      if (base + c > G.P.list_cap) {  // ordinals from `first` on overflow the list
+        const uint32_t first = base < G.P.list_cap ? G.P.list_cap - base : 0u;
+        G.s.kovf[k] = atomicAdd(&G.B.ovf_cnt[G.scan], c - first) - first;  // (wraps below zero for ordinals that stay in the list: unused there)
       }
     }
-    nib = nnib;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) v[u] = nv[u];
+    G.s.kcnt[k] = 0;
   }
-  drain();
   __syncthreads();
-  if (MODE == 0) flush(s_w[8]);
-  if (MODE == 1) {  // this slice's entries per keypoint
-    uint32_t *cnt = B.gather_cnt + ((size_t)scan * gridDim.x + slice) * P.max_keypoints;
-    for (uint32_t k = tid; k < K; k += NT) cnt[k] = s_kpos[k];
-  }
-  if (solo) {
-    for (uint32_t k = tid; k < K; k += NT) B.s_cnt[row0 + k] = s_kpos[k];
-    // the counts are final: every row to its tier's work list (a row a lane, whole wavefronts: see classify_rows)
-    for (uint32_t k0 = wave * 64u; k0 < K; k0 += NT) {
-      const uint32_t k = k0 + lane;
-      classify_rows(P, B, k < K, row0 + k, scan, k < K ? s_kpos[k] : 0u);
-    }
-    // RNG ordinals: keypoint k takes the x-axis number (keypoints before it that have a neighbour)
-    __syncthreads();
-    if (wave == 0 && !passes) {
-      uint32_t base = 0;
-      for (uint32_t k0 = 0; k0 < K; k0 += 64) {
-        const uint32_t k = k0 + lane;
-        const unsigned long long m = __ballot(k < K && s_knbr[k] != 0u);
-        if (k < K) B.row_xa[row0 + k] = B.xaxis[base + lanes_below(m)];
-        base += (uint32_t)__popcll(m);
+  for (uint32_t e = G.tid; e < staged; e += NT) {
+    const uint32_t meta = G.s.smeta[e], k = meta >> 16;
+    const uint32_t pos = G.s.kbase[k] + (meta & 0xffffu);
+    if (pos < G.P.list_cap) {
+      G.B.s_pts[(size_t)(G.row0 + k) * G.P.list_cap + pos] = G.s.spt[e];
+    } else {
+      const uint32_t slot = G.s.kovf[k] + (meta & 0xffffu);
+      if (slot < G.P.ovf_cap) {
+        G.ovf_pts[slot] = G.s.spt[e];
+        G.ovf_kp[slot] = k;
       }
     }
   }
+  if (G.tid == 0) G.s.w[GW_STAGED] = 0;
+  __syncthreads();
+}
+// Drain: this wavefront's qn parked points against the keypoints of their cells' lists, one point per lane
+template <int MODE>
+__device__ __forceinline__ void gather_drain(const GatherWg &G, uint32_t &qn) {
+  wave_sync_lds();
+  for (uint32_t t = G.lane; t < qn; t += 64) {
+    const float4 pq = G.s.q_pt[t];
+    const uint32_t info = G.s.q_info[t], st = info & 0xfffffu, cnt = info >> 20;
+    for (uint32_t e = 0; e < cnt; ++e) {
+      const uint32_t k = G.s.flat[st + e];
+      const float4 kp = G.s.kp[k];
+      const float d2 = dist2(kp.x, kp.y, kp.z, pq.x, pq.y, pq.z);
+      if (d2 < G.P.r2_support) {
+        // 3DSC draws its x-axis only for keypoints that have a neighbour (d2 < R^2: the descriptor kernels' count)
+        if (d2 < G.P.r2_search && MODE != 2) {
+          if (G.solo && !G.passes)
+            G.s.knbr[k] = 1u;
+          else
+            G.B.kp_nbrs[(size_t)G.scan * G.P.max_keypoints + G.kb + k] = 1u;  // (cleared by the merge stage; k_rng_ord reads it)
+        }
+        if (MODE == 1)
+          hit_count(G, k);
+        else if (G.own || !hit_staged(G, k, pq))  // (own: MODE 2 at compile time; MODE 0 alone on its scan, workgroup-uniform)
+          hit_direct(G, k, pq);
+      }
+    }
+  }
+  wave_sync_lds();
+  qn = 0;
+}
+// Park: the 64 points of one load (this lane's: v, point i of the scan) rotated and tested against the keypoints' box; those whose cell
+// lists keypoints join the wavefront's queue, with all lanes busy when it is drained (in firing order only some lanes hold such points)
+template <int NT, int MODE>
+__device__ __forceinline__ void gather_park(const GatherWg &G, const GatherGrid &g, const float4 &v, uint32_t i, uint32_t &qn) {
+  const float rx = ((G.M.R[0] * v.x + G.M.R[1] * v.y) + G.M.R[2] * v.z) + 0.0f;
+  const float ry = ((G.M.R[3] * v.x + G.M.R[4] * v.y) + G.M.R[5] * v.z) + 0.0f;
+  const float rz = ((G.M.R[6] * v.x + G.M.R[7] * v.y) + G.M.R[8] * v.z) + 0.0f;
+  // non-finite points are not part of the search surface; NaN fails every comparison
+  const bool near = rx >= g.bx0 && rx <= g.bx1 && ry >= g.by0 && ry <= g.by1 && rz >= g.bz0 && rz <= g.bz1 &&
+                    isfinite(rx) && isfinite(ry) && isfinite(rz);
+  uint32_t info = 0;
+  if (near) info = G.s.cell[g.cell_y(ry) * g.ncx + g.cell_x(rx)];
+  const bool has = (info >> 20) != 0u;
+  const unsigned long long m = __ballot(has);
+  if (m) {  // wave-uniform
+    if (has) {
+      const uint32_t slot = qn + lanes_below(m);
+      G.s.q_pt[slot] = make_float4(rx, ry, rz, __uint_as_float(i));
+      G.s.q_info[slot] = info;
+    }
+    qn += (uint32_t)__popcll(m);
+    if (qn > gather_queue(NT) - 64) gather_drain<MODE>(G, qn);
+  }
+}
+// Tail of a pass: the counting pass's counts; a workgroup alone on its scan settles the support counts, the rows' classes and (but for
+// the ordinals of a scan of several passes, which follow its last pass) the RNG ordinals, its flags being in LDS
+template <int NT, int MODE>
+__device__ __forceinline__ void gather_tail(const GatherWg &G) {
+  if (MODE == 1)  // this slice's entries per keypoint
+    for (uint32_t k = G.tid; k < G.K; k += NT) G.B.gather_cnt[((size_t)G.scan * gridDim.x + G.slice) * G.P.max_keypoints + k] = G.s.kpos[k];
+  if (G.solo) {
+    for (uint32_t k = G.tid; k < G.K; k += NT) G.B.s_cnt[G.row0 + k] = G.s.kpos[k];
+    // the counts are final: every row to its tier's work list (a row a lane, whole wavefronts: see classify_rows)
+    for (uint32_t k0 = G.wave * 64u; k0 < G.K; k0 += NT) {
+      const uint32_t k = k0 + G.lane;
+      classify_rows(G.P, G.B, k < G.K, G.row0 + k, G.scan, k < G.K ? G.s.kpos[k] : 0u);
+    }
+    __syncthreads();
+    if (G.wave == 0 && !G.passes) rng_ordinals(G.B, G.row0, G.K, G.lane, G.s.knbr);
+  }
+}
+// PASSES: contexts whose max_keypoints exceeds FX_GATHER_KCAP (the instance without the pass loop keeps its registers)
+// MODE (batches of few big scans: 64 scans of config 5 are 64 workgroups on 256 CUs): several workgroups a scan WITHOUT the
+// staged appends and their global atomics (which serialise on a dense scan's hot keypoints: 5 x slower, see hit_staged) — two
+// launches over the same slices.  1: the counting pass — every hit adds one to its keypoint's LDS counter, nothing is stored;
+// the slice's counts go to B.gather_cnt.  2: the scatter pass — a keypoint's first list position for this slice is the sum
+// of the earlier slices' counts, so its hits go straight to their slots as with one workgroup a scan; the overflow region's
+// positions (entries beyond list_cap) follow from the same counts.  The near sectors are read and tested twice, by several
+// times as many workgroups.  0: as before (one workgroup a scan, or the streaming mode's staged appends).
+template <int NT, bool PASSES, int MODE = 0>
+__device__ __forceinline__ void gather_body(const FxDevParams &P, const FxBuffers &B, float box_margin) {
+  static_assert(MODE == 0 || !PASSES, "the counted slices hold a scan's keypoints in one pass");
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];  // the image GatherLds describes
+  // keypoints the LDS tables hold at a time: a scan with more (a forest under the launch preset) is gathered in passes —
+  // the scan's near sectors are streamed once per FX_GATHER_KCAP keypoints
+  const uint32_t MK = PASSES ? (uint32_t)FX_GATHER_KCAP : P.max_keypoints;  // (the host launches the PASSES instance beyond FX_GATHER_KCAP)
+  const uint32_t scan = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  uint32_t K_all = B.n_kp[scan];
+  if (K_all == 0) return;
+  const uint32_t row_first = B.kp_offset[scan];
+  if (row_first >= P.max_total_kp) return;
+  if (row_first + K_all > P.max_total_kp) K_all = P.max_total_kp - row_first;
+  const FxScanMeta M = B.meta[scan];
+  const bool solo = gridDim.x == 1 && MODE == 0, passes = PASSES && K_all > MK;
+  const GatherMem s(smem, GatherLds(MK, NT), wave, gather_queue(NT));
+  if (tid == 0) s.w[GW_OVF] = 0;
+  uint32_t kb = 0;
+  do {
+    const GatherWg G{P, B, M, s, scan, blockIdx.x, tid, lane, wave, solo, solo || MODE == 2, passes, B.ovf_pts + (size_t)scan * P.ovf_cap,
+                     B.ovf_kp + (size_t)scan * P.ovf_cap, PASSES ? min(MK, K_all - kb) : K_all, kb, row_first + kb};
+    const GatherGrid grid = gather_tables<NT, MODE>(G, box_margin);
+    if (MODE == 2) gather_slice_positions<NT>(G);
+    GatherStream<NT, MODE> st(G);
+    uint32_t qn = 0;  // points parked in this wavefront's queue
+    float4 v[4], nv[4];
+    unsigned long long nib = st.near_sectors(G, st.lo), nnib = 0;
+    st.load_tile(G, st.lo, nib, v);
+    for (uint32_t i0 = st.lo; i0 < st.hi; i0 += st.tstep) {
+      nnib = st.near_sectors(G, i0 + st.tstep);
+      st.load_tile(G, i0 + st.tstep, nnib, nv);  // the next tile's loads are in flight while this one is tested
+      if (MODE == 0 && i0 != st.lo && !solo) {  // staged hits: flush when the next tile might not fit any more (workgroup-uniform decision)
+        __syncthreads();
+        const uint32_t staged = s.w[GW_STAGED];
+        __syncthreads();
+        if (staged > FX_GATHER_STAGE / 2) gather_flush<NT>(G, staged);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (!((nib >> (16 * u)) & 0xffffull)) continue;  // (wave-uniform: none of the load's sixteen sectors was loaded)
+        gather_park<NT, MODE>(G, grid, v[u], i0 + wave * 256 + u * 64 + lane, qn);
+      }
+      nib = nnib;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) v[u] = nv[u];
+    }
+    gather_drain<MODE>(G, qn);
+    __syncthreads();
+    if (MODE == 0) gather_flush<NT>(G, s.w[GW_STAGED]);
+    gather_tail<NT, MODE>(G);
   } while (PASSES && (kb += MK) < K_all);
   if (solo) {
-    if (tid == 0) B.ovf_cnt[scan] = s_w[9];
+    if (tid == 0) B.ovf_cnt[scan] = s.w[GW_OVF];
     if (passes) {  // the ordinals over all passes' flags
       wg_global_sync();
-      if (wave == 0) {
-        uint32_t base = 0;
-        for (uint32_t k0 = 0; k0 < K_all; k0 += 64) {
-          const uint32_t k = k0 + lane;
-          const unsigned long long m = __ballot(k < K_all && B.kp_nbrs[(size_t)scan * P.max_keypoints + k] != 0u);
-          if (k < K_all) B.row_xa[row_first + k] = B.xaxis[base + lanes_below(m)];
-          base += (uint32_t)__popcll(m);
-        }
-      }
+      if (wave == 0) rng_ordinals(B, row_first, K_all, lane, B.kp_nbrs + (size_t)scan * P.max_keypoints);
     }
   }
 }
-extern "C" __global__ __launch_bounds__(FX_GATHER_T) void k_gather(FxDevParams P, FxBuffers B, float box_margin) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-  gather_body<FX_GATHER_T, false>(P, B, box_margin, smem);
-}
-extern "C" __global__ __launch_bounds__(FX_GATHER_WIDE_T) void k_gather_wide(FxDevParams P, FxBuffers B, float box_margin) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-  gather_body<FX_GATHER_WIDE_T, false>(P, B, box_margin, smem);
-}
-// contexts of more than FX_GATHER_KCAP keypoints a scan: the wide workgroup, whatever the batch (its tables take most of a CU's LDS)
-// batches of few big scans: the counted slices (gather_body's MODE), two launches
-extern "C" __global__ __launch_bounds__(FX_GATHER_T) void k_gather_count(FxDevParams P, FxBuffers B, float box_margin) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-  gather_body<FX_GATHER_T, false, 1>(P, B, box_margin, smem);
-}
-extern "C" __global__ __launch_bounds__(FX_GATHER_T) void k_gather_scatter(FxDevParams P, FxBuffers B, float box_margin) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-  gather_body<FX_GATHER_T, false, 2>(P, B, box_margin, smem);
-}
-extern "C" __global__ __launch_bounds__(FX_GATHER_WIDE_T) void k_gather_passes(FxDevParams P, FxBuffers B, float box_margin) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-  gather_body<FX_GATHER_WIDE_T, true>(P, B, box_margin, smem);
-}
+
+// The instances (see the head of this section).  k_gather_passes: contexts of more than FX_GATHER_KCAP keypoints a scan: the wide
+// workgroup, whatever the batch (its tables take most of a CU's LDS).  k_gather_count, k_gather_scatter: batches of few big scans:
+// the counted slices (gather_body's MODE), two launches.
+extern "C" __global__ __launch_bounds__(FX_GATHER_T) void k_gather(FxDevParams P, FxBuffers B, float box_margin) { gather_body<FX_GATHER_T, false>(P, B, box_margin); }
+extern "C" __global__ __launch_bounds__(FX_GATHER_WIDE_T) void k_gather_wide(FxDevParams P, FxBuffers B, float box_margin) { gather_body<FX_GATHER_WIDE_T, false>(P, B, box_margin); }
+extern "C" __global__ __launch_bounds__(FX_GATHER_T) void k_gather_count(FxDevParams P, FxBuffers B, float box_margin) { gather_body<FX_GATHER_T, false, 1>(P, B, box_margin); }
+extern "C" __global__ __launch_bounds__(FX_GATHER_T) void k_gather_scatter(FxDevParams P, FxBuffers B, float box_margin) { gather_body<FX_GATHER_T, false, 2>(P, B, box_margin); }
+extern "C" __global__ __launch_bounds__(FX_GATHER_WIDE_T) void k_gather_passes(FxDevParams P, FxBuffers B, float box_margin) { gather_body<FX_GATHER_WIDE_T, true>(P, B, box_margin); }
 
 // ---------------------------------------------------------------- wavefront tier (runs inside k_desc)
 #define FX_WAVE_WORDS (FX_WAVE_CAP * 8)  // (FX_WAVE_CAP: defined with the row classes, above)
@@ -6538,13 +6600,10 @@ extern "C" __global__ __launch_bounds__(FX_WG) void k_rng_ord(FxDevParams P, FxB
   const uint32_t row0 = B.kp_offset[b];
   if (row0 >= P.max_total_kp) return;
   if (row0 + K > P.max_total_kp) K = P.max_total_kp - row0;
-  uint32_t base = 0;
+  rng_ordinals(B, row0, K, lane, B.kp_nbrs + (size_t)b * P.max_keypoints);
+  // ... and, the scan's support counts being final only now that all its workgroups are done, every row to its tier's list
   for (uint32_t k0 = 0; k0 < K; k0 += 64) {
     const uint32_t k = k0 + lane;
-    const unsigned long long m = __ballot(k < K && B.kp_nbrs[(size_t)b * P.max_keypoints + k] != 0u);
-    if (k < K) B.row_xa[row0 + k] = B.xaxis[base + lanes_below(m)];
-    base += (uint32_t)__popcll(m);
-    // ... and, the scan's support counts being final only now that all its workgroups are done, every row to its tier's list
     classify_rows(P, B, k < K, row0 + k, b, k < K ? B.s_cnt[row0 + k] : 0u);
   }
 }
@@ -6864,7 +6923,7 @@ void fxk_rings_large(hipStream_t s, const FxDevParams &P, const FxBuffers &B, ui
 }
 size_t fxk_merge_lds_bytes(uint32_t cap, uint32_t n_rings) { return merge_words(cap, cap, n_rings, true) * 4; }
 size_t fxk_merge_huge_lds_bytes(uint32_t cap, uint32_t ccap, uint32_t n_rings) { return merge_words(cap, ccap, n_rings, false) * 4; }
-size_t fxk_gather_lds_bytes(uint32_t max_keypoints) { return (size_t)gather_words(std::min(max_keypoints, (uint32_t)FX_GATHER_KCAP), FX_GATHER_WIDE_T) * 4; }
+size_t fxk_gather_lds_bytes(uint32_t max_keypoints) { return (size_t)GatherLds(std::min(max_keypoints, (uint32_t)FX_GATHER_KCAP), FX_GATHER_WIDE_T).end * 4; }
 size_t fxk_dense_finish_lds_bytes(void) {
   const size_t k = FX_DFIN_K;
   return (2 * k + k / 2 + 1984 + FX_TABLE_WORDS + 16) * 4;
@@ -6885,16 +6944,12 @@ hipError_t fxk_configure(size_t ring_big, size_t merge_big, size_t merge_huge, s
   if (e != hipSuccess) return e;
   e = hipFuncSetAttribute((const void *)k_merge_huge_c, hipFuncAttributeMaxDynamicSharedMemorySize, (int)merge_huge);
   if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute((const void *)k_gather, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gather);
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute((const void *)k_gather_wide, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gather);
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute((const void *)k_gather_count, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gather);
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute((const void *)k_gather_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gather);
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute((const void *)k_gather_passes, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gather);
-  if (e != hipSuccess) return e;
+  const void *const gathers[] = {(const void *)k_gather, (const void *)k_gather_wide, (const void *)k_gather_count, (const void *)k_gather_scatter,
+                                 (const void *)k_gather_passes};
+  for (const void *k : gathers) {
+    e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gather);
+    if (e != hipSuccess) return e;
+  }
   e = hipFuncSetAttribute((const void *)k_rings_large, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ring_big);
   if (e != hipSuccess) return e;
   e = hipFuncSetAttribute((const void *)k_merge_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)merge_big);
@@ -7014,8 +7069,8 @@ uint32_t fxk_gather_counted_max(void) { return FX_GATHER_COUNTED_MAX; }
 // FX_GATHER_COUNTED: two launches, a counting pass, then the scatter with every slice's list positions known (gather_body's
 // MODE) — batches of few big scans; needs FxBuffers::gather_cnt.
 void fxk_gather(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, float box_margin, FxGatherKind kind, uint32_t per_scan) {
-  const size_t lds = (size_t)gather_words(std::min(P.max_keypoints, (uint32_t)FX_GATHER_KCAP), FX_GATHER_T) * 4;
-  const size_t lds_wide = (size_t)gather_words(std::min(P.max_keypoints, (uint32_t)FX_GATHER_KCAP), FX_GATHER_WIDE_T) * 4;
+  const size_t lds = (size_t)GatherLds(std::min(P.max_keypoints, (uint32_t)FX_GATHER_KCAP), FX_GATHER_T).end * 4;
+  const size_t lds_wide = (size_t)GatherLds(std::min(P.max_keypoints, (uint32_t)FX_GATHER_KCAP), FX_GATHER_WIDE_T).end * 4;
   const uint32_t kcap = FX_GATHER_KCAP, counted_max = FX_GATHER_COUNTED_MAX;
   assert((kind == FX_GATHER_PASSES) == (P.max_keypoints > kcap));  // (only the passes instance loops over the LDS tables' capacity)
   switch (kind) {
