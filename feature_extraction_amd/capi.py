@@ -414,6 +414,21 @@ class FxSpliceSource(C.Structure):
 FX_SPLICE_LAST_SCAN = 0xffffffff  # scan0: the source's last scan, read on the device
 
 
+class FxTestGatherInfo(C.Structure):  # (the header's FX_TEST_HOOKS section)
+    _fields_ = [("batch", C.c_uint32), ("rows", C.c_uint32), ("near_words", C.c_uint32), ("list_cap", C.c_uint32), ("ovf_cap", C.c_uint32),
+                ("ovf_stored", C.c_uint32), ("dense_min", C.c_uint32), ("max_dense_rows", C.c_uint32),
+                ("r2_support", C.c_float), ("r2_search", C.c_float), ("box_margin", C.c_float),
+                ("n_list", C.c_uint32), ("n_wave", C.c_uint32), ("n_group", C.c_uint32 * 3), ("n_dense", C.c_uint32)]
+
+
+_GATHER_OUT = ("near_bits", "s_cnt", "s_pts", "ovf_cnt", "ovf_pts", "ovf_kp", "row_map", "row_kp", "row_class", "row_xa", "list_desc",
+               "wave_desc", "group_desc", "dense_rows")
+
+
+class FxTestGatherOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in _GATHER_OUT]
+
+
 class FxTimings(C.Structure):
     _fields_ = [("ms", C.c_float * FX_N_STAGES), ("total_ms", C.c_float), ("k_prep_exec_ms", C.c_float)]
 
@@ -453,7 +468,7 @@ EXPORTS = ("fx_version", "fx_check_abi", "fx_status_str", "fx_last_error", "fx_p
            "fx_synth_scan", "fx_unpack_pointcloud2", "fx_pack_pointxyzi")
 # the header's FX_TEST_HOOKS section: exported by lib/libfx_hip_test.so only
 TEST_EXPORTS = ("fx_test_sort_replay", "fx_test_sort_replay_ranked", "fx_test_sort_replay_lists", "fx_test_sort_replay_device",
-                "fx_test_elevation_device", "fx_test_within_device")
+                "fx_test_elevation_device", "fx_test_within_device", "fx_test_gather_state")
 
 _lib = None
 _libs = {}
@@ -645,6 +660,7 @@ def load():
         lib.fx_test_sort_replay_device.argtypes = [C.c_int, _U32P, C.c_uint32, C.c_uint32, _U32P]
         lib.fx_test_elevation_device.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.fx_test_within_device.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p]
+        lib.fx_test_gather_state.argtypes = [C.c_void_p, C.POINTER(FxTestGatherInfo), C.POINTER(FxTestGatherOut)]
     _lib = lib
     _libs[LIB_PATH] = lib
     return lib
@@ -3212,6 +3228,34 @@ class Context:
 
     def synchronize(self):
         check(self.lib.fx_synchronize(self.handle))
+
+    def gather_state(self):
+        """fx_test_gather_state (the test build only): what the support gather of the last batch left on the device, as numpy
+        copies — near_bits [B, near_words], s_cnt [rows], s_pts [rows, list_cap, 4] (float32; word 3 holds the point's index as
+        bits), ovf_cnt [B], ovf_pts [B, ovf_stored, 4], ovf_kp [B, ovf_stored], row_map [rows, 2], row_kp [rows, 4], row_class
+        [rows], row_xa [rows, 2], the work lists list_desc, wave_desc, group_desc (a list of three), dense_rows cut to their
+        counters — and the reported constants (r2_support, r2_search, box_margin as np.float32; list_cap, ovf_cap, dense_min,
+        near_words, batch, rows; n_list, n_wave, n_group, n_dense)."""
+        info = FxTestGatherInfo()
+        check(self.lib.fx_test_gather_state(self.handle, C.byref(info), None))
+        B, rows, S = info.batch, info.rows, info.ovf_stored
+        n_group = [int(v) for v in info.n_group]
+        shapes = {"near_bits": ((B, info.near_words), np.uint32), "s_cnt": ((rows,), np.uint32), "s_pts": ((rows, info.list_cap, 4), np.float32),
+                  "ovf_cnt": ((B,), np.uint32), "ovf_pts": ((B, S, 4), np.float32), "ovf_kp": ((B, S), np.uint32),
+                  "row_map": ((rows, 2), np.uint32), "row_kp": ((rows, 4), np.float32), "row_class": ((rows,), np.uint8),
+                  "row_xa": ((rows, 2), np.float32), "list_desc": ((min(info.n_list, rows),), np.uint32),
+                  "wave_desc": ((min(info.n_wave, rows),), np.uint32), "group_desc": ((3, rows), np.uint32),
+                  "dense_rows": ((min(info.n_dense, info.max_dense_rows),), np.uint32)}
+        st = {k: np.zeros(sh, dt) for k, (sh, dt) in shapes.items()}
+        out = FxTestGatherOut(**{k: st[k].ctypes.data if st[k].size else None for k in _GATHER_OUT})
+        check(self.lib.fx_test_gather_state(self.handle, C.byref(info), C.byref(out)))
+        st["group_desc"] = [st["group_desc"][g, :min(n_group[g], rows)].copy() for g in range(3)]
+        for k in ("r2_support", "r2_search", "box_margin"):
+            st[k] = np.float32(getattr(info, k))
+        for k in ("batch", "rows", "near_words", "list_cap", "ovf_cap", "dense_min", "max_dense_rows", "n_list", "n_wave", "n_dense"):
+            st[k] = int(getattr(info, k))
+        st["n_group"] = n_group
+        return st
 
     def set_descriptor_csr_capacity(self, entries):
         """Initial entries of the context's CSR block (0: max_total_keypoints * 128); it grows when a batch needs more."""

@@ -948,6 +948,10 @@ fx_status fx_create(const fx_params *params, const fx_limits *limits, int device
   if (const char *e = test_hook("FX_PREP_SLICES")) pc.prep_slices = std::max(1, atoi(e));
   if (const char *e = test_hook("FX_MERGE_SLICES")) pc.merge_slices = std::max(1, atoi(e));
   if (const char *e = test_hook("FX_GATHER_COUNTED")) pc.gather_slices = std::max(1, atoi(e));
+  if (const char *e = test_hook("FX_GATHER_ONE")) {  // one workgroup a scan at any batch size: 256 k_gather, 1024 k_gather_wide
+    const int v = atoi(e);
+    if (v == 256 || v == 1024) pc.gather_one = v;
+  }
   if (const char *e = test_hook("FX_CSR_FULL_ROWS")) c->csr_full_rows = atoi(e) != 0 ? 1u : 0u;
   if (pc.front_ok) {
     hipError_t ce = fxk_configure_front();
@@ -1416,6 +1420,61 @@ fx_status fx_test_within_device(int device, const float *support_xyzw, uint32_t 
   if (e == hipSuccess) e = hipMemcpy(plain_out, d + o_c, (size_t)nq * 4, hipMemcpyDeviceToHost);
   (void)hipFree(d);
   FX_HIP(e);
+  return FX_OK;
+}
+
+// Test hook: what the support gather of the last batch left (include/fx.h).  Copies only: the stream is waited for, nothing is
+// launched and nothing on the device is written.  Every access to s_pts, s_cnt, ovf_*, row_map, row_kp, row_class, row_xa, the
+// work lists and their counters (4, 6, 8, FX_CNT_GROUP ..) behind gather_body and k_rng_ord in fx_kernels.hip is a load — the
+// tiers draw TICKETS from other counters —, and near_bits is written by the streaming pass alone: what is read here after a
+// batch is what the gather left.  (kp_nbrs is not read back: the descriptor tiers overwrite its flags with counts.)
+fx_status fx_test_gather_state(fx_ctx *c, fx_test_gather_info *info, const fx_test_gather_out *out) {
+  if (!c || !info) return fail(FX_ERR_INVALID_ARG, "null argument");
+  std::memset(info, 0, sizeof(*info));
+  const FxDevParams &P = c->dp;
+  const FxBuffers &b = c->buf;
+  const uint32_t B = c->plan_state.last_batch;
+  info->batch = B;
+  info->near_words = P.near_words, info->list_cap = P.list_cap, info->ovf_cap = P.ovf_cap, info->dense_min = P.dense_min;
+  info->max_dense_rows = P.max_dense_rows;
+  info->r2_support = P.r2_support, info->r2_search = P.r2_search, info->box_margin = c->box_margin;
+  if (!B || !P.estimate_descriptors) return FX_OK;
+  FX_HIP(hipSetDevice(c->device));
+  FX_HIP(hipStreamSynchronize(c->stream));
+  auto get = [](void *dst, const void *src, size_t bytes) -> hipError_t {
+    return dst && bytes ? hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) : hipSuccess;
+  };
+  uint32_t total = 0;
+  FX_HIP(hipMemcpy(&total, b.kp_offset + B, 4, hipMemcpyDeviceToHost));
+  const uint32_t rows = total < P.max_total_kp ? total : P.max_total_kp;
+  info->rows = rows;
+  std::vector<uint32_t> cnt(FX_N_COUNTERS), ovf(B);
+  FX_HIP(hipMemcpy(cnt.data(), b.counters, FX_N_COUNTERS * 4, hipMemcpyDeviceToHost));
+  FX_HIP(hipMemcpy(ovf.data(), b.ovf_cnt, (size_t)B * 4, hipMemcpyDeviceToHost));
+  info->n_list = cnt[4], info->n_wave = cnt[8], info->n_dense = cnt[6];
+  for (uint32_t g = 0; g < FX_GROUP_CLASSES; ++g) info->n_group[g] = cnt[FX_CNT_GROUP + g];
+  for (uint32_t i = 0; i < B; ++i) info->ovf_stored = std::max(info->ovf_stored, std::min(ovf[i], P.ovf_cap));
+  if (!out) return FX_OK;
+  const size_t S = info->ovf_stored;
+  FX_HIP(get(out->near_bits, b.near_bits, (size_t)B * P.near_words * 4));
+  FX_HIP(get(out->s_cnt, b.s_cnt, (size_t)rows * 4));
+  FX_HIP(get(out->s_pts, b.s_pts, (size_t)rows * P.list_cap * 16));
+  if (out->ovf_cnt) std::memcpy(out->ovf_cnt, ovf.data(), (size_t)B * 4);
+  for (uint32_t i = 0; i < B; ++i) {
+    const size_t n = std::min(ovf[i], P.ovf_cap);
+    FX_HIP(get(out->ovf_pts ? out->ovf_pts + i * S * 4 : nullptr, b.ovf_pts + (size_t)i * P.ovf_cap, n * 16));
+    FX_HIP(get(out->ovf_kp ? out->ovf_kp + i * S : nullptr, b.ovf_kp + (size_t)i * P.ovf_cap, n * 4));
+  }
+  FX_HIP(get(out->row_map, b.row_map, (size_t)rows * 8));
+  FX_HIP(get(out->row_kp, b.row_kp, (size_t)rows * 16));
+  FX_HIP(get(out->row_class, b.row_class, (size_t)rows));
+  FX_HIP(get(out->row_xa, b.row_xa, (size_t)rows * 8));
+  FX_HIP(get(out->list_desc, b.list_desc, (size_t)std::min(info->n_list, rows) * 4));
+  FX_HIP(get(out->wave_desc, b.wave_desc, (size_t)std::min(info->n_wave, rows) * 4));
+  for (uint32_t g = 0; g < FX_GROUP_CLASSES; ++g)
+    FX_HIP(get(out->group_desc ? out->group_desc + (size_t)g * rows : nullptr, b.group_desc + (size_t)g * P.max_total_kp,
+               (size_t)std::min(info->n_group[g], rows) * 4));
+  FX_HIP(get(out->dense_rows, b.dense_rows, (size_t)std::min(info->n_dense, P.max_dense_rows) * 4));
   return FX_OK;
 }
 

@@ -6961,7 +6961,14 @@ hipError_t fxk_configure(size_t ring_big, size_t merge_big, size_t merge_huge, s
   return e;
 }
 
-uint32_t fxk_near_words(uint32_t max_points) { return (max_points + FX_PREP_TILE - 1) / FX_PREP_TILE * (FX_PREP_TILE / 128); }  // one bit per 4 points
+// one bit per 4 points, for whole tiles of the streaming pass (which writes them) AND of the widest gather workgroup (whose
+// wavefronts fetch the two words of their 256 points for every tile that starts below n: GatherStream::nb_fill — a scan's last
+// 4096-point tile reached sixteen words past a region sized for 2048-point tiles, for the last scan past the allocation)
+uint32_t fxk_near_words(uint32_t max_points) {
+  constexpr uint32_t span = FX_PREP_TILE > 4u * FX_GATHER_WIDE_T ? FX_PREP_TILE : 4u * FX_GATHER_WIDE_T;
+  static_assert(span % FX_PREP_TILE == 0 && span % (4u * FX_GATHER_WIDE_T) == 0 && span % (4u * FX_GATHER_T) == 0, "whole tiles of every reader and the writer");
+  return (max_points + span - 1) / span * (span / 128);
+}
 void fxk_prep(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch, float near_margin, float el0, float inv_step,
               uint32_t clk_slot) {
   hipLaunchKernelGGL(k_prep, dim3(batch), dim3(FX_PREP_T), 0, s, P, B, near_margin, el0, inv_step, clk_slot);

@@ -64,6 +64,7 @@ struct FxPlanConfig {
   int prep_slices = -1;            // FX_PREP_SLICES: workgroups a scan in the separate kernels' streaming pass and ring split
   int merge_slices = -1;           // FX_MERGE_SLICES: workgroups a scan in the large merge tier's pair loop (1: the one launch)
   int gather_slices = -1;          // FX_GATHER_COUNTED: workgroups a scan in the support gather's counted slices (1: one workgroup a scan)
+  int gather_one = 0;              // FX_GATHER_ONE: 256 one k_gather workgroup a scan, 1024 k_gather_wide, at any batch size (0: by the batch)
   int dense_force = -1;            // FX_DENSE_SLOW: 1 always k_desc's stand-in workgroups, 0 always the tier's own kernels
   // FX_SKIP_EMPTY (experiment): bit 0 no k_front_redo, bit 1 no dense tier — only for workloads that need neither (a dense row
   // that does turn up is then neither computed NOR CLEARED: every tier clears its own rows, so such a row keeps what the last
@@ -280,6 +281,10 @@ inline FxLaunchPlan fx_plan_batch(const FxPlanConfig &cfg, FxPlanState *st, cons
   const uint32_t slices = batch >= 64u ? cfg.gather_slices_big : (batch >= 16u ? 4u : 16u);
   if (cfg.max_keypoints > cfg.gather_kcap) {  // (the wide workgroup, whatever the batch: its tables take most of a CU's LDS)
     p.gather = FX_GATHER_PASSES, p.gather_n = slices;
+  } else if (cfg.gather_one == 256) {  // (test hook: the kind batches of 1024 scans and more take, at any batch size)
+    p.gather = FX_GATHER_SLICED, p.gather_n = 1;
+  } else if (cfg.gather_one == 1024) {  // (test hook: the kind batches of 64 to 1023 scans take)
+    p.gather = FX_GATHER_WIDE, p.gather_n = 1;
   } else if (counted > 1u && cfg.gather_cnt) {
     p.gather = FX_GATHER_COUNTED, p.gather_n = umin(counted, cfg.gather_counted_max);
   } else if (slices == 1 && batch < 1024u) {

@@ -5,6 +5,7 @@
 // parity test on the device can see a wrong grid — this is where one shows.
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 
 #include "fx_launch_plan.h"
 
@@ -243,6 +244,36 @@ static void test_gather() {
   CHECK_EQ(plan1(c, Hints(0), 8).gather, FX_GATHER_COUNTED);
   c.estimate_descriptors = false;
   CHECK_EQ(plan1(c, Hints(0), 8).descriptors, 0);
+  // FX_GATHER_ONE: a one-workgroup kind at any batch size, also where the batch alone would pick counted slices or sixteen
+  // staged workgroups a scan — but never beyond the LDS tables; unset (0), every plan above is what it was
+  c = base(true);
+  c.max_points = 65536;
+  for (uint32_t batch : {1u, 3u, 16u, 64u, 1024u}) {
+    for (int cap = 0; cap < 2; ++cap) {
+      c.gather_one = 256;
+      p = plan1(c, Hints(0), batch, cap != 0);
+      CHECK_EQ(p.gather, FX_GATHER_SLICED);
+      CHECK_EQ(p.gather_n, 1);
+      CHECK_EQ(p.rng_ord, 0);
+      c.gather_one = 1024;
+      p = plan1(c, Hints(0), batch, cap != 0);
+      CHECK_EQ(p.gather, FX_GATHER_WIDE);
+      CHECK_EQ(p.gather_n, 1);
+      CHECK_EQ(p.rng_ord, 0);
+    }
+  }
+  c.gather_slices = 7;  // (it also beats the other hook)
+  CHECK_EQ(plan1(c, Hints(0), 3).gather, FX_GATHER_WIDE);
+  c.gather_slices = -1, c.max_keypoints = 2049;
+  p = plan1(c, Hints(0), 3);
+  CHECK_EQ(p.gather, FX_GATHER_PASSES);
+  CHECK_EQ(p.gather_n, 16);
+  c.gather_one = 256;
+  CHECK_EQ(plan1(c, Hints(0), 64).gather, FX_GATHER_PASSES);
+  c.gather_one = 0, c.max_keypoints = 50;
+  CHECK_EQ(plan1(c, Hints(0), 3).gather, FX_GATHER_COUNTED);  // (768 / 3, the maximum is 16)
+  CHECK_EQ(plan1(c, Hints(0), 3).gather_n, 16);
+  CHECK_EQ(FxPlanConfig().gather_one, 0);
 }
 
 static void test_merge_huge() {

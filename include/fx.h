@@ -1745,6 +1745,41 @@ fx_status fx_test_elevation_device(int device, const float *xyz, uint32_t n, flo
  * number of the n support points (xyzw records) closer than sqrt(r2), both ways. */
 fx_status fx_test_within_device(int device, const float *support_xyzw, uint32_t n, const float *query_xyzw, uint32_t nq, float r2,
                                 uint32_t *packed_out, uint32_t *plain_out);
+/* Test hook: what the support gather of the context's last batch left on the device, copied to the host.  Waits for the context's
+ * stream, launches nothing and writes nothing on the device.  Nothing after the gather (k_gather*, k_rng_ord) writes what is copied
+ * here — the descriptor tiers only load the lists, the overflow region, the counts, the row tables, the work lists and their
+ * counters —, so what is read after a batch is what the gather left.
+ * `info` is always filled: the constants a reference must not re-derive loosely, the sizes of the arrays, the work lists' counters.
+ * `out` may be NULL (sizes only); any of its pointers may be NULL (not copied).  rows = info->rows below. */
+typedef struct fx_test_gather_info {
+  uint32_t batch;        /* scans of the last batch */
+  uint32_t rows;         /* descriptor rows of the batch: min(kp_offset[batch], max_total_keypoints) */
+  uint32_t near_words;   /* words of a scan's near-sector bits (bit s of the scan, points 4 s .. 4 s + 3: bit s % 32 of word s / 32) */
+  uint32_t list_cap;     /* entries of a row's list */
+  uint32_t ovf_cap;      /* entries of a scan's overflow region */
+  uint32_t ovf_stored;   /* the largest min(ovf_cnt, ovf_cap) of the batch's scans: entries a scan copied to ovf_pts / ovf_kp */
+  uint32_t dense_min;    /* list rows hold up to min(list_cap, dense_min) support points */
+  uint32_t max_dense_rows;
+  float r2_support, r2_search, box_margin;
+  uint32_t n_list, n_wave, n_group[3], n_dense; /* the work lists' counters */
+} fx_test_gather_info;
+typedef struct fx_test_gather_out {
+  uint32_t *near_bits;  /* [batch][near_words] */
+  uint32_t *s_cnt;      /* [rows] */
+  float *s_pts;         /* [rows][list_cap][4]: x, y, z rotated, the point's index as bits */
+  uint32_t *ovf_cnt;    /* [batch] */
+  float *ovf_pts;       /* [batch][ovf_stored][4] */
+  uint32_t *ovf_kp;     /* [batch][ovf_stored] */
+  uint32_t *row_map;    /* [rows][2]: scan, keypoint */
+  float *row_kp;        /* [rows][4] */
+  uint8_t *row_class;   /* [rows] */
+  float *row_xa;        /* [rows][2] */
+  uint32_t *list_desc;  /* [min(n_list, rows)] */
+  uint32_t *wave_desc;  /* [min(n_wave, rows)] */
+  uint32_t *group_desc; /* [3][rows]: the leading min(n_group[c], rows) of class c */
+  uint32_t *dense_rows; /* [min(n_dense, max_dense_rows)] */
+} fx_test_gather_out;
+fx_status fx_test_gather_state(fx_ctx *ctx, fx_test_gather_info *info, const fx_test_gather_out *out);
 #endif /* FX_TEST_HOOKS */
 
 #ifdef __cplusplus
