@@ -2443,8 +2443,15 @@ __device__ __forceinline__ bool merge_body(const FxDevParams &P, const FxBuffers
   if (!LDS_PTS) mlist = reinterpret_cast<uint16_t *>(cand_kp);  // the row is scratch until its values are written at the end
   const float inv_w = 1.0f / (sqrtf(P.r2_merge) * 1.01f);
   auto bin_of = [&](int cx, int cy) { return (uint32_t)((cx & (int)nb_mask) | ((cy & (int)nb_mask) << nb_shift)); };
-  auto cell_x = [&](float x) { return (int)floorf((x - P.x_min) * inv_w); };
-  auto cell_y = [&](float y) { return (int)floorf((y - P.y_min) * inv_w); };
+  // Two candidates within the merge radius must land in neighbouring cells.  The cells are 1 % wider than the radius, and that
+  // margin covers the rounding of (x - origin) * inv_w while the result stays below some 41 000 cells (2^-22 of it < 0.0099).
+  // A box of fewer than 2^15 cells is measured from its own corner; a wider one (x_min = -4e6, -1e30, -inf: "no limit") from
+  // the sensor, where the same holds out to 2^15 cells — 6.6 km at the launch preset's radius.  Measured from -4e6 the
+  // coordinates would be rounded to 0.25 m first, and two candidates 0.19 m apart could end up two cells apart, unmerged.
+  const float ox = (P.x_max - P.x_min) * inv_w < 32768.0f ? P.x_min : 0.0f;
+  const float oy = (P.y_max - P.y_min) * inv_w < 32768.0f ? P.y_min : 0.0f;
+  auto cell_x = [&](float x) { return (int)floorf((x - ox) * inv_w); };
+  auto cell_y = [&](float y) { return (int)floorf((y - oy) * inv_w); };
   // ref: node.cpp:217  z = intensity*0.75*clusterRadiusThreshold/2  (double, left to right)
   auto pseudo_z = [&](float el) { return (float)((double)el * 0.75 * P.crt / 2); };
   auto merge_pt = [&](uint32_t i) {  // (x, y, pseudo z, elevation)
