@@ -468,7 +468,7 @@ EXPORTS = ("fx_version", "fx_check_abi", "fx_status_str", "fx_last_error", "fx_p
            "fx_synth_scan", "fx_unpack_pointcloud2", "fx_pack_pointxyzi")
 # the header's FX_TEST_HOOKS section: exported by lib/libfx_hip_test.so only
 TEST_EXPORTS = ("fx_test_sort_replay", "fx_test_sort_replay_ranked", "fx_test_sort_replay_lists", "fx_test_sort_replay_device",
-                "fx_test_elevation_device", "fx_test_within_device", "fx_test_gather_state")
+                "fx_test_cc_order_device", "fx_test_elevation_device", "fx_test_within_device", "fx_test_gather_state")
 
 _lib = None
 _libs = {}
@@ -658,6 +658,8 @@ def load():
         lib.fx_test_sort_replay_lists.argtypes = [_U32P, C.c_uint32, _U32P]
         lib.fx_test_sort_replay_lists.restype = None
         lib.fx_test_sort_replay_device.argtypes = [C.c_int, _U32P, C.c_uint32, C.c_uint32, _U32P]
+        lib.fx_test_cc_order_device.argtypes = [C.c_int, _U32P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _U32P, C.c_uint32, C.c_int,
+                                                _U32P, _U32P, _U32P, _U32P]
         lib.fx_test_elevation_device.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.fx_test_within_device.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p]
         lib.fx_test_gather_state.argtypes = [C.c_void_p, C.POINTER(FxTestGatherInfo), C.POINTER(FxTestGatherOut)]

@@ -1500,6 +1500,47 @@ fx_status fx_test_sort_replay_device(int device, const uint32_t *sizes, uint32_t
   return FX_OK;
 }
 
+// Test hook: cc_order itself (the code the ring and merge kernels run) on caller-supplied size sequences.
+fx_status fx_test_cc_order_device(int device, const uint32_t *sizes, uint32_t n_seq, uint32_t n, uint32_t min_sz, uint32_t max_sz,
+                                  const uint32_t *ccap, uint32_t nt, int gs, uint32_t *perm_out, uint32_t *root_out, uint32_t *n_c_out,
+                                  uint32_t *guard_bad_out) {
+  if (!sizes || !ccap || !perm_out || !n_c_out || !guard_bad_out) return fail(FX_ERR_INVALID_ARG, "null argument");
+  if (nt != 64 && nt != 256 && nt != 1024) return fail(FX_ERR_INVALID_ARG, "nt: 64, 256 or 1024");
+  if (n > 4096) return fail(FX_ERR_TOO_LARGE, "n > 4096");
+  if (!n_seq || !n) return FX_OK;
+  uint32_t ccap_max = 0;
+  for (uint32_t q = 0; q < n_seq; ++q) ccap_max = std::max(ccap_max, ccap[q]);
+  if (ccap_max > 4096) return fail(FX_ERR_TOO_LARGE, "ccap > 4096");  // (three arrays of it fit the LDS form)
+  for (size_t i = 0; i < (size_t)n_seq * n; ++i)
+    if (sizes[i] > 0xffffu) return fail(FX_ERR_INVALID_ARG, "a size above 65535 does not fit the sort record");
+  FX_HIP(hipSetDevice(device));
+  // one allocation: sizes | parent | ccaps | perm | roots | n_c | guard_bad | scratch (GS)
+  const size_t w_seq = (size_t)n_seq * n, w_scratch = gs ? fxk_test_cc_order_scratch_words(n_seq, ccap_max) : 0;
+  const size_t o_parent = w_seq, o_ccap = o_parent + n, o_perm = o_ccap + n_seq, o_root = o_perm + w_seq, o_nc = o_root + w_seq,
+               o_bad = o_nc + n_seq, o_scratch = o_bad + n_seq, words = o_scratch + w_scratch;
+  std::vector<uint32_t> iota(n);
+  for (uint32_t i = 0; i < n; ++i) iota[i] = i;
+  uint32_t *d = nullptr;
+  FX_HIP(hipMalloc((void **)&d, words * 4));
+  hipError_t e = hipMemset(d + o_perm, 0xff, (o_bad - o_perm) * 4);
+  if (e == hipSuccess) e = hipMemset(d + o_bad, 0, (size_t)n_seq * 4);
+  if (e == hipSuccess) e = hipMemcpy(d, sizes, w_seq * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d + o_parent, iota.data(), (size_t)n * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d + o_ccap, ccap, (size_t)n_seq * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess)
+    e = fxk_test_cc_order(nullptr, nt, gs != 0, d, d + o_parent, n_seq, n, min_sz, max_sz, d + o_ccap, ccap_max, d + o_scratch, d + o_perm,
+                          d + o_root, d + o_nc, d + o_bad);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(perm_out, d + o_perm, w_seq * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && root_out) e = hipMemcpy(root_out, d + o_root, w_seq * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(n_c_out, d + o_nc, (size_t)n_seq * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(guard_bad_out, d + o_bad, (size_t)n_seq * 4, hipMemcpyDeviceToHost);
+  (void)hipFree(d);
+  FX_HIP(e);
+  return FX_OK;
+}
+
 #endif  // FX_TEST_HOOKS
 
 // Diagnostic: what the last completed batch left for the next one's tier grids (FxBuffers::tier_hint).

@@ -791,7 +791,7 @@ __device__ __noinline__ void sort_partition_wave(uint32_t *crec, int n, int *stk
 
 // Size-admissible components in discovery order (ascending smallest index), then PCL's final
 // std::sort(rbegin, rend, bySize): its partition phase is replayed by one wavefront (only needed
-// above 16 clusters; one lane, sequentially, beyond 192), its insertion phase — a stable sort — as a parallel ranking
+// above 16 clusters; one lane, sequentially, beyond 256), its insertion phase — a stable sort — as a parallel ranking
 // (csrc/fx_sort_replay.h).  crec[s] = (size << 16) | discovery ordinal, in the order PCL returns
 // the clusters; croot[ordinal] = root index; tmp: scratch.  croot / crec / tmp hold ccap entries;
 // returns the cluster count, which the caller must check against ccap (nothing is written past it,
@@ -835,7 +835,7 @@ __device__ __forceinline__ uint32_t cc_order(uint32_t n, const uint32_t *parent,
         sort_partition_wave<3, GS>(crec, (int)n_c, (int *)(s_w + 32), pos, pos + n_c);
       } else if (n_c <= 256) {
         sort_partition_wave<4, GS>(crec, (int)n_c, (int *)(s_w + 32), pos, pos + n_c);
-      } else if (threadIdx.x == 0) {  // more clusters than three words of lanes: one lane, sequentially
+      } else if (threadIdx.x == 0) {  // more clusters than four words of lanes: one lane, sequentially
         fx_sort_detail::RevView v{crec, (int)n_c};
         fx_sort_partition_phase(v, (int)n_c, (int *)(s_w + 32));
       }
@@ -6889,8 +6889,9 @@ extern "C" __global__ __launch_bounds__(FX_WG) void k_pack_xyzi32(const float4 *
 
 // ====================================================================== launchers
 #ifdef FX_TEST_HOOKS
-// Test hook (fx_test_sort_replay_device): the cluster-order replay exactly as cc_order runs it, on
-// arbitrary size sequences; one 64-thread workgroup per sequence, n <= 192.
+// Test hook (fx_test_sort_replay_device): the wavefront partition phase for up to three words of lanes and a ranking of
+// its own, in LDS, on arbitrary size sequences; one 64-thread workgroup per sequence, n <= 192.  (A restatement of the
+// dispatch, not cc_order: the <4> form, the one-lane form beyond 256 and the GS forms run under k_test_cc_order below.)
 extern "C" __global__ __launch_bounds__(64) void k_test_sort_replay(const uint32_t *sizes, uint32_t n, uint32_t *perm) {
   __shared__ uint32_t crec[192], tmp[192], stk[FX_SORT_STACK_WORDS];
   const uint32_t *src = sizes + (size_t)blockIdx.x * n;
@@ -6915,6 +6916,40 @@ extern "C" __global__ __launch_bounds__(64) void k_test_sort_replay(const uint32
   }
   __syncthreads();
   for (uint32_t c = threadIdx.x; c < n; c += 64) perm[(size_t)blockIdx.x * n + c] = tmp[c] & 0xffffu;
+}
+
+// Test hook (fx_test_cc_order_device): cc_order ITSELF — the acceptance pass, the dispatch over the partition forms, the
+// ranking — on caller-supplied sizes; one workgroup per sequence, every entry its own root (parent[i] = i, csize = sizes).
+// croot / crec / tmp hold ccap[seq] entries each and lie where the kernels put them: behind the scratch words in LDS, or
+// (GS) in a scratch region of HBM with only the scratch words — block helpers, sort stack — in LDS, as in k_slow.  Each
+// array is followed by FX_TEST_CC_GUARD guard words; guard_bad[seq] counts the ones cc_order changed.
+#define FX_TEST_CC_GUARD 16
+#define FX_TEST_CC_SW 152  // (block helpers and, from word 32, the sort stack: the ring and merge kernels' s_w)
+template <int NT, bool GS>
+__global__ __launch_bounds__(NT) void k_test_cc_order(const uint32_t *sizes, const uint32_t *parent, uint32_t n, uint32_t min_sz,
+                                                      uint32_t max_sz, const uint32_t *ccaps, uint32_t ccap_max, uint32_t *gs,
+                                                      uint32_t *perm, uint32_t *roots, uint32_t *n_c_out, uint32_t *guard_bad) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  const uint32_t seq = blockIdx.x, ccap = ccaps[seq], G = FX_TEST_CC_GUARD;
+  uint32_t *s_w = smem;
+  uint32_t *p = GS ? gs + (size_t)seq * 3u * (ccap_max + G) : smem + FX_TEST_CC_SW;
+  uint32_t *croot = p, *crec = croot + ccap + G, *tmp = crec + ccap + G;
+  for (uint32_t k = threadIdx.x; k < 3u * (ccap + G); k += NT) p[k] = 0xc0ffee00u ^ k;
+  wg_sync<GS>();
+  const uint32_t n_c = cc_order<NT, GS>(n, parent, sizes + (size_t)seq * n, min_sz, max_sz, croot, crec, tmp, ccap, s_w);
+  wg_sync<GS>();
+  uint32_t bad = 0;
+  for (uint32_t k = threadIdx.x; k < 3u * G; k += NT) {
+    const uint32_t at = (k / G) * (ccap + G) + ccap + k % G;
+    bad += p[at] != (0xc0ffee00u ^ at) ? 1u : 0u;
+  }
+  if (threadIdx.x == 0) n_c_out[seq] = n_c;
+  if (bad) atomicAdd(&guard_bad[seq], bad);  // (zeroed by the launcher's caller)
+  if (n_c > ccap) return;
+  for (uint32_t c = threadIdx.x; c < n_c; c += NT) {
+    perm[(size_t)seq * n + c] = crec[c] & 0xffffu;
+    roots[(size_t)seq * n + c] = croot[c];
+  }
 }
 
 #endif  // FX_TEST_HOOKS
@@ -7177,6 +7212,33 @@ void fxk_test_elevation(hipStream_t s, const float *xyz, uint32_t n, const doubl
 }
 void fxk_test_sort_replay(hipStream_t s, const uint32_t *sizes, uint32_t n_seq, uint32_t n, uint32_t *perm) {
   hipLaunchKernelGGL(k_test_sort_replay, dim3(n_seq), dim3(64), 0, s, sizes, n, perm);
+}
+size_t fxk_test_cc_order_scratch_words(uint32_t n_seq, uint32_t ccap_max) { return (size_t)n_seq * 3u * (ccap_max + FX_TEST_CC_GUARD); }
+// nt: 64, 256 (k_slow, k_merge_small) or 1024 (k_rings_large, k_merge_big); gs: the arrays in `scratch` instead of LDS
+hipError_t fxk_test_cc_order(hipStream_t s, uint32_t nt, bool gs, const uint32_t *sizes, const uint32_t *parent, uint32_t n_seq, uint32_t n,
+                             uint32_t min_sz, uint32_t max_sz, const uint32_t *ccaps, uint32_t ccap_max, uint32_t *scratch, uint32_t *perm,
+                             uint32_t *roots, uint32_t *n_c, uint32_t *guard_bad) {
+  const size_t lds = (FX_TEST_CC_SW + (gs ? 0u : 3u * (size_t)(ccap_max + FX_TEST_CC_GUARD))) * sizeof(uint32_t);
+  if (lds > 64u * 1024u) return hipErrorInvalidValue;
+#define FX_TEST_CC_LAUNCH(NT, GS) \
+  hipLaunchKernelGGL((k_test_cc_order<NT, GS>), dim3(n_seq), dim3(NT), lds, s, sizes, parent, n, min_sz, max_sz, ccaps, ccap_max, scratch, perm, \
+                     roots, n_c, guard_bad)
+  if (nt == 64 && !gs)
+    FX_TEST_CC_LAUNCH(64, false);
+  else if (nt == 64)
+    FX_TEST_CC_LAUNCH(64, true);
+  else if (nt == 256 && !gs)
+    FX_TEST_CC_LAUNCH(256, false);
+  else if (nt == 256)
+    FX_TEST_CC_LAUNCH(256, true);
+  else if (nt == 1024 && !gs)
+    FX_TEST_CC_LAUNCH(1024, false);
+  else if (nt == 1024)
+    FX_TEST_CC_LAUNCH(1024, true);
+  else
+    return hipErrorInvalidValue;
+#undef FX_TEST_CC_LAUNCH
+  return hipGetLastError();
 }
 #endif  // FX_TEST_HOOKS
 void fxk_rng_ord(hipStream_t s, const FxDevParams &P, const FxBuffers &B, uint32_t batch) {

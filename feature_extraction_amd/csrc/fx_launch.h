@@ -86,6 +86,10 @@ void fxk_pack_features(hipStream_t s, const FxDevParams &P, const FxBuffers &B, 
                        uint32_t capacity, uint32_t grid);
 #ifdef FX_TEST_HOOKS
 void fxk_test_sort_replay(hipStream_t s, const uint32_t *sizes, uint32_t n_seq, uint32_t n, uint32_t *perm);
+size_t fxk_test_cc_order_scratch_words(uint32_t n_seq, uint32_t ccap_max);
+hipError_t fxk_test_cc_order(hipStream_t s, uint32_t nt, bool gs, const uint32_t *sizes, const uint32_t *parent, uint32_t n_seq, uint32_t n,
+                             uint32_t min_sz, uint32_t max_sz, const uint32_t *ccaps, uint32_t ccap_max, uint32_t *scratch, uint32_t *perm,
+                             uint32_t *roots, uint32_t *n_c, uint32_t *guard_bad);
 void fxk_test_elevation(hipStream_t s, const float *xyz, uint32_t n, const double *tab, float *fast, uint8_t *ok, float *exact);
 void fxk_test_within(hipStream_t s, const float4 *sp, uint32_t n, const float4 *queries, uint32_t nq, float r2, uint32_t *packed, uint32_t *plain);
 #endif

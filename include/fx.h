@@ -1736,6 +1736,18 @@ void fx_test_sort_replay_lists(const uint32_t *sizes, uint32_t n, uint32_t *perm
 /* Test hook: the replay as the kernels run it (wavefront partition phase + ranking) on device `device`,
  * one workgroup per sequence; n <= 192 per sequence.  sizes / perm_out: host arrays [n_seq][n]. */
 fx_status fx_test_sort_replay_device(int device, const uint32_t *sizes, uint32_t n_seq, uint32_t n, uint32_t *perm_out);
+/* Test hook: cc_order itself, the routine the ring and merge kernels call (acceptance by size, discovery ordinals, the dispatch
+ * over the partition forms, the stable ranking), one workgroup of nt threads (64, 256 or 1024) per sequence.  Entry i of a
+ * sequence is a component of its own of sizes[seq][i] (<= 65535) members; those with min_sz <= size <= max_sz are accepted.
+ * gs = 0: croot / crec / tmp of ccap[seq] entries each in LDS; gs != 0: in a scratch region of HBM, the block helpers and the
+ * sort stack in LDS, as the slow tier places them.  n, ccap[seq] <= 4096.
+ * n_c_out[seq]: accepted entries.  If n_c_out[seq] <= ccap[seq]: perm_out[seq][s] = discovery ordinal (rank among the accepted,
+ * in index order) of the cluster PCL returns at position s, root_out[seq][ordinal] = its index (root_out may be NULL), s and
+ * ordinal < n_c_out[seq]; the rest of both rows, and all of them otherwise, is 0xffffffff.
+ * guard_bad_out[seq]: how many of the guard words behind the three arrays the routine changed (0 whether it fits or not). */
+fx_status fx_test_cc_order_device(int device, const uint32_t *sizes, uint32_t n_seq, uint32_t n, uint32_t min_sz, uint32_t max_sz,
+                                  const uint32_t *ccap, uint32_t nt, int gs, uint32_t *perm_out, uint32_t *root_out, uint32_t *n_c_out,
+                                  uint32_t *guard_bad_out);
 /* Test hook: the two evaluations of a point's elevation angle the filter stage has (ref: node.cpp:147-156) on host
  * points xyz[n][3]: the table-driven one (fast_out, and whether it vouches for its value: fast_ok_out) and the one
  * through the library's fp64 atan2 that takes the points it does not vouch for (exact_out). */

@@ -36,13 +36,14 @@ def test_test_entry_points_only_in_the_test_build(fxlib, fxtestlib):
     import subprocess
     from feature_extraction_amd import build
     hooks = _declared(test_section=True)
-    assert sorted(capi.TEST_EXPORTS) == hooks and len(hooks) >= 7 and "fx_test_gather_state" in hooks
+    assert sorted(capi.TEST_EXPORTS) == hooks and len(hooks) >= 8 and "fx_test_gather_state" in hooks and "fx_test_cc_order_device" in hooks
     assert not [n for n in hooks + list(capi.EXPORTS) if not hasattr(fxtestlib, n)]
     dyn = subprocess.check_output(["nm", "-D", "--defined-only", build.LIB], text=True)
     assert "fx_create" in dyn and "fx_test_" not in dyn, [l for l in dyn.splitlines() if "fx_test_" in l]
     product = open(build.LIB, "rb").read()
     assert b"k_test_" not in product  # (kernel names are in the code object's symbol table)
-    assert b"k_test_within" in open(build.build_test_hooks(), "rb").read()
+    test = open(build.build_test_hooks(), "rb").read()
+    assert b"k_test_within" in test and b"k_test_cc_order" in test
 
 
 def test_struct_sizes_match_header(fxlib):
