@@ -414,6 +414,26 @@ class FxSpliceSource(C.Structure):
 FX_SPLICE_LAST_SCAN = 0xffffffff  # scan0: the source's last scan, read on the device
 
 
+class FxDeskewOptions(C.Structure):
+    _fields_ = [("start_turn", C.c_double), ("ref_fraction", C.c_double), ("sweep_fraction", C.c_double), ("direction", C.c_int32),
+                ("source", C.c_uint32), ("require_flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class FxDeskewScan(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("motion", C.c_uint32), ("rows_moved", C.c_uint32), ("max_shift", C.c_float)]
+
+
+FX_DESKEW_LINKS, FX_DESKEW_PER_SCAN = 0, 1
+FX_DESKEW_MOVED, FX_DESKEW_NEXT_LINK, FX_DESKEW_NO_MOTION, FX_DESKEW_NO_SCAN = 0x1, 0x2, 0x4, 0x8
+FX_DESKEW_NO_RECORD = 0xffffffff
+# include/fx.h FX_DESKEW_TURN_K restated (tests/test_deskew_reference.py holds the two together)
+DESKEW_TURN_K = (0.15915173357526405, -0.052943764423474274, 0.030823588143917297, -0.01856560178002491, 0.008407119202664756,
+                 -0.001873333241134883)
+# fx_deskew_scan as a numpy record (deskew_records)
+DESKEW_DTYPE = np.dtype([("flags", "<u4"), ("motion", "<u4"), ("rows_moved", "<u4"), ("max_shift", "<f4")])
+DESKEW_DEFAULTS = dict(start_turn=0.5, ref_fraction=1.0, sweep_fraction=1.0, direction=-1, source=FX_DESKEW_LINKS, require_flags=0x1)
+
+
 class FxTestGatherInfo(C.Structure):  # (the header's FX_TEST_HOOKS section)
     _fields_ = [("batch", C.c_uint32), ("rows", C.c_uint32), ("near_words", C.c_uint32), ("list_cap", C.c_uint32), ("ovf_cap", C.c_uint32),
                 ("ovf_stored", C.c_uint32), ("dense_min", C.c_uint32), ("max_dense_rows", C.c_uint32),
@@ -464,6 +484,7 @@ EXPORTS = ("fx_version", "fx_check_abi", "fx_status_str", "fx_last_error", "fx_p
            "fx_map_join_options_default", "fx_map_join_segments",
            "fx_map_loop_options_default", "fx_map_close_loop", "fx_map_loop_correct_poses",
            "fx_map_find_loop_options_default", "fx_map_find_loop", "fx_splice_blocks",
+           "fx_deskew_options_default", "fx_deskew_keypoint_block",
            "fx_rotation_from_roll_pitch", "fx_sc3d_tables", "fx_sc3d_xaxis", "fx_synth_cfg_vlp16",
            "fx_synth_scan", "fx_unpack_pointcloud2", "fx_pack_pointxyzi")
 # the header's FX_TEST_HOOKS section: exported by lib/libfx_hip_test.so only
@@ -638,6 +659,10 @@ def load():
     lib.fx_map_find_loop.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(FxMapFindLoopOptions), C.c_void_p, C.c_void_p]
     lib.fx_splice_blocks.argtypes = [C.c_void_p, C.POINTER(FxSpliceSource), C.POINTER(FxSpliceSource), C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
                                      C.c_uint32, C.c_uint32]
+    lib.fx_deskew_options_default.argtypes = [C.POINTER(FxDeskewOptions)]
+    lib.fx_deskew_options_default.restype = None
+    lib.fx_deskew_keypoint_block.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
+                                             C.POINTER(FxDeskewOptions), C.c_void_p]
     lib.fx_rotation_from_roll_pitch.argtypes = [C.c_double, C.c_double, _F32P]
     lib.fx_rotation_from_roll_pitch.restype = None
     lib.fx_sc3d_tables.argtypes = [C.c_double, _F32P, _F32P, _F32P, _F32P]
@@ -2749,6 +2774,113 @@ def splice_kp_offset(off_a, off_b, a=(FX_SPLICE_LAST_SCAN, 1), b=(0, 0xffffffff)
     return np.concatenate([[0], np.cumsum(np.concatenate(n))]).astype(np.uint32)
 
 
+# ---- keypoints de-skewed for the sensor's motion during a sweep (include/fx.h fx_deskew_keypoint_block)
+def deskew_records(out):
+    """A host copy of fx_deskew_keypoint_block's records (a torch tensor, or any array of n * 16 bytes) as a structured numpy array
+    of DESKEW_DTYPE records."""
+    if hasattr(out, "detach"):
+        out = out.detach().cpu().numpy()
+    return np.ascontiguousarray(out).view(np.uint8).reshape(-1).view(DESKEW_DTYPE).copy()
+
+
+def deskew_turn(x, y):
+    """include/fx.h "Turn of a row": atan2(y, x) in turns through the odd polynomial DESKEW_TURN_K, Python floats in the clause's
+    order."""
+    k = DESKEW_TURN_K
+    ax, ay = abs(x), abs(y)
+    hi, lo = (ay, ax) if ay > ax else (ax, ay)
+    if not hi > 0.0:
+        return 0.0
+    a = lo / hi
+    t = a * a
+    g = a * (k[0] + t * (k[1] + t * (k[2] + t * (k[3] + t * (k[4] + t * k[5])))))
+    q = 0.25 - g if ay > ax else g
+    h = 0.5 - q if x < 0.0 else q
+    return -h if y < 0.0 else h
+
+
+def deskew_share(x, y, start_turn=0.5, ref_fraction=1.0, sweep_fraction=1.0, direction=-1):
+    """include/fx.h "Sweep fraction": (phi, a) of a row at (x, y), Python floats."""
+    u = float(direction) * (deskew_turn(x, y) - start_turn)
+    phi = u - float(math.floor(u))
+    if phi >= 1.0:
+        phi = 0.0
+    return phi, (phi - ref_fraction) * sweep_fraction
+
+
+def _deskew_usable(m, p, require_flags):
+    """include/fx.h "Usable motion" of record p."""
+    r = m[p]
+    finite = all(math.isfinite(float(r[f])) for f in ("c", "s", "tx", "ty", "tz"))
+    return (int(r["flags"]) & require_flags) == require_flags and finite and float(r["c"]) > 0.0
+
+
+def deskew_reference(block, max_scans, max_total, motions, n_scans, **opts):
+    """The definition of fx_deskew_keypoint_block (include/fx.h) in numpy and Python floats.  block: the source keypoint block's
+    bytes, laid out for (max_scans, max_total); motions: REG_DTYPE records ([>= n_scans - 1] with FX_DESKEW_LINKS, [>= n_scans]
+    with FX_DESKEW_PER_SCAN; may be None where none is read); opts: the fields of fx_deskew_options (DESKEW_DEFAULTS).  Returns
+    (the destination block as uint8, DESKEW_DTYPE [n_scans])."""
+    bad = set(opts) - set(DESKEW_DEFAULTS)
+    if bad:
+        raise TypeError(f"unknown deskew options {sorted(bad)}")
+    o = dict(DESKEW_DEFAULTS, **opts)
+    start, ref, sweep = float(o["start_turn"]), float(o["ref_fraction"]), float(o["sweep_fraction"])
+    direction, source, require = int(o["direction"]), int(o["source"]), int(o["require_flags"]) & 0xffffffff
+    n_scans = int(n_scans)
+    if not (1 <= n_scans <= max_scans and math.isfinite(start) and 0.0 <= ref <= 1.0 and 0.0 < sweep <= 1.0 and direction in (1, -1) and
+            source in (FX_DESKEW_LINKS, FX_DESKEW_PER_SCAN)):
+        raise ValueError("arguments outside what fx_deskew_keypoint_block accepts")
+    lay = keypoint_block_layout(max_scans, max_total)
+    src = np.ascontiguousarray(block).view(np.uint8).reshape(-1)[:16 * lay.n_rows]
+    assert len(src) == 16 * lay.n_rows, (len(src), max_scans, max_total)
+    dst = src.copy()
+    u = src.view(np.uint32)
+    S, rows = min(n_scans, int(u[0]), max_scans), min(int(u[1]), max_total)
+    off = [int(x) for x in u[4:5 + max_scans]]
+    kp = src[16 * lay.k0:].view(np.float32).reshape(-1, 4)
+    out_kp = dst[16 * lay.k0:].view(np.float32).reshape(-1, 4)
+    m = None if motions is None else np.asarray(motions)
+    rec = np.zeros(n_scans, DESKEW_DTYPE)
+    rec["flags"], rec["motion"] = FX_DESKEW_NO_SCAN, FX_DESKEW_NO_RECORD
+    # the motion of every scan
+    for b in range(S):
+        flags, p = FX_DESKEW_NO_MOTION, FX_DESKEW_NO_RECORD
+        if source == FX_DESKEW_PER_SCAN:
+            if _deskew_usable(m, b, require):
+                flags, p = FX_DESKEW_MOVED, b
+        elif b >= 1 and _deskew_usable(m, b - 1, require):
+            flags, p = FX_DESKEW_MOVED, b - 1
+        elif b + 1 < S and _deskew_usable(m, b, require):
+            flags, p = FX_DESKEW_MOVED | FX_DESKEW_NEXT_LINK, b
+        rec["flags"][b], rec["motion"][b] = flags, p
+    # the scan of every row (fx_track_landmarks's scan(r))
+    scan = np.full(max_total, -1, np.int64)
+    for b in range(S):
+        scan[off[b]:min(off[b + 1], rows)] = b
+    shift_bits = np.zeros(n_scans, np.uint32)
+    for r in range(rows):
+        b = int(scan[r])
+        if b < 0 or not rec["flags"][b] & FX_DESKEW_MOVED or not np.isfinite(kp[r, :3]).all():
+            continue
+        x, y, z = (float(v) for v in kp[r, :3])
+        _, a = deskew_share(x, y, start, ref, sweep, direction)
+        w = abs(a)
+        if w == 0.0:
+            continue
+        c, s, tx, ty, tz = (float(m[f][rec["motion"][b]]) for f in ("c", "s", "tx", "ty", "tz"))
+        G = (c, s, tx, ty, tz) if a > 0.0 else (c, -s, -(c * tx + s * ty), (s * tx - c * ty), -tz)
+        ca, sa, txa, tya, tza = _loop_transform(G, 0.0, 0.0, w)
+        with np.errstate(all="ignore"):
+            new = np.array([(ca * x - sa * y) + txa, (sa * x + ca * y) + tya, z + tza], np.float64).astype(np.float32)
+            out_kp[r, :3] = new
+            dx, dy = float(new[0]) - x, float(new[1]) - y
+            sh = np.float32(math.sqrt(dx * dx + dy * dy))
+        rec["rows_moved"][b] += 1
+        shift_bits[b] = max(int(shift_bits[b]), int(sh.view(np.uint32)))
+    rec["max_shift"] = shift_bits.view(np.float32)
+    return dst, rec
+
+
 @contextlib.contextmanager
 def _on_stream(stream_ptr, dev):
     """The stream hand-over of every wrapper that enqueues on a context's stream: that stream (stream_ptr, a hipStream_t as an
@@ -3445,6 +3577,35 @@ class Context:
             check(self.lib.fx_splice_blocks(self.handle, C.byref(src[0]), C.byref(src[1]), C.c_void_p(kp_ptr), int(dst_kp[1]), int(dst_kp[2]),
                                             C.c_void_p(csr_ptr), rows, cap))
         return dst_kp, dst_csr
+
+    def deskew_keypoint_block(self, kp, motions, n_scans, dst=None, out=None, **opts):
+        """fx_deskew_keypoint_block: kp is the source keypoint block as (device tensor, max_scans, max_total_keypoints), motions the
+        device torch.float64 tensor [n, 8] of fx_registration records register_matches returned for pairs_consecutive
+        (FX_DESKEW_LINKS, n >= n_scans - 1; None with n_scans == 1) or one record a scan (FX_DESKEW_PER_SCAN, n >= n_scans).  dst: the
+        destination block's tensor (None allocates one; kp's own tensor: in place); out: a device torch.int32 tensor [n_scans, 4] to
+        reuse.  opts: the fields of fx_deskew_options (DESKEW_DEFAULTS).  Returns ((dst, max_scans, max_total_keypoints), out);
+        deskew_records views a host copy of `out` as named fields.  Stream-correct like match_descriptors; never waits for the
+        stream."""
+        import torch
+        kb, scans, total = kp
+        dev = torch.device("cuda", self.device)
+        nbytes, n_scans = int(self.lib.fx_keypoint_block_bytes(int(scans), int(total))), int(n_scans)
+        if dst is None:
+            dst = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        for b in (kb, dst):
+            if b.device != dev or b.numel() * b.element_size() < nbytes or not b.is_contiguous() or b.data_ptr() % 16:
+                raise ValueError(f"a keypoint block must be a contiguous, 16-byte aligned tensor of >= {nbytes} bytes on {dev}")
+        opt = _options(FxDeskewOptions, DESKEW_DEFAULTS, "deskew", opts)
+        opt.direction = int(dict(DESKEW_DEFAULTS, **opts)["direction"])
+        need = n_scans if opt.source == FX_DESKEW_PER_SCAN else n_scans - 1
+        if motions is not None and (motions.dtype != torch.float64 or motions.device != dev or motions.dim() != 2 or motions.shape[1] != 8 or
+                                    motions.shape[0] < need or not motions.is_contiguous()):
+            raise ValueError(f"motions must be a contiguous torch.float64 tensor [>= {need}, 8] on {dev}")
+        out = _out_tensor(out, (max(n_scans, 0), 4), torch.int32, dev, f"out must be a contiguous torch.int32 tensor [{n_scans}, 4] on {dev}", typed=True)
+        with _on_stream(self.stream_ptr(), dev):
+            check(self.lib.fx_deskew_keypoint_block(self.handle, C.c_void_p(kb.data_ptr()), C.c_void_p(dst.data_ptr()), int(scans), int(total),
+                                                    _ptr(motions), n_scans, C.byref(opt), C.c_void_p(out.data_ptr())))
+        return (dst, int(scans), int(total)), out
 
     def map_create(self, max_landmarks, max_carry_rows):
         """fx_map_create: a persistent landmark map owned by this context (Map.update after every track_landmarks)."""

@@ -1671,6 +1671,43 @@ fx_status fx_splice_blocks(fx_ctx *c, const fx_splice_source *a, const fx_splice
   return FX_OK;
 }
 
+void fx_deskew_options_default(fx_deskew_options *o) {
+  if (!o) return;
+  o->start_turn = 0.5, o->ref_fraction = 1.0, o->sweep_fraction = 1.0;
+  o->direction = -1;
+  o->source = FX_DESKEW_LINKS, o->require_flags = FX_REG_VALID, o->reserved = 0u;
+}
+
+fx_status fx_deskew_keypoint_block(fx_ctx *c, const void *src, void *dst, uint32_t max_scans, uint32_t max_total, const fx_registration *motions,
+                                   uint32_t n_scans, const fx_deskew_options *opt, fx_deskew_scan *out) {
+  if (!c) return fail(FX_ERR_INVALID_ARG, "null argument");
+  FX_TRY(query_check(max_scans, n_scans));
+  fx_deskew_options o;
+  fx_deskew_options_default(&o);
+  if (opt) o = *opt;
+  if (o.source != FX_DESKEW_LINKS && o.source != FX_DESKEW_PER_SCAN) return fail(FX_ERR_INVALID_ARG, "source must be FX_DESKEW_LINKS or FX_DESKEW_PER_SCAN");
+  if (!src || !dst || !out || (!motions && !(o.source == FX_DESKEW_LINKS && n_scans == 1u))) return fail(FX_ERR_INVALID_ARG, "null argument");
+  if (!std::isfinite(o.start_turn)) return fail(FX_ERR_INVALID_ARG, "start_turn must be finite");
+  if (!(o.ref_fraction >= 0.0 && o.ref_fraction <= 1.0)) return fail(FX_ERR_INVALID_ARG, "ref_fraction must be in [0, 1]");
+  if (!(o.sweep_fraction > 0.0 && o.sweep_fraction <= 1.0)) return fail(FX_ERR_INVALID_ARG, "sweep_fraction must be in (0, 1]");
+  if (o.direction != 1 && o.direction != -1) return fail(FX_ERR_INVALID_ARG, "direction must be +1 or -1");
+  if (o.reserved) return fail(FX_ERR_INVALID_ARG, "reserved must be 0");
+  if (((uintptr_t)src % 16) != 0 || ((uintptr_t)dst % 16) != 0 || ((uintptr_t)motions % 8) != 0 || ((uintptr_t)out % 4) != 0)
+    return fail(FX_ERR_INVALID_ARG, "the keypoint blocks must be 16-byte, the motion records 8-byte, out 4-byte aligned");
+  const size_t bytes = fxk_kp_block_bytes(max_scans, max_total);
+  if (dst != src && (uintptr_t)dst < (uintptr_t)src + bytes && (uintptr_t)src < (uintptr_t)dst + bytes)
+    return fail(FX_ERR_INVALID_ARG, "dst overlaps src without being src (in place: dst == src)");
+  FX_HIP(hipSetDevice(c->device));
+  FxDeskewArgs A{};
+  A.src = (const uint32_t *)src, A.dst = (uint32_t *)dst, A.max_scans = max_scans, A.max_total = max_total;
+  A.motions = motions, A.n_scans = n_scans;
+  A.start_turn = o.start_turn, A.ref_fraction = o.ref_fraction, A.sweep_fraction = o.sweep_fraction, A.direction = (double)o.direction;
+  A.source = o.source, A.require_flags = o.require_flags;
+  A.out = out;
+  FX_HIP(fxk_deskew(c->stream, A, 8u * c->plan_cfg.n_cu));
+  return FX_OK;
+}
+
 fx_status fx_get_descriptors_csr(fx_ctx *c, fx_descriptor_csr_view *out) {
   if (!c || !out) return fail(FX_ERR_INVALID_ARG, "null argument");
   if (!c->csr_valid) return fail(FX_ERR_INVALID_ARG, "the last batch was not FX_OUT_HOST | FX_OUT_DESC_CSR");

@@ -534,6 +534,17 @@ struct FxSpliceArgs {
   uint32_t dst_max_rows, dst_cap;
   uint32_t *plan;               // [FX_SPLICE_PLAN_WORDS]
 };
+// fx_deskew_keypoint_block (csrc/fx_deskew.hip): the launch's arguments.  dst may be src itself; the options are fx.h's, checked.
+struct FxDeskewArgs {
+  const uint32_t *src;          // keypoint block (include/fx.h fx_pack_keypoint_block)
+  uint32_t *dst;                // a block of the same layout
+  uint32_t max_scans, max_total;
+  const void *motions;          // fx_registration [n_scans - 1] (LINKS) or [n_scans] (PER_SCAN)
+  uint32_t n_scans;
+  double start_turn, ref_fraction, sweep_fraction, direction;  // (direction: +1.0 or -1.0)
+  uint32_t source, require_flags;
+  void *out;                    // fx_deskew_scan [n_scans], zeroed in front of the launch
+};
 #define FX_TRACK_NONE 0xffffffffu
 #define FX_CNT_QPOOL 32   // counters[32]: entries of the dense tier's query pool in use
 #define FX_CNT_LARGE2 16  // counters[16 + c]: rings of XCD class c the second run tier hands to the workgroup tier

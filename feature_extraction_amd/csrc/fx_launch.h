@@ -93,7 +93,8 @@ hipError_t fxk_test_cc_order(hipStream_t s, uint32_t nt, bool gs, const uint32_t
 void fxk_test_elevation(hipStream_t s, const float *xyz, uint32_t n, const double *tab, float *fast, uint8_t *ok, float *exact);
 void fxk_test_within(hipStream_t s, const float4 *sp, uint32_t n, const float4 *queries, uint32_t nq, float r2, uint32_t *packed, uint32_t *plain);
 #endif
-// ---- fx_match.hip, fx_register.hip, fx_track.hip, fx_splice.hip
+// ---- fx_match.hip, fx_register.hip, fx_track.hip, fx_splice.hip, fx_deskew.hip
+hipError_t fxk_deskew(hipStream_t s, const FxDeskewArgs &A, uint32_t max_grid);
 hipError_t fxk_match(hipStream_t s, const FxMatchArgs &A, uint32_t n_items, uint32_t mut_n, uint32_t shifts);
 uint32_t fxk_match_tile_rows(void);
 hipError_t fxk_register(hipStream_t s, const FxRegisterArgs &A, uint32_t n_pairs);

@@ -24,6 +24,7 @@
 #include "fx_map_consensus.h"
 #include "fx_map_grid.h"
 #include "fx_launch.h"
+#include "fx_rigid.h"
 #include "fx_scan_query.h"
 
 #define FXA_WG FXC_MAP_WG
@@ -32,9 +33,7 @@
 
 
 namespace fxa {
-struct Rigid {
-  double c, s, tx, ty, tz;
-};
+// (Rigid: csrc/fx_rigid.h)
 // a Rigid from / into anything with the members c, s, tx, ty, tz: an fx_pose, the head of a result record
 template <typename P>
 __device__ __forceinline__ Rigid load_rigid(const P &p) {

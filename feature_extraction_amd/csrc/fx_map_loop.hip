@@ -60,20 +60,7 @@ __device__ __forceinline__ double loop_weight(unsigned long long t2, uint32_t s0
   if (t2 >= b) return 1.0;
   return (double)(t2 - a) / (double)(b - a);
 }
-// include/fx.h "Interpolated transform": the one statement on the device, for the landmarks, last_pose and the poses.  alpha in (0, 1]
-__device__ __forceinline__ Rigid loop_transform(const Rigid &T, double px, double py, double alpha) {
-  if (alpha == 1.0) return T;
-  const double cu = (1.0 - alpha) + alpha * T.c, su = alpha * T.s;
-  const double nrm = sqrt(cu * cu + su * su);
-  Rigid o;
-  o.c = cu / nrm, o.s = su / nrm;
-  const double gx = (T.c * px - T.s * py) + T.tx, gy = (T.s * px + T.c * py) + T.ty;
-  const double hx = px + alpha * (gx - px), hy = py + alpha * (gy - py);
-  o.tx = hx - (o.c * px - o.s * py);
-  o.ty = hy - (o.s * px + o.c * py);
-  o.tz = alpha * T.tz;
-  return o;
-}
+// (include/fx.h "Interpolated transform" is csrc/fx_rigid.h's loop_transform, which fx_deskew_keypoint_block shares)
 __device__ __forceinline__ fx_map_loop_result no_fit(const Ctl &C, uint32_t flags) {
   fx_map_loop_result r;
   store_rigid(r, C.p);

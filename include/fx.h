@@ -1698,6 +1698,82 @@ fx_status fx_splice_blocks(fx_ctx *ctx, const fx_splice_source *a, const fx_spli
     void *dst_kp_block_device, uint32_t dst_max_scans, uint32_t dst_max_total_keypoints,
     void *dst_csr_block_device /* or NULL: keypoints only */, uint32_t dst_max_rows, uint32_t dst_capacity);
 
+/* ---- De-skewing a block's keypoints for the sensor's motion during a sweep ----
+ * A spinning sensor captures a scan over a whole sweep while it moves; every call behind fx_process_batch (fx_register_matches,
+ * fx_track_landmarks, fx_map_update, fx_map_localize, fx_map_relocalize, fx_map_observe, fx_map_expect, fx_map_discover, the loop
+ * calls) reads a scan's keypoints as one rigid snapshot.  All rings fire at one azimuth at nearly the same time, so a pole's
+ * clusters, and the keypoint the secondary merge makes of them, are captured within about a millisecond: moving the KEYPOINT by the
+ * sensor's motion between its capture and the scan's stamp is, to first order, de-skewing the points.  fx_deskew_keypoint_block
+ * does that with the motion over one scan period the caller holds on the device (fx_register_matches's records, or odometry) and
+ * writes a block of the same layout, which every call above takes unchanged.  The descriptors (local, R = 2.5 m) stay as they are.
+ * Sizes: S = min(n_scans, the block's scans, max_scans), rows = min(the block's keypoints stored, max_total_keypoints); scan(r) and
+ * the non-rows exactly as in fx_track_landmarks (csrc/fx_scan_query.h, the one device definition).  The whole block is written:
+ * row 0, the kp_offset rows and the flag rows byte for byte, and byte for byte every row of the keypoint area that is not corrected
+ * (rows beyond `rows`, non-rows, rows of scans >= S included).  All n_scans records are written and nothing beyond them.
+ * Every floating-point step below is fp64, no contraction, no fma, each expression in the stated order.
+ * Usable motion: a record is usable iff (flags & require_flags) == require_flags, its c, s, tx, ty and tz are finite, and c > 0
+ * (less than a quarter turn a period; it also keeps the interpolation's norm away from 0).
+ * The motion of scan b < S: FX_DESKEW_PER_SCAN: record b.  FX_DESKEW_LINKS: record b - 1 (when b >= 1) if usable; otherwise
+ * record b (when b + 1 < S) if usable, with FX_DESKEW_NEXT_LINK (constant velocity: the motion into the next scan stands for
+ * this one).  With a usable record the scan is FX_DESKEW_MOVED and `motion` its index.  Without: FX_DESKEW_NO_MOTION, motion =
+ * 0xffffffff, the scan's rows are copied.  b >= S: FX_DESKEW_NO_SCAN only, motion = 0xffffffff, rows_moved = 0, max_shift = 0.
+ * Turn of a row (x, y the floats widened): ax = |x|, ay = |y|, hi = ay > ax ? ay : ax, lo = the other; the turn is 0.0 when hi
+ * is not > 0; otherwise a = lo / hi, t = a a, g = a (k0 + t (k1 + t (k2 + t (k3 + t (k4 + t k5))))) with FX_DESKEW_TURN_K's six
+ * constants (a least-squares odd polynomial for atan(a) / 2 pi on [0, 1]: within 2.9e-7 of a turn, monotone, a step of 5e-7
+ * upwards at the octant seam); q = ay > ax ? 0.25 - g : g; h = x < 0.0 ? 0.5 - q : q; turn = y < 0.0 ? -h : h (-0.0 is not below
+ * 0).  No library arctangent: numpy reproduces the turn bit for bit.
+ * Sweep fraction: u = (double)direction (turn - start_turn); phi = u - floor(u), taken as 0.0 when that is >= 1.0;
+ * a = (phi - ref_fraction) sweep_fraction.
+ * Correction of a row of a MOVED scan whose x, y, z are finite (every other row is copied and not counted): w = |a|; w == 0.0
+ * copies the row bit for bit.  G = the motion M when a > 0; when a < 0, M's inverse taken as (c, -s, -(c tx + s ty),
+ * (s tx - c ty), -tz).  (ca, sa, txa, tya, tza) is fx_map_close_loop's "Interpolated transform" of G with pivot (0, 0) and alpha =
+ * w (the same device function; w == 1 gives G bit for bit).  x' = (ca x - sa y) + txa, y' = (sa x + ca y) + tya, z' = z + tza,
+ * each rounded once to float; the fourth word (the elevation) is copied bit for bit.
+ * Records: rows_moved counts the corrected rows; max_shift is the maximum over them of (float)sqrt(dx dx + dy dy), dx and dy
+ * taken in fp64 between the stored floats and the source floats (a 32-bit integer maximum on the bit pattern: order-free).
+ * dst may be src itself (in place) or disjoint from it.  motions[p] of FX_DESKEW_LINKS, p < n_scans - 1, is the record "scan
+ * p + 1 -> scan p" fx_register_matches wrote for capi.pairs_consecutive; it is read on the device, so a register in front of the
+ * call needs no host read.
+ * FX_ERR_INVALID_ARG with the reason in fx_last_error(), nothing launched, no output byte touched: a NULL required pointer
+ * (motions may be NULL only with FX_DESKEW_LINKS and n_scans == 1; opt NULL = the defaults), n_scans == 0 or n_scans > max_scans,
+ * a start_turn that is not finite, ref_fraction outside [0, 1], sweep_fraction outside (0, 1], a direction that is not +1 or -1,
+ * an unknown source, reserved != 0, blocks not 16-byte, records not 8-byte or `out` not 4-byte aligned, a dst that overlaps src
+ * without being equal to it.
+ * Limits: the motion is taken as constant over a period; levelling (roll, pitch) changes a row's azimuth only to second order; a
+ * pole at the sweep's seam is ambiguous (with the reference's pass-through box, x >= 0, and the seam behind the sensor none lies
+ * there); descriptors are not recomputed; de-skewing the points themselves is out of scope.
+ * Enqueued on the context's stream: a memset of the records and one launch, no host synchronisation, no allocation; needs no
+ * batch to have been processed.  The same bytes from run to run and with any number of contexts in flight: every decision is an
+ * integer or an ordered, correctly rounded operation on one lane, the two reductions are 32-bit integer atomics.  New in 0.7
+ * (added symbols only). */
+#define FX_DESKEW_LINKS    0u  /* motions[p], p < n_scans - 1, is the link record "scan p + 1 -> scan p" (what fx_register_matches wrote for pairs_consecutive) */
+#define FX_DESKEW_PER_SCAN 1u  /* motions[b], b < n_scans, is scan b's own motion over one scan period (odometry, IMU), same meaning of the five doubles */
+/* k0 .. k5 of the turn's polynomial: the one place the device reads (csrc/fx_deskew.hip) and capi.DESKEW_TURN_K restates */
+#define FX_DESKEW_TURN_K {0.15915173357526405, -0.052943764423474274, 0.030823588143917297, -0.01856560178002491, 0.008407119202664756, -0.001873333241134883}
+typedef struct fx_deskew_options {   /* 40 B */
+  double start_turn;      /* azimuth where a sweep begins, in turns of atan2(y, x); finite; default 0.5 (behind the sensor) */
+  double ref_fraction;    /* the sweep fraction the scan's pose refers to; 0 start .. 1 end; in [0, 1]; default 1.0 */
+  double sweep_fraction;  /* share of the scan period that one sweep takes; in (0, 1]; default 1.0 (continuous rotation) */
+  int32_t direction;      /* +1: azimuth grows during the sweep, -1: it falls (a Velodyne seen from above; note node.cpp:65's roll - pi flips it); default -1 */
+  uint32_t source;        /* FX_DESKEW_LINKS (default) or FX_DESKEW_PER_SCAN */
+  uint32_t require_flags; /* FX_REG_* bits a motion record must carry; default FX_REG_VALID */
+  uint32_t reserved;      /* 0 */
+} fx_deskew_options;
+#define FX_DESKEW_MOVED 0x1u      /* a usable motion was found: the scan's finite rows were corrected */
+#define FX_DESKEW_NEXT_LINK 0x2u  /* (LINKS) link b - 1 was not usable, link b was taken */
+#define FX_DESKEW_NO_MOTION 0x4u  /* no usable motion: the scan's rows are copied bit for bit */
+#define FX_DESKEW_NO_SCAN 0x8u    /* b is beyond the block's scans */
+typedef struct fx_deskew_scan {   /* 16 B, one per scan */
+  uint32_t flags, motion;         /* motion: index of the record used, 0xffffffff: none */
+  uint32_t rows_moved;            /* rows written through the correction (w != 0) */
+  float max_shift;                /* largest xy distance between a corrected row (as stored) and its source row; 0 when none */
+} fx_deskew_scan;
+void fx_deskew_options_default(fx_deskew_options *o);
+fx_status fx_deskew_keypoint_block(fx_ctx *ctx,
+    const void *src_block_device, void *dst_block_device, uint32_t max_scans, uint32_t max_total_keypoints,
+    const fx_registration *motions_device, uint32_t n_scans, const fx_deskew_options *opt /* NULL: defaults */,
+    fx_deskew_scan *out_device /* [n_scans] */);
+
 /* Rotation matrix of rotateCloud (ref: node.cpp:161-164): R = Ry(pitch)*Rx(roll)
  * through Eigen's AngleAxisf -> Quaternionf -> toRotationMatrix, all float. Host only. */
 void fx_rotation_from_roll_pitch(double roll, double pitch, float R[9]);
