@@ -9,8 +9,8 @@ LIB = os.path.join(HERE, "lib", "libfx_hip.so")
 # the same sources with -DFX_TEST_HOOKS: the environment hooks tests (and A/B measurements) use to push work through the
 # rarely used tiers and kernels — the product library has none of them compiled in
 LIB_TEST = os.path.join(HERE, "lib", "libfx_hip_test.so")
-SOURCES = ["fx_kernels.hip", "fx_match.hip", "fx_register.hip", "fx_track.hip", "fx_map.hip", "fx_map_grid.hip", "fx_map_merge.hip", "fx_map_localize.hip", "fx_map_relocalize.hip", "fx_map_observe.hip", "fx_map_expect.hip", "fx_map_discover.hip", "fx_map_compact.hip", "fx_map_append.hip", "fx_splice.hip", "fx_deskew.hip", "fx_map_assoc.hip", "fx_map_join.hip", "fx_map_loop.hip", "fx_map_find_loop.hip", "fx_api.cpp", "fx_host.cpp"]
-HEADERS = ["fx_device.h", "fx_launch.h", "fx_launch_plan.h", "fx_scan_query.h", "fx_consensus.h", "fx_map_consensus.h", "fx_map_grid.h", "fx_map_assoc.h", "fx_rigid.h", "fx_map_constellation.h", "fx_sort_replay.h", os.path.join("..", "..", "include", "fx.h")]
+SOURCES = ["fx_kernels.hip", "fx_match.hip", "fx_register.hip", "fx_track.hip", "fx_map.hip", "fx_map_grid.hip", "fx_map_merge.hip", "fx_map_localize.hip", "fx_map_follow.hip", "fx_map_relocalize.hip", "fx_map_observe.hip", "fx_map_expect.hip", "fx_map_discover.hip", "fx_map_compact.hip", "fx_map_append.hip", "fx_splice.hip", "fx_deskew.hip", "fx_map_assoc.hip", "fx_map_join.hip", "fx_map_loop.hip", "fx_map_find_loop.hip", "fx_api.cpp", "fx_host.cpp"]
+HEADERS = ["fx_device.h", "fx_launch.h", "fx_launch_plan.h", "fx_scan_query.h", "fx_consensus.h", "fx_map_consensus.h", "fx_map_localize_body.h", "fx_map_grid.h", "fx_map_assoc.h", "fx_rigid.h", "fx_map_constellation.h", "fx_sort_replay.h", os.path.join("..", "..", "include", "fx.h")]
 # -ffp-contract=off: the numerics contract forbids FMA contraction (results must follow
 # PCL/FLANN/Eigen operation order); fp32 divide/sqrt stay at hipcc's correctly rounded default.
 # -O2, not -O3: the kernels are big (k_front 60 KB, k_rings_runs 42 KB of code against a 64 KB instruction cache that two CUs

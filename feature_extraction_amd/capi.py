@@ -434,6 +434,23 @@ DESKEW_DTYPE = np.dtype([("flags", "<u4"), ("motion", "<u4"), ("rows_moved", "<u
 DESKEW_DEFAULTS = dict(start_turn=0.5, ref_fraction=1.0, sweep_fraction=1.0, direction=-1, source=FX_DESKEW_LINKS, require_flags=0x1)
 
 
+class FxFollowOptions(C.Structure):
+    _fields_ = [("loc", FxLocalizeOptions), ("chain_scans", C.c_uint32), ("require_flags", C.c_uint32), ("max_lost", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class FxFollowScan(C.Structure):
+    _fields_ = [("prior", FxPose), ("flags", C.c_uint32), ("motion", C.c_uint32), ("streak", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+FX_FOLLOW_START, FX_FOLLOW_LINK, FX_FOLLOW_COASTED, FX_FOLLOW_HELD, FX_FOLLOW_LOST = 0x1, 0x2, 0x4, 0x8, 0x10
+FX_FOLLOW_NO_MOTION = 0xffffffff
+# fx_follow_scan as a numpy record (follow_records); "prior" is a POSE_DTYPE record
+FOLLOW_DTYPE = np.dtype([("prior", POSE_DTYPE), ("flags", "<u4"), ("motion", "<u4"), ("streak", "<u4"), ("reserved", "<u4")])
+# the fields of fx_follow_options: fx_localize_options's (segment: every segment) and the chain's own
+FOLLOW_DEFAULTS = dict(LOC_DEFAULTS, segment=FX_LOC_ANY_SEGMENT, chain_scans=0, require_flags=FX_REG_VALID, max_lost=5)
+
+
 class FxTestGatherInfo(C.Structure):  # (the header's FX_TEST_HOOKS section)
     _fields_ = [("batch", C.c_uint32), ("rows", C.c_uint32), ("near_words", C.c_uint32), ("list_cap", C.c_uint32), ("ovf_cap", C.c_uint32),
                 ("ovf_stored", C.c_uint32), ("dense_min", C.c_uint32), ("max_dense_rows", C.c_uint32),
@@ -484,7 +501,7 @@ EXPORTS = ("fx_version", "fx_check_abi", "fx_status_str", "fx_last_error", "fx_p
            "fx_map_join_options_default", "fx_map_join_segments",
            "fx_map_loop_options_default", "fx_map_close_loop", "fx_map_loop_correct_poses",
            "fx_map_find_loop_options_default", "fx_map_find_loop", "fx_splice_blocks",
-           "fx_deskew_options_default", "fx_deskew_keypoint_block",
+           "fx_deskew_options_default", "fx_deskew_keypoint_block", "fx_follow_options_default", "fx_map_follow",
            "fx_rotation_from_roll_pitch", "fx_sc3d_tables", "fx_sc3d_xaxis", "fx_synth_cfg_vlp16",
            "fx_synth_scan", "fx_unpack_pointcloud2", "fx_pack_pointxyzi")
 # the header's FX_TEST_HOOKS section: exported by lib/libfx_hip_test.so only
@@ -663,6 +680,10 @@ def load():
     lib.fx_deskew_options_default.restype = None
     lib.fx_deskew_keypoint_block.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
                                              C.POINTER(FxDeskewOptions), C.c_void_p]
+    lib.fx_follow_options_default.argtypes = [C.POINTER(FxFollowOptions)]
+    lib.fx_follow_options_default.restype = None
+    lib.fx_map_follow.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                  C.POINTER(FxFollowOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.fx_rotation_from_roll_pitch.argtypes = [C.c_double, C.c_double, _F32P]
     lib.fx_rotation_from_roll_pitch.restype = None
     lib.fx_sc3d_tables.argtypes = [C.c_double, _F32P, _F32P, _F32P, _F32P]
@@ -1770,6 +1791,80 @@ def map_localize_reference(state, kp_offset, kp_rows, prior_poses, n_scans, q_ma
                 rec["pose"]["tz"][b] = qtz + dtz
             map_id[i[final]] = g[final]
     return {"rec": rec, "map_id_of_row": map_id, "nearest_of_row": nearest, "corr": corrs}
+
+
+# ---- chains of scans followed through the map (include/fx.h fx_map_follow)
+def follow_records(out):
+    """A host copy of fx_map_follow's per-scan records (a torch tensor, or any array of n * 64 bytes) as FOLLOW_DTYPE records."""
+    if hasattr(out, "detach"):
+        out = out.detach().cpu().numpy()
+    return np.ascontiguousarray(out).view(np.uint8).reshape(-1).view(FOLLOW_DTYPE).copy()
+
+
+_POSE5 = ("c", "s", "tx", "ty", "tz")
+
+
+def map_follow_reference(state, kp_offset, kp_rows, links, start_poses, n_scans, q_max_rows=None, **options):
+    """The definition of fx_map_follow (include/fx.h): the chain in Python floats around map_localize_reference called one scan at
+    a time (every other scan of such a call has a prior that is not finite and is left out).  The prior is the track's good-link
+    composition as track_reference writes it; nothing of the localise is restated.  state, kp_offset, kp_rows, q_max_rows: as in
+    map_localize_reference; links: REG_DTYPE [>= n_scans - 1] (may be None where none is read); start_poses: POSE_DTYPE
+    [>= n_chains]; options: the fields of fx_follow_options (FOLLOW_DEFAULTS).  Returns {"rec": LOC_DTYPE [n_scans], "follow":
+    FOLLOW_DTYPE [n_scans], "poses": POSE_DTYPE [n_scans], "map_id_of_row", "nearest_of_row": int32 [q_max_rows]}."""
+    bad = set(options) - set(FOLLOW_DEFAULTS)
+    if bad:
+        raise TypeError(f"unknown follow options {sorted(bad)}")
+    o = dict(FOLLOW_DEFAULTS, **options)
+    loc = {k: o[k] for k in LOC_DEFAULTS}
+    n_scans, chain, require, max_lost = int(n_scans), int(o["chain_scans"]), int(o["require_flags"]), int(o["max_lost"])
+    if n_scans < 1 or chain < 0 or max_lost < 1 or require & ~(FX_REG_VALID | FX_REG_TRUNCATED | FX_REG_NO_HYPOTHESIS):
+        raise ValueError("arguments outside what fx_map_follow accepts")
+    L = chain if 0 < chain < n_scans else n_scans
+    n_chains = -(-n_scans // L)
+    if links is None and L > 1:
+        raise ValueError("links may be None only when every chain is one scan")
+    starts = np.asarray(start_poses)[:n_chains]
+    off = [int(x) for x in kp_offset]
+    kp = np.ascontiguousarray(kp_rows, dtype=np.float32)
+    R = len(kp) if q_max_rows is None else int(q_max_rows)
+    S, rows = min(n_scans, len(off) - 1), min(len(kp), R)
+    usable = lambda p: (int(links["flags"][p]) & require) == require and all(math.isfinite(float(links[f][p])) for f in _POSE5)
+    rec, fol = np.zeros(n_scans, LOC_DTYPE), np.zeros(n_scans, FOLLOW_DTYPE)
+    map_id, nearest = np.full(R, -1, np.int32), np.full(R, -1, np.int32)
+    for j in range(n_chains):
+        last, streak = None, 0
+        for b in range(j * L, min((j + 1) * L, n_scans)):
+            P = np.zeros(1, POSE_DTYPE)
+            flags, motion = FX_FOLLOW_START, FX_FOLLOW_NO_MOTION
+            if b == j * L:
+                P[0] = starts[j]
+            else:
+                P[0] = rec["pose"][b - 1]  # p*
+                flags = FX_FOLLOW_HELD
+                own = usable(b - 1)
+                if own:
+                    last = b - 1
+                pc, ps, ptx, pty, ptz = (float(P[f][0]) for f in _POSE5)
+                if last is not None and b < S and all(math.isfinite(v) for v in (pc, ps, ptx, pty, ptz)):
+                    rc, rs, rtx, rty, rtz = (float(links[f][last]) for f in _POSE5)
+                    new = (pc * rc - ps * rs, ps * rc + pc * rs, (pc * rtx - ps * rty) + ptx, (ps * rtx + pc * rty) + pty, ptz + rtz)  # (track_reference's fold)
+                    if all(math.isfinite(v) for v in new):
+                        P[0] = new + (int(starts["segment"][j]), 0)
+                        flags, motion = (FX_FOLLOW_LINK if own else FX_FOLLOW_COASTED), last
+            pri = np.zeros(n_scans, POSE_DTYPE)
+            for f in _POSE5:
+                pri[f] = np.nan
+            pri[b] = P[0]
+            one = map_localize_reference(state, off, kp, pri, n_scans, q_max_rows=R, **loc)
+            rec[b] = one["rec"][b]
+            if b < S:
+                lo = min(off[b], rows)
+                hi = max(min(off[b + 1], rows), lo)
+                map_id[lo:hi], nearest[lo:hi] = one["map_id_of_row"][lo:hi], one["nearest_of_row"][lo:hi]
+            streak = 0 if int(rec["flags"][b]) & FX_LOC_VALID else streak + 1
+            fol["prior"][b] = P[0]
+            fol["flags"][b], fol["motion"][b], fol["streak"][b] = flags | (FX_FOLLOW_LOST if streak >= max_lost else 0), motion, streak
+    return {"rec": rec, "follow": fol, "poses": rec["pose"].copy(), "map_id_of_row": map_id, "nearest_of_row": nearest}
 
 
 # ---- localised scans folded into the map (include/fx.h fx_map_observe)
@@ -3024,6 +3119,41 @@ class Map:
                                            C.c_void_p(prior_poses.data_ptr()), n_scans, n_rows, C.byref(opt), C.c_void_p(recs.data_ptr()),
                                            C.c_void_p(ids.data_ptr() if n_rows else None), _ptr(nearest if n_rows else None)))
         return recs, ids, nearest
+
+    def follow(self, kp, links, start_poses, n_scans, q_max_rows=None, out=None, poses=None, nearest=None, **opts):
+        """fx_map_follow: chains of the consecutive scans of the keypoint block kp = (device tensor, max_scans,
+        max_total_keypoints) followed through this map.  links: a device tensor of the register's n_scans - 1 link records (None
+        where every chain is one scan); start_poses: a device tensor that begins with the n_chains fx_pose records, or a view into
+        one (records[last] of the batch before: a record begins with its pose), or a device address; it is read on the device.
+        opts: the fields of fx_follow_options (FOLLOW_DEFAULTS).  Returns (records, follow, poses, map_id_of_row, nearest_of_row):
+        device tensors of n_scans * 112, n_scans * 64 and n_scans * 48 bytes (localize_records, follow_records and a POSE_DTYPE
+        view read them) and torch.int32 [q_max_rows] each; out = (records, follow, map_id_of_row) reuses three, poses=False and
+        nearest=False pass NULL (None is returned), a tensor reuses it.  Stream-correct like update(); never waits for the stream."""
+        import torch
+        kb, scans, total = kp
+        dev = torch.device("cuda", self.ctx.device)
+        n_scans = int(n_scans)
+        n_rows = int(total) if q_max_rows is None else int(q_max_rows)
+        bad = set(opts) - set(FOLLOW_DEFAULTS)
+        if bad:
+            raise TypeError(f"unknown follow options {sorted(bad)}")
+        o = dict(FOLLOW_DEFAULTS, **opts)
+        opt = FxFollowOptions()
+        opt.loc = _options(FxLocalizeOptions, {k: o[k] for k in LOC_DEFAULTS}, "follow", {})
+        opt.chain_scans, opt.require_flags, opt.max_lost = (int(o[k]) & 0xffffffff for k in ("chain_scans", "require_flags", "max_lost"))
+        error = f"outputs must be contiguous tensors of {n_scans} * 112, {n_scans} * 64, {n_scans} * 48 and {n_rows} * 4 bytes on {dev}"
+        recs, fol, ids = (None, None, None) if out is None else out
+        recs = _out_tensor(recs, (n_scans, LOC_DTYPE.itemsize // 8), torch.float64, dev, error)
+        fol = _out_tensor(fol, (n_scans, FOLLOW_DTYPE.itemsize // 8), torch.float64, dev, error)
+        poses = _out_tensor(poses, (n_scans, POSE_DTYPE.itemsize // 8), torch.float64, dev, error)
+        ids = _out_tensor(ids, (n_rows,), torch.int32, dev, error)
+        nearest = _out_tensor(nearest, (n_rows,), torch.int32, dev, error)
+        starts = start_poses.data_ptr() if hasattr(start_poses, "data_ptr") else int(start_poses)
+        with _on_stream(self.ctx.stream_ptr(), dev):
+            check(self.lib.fx_map_follow(self.ctx.handle, self.handle, C.c_void_p(kb.data_ptr()), int(scans), int(total), _ptr(links),
+                                         C.c_void_p(starts), n_scans, n_rows, C.byref(opt), C.c_void_p(recs.data_ptr()), C.c_void_p(fol.data_ptr()),
+                                         _ptr(poses), C.c_void_p(ids.data_ptr() if n_rows else None), _ptr(nearest if n_rows else None)))
+        return recs, fol, poses, ids, nearest
 
     def observe(self, kp, loc, n_scans, map_id_of_row, q_max_rows=None, out=None, gained=None, observed=None, **opts):
         """fx_map_observe: the inlier rows of localised scans folded into the landmarks they were matched to (include/fx.h).  kp is

@@ -2035,6 +2035,46 @@ fx_status fx_map_localize(fx_ctx *c, fx_map *m, const void *kp, uint32_t max_sca
   return FX_OK;
 }
 
+void fx_follow_options_default(fx_follow_options *o) {
+  if (!o) return;
+  fx_localize_options_default(&o->loc);
+  o->loc.segment = FX_LOC_ANY_SEGMENT;
+  o->chain_scans = 0u, o->require_flags = FX_REG_VALID, o->max_lost = 5u, o->reserved = 0u;
+}
+
+fx_status fx_map_follow(fx_ctx *c, fx_map *m, const void *kp, uint32_t max_scans, uint32_t max_total, const fx_registration *links,
+                        const fx_pose *starts, uint32_t n_scans, uint32_t q_max_rows, const fx_follow_options *opt, fx_localization *out,
+                        fx_follow_scan *follow, fx_pose *poses, int32_t *map_id_of_row, int32_t *nearest_of_row) {
+  FX_TRY(map_call_check(c, m));
+  FX_TRY(query_check(max_scans, n_scans));
+  fx_follow_options o;
+  fx_follow_options_default(&o);
+  if (opt) o = *opt;
+  const uint32_t chain = o.chain_scans && o.chain_scans < n_scans ? o.chain_scans : n_scans;
+  if (!kp || !starts || !out || !follow || (q_max_rows && !map_id_of_row) || (!links && chain > 1u)) return fail(FX_ERR_INVALID_ARG, "null argument");
+  if (((uintptr_t)kp % 16) != 0 || ((uintptr_t)links % 8) != 0 || ((uintptr_t)starts % 8) != 0 || ((uintptr_t)out % 8) != 0 ||
+      ((uintptr_t)follow % 8) != 0 || ((uintptr_t)poses % 8) != 0 || ((uintptr_t)map_id_of_row % 4) != 0 || ((uintptr_t)nearest_of_row % 4) != 0)
+    return fail(FX_ERR_INVALID_ARG, "the keypoint block must be 16-byte, the records 8-byte, the words 4-byte aligned");
+  FX_TRY(consensus_options_check(o.loc));
+  if (o.loc.reserved || o.reserved) return fail(FX_ERR_INVALID_ARG, "reserved must be 0");
+  if (!o.max_lost) return fail(FX_ERR_INVALID_ARG, "max_lost must be at least 1");
+  if (o.require_flags & ~(FX_REG_VALID | FX_REG_TRUNCATED | FX_REG_NO_HYPOTHESIS))
+    return fail(FX_ERR_INVALID_ARG, "unknown require_flags bits (only the FX_REG_* flags are defined)");
+  FX_HIP(hipSetDevice(c->device));
+  FxMapFollowArgs A{};
+  map_grid_view(&A.L.G, m, (double)o.loc.search_dist);
+  query_args(&A.L.K, kp, max_scans, max_total, n_scans, q_max_rows);
+  A.L.inlier_dist = o.loc.inlier_dist, A.L.min_baseline = o.loc.min_baseline;
+  A.L.hyp_corr = o.loc.hyp_corr, A.L.min_inliers = o.loc.min_inliers, A.L.min_landmark_obs = o.loc.min_landmark_obs, A.L.segment = o.loc.segment;
+  A.L.out = out, A.L.map_id_of_row = map_id_of_row, A.L.nearest_of_row = nearest_of_row;
+  A.links = links, A.starts = starts;
+  A.chain_scans = chain, A.n_chains = (n_scans + chain - 1u) / chain;
+  A.require_flags = o.require_flags, A.max_lost = o.max_lost;
+  A.follow = follow, A.poses = poses;
+  FX_MAP_RUN(fxk_map_follow, "map follow scratch");
+  return FX_OK;
+}
+
 void fx_relocalize_options_default(fx_relocalize_options *o) {
   if (!o) return;
   o->inlier_dist = 0.30f;

@@ -297,6 +297,17 @@ struct FxMapLocalizeArgs {
   int32_t *near;                // the row's landmark, -1: none
   unsigned long long *d2;       // its squared xy distance as bits
 };
+// fx_map_follow (csrc/fx_map_follow.hip): a launch set's arguments.  L is the localise's (L.priors is null: the chain forms its
+// priors; L.out, the row arrays and the scratch as there); the options are fx.h's, checked, chain_scans resolved to >= 1.
+struct FxMapFollowArgs {
+  FxMapLocalizeArgs L;
+  const void *links;            // fx_registration [n_scans - 1], or null when every chain is one scan
+  const void *starts;           // fx_pose [n_chains]
+  uint32_t chain_scans, n_chains;
+  uint32_t require_flags, max_lost;
+  void *follow;                 // fx_follow_scan [n_scans]
+  void *poses;                  // fx_pose [n_scans] or null
+};
 // fx_map_observe (csrc/fx_map_observe.hip): a launch set's arguments.  The first group is the map's own memory, the last the
 // context's scratch, sized by the map's max_landmarks (cap) and by q_max_rows.
 #define FX_MAP_OBSERVE_ST_WORDS 8  // 0 scans_used, 1 proposed, 2 added, 3 duplicates, 4 gated, 5 stale, 6 landmarks_touched, 7 list entries

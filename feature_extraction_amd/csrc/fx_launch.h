@@ -112,6 +112,8 @@ size_t fxk_map_merge_scratch(FxMapMergeArgs *A, uint8_t *base);
 uint32_t fxk_map_merge_wg(void);
 hipError_t fxk_map_localize(hipStream_t s, const FxMapLocalizeArgs &A);
 size_t fxk_map_localize_scratch(FxMapLocalizeArgs *A, uint8_t *base);
+hipError_t fxk_map_follow(hipStream_t s, const FxMapFollowArgs &A);
+size_t fxk_map_follow_scratch(FxMapFollowArgs *A, uint8_t *base);
 hipError_t fxk_map_relocalize(hipStream_t s, const FxMapRelocalizeArgs &A);
 size_t fxk_map_relocalize_scratch(FxMapRelocalizeArgs *A, uint8_t *base);
 hipError_t fxk_map_observe(hipStream_t s, const FxMapObserveArgs &A);

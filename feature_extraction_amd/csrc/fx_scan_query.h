@@ -1,5 +1,5 @@
 // fx_scan_query.h — what the calls that read a keypoint block as a query share (fx_track_landmarks, fx_map_localize,
-// fx_map_relocalize, fx_map_observe, fx_map_expect, fx_map_discover), and the eligibility clauses and workgroup idioms of the
+// fx_map_follow, fx_map_relocalize, fx_map_observe, fx_map_expect, fx_map_discover), and the eligibility clauses and workgroup idioms of the
 // map's calls.  Every decision here is part of the bit-for-bit contract of include/fx.h: each has this one definition, and the
 // kernels cite it.
 #ifndef FX_SCAN_QUERY_H_

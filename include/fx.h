@@ -1774,6 +1774,76 @@ fx_status fx_deskew_keypoint_block(fx_ctx *ctx,
     const fx_registration *motions_device, uint32_t n_scans, const fx_deskew_options *opt /* NULL: defaults */,
     fx_deskew_scan *out_device /* [n_scans] */);
 
+/* ---- Following a stream of scans through the map: each scan's fix is the next scan's prior ----
+ * fx_map_localize takes one prior a scan and localises the scans of a call in parallel, so a scan's fix never helps the next
+ * scan's prior, and dead-reckoned priors (fx_track_landmarks's fold of the links from one start pose) drift out of search_dist.
+ * fx_map_follow runs CHAINS of consecutive scans: the prior of scan b is the pose of scan b - 1 (its fix when FX_LOC_VALID,
+ * otherwise its own prior) composed with the motion into scan b, and scan b is then localised exactly as fx_map_localize would
+ * under that prior.  Many chains run at once, one workgroup each; a chain's only dependence is its own loop.  The call is
+ * enqueued on the context's stream, never waits for it, READS the map only (bit for bit what it was) and allocates nothing in the
+ * steady state: its scratch is fx_map_localize's carve of the shared buffer.
+ * Sizes, non-rows and eligible landmarks: exactly fx_map_localize's, with opt.loc for its options and kp_offset ascending (as
+ * fx_pack_keypoint_block writes it).  Chains: L = opt.chain_scans, or n_scans when that is 0; chain j is the scans
+ * [j L, min((j + 1) L, n_scans)), n_chains = ceil(n_scans / L); start_poses_device holds n_chains fx_pose records and is read on
+ * the device.  links[p], p < n_scans - 1, is the record "scan p + 1 -> scan p" fx_register_matches wrote for pairs_consecutive.
+ * For chain j with first scan f, in scan order:
+ * 1. Scan f: prior = start_poses[j] bit for bit (all 48 bytes), FX_FOLLOW_START, motion = 0xffffffff.
+ * 2. Scan b > f: p* = out[b - 1].pose.  Link b - 1 is usable iff (flags & require_flags) == require_flags and its c, s, tx, ty
+ *    and tz are finite (the de-skew's usable clause without its c > 0: fx_track_landmarks's good link under require_flags).  Usable:
+ *    the motion m is link b - 1, FX_FOLLOW_LINK, motion = b - 1.  Otherwise, if a link p in [f, b - 1) was usable: m is the latest
+ *    such link, FX_FOLLOW_COASTED (constant velocity: the last usable motion applied again), motion = p.  Otherwise
+ *    FX_FOLLOW_HELD.  With a motion the prior is the track's good-link composition p* o m, fp64, no contraction, no fma, no
+ *    renormalisation: c = pc mc - ps ms, s = ps mc + pc ms, tx = (pc mtx - ps mty) + ptx, ty = (ps mtx + pc mty) + pty,
+ *    tz = ptz + mtz; its segment is start_poses[j]'s and its flags are 0.  The prior is p* itself, all 48 bytes, with
+ *    FX_FOLLOW_HELD alone and motion = 0xffffffff, when there is no motion and also when p* is not finite (c, s, tx, ty or tz),
+ *    when any of the five composed values is not finite, or when b >= S (beyond the block's scans).  No NaN is ever produced and
+ *    stored: the bit pattern of a default NaN differs between processors, and the contract is bit for bit.
+ * 3. The fix: out[b] and the map_id_of_row / nearest_of_row words of scan b's rows are what fx_map_localize writes for scan b
+ *    under that prior and opt.loc (the same device functions): b >= S gets FX_LOC_NO_SCAN, a prior that is not finite
+ *    FX_LOC_BAD_PRIOR.
+ * 4. streak = the number of consecutive scans of the chain, up to and including b, whose record lacks FX_LOC_VALID (0 behind a
+ *    VALID scan).  FX_FOLLOW_LOST iff streak >= max_lost.  The chain goes on either way: the caller decides when to call
+ *    fx_map_relocalize.
+ * 5. poses[b] = out[b].pose when poses_device is given: a contiguous fx_pose array for a second round of fx_map_localize, for
+ *    fx_map_loop_correct_poses or for the next batch.
+ * All n_scans records of out, follow and poses are written and nothing behind them; all q_max_rows words of both row arrays are
+ * written, -1 outside the scans' rows.
+ * The start pose is read on the device, so no host read stands between two batches: a batch that overlaps the last by one scan
+ * passes &out_prev[last].pose, a first batch &reloc[b].pose of fx_map_relocalize, a mapping run fx_map_get's last_pose address.
+ * FX_ERR_INVALID_ARG with the reason in fx_last_error(), nothing launched, no output byte touched: fx_map_localize's own list
+ * applied to opt.loc; a NULL start_poses_device, out_device or follow_device; a NULL links_device when some chain has more than one
+ * scan; max_lost == 0; require_flags bits beyond the FX_REG_* flags; reserved != 0; records not 8-byte (words: 4-byte) aligned.
+ * The same bytes from run to run and with any number of contexts in flight.  Limits: a chain is sequential by definition (one
+ * workgroup walks it); the search distance does not widen with the streak, the motion model is constant velocity, and the call
+ * never relocalises by itself.  New in 0.7 (added symbols only). */
+typedef struct fx_follow_options {  /* 48 B */
+  fx_localize_options loc;  /* fx_localize_options_default's, except segment = FX_LOC_ANY_SEGMENT */
+  uint32_t chain_scans;     /* scans a chain; 0 (default): one chain of all n_scans */
+  uint32_t require_flags;   /* FX_REG_* bits a link must carry to be usable; default FX_REG_VALID */
+  uint32_t max_lost;        /* FX_FOLLOW_LOST from this many scans in a row without FX_LOC_VALID; >= 1, default 5 */
+  uint32_t reserved;        /* 0 */
+} fx_follow_options;
+#define FX_FOLLOW_START 0x1u    /* the first scan of its chain: the prior is the start pose */
+#define FX_FOLLOW_LINK 0x2u     /* the prior is the pose before composed with the scan's own link */
+#define FX_FOLLOW_COASTED 0x4u  /* the link was unusable: the chain's last usable motion was applied again */
+#define FX_FOLLOW_HELD 0x8u     /* the prior is the pose of the scan before, bit for bit */
+#define FX_FOLLOW_LOST 0x10u    /* streak >= max_lost */
+#define FX_FOLLOW_NO_MOTION 0xffffffffu
+typedef struct fx_follow_scan {  /* 64 B, one per scan */
+  fx_pose prior;                 /* the prior scan b was localised under */
+  uint32_t flags, motion;        /* motion: index of the link applied, FX_FOLLOW_NO_MOTION: none */
+  uint32_t streak, reserved;     /* scans in a row up to this one without FX_LOC_VALID; 0 */
+} fx_follow_scan;
+void fx_follow_options_default(fx_follow_options *o);
+fx_status fx_map_follow(fx_ctx *ctx, fx_map *map,
+    const void *kp_block_device, uint32_t max_scans, uint32_t max_total_keypoints,
+    const fx_registration *links_device,        /* links[p], p < n_scans - 1: scan p + 1 -> scan p (pairs_consecutive) */
+    const fx_pose *start_poses_device,           /* [n_chains], on the DEVICE */
+    uint32_t n_scans, uint32_t q_max_rows, const fx_follow_options *opt /* NULL: defaults */,
+    fx_localization *out_device /* [n_scans] */, fx_follow_scan *follow_device /* [n_scans] */,
+    fx_pose *poses_device /* [n_scans] or NULL */,
+    int32_t *map_id_of_row_device /* [q_max_rows] */, int32_t *nearest_of_row_device /* [q_max_rows] or NULL */);
+
 /* Rotation matrix of rotateCloud (ref: node.cpp:161-164): R = Ry(pitch)*Rx(roll)
  * through Eigen's AngleAxisf -> Quaternionf -> toRotationMatrix, all float. Host only. */
 void fx_rotation_from_roll_pitch(double roll, double pitch, float R[9]);

@@ -99,6 +99,14 @@ context of two scans: `twice`, fx_process_batch of both scans and the two packs;
 packs and the splice behind the last scan of the block pair before.  Medians; the two routes' blocks are compared at every step.
 (2) 1 + 1023 scans: synthetic block pairs (54 rows a scan, 40 entries a row), the splice of (previous, last, 1) with (current, 0,
 1023) between one pair of HIP events, alternating with one hipMemcpyAsync, device to device, of the bytes the splice defines.
+  timeout -k 10 600 python tools/map_times.py --follow [--sizes 10000,1000000] [--scans 1024] [--warmup 1] [--repeats 5] [--out profiles/map_follow_times.txt]
+
+times fx_map_follow: a drive of --scans scans of 54 keypoints, 0.5 m apart on a gentle arc through the synthetic map, with links 2 %
+long.  Timed with one pair of HIP events each: one chain of all the scans from the true first pose; chains of 16 scans from the true
+poses; a chain of one scan (the grid build, the fill and one turn of the loop: what a call costs before its chains run); and
+fx_map_localize over the same scans under the true poses (the parallel call the follow replaces when no good priors exist).  The
+records of every call are asserted equal across repeats.  Reported per size: the medians with min and max, and the VALID scans.
+No target is set.
 """
 import argparse
 import ctypes as C
@@ -597,6 +605,98 @@ def main_expect(a):
                      f"{v['retired']:>8} {v['dropped_absorbed']:>9} {r['expect_ms']:>8.3f} {r['expect_ms_min_max'][0]:>7.3f} {r['expect_ms_min_max'][1]:>7.3f} "
                      f"{r['localize_ms']:>9.3f} {r['retire_ms']:>8.3f} {r['retire_ms_min_max'][0]:>7.3f} {r['retire_ms_min_max'][1]:>7.3f} "
                      f"{r['compact_ms']:>8.3f} {r['compact_ms_min_max'][0]:>7.3f} {r['compact_ms_min_max'][1]:>7.3f}")
+    s = "\n".join(lines)
+    print(s)
+    print(json.dumps(rows))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(s + "\n")
+
+
+def follow_scene(ctx, n, n_scans, per=54, step=0.5):
+    """What --follow drives through: merge_case(n) through one track and one update into a map of n landmarks, and a drive of
+    n_scans scans, `step` metres apart on a gentle arc from the map's middle, each the `per` poles nearest to the sensor.  Returns
+    (the map, the scans' block, the links between consecutive scans, the true poses): device tensors, the poses also as records."""
+    import torch
+    blk, (S, T), m, inl, reg, M = merge_case(n, np.random.default_rng(n))
+    kp = (torch.from_numpy(blk).cuda(), S, T)
+    md, inl_t = torch.from_numpy(m.view(np.int32).reshape(-1, 8).copy()).cuda(), torch.from_numpy(inl).cuda()
+    reg_t = torch.from_numpy(reg.view(np.float64).reshape(-1, 8).copy()).cuda()
+    mp = ctx.map_create(n, 16)
+    mp.update(kp, ctx.track_landmarks(kp, md, inl_t, reg_t, S, max_landmarks=n), overlap=False, row_ids=False)
+    lm = mp.landmarks(0, mp.header()["n_landmarks"])
+    xy = np.stack([lm["x"], lm["y"]], axis=1)
+    yaw = 0.3 + 0.0005 * np.arange(n_scans)
+    at = np.median(xy, axis=0) + np.concatenate([[[0.0, 0.0]], np.cumsum(step * np.stack([np.cos(yaw[:-1]), np.sin(yaw[:-1])], axis=1), axis=0)])
+    box = xy[(np.abs(xy - (at.min(axis=0) + at.max(axis=0)) / 2) <= np.ptp(at, axis=0) / 2 + 150.0).all(axis=1)]  # (the poles the drive can see)
+    assert len(box) >= per, "the map is too small for the drive"
+    rows, poses, links = np.zeros((n_scans * per, 4), np.float32), np.zeros(n_scans, capi.POSE_DTYPE), np.zeros(max(n_scans - 1, 1), capi.REG_DTYPE)
+    for b in range(n_scans):
+        d = box[np.argpartition(((box - at[b]) ** 2).sum(axis=1), per - 1)[:per]] - at[b]
+        c, s = np.cos(yaw[b]), np.sin(yaw[b])
+        rows[b * per:(b + 1) * per, 0], rows[b * per:(b + 1) * per, 1], rows[b * per:(b + 1) * per, 2] = c * d[:, 0] + s * d[:, 1], -s * d[:, 0] + c * d[:, 1], 1.0
+        poses[b] = (c, s, at[b, 0], at[b, 1], 0.0, 0, 0)
+        if b:  # scan b -> scan b - 1, 2 % long: the odometry's bias
+            c0, s0, dx, dy, dyaw = np.cos(yaw[b - 1]), np.sin(yaw[b - 1]), *(at[b] - at[b - 1]), yaw[b] - yaw[b - 1]
+            links[b - 1] = (np.cos(dyaw), np.sin(dyaw), 1.02 * (c0 * dx + s0 * dy), 1.02 * (-s0 * dx + c0 * dy), 0.0, 0.0, per, per, capi.FX_REG_VALID, 0, 1)
+    T2 = len(rows)
+    k0, n_blk = capi.keypoint_block_layout(n_scans, T2)
+    sb = np.zeros((n_blk, 4), np.float32)
+    u = sb.view(np.uint32).reshape(-1)
+    u[:4] = (n_scans, T2, 0, T2)
+    u[4:4 + n_scans + 1] = np.arange(n_scans + 1) * per
+    sb[k0:k0 + T2] = rows
+    skp = (torch.from_numpy(sb.view(np.uint8).reshape(-1)).cuda(), n_scans, T2)
+    dev = lambda a, w: torch.from_numpy(a.view(np.float64).reshape(-1, w).copy()).cuda()
+    return mp, skp, dev(links, 8), dev(poses, 6), poses
+
+
+def measure_follow(ctx, n, warmup, repeats, n_scans=1024, chain=16):
+    import torch
+    mp, skp, links, poses_t, poses = follow_scene(ctx, n, n_scans)
+    starts = torch.from_numpy(poses[::chain].copy().view(np.float64).reshape(-1, 6).copy()).cuda()
+    stream = torch.cuda.ExternalStream(ctx.stream_ptr())
+    calls = {"one_chain_ms": lambda: mp.follow(skp, links, poses_t, n_scans, nearest=False)[0],
+             "chains_ms": lambda: mp.follow(skp, links, starts, n_scans, nearest=False, chain_scans=chain)[0],
+             "one_scan_ms": lambda: mp.follow(skp, None, poses_t, 1, nearest=False)[0],
+             "localize_ms": lambda: mp.localize(skp, poses_t, n_scans, nearest=False, segment=capi.FX_LOC_ANY_SEGMENT)[0]}
+    torch.cuda.synchronize()
+    t, first, valid = {k: [] for k in calls}, {}, {}
+    for rep in range(warmup + repeats):
+        for k, call in calls.items():
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            e[0].record(stream)
+            recs = call()
+            e[1].record(stream)
+            ctx.synchronize()
+            got = capi.localize_records(recs)
+            assert first.setdefault(k, got.tobytes()) == got.tobytes(), f"{k}: other bytes in repeat {rep}"
+            valid[k] = int((got["flags"] & capi.FX_LOC_VALID != 0).sum())
+            if rep >= warmup:
+                t[k].append(e[0].elapsed_time(e[1]))
+    mp.close()
+    out = {"landmarks": n, "scans": n_scans, "chain_scans": chain, "valid": valid}
+    for k, v in t.items():
+        out[k] = statistics.median(v)
+        out[k + "_min_max"] = [min(v), max(v)]
+    return out
+
+
+def main_follow(a):
+    sizes = [int(x) for x in a.sizes.split(",")]
+    ctx = capi.Context(capi.params("launch"), capi.limits(2, 1024))
+    rows = [measure_follow(ctx, n, a.warmup, a.repeats, a.scans) for n in sizes]
+    ctx.close()
+    lines = [f"fx_map_follow next to fx_map_localize on synthetic maps (tools/map_times.py --follow): 1 pole per 250 m^2, one segment; a drive of",
+             f"{a.scans} scans of 54 keypoints, 0.5 m apart, links 2 % long; one chain of all scans, chains of 16 scans from the true poses, a chain",
+             f"of 1 scan (the grid build, the fill and one turn), and fx_map_localize over the same scans under the true poses; one context,",
+             f"HIP events around each call, median of {a.repeats} after {a.warmup} warm-up; ms (min .. max); valid: scans FX_LOC_VALID",
+             f"{'landmarks':>10} {'one chain':>24} {'valid':>6} {'chains of 16':>24} {'valid':>6} {'one scan':>24} {'localize':>24} {'valid':>6}"]
+    cell = lambda r, k: f"{r[k]:>9.3f} ({r[k + '_min_max'][0]:.3f} .. {r[k + '_min_max'][1]:.3f})".rjust(24)
+    for r in rows:
+        lines.append(f"{r['landmarks']:>10} {cell(r, 'one_chain_ms')} {r['valid']['one_chain_ms']:>6} {cell(r, 'chains_ms')} {r['valid']['chains_ms']:>6} "
+                     f"{cell(r, 'one_scan_ms')} {cell(r, 'localize_ms')} {r['valid']['localize_ms']:>6}")
     s = "\n".join(lines)
     print(s)
     print(json.dumps(rows))
@@ -1132,6 +1232,7 @@ def main():
     ap.add_argument("--find-loop", action="store_true", help="time fx_map_find_loop next to fx_map_relocalize on one-segment synthetic maps instead")
     ap.add_argument("--append", action="store_true", help="time fx_map_append and fx_map_append_host next to fx_map_import_host and a plain copy instead")
     ap.add_argument("--splice", action="store_true", help="time fx_splice_blocks instead: one new scan a call against processing two, and 1 + 1023 scans against a plain copy")
+    ap.add_argument("--follow", action="store_true", help="time fx_map_follow (one chain, chains of 16, one scan) next to fx_map_localize over a drive of --scans scans (pass --sizes 10000,1000000)")
     ap.add_argument("--steps", type=int, default=200, help="--splice: scans of the one-scan-a-call comparison")
     ap.add_argument("--sizes", default="1000,100000,1000000")
     ap.add_argument("--scans", type=int, default=1024)
@@ -1165,6 +1266,8 @@ def main():
         return main_append(a)
     if a.splice:
         return main_splice(a)
+    if a.follow:
+        return main_follow(a)
     N = 28800
     ctx = capi.Context(capi.params("launch"), capi.limits(a.batch, N, sparse=True))
     scenes = np.stack([capi.synth_scan(capi.synth_cfg(1000 + b)) for b in range(a.scans)])
